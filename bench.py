@@ -11,8 +11,11 @@ communication is the gather of token ids to rank 0 after each step).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP events on the launch stream) and `cpu_baseline` (oracle timed on this host's cores, N = 1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints; --full adds what the headline figure does not need: the same steps one batch after the other
+(`value_one_batch_in_flight`, per-stage times), `roofline` (dominant kernel, HIP events on the launch stream),
+`latency` (small-batch figures) and `cpu_baseline` (oracle timed on this host's cores, N = 1 only).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -66,7 +69,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-tokens", type=int, default=0, help="decode tokens in the CPU sample (0 = same as --tokens)")
     ap.add_argument("--cpu-windows", type=int, default=2, help="30 s windows in the CPU sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed legs: the same steps one batch after the other, the roofline leg, "
+                         "the small-batch latency figures and the CPU baseline (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (token ids, float64; sum of log-probabilities, float32) "
+                         "as DIR/<name>.npy; with several ranks each rank writes its own windows as DIR/<name>_rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from openhush_amd import engine as E, shard, synth
@@ -131,7 +142,8 @@ def main():
     st = states[0]
 
     # synthetic 16 kHz audio: window ids are global so that every rank transcribes different audio
-    pcm_host = np.stack([synth.synth_audio(rank * B + b) for b in range(B)])
+    audio = {}
+    pcm_host = synth_windows(synth, [rank * B + b for b in range(B)], audio)
     pcm = torch.from_numpy(pcm_host).cuda()
     n_samples = [synth.CHUNK_SAMPLES] * Bs
     p = ctx.default_params()
@@ -144,9 +156,9 @@ def main():
         s_ = states[i]
         s_.mel_device(pcm.data_ptr() + i * Bs * pcm.shape[1] * 4, pcm.shape[1], n_samples, E.OHW_MEL_ZERO_TAIL)
         s_.encode(Bs)
-        out[i], _ = s_.greedy(Bs, p)
+        out[i] = s_.greedy(Bs, p)       # (token lists, sum_logprob)
 
-    def step():
+    def step():                         # -> (token lists, sum_logprob) of the step's windows
         out = [None] * S
         if S == 1:
             run_state(0, out)
@@ -156,10 +168,10 @@ def main():
                 t.start()
             for t in th:
                 t.join()
-        toks = [t for o in out for t in o]
+        toks = [t for o in out for t in o[0]]
         if use_dist:    # the path's only communication: token ids of every rank's windows to rank 0 (KBs, RCCL)
             shard.gather_tokens(shard.pack_tokens(toks, args.tokens), dist, world, rank, dev, force=True)
-        return toks
+        return toks, np.concatenate([o[1] for o in out])
 
     def fence():
         torch.cuda.synchronize()
@@ -167,11 +179,11 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def run_steps(n):
-        toks = None
+    def run_steps(n):                   # -> step() of the last step
+        res = None
         for _ in range(n):
-            toks = step()
-        return toks
+            res = step()
+        return res
 
     pipe = None
     G = max(0, args.phases)
@@ -188,7 +200,7 @@ def main():
             # every window in flight is its own synthetic recording: lane j's decode batch = windows [j * MG * B, (j + 1) * MG * B)
             # of this rank's G * MG * B (window ids are global: rank * G * MG * B + ...)
             n_fl = G * MG * B
-            pcm_all = torch.from_numpy(np.stack([synth.synth_audio(rank * n_fl + w) for w in range(n_fl)])).cuda() if n_fl > B else pcm
+            pcm_all = torch.from_numpy(synth_windows(synth, [rank * n_fl + w for w in range(n_fl)], audio)).cuda() if n_fl > B else pcm
             pipe = {"schedule": "lanes", "decoders_side_by_side": G, "batches_per_decode": MG, "decoder_cus": n_cu // G,
                     "batches_in_flight": G * MG}
         except E.WhisperError as ex:
@@ -197,6 +209,7 @@ def main():
     if pipe and G > 1:
         def run_steps(n):           # noqa: F811
             out = [None] * n
+            out_lp = [None] * n
             err = []
             for g0 in range(0, n, G * MG):
                 grp = list(range(g0, min(n, g0 + G * MG)))
@@ -227,10 +240,11 @@ def main():
                 def lane(j, steps_j):
                     try:
                         tl0 = time.perf_counter()
-                        toks_j, _ = pst[j].greedy(len(steps_j) * B, p)
+                        toks_j, lp_j = pst[j].greedy(len(steps_j) * B, p)
                         lane_ms[j] = 1e3 * (time.perf_counter() - tl0)
                         for k, i in enumerate(steps_j):
                             out[i] = toks_j[k * B:(k + 1) * B]
+                            out_lp[i] = lp_j[k * B:(k + 1) * B]
                     except Exception as ex:      # noqa: BLE001
                         err.append(ex)
                 if len(lanes) == 1:
@@ -254,7 +268,7 @@ def main():
             if use_dist:
                 for toks_i in out:
                     shard.gather_tokens(shard.pack_tokens(toks_i, args.tokens), dist, world, rank, dev, force=True)
-            return out[-1] if n > 0 else None
+            return (out[-1], out_lp[-1]) if n > 0 else None
     elif args.pipeline > 0 and S == 1:
         # Batches in flight on disjoint CU sets (include/ohw.h, ohw_stream_create): while batch i decodes (HBM- and
         # latency-bound, MFMA idle) batch i+1 runs mel + encoder + cross-K/V (MFMA-bound) - round 1's schedule.  A step is still one whole
@@ -273,6 +287,8 @@ def main():
             print(f"[bench] two-batch pipeline unavailable ({ex}); running one batch after the other", file=sys.stderr, flush=True)
             pipe = None
 
+    audio.clear()                   # the host copies of the windows are stacked: the per-window arrays are no longer needed
+
     if pipe and G > 1:
         pass
     elif pipe:
@@ -282,7 +298,7 @@ def main():
             s_.encode(B)
 
         def run_steps(n):           # noqa: F811
-            toks = None
+            res = None
             if n > 0:
                 enqueue_front(pst[0], full)
                 last_front = full
@@ -295,10 +311,10 @@ def main():
                     enqueue_front(nxt, es)       # batch i+1's front end runs beside batch i's decode
                     last_front = es
                 cur.set_stream(dstream.ptr)
-                toks, _ = cur.greedy(B, p)       # host-blocking greedy loop (hipGraph replays on the decoder's stream)
+                res = cur.greedy(B, p)           # host-blocking greedy loop (hipGraph replays on the decoder's stream)
                 if use_dist:
-                    shard.gather_tokens(shard.pack_tokens(toks, args.tokens), dist, world, rank, dev, force=True)
-            return toks
+                    shard.gather_tokens(shard.pack_tokens(res[0], args.tokens), dist, world, rank, dev, force=True)
+            return res
 
     if pipe and G > 1:
         # set-up, not a step: the decode graphs are captured per (state, decode-batch size) on first use and a capture holds
@@ -306,65 +322,14 @@ def main():
         # the warm-up (K = 20 on 4 lanes x 3: a group of 12 and one of 8)
         for shape in sorted({min(G * MG, args.steps - g0) for g0 in range(0, args.steps, G * MG)}, reverse=True):
             run_steps(shape)
-    toks = run_steps(args.warmup)
+    run_steps(args.warmup)
 
     # ---- timed region: exactly K steps, no profiling hooks active (the decode loop replays its hipGraph)
     fence()
     t0 = time.perf_counter()
-    toks = run_steps(args.steps)
+    toks, lps = run_steps(args.steps)
     fence()
     dt = time.perf_counter() - t0
-    if pipe:
-        # the same K steps one batch after the other (untimed for `value`; reported beside it, and the per-stage times
-        # below come from this leg, where the stages do not overlap)
-        st.set_stream(None)
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        pipe["unpipelined_ms_per_step"] = round(1e3 * (time.perf_counter() - t1) / args.steps, 2)
-        pipe["unpipelined_value"] = round(30.0 * B * world * args.steps / (time.perf_counter() - t1), 1)   # rank 0's clock
-    tm = st.timings()
-
-    # ---- roofline leg (untimed, same workload): HIP events recorded on the launch stream around every
-    # launch of one kernel class.  Events cannot be recorded inside a replayed graph, so these passes
-    # launch the same kernels eagerly; only per-kernel durations are taken from them, never `value`.
-    prof_class = args.profile_class
-    class_totals, class_work = {}, {}
-    S_saved, S = S, 1          # the roofline leg runs sub-batch 0 alone, eagerly, on its own stream
-    def step():                # noqa: F811
-        out = [None]
-        run_state(0, out)
-        return out[0]
-    if prof_class == 0:
-        for cls in sorted(PROF_NAMES):
-            st.profile_begin(cls)
-            step()
-            n, ms, w = st.profile_end()
-            class_totals[cls] = ms
-            class_work[cls] = w
-        prof_class = max(class_totals, key=class_totals.get)
-    st.profile_begin(prof_class)
-    for _ in range(args.steps):
-        step()
-    launches, k_ms, work = st.profile_end()
-    # the MFMA class once more at the shape the TIMED schedule launches it: one front-end pass over a lane's MG x B windows (the
-    # 32-window figures above pay 8 % for a last round of 256-row tiles that is two thirds empty)
-    lane_pass = None
-    if pipe and G > 1 and MG > 1:
-        s_ = pst[0]
-        s_.set_stream(full.ptr)
-        lane_pass = {"windows": MG * B}
-        for cls, key in ((1, "gemm"), (2, "attention")):
-            s_.profile_begin(cls)
-            s_.mel_device(pcm_all.data_ptr(), pcm_all.shape[1], n_samples * MG, E.OHW_MEL_ZERO_TAIL)
-            s_.encode(MG * B)
-            _, ms_c, w_c = s_.profile_end()
-            lane_pass[key + "_ms_per_step"] = round(ms_c / MG, 3)
-            lane_pass[key + "_tflops"] = round(w_c / (ms_c * 1e-3) / 1e12, 1) if ms_c > 0 else 0.0
-        lane_pass["gemm_frac"] = round(lane_pass["gemm_tflops"] / PEAK_MFMA_TFLOPS, 4)
-
     dt_t = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if use_dist:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
@@ -373,8 +338,68 @@ def main():
     value = audio_s / dt_max
 
     assert all(len(t) == args.tokens for t in toks), "every window must decode exactly --tokens tokens"
+    if args.dump_outputs:
+        # what a caller of the timed path receives for the last step's windows (this rank's): greedy's token ids and sum_logprob
+        dump_outputs(args.dump_outputs, {"tokens": np.asarray(toks, dtype=np.float64), "sum_logprob": np.asarray(lps, dtype=np.float32)},
+                     f"_rank{rank}" if world > 1 else "")
 
-    if rank == 0:
+    S_saved = S
+    tm = st.timings() if not pipe else None      # without a schedule the timed steps ran through `st` itself
+    roof = mfma = latency = cpu = None
+    if args.full:
+        if pipe:
+            # the same K steps one batch after the other (untimed for `value`; reported beside it, and the per-stage times
+            # below come from this leg, where the stages do not overlap)
+            st.set_stream(None)
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            fence()
+            pipe["unpipelined_ms_per_step"] = round(1e3 * (time.perf_counter() - t1) / args.steps, 2)
+            pipe["unpipelined_value"] = round(30.0 * B * world * args.steps / (time.perf_counter() - t1), 1)   # rank 0's clock
+        tm = st.timings()
+
+        # ---- roofline leg (untimed, same workload): HIP events recorded on the launch stream around every
+        # launch of one kernel class.  Events cannot be recorded inside a replayed graph, so these passes
+        # launch the same kernels eagerly; only per-kernel durations are taken from them, never `value`.
+        prof_class = args.profile_class
+        class_totals, class_work = {}, {}
+        S = 1                      # the roofline leg runs sub-batch 0 alone, eagerly, on its own stream
+
+        def step():                # noqa: F811
+            out = [None]
+            run_state(0, out)
+            return out[0]
+        if prof_class == 0:
+            for cls in sorted(PROF_NAMES):
+                st.profile_begin(cls)
+                step()
+                n, ms, w = st.profile_end()
+                class_totals[cls] = ms
+                class_work[cls] = w
+            prof_class = max(class_totals, key=class_totals.get)
+        st.profile_begin(prof_class)
+        for _ in range(args.steps):
+            step()
+        launches, k_ms, work = st.profile_end()
+        # the MFMA class once more at the shape the TIMED schedule launches it: one front-end pass over a lane's MG x B windows (the
+        # 32-window figures above pay 8 % for a last round of 256-row tiles that is two thirds empty)
+        lane_pass = None
+        if pipe and G > 1 and MG > 1:
+            s_ = pst[0]
+            s_.set_stream(full.ptr)
+            lane_pass = {"windows": MG * B}
+            for cls, key in ((1, "gemm"), (2, "attention")):
+                s_.profile_begin(cls)
+                s_.mel_device(pcm_all.data_ptr(), pcm_all.shape[1], n_samples * MG, E.OHW_MEL_ZERO_TAIL)
+                s_.encode(MG * B)
+                _, ms_c, w_c = s_.profile_end()
+                lane_pass[key + "_ms_per_step"] = round(ms_c / MG, 3)
+                lane_pass[key + "_tflops"] = round(w_c / (ms_c * 1e-3) / 1e12, 1) if ms_c > 0 else 0.0
+            lane_pass["gemm_frac"] = round(lane_pass["gemm_tflops"] / PEAK_MFMA_TFLOPS, 4)
+
+    if rank == 0 and args.full:
         if prof_class in (1, 2):
             achieved = work / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
             roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -393,7 +418,6 @@ def main():
             roof["whole_path"] = {"bound_ms_per_step": round(mfma_ms + hbm_ms, 2), "mfma_bound_ms": round(mfma_ms, 2), "hbm_bound_ms": round(hbm_ms, 2),
                                   "measured_ms_per_step": round(ms_step, 2), "frac": round((mfma_ms + hbm_ms) / ms_step, 4)}
         # the path's MFMA-bound class beside the dominant (HBM-bound) kernel: BASELINE.json's north_star asks for both
-        mfma = None
         if class_totals.get(1, 0) > 0 and class_work.get(1, 0) > 0:
             tf = class_work[1] / (class_totals[1] * 1e-3) / 1e12
             mfma = {"kernel": PROF_NAMES[1], "bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -403,22 +427,22 @@ def main():
         roof.update({"kernel": PROF_NAMES[prof_class], "launches": launches, "avg_launch_us": round(1e3 * k_ms / max(1, launches), 2),
                      "kernel_ms_per_step": round(k_ms / args.steps, 3),
                      "class_ms_per_step": {PROF_NAMES[k]: round(v, 3) for k, v in class_totals.items()}})
-        latency = None
         if world == 1 and not args.no_latency:
             latency = latency_figures(E, synth, ctx, hp, dtype, args.tokens)
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(hp, pcm_host[:max(1, min(args.cpu_windows, B))], args.cpu_tokens or args.tokens)
+    if rank == 0:
         print(f"[bench] rank 0 ok: {value:.1f} audio-s/s over {world} rank(s)", file=sys.stderr, flush=True)
         line = {
             "metric": baseline_metric(), "value": round(value, 1), "unit": "audio-sec/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt_max / args.steps, 2),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            # with a schedule, the one-batch-in-flight figure is the --full leg's (null in a plain run)
             "value_one_batch_in_flight": pipe.get("unpipelined_value") if pipe else round(value, 1),
             "config": {"workload": workload_string(args, B, G if pipe and G > 1 else 0, MG, pipe), "model_dims": hp.as_list(),
                        "concurrent_sub_batches": S_saved, "pipeline": pipe,
-                       "stage_ms_last_step": {"mel": round(tm.mel_ms, 2), "encode": round(tm.encode_ms, 2), "decode": round(tm.decode_ms, 2)},
-                       "decode_steps": tm.decode_steps},
+                       "stage_ms_last_step": {"mel": round(tm.mel_ms, 2), "encode": round(tm.encode_ms, 2), "decode": round(tm.decode_ms, 2)} if tm else None,
+                       "decode_steps": tm.decode_steps if tm else None},
             "roofline": roof, "roofline_mfma": mfma, "latency": latency, "cpu_baseline": cpu,
         }
         sys.stdout.flush()
@@ -439,6 +463,24 @@ def main():
     ctx.close()
 
 
+def synth_windows(synth, ids, cache):
+    """[len(ids), 480000] float32: synth.synth_audio(i) for every id, bit for bit, on a few host threads (numpy releases the GIL;
+    one window costs tens of ms and the LANES schedule holds 384 in flight); ids already in `cache` are not generated again"""
+    from concurrent.futures import ThreadPoolExecutor
+    todo = [i for i in dict.fromkeys(ids) if i not in cache]
+    with ThreadPoolExecutor(max_workers=usable_cores()) as ex:
+        cache.update(zip(todo, ex.map(synth.synth_audio, todo)))
+    return np.stack([cache[i] for i in ids])
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: one DIR/<name><suffix>.npy per array (float32 / float64 only)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def workload_string(args, B, lanes, merge, pipe):
     """what the timed region ran, in one string (the driver keeps config.workload and drops the nested objects)"""
     base = (f"{args.model} dims, steps of batch={B} x 30 s windows per GPU, greedy, {args.tokens} tokens/window (EOT suppressed), "
@@ -446,8 +488,8 @@ def workload_string(args, B, lanes, merge, pipe):
     if lanes:
         strict = pipe.get("unpipelined_value")
         return (base + f"; schedule LANES {lanes}x{merge}: {lanes * merge} steps ({lanes * merge * B} windows) in flight per GPU - per lane ONE front-end pass "
-                f"and ONE decode batch of {merge * B} rows, {lanes} decodes side by side on {pipe['decoder_cus']} CUs each; the same steps strictly one "
-                f"batch of {B} in flight: {strict} audio-s/s (value_one_batch_in_flight)")
+                f"and ONE decode batch of {merge * B} rows, {lanes} decodes side by side on {pipe['decoder_cus']} CUs each"
+                + (f"; the same steps strictly one batch of {B} in flight: {strict} audio-s/s (value_one_batch_in_flight)" if strict is not None else ""))
     if pipe:
         return base + f"; schedule PIPELINE: 2 batches in flight (front end on {pipe['encoder_cus']} CUs beside the decode on {pipe['decoder_cus']})"
     return base + "; one batch after the other"
@@ -572,6 +614,10 @@ def pool_bench(args, torch, E, synth):
         lens += pool.last_window_tokens()
     dt = time.perf_counter() - t0
     assert len(lens) == n_dev * B * args.steps and all(n == args.tokens for n in lens), "every window must decode exactly --tokens tokens"
+    if args.dump_outputs:
+        # the token ids of the last step's n_dev x B windows: the tail of the last call's windows, each exactly --tokens long
+        last = np.asarray(pool.last_tokens(), dtype=np.float64).reshape(-1, args.tokens)[-n_dev * B:]
+        dump_outputs(args.dump_outputs, {"tokens": last})
     value = 30.0 * len(lens) / dt
     line = {
         "metric": baseline_metric(), "value": round(value, 1), "unit": "audio-sec/sec", "n_gpus": n_dev, "steps": args.steps, "warmup": args.warmup,
