@@ -321,6 +321,12 @@ ohw_rng* ohw_rng_new(uint32_t seed);
 void ohw_rng_free(ohw_rng* rng);
 int32_t ohw_sample_host(const ohw_ctx* ctx, const ohw_sample_params* p, float* logits, const int32_t* cur, int n_cur,
                         float temperature, ohw_rng* rng, float* logprob_out, float* no_speech_prob_out);
+/* the draws of a generator, for a sampler that is not on the host: one draw of std::discrete_distribution is one
+ * std::generate_canonical<double, 53> (two engine outputs), compared against the normalised partial sums.
+ * ohw_rng_uniforms writes the next n canonical doubles, drawn from a COPY of the generator (rng does not advance);
+ * ohw_rng_discard_draws advances rng by n draws, where n calls of ohw_sample_host at T > 0 would leave it.             */
+int ohw_rng_uniforms(const ohw_rng* rng, int n, double* out);
+int ohw_rng_discard_draws(ohw_rng* rng, int n);
 
 /* device-resident greedy loop for the windows of the last ohw_encode: prompt, KV-cached steps,   */
 /* logits filter and arg-max all stay on the GPU; only token ids come back.                        */
@@ -341,6 +347,14 @@ typedef struct {
   float* no_speech_prob;  /* [batch] */
 } ohw_greedy_result;
 int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* p, int batch, int max_tokens, const ohw_greedy_result* out);
+/* one pass of the temperature fallback on the device, shaped like ohw_greedy_ex on the resident cross K/V: the prompt, then
+ * replayed {decoder step, temperature sampler} steps.  Per row the sampler is ohw_sample_host at `temperature` (> 0): the
+ * state's logit bias added, divided by the temperature, the same filter, then the first index whose partial sum of
+ * probabilities reaches u * their total, u = uniforms[b][step] (ohw_rng_uniforms).  Rows with active[b] == 0 are not
+ * decoded (their results are 0).  A row stops at end-of-text or a length limit only (at most max_tokens draws): the
+ * caller cuts the pass at whisper.cpp's other loop exits and discards the draws it kept (ohw_rng_discard_draws).    */
+int ohw_sample_pass(ohw_state* st, const ohw_sample_params* p, int batch, int max_tokens, float temperature, const int32_t* active,
+                    const double* uniforms /* [batch][max_tokens] */, const ohw_greedy_result* out);
 
 /* beam search for the windows of the last ohw_encode (BASELINE.json config #5: beam = 5, hipGraph-captured decoder step).
  * The reference never uses one (Greedy{best_of:1}, src/engine/whisper.rs:243); the rule is the published Whisper
@@ -418,13 +432,18 @@ int ohw_engine_last_text(ohw_engine* e, const char** text, size_t* len);
  *     with no timestamp while audio is left;
  *   - acceptance: not failed, token-frequency entropy of the last 32 tokens >= entropy_thold, and not
  *     (avg_logprob < logprob_thold while no_speech_prob < no_speech_thold); a pass that is not accepted is decoded again
- *     at temperature += temperature_inc (up to 1.0), sampled on the host with std::mt19937(0) + std::discrete_distribution
- *     on the window's resident cross K/V (ohw_decode_active); the last temperature is accepted whatever it gives;
+ *     at temperature += temperature_inc (up to 1.0), drawn from std::mt19937(0) through std::discrete_distribution on
+ *     the window's resident cross K/V: by default the host samples every step (ohw_decode_active + ohw_sample_host), with
+ *     ohw_engine_set_fallback_device(e, 1) the device does (ohw_sample_pass, the host's generator pre-drawn); the last
+ *     temperature is accepted whatever it gives;
  *   - no speech: a window with no_speech_prob > no_speech_thold and avg_logprob < logprob_thold yields no text.
  * temperature_inc <= 0 keeps every window at T = 0 (what bench.py times: SURVEY.md 8d). */
 typedef struct { float temperature_inc, entropy_thold, logprob_thold, no_speech_thold; } ohw_decode_policy;
 void ohw_default_decode_policy(ohw_decode_policy* q);   /* 0.2, 2.4, -1.0, 0.6 */
 int ohw_engine_set_decode_policy(ohw_engine* e, const ohw_decode_policy* q);
+/* on != 0: the temperature fallback samples on the device (ohw_sample_pass, one call per rung) instead of the host; the
+ * same passes, generators and decisions.  Default 0. */
+int ohw_engine_set_fallback_device(ohw_engine* e, int on);
 /* per window of the last transcribe, for the pass that was kept */
 typedef struct {
   int32_t n_tokens;        /* tokens that reached the text / ohw_engine_last_tokens (0 for a no-speech window) */
@@ -503,6 +522,7 @@ int ohw_pool_last_text(ohw_pool* p, const char** text, size_t* len);
 int ohw_pool_last_tokens(ohw_pool* p, const int32_t** tokens, int* n);
 int ohw_pool_last_quality(ohw_pool* p, const ohw_window_quality** q, int* n_windows);
 int ohw_pool_set_decode_policy(ohw_pool* p, const ohw_decode_policy* q);
+int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw_engine_set_fallback_device on every engine */
 /* the window mode of EVERY engine of the pool (ohw_engine_set_window_mode): ohw_pool_transcribe rejects a pool whose engines
  * disagree.  All three modes give the single engine's tokens: each device is handed the whole recording and cuts its own
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
@@ -538,6 +558,10 @@ int ohw_dbg_attention(int dtype, const void* qkv, void* out, int batch, int T, i
  * logprobs_out [batch] / no_speech_out [batch] may be NULL (no-speech is defined for rows with n_hist == 0). */
 int ohw_dbg_sample(ohw_state* st, const ohw_sample_params* p, const float* logits, const int32_t* history, int hist_stride,
                    const int32_t* n_hist, int batch, int32_t* tokens_out, float* logprobs_out, float* no_speech_out);
+/* the same for the temperature sampler of ohw_sample_pass: temperature > 0, uniforms [batch] the draw of each row's step */
+int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* p, const float* logits, const int32_t* history, int hist_stride,
+                     const int32_t* n_hist, int batch, float temperature, const double* uniforms, int32_t* tokens_out,
+                     float* logprobs_out, float* no_speech_out);
 /* counters of a state's graph caches: "step_captures" / "beam_captures" (graphs / graph pairs captured so far),
  * "step_graphs" / "beam_graphs" (entries held now), "persist_launches" (persistent decoder steps launched or captured);
  * OHW_E_INVALID_ARG for another name.  A second ohw_greedy /

@@ -1296,6 +1296,257 @@ void launch_sampler(const SamplerParams& p, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// the same filter at a temperature T > 0, then one draw: whisper_sample_token(best = false) as ohw_sample_host restates it
+// (host_engine.cpp).  v = (logit + bias) / T; the no-speech probability (first step) from the unfiltered scaled row; the
+// sp_allowed rules and the timestamp-mass rule on the scaled row; p_i = expf(v_i - lse); the pick is the first index whose
+// partial sum of p reaches u * sum(p), u = the row's pre-drawn canonical double for this step (std::discrete_distribution's
+// lower_bound over the normalised partial sums, which is the same comparison up to one division's rounding).
+// T and the draws come from device memory, so one captured step graph serves every rung of the ladder.
+//   phase 1: SAMPLER_SPLIT slices publish their log-sum-exp partials, as sampler_kernel's; the last arriver fixes lse and the
+//            timestamp decision
+//   phase 2: that workgroup alone walks the row: each wave owns one eighth of it in index order and sums p in fp64 over
+//            tiles of 64 (inclusive lane scan, the tile's total is lane 63's value); the wave whose range holds the target
+//            walks its tiles again with the same arithmetic, so the running sum at every index is the one that was summed,
+//            and the crossing is found inside that range.  fl(u * S) <= S for u < 1: the target never lies past the total.
+// ------------------------------------------------------------------------------------------------
+constexpr int SPT_WAVES = SP_THREADS / 64;
+
+__device__ __forceinline__ double wave_incl_scan(double x, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(SP_THREADS) void sampler_t_kernel(SamplerParams p, const float* __restrict__ temp, const double* __restrict__ uniforms) {
+  __shared__ SampAcc sh[SPT_WAVES];
+  __shared__ int sh_ts[SPT_WAVES];
+  __shared__ double sh_wsum[SPT_WAVES];
+  __shared__ float sh_lse;
+  __shared__ int sh_last, sh_force_ts, sh_pick;
+  const int part = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (p.done[b]) return;
+  const float T = temp[0];
+  const int np_now = p.n_past[b] + p.advance;
+  const float* lg = p.logits + (int64_t)b * p.ld;
+  int32_t* toks = p.tokens + (int64_t)b * p.max_tokens;
+  const int n_cur = p.n_cur[b];
+  SampState st;
+  st.is_initial = n_cur == 0;
+  st.last_ts = n_cur > 0 && toks[n_cur - 1] >= p.ts_begin;
+  st.penult_ts = n_cur < 2 || toks[n_cur - 2] >= p.ts_begin;
+  st.last_seen = block_last_timestamp<SP_THREADS>(toks, n_cur, p.ts_begin, tid, sh_ts);
+  st.suppress_eot = p.force_len > 0 && n_cur < p.force_len;
+  const int per = (p.n_vocab + SAMPLER_SPLIT - 1) / SAMPLER_SPLIT;
+  const int lo = part * per, V = lo + per < p.n_vocab ? lo + per : p.n_vocab;
+  const bool want_raw = st.is_initial && p.nosp_prob != nullptr;
+  SampAcc a;
+  a.m = -INFINITY; a.s_all = 0.f; a.s_ts = 0.f; a.tv = -INFINITY; a.ti = 0x7fffffff; a.zv = -INFINITY; a.zi = 0x7fffffff;
+  a.rm = -INFINITY; a.rs = 0.f;
+  constexpr int SP_BATCH = 13;
+  for (int i0 = lo + tid; i0 < V; i0 += SP_THREADS * SP_BATCH) {
+    float vv[SP_BATCH];
+#pragma unroll
+    for (int u = 0; u < SP_BATCH; ++u) {
+      const int i = i0 + u * SP_THREADS;
+      vv[u] = lg[i < V ? i : V - 1];
+    }
+    if (p.bias) {
+      float bb[SP_BATCH];
+#pragma unroll
+      for (int u = 0; u < SP_BATCH; ++u) {
+        const int i = i0 + u * SP_THREADS;
+        bb[u] = p.bias[i < V ? i : V - 1];
+      }
+#pragma unroll
+      for (int u = 0; u < SP_BATCH; ++u) vv[u] += bb[u];
+    }
+#pragma unroll
+    for (int u = 0; u < SP_BATCH; ++u) vv[u] = vv[u] / T;       // a true division, as the host's logits[i] /= temperature
+    if (want_raw) {
+#pragma unroll
+      for (int u = 0; u < SP_BATCH; ++u) {
+        const int i = i0 + u * SP_THREADS;
+        const float v = vv[u];
+        if (i >= V) continue;
+        if (v > a.rm) { a.rs *= a.rm == -INFINITY ? 0.f : expf(a.rm - v); a.rm = v; }
+        a.rs += expf(v - a.rm);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < SP_BATCH; ++u) {
+      const int i = i0 + u * SP_THREADS;
+      const float v = vv[u];
+      if (i >= V || !sp_allowed(p, st, i)) continue;
+      if (v > a.m) {
+        const float f = a.m == -INFINITY ? 0.f : expf(a.m - v);
+        a.s_all *= f; a.s_ts *= f; a.m = v;
+      }
+      const float e = expf(v - a.m);
+      a.s_all += e;
+      if (i >= p.ts_begin) { a.s_ts += e; if (v > a.zv) { a.zv = v; a.zi = i; } }
+      else if (v > a.tv) { a.tv = v; a.ti = i; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    SampAcc bb;
+    bb.m = __shfl_xor(a.m, o, 64); bb.s_all = __shfl_xor(a.s_all, o, 64); bb.s_ts = __shfl_xor(a.s_ts, o, 64);
+    bb.tv = __shfl_xor(a.tv, o, 64); bb.ti = __shfl_xor(a.ti, o, 64); bb.zv = __shfl_xor(a.zv, o, 64); bb.zi = __shfl_xor(a.zi, o, 64);
+    bb.rm = __shfl_xor(a.rm, o, 64); bb.rs = __shfl_xor(a.rs, o, 64);
+    samp_merge(a, bb);
+  }
+  if (lane == 0) sh[wid] = a;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < SPT_WAVES; ++w) samp_merge(a, sh[w]);
+    constexpr int NW = 9;
+    unsigned* slot = (unsigned*)p.partials + ((int64_t)b * SAMPLER_SPLIT + part) * SAMPLER_PART_WORDS;
+    const unsigned words[NW] = {__float_as_uint(a.m), __float_as_uint(a.s_all), __float_as_uint(a.s_ts), __float_as_uint(a.tv), (unsigned)a.ti,
+                                __float_as_uint(a.zv), (unsigned)a.zi, __float_as_uint(a.rm), __float_as_uint(a.rs)};
+#pragma unroll
+    for (int k = 0; k < NW; ++k) __hip_atomic_store(slot + k, words[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned ticket = __hip_atomic_fetch_add(p.tickets + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sh_last = ticket == SAMPLER_SPLIT - 1;
+    if (ticket == SAMPLER_SPLIT - 1) {
+      __hip_atomic_store(p.tickets + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned* all = (const unsigned*)p.partials + (int64_t)b * SAMPLER_SPLIT * SAMPLER_PART_WORDS;
+      unsigned w8[SAMPLER_SPLIT][NW];
+#pragma unroll
+      for (int q = 0; q < SAMPLER_SPLIT; ++q)
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w8[q][k] = __hip_atomic_load(all + q * SAMPLER_PART_WORDS + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+      for (int q = 0; q < SAMPLER_SPLIT; ++q) {
+        SampAcc c;
+        c.m = __uint_as_float(w8[q][0]); c.s_all = __uint_as_float(w8[q][1]); c.s_ts = __uint_as_float(w8[q][2]);
+        c.tv = __uint_as_float(w8[q][3]); c.ti = (int)w8[q][4]; c.zv = __uint_as_float(w8[q][5]); c.zi = (int)w8[q][6];
+        c.rm = __uint_as_float(w8[q][7]); c.rs = __uint_as_float(w8[q][8]);
+        if (q == 0) a = c; else samp_merge(a, c);
+      }
+      if (want_raw) {
+        const float v = (lg[p.nosp] + (p.bias ? p.bias[p.nosp] : 0.f)) / T;
+        p.nosp_prob[b] = expf(v - (a.rm + logf(a.rs)));
+      }
+      const float lse = a.m + logf(a.s_all);
+      bool force_ts = false;
+      if (!p.no_timestamps && a.s_ts > 0.f) {
+        const float ts_lp = a.m + logf(a.s_ts) - lse;
+        const float text_lp = a.tv - lse;
+        force_ts = ts_lp > text_lp;
+      }
+      sh_lse = lse;
+      sh_force_ts = force_ts;
+    }
+  }
+  __syncthreads();
+  if (!sh_last) return;
+  // ---- phase 2: the last arriver draws ----
+  const float lse = sh_lse;
+  const bool force_ts = sh_force_ts != 0;
+  const int NV = p.n_vocab;
+  auto scaled = [&](int i) { return (lg[i] + (p.bias ? p.bias[i] : 0.f)) / T; };
+  auto allowed = [&](int i) { return sp_allowed(p, st, i) && !(force_ts && i < p.ts_begin); };
+  // a wave's range: whole tiles of 64, walked in batches of SPT_BATCH tiles whose loads are all in flight before the first is used
+  constexpr int SPT_BATCH = 16;
+  const int wper = ((NV + SPT_WAVES - 1) / SPT_WAVES + 63) / 64 * 64;
+  const int wlo = wid * wper, whi = wlo + wper < NV ? wlo + wper : NV;
+  auto load_batch = [&](int t0, double* pr) {
+    float vv[SPT_BATCH];
+#pragma unroll
+    for (int k = 0; k < SPT_BATCH; ++k) {
+      const int i = t0 + k * 64 + lane;
+      vv[k] = lg[i < NV ? i : NV - 1];
+    }
+    if (p.bias) {
+      float bb[SPT_BATCH];
+#pragma unroll
+      for (int k = 0; k < SPT_BATCH; ++k) {
+        const int i = t0 + k * 64 + lane;
+        bb[k] = p.bias[i < NV ? i : NV - 1];
+      }
+#pragma unroll
+      for (int k = 0; k < SPT_BATCH; ++k) vv[k] += bb[k];
+    }
+#pragma unroll
+    for (int k = 0; k < SPT_BATCH; ++k) {
+      const int i = t0 + k * 64 + lane;
+      pr[k] = i < whi && allowed(i) ? (double)expf(vv[k] / T - lse) : 0.0;
+    }
+  };
+  double acc = 0.0;
+  for (int t0 = wlo; t0 < whi; t0 += 64 * SPT_BATCH) {
+    double pr[SPT_BATCH];
+    load_batch(t0, pr);
+#pragma unroll
+    for (int k = 0; k < SPT_BATCH; ++k) acc += __shfl(wave_incl_scan(pr[k], lane), 63, 64);
+  }
+  if (lane == 0) sh_wsum[wid] = acc;
+  if (tid == 0) sh_pick = -1;
+  __syncthreads();
+  const double u = uniforms[(int64_t)b * p.max_tokens + n_cur];
+  double pre = 0.0, total = 0.0;
+  for (int w = 0; w < SPT_WAVES; ++w) total += sh_wsum[w];
+  const double target = u * total;
+  // the first wave whose range ends at or past the target (the last one at the latest: its end is the total, summed alike)
+  int w_hit = SPT_WAVES - 1;
+  for (int w = 0; w < SPT_WAVES; ++w) {
+    if (pre + sh_wsum[w] >= target) { w_hit = w; break; }
+    pre += sh_wsum[w];
+  }
+  if (wid == w_hit) {
+    // pre + this wave's tile totals is not bit for bit pre + its range total (another order of the same additions): should
+    // the walk end one rounding short of the target, the last index with p > 0 in the range is the pick
+    double cum = pre;
+    int pick = -1, last_pos = -1;
+    for (int t0 = wlo; t0 < whi && pick < 0; t0 += 64 * SPT_BATCH) {
+      double pr[SPT_BATCH];
+      load_batch(t0, pr);
+#pragma unroll
+      for (int k = 0; k < SPT_BATCH; ++k) {
+        if (pick >= 0) continue;          // wave-uniform
+        const double incl = wave_incl_scan(pr[k], lane);
+        const unsigned long long pos = __ballot(pr[k] > 0.0);
+        const unsigned long long hit = __ballot(t0 + k * 64 + lane < whi && cum + incl >= target);
+        if (hit) pick = t0 + k * 64 + __ffsll((unsigned long long)hit) - 1;
+        else if (pos) last_pos = t0 + k * 64 + 63 - __clzll((long long)pos);
+        cum += __shfl(incl, 63, 64);
+      }
+    }
+    if (lane == 0) sh_pick = pick >= 0 ? pick : last_pos;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int bi = sh_pick >= 0 ? sh_pick : NV - 1;
+    const float vb = scaled(bi);
+    const float lp = allowed(bi) ? vb - lse : -INFINITY;        // the host's logits[id] - lse over the filtered row
+    const int n_max = p.force_len > 0 ? p.force_len : p.n_max;
+    bool finished = false;
+    if (p.tok_lp) p.tok_lp[(int64_t)b * (p.max_tokens + 1) + n_cur] = lp;
+    if (bi == p.eot) {
+      finished = true;
+      p.next_tok[b] = bi;
+    } else {
+      toks[n_cur] = bi;
+      p.n_cur[b] = n_cur + 1;
+      p.sum_logprob[b] += lp;
+      p.next_tok[b] = bi;
+      if (p.advance) p.n_past[b] = np_now;
+      const int np = np_now;
+      if (n_cur + 1 >= n_max || n_cur + 1 >= p.max_tokens || np + 1 >= p.n_text_ctx) finished = true;
+    }
+    if (finished) { p.done[b] = 1; atomicAdd(p.n_done, 1); }
+  }
+}
+void launch_sampler_t(const SamplerParams& p, const float* temperature, const double* uniforms, hipStream_t s) {
+  hipLaunchKernelGGL(sampler_t_kernel, dim3(SAMPLER_SPLIT, p.batch), dim3(SP_THREADS), 0, s, p, temperature, uniforms);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // beam search (BASELINE.json config #5).  The reference never uses beam search (Greedy{best_of:1},
 // src/engine/whisper.rs:243); the rule restated here is the published Whisper BeamSearchDecoder (openai/whisper
 // decoding.py): every live beam proposes its beam_size + 1 most likely next tokens (after the same logits filter),

@@ -121,6 +121,7 @@ struct ohw_state {
   int stream_cus = 0;            // CUs of the current stream's mask (0 = unrestricted)
   bool skip_done = false;        // inside ohw_greedy: cross-attention skips windows whose done flag is set
   DevBuf samp_part, samp_ticket;   // sampler: per-slice partial states and arrival tickets
+  DevBuf samp_temp, samp_u;        // the temperature sampler's T [1] and pre-drawn canonical doubles [B][max_tokens] (ohw_sample_pass)
   DevBuf xa_part, xa_ticket;       // cross-attention over key slices (small batches)
   int xa_rows = 0;
   DevBuf step_tok, n_past, tokens, n_cur, next_tok, done, n_done, sum_lp;
@@ -154,7 +155,7 @@ struct ohw_state {
   double prof_work = 0.0;
   // hipGraph of one greedy iteration {feed sampled token, single-token decoder step, sampler}
   // captured greedy iterations, one per (batch, sampler parameters, CU budget of the stream) seen; a handful at most
-  struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; bool invariant = false, persist = false; SamplerParams spar{}; };
+  struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; bool invariant = false, persist = false, temp = false; SamplerParams spar{}; };
   bool batch_invariant = false;      // cross-attention variant picked from n_new alone (state_set_batch_invariant)
   std::vector<StepGraph> step_graphs;
   bool graphs_enabled = true;
@@ -271,6 +272,8 @@ void state_alloc(ohw_state* st) {
   st->sum_lp.alloc((size_t)B * 4, true);
   st->tok_lp.alloc((size_t)B * (st->max_tokens + 1) * 4, true);
   st->nosp_prob.alloc((size_t)B * 4, true);
+  st->samp_temp.alloc(16, true);
+  st->samp_u.alloc((size_t)B * st->max_tokens * 8, true);
   for (auto& e : st->ev) HIP_CHECK(hipEventCreate(&e));
   persist_prepare(st);
 }
@@ -902,30 +905,54 @@ void ohw_default_sample_params(const ohw_ctx* ctx, ohw_sample_params* p) {
   p->force_len = 0;
 }
 
-int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max_tokens, const ohw_greedy_result* res) {
-  return guard([&] {
+// the device-resident decode loop of ohw_greedy_ex (tp == nullptr: arg-max) and of ohw_sample_pass (tp: one temperature pass
+// over the windows tp->active names, drawing with tp->uniforms).  Throws; the entries wrap it in guard().
+struct TempPass {
+  float temperature;
+  const int32_t* active;     // [batch]
+  const double* uniforms;    // [batch][max_tokens]
+};
+static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, int max_tokens, const ohw_greedy_result* res, const TempPass* tp) {
+    const char* what = tp ? "sample_pass" : "greedy";
     if (!st || !sp || !res || !res->tokens || !res->n_tokens) throw Error(OHW_E_INVALID_ARG, "null argument");
     int32_t* tokens_out = res->tokens;
     int32_t* n_tokens_out = res->n_tokens;
     float* sum_logprob_out = res->sum_logprob;
-    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "greedy: batch must equal the batch of the last ohw_encode");
+    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": batch must equal the batch of the last ohw_encode");
     const ohw_ctx* c = st->ctx;
-    if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, "greedy: lang_id out of range");
+    if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": lang_id out of range");
+    if (tp && (!tp->active || !tp->uniforms || !(tp->temperature > 0.0f) || max_tokens < 1))
+      throw Error(OHW_E_INVALID_ARG, "sample_pass: needs temperature > 0, active, uniforms and max_tokens >= 1");
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = st->stream;
     int32_t prompt[8];
     const int n_prompt = build_prompt(c, sp, prompt);
     const int n_max_raw = sp->force_len > 0 ? sp->force_len : sp->n_max;
-    const int n_max = std::min(std::min(n_max_raw, st->max_tokens), c->hp.n_text_ctx - n_prompt);
-    if (n_max < 1) throw Error(OHW_E_INVALID_ARG, "greedy: n_max < 1");
+    int n_max = std::min(std::min(n_max_raw, st->max_tokens), c->hp.n_text_ctx - n_prompt);
+    if (tp) n_max = std::min(n_max, max_tokens);          // a row consumes at most max_tokens draws
+    if (n_max < 1) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": n_max < 1");
     std::vector<int32_t> ptoks((size_t)batch * n_prompt);
     for (int b = 0; b < batch; ++b) std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
-    HIP_CHECK(hipEventRecord(st->ev[4], s));
+    if (!tp) HIP_CHECK(hipEventRecord(st->ev[4], s));
     HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)batch * 4, s));
     HIP_CHECK(hipMemsetAsync(st->n_cur.p, 0, (size_t)batch * 4, s));
-    HIP_CHECK(hipMemsetAsync(st->done.p, 0, (size_t)batch * 4, s));
-    HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
+    // a temperature pass: windows with active[b] == 0 start finished (cross-attention and the sampler skip them)
+    std::vector<int32_t> done0;
+    int32_t n_done0[4] = {0, 0, 0, 0};
+    if (tp) {
+      done0.resize((size_t)batch);
+      for (int b = 0; b < batch; ++b) { done0[(size_t)b] = tp->active[b] ? 0 : 1; n_done0[0] += done0[(size_t)b]; }
+      HIP_CHECK(hipMemcpyAsync(st->done.p, done0.data(), done0.size() * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->n_done.p, n_done0, 16, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->samp_temp.p, &tp->temperature, 4, hipMemcpyHostToDevice, s));
+      const int nu = std::min(max_tokens, st->max_tokens);
+      HIP_CHECK(hipMemcpy2DAsync(st->samp_u.p, (size_t)st->max_tokens * 8, tp->uniforms, (size_t)max_tokens * 8, (size_t)nu * 8, (size_t)batch,
+                                 hipMemcpyHostToDevice, s));
+    } else {
+      HIP_CHECK(hipMemsetAsync(st->done.p, 0, (size_t)batch * 4, s));
+      HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
+    }
     HIP_CHECK(hipMemsetAsync(st->sum_lp.p, 0, (size_t)batch * 4, s));
     HIP_CHECK(hipMemsetAsync(st->next_tok.p, 0, (size_t)batch * 4, s));
     HIP_CHECK(hipMemsetAsync(st->nosp_prob.p, 0, (size_t)batch * 4, s));
@@ -941,10 +968,14 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max
       run_decoder_step<T>(st, batch, n_prompt);
       std::vector<int32_t> np((size_t)batch, n_prompt);
       HIP_CHECK(hipMemcpyAsync(st->n_past.p, np.data(), np.size() * 4, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipStreamSynchronize(s));  // np is a stack-lifetime source
+      HIP_CHECK(hipStreamSynchronize(s));  // np (and a temperature pass's done0, n_done0, T, draws) are stack-lifetime sources
       ++steps;
+      auto sample = [&](hipStream_t q) {
+        if (tp) launch_sampler_t(spar, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
+        else launch_sampler(spar, q);
+      };
       spar.advance = 0;
-      launch_sampler(spar, s);   // first token of every window from the prompt's logits
+      sample(s);                 // first token of every window from the prompt's logits
       spar.advance = 1;          // every later sampler call follows a single-token step
       // One greedy iteration = {feed next_tok, decoder step, sampler}.  It is launch-bound (about 260
       // short kernels), so it is captured once into a hipGraph and replayed; positions, tokens and
@@ -953,7 +984,7 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max
       hipGraphExec_t step_exec = nullptr;
       if (use_graph) {
         for (auto& g : st->step_graphs)
-          if (g.batch == batch && g.cus == st->stream_cus && g.invariant == st->batch_invariant && g.persist == st->persist && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
+          if (g.batch == batch && g.cus == st->stream_cus && g.invariant == st->batch_invariant && g.persist == st->persist && g.temp == (tp != nullptr) && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
       }
       if (use_graph && !step_exec) {
         if (st->step_graphs.size() >= 8) {     // bounded: drop the oldest capture
@@ -978,7 +1009,7 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max
         HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
         try {
           run_decoder_step<T>(st, batch, 1, st->next_tok.as<int32_t>());   // the token the sampler just wrote
-          launch_sampler(spar, cap);
+          sample(cap);
         } catch (...) {
           hipGraph_t g = nullptr;
           (void)hipStreamEndCapture(cap, &g);
@@ -988,7 +1019,7 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max
         HIP_CHECK(hipStreamEndCapture(cap, &ng.graph));
         hipError_t ie = hipGraphInstantiate(&ng.exec, ng.graph, nullptr, nullptr, 0);
         if (ie != hipSuccess) { (void)hipGraphDestroy(ng.graph); HIP_CHECK(ie); }
-        ng.batch = batch; ng.cus = st->stream_cus; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.spar = spar;
+        ng.batch = batch; ng.cus = st->stream_cus; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.temp = tp != nullptr; ng.spar = spar;
         st->step_graphs.push_back(ng);
         ++st->step_captures;
         step_exec = ng.exec;
@@ -999,7 +1030,7 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max
           HIP_CHECK(hipGraphLaunch(step_exec, s));
         } else {
           run_decoder_step<T>(st, batch, 1, st->next_tok.as<int32_t>());
-          launch_sampler(spar, s);
+          sample(s);
         }
         ++steps;
         if (sp->force_len <= 0 && ((it & 7) == 7)) {
@@ -1009,7 +1040,7 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max
         }
       }
     });
-    HIP_CHECK(hipEventRecord(st->ev[5], s));
+    if (!tp) HIP_CHECK(hipEventRecord(st->ev[5], s));
     std::vector<int32_t> toks((size_t)batch * st->max_tokens), ncur((size_t)batch);
     HIP_CHECK(hipMemcpyAsync(toks.data(), st->tokens.p, toks.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(ncur.data(), st->n_cur.p, ncur.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1036,7 +1067,18 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max
         std::memcpy(dst, &lps[(size_t)b * (st->max_tokens + 1)], (size_t)m * 4);
       }
     }
-    st->last.decode_steps = steps;
+    if (!tp) st->last.decode_steps = steps;     // ohw_state_timings reports the T = 0 loop
+}
+
+int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* sp, int batch, int max_tokens, const ohw_greedy_result* res) {
+  return guard([&] { decode_loop(st, sp, batch, max_tokens, res, nullptr); });
+}
+
+int ohw_sample_pass(ohw_state* st, const ohw_sample_params* sp, int batch, int max_tokens, float temperature, const int32_t* active,
+                    const double* uniforms, const ohw_greedy_result* out) {
+  return guard([&] {
+    const TempPass tp{temperature, active, uniforms};
+    decode_loop(st, sp, batch, max_tokens, out, &tp);
   });
 }
 
@@ -1279,10 +1321,12 @@ int ohw_state_set_logit_bias(ohw_state* st, const float* bias, int n) {
 // test entry: the device sampler on caller-supplied rows.  logits [batch][n_vocab] (host), history [batch][hist_stride]
 // with n_hist[b] tokens sampled so far.  Returns the token the sampler picks per row (end-of-text included), its
 // log-probability, and the first-step no-speech probability (rows with n_hist == 0; 0 elsewhere).
-int ohw_dbg_sample(ohw_state* st, const ohw_sample_params* sp, const float* logits, const int32_t* history, int hist_stride,
-                   const int32_t* n_hist, int batch, int32_t* tokens_out, float* logprobs_out, float* no_speech_out) {
-  return guard([&] {
+// temperature > 0: the temperature sampler, uniforms [batch] the draw of each row's step
+static void dbg_sample(ohw_state* st, const ohw_sample_params* sp, const float* logits, const int32_t* history, int hist_stride,
+                       const int32_t* n_hist, int batch, float temperature, const double* uniforms, int32_t* tokens_out, float* logprobs_out,
+                       float* no_speech_out) {
     if (!st || !sp || !logits || !n_hist || !tokens_out) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (temperature > 0.0f && !uniforms) throw Error(OHW_E_INVALID_ARG, "dbg_sample_t: uniforms is null");
     if (batch < 1 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "dbg_sample: batch exceeds the state's max_batch");
     const ohw_ctx* c = st->ctx;
     const int V = c->hp.n_vocab;
@@ -1307,7 +1351,16 @@ int ohw_dbg_sample(ohw_state* st, const ohw_sample_params* sp, const float* logi
     SamplerParams spar;
     fill_sampler(st, sp, batch, &spar);
     spar.advance = 0;
-    launch_sampler(spar, s);
+    std::vector<double> u;
+    if (temperature > 0.0f) {
+      u.assign((size_t)batch * st->max_tokens, 0.0);
+      for (int b = 0; b < batch; ++b) u[(size_t)b * st->max_tokens + n_hist[b]] = uniforms[b];
+      HIP_CHECK(hipMemcpyAsync(st->samp_temp.p, &temperature, 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->samp_u.p, u.data(), u.size() * 8, hipMemcpyHostToDevice, s));
+      launch_sampler_t(spar, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);
+    } else {
+      launch_sampler(spar, s);
+    }
     std::vector<float> lps((size_t)batch * (st->max_tokens + 1));
     HIP_CHECK(hipMemcpyAsync(tokens_out, st->next_tok.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(lps.data(), st->tok_lp.p, lps.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1315,6 +1368,19 @@ int ohw_dbg_sample(ohw_state* st, const ohw_sample_params* sp, const float* logi
     HIP_CHECK(hipStreamSynchronize(s));
     if (logprobs_out)
       for (int b = 0; b < batch; ++b) logprobs_out[b] = lps[(size_t)b * (st->max_tokens + 1) + n_hist[b]];
+}
+
+int ohw_dbg_sample(ohw_state* st, const ohw_sample_params* sp, const float* logits, const int32_t* history, int hist_stride,
+                   const int32_t* n_hist, int batch, int32_t* tokens_out, float* logprobs_out, float* no_speech_out) {
+  return guard([&] { dbg_sample(st, sp, logits, history, hist_stride, n_hist, batch, 0.0f, nullptr, tokens_out, logprobs_out, no_speech_out); });
+}
+
+int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* sp, const float* logits, const int32_t* history, int hist_stride,
+                     const int32_t* n_hist, int batch, float temperature, const double* uniforms, int32_t* tokens_out, float* logprobs_out,
+                     float* no_speech_out) {
+  return guard([&] {
+    if (!(temperature > 0.0f)) throw Error(OHW_E_INVALID_ARG, "dbg_sample_t: temperature must be > 0");
+    dbg_sample(st, sp, logits, history, hist_stride, n_hist, batch, temperature, uniforms, tokens_out, logprobs_out, no_speech_out);
   });
 }
 

@@ -16,6 +16,7 @@
 #include <memory>
 #include <random>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -234,9 +235,35 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         trace(sc, w0 + b, 0.f, r.tok);
       }
     };
-    // the temperature ladder for the windows of a batch whose pass failed the acceptance test: the HOST samples
-    // (std::mt19937 + std::discrete_distribution, as whisper.cpp's decoders do), the device runs the decoder steps of the
-    // pending windows only and re-uses their resident cross K/V; the logits of the pending rows cross PCIe every step
+    // the temperature ladder for the windows of a batch whose pass failed the acceptance test, drawn from std::mt19937 through
+    // std::discrete_distribution as whisper.cpp's decoders do, on the pending windows' resident cross K/V.  By default the
+    // HOST samples: the device runs the decoder steps of the pending windows only and their logits cross PCIe every step.
+    // e->fallback_device: the device samples too (ohw_sample_pass: the greedy loop's replayed {step, sampler} with the
+    // temperature sampler), from the host generators' pre-drawn doubles; the host then cuts each pass at whisper.cpp's loop
+    // exits (evaluate_sequence) and advances each generator by the draws it kept, where the host ladder would leave it
+    auto device_pass = [&](Scratch& sc, ohw_state* st, int B, const int* seek, const int* seek_end, const std::vector<int32_t>& active, float T,
+                           const std::vector<ohw_rng*>& rngs, std::vector<WindowRun>& pass) {
+      std::vector<double> u((size_t)B * max_tok, 0.0);
+      const int n_draw = std::min(n_max, max_tok);
+      for (int b = 0; b < B; ++b)
+        if (active[(size_t)b] && ohw_rng_uniforms(rngs[(size_t)b], n_draw, &u[(size_t)b * max_tok]) != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: generator");
+      ohw_greedy_result gr{};
+      gr.tokens = sc.toks.data(); gr.n_tokens = sc.ntok.data(); gr.token_logprobs = sc.lps.data(); gr.ended_by_eot = sc.eot.data(); gr.no_speech_prob = sc.nsp.data();
+      check(ohw_sample_pass(st, &sp, B, max_tok, T, active.data(), u.data(), &gr));
+      for (int b = 0; b < B; ++b) {
+        if (!active[(size_t)b]) continue;
+        WindowRun& r = pass[(size_t)b];
+        const int nt = sc.ntok[(size_t)b] + (sc.eot[(size_t)b] ? 1 : 0);
+        r.tok.assign(&sc.toks[(size_t)b * max_tok], &sc.toks[(size_t)b * max_tok] + sc.ntok[(size_t)b]);
+        if (sc.eot[(size_t)b]) r.tok.push_back(tk.eot);
+        r.plog.assign(&sc.lps[(size_t)b * (max_tok + 1)], &sc.lps[(size_t)b * (max_tok + 1)] + nt);
+        r.nosp = sc.nsp[(size_t)b];
+        const SeqEval ev = evaluate_sequence(tk, r.tok.data(), r.plog.data(), nt, seek[b], seek_end[b], n_max, sp.no_timestamps != 0, e->window_mode);
+        r.tok.resize((size_t)ev.n_sampled);
+        r.plog.resize((size_t)ev.n_sampled);
+        if (ohw_rng_discard_draws(rngs[(size_t)b], ev.n_sampled) != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: generator");
+      }
+    };
     auto run_ladder = [&](Scratch& sc, ohw_state* st, int B, const int* seek, const int* seek_end, int64_t w0, const std::vector<ohw_rng*>& rngs) {
       std::vector<float>& logits = sc.logits;
       std::vector<WindowRun>& runs = sc.runs;
@@ -247,30 +274,34 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         if (!any) break;
         const float T = temps[ti];
         const bool is_last = ti + 1 == temps.size();
-        logits.resize((size_t)B * V);
-        std::vector<int32_t> ptoks((size_t)B * n_prompt), past((size_t)B, 0), feed((size_t)B, tk.eot), npast((size_t)B, n_prompt), live = active;
-        for (int b = 0; b < B; ++b) std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
-        check(ohw_decode_active(st, ptoks.data(), n_prompt, past.data(), B, active.data(), logits.data()));
         std::vector<WindowRun> pass((size_t)B);
-        for (int i = 0; i < n_max; ++i) {
-          bool any_live = false;
-          for (int b = 0; b < B; ++b) {
-            if (!live[(size_t)b]) continue;
-            WindowRun& r = pass[(size_t)b];
-            float lp = 0.f;
-            if (const float* bias = state_bias_host(st))          // the state's logit bias: the device sampler adds it itself
-              for (int i2 = 0; i2 < V; ++i2) logits[(size_t)b * V + i2] += bias[i2];
-            const int32_t t = ohw_sample_host(e->ctx, &sp, &logits[(size_t)b * V], r.tok.data(), (int)r.tok.size(), T, rngs[(size_t)b], &lp, &r.nosp);
-            if (t < 0) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: host sampler");
-            r.tok.push_back(t); r.plog.push_back(lp);
-            const SeqEval ev = evaluate_sequence(tk, r.tok.data(), r.plog.data(), (int)r.tok.size(), seek[b], seek_end[b], n_max,
-                                                 sp.no_timestamps != 0, e->window_mode);
-            if (t == tk.eot || ev.completed || ev.failed || (int)r.tok.size() >= n_max || npast[(size_t)b] + 1 >= max_tok) live[(size_t)b] = 0;
-            else { feed[(size_t)b] = t; any_live = true; }
+        if (e->fallback_device) {
+          device_pass(sc, st, B, seek, seek_end, active, T, rngs, pass);
+        } else {
+          logits.resize((size_t)B * V);
+          std::vector<int32_t> ptoks((size_t)B * n_prompt), past((size_t)B, 0), feed((size_t)B, tk.eot), npast((size_t)B, n_prompt), live = active;
+          for (int b = 0; b < B; ++b) std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
+          check(ohw_decode_active(st, ptoks.data(), n_prompt, past.data(), B, active.data(), logits.data()));
+          for (int i = 0; i < n_max; ++i) {
+            bool any_live = false;
+            for (int b = 0; b < B; ++b) {
+              if (!live[(size_t)b]) continue;
+              WindowRun& r = pass[(size_t)b];
+              float lp = 0.f;
+              if (const float* bias = state_bias_host(st))          // the state's logit bias: the device sampler adds it itself
+                for (int i2 = 0; i2 < V; ++i2) logits[(size_t)b * V + i2] += bias[i2];
+              const int32_t t = ohw_sample_host(e->ctx, &sp, &logits[(size_t)b * V], r.tok.data(), (int)r.tok.size(), T, rngs[(size_t)b], &lp, &r.nosp);
+              if (t < 0) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: host sampler");
+              r.tok.push_back(t); r.plog.push_back(lp);
+              const SeqEval ev = evaluate_sequence(tk, r.tok.data(), r.plog.data(), (int)r.tok.size(), seek[b], seek_end[b], n_max,
+                                                   sp.no_timestamps != 0, e->window_mode);
+              if (t == tk.eot || ev.completed || ev.failed || (int)r.tok.size() >= n_max || npast[(size_t)b] + 1 >= max_tok) live[(size_t)b] = 0;
+              else { feed[(size_t)b] = t; any_live = true; }
+            }
+            if (!any_live) break;
+            check(ohw_decode_active(st, feed.data(), 1, npast.data(), B, live.data(), logits.data()));
+            for (int b = 0; b < B; ++b) if (live[(size_t)b]) ++npast[(size_t)b];
           }
-          if (!any_live) break;
-          check(ohw_decode_active(st, feed.data(), 1, npast.data(), B, live.data(), logits.data()));
-          for (int b = 0; b < B; ++b) if (live[(size_t)b]) ++npast[(size_t)b];
         }
         for (int b = 0; b < B; ++b) {
           if (!active[(size_t)b]) continue;
@@ -757,6 +788,21 @@ int32_t ohw_sample_host(const ohw_ctx* ctx, const ohw_sample_params* p, float* l
   return id;
 }
 
+// a draw of std::discrete_distribution<int> in libstdc++ is exactly one std::generate_canonical<double, 53> (two engine
+// outputs, the lower_bound of it in the normalised partial sums): the stream position of every draw is known in advance
+int ohw_rng_uniforms(const ohw_rng* rng, int n, double* out) {
+  if (!rng || n < 0 || (n > 0 && !out)) return OHW_E_INVALID_ARG;
+  std::mt19937 g = rng->gen;
+  for (int i = 0; i < n; ++i) out[i] = std::generate_canonical<double, std::numeric_limits<double>::digits>(g);
+  return OHW_OK;
+}
+
+int ohw_rng_discard_draws(ohw_rng* rng, int n) {
+  if (!rng || n < 0) return OHW_E_INVALID_ARG;
+  for (int i = 0; i < n; ++i) (void)std::generate_canonical<double, std::numeric_limits<double>::digits>(rng->gen);
+  return OHW_OK;
+}
+
 int ohw_detect_language(ohw_state* st, int batch, int32_t* lang_ids_out, float* lang_probs_out) {
   return guard([&] {
     if (!st || !lang_ids_out || batch < 1) throw Error(OHW_E_INVALID_ARG, "bad argument");
@@ -878,6 +924,12 @@ void ohw_default_decode_policy(ohw_decode_policy* q) {
 int ohw_engine_set_decode_policy(ohw_engine* e, const ohw_decode_policy* q) {
   if (!e || !q) return OHW_E_INVALID_ARG;
   e->policy = *q;
+  return OHW_OK;
+}
+
+int ohw_engine_set_fallback_device(ohw_engine* e, int on) {
+  if (!e) return OHW_E_INVALID_ARG;
+  e->fallback_device = on != 0;
   return OHW_OK;
 }
 

@@ -30,6 +30,7 @@ struct ohw_engine {
   int enc_cus = 96;
   int device = 0;
   ohw_decode_policy policy{0.2f, 2.4f, -1.0f, 0.6f};
+  bool fallback_device = false;          // the temperature ladder samples on the device (ohw_engine_set_fallback_device)
   std::vector<int32_t> last_trace;   // every decode pass of the last transcribe: {window, temperature * 1000, n, tokens...}
 };
 

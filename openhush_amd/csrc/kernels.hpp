@@ -185,5 +185,8 @@ void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_window
 constexpr int SAMPLER_SPLIT = 8;
 constexpr int SAMPLER_PART_WORDS = 12;
 void launch_sampler(const SamplerParams& p, hipStream_t s);
+// the same filter at a temperature, then one draw (the fallback ladder on the device): temperature [1] and
+// uniforms [batch][p.max_tokens] (the canonical double of step n_cur of row b) are read from device memory
+void launch_sampler_t(const SamplerParams& p, const float* temperature, const double* uniforms, hipStream_t s);
 
 }  // namespace ohw

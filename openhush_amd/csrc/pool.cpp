@@ -311,6 +311,12 @@ int ohw_pool_set_decode_policy(ohw_pool* p, const ohw_decode_policy* q) {
   return OHW_OK;
 }
 
+int ohw_pool_set_fallback_device(ohw_pool* p, int on) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) (void)ohw_engine_set_fallback_device(e, on);
+  return OHW_OK;
+}
+
 int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t sample_rate, char* text_buf, size_t text_cap,
                         char* language_out, uint64_t* duration_ms, ohw_audio_info* info_out) {
   return guard([&] {

@@ -144,6 +144,8 @@ EXPORTS = [
     "ohw_dbg_counter", "ohw_dsp_denoise", "ohw_denoise_passthrough_engine", "ohw_preprocess_audio_ex", "ohw_pool_set_window_mode",
     "ohw_state_set_persistent", "ohw_pool_broadcast_note", "ohw_pool_create_synthetic", "ohw_pool_set_force_len", "ohw_pool_set_schedule", "ohw_engine_set_force_len",
     "ohw_pool_set_decode_policy", "ohw_pool_n_devices", "ohw_pool_broadcast_kind", "ohw_pool_engine", "ohw_pool_free",
+    "ohw_rng_uniforms", "ohw_rng_discard_draws", "ohw_sample_pass", "ohw_dbg_sample_t", "ohw_engine_set_fallback_device",
+    "ohw_pool_set_fallback_device",
 ]
 
 
@@ -313,6 +315,12 @@ def lib():
         L.ohw_rng_free.argtypes = [vp]
         L.ohw_rng_free.restype = None
         L.ohw_sample_host.argtypes = [vp, C.POINTER(SampleParams), fp, ip, C.c_int, C.c_float, vp, fp, fp]
+        L.ohw_rng_uniforms.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
+        L.ohw_rng_discard_draws.argtypes = [vp, C.c_int]
+        L.ohw_sample_pass.argtypes = [vp, C.POINTER(SampleParams), C.c_int, C.c_int, C.c_float, ip, C.POINTER(C.c_double), C.POINTER(GreedyResult)]
+        L.ohw_dbg_sample_t.argtypes = [vp, C.POINTER(SampleParams), fp, ip, C.c_int, ip, C.c_int, C.c_float, C.POINTER(C.c_double), ip, fp, fp]
+        L.ohw_engine_set_fallback_device.argtypes = [vp, C.c_int]
+        L.ohw_pool_set_fallback_device.argtypes = [vp, C.c_int]
         L.ohw_default_decode_policy.argtypes = [C.POINTER(DecodePolicy)]
         L.ohw_default_decode_policy.restype = None
         L.ohw_engine_set_decode_policy.argtypes = [vp, C.POINTER(DecodePolicy)]
@@ -500,6 +508,16 @@ class HostRng:
     """ohw_rng: the std::mt19937 whisper.cpp's decoders sample with (seed 0 per call)"""
     def __init__(self, seed: int = 0):
         self.h = C.c_void_p(lib().ohw_rng_new(seed))
+
+    def uniforms(self, n: int) -> np.ndarray:
+        """ohw_rng_uniforms: the next n draws (canonical doubles) without advancing the generator"""
+        out = np.zeros(max(1, n), dtype=np.float64)
+        _check(lib().ohw_rng_uniforms(self.h, n, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:n]
+
+    def discard_draws(self, n: int):
+        """ohw_rng_discard_draws: advance by n draws"""
+        _check(lib().ohw_rng_discard_draws(self.h, n))
 
     def __del__(self):
         try:
@@ -700,6 +718,45 @@ class State:
         ns = np.zeros(B, dtype=np.float32)
         _check(lib().ohw_dbg_sample(self.h, C.byref(p), _fp(lg), _ip(hist), stride, _ip(nh), B, _ip(tok), _fp(lp), _fp(ns)))
         return tok, lp, ns
+
+    def dbg_sample_t(self, p: SampleParams, logits: np.ndarray, histories: Sequence[Sequence[int]], temperature: float,
+                     uniforms: Sequence[float]):
+        """the DEVICE temperature sampler on caller-supplied rows, one draw per row -> (tokens [B], logprobs [B], no_speech_prob [B])"""
+        lg = np.ascontiguousarray(np.atleast_2d(logits), dtype=np.float32)
+        B = lg.shape[0]
+        stride = max(1, max(len(h) for h in histories))
+        hist = np.zeros((B, stride), dtype=np.int32)
+        nh = np.zeros(B, dtype=np.int32)
+        for b, h in enumerate(histories):
+            hist[b, :len(h)] = h
+            nh[b] = len(h)
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        assert u.shape == (B,)
+        tok = np.zeros(B, dtype=np.int32)
+        lp = np.zeros(B, dtype=np.float32)
+        ns = np.zeros(B, dtype=np.float32)
+        _check(lib().ohw_dbg_sample_t(self.h, C.byref(p), _fp(lg), _ip(hist), stride, _ip(nh), B, temperature,
+                                      u.ctypes.data_as(C.POINTER(C.c_double)), _ip(tok), _fp(lp), _fp(ns)))
+        return tok, lp, ns
+
+    def sample_pass(self, batch: int, temperature: float, active: Sequence[int], uniforms: np.ndarray, p: Optional[SampleParams] = None):
+        """ohw_sample_pass: one temperature pass on the device; uniforms [batch][n_text_ctx] -> greedy_ex's dicts (zeros for
+        inactive rows)"""
+        p = p or self.ctx.default_params()
+        cap = self.ctx.hp.n_text_ctx
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        assert u.shape == (batch, cap)
+        act = np.ascontiguousarray(active, dtype=np.int32)
+        toks = np.zeros((batch, cap), dtype=np.int32)
+        nt = np.zeros(batch, dtype=np.int32)
+        slp = np.zeros(batch, dtype=np.float32)
+        lps = np.zeros((batch, cap + 1), dtype=np.float32)
+        eot = np.zeros(batch, dtype=np.int32)
+        nsp = np.zeros(batch, dtype=np.float32)
+        r = GreedyResult(_ip(toks), _ip(nt), _fp(slp), _fp(lps), _ip(eot), _fp(nsp))
+        _check(lib().ohw_sample_pass(self.h, C.byref(p), batch, cap, temperature, _ip(act), u.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))
+        return [{"tokens": [int(x) for x in toks[b, :nt[b]]], "logprobs": lps[b, :nt[b] + (1 if eot[b] else 0)].copy(),
+                 "ended_by_eot": bool(eot[b]), "no_speech_prob": float(nsp[b]), "sum_logprob": float(slp[b])} for b in range(batch)]
 
     def greedy_host_sampler(self, batch: int, p: Optional[SampleParams] = None):
         """the same loop with the HOST owning the sampler: logits cross PCIe every step"""
@@ -1079,6 +1136,10 @@ class WhisperEngine:
                 setattr(pol, k, v)
         _check(lib().ohw_engine_set_decode_policy(self.h, C.byref(pol)))
 
+    def set_fallback_on_device(self, on: bool = True):
+        """ohw_engine_set_fallback_device: the temperature fallback samples on the device (default: on the host)"""
+        _check(lib().ohw_engine_set_fallback_device(self.h, 1 if on else 0))
+
     def last_trace(self):
         """[(window, temperature, [sampled tokens, end-of-text included])] for every decode pass of the last transcribe"""
         p = C.POINTER(C.c_int32)()
@@ -1171,6 +1232,10 @@ class EnginePool:
         for k, v in kw.items():
             setattr(pol, k, v)
         _check(lib().ohw_pool_set_decode_policy(self.h, C.byref(pol)))
+
+    def set_fallback_on_device(self, on: bool = True):
+        """ohw_pool_set_fallback_device: ohw_engine_set_fallback_device on every engine of the pool"""
+        _check(lib().ohw_pool_set_fallback_device(self.h, 1 if on else 0))
 
     def transcribe(self, audio: AudioBuffer) -> TranscriptionResult:
         s = np.ascontiguousarray(audio.samples, dtype=np.float32)
