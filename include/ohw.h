@@ -565,7 +565,18 @@ int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* p, const float* log
 /* counters of a state's graph caches: "step_captures" / "beam_captures" (graphs / graph pairs captured so far),
  * "step_graphs" / "beam_graphs" (entries held now), "persist_launches" (persistent decoder steps launched or captured);
  * OHW_E_INVALID_ARG for another name.  A second ohw_greedy /
- * ohw_beam_search with the same batch, parameters and stream must add no capture (tests/test_gpu_beam.py).        */
+ * ohw_beam_search with the same batch, parameters and stream must add no capture (tests/test_gpu_beam.py).
+ * The decoder step's kernel variants, launches counted per state since its creation (host-side: a captured step
+ * counts once, at its capture; saturates at INT32_MAX):
+ *   "dec_gemm.<gemm><form>.<NT>x<MT>"  gemm: qkv, o (self-attention out), xq, xo (cross-attention q / out), fc1, fc2,
+ *                                      logits; form: ".ln" (LayerNorm in the prologue), ".pn" (post-norm), ".ks"
+ *                                      (split-K), "" (none); NT x MT n-tiles x m-tiles per workgroup: 1x1 2x1 1x2 2x2 4x2
+ *   "xattn.plain" / "xattn.split"      cross-attention, one workgroup per (row, head) / keys cut over gridDim.z > 1
+ *   "xattn.rows2" .. "xattn.rows4"     one workgroup per (window, head) for 2..4 new tokens
+ *   "xattn.group2" .. "xattn.group5"   the same for 2..5 beams of a window; "xattn.group_split": beams, keys cut
+ *   "self_attn.plain" / ".slots"       masked self-attention, without / with the beam kv_slot table; ".fused" /
+ *                                      ".fused_slots": the same inside the QKV launch (OHW_DEC_FUSE_ATTN=1)
+ * The persistent step (ohw_state_set_persistent) counts only its logits GEMM.                                    */
 int ohw_dbg_counter(const ohw_state* st, const char* name);
 
 #ifdef __cplusplus

@@ -588,16 +588,17 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_kernel(DecGemmParams p
 }
 
 template <typename T, int EPI, bool LN, int NT, int MT>
-static void dec_gemm_launch(const DecGemmParams& p, hipStream_t s) {
+static int dec_gemm_launch(const DecGemmParams& p, hipStream_t s) {
   const int n_tiles = (p.N + 15) / 16;
   dim3 grid((n_tiles + NT - 1) / NT, (p.M + 16 * MT - 1) / (16 * MT), p.ksplit > 1 ? p.ksplit : 1);
   const size_t smem = (size_t)DG_WAVES * NT * 2 * 64 * 16 + (LN ? (size_t)16 * MT * (p.K * 2 + 16) : 256);
   if (LN) ensure_dynamic_lds((const void*)dec_gemm_kernel<T, EPI, LN, NT, MT>, 160 * 1024);
   hipLaunchKernelGGL((dec_gemm_kernel<T, EPI, LN, NT, MT>), grid, dim3(DG_THREADS), smem, s, p);
+  return NT == 4 ? DG_SHAPE_4x2 : NT == 2 ? (MT == 1 ? DG_SHAPE_2x1 : DG_SHAPE_2x2) : (MT == 1 ? DG_SHAPE_1x1 : DG_SHAPE_1x2);
 }
 
 template <typename T, int EPI, bool LN>
-static void dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
+static int dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
   // with the LayerNorm image in LDS one workgroup fills a CU: keep the grid within one wave of the CUs this
   // launch may use (256, or the decoder's share when two batches are in flight)
   const int n_tiles = (p.N + 15) / 16;
@@ -608,27 +609,27 @@ static void dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
   if constexpr (EPI == DEPI_BIAS_RESID && !LN) {
     // one m-tile per workgroup when that still fits one wave of CUs (and the hand-off path is not in use); a single
     // m-tile (batch <= 16) never takes the two-tile kernel, whose second tile would be loaded for nothing
-    if (msplit && p.ksplit <= 1 && (mt == 1 || n_tiles * mt <= 2 * cus)) { dec_gemm_launch<T, EPI, LN, 1, 1>(p, s); return; }
+    if (msplit && p.ksplit <= 1 && (mt == 1 || n_tiles * mt <= 2 * cus)) return dec_gemm_launch<T, EPI, LN, 1, 1>(p, s);
   }
   if constexpr (!LN && (EPI == DEPI_QKV || EPI == DEPI_BIAS_T || EPI == DEPI_BIAS_GELU_T)) {
     // post-norm consumers: the same grid rule as the LayerNorm variants (one workgroup per CU: at 512 threads and up to
     // 256 registers a second workgroup does not fit beside it; a two-round grid doubled the QKV launch, 4.9 -> 8.9 us)
     if (p.pn && msplit && mt <= 2) {
-      if (n_tiles * mt <= cus) { dec_gemm_launch<T, EPI, LN, 1, 1>(p, s); return; }
-      if ((n_tiles + 1) / 2 * mt <= cus || mt == 1) { dec_gemm_launch<T, EPI, LN, 2, 1>(p, s); return; }
+      if (n_tiles * mt <= cus) return dec_gemm_launch<T, EPI, LN, 1, 1>(p, s);
+      if ((n_tiles + 1) / 2 * mt <= cus || mt == 1) return dec_gemm_launch<T, EPI, LN, 2, 1>(p, s);
     }
-    if (p.pn && n_tiles > cus) { dec_gemm_launch<T, EPI, LN, 2, 2>(p, s); return; }
+    if (p.pn && n_tiles > cus) return dec_gemm_launch<T, EPI, LN, 2, 2>(p, s);
   }
   if constexpr (LN) {
     // one m-tile per workgroup halves the fp32 rows a workgroup normalises; pick the n-tiles per workgroup that keep
     // the grid within one wave of CUs
     if (msplit && mt <= 2) {
-      if (n_tiles * mt <= cus) { dec_gemm_launch<T, EPI, LN, 1, 1>(p, s); return; }
-      if ((n_tiles + 1) / 2 * mt <= cus || mt == 1) { dec_gemm_launch<T, EPI, LN, 2, 1>(p, s); return; }
+      if (n_tiles * mt <= cus) return dec_gemm_launch<T, EPI, LN, 1, 1>(p, s);
+      if ((n_tiles + 1) / 2 * mt <= cus || mt == 1) return dec_gemm_launch<T, EPI, LN, 2, 1>(p, s);
     }
   }
   if constexpr (EPI == DEPI_LOGITS) {
-    if (msplit && mt == 1 && logits_nt == 2) { dec_gemm_launch<T, EPI, LN, 2, 1>(p, s); return; }
+    if (msplit && mt == 1 && logits_nt == 2) return dec_gemm_launch<T, EPI, LN, 2, 1>(p, s);
   }
   // many rows on few CUs (a lane of the LANES schedule: 96 rows on 64 CUs): when the largest grid above would still take
   // more than two rounds of the CUs, a workgroup takes four n-tiles (QKV at 96 rows: 360 workgroups -> 180; the
@@ -636,15 +637,15 @@ static void dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
   static const int nt4 = getenv("OHW_DEC_NT4") ? atoi(getenv("OHW_DEC_NT4")) : 1;
   if constexpr ((LN && (EPI == DEPI_QKV || EPI == DEPI_BIAS_T || EPI == DEPI_BIAS_GELU_T)) || (!LN && (EPI == DEPI_BIAS_RESID || EPI == DEPI_LOGITS))) {
     const int64_t wgs = LN ? (int64_t)((n_tiles + 1) / 2) * ((mt + 1) / 2) : (int64_t)n_tiles * ((mt + 1) / 2);
-    if (nt4 && mt > 2 && p.ksplit <= 1 && !p.pn && !p.stat_out && p.K <= DG_LN_MAXK && wgs > 2 * cus) { dec_gemm_launch<T, EPI, LN, 4, 2>(p, s); return; }
+    if (nt4 && mt > 2 && p.ksplit <= 1 && !p.pn && !p.stat_out && p.K <= DG_LN_MAXK && wgs > 2 * cus) return dec_gemm_launch<T, EPI, LN, 4, 2>(p, s);
     // (mlp.2, K = 5120, keeps its single-tile workgroups: two tiles per workgroup measured the same within the run-to-run noise)
   }
-  if ((LN && n_tiles > cus) || (EPI == DEPI_LOGITS && logits_nt == 2)) dec_gemm_launch<T, EPI, LN, 2, 2>(p, s);
-  else dec_gemm_launch<T, EPI, LN, 1, 2>(p, s);
+  if ((LN && n_tiles > cus) || (EPI == DEPI_LOGITS && logits_nt == 2)) return dec_gemm_launch<T, EPI, LN, 2, 2>(p, s);
+  return dec_gemm_launch<T, EPI, LN, 1, 2>(p, s);
 }
 
 template <typename T>
-void launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s) {
+int launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s) {
   if (p.K % 32 != 0) throw Error(OHW_E_INVALID_ARG, "dec_gemm: K must be a multiple of 32");
   const bool ln = p.ln != 0;
   if (p.ksplit > 1) {
@@ -656,15 +657,17 @@ void launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s) {
   if (p.pn && (ln || !p.stat_in || !p.wsum || p.n_stat * 16 != p.K || p.n_stat > 128)) throw Error(OHW_E_INVALID_ARG, "dec_gemm: post-norm needs statistics of K / 16 tiles per row and the weights' row sums");
   if (p.stat_out && (epilogue != DEPI_BIAS_RESID || !p.x16_out || p.N % 32 != 0 || p.ksplit > 1))
     throw Error(OHW_E_INVALID_ARG, "dec_gemm: statistics come from the unsplit RESID epilogue with N % 32 == 0");
+  int shape = 0;
   switch (epilogue) {
-    case DEPI_QKV: if (ln) dec_gemm_pick<T, DEPI_QKV, true>(p, s); else dec_gemm_pick<T, DEPI_QKV, false>(p, s); break;
-    case DEPI_BIAS_T: if (ln) dec_gemm_pick<T, DEPI_BIAS_T, true>(p, s); else dec_gemm_pick<T, DEPI_BIAS_T, false>(p, s); break;
-    case DEPI_BIAS_GELU_T: if (ln) dec_gemm_pick<T, DEPI_BIAS_GELU_T, true>(p, s); else dec_gemm_pick<T, DEPI_BIAS_GELU_T, false>(p, s); break;
-    case DEPI_BIAS_RESID: if (ln) throw Error(OHW_E_INVALID_ARG, "dec_gemm: no LN variant"); dec_gemm_pick<T, DEPI_BIAS_RESID, false>(p, s); break;
-    case DEPI_LOGITS: if (ln) throw Error(OHW_E_INVALID_ARG, "dec_gemm: no LN variant"); dec_gemm_pick<T, DEPI_LOGITS, false>(p, s); break;
+    case DEPI_QKV: shape = ln ? dec_gemm_pick<T, DEPI_QKV, true>(p, s) : dec_gemm_pick<T, DEPI_QKV, false>(p, s); break;
+    case DEPI_BIAS_T: shape = ln ? dec_gemm_pick<T, DEPI_BIAS_T, true>(p, s) : dec_gemm_pick<T, DEPI_BIAS_T, false>(p, s); break;
+    case DEPI_BIAS_GELU_T: shape = ln ? dec_gemm_pick<T, DEPI_BIAS_GELU_T, true>(p, s) : dec_gemm_pick<T, DEPI_BIAS_GELU_T, false>(p, s); break;
+    case DEPI_BIAS_RESID: if (ln) throw Error(OHW_E_INVALID_ARG, "dec_gemm: no LN variant"); shape = dec_gemm_pick<T, DEPI_BIAS_RESID, false>(p, s); break;
+    case DEPI_LOGITS: if (ln) throw Error(OHW_E_INVALID_ARG, "dec_gemm: no LN variant"); shape = dec_gemm_pick<T, DEPI_LOGITS, false>(p, s); break;
     default: throw Error(OHW_E_INVALID_ARG, "dec_gemm: unknown epilogue");
   }
   HIP_CHECK(hipGetLastError());
+  return shape;
 }
 
 // One wave, one (row, head).  Keys are processed in chunks of 64: lane j owns key (chunk*64 + j) for the
@@ -769,7 +772,7 @@ __global__ __launch_bounds__(64) void self_attn_kernel(const T* __restrict__ q, 
   TRACE(2, 3);
 }
 template <typename T>
-void launch_self_attn(const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past, void* out, int M, int n_new,
+int launch_self_attn(const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past, void* out, int M, int n_new,
                       int n_head, int n_ctx, hipStream_t s, const int32_t* kv_slot) {
   if (kv_slot)
     hipLaunchKernelGGL((self_attn_kernel<T, true>), dim3(n_head, M), dim3(64), 0, s, (const T*)q, (const T*)k_cache, (const T*)v_cache, n_past,
@@ -778,6 +781,7 @@ void launch_self_attn(const void* q, const void* k_cache, const void* v_cache, c
     hipLaunchKernelGGL((self_attn_kernel<T, false>), dim3(n_head, M), dim3(64), 0, s, (const T*)q, (const T*)k_cache, (const T*)v_cache, n_past,
                        (T*)out, n_new, n_head, n_ctx, kv_slot);
   HIP_CHECK(hipGetLastError());
+  return kv_slot ? SA_SLOTS : SA_PLAIN;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1030,7 +1034,7 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_rows_kernel(const T* __
 }
 
 template <typename T>
-void launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, int M, int n_new, int n_head, int t_len, float* partials,
+int launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, int M, int n_new, int n_head, int t_len, float* partials,
                        unsigned* tickets, int max_split_rows, const int32_t* done, hipStream_t s, int kv_group, bool batch_invariant) {
   // batch_invariant: the kernel variant (and with it the order of the softmax reduction) is picked from n_new alone, never
   // from the number of rows, so a window's result does not depend on how many windows share its batch
@@ -1047,7 +1051,7 @@ void launch_cross_attn(const void* q, const void* xk, const void* xv, void* out,
       hipLaunchKernelGGL((cross_attn_kernel<T>), dim3(n_head, M, ks), dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, kv_group,
                          n_head, t_len, partials, tickets, done);
       HIP_CHECK(hipGetLastError());
-      return;
+      return XA_GROUP_SPLIT;
     }
     const dim3 grid(n_head, M / kv_group);
     switch (kv_group) {
@@ -1057,7 +1061,7 @@ void launch_cross_attn(const void* q, const void* xk, const void* xv, void* out,
       default: hipLaunchKernelGGL((cross_attn_rows_kernel<T, 5>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done); break;
     }
     HIP_CHECK(hipGetLastError());
-    return;
+    return XA_GROUP2 + (kv_group - 2);
   }
   // fewer (row, head) pairs than two per CU: cut the keys (at most 8 slices, each at least a few hundred keys)
   int ks = 1;
@@ -1071,11 +1075,12 @@ void launch_cross_attn(const void* q, const void* xk, const void* xv, void* out,
     else if (n_new == 3) hipLaunchKernelGGL((cross_attn_rows_kernel<T, 3>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done);
     else hipLaunchKernelGGL((cross_attn_rows_kernel<T, 4>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done);
     HIP_CHECK(hipGetLastError());
-    return;
+    return XA_ROWS2 + (n_new - 2);
   }
   hipLaunchKernelGGL((cross_attn_kernel<T>), dim3(n_head, M, ks), dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_new,
                      n_head, t_len, partials, tickets, done);
   HIP_CHECK(hipGetLastError());
+  return ks > 1 ? XA_SPLIT : XA_PLAIN;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1885,10 +1890,10 @@ void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_window
 }
 
 #define INST(T) \
-  template void launch_dec_gemm<T>(const DecGemmParams&, int, hipStream_t); \
+  template int launch_dec_gemm<T>(const DecGemmParams&, int, hipStream_t); \
   template void launch_embed<T>(const void*, const float*, const int32_t*, const int32_t*, float*, void*, float*, int, int, int, hipStream_t); \
-  template void launch_self_attn<T>(const void*, const void*, const void*, const int32_t*, void*, int, int, int, int, hipStream_t, const int32_t*); \
-  template void launch_cross_attn<T>(const void*, const void*, const void*, void*, int, int, int, int, float*, unsigned*, int, const int32_t*, hipStream_t, int, bool);
+  template int launch_self_attn<T>(const void*, const void*, const void*, const int32_t*, void*, int, int, int, int, hipStream_t, const int32_t*); \
+  template int launch_cross_attn<T>(const void*, const void*, const void*, void*, int, int, int, int, float*, unsigned*, int, const int32_t*, hipStream_t, int, bool);
 INST(bf16_t)
 INST(f16_t)
 #undef INST

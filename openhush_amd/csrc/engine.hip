@@ -94,6 +94,15 @@ static int dec_ksplit_long() { return env_int("OHW_DEC_KSPLIT_LONG", 1, 1, DEC_K
 static int dec_ksplit_short() { return env_int("OHW_DEC_KSPLIT_SHORT", 1, 1, DEC_KSPLIT_MAX); }
 
 
+// the decoder GEMMs and the forms of their input, as ohw_dbg_counter names them ("dec_gemm.<gemm>[.<form>].<NT>x<MT>")
+enum DecTallyGemm { DT_QKV, DT_O, DT_XQ, DT_XO, DT_FC1, DT_FC2, DT_LOGITS, DT_GEMMS };
+enum DecTallyForm { DT_PLAIN, DT_LN, DT_PN, DT_KSPLIT, DT_FORMS };
+static const char* const kDecTallyGemm[DT_GEMMS] = {"qkv", "o", "xq", "xo", "fc1", "fc2", "logits"};
+static const char* const kDecTallyForm[DT_FORMS] = {"", ".ln", ".pn", ".ks"};
+static const char* const kDecTallyShape[DG_N_SHAPES] = {"1x1", "2x1", "1x2", "2x2", "4x2"};
+static const char* const kXattnTally[XA_N_VARIANTS] = {"plain", "split", "rows2", "rows3", "rows4", "group2", "group3", "group4", "group5", "group_split"};
+static const char* const kSelfAttnTally[4] = {"plain", "slots", "fused", "fused_slots"};
+
 struct ohw_state {
   ohw_ctx* ctx = nullptr;
   int max_batch = 0;
@@ -142,6 +151,11 @@ struct ohw_state {
   int n_cu = 0;
   int step_captures = 0;
   int beam_captures = 0;            // graph pairs captured so far (ohw_dbg_counter: a second call with the same key adds none)
+  // which decoder kernel instantiations run_decoder_step launched (ohw_dbg_counter "dec_gemm.*", "xattn.*", "self_attn.*"):
+  // counted on the host, so a captured step counts once, at its capture
+  int64_t tally_gemm[DT_GEMMS][DT_FORMS][DG_N_SHAPES] = {};
+  int64_t tally_xattn[XA_N_VARIANTS] = {};
+  int64_t tally_self[4] = {};      // SA_PLAIN, SA_SLOTS, then the same two run inside the QKV launch (OHW_DEC_FUSE_ATTN)
   DevBuf tok_lp, nosp_prob;        // per-token log-probabilities [B][max_tokens + 1], no-speech probability [B]
   DevBuf logit_bias;               // optional f32 [n_vocab] (ohw_state_set_logit_bias)
   std::vector<float> bias_host;    // the same on the host: the temperature ladder samples there (host_engine.cpp)
@@ -417,14 +431,14 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     DecGemmParams lp{};
     lp.x = st->dy.p; lp.w = c->emb.p; lp.bias = nullptr; lp.out = st->logits.p; lp.cu_budget = st->stream_cus;
     lp.M = M; lp.N = hp.n_vocab; lp.K = d; lp.n_new = 1; lp.ld_out = st->logits_ld; lp.n_past = n_past; lp.d_model = d; lp.n_head = H; lp.n_ctx = C;
-    launch_dec_gemm<T>(lp, DEPI_LOGITS, s);
+    ++st->tally_gemm[DT_LOGITS][DT_PLAIN][launch_dec_gemm<T>(lp, DEPI_LOGITS, s)];
     return;
   }
   launch_embed<T>(c->emb.p, c->dec_pos.as<float>(), tok_src ? tok_src : st->step_tok.as<int32_t>(), n_past, st->dx.as<float>(),
                   pn ? st->dx16.p : nullptr, pn ? st->xstat.as<float>() : nullptr, M, n_new, d, s);
   const int64_t kv_layer = (int64_t)st->max_batch * H * C * 64;      // elements per K (or V) cache of one layer
   const int64_t xkv_slab = (int64_t)(B / kv_group) * H * Tn * 64;    // cross K/V slab (batch of the last encode)
-  auto gemm = [&](const void* x, const LayerNormW* ln, const DevBuf& w, const DevBuf& bias, void* out, int N, int K, int epi, int64_t ld,
+  auto gemm = [&](int which, const void* x, const LayerNormW* ln, const DevBuf& w, const DevBuf& bias, void* out, int N, int K, int epi, int64_t ld,
                   const DevBuf* wsum = nullptr) {
     DecGemmParams p{};
     p.x = x; p.w = w.p; p.bias = bias.p ? bias.as<float>() : nullptr; p.out = out;
@@ -446,7 +460,8 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
                   : epi == DEPI_LOGITS ? OHW_PROF_DEC_GEMM_LOGITS : OHW_PROF_DEC_GEMM;
     // algorithmic bytes: the weights once per launch (the m-blocks of a prompt pass share them through L2)
     ProfScope ps(st, cls, 2.0 * (double)N * K);
-    launch_dec_gemm<T>(p, epi, s);
+    const int form = p.ln ? DT_LN : p.pn ? DT_PN : p.ksplit > 1 ? DT_KSPLIT : DT_PLAIN;
+    ++st->tally_gemm[which][form][launch_dec_gemm<T>(p, epi, s)];
   };
   // OHW_DEC_FUSE_ATTN=1: single-token steps of at most 16 rows run their self-attention inside the QKV launch (decode.hip,
   // self_attn_row<COH>): one launch less per layer, the same bits - and 1.6 us per layer SLOWER (large-v3, one row: 77.3 against
@@ -466,27 +481,28 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
       p.k_cache = kc; p.v_cache = vc; p.n_past = n_past; p.d_model = d; p.n_head = H; p.n_ctx = C;
       if (fuse_attn) { p.attn_ticket = st->attn_ticket.as<unsigned>(); p.attn_out = st->da.p; p.attn_slots = kv_slot; p.kv_bytes = kv_layer * 2; }
       ProfScope ps(st, OHW_PROF_DEC_GEMM_QKV, 2.0 * (3.0 * d * d));
-      launch_dec_gemm<T>(p, DEPI_QKV, s);
+      ++st->tally_gemm[DT_QKV][p.pn ? DT_PN : DT_LN][launch_dec_gemm<T>(p, DEPI_QKV, s)];
     }
-    if (!fuse_attn) launch_self_attn<T>(st->dq.p, kc, vc, n_past, st->da.p, M, n_new, H, C, s, kv_slot);
-    gemm(st->da.p, nullptr, w.wo, w.bo, st->dx.p, d, d, DEPI_BIAS_RESID, d);
-    gemm(st->dx.p, &w.lnx, w.wxq, w.bxq, st->dq.p, d, d, DEPI_BIAS_T, d, &w.sxq);
+    if (!fuse_attn) ++st->tally_self[launch_self_attn<T>(st->dq.p, kc, vc, n_past, st->da.p, M, n_new, H, C, s, kv_slot)];
+    else ++st->tally_self[2 + (kv_slot ? SA_SLOTS : SA_PLAIN)];
+    gemm(DT_O, st->da.p, nullptr, w.wo, w.bo, st->dx.p, d, d, DEPI_BIAS_RESID, d);
+    gemm(DT_XQ, st->dx.p, &w.lnx, w.wxq, w.bxq, st->dq.p, d, d, DEPI_BIAS_T, d, &w.sxq);
     {
       // algorithmic bytes: K and V of every (query row, head); the prompt pass streams them once per (window, head)
       // for all its rows (cross_attn_rows_kernel: same condition as launch_cross_attn)
       const bool rows_path = n_new >= 2 && n_new <= 4 && ((int64_t)B * H >= 256 || st->batch_invariant);
       ProfScope psx(st, OHW_PROF_DEC_XATTN, 2.0 * 2.0 * (double)(kv_group > 1 ? B / kv_group : rows_path ? B : M) * H * Tn * 64.0);
-      launch_cross_attn<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab,
-                           st->da.p, M, n_new, H, Tn, st->xa_part.as<float>(), st->xa_ticket.as<unsigned>(), st->xa_rows,
-                           kv_group > 1 ? win_done : (st->skip_done ? st->done.as<int32_t>() : nullptr), s, kv_group, st->batch_invariant);
+      ++st->tally_xattn[launch_cross_attn<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab,
+                                             st->da.p, M, n_new, H, Tn, st->xa_part.as<float>(), st->xa_ticket.as<unsigned>(), st->xa_rows,
+                                             kv_group > 1 ? win_done : (st->skip_done ? st->done.as<int32_t>() : nullptr), s, kv_group, st->batch_invariant)];
     }
-    gemm(st->da.p, nullptr, w.wxo, w.bxo, st->dx.p, d, d, DEPI_BIAS_RESID, d);
-    gemm(st->dx.p, &w.ln2, w.w1, w.b1, st->df.p, 4 * d, d, DEPI_BIAS_GELU_T, 4 * d, &w.s1);
-    gemm(st->df.p, nullptr, w.w2, w.b2, st->dx.p, d, 4 * d, DEPI_BIAS_RESID, d);
+    gemm(DT_XO, st->da.p, nullptr, w.wxo, w.bxo, st->dx.p, d, d, DEPI_BIAS_RESID, d);
+    gemm(DT_FC1, st->dx.p, &w.ln2, w.w1, w.b1, st->df.p, 4 * d, d, DEPI_BIAS_GELU_T, 4 * d, &w.s1);
+    gemm(DT_FC2, st->df.p, nullptr, w.w2, w.b2, st->dx.p, d, 4 * d, DEPI_BIAS_RESID, d);
   }
   launch_layernorm<T>(st->dx.as<float>(), c->dec_ln.g.as<float>(), c->dec_ln.b.as<float>(), st->dy.p, M, d, s, true);
   DevBuf none;
-  gemm(st->dy.p, nullptr, c->emb, none, st->logits.p, hp.n_vocab, d, DEPI_LOGITS, st->logits_ld);
+  gemm(DT_LOGITS, st->dy.p, nullptr, c->emb, none, st->logits.p, hp.n_vocab, d, DEPI_LOGITS, st->logits_ld);
 }
 
 // after a stream synchronisation: did a workgroup of a persistent decoder step give up waiting (decode_persist.hip)?  Loud.
@@ -1289,6 +1305,15 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "step_captures") return st->step_captures;
   if (n == "step_graphs") return (int)st->step_graphs.size();
   if (n == "persist_launches") return st->persist_launches;
+  auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
+  for (int g = 0; g < DT_GEMMS; ++g)
+    for (int f = 0; f < DT_FORMS; ++f)
+      for (int k = 0; k < DG_N_SHAPES; ++k)
+        if (n == std::string("dec_gemm.") + kDecTallyGemm[g] + kDecTallyForm[f] + "." + kDecTallyShape[k]) return clamp(st->tally_gemm[g][f][k]);
+  for (int v = 0; v < XA_N_VARIANTS; ++v)
+    if (n == std::string("xattn.") + kXattnTally[v]) return clamp(st->tally_xattn[v]);
+  for (int v = 0; v < 4; ++v)
+    if (n == std::string("self_attn.") + kSelfAttnTally[v]) return clamp(st->tally_self[v]);
   return OHW_E_INVALID_ARG;
 }
 

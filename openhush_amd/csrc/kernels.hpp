@@ -91,7 +91,10 @@ struct DecGemmParams {
   const int32_t* attn_slots;        // beam search: i32 [rows][n_ctx] (launch_self_attn's kv_slot), else null
   int64_t kv_bytes;                 // bytes of one layer's K (or V) cache: bound of the kernel's buffer descriptors
 };
-template <typename T> void launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s);
+// the launchers below return which instantiation they launched (the state tallies them: ohw_dbg_counter); the pick itself
+// does not depend on the tally
+enum DecGemmShape { DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_N_SHAPES };   // n-tiles x m-tiles per workgroup
+template <typename T> int launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s);
 
 // x f32 [M][d] = token_embedding[tok[m]] + pos_emb[n_past[m / n_new] + m % n_new]
 // x16 / stat (may be null): the 16-bit tiled copy and the per-16-column statistics of the post-norm path
@@ -99,13 +102,18 @@ template <typename T> void launch_embed(const void* emb_tiled, const float* pos,
                                         float* x, void* x16, float* stat, int M, int n_new, int d, hipStream_t s);
 // causal self-attention of the new tokens against the cache.  q T [M][d] -> out T, activation-tile order
 // kv_slot (beam search, else null): i32 [rows][n_ctx], the cache row that holds position j of a row's sequence
-template <typename T> void launch_self_attn(const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past,
+enum SelfAttnVariant { SA_PLAIN, SA_SLOTS };
+template <typename T> int launch_self_attn(const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past,
                                             void* out, int M, int n_new, int n_head, int n_ctx, hipStream_t s, const int32_t* kv_slot = nullptr);
 // cross-attention: q T [M][d]; cross K/V head-major T [B][H][t_len][64] of this layer -> out T, activation-tile order
 // partials / tickets (may be null): scratch for cutting the keys of a (row, head) over up to XA_MAX_SPLIT workgroups when
 // M <= max_split_rows leaves most CUs idle: f32 [max_split_rows][n_head][XA_MAX_SPLIT][68], u32 [max_split_rows][n_head] (zero)
 constexpr int XA_MAX_SPLIT = 8;
-template <typename T> void launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, int M, int n_new,
+// PLAIN: cross_attn_kernel, one workgroup per (row, head); SPLIT: the same with the keys cut over gridDim.z > 1 workgroups;
+// ROWS<n>: cross_attn_rows_kernel<n> for n new tokens per window; GROUP<k>: the same for k beams per window; GROUP_SPLIT: beams
+// through the split cross_attn_kernel
+enum XattnVariant { XA_PLAIN, XA_SPLIT, XA_ROWS2, XA_ROWS3, XA_ROWS4, XA_GROUP2, XA_GROUP3, XA_GROUP4, XA_GROUP5, XA_GROUP_SPLIT, XA_N_VARIANTS };
+template <typename T> int launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, int M, int n_new,
                                              int n_head, int t_len, float* partials, unsigned* tickets, int max_split_rows,
                                              const int32_t* done /* [B] or null: windows whose rows are skipped */, hipStream_t s,
                                              int kv_group = 1 /* beam search: consecutive rows that share one window's K/V */,

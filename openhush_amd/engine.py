@@ -581,7 +581,8 @@ class State:
         _check(lib().ohw_state_set_stream(self.h, C.c_void_p(stream_ptr or 0)))
 
     def counter(self, name: str) -> int:
-        """ohw_dbg_counter: step_captures, beam_captures, step_graphs, beam_graphs"""
+        """ohw_dbg_counter: step_captures, beam_captures, step_graphs, beam_graphs, persist_launches, and the decoder
+        step's kernel-variant tally (dec_gemm.*, xattn.*, self_attn.*: the names are listed in include/ohw.h)"""
         v = int(lib().ohw_dbg_counter(self.h, name.encode()))
         if v < 0:
             raise ValueError(name)
