@@ -44,7 +44,9 @@ enum {
 
 /* compute dtype of weights/activations fed to MFMA (accumulation, LN, softmax, logits: fp32) */
 /* OHW_DTYPE_AUTO (ohw_ctx_create / ohw_engine_new / ohw_pool_create only): f16 when the file stores f16 weights (ftype 1, the
- * stock ggml-*.bin files: the weights stay exact), bf16 for f32 files.  BASELINE.json's bench dtype is bf16, chosen explicitly. */
+ * stock ggml-*.bin files: the weights stay exact), bf16 for f32 files.  BASELINE.json's bench dtype is bf16, chosen explicitly.
+ * A quantised file (ftype 2, 3, 7, 8, 9) picks f16 as well: ggml expands its blocks to f16 / f32, and bf16 would drop three
+ * more mantissa bits of every expanded weight for nothing. */
 enum { OHW_DTYPE_AUTO = -1, OHW_DTYPE_BF16 = 0, OHW_DTYPE_F16 = 1 };
 
 /* log-mel tail convention */
@@ -80,6 +82,10 @@ int ohw_validate_audio(const float* samples, int64_t n, uint32_t sample_rate, oh
 /* ---- model: replaces WhisperContext::new_with_params (reference src/engine/whisper.rs:156-160) - */
 /* model_path: a ggml `ggml-*.bin` file (reference src/engine/whisper.rs:71-79).  A missing file   */
 /* returns OHW_E_MODEL_NOT_FOUND before any device work (reference :141-154, test :984-997).       */
+/* Tensors may be f32, f16 or block-quantised Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 (ttype 0, 1, 2, 3, 6, 7, 8; a file may mix):  */
+/* quantised blocks are uploaded as stored and expanded on the device at load, so the resident weights, their footprint   */
+/* and the throughput are those of an f16 file.  The header's ftype word is ftype + 1000 * quantisation version;          */
+/* ohw_hparams.ftype holds the reduced ftype.  k-quants and quantisation versions other than 2: OHW_E_LOAD_FAILED.        */
 int ohw_ctx_create(const char* model_path, int device, int dtype, ohw_ctx** out);
 /* procedural weights generated on the device (tests / bench; openhush_amd/synth.py is the spec)  */
 int ohw_ctx_create_synthetic(const ohw_hparams* hp, uint32_t seed, int device, int dtype, ohw_ctx** out);
@@ -549,6 +555,12 @@ int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int6
 /* 64-bit digest of the index-th resident weight buffer (engine layout); returns OHW_E_INVALID_ARG  */
 /* past the last buffer.  Lets tests prove "synthetic ctx == ctx loaded from the synthetic file".  */
 int ohw_ctx_weight_digest(const ohw_ctx* ctx, int index, char* name_out /* >= 64 bytes */, uint64_t* digest);
+/* ggml block dequantisation: `blocks` holds n / 32 blocks of ttype 2 (Q4_0, 18 B), 3 (Q4_1, 20 B), 6 (Q5_0, 22 B),       */
+/* 7 (Q5_1, 24 B) or 8 (Q8_0, 34 B) as stored in a model file, out receives n floats; n % 32 == 0.  The host twin needs no  */
+/* device and defines the result bit for bit (fp32 after widening d / m, multiply then add, no fused multiply-add); the   */
+/* dbg entry copies the blocks to `device`, runs the loader's kernel on them and copies the result back.                   */
+int ohw_dequantize_host(int ttype, const void* blocks, int64_t n, float* out);
+int ohw_dbg_dequantize(int device, int ttype, const void* blocks_host, int64_t n, float* out_host);
 /* kernel-level entry points on raw device pointers (tests against a torch fp32 reference)         */
 int ohw_dbg_gemm(int dtype, const void* A, const void* W, const float* bias, void* out, int64_t M, int64_t N,
                  int64_t K, int epilogue, void* stream);

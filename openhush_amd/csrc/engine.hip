@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "attention.hpp"
+#include "dequant.hpp"
 #include "gemm.hpp"
 #include "kernels.hpp"
 #include "model.hpp"
@@ -24,6 +25,7 @@ namespace ohw {
 ohw_ctx* ctx_from_file(const char* path, int device, int dtype);
 ohw_ctx* ctx_synthetic(const ohw_hparams* hp, uint32_t seed, int device, int dtype);
 ohw_ctx* ctx_shell(const ohw_hparams* hp, int device, int dtype);
+void select_device(int device);
 
 thread_local std::string g_last_error;
 
@@ -1618,6 +1620,23 @@ int ohw_dbg_gemm(int dtype, const void* A, const void* W, const float* bias, voi
       using T = std::remove_pointer_t<decltype(tag)>;
       launch_gemm<T>(g, epilogue, (hipStream_t)stream);
     });
+  });
+}
+
+int ohw_dbg_dequantize(int device, int ttype, const void* blocks_host, int64_t n, float* out_host) {
+  return guard([&] {
+    const int bs = quant_block_bytes(ttype);
+    if (bs == 0 || !blocks_host || !out_host || n <= 0 || n % QK != 0 || n > ((int64_t)1 << 31))
+      throw Error(OHW_E_INVALID_ARG, "dbg_dequantize: ttype must be 2, 3, 6, 7 or 8 and n a positive multiple of 32 (at most 2^31)");
+    select_device(device);
+    const size_t raw_bytes = (size_t)(n / QK) * bs;
+    DevBuf raw, out;
+    raw.alloc(raw_bytes);
+    out.alloc((size_t)n * 4);
+    HIP_CHECK(hipMemcpy(raw.p, blocks_host, raw_bytes, hipMemcpyHostToDevice));
+    launch_dequant_blocks(ttype, raw.p, out.as<float>(), n, nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    HIP_CHECK(hipMemcpy(out_host, out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   });
 }
 

@@ -8,6 +8,9 @@ namespace ohw {
 // dst[i] = value of the procedural generator (openhush_amd/synth.py) for flat index i
 void launch_synth_fill(float* dst, int64_t n, uint32_t key, float scale, float offset, int round_f16, hipStream_t s);
 void launch_f16_to_f32(const void* src_f16, float* dst, int64_t n, hipStream_t s);
+// ggml block-quantised tensor (dequant.hpp: ttype 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0) -> f32; raw: n / 32 blocks as
+// stored in the file, 4-byte aligned; throws OHW_E_INVALID_ARG for another ttype or n % 32 != 0 (dequant.hip)
+void launch_dequant_blocks(int ttype, const void* raw_blocks, float* dst, int64_t n, hipStream_t s);
 // plain row-major convert: dst T [rows][cols] (dst row stride ld_dst) from src f32 [rows][cols]
 template <typename T> void launch_convert_rows(const float* src, void* dst, int64_t rows, int64_t cols, int64_t ld_dst, hipStream_t s);
 // conv weight [d_out][c_in][3] f32 -> T [d_out][3][c_pad]

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <memory>
 
+#include "dequant.hpp"
 #include "kernels.hpp"
 #include "model.hpp"
 
@@ -275,7 +276,7 @@ static void upload_front_end(ohw_ctx* c, const std::vector<float>& filters) {
   HIP_CHECK(hipMemcpy(c->window.p, win.data(), win.size() * 4, hipMemcpyHostToDevice));
 }
 
-static void select_device(int device) {
+void select_device(int device) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n <= 0) throw Error(OHW_E_NO_GPU, "no HIP device visible (this library has no CPU fallback)");
@@ -300,6 +301,9 @@ struct FileReader {
   template <typename U> U get() { U v; read(&v, sizeof v); return v; }
 };
 
+// header ftype ("mostly" type of the 2-D weights): 2 Q4_0, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1
+static bool file_ftype_is_quantised(int32_t ftype) { return ftype == 2 || ftype == 3 || ftype == 7 || ftype == 8 || ftype == 9; }
+
 template <typename T>
 static void load_file_typed(ohw_ctx* c, FileReader& fr) {
   hipStream_t s = nullptr;
@@ -310,21 +314,39 @@ static void load_file_typed(ohw_ctx* c, FileReader& fr) {
   for (;;) {
     int32_t hdr[3];
     if (fread(hdr, 4, 3, fr.f) != 3) break;
-    if (hdr[0] < 1 || hdr[0] > 4 || hdr[1] <= 0 || hdr[1] > 255 || (hdr[2] != 0 && hdr[2] != 1))
-      throw Error(OHW_E_LOAD_FAILED, "unsupported tensor header (only f32 / f16 tensors are supported)");
+    // each tensor goes by its own ttype, never by the header's ftype: a quantised file keeps conv weights, biases, LayerNorms
+    // and positional embeddings f16 / f32, and a file may mix
+    const int qbytes = quant_block_bytes(hdr[2]);
+    if (hdr[0] < 1 || hdr[0] > 4 || hdr[1] <= 0 || hdr[1] > 255)
+      throw Error(OHW_E_LOAD_FAILED, "unsupported tensor header");
+    if (hdr[2] != TT_F32 && hdr[2] != TT_F16 && qbytes == 0)
+      throw Error(OHW_E_LOAD_FAILED, "unsupported tensor type " + std::to_string(hdr[2]) +
+                                         " (f32, f16, Q4_0, Q4_1, Q5_0, Q5_1 and Q8_0 tensors are supported; k-quants are not supported)");
     int32_t dims_r[4] = {1, 1, 1, 1};
     fr.read(dims_r, 4 * (size_t)hdr[0]);
     std::string name((size_t)hdr[1], '\0');
     fr.read(&name[0], (size_t)hdr[1]);
     std::vector<int64_t> dims;
     int64_t n = 1;
-    for (int i = hdr[0] - 1; i >= 0; --i) { dims.push_back(dims_r[i]); n *= dims_r[i]; }
-    if (n <= 0 || n > ((int64_t)1 << 31)) throw Error(OHW_E_LOAD_FAILED, "tensor " + name + " has a bad size");
-    const size_t esz = hdr[2] == 1 ? 2 : 4;
-    host.resize((size_t)n * esz);
+    for (int i = hdr[0] - 1; i >= 0; --i) {
+      if (dims_r[i] <= 0) throw Error(OHW_E_LOAD_FAILED, "tensor " + name + " has a bad size");
+      dims.push_back(dims_r[i]);
+      n *= dims_r[i];
+      if (n > ((int64_t)1 << 31)) throw Error(OHW_E_LOAD_FAILED, "tensor " + name + " has a bad size");
+    }
+    // blocks of 32 values run along the fastest dimension (the file's first)
+    if (qbytes && dims_r[0] % QK != 0)
+      throw Error(OHW_E_LOAD_FAILED, "quantised tensor " + name + ": its first dimension (" + std::to_string(dims_r[0]) +
+                                         ") is not a multiple of the block size 32");
+    host.resize(qbytes ? (size_t)(n / QK) * qbytes : (size_t)n * (hdr[2] == TT_F16 ? 2 : 4));
     fr.read(host.data(), host.size());
     if (staging.bytes < (size_t)n * 4) staging.alloc((size_t)n * 4);
-    if (hdr[2] == 1) {
+    if (qbytes) {
+      // uploaded as stored (0.28 - 0.53 of the f16 bytes), expanded on the device
+      if (raw.bytes < host.size()) raw.alloc(host.size());
+      HIP_CHECK(hipMemcpy(raw.p, host.data(), host.size(), hipMemcpyHostToDevice));
+      launch_dequant_blocks(hdr[2], raw.p, staging.as<float>(), n, s);
+    } else if (hdr[2] == TT_F16) {
       if (raw.bytes < (size_t)n * 2) raw.alloc((size_t)n * 2);
       HIP_CHECK(hipMemcpy(raw.p, host.data(), host.size(), hipMemcpyHostToDevice));
       launch_f16_to_f32(raw.p, staging.as<float>(), n, s);
@@ -349,10 +371,23 @@ ohw_ctx* ctx_from_file(const char* path, int device, int dtype) {
   if (fr.get<uint32_t>() != 0x67676d6cu) throw Error(OHW_E_LOAD_FAILED, "not a ggml model file (bad magic)");
   std::unique_ptr<ohw_ctx> c(new ohw_ctx());
   fr.read(&c->hp, sizeof c->hp);
+  // whisper.cpp stores ftype + 1000 * quantisation version in the header word; ohw_hparams keeps the reduced ftype
+  const int32_t ftype_word = c->hp.ftype;
+  const int32_t qntvr = ftype_word / 1000;
+  c->hp.ftype = ftype_word % 1000;
+  const bool quantised = file_ftype_is_quantised(c->hp.ftype);
+  if (c->hp.ftype >= 10 && c->hp.ftype <= 14)
+    throw Error(OHW_E_LOAD_FAILED, "unsupported ftype " + std::to_string(c->hp.ftype) + ": k-quants are not supported");
+  if (ftype_word < 0 || (c->hp.ftype != 0 && c->hp.ftype != 1 && !quantised))
+    throw Error(OHW_E_LOAD_FAILED, "unsupported ftype " + std::to_string(c->hp.ftype) +
+                                       " (supported: 0 f32, 1 f16, 2 Q4_0, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1)");
+  if (quantised && qntvr != 2)
+    throw Error(OHW_E_LOAD_FAILED, "unsupported quantisation version " + std::to_string(qntvr) + " (only version 2 is supported)");
   check_hparams(c->hp);
   // AUTO: the file's own weight precision.  The stock ggml-*.bin files store f16 (ftype 1): f16 keeps them EXACT (bf16 would
   // drop 3 mantissa bits of every weight for +1 % throughput); f32 files (ftype 0) get bf16's range
-  if (dtype == OHW_DTYPE_AUTO) dtype = c->hp.ftype == 1 ? OHW_DTYPE_F16 : OHW_DTYPE_BF16;
+  // a quantised file: f16 too (ggml expands its blocks to f16 / f32; bf16 would drop three more mantissa bits for nothing)
+  if (dtype == OHW_DTYPE_AUTO) dtype = c->hp.ftype == 1 || quantised ? OHW_DTYPE_F16 : OHW_DTYPE_BF16;
   const int32_t n_mel = fr.get<int32_t>(), n_fft = fr.get<int32_t>();
   if (n_mel != c->hp.n_mels || n_fft != N_FREQ) throw Error(OHW_E_LOAD_FAILED, "mel filterbank shape mismatch");
   std::vector<float> filters((size_t)n_mel * n_fft);

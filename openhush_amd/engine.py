@@ -145,7 +145,7 @@ EXPORTS = [
     "ohw_state_set_persistent", "ohw_pool_broadcast_note", "ohw_pool_create_synthetic", "ohw_pool_set_force_len", "ohw_pool_set_schedule", "ohw_engine_set_force_len",
     "ohw_pool_set_decode_policy", "ohw_pool_n_devices", "ohw_pool_broadcast_kind", "ohw_pool_engine", "ohw_pool_free",
     "ohw_rng_uniforms", "ohw_rng_discard_draws", "ohw_sample_pass", "ohw_dbg_sample_t", "ohw_engine_set_fallback_device",
-    "ohw_pool_set_fallback_device",
+    "ohw_pool_set_fallback_device", "ohw_dequantize_host", "ohw_dbg_dequantize",
 ]
 
 
@@ -361,6 +361,8 @@ def lib():
         L.ohw_dbg_gemm.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp]
         L.ohw_dbg_attention.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
+        L.ohw_dequantize_host.argtypes = [C.c_int, vp, C.c_int64, fp]
+        L.ohw_dbg_dequantize.argtypes = [C.c_int, C.c_int, vp, C.c_int64, fp]
         _lib = L
     return _lib
 
@@ -404,6 +406,35 @@ def validate_audio(samples: np.ndarray, sample_rate: int) -> AudioInfo:
     if rc != 0:
         raise ValidationFailed(rc, "Audio validation failed: " + AUDIO_ERRORS.get(info.error, "?"), info)
     return info
+
+
+_QUANT_BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34}   # ttype -> bytes of one block of 32 values
+
+
+def _dequantize(ttype: int, blocks, n: int, device: Optional[int]) -> np.ndarray:
+    raw = np.ascontiguousarray(np.frombuffer(blocks, np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else blocks)
+    out = np.empty(max(int(n), 0), np.float32)
+    if ttype in _QUANT_BLOCK_BYTES and raw.nbytes < n // 32 * _QUANT_BLOCK_BYTES[ttype]:
+        raise ValueError("block data is shorter than n / 32 blocks")
+    src = C.c_void_p(raw.ctypes.data)
+    if device is None:
+        rc = lib().ohw_dequantize_host(ttype, src, n, _fp(out))
+        if rc != 0:
+            raise ValueError(f"ohw_dequantize_host: bad arguments (ttype {ttype}, n {n})")
+    else:
+        _check(lib().ohw_dbg_dequantize(device, ttype, src, n, _fp(out)))
+    return out
+
+
+def dequantize_host(ttype: int, blocks, n: int) -> np.ndarray:
+    """ohw_dequantize_host: n / 32 ggml blocks of ttype 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1 or 8 Q8_0 (bytes or a uint8 array) -> n floats;
+    no device needed"""
+    return _dequantize(ttype, blocks, n, None)
+
+
+def dbg_dequantize(ttype: int, blocks, n: int, device: int = 0) -> np.ndarray:
+    """ohw_dbg_dequantize: the same through the loader's kernel on `device`"""
+    return _dequantize(ttype, blocks, n, device)
 
 
 def lang_id_to_code(i: int) -> str:
