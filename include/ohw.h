@@ -401,6 +401,24 @@ int ohw_state_set_persistent(ohw_state* st, int on);
  * ohw_engine_transcribe turns it on for audio longer than one batch, which makes its schedules agree token for token. */
 int ohw_state_set_batch_invariant(ohw_state* st, int on);
 
+/* reduced audio context (whisper.cpp's whisper_full_params.audio_ctx, whisper-rs set_audio_ctx; the reference sets none,
+ * so the default is the full context).  With n_ctx = C, 1 <= C <= n_audio_ctx: conv1 sees mel frames 0 .. 2C-1 of the
+ * window with zero padding on both sides (frame 2C is padding, not audio), conv2 produces C rows and adds positional rows
+ * 0 .. C-1, the encoder and the cross-K/V projection run on C positions per window, cross K/V are stored packed
+ * [2L][B][H][C][64], and every decoder cross-attention reads C keys: encoder work, cross-K/V bytes and cross-attention
+ * bytes scale with the audio, not with the 30 s window.  The log-mel spectrogram (its clamp maximum too) does not change.
+ * 0 or n_audio_ctx = full context; a value outside 0..n_audio_ctx returns OHW_E_INVALID_ARG.  The setting holds for later
+ * ohw_mel*, ohw_encode*, ohw_decode*, ohw_greedy*, ohw_sample_pass, ohw_beam_search and ohw_detect_language calls; an
+ * encode under another context than the last ohw_mel* of the state, or a decode under another context than its last
+ * encode, returns OHW_E_INVALID_ARG (neither ever reads a stale image or stale K/V).  Buffers stay sized for n_audio_ctx. */
+int ohw_state_set_audio_ctx(ohw_state* st, int n_ctx);
+int ohw_state_audio_ctx(const ohw_state* st);   /* the context in effect, 1..n_audio_ctx (n_audio_ctx = full) */
+/* the context that covers n_samples of 16 kHz audio (host only, no device):
+ *     min(1500, round_up(ceil(n_samples / 320) + 32, 64))
+ * one encoder position is 320 samples; the 32 extra positions are 0.64 s of headroom behind the last sample, and the
+ * multiple of 64 matches the key block of the encoder's attention.  1.1 s -> 128, 5 s -> 320, more than 28.8 s -> 1500.     */
+int32_t ohw_audio_ctx_for(int64_t n_samples);
+
 /* per-stage device time of the last calls on this state, in milliseconds (reference logs the     */
 /* same split per job: src/queue/worker.rs:170-180)                                               */
 typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t decode_steps; } ohw_timings;
@@ -481,6 +499,12 @@ int ohw_engine_set_window_mode(ohw_engine* e, int mode);
  * that many tokens with end-of-text suppressed (ohw_sample_params.force_len; use with temperature_inc = 0: a forced sequence
  * fails whisper.cpp's acceptance test by construction); 0 (default) = the reference's behaviour.                         */
 int ohw_engine_set_force_len(ohw_engine* e, int n_tokens);
+/* reduced audio context of every window ohw_engine_transcribe runs (ohw_state_set_audio_ctx on the engine's own, pipeline
+ * and lane states): 0 (default) = off, the full context; n > 0 = that context for every window of every window mode and
+ * schedule - a transcribe in which some window holds samples past n * 320 fails with OHW_E_INVALID_ARG naming the window
+ * (audio is never dropped silently); -1 = auto: a recording that fits one window runs at ohw_audio_ctx_for(n_samples),
+ * anything longer at the full context.                                                                                   */
+int ohw_engine_set_audio_ctx(ohw_engine* e, int n);
 /* How audio of more than max_batch windows is overlapped on the device (the reference transcribes one buffer at a time,
  * src/queue/worker.rs:100-160; results are identical under every schedule):
  *   SEQUENTIAL  one batch after the other;
@@ -533,6 +557,7 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
  * disagree.  All three modes give the single engine's tokens: each device is handed the whole recording and cuts its own
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
+int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
 /* "" or why the RCCL broadcast was given up for peer copies.  After either kind every replica's weight buffers are compared
  * with device_ids[0]'s (64-bit digests); a mismatch fails ohw_pool_create with OHW_E_LOAD_FAILED naming the device.          */
 const char* ohw_pool_broadcast_note(const ohw_pool* p);
@@ -551,6 +576,7 @@ const char* ohw_last_error(void);
 int ohw_abi_version(void);
 /* copy an internal activation to the host as f32: what = "mel" [B][n_mels][3000], "conv1"        */
 /* [B][3000][d], "stem" / "block0" / "enc" [B][1500][d], "xk<l>" / "xv<l>" [B][1500][d]            */
+/* (under a reduced audio context C, "stem" / "block0" / "enc" / "xk<l>" / "xv<l>" are [B][C][d])    */
 int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int64_t out_elems);
 /* 64-bit digest of the index-th resident weight buffer (engine layout); returns OHW_E_INVALID_ARG  */
 /* past the last buffer.  Lets tests prove "synthetic ctx == ctx loaded from the synthetic file".  */
@@ -564,6 +590,12 @@ int ohw_dbg_dequantize(int device, int ttype, const void* blocks_host, int64_t n
 /* kernel-level entry points on raw device pointers (tests against a torch fp32 reference)         */
 int ohw_dbg_gemm(int dtype, const void* A, const void* W, const float* bias, void* out, int64_t M, int64_t N,
                  int64_t K, int epilogue, void* stream);
+/* the short-window encoder GEMM (gemm_small.hip: 64x64 tiles, four times the workgroups of ohw_dbg_gemm's kernel) with
+ * ohw_dbg_gemm's contract; N % 64 == 0, K % 64 == 0.  With OHW_GEMM_SMALL=1 (default 0: its on / off times have not been
+ * measured yet) run_encode selects it under a reduced audio context when the 128x128 grid would leave more than half the
+ * compute units idle; it gives ohw_dbg_gemm's bits.                                                                  */
+int ohw_dbg_gemm_small(int dtype, const void* A, const void* W, const float* bias, void* out, int64_t M, int64_t N,
+                       int64_t K, int epilogue, void* stream);
 int ohw_dbg_attention(int dtype, const void* qkv, void* out, int batch, int T, int n_head, void* stream);
 /* the DEVICE sampler on caller-supplied rows: logits [batch][n_vocab] (host), history [batch][hist_stride] with
  * n_hist[b] tokens sampled so far in the window.  tokens_out [batch]: the pick (end-of-text included);

@@ -149,9 +149,17 @@ def main(argv=None) -> int:
     t.add_argument("--mel", default="window", choices=["window", "recording"],
                    help="window (default): every 30 s cut is its own call; recording: the cuts are taken from the spectrogram of the whole "
                         "recording (one clamp maximum, real samples across the 30 s marks), as whisper.cpp computes it for one call")
+    t.add_argument("--audio-ctx", default="0", metavar="N|auto",
+                   help="reduced audio context (whisper.cpp's audio_ctx): 0 (default) the full 30 s context; N encoder positions per window "
+                        "(320 samples each; audio past them is an error, never dropped); auto: sized to a recording of at most 30 s")
     args = ap.parse_args(argv)
 
     from . import engine as E
+    try:
+        audio_ctx = E._audio_ctx_arg(args.audio_ctx)
+    except ValueError:
+        print(f"error: --audio-ctx takes 0, a positive number or 'auto', not '{args.audio_ctx}'", file=sys.stderr)
+        return 1
     if not os.path.isfile(args.file):            # reference src/main.rs:985-987 and tests/cli_integration.rs:262-269
         print(f"error: File not found: {args.file}", file=sys.stderr)
         return 1
@@ -161,6 +169,9 @@ def main(argv=None) -> int:
         print(f"error: {ex}", file=sys.stderr)
         return 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        if audio_ctx != 0:
+            print("error: --audio-ctx is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+            return 1
         return _transcribe_ranks(args, audio)
     use_gpu = args.device.lower() != "cpu"                    # reference src/main.rs:1037
     dev = int(args.device.split(":")[1]) if ":" in args.device else 0
@@ -170,6 +181,8 @@ def main(argv=None) -> int:
     print(f"Model loaded in {1e3 * (time.perf_counter() - t0):.0f}ms", file=sys.stderr)
     if args.mel == "recording":
         eng.set_window_mode(E.OHW_WINDOW_FIXED_RECORDING_MEL)
+    if audio_ctx != 0:
+        eng.set_audio_ctx(audio_ctx)
     t1 = time.perf_counter()
     res = eng.transcribe(audio)
     dt = time.perf_counter() - t1

@@ -110,6 +110,10 @@ struct ohw_state {
   int max_batch = 0;
   int enc_batch = 0;  // windows of the decode batch the cross K/V holds (the last ohw_encode, or the total of its slices)
   int mel_batch = 0;  // windows of the last ohw_mel
+  // reduced audio context (ohw_state_set_audio_ctx): encoder positions per window; 0 = the model's n_audio_ctx.  mel_ctx /
+  // enc_ctx: the context the mel image / the cross K/V were made under - an encode or a decode under another one is refused
+  int audio_ctx = 0, mel_ctx = 0, enc_ctx = 0;
+  bool gemm_small = false;  // OHW_GEMM_SMALL=1: short windows take the 64x64-tile encoder GEMM (gemm_small.hip; off until measured)
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   // front end
@@ -141,7 +145,7 @@ struct ohw_state {
   // one entry = the PAIR of graphs of a (windows, beam size, sampler parameters, CU budget, cross-attention variant) key: the
   // odd and the even iteration (the token-history and kv_slot double buffers alternate); made, looked up and evicted together,
   // so a call never holds an exec of an entry it then evicts
-  struct BeamGraph { hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr}; int windows = 0, K = 0, cus = 0; bool invariant = false, persist = false; SamplerParams spar; };
+  struct BeamGraph { hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr}; int windows = 0, K = 0, cus = 0, t_len = 0; bool invariant = false, persist = false; SamplerParams spar; };
   std::vector<BeamGraph> beam_graphs;
   // the persistent small-batch decoder step (decode_persist.hip): per-layer pointer table, granule arena, epoch / abort words
   DevBuf ps_layers, ps_gran, ps_words;
@@ -170,8 +174,9 @@ struct ohw_state {
   size_t prof_used = 0;
   double prof_work = 0.0;
   // hipGraph of one greedy iteration {feed sampled token, single-token decoder step, sampler}
-  // captured greedy iterations, one per (batch, sampler parameters, CU budget of the stream) seen; a handful at most
-  struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; bool invariant = false, persist = false, temp = false; SamplerParams spar{}; };
+  // captured greedy iterations, one per (batch, sampler parameters, CU budget of the stream, audio context: t_len is a
+  // captured kernel argument) seen; a handful at most
+  struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; int t_len = 0; bool invariant = false, persist = false, temp = false; SamplerParams spar{}; };
   bool batch_invariant = false;      // cross-attention variant picked from n_new alone (state_set_batch_invariant)
   std::vector<StepGraph> step_graphs;
   bool graphs_enabled = true;
@@ -212,6 +217,14 @@ struct Dispatch {
 };
 
 void persist_prepare(ohw_state* st);
+
+// encoder positions per window in effect (ohw_state_set_audio_ctx)
+int audio_ctx_of(const ohw_state* st) { return st->audio_ctx > 0 ? st->audio_ctx : st->ctx->hp.n_audio_ctx; }
+void check_decode_ctx(const ohw_state* st, const char* what) {
+  if (audio_ctx_of(st) != st->enc_ctx)
+    throw Error(OHW_E_INVALID_ARG, std::string(what) + ": the audio context changed since the last ohw_encode (" + std::to_string(st->enc_ctx) + " -> " +
+                                       std::to_string(audio_ctx_of(st)) + "): encode again");
+}
 
 void state_alloc(ohw_state* st) {
   const ohw_ctx* c = st->ctx;
@@ -255,6 +268,8 @@ void state_alloc(ohw_state* st) {
   st->graph_max_batch = env_int("OHW_GRAPH_MAX_BATCH", 32, 1, 1 << 20);
   st->persist = env_int("OHW_DEC_PERSIST", 0, 0, 1) != 0;
   st->fuse_attn = env_int("OHW_DEC_FUSE_ATTN", 0, 0, 1) != 0;
+  st->gemm_small = env_int("OHW_GEMM_SMALL", 0, 0, 1) != 0;
+  st->mel_ctx = st->enc_ctx = hp.n_audio_ctx;
   st->attn_ticket.alloc((size_t)hp.n_text_head * 4, true);
   (void)hipDeviceGetAttribute(&st->n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
   st->postnorm = env_int("OHW_DEC_POSTNORM", 0, 0, 1) != 0 && dec_ksplit_long() == 1 && dec_ksplit_short() == 1 && dt % 32 == 0;
@@ -329,7 +344,9 @@ void run_mel(ohw_state* st, const float* pcm_dev, int64_t stride, int batch, int
   p.filters = c->mel_filters.as<float>(); p.twiddle = c->twiddle.as<float>(); p.window = c->window.as<float>();
   p.logmel = st->logmel.as<float>(); p.max_bits = st->max_bits.as<int32_t>(); p.mel_t = st->mel_t.p;
   p.n_mels = c->hp.n_mels; p.batch = batch; p.mode = mode;
+  p.frame_limit = 2 * audio_ctx_of(st);
   launch_mel<T>(p, st->stream);
+  st->mel_ctx = audio_ctx_of(st);
 }
 
 // first / total: the cross K/V of these B windows go to windows [first, first + B) of a decode batch of `total` windows
@@ -338,15 +355,24 @@ void run_encode(ohw_state* st, int B, int first, int total) {
   const ohw_ctx* c = st->ctx;
   const ohw_hparams& hp = c->hp;
   hipStream_t s = st->stream;
-  const int64_t d = hp.n_audio_state, Tn = hp.n_audio_ctx, M = (int64_t)B * Tn;
+  // Tn: encoder positions per window - the state's audio context; conv1 runs the 2 * Tn frames conv2 reads (image row
+  // 1 + 2 * Tn, conv1's right padding, was written as zeros by the mel pass)
+  const int64_t d = hp.n_audio_state, Tn = audio_ctx_of(st), M = (int64_t)B * Tn;
+  // a short window: the 64x64-tile kernel where the 128x128 grid would leave more than half the compute units idle
+  const bool reduced = Tn < hp.n_audio_ctx;
+  auto pick_small = [&](GemmParams& q) {
+    const int64_t tiles128 = ((q.M + 127) / 128) * (q.N / 128);
+    q.small_m = reduced && st->gemm_small && q.N % 64 == 0 && q.K % 64 == 0 && 2 * tiles128 < (st->n_cu > 0 ? st->n_cu : 256) ? 1 : 0;
+  };
   GemmParams g{};
   // conv1 (k=3, pad 1) as a GEMM over overlapping rows of the time-major mel image
   g = GemmParams{};
   g.A = st->mel_t.p; g.W = c->conv1_w.p; g.bias = c->conv1_b.as<float>();
   g.out = (T*)st->c1.p + d;  // output row t -> image row 1 + t
-  g.M = (int64_t)B * CHUNK_FRAMES; g.N = d; g.K = 3 * MEL_CPAD;
-  g.lda = MEL_CPAD; g.a_batch_stride = (int64_t)MEL_ROWS * MEL_CPAD; g.rows_per_batch = CHUNK_FRAMES;
+  g.M = (int64_t)B * 2 * Tn; g.N = d; g.K = 3 * MEL_CPAD;
+  g.lda = MEL_CPAD; g.a_batch_stride = (int64_t)MEL_ROWS * MEL_CPAD; g.rows_per_batch = 2 * Tn;
   g.ldc = d; g.c_batch_stride = (int64_t)MEL_ROWS * d;
+  pick_small(g);
   { ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * g.M * g.N * g.K); launch_gemm<T>(g, EPI_BIAS_GELU_T, s); }
   // conv2 (k=3, stride 2, pad 1): row t reads image rows 2t .. 2t+2 of conv1's padded output
   g = GemmParams{};
@@ -355,6 +381,7 @@ void run_encode(ohw_state* st, int B, int first, int total) {
   g.M = M; g.N = d; g.K = 3 * d;
   g.lda = 2 * d; g.a_batch_stride = (int64_t)MEL_ROWS * d; g.rows_per_batch = Tn;
   g.ldc = d; g.c_batch_stride = Tn * d;
+  pick_small(g);
   { ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * g.M * g.N * g.K); launch_gemm<T>(g, EPI_GELU_POS_F32, s); }
   if (st->taps) HIP_CHECK(hipMemcpyAsync(st->tap_stem.p, st->h.p, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
 
@@ -362,6 +389,7 @@ void run_encode(ohw_state* st, int B, int first, int total) {
     GemmParams q{};
     q.A = A; q.W = W.p; q.bias = bias.as<float>(); q.out = out;
     q.M = M; q.N = N; q.K = K; q.lda = K; q.a_batch_stride = 0; q.rows_per_batch = M; q.ldc = N; q.c_batch_stride = 0;
+    pick_small(q);
     ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * q.M * q.N * q.K);
     launch_gemm<T>(q, epi, s);
   };
@@ -386,6 +414,7 @@ void run_encode(ohw_state* st, int B, int first, int total) {
   g.M = M; g.N = (int64_t)2 * hp.n_text_layer * hp.n_text_state; g.K = d;
   g.lda = d; g.a_batch_stride = Tn * d; g.rows_per_batch = Tn; g.ldc = 0; g.c_batch_stride = 0;
   g.d_model = hp.n_text_state; g.n_head = hp.n_text_head; g.t_len = (int)Tn; g.batch = total; g.batch_offset = first;
+  pick_small(g);
   { ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * g.M * g.N * g.K); launch_gemm<T>(g, EPI_CROSSKV_T, s); }
 }
 
@@ -398,7 +427,8 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
   const ohw_ctx* c = st->ctx;
   const ohw_hparams& hp = c->hp;
   hipStream_t s = st->stream;
-  const int d = hp.n_text_state, H = hp.n_text_head, C = hp.n_text_ctx, Tn = hp.n_audio_ctx, L = hp.n_text_layer;
+  // Tn: keys per cross-attention = the context of the last encode (the entries refuse a call under another one)
+  const int d = hp.n_text_state, H = hp.n_text_head, C = hp.n_text_ctx, Tn = st->enc_ctx, L = hp.n_text_layer;
   const int M = B * n_new;
   if (M > st->m_max) throw Error(OHW_E_INVALID_ARG, "decode: batch * n_new exceeds the state's capacity (8 tokens per window per call)");
   const int32_t* n_past = st->n_past.as<int32_t>();
@@ -414,6 +444,8 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     const int Wn = M / kv_group;
     q.layers = st->ps_layers.as<PersistLayer>(); q.L = L; q.M = M; q.group = kv_group; q.d = d; q.H = H; q.n_ctx = C; q.t_len = Tn;
     q.S = std::max(1, std::min(16, grid / std::max(1, Wn * H)));
+    // a short context: no slice without an 8-key group (at 1500 keys, 188 groups, every S <= 16 already passes)
+    for (const int ng = (Tn + 7) / 8; q.S > 1 && (q.S - 1) * ((ng + q.S - 1) / q.S) >= ng;) --q.S;
     const int kb_mlp = 4 * d / 32;
     int ns = std::max(1, std::min(4, (grid + d / 16 - 1) / (d / 16)));
     while (ns < 4 && (kb_mlp + ns - 1) / ns + 1 > 56) ++ns;
@@ -835,6 +867,8 @@ int ohw_mel_seek(ohw_state* st, const int32_t* seek_frames, int batch, float* me
     p.logmel = st->logmel.as<float>(); p.max_bits = st->rec_max.as<int32_t>(); p.mel_t = st->mel_t.p;
     p.n_mels = c->hp.n_mels; p.batch = batch; p.mode = OHW_MEL_ZERO_TAIL;
     p.offsets = st->rec_off.as<int64_t>(); p.n_total = st->rec_n; p.shared_max = 1; p.max_only = 0;
+    p.frame_limit = 2 * audio_ctx_of(st);
+    st->mel_ctx = audio_ctx_of(st);
     Dispatch::run(c->dtype, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
       launch_mel<T>(p, s);
@@ -854,6 +888,8 @@ int ohw_encode_slice(ohw_state* st, int batch, int first, int total) {
     if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
     if (batch < 1 || batch != st->mel_batch) throw Error(OHW_E_INVALID_ARG, "encode: batch must equal the batch of the last ohw_mel");
     if (first < 0 || total < first + batch || total > st->max_batch) throw Error(OHW_E_INVALID_ARG, "encode: slice exceeds the state's max_batch");
+    if (st->mel_ctx != audio_ctx_of(st)) throw Error(OHW_E_INVALID_ARG, "encode: the audio context changed since the last ohw_mel: run it again");
+    if (first > 0 && st->enc_ctx != audio_ctx_of(st)) throw Error(OHW_E_INVALID_ARG, "encode: the slices of one decode batch must share one audio context");
     HIP_CHECK(hipSetDevice(st->ctx->device));
     HIP_CHECK(hipEventRecord(st->ev[2], st->stream));
     Dispatch::run(st->ctx->dtype, [&](auto* tag) {
@@ -862,6 +898,7 @@ int ohw_encode_slice(ohw_state* st, int batch, int first, int total) {
     });
     HIP_CHECK(hipEventRecord(st->ev[3], st->stream));
     st->enc_batch = total;
+    st->enc_ctx = audio_ctx_of(st);
   });
 }
 
@@ -873,6 +910,7 @@ int ohw_decode_active(ohw_state* st, const int32_t* tokens, int n_new, const int
     if (!st || !tokens || !n_past) throw Error(OHW_E_INVALID_ARG, "null argument");
     if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "decode: batch must equal the batch of the last ohw_encode");
     if (n_new < 1 || n_new > 8) throw Error(OHW_E_INVALID_ARG, "decode: n_new must be in 1..8");
+    check_decode_ctx(st, "decode");
     const ohw_hparams& hp = st->ctx->hp;
     for (int b = 0; b < batch; ++b) {
       if (n_past[b] < 0 || n_past[b] + n_new > hp.n_text_ctx) throw Error(OHW_E_INVALID_ARG, "decode: position exceeds n_text_ctx");
@@ -938,6 +976,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
     float* sum_logprob_out = res->sum_logprob;
     if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": batch must equal the batch of the last ohw_encode");
     const ohw_ctx* c = st->ctx;
+    check_decode_ctx(st, what);
     if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": lang_id out of range");
     if (tp && (!tp->active || !tp->uniforms || !(tp->temperature > 0.0f) || max_tokens < 1))
       throw Error(OHW_E_INVALID_ARG, "sample_pass: needs temperature > 0, active, uniforms and max_tokens >= 1");
@@ -1002,7 +1041,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
       hipGraphExec_t step_exec = nullptr;
       if (use_graph) {
         for (auto& g : st->step_graphs)
-          if (g.batch == batch && g.cus == st->stream_cus && g.invariant == st->batch_invariant && g.persist == st->persist && g.temp == (tp != nullptr) && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
+          if (g.batch == batch && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.invariant == st->batch_invariant && g.persist == st->persist && g.temp == (tp != nullptr) && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
       }
       if (use_graph && !step_exec) {
         if (st->step_graphs.size() >= 8) {     // bounded: drop the oldest capture
@@ -1037,7 +1076,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
         HIP_CHECK(hipStreamEndCapture(cap, &ng.graph));
         hipError_t ie = hipGraphInstantiate(&ng.exec, ng.graph, nullptr, nullptr, 0);
         if (ie != hipSuccess) { (void)hipGraphDestroy(ng.graph); HIP_CHECK(ie); }
-        ng.batch = batch; ng.cus = st->stream_cus; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.temp = tp != nullptr; ng.spar = spar;
+        ng.batch = batch; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.temp = tp != nullptr; ng.spar = spar;
         st->step_graphs.push_back(ng);
         ++st->step_captures;
         step_exec = ng.exec;
@@ -1117,6 +1156,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
     if (W < 1 || W != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "beam search: n_windows must equal the batch of the last ohw_encode");
     if (K < 2 || K > 5) throw Error(OHW_E_INVALID_ARG, "beam search: beam_size must be in 2..5");
     if (R > st->max_batch) throw Error(OHW_E_INVALID_ARG, "beam search: the state needs max_batch >= n_windows * beam_size decoder rows");
+    check_decode_ctx(st, "beam search");
     const ohw_ctx* c = st->ctx;
     if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, "beam search: lang_id out of range");
     if (sp->force_len > 0) throw Error(OHW_E_INVALID_ARG, "beam search: force_len is a greedy-only knob");
@@ -1174,7 +1214,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
       hipGraphExec_t exec[2] = {nullptr, nullptr};
       if (use_graph) {
         for (auto& g : st->beam_graphs)
-          if (g.windows == W && g.K == K && g.cus == st->stream_cus && g.invariant == st->batch_invariant && g.persist == st->persist && std::memcmp(&g.spar, &base, sizeof base) == 0) {
+          if (g.windows == W && g.K == K && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.invariant == st->batch_invariant && g.persist == st->persist && std::memcmp(&g.spar, &base, sizeof base) == 0) {
             exec[0] = g.exec[0]; exec[1] = g.exec[1];
           }
       }
@@ -1227,7 +1267,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
           drop();
           throw;
         }
-        ng.windows = W; ng.K = K; ng.cus = st->stream_cus; ng.invariant = st->batch_invariant; ng.persist = st->persist;
+        ng.windows = W; ng.K = K; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.invariant = st->batch_invariant; ng.persist = st->persist;
         std::memcpy(&ng.spar, &base, sizeof base);
         st->beam_graphs.push_back(ng);
         ++st->beam_captures;
@@ -1329,6 +1369,23 @@ int ohw_state_set_batch_invariant(ohw_state* st, int on) {
   if (!st) return OHW_E_INVALID_ARG;
   st->batch_invariant = on != 0;
   return OHW_OK;
+}
+
+int ohw_state_set_audio_ctx(ohw_state* st, int n_ctx) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    const int full = st->ctx->hp.n_audio_ctx;
+    if (n_ctx < 0 || n_ctx > full) throw Error(OHW_E_INVALID_ARG, "audio_ctx must be in 0.." + std::to_string(full) + " (0 = full context)");
+    st->audio_ctx = n_ctx == full ? 0 : n_ctx;
+  });
+}
+
+int ohw_state_audio_ctx(const ohw_state* st) { return st ? audio_ctx_of(st) : OHW_E_INVALID_ARG; }
+
+int32_t ohw_audio_ctx_for(int64_t n_samples) {
+  if (n_samples < 0) n_samples = 0;
+  const int64_t pos = (n_samples + 319) / 320 + 32;      // 320 samples per encoder position, 0.64 s of headroom
+  return (int32_t)std::min<int64_t>(1500, (pos + 63) / 64 * 64);
 }
 
 int ohw_state_set_logit_bias(ohw_state* st, const float* bias, int n) {
@@ -1466,7 +1523,7 @@ int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int6
     const ohw_hparams& hp = st->ctx->hp;
     HIP_CHECK(hipSetDevice(st->ctx->device));
     hipStream_t s = st->stream;
-    const int64_t d = hp.n_audio_state, Tn = hp.n_audio_ctx;
+    const int64_t d = hp.n_audio_state, Tn = st->enc_ctx;   // rows per window of the last encode
     const std::string w = what;
     DevBuf tmp;
     auto need = [&](int64_t n) { if (out_elems < n) throw Error(OHW_E_INVALID_ARG, "fetch: output buffer too small"); };
@@ -1619,6 +1676,21 @@ int ohw_dbg_gemm(int dtype, const void* A, const void* W, const float* bias, voi
     Dispatch::run(dtype, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
       launch_gemm<T>(g, epilogue, (hipStream_t)stream);
+    });
+  });
+}
+
+int ohw_dbg_gemm_small(int dtype, const void* A, const void* W, const float* bias, void* out, int64_t M, int64_t N, int64_t K, int epilogue,
+                       void* stream) {
+  return guard([&] {
+    GemmParams g{};
+    g.A = A; g.W = W; g.bias = bias; g.out = out; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.a_batch_stride = 0; g.rows_per_batch = M; g.ldc = N; g.c_batch_stride = 0;
+    if (epilogue != EPI_BIAS_T && epilogue != EPI_BIAS_GELU_T && epilogue != EPI_BIAS_RESID_F32 && epilogue != EPI_F32)
+      throw Error(OHW_E_INVALID_ARG, "dbg_gemm_small: epilogue must be 0, 1, 2 or 4");
+    Dispatch::run(dtype, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      launch_gemm_small<T>(g, epilogue, (hipStream_t)stream);
     });
   });
 }

@@ -26,10 +26,13 @@ struct GemmParams {
   int32_t d_model, n_head, t_len, batch;   // batch = windows of the decode batch the K/V belong to
   int32_t batch_offset;                    // first window of this GEMM's rows inside that decode batch (ohw_encode_slice)
   int32_t group_m;    // gemm256: m-tiles per L2-locality group (set by the launcher)
+  int32_t small_m;    // != 0: the 64x64-tile kernel of gemm_small.hip (run_encode sets it for a short window; same bits)
 };
 
 // N % 128 == 0, K % 64 == 0, lda/ldc/strides multiples of 8 elements (16-byte rows)
 template <typename T> void launch_gemm(const GemmParams& p, int epilogue, hipStream_t stream);
+// the 64x64x64 variant for short windows (N % 64 == 0); launch_gemm hands a problem over only when p.small_m is set
+template <typename T> void launch_gemm_small(const GemmParams& p, int epilogue, hipStream_t stream);
 // the 256x256x64 variant (N % 256 == 0); launch_gemm dispatches to it for large problems
 template <typename T> void launch_gemm256(const GemmParams& p, int epilogue, hipStream_t stream);
 

@@ -348,6 +348,21 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       for (const auto& r : recs) e->last_trace.insert(e->last_trace.end(), sc.trace.begin() + (long)r.second, sc.trace.begin() + (long)(r.second + 3 + (size_t)sc.trace[r.second + 2]));
       sc.trace.clear();
     };
+    // the audio context of this call (ohw_engine_set_audio_ctx), on every state it may run on: auto = the context that covers a
+    // recording of at most one window, the full context for anything longer
+    const int full_ctx = e->ctx->hp.n_audio_ctx;
+    const int call_ctx = e->audio_ctx > 0 ? e->audio_ctx : (e->audio_ctx < 0 && n <= CHUNK_SAMPLES) ? std::min<int>(ohw_audio_ctx_for(n), full_ctx) : 0;
+    auto apply_ctx = [&] {
+      check(ohw_state_set_audio_ctx(e->state, call_ctx));
+      for (ohw_state* st : e->states) check(ohw_state_set_audio_ctx(st, call_ctx));
+      for (ohw_state* st : e->lane_states) check(ohw_state_set_audio_ctx(st, call_ctx));
+    };
+    // a fixed context never drops audio silently: a window that holds samples past it fails the call
+    auto check_window_fits = [&](int64_t window, int64_t win_samples) {
+      if (call_ctx > 0 && win_samples > (int64_t)call_ctx * 320)
+        throw Error(OHW_E_INVALID_ARG, "audio_ctx " + std::to_string(call_ctx) + " covers " + std::to_string((int64_t)call_ctx * 320) + " samples, window " +
+                                           std::to_string(window) + " holds " + std::to_string(win_samples));
+    };
     if (e->window_mode == OHW_WINDOW_SEEK) {
       // whisper.cpp's seek loop as recalled: sequential windows, advanced by the last timestamp; one
       // generator for the whole call
@@ -359,8 +374,10 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       // whisper.cpp computes the log-mel spectrogram of the whole input once (the clamp uses its global maximum) and every
       // window reads 3000 frames of it at its seek offset
       if (seek_end >= 100) check(ohw_recording_set(e->state, samples, n, 0, nullptr));
+      apply_ctx();
       while (seek_end >= 100 && seek + 100 < seek_end) {
         const int32_t seek32 = seek;
+        check_window_fits(w, std::min<int64_t>(CHUNK_SAMPLES, n - (int64_t)seek * HOP));
         check(ohw_mel_seek(e->state, &seek32, 1, nullptr));      // 3000 frames of the recording-wide spectrogram
         check(ohw_encode(e->state, 1));
         greedy_t0(sc, e->state, 1, &seek, &seek_end, w);
@@ -380,6 +397,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       const int64_t n_win_rec = (n + CHUNK_SAMPLES - 1) / CHUNK_SAMPLES;
       const int64_t n_win = n_win_rec > win_first ? (n_win_rec - win_first + win_step - 1) / win_step : 0;
       auto rec_win = [&](int64_t k) { return win_first + k * win_step; };
+      for (int64_t k = 0; k < n_win; ++k) check_window_fits(rec_win(k), std::min<int64_t>(CHUNK_SAMPLES, n - rec_win(k) * CHUNK_SAMPLES));
       const int64_t n_batches = (n_win + e->max_batch - 1) / e->max_batch;
       auto batch_of = [&](int64_t bi) { return (int)std::min<int64_t>(e->max_batch, n_win - bi * e->max_batch); };
       // windows w0 .. w0 + B of the recording into st: each cut on its own (its own `full()` call), or cut from the spectrogram
@@ -528,6 +546,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         for (ohw_state* st : e->states) same(st);
         for (ohw_state* st : e->lane_states) same(st);
       }
+      apply_ctx();
       auto restore = [&] {
         for (ohw_state* st : e->states) (void)ohw_state_set_stream(st, nullptr);
         for (ohw_state* st : e->lane_states) (void)ohw_state_set_stream(st, nullptr);
@@ -959,6 +978,12 @@ int ohw_engine_set_schedule(ohw_engine* e, int schedule, int lanes, int merge) {
   e->schedule = schedule;
   if (lanes > 0) e->lanes = lanes;
   if (merge > 0) e->merge = std::min(merge, std::max(1, 256 / e->max_batch));
+  return OHW_OK;
+}
+
+int ohw_engine_set_audio_ctx(ohw_engine* e, int n) {
+  if (!e || n < -1 || n > e->ctx->hp.n_audio_ctx) return OHW_E_INVALID_ARG;
+  e->audio_ctx = n == e->ctx->hp.n_audio_ctx ? 0 : n;
   return OHW_OK;
 }
 

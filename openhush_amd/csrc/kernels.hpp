@@ -42,6 +42,9 @@ struct MelParams {
   const int64_t* offsets = nullptr;
   int64_t n_total = 0;
   int32_t shared_max = 0, max_only = 0;
+  // reduced audio context: frames >= frame_limit go into the time-major image as zeros, the conv padding value (the fp32
+  // log-mel output is untouched); 0 = all 3000 frames
+  int32_t frame_limit = 0;
 };
 template <typename T> void launch_mel(const MelParams& p, hipStream_t s);
 

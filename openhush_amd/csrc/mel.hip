@@ -93,7 +93,9 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_power_kernel(MelParams p) {
   }
 }
 
-// clamp / scale in place and write the time-major 16-bit image (rows 1..3000; pad rows stay zero)
+// clamp / scale in place and write the time-major 16-bit image (rows 1..3000; pad rows stay zero); under a reduced audio
+// context the rows of frames >= frame_limit are written as zeros too: frame 2C is conv1's right padding, and an earlier call
+// at a larger context may have left audio there
 template <typename T>
 __global__ __launch_bounds__(256) void mel_normalize_kernel(MelParams p) {
   __shared__ float tile[128][65];
@@ -116,12 +118,13 @@ __global__ __launch_bounds__(256) void mel_normalize_kernel(MelParams p) {
   }
   __syncthreads();
   T* img = (T*)p.mel_t + (int64_t)b * MEL_ROWS * MEL_CPAD;
+  const int t_lim = p.frame_limit > 0 ? p.frame_limit : CHUNK_FRAMES;
   for (int i = tid; i < 64 * (MEL_CPAD / 2); i += 256) {
     const int tt = i / (MEL_CPAD / 2), c2 = (i % (MEL_CPAD / 2)) * 2;
     const int t = t0 + tt;
     if (t >= CHUNK_FRAMES) continue;
-    const float v0 = c2 < p.n_mels ? tile[c2][tt] : 0.f;
-    const float v1 = c2 + 1 < p.n_mels ? tile[c2 + 1][tt] : 0.f;
+    const float v0 = c2 < p.n_mels && t < t_lim ? tile[c2][tt] : 0.f;
+    const float v1 = c2 + 1 < p.n_mels && t < t_lim ? tile[c2 + 1][tt] : 0.f;
     *(unsigned*)(img + (int64_t)(1 + t) * MEL_CPAD + c2) = pack2<T>(v0, v1);
   }
 }

@@ -146,6 +146,7 @@ EXPORTS = [
     "ohw_pool_set_decode_policy", "ohw_pool_n_devices", "ohw_pool_broadcast_kind", "ohw_pool_engine", "ohw_pool_free",
     "ohw_rng_uniforms", "ohw_rng_discard_draws", "ohw_sample_pass", "ohw_dbg_sample_t", "ohw_engine_set_fallback_device",
     "ohw_pool_set_fallback_device", "ohw_dequantize_host", "ohw_dbg_dequantize",
+    "ohw_state_set_audio_ctx", "ohw_state_audio_ctx", "ohw_audio_ctx_for", "ohw_engine_set_audio_ctx", "ohw_pool_set_audio_ctx", "ohw_dbg_gemm_small",
 ]
 
 
@@ -360,11 +361,38 @@ def lib():
         L.ohw_ctx_weight_digest.argtypes = [vp, C.c_int, C.c_char_p, C.POINTER(C.c_uint64)]
         L.ohw_dbg_gemm.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp]
         L.ohw_dbg_attention.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+        L.ohw_dbg_gemm_small.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp]
+        L.ohw_state_set_audio_ctx.argtypes = [vp, C.c_int]
+        L.ohw_state_audio_ctx.argtypes = [vp]
+        L.ohw_audio_ctx_for.argtypes = [C.c_int64]
+        L.ohw_audio_ctx_for.restype = C.c_int32
+        L.ohw_engine_set_audio_ctx.argtypes = [vp, C.c_int]
+        L.ohw_pool_set_audio_ctx.argtypes = [vp, C.c_int]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
         L.ohw_dequantize_host.argtypes = [C.c_int, vp, C.c_int64, fp]
         L.ohw_dbg_dequantize.argtypes = [C.c_int, C.c_int, vp, C.c_int64, fp]
         _lib = L
     return _lib
+
+
+def audio_ctx_for(n_samples: int) -> int:
+    """the audio context that covers n_samples of 16 kHz audio - the rule of ohw_audio_ctx_for, restated (no library needed):
+    min(1500, round_up(ceil(n_samples / 320) + 32, 64)): 320 samples per encoder position, 0.64 s of headroom, whole key blocks"""
+    pos = (max(int(n_samples), 0) + 319) // 320 + 32
+    return min(1500, (pos + 63) // 64 * 64)
+
+
+def _audio_ctx_arg(n) -> int:
+    """0 / None (off), n > 0 (fixed) or "auto" / -1 -> the integer ohw_engine_set_audio_ctx takes"""
+    if n is None:
+        return 0
+    if isinstance(n, str):
+        if n.strip().lower() == "auto":
+            return -1
+        n = int(n)
+    if int(n) < -1:
+        raise ValueError("audio_ctx must be 0 (off), a positive context or \"auto\"")
+    return int(n)
 
 
 def last_error() -> str:
@@ -727,6 +755,15 @@ class State:
             b = np.ascontiguousarray(bias, dtype=np.float32)
             _check(lib().ohw_state_set_logit_bias(self.h, _fp(b), b.size))
 
+    def set_audio_ctx(self, n_ctx: int):
+        """ohw_state_set_audio_ctx: encoder positions per window for later mel / encode / decode calls (whisper.cpp's audio_ctx);
+        0 or n_audio_ctx = full context"""
+        _check(lib().ohw_state_set_audio_ctx(self.h, int(n_ctx)))
+
+    @property
+    def audio_ctx(self) -> int:
+        return int(lib().ohw_state_audio_ctx(self.h))
+
     def set_persistent(self, on: bool = True):
         """ohw_state_set_persistent: the one-launch decoder step for at most 16 single-token rows (default off: slower than the launches it replaces)"""
         _check(lib().ohw_state_set_persistent(self.h, int(on)))
@@ -843,6 +880,10 @@ class State:
         shape = {"mel": (batch, hp.n_mels, CHUNK_FRAMES), "conv1": (batch, CHUNK_FRAMES, d)}.get(what, (batch, T, d))
         out = np.empty(shape, dtype=np.float32)
         _check(lib().ohw_state_fetch(self.h, what.encode(), batch, _fp(out), out.size))
+        if what not in ("mel", "conv1") and self.audio_ctx < T:
+            # the last encode ran a reduced context: the library packed [batch][C][d] into the front of the buffer
+            Cn = self.audio_ctx
+            out = out.reshape(-1)[:batch * Cn * d].reshape(batch, Cn, d).copy()
         return out
 
 
@@ -1193,6 +1234,11 @@ class WhisperEngine:
         """OHW_SCHEDULE_SEQUENTIAL / _PIPELINE / _LANES (default) for audio longer than max_batch windows"""
         _check(lib().ohw_engine_set_schedule(self.h, schedule, lanes, merge))
 
+    def set_audio_ctx(self, n):
+        """ohw_engine_set_audio_ctx: 0 (default, off), a fixed context n, or "auto" (audio_ctx_for(len) for a recording of at most
+        one window, full context beyond); a fixed context that does not cover a window's audio fails the transcribe"""
+        _check(lib().ohw_engine_set_audio_ctx(self.h, _audio_ctx_arg(n)))
+
     def last_tokens(self) -> List[int]:
         p = C.POINTER(C.c_int32)()
         n = C.c_int(0)
@@ -1254,6 +1300,10 @@ class EnginePool:
 
     def set_window_mode(self, mode: int):
         _check(lib().ohw_pool_set_window_mode(self.h, mode))
+
+    def set_audio_ctx(self, n):
+        """ohw_pool_set_audio_ctx: WhisperEngine.set_audio_ctx on every engine of the pool"""
+        _check(lib().ohw_pool_set_audio_ctx(self.h, _audio_ctx_arg(n)))
 
     def engine_handle(self, i: int):
         return lib().ohw_pool_engine(self.h, i)

@@ -132,13 +132,18 @@ class StreamingSession:
     noise reduction (the RNNoise stage of BASELINE config #5: a plugged-in `denoiser`, reference src/input/audio.rs:249-341) ->
     normalise / compress / limit when `audio_config.preprocessing` is on (:196-240) -> VAD gate -> every 30 s window of the
     job through mel -> encoder -> beam search or greedy -> text.  beam_size 0 = greedy; vad: callable samples -> probability
-    (the VadEngine hook) with `vad_threshold`, or None."""
+    (the VadEngine hook) with `vad_threshold`, or None.  audio_ctx: 0 (default) the full 30 s context, n a fixed reduced
+    context (a window with samples past n * 320 is refused), "auto" engine.audio_ctx_for(len) for a job of at most one window -
+    a 1.1 s chunk then pays for 128 encoder positions instead of 1500 (WhisperEngine.set_audio_ctx's rule)."""
 
     def __init__(self, ctx: E.Context, beam_size: int = 5, vad: Optional[Callable[[np.ndarray], float]] = None, vad_threshold: float = 0.5,
                  sequence_id: int = 1, tracker: Optional[TranscriptionTracker] = None, params: Optional[E.SampleParams] = None,
                  audio_config: Optional[E.PreprocessConfig] = None, noise_reduction: bool = False, noise_reduction_strength: float = 1.0,
-                 denoiser: Optional["E.Denoiser"] = None):
+                 denoiser: Optional["E.Denoiser"] = None, audio_ctx=0):
         self.ctx = ctx
+        self.audio_ctx = E._audio_ctx_arg(audio_ctx)
+        if self.audio_ctx > ctx.hp.n_audio_ctx:
+            raise E.WhisperError(E.OHW_E_INVALID_ARG, f"audio_ctx {self.audio_ctx} exceeds the model's {ctx.hp.n_audio_ctx}")
         self.beam_size = beam_size
         self.state = E.State(ctx, max(1, beam_size))          # one window at a time: beam_size decoder rows
         self.vad, self.vad_threshold = vad, vad_threshold
@@ -172,8 +177,13 @@ class StreamingSession:
             # the worker hands the WHOLE buffer to engine.transcribe (worker.rs:152): a job longer than 30 s (a late timer
             # tick, a long VAD segment in continuous mode) is cut at the 30 s marks like any other input, window after window
             parts = []
+            n_ctx = self.audio_ctx if self.audio_ctx > 0 else (
+                min(E.audio_ctx_for(len(s_all)), self.ctx.hp.n_audio_ctx) if self.audio_ctx < 0 and len(s_all) <= E.CHUNK_SAMPLES else 0)
+            self.state.set_audio_ctx(n_ctx)
             for off in range(0, len(s_all), E.CHUNK_SAMPLES):
                 s = s_all[off:off + E.CHUNK_SAMPLES]
+                if n_ctx > 0 and len(s) > n_ctx * 320:
+                    raise E.WhisperError(E.OHW_E_INVALID_ARG, f"audio_ctx {n_ctx} covers {n_ctx * 320} samples, window {off // E.CHUNK_SAMPLES} holds {len(s)}")
                 self.state.mel(s[None, :], [len(s)], E.OHW_MEL_ZERO_TAIL, want=False)
                 self.state.encode(1)
                 if self.beam_size >= 2:

@@ -3,7 +3,12 @@ in front (the reference's RNNoise and Silero models are not available offline; D
 seconds over a synthetic recording; prints the per-chunk latency of StreamingSession.transcribe_job (mel + encoder +
 cross-K/V + beam search of --tokens forced steps, detokenise) and the real-time factor of the stream.
 
-    gpurun -- python tools/streaming_latency.py [--chunk 5 --chunks 12 --beam 5 --tokens 48]
+    python tools/streaming_latency.py [--chunk 5 --chunks 12 --beam 5 --tokens 48]
+
+--audio-ctx N|auto runs the chunks under a reduced audio context (StreamingSession(audio_ctx=...)); every run also reports the
+state's own device times per chunk (encode_ms, decode ms per step).  --batch B leaves the session aside and takes B windows of
+--chunk seconds through mel -> encode -> greedy (--tokens forced steps) as ONE batch, --reps times: the server-shaped case.
+--out FILE appends the JSON line to FILE as well (profiles/).
 """
 import argparse
 import json
@@ -26,7 +31,18 @@ def main():
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--tokens", type=int, default=48, help="decoder steps per chunk (synthetic weights never emit end-of-text by themselves)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
+    ap.add_argument("--audio-ctx", default="0", help="0 (full context), N encoder positions, or auto (engine.audio_ctx_for of the chunk)")
+    ap.add_argument("--batch", type=int, default=0, help="B > 0: B windows as one greedy batch instead of the streaming session")
+    ap.add_argument("--reps", type=int, default=5, help="timed repetitions of the --batch run (after 2 warm-up runs)")
+    ap.add_argument("--out", default=None, help="append the JSON result line to this file")
     a = ap.parse_args()
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
     ctx = E.Context.synthetic(synth.PRESETS[a.model].as_list(), 1234, 0, E.OHW_DTYPE_BF16 if a.dtype == "bf16" else E.OHW_DTYPE_F16)
     p = ctx.default_params()
     if a.beam >= 2:
@@ -34,22 +50,51 @@ def main():
     else:
         p.force_len = a.tokens
     n = int(a.chunk * 16000)
+    if a.batch > 0:
+        n_ctx = E._audio_ctx_arg(a.audio_ctx)
+        n_ctx = min(E.audio_ctx_for(n), ctx.hp.n_audio_ctx) if n_ctx < 0 else n_ctx
+        st = E.State(ctx, a.batch)
+        st.set_audio_ctx(n_ctx)
+        p.force_len = a.tokens
+        pcm = np.zeros((a.batch, E.CHUNK_SAMPLES), np.float32)
+        for b in range(a.batch):
+            pcm[b, :n] = synth.synth_audio(40 + b)[:n]
+        enc, dec, wall, steps = [], [], [], 0
+        for r in range(a.reps + 2):
+            t0 = time.perf_counter()
+            st.mel(pcm, [n] * a.batch, E.OHW_MEL_ZERO_TAIL, want=False)
+            st.encode(a.batch)
+            st.greedy(a.batch, p)
+            t = st.timings()
+            if r >= 2:
+                wall.append(time.perf_counter() - t0); enc.append(t.encode_ms); dec.append(t.decode_ms); steps = t.decode_steps
+        emit({"workload": f"{a.model} batch of {a.batch} windows of {a.chunk:g} s, greedy, {a.tokens} decoder steps, {a.dtype}",
+              "audio_ctx": st.audio_ctx, "gemm_small": os.environ.get("OHW_GEMM_SMALL", "default"), "reps": a.reps,
+              "encode_ms": {"median": round(float(np.median(enc)), 3), "min": round(min(enc), 3), "max": round(max(enc), 3)},
+              "decode_ms_per_step": {"median": round(float(np.median(dec)) / max(1, steps), 4), "min": round(min(dec) / max(1, steps), 4),
+                                     "max": round(max(dec) / max(1, steps), 4)},
+              "batch_latency_ms": {"median": round(1e3 * float(np.median(wall)), 2), "min": round(1e3 * min(wall), 2), "max": round(1e3 * max(wall), 2)}})
+        return
     rec = np.concatenate([synth.synth_audio(40 + i)[:n] for i in range(a.chunks)])
     vad = E.EnergyVad(-40.0)
-    ses = S.StreamingSession(ctx, beam_size=a.beam, vad=vad, params=p)
-    lat = []
+    ses = S.StreamingSession(ctx, beam_size=a.beam, vad=vad, params=p, audio_ctx=a.audio_ctx)
+    lat, enc, dec = [], [], []
     for i in range(a.chunks):
         job = ses.scheduler.tick(rec, (i + 1) * n)
         t0 = time.perf_counter()
         r = ses.transcribe_job(job)
         lat.append(time.perf_counter() - t0)
+        t = ses.state.timings()
+        enc.append(t.encode_ms); dec.append(t.decode_ms / max(1, t.decode_steps))
         ses.tracker.add_result(r)
         ses.tracker.take_ready()
     warm = lat[2:] or lat[-1:]        # the first chunks capture the two beam-step graphs (a one-chunk run - profiling - reports that chunk)
-    print(json.dumps({"workload": f"{a.model} streaming, {a.chunk:g} s chunks, beam {a.beam}, {a.tokens} decoder steps per chunk, {a.dtype}",
+    emit({"workload": f"{a.model} streaming, {a.chunk:g} s chunks, beam {a.beam}, {a.tokens} decoder steps per chunk, {a.dtype}",
+                      "audio_ctx": ses.state.audio_ctx, "gemm_small": os.environ.get("OHW_GEMM_SMALL", "default"),
+                      "encode_ms": round(float(np.median(enc[2:] or enc[-1:])), 3), "decode_ms_per_step": round(float(np.median(dec[2:] or dec[-1:])), 4),
                       "first_chunk_ms": round(1e3 * lat[0], 2), "chunk_latency_ms": {"mean": round(1e3 * float(np.mean(warm)), 2),
                       "min": round(1e3 * min(warm), 2), "max": round(1e3 * max(warm), 2)},
-                      "stream_real_time_factor": round(a.chunk / float(np.mean(warm)), 1), "silent_chunks_skipped": ses.skipped_silent}))
+                      "stream_real_time_factor": round(a.chunk / float(np.mean(warm)), 1), "silent_chunks_skipped": ses.skipped_silent})
 
 
 if __name__ == "__main__":
