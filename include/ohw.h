@@ -418,6 +418,21 @@ int ohw_state_audio_ctx(const ohw_state* st);   /* the context in effect, 1..n_a
  * one encoder position is 320 samples; the 32 extra positions are 0.64 s of headroom behind the last sample, and the
  * multiple of 64 matches the key block of the encoder's attention.  1.1 s -> 128, 5 s -> 320, more than 28.8 s -> 1500.     */
 int32_t ohw_audio_ctx_for(int64_t n_samples);
+/* per-window audio context inside one batch, for the next ohw_mel* / ohw_encode* and the decodes on them.
+ * n_ctx[b], b < batch: 1 <= n_ctx[b] <= E, where E is the state's context in effect (ohw_state_audio_ctx: the "envelope").
+ * NULL (or batch 0) clears it: every window runs at E.  batch must equal the batch of the ohw_mel* that follows.
+ * Layouts and strides are those of a uniform run at E (activations [B][E][d], cross K/V [2L][B][H][E][64]); window b uses
+ * its first n_ctx[b] rows of each: its mel image ends at frame 2 * n_ctx[b], the encoder's attention runs n_ctx[b] queries
+ * against n_ctx[b] keys, every cross-attention streams n_ctx[b] keys.  Rows from n_ctx[b] on are unspecified and no valid
+ * row depends on them; the valid rows carry the bits of a uniform run at ohw_state_set_audio_ctx(n_ctx[b]).  The encoder's
+ * GEMMs and LayerNorms still run B * E rows (no packed-row encoder).  The lengths live in device memory, so a captured
+ * greedy / beam step graph is reused across every mix of one envelope.  While lengths are set the cross-attention variant
+ * is picked as under ohw_state_set_batch_invariant (never a key-split form) and the persistent step is not used.
+ * An encode under other lengths than the last ohw_mel*'s, or a decode after the lengths changed without a new encode,
+ * returns OHW_E_INVALID_ARG.  ohw_encode_slice records its windows' lengths into decode-batch slots first .. first + batch - 1;
+ * the slices of one decode batch run all with or all without lengths.  ohw_state_set_audio_ctx clears the lengths.       */
+int ohw_state_set_window_ctx(ohw_state* st, const int32_t* n_ctx, int batch);
+int ohw_state_window_ctx(const ohw_state* st, int window);   /* the context of a decode-batch slot of the last encode; E when it ran without lengths */
 
 /* per-stage device time of the last calls on this state, in milliseconds (reference logs the     */
 /* same split per job: src/queue/worker.rs:170-180)                                               */
@@ -505,6 +520,29 @@ int ohw_engine_set_force_len(ohw_engine* e, int n_tokens);
  * (audio is never dropped silently); -1 = auto: a recording that fits one window runs at ohw_audio_ctx_for(n_samples),
  * anything longer at the full context.                                                                                   */
 int ohw_engine_set_audio_ctx(ohw_engine* e, int n);
+/* Several independent recordings in one call: each is its own whisper_full call of at most one 30 s window (cut as
+ * OHW_WINDOW_FIXED cuts; another window mode returns OHW_E_INVALID_ARG), with its own std::mt19937(0) and its own frame count
+ * as the end of the audio, decoded by the per-window policy of ohw_engine_transcribe.  Every recording passes
+ * ohw_validate_audio before any device work (a failure: OHW_E_VALIDATION, ohw_last_error() names the recording's index); one
+ * longer than 30 s returns OHW_E_INVALID_ARG naming its index.  The recordings are sorted by length, longest first, cut into
+ * batches of max_batch and run one batch after the other on the engine's own state (no lanes, no pipeline).  The context of
+ * recording i follows ohw_engine_set_audio_ctx: 0 = the full context; n > 0 = n for all (a recording with samples past n * 320
+ * is refused by index); -1 = ohw_audio_ctx_for(n_i) per recording through ohw_state_set_window_ctx, the batch's envelope
+ * being the largest of them.  ohw_state_set_batch_invariant is on for the whole call, so a recording's result does not depend
+ * on which other recordings it was submitted with.  Results are read back per recording, in submission order, and stay
+ * valid until the next ohw_engine_transcribe_batch; ohw_engine_last_* are empty after this call.                        */
+typedef struct { const float* samples; int64_t n; } ohw_audio_span;
+int ohw_engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, uint32_t sample_rate);
+/* result of recording i of the last ohw_engine_transcribe_batch; every out pointer may be NULL; language_out: >= 8 bytes */
+int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* text_len, const int32_t** tokens, int* n_tokens,
+                            const ohw_window_quality** quality, char* language_out);
+/* host only: how ohw_engine_transcribe_batch batches n_recs recordings of n_samples[i] samples.  order_out [n_recs]: the
+ * recordings' indices, longest first (equal lengths keep submission order); batch j holds order_out[j * max_batch ..];
+ * ctx_out [n_recs]: the context of recording i under audio_ctx_setting (0 -> 1500, n -> n, -1 -> ohw_audio_ctx_for);
+ * envelope_out [ceil(n_recs / max_batch)]: the largest context of each batch.  OHW_E_INVALID_ARG naming the index for a
+ * recording of more than 480000 samples or one a fixed n does not cover (the first such in submission order).              */
+int ohw_batch_plan(const int64_t* n_samples, int n_recs, int max_batch, int audio_ctx_setting, int32_t* order_out, int32_t* ctx_out,
+                   int32_t* envelope_out);
 /* How audio of more than max_batch windows is overlapped on the device (the reference transcribes one buffer at a time,
  * src/queue/worker.rs:100-160; results are identical under every schedule):
  *   SEQUENTIAL  one batch after the other;

@@ -10,6 +10,11 @@
 //                 (cdna_hip_programming.md section 3 "An accumulator tile as the next MFMA's operand")
 //                 and V^T fragments come from row-major V via ds_read_b64_tr_b16.
 // d_head = 64 makes this softmax(VALU)-heavy: 256 flop per exp; the bound is MFMA/VALU co-issue, not HBM.
+//
+// VAR (per-window contexts, ohw_state_set_window_ctx): the rows of a window keep the stride t_len (the envelope), window b has
+// win_len[b] queries and keys.  The workgroup loads its window's length once (a uniform load), a query block wholly past the
+// length writes zeros and leaves, the key loop ends at the window's own last key block and masks its tail as the uniform
+// kernel masks t_len: the valid rows get the bits of a uniform launch at t_len = win_len[b].
 #include <type_traits>
 
 #include "attention.hpp"
@@ -23,9 +28,9 @@ constexpr int ATT_KB = 64;      // keys per block
 __device__ __forceinline__ int k_swz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int v_swz(int row) { return ((row >> 1) & 1) << 2; }
 
-template <typename T>
+template <typename T, bool VAR>
 __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const T* __restrict__ qkv, T* __restrict__ out,
-                                                                          int batch, int t_len, int n_head) {
+                                                                          int batch, int t_len, int n_head, const int32_t* __restrict__ win_len) {
   using Ops = TypeOps<T>;
   using vec8 = typename Ops::vec8;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16384];  // stage: K 8 KiB | V 8 KiB
@@ -39,7 +44,22 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const
   const int bh = lid / nqb;
   const int h = bh % n_head, b = bh / n_head;
 
-  const T* base = qkv + (int64_t)b * t_len * ld;
+  const int t_stride = t_len;   // rows per window in memory
+  if (VAR) {
+    t_len = win_len[b];
+    if (qb * ATT_QROWS >= t_len) {
+      // nothing to attend: zeros for this block's rows (row = 2 threads x 64 bytes)
+      const int r = qb * ATT_QROWS + (tid >> 1);
+      if (r < t_stride) {
+        u32x4* o = (u32x4*)(out + ((int64_t)b * t_stride + r) * d + h * 64 + (tid & 1) * 32);
+        const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = z;
+      }
+      return;
+    }
+  }
+  const T* base = qkv + (int64_t)b * t_stride * ld;
   const int ql = lane & 31, hh = lane >> 5;
 
   // Q fragments: B operand of S^T = K Q^T: lane holds Q[q][16*ks + 8*hh + 0..7]
@@ -198,7 +218,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const
   l_run += __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_run;
   if (q_valid) {
-    T* o = out + ((int64_t)b * t_len + q_row) * d + h * 64;
+    T* o = out + ((int64_t)b * t_stride + q_row) * d + h * 64;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -212,13 +232,16 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const
 }
 
 template <typename T>
-void launch_encoder_attention(const void* qkv, void* out, int batch, int t_len, int n_head, hipStream_t stream) {
+void launch_encoder_attention(const void* qkv, void* out, int batch, int t_len, int n_head, hipStream_t stream, const int32_t* win_len) {
   const int nqb = (t_len + ATT_QROWS - 1) / ATT_QROWS;
   const unsigned nwg = (unsigned)(nqb * n_head * batch);
-  hipLaunchKernelGGL((encoder_attention_kernel<T>), dim3(nwg), dim3(ATT_THREADS), 0, stream, (const T*)qkv, (T*)out, batch, t_len, n_head);
+  if (win_len)
+    hipLaunchKernelGGL((encoder_attention_kernel<T, true>), dim3(nwg), dim3(ATT_THREADS), 0, stream, (const T*)qkv, (T*)out, batch, t_len, n_head, win_len);
+  else
+    hipLaunchKernelGGL((encoder_attention_kernel<T, false>), dim3(nwg), dim3(ATT_THREADS), 0, stream, (const T*)qkv, (T*)out, batch, t_len, n_head, win_len);
   HIP_CHECK(hipGetLastError());
 }
-template void launch_encoder_attention<bf16_t>(const void*, void*, int, int, int, hipStream_t);
-template void launch_encoder_attention<f16_t>(const void*, void*, int, int, int, hipStream_t);
+template void launch_encoder_attention<bf16_t>(const void*, void*, int, int, int, hipStream_t, const int32_t*);
+template void launch_encoder_attention<f16_t>(const void*, void*, int, int, int, hipStream_t, const int32_t*);
 
 }  // namespace ohw

@@ -794,11 +794,13 @@ int launch_self_attn(const void* q, const void* k_cache, const void* v_cache, co
 constexpr int XA_THREADS = 256;
 constexpr int XA_UNROLL = 4;
 
-template <typename T>
+// VAR (per-window contexts, ohw_state_set_window_ctx): window b streams its first win_len[b] keys - one uniform load per
+// workgroup - of a K/V slab whose stride per (window, head) stays t_len; never launched with key slices (gridDim.z == 1).
+template <typename T, bool VAR>
 __global__ __launch_bounds__(XA_THREADS) void cross_attn_kernel(const T* __restrict__ q, const T* __restrict__ xk, const T* __restrict__ xv,
                                                                 T* __restrict__ out, int n_new, int n_head, int t_len,
                                                                 float* __restrict__ partials, unsigned* __restrict__ tickets,
-                                                                const int32_t* __restrict__ done) {
+                                                                const int32_t* __restrict__ done, const int32_t* __restrict__ win_len) {
   // gridDim.z > 1 (small batches: fewer than a wave of (row, head) pairs): the keys of one (row, head) are cut into
   // gridDim.z contiguous slices on as many CUs - one CU pulls only ~25 GB/s of a 384 KB stream; each slice publishes
   // its (max, sum, 64-vector) state, the workgroup that draws the last ticket merges them in slice order.
@@ -823,6 +825,7 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_kernel(const T* __restr
   }
   const T* kb = xk + (((int64_t)b * n_head + h) * t_len << 6) + part * 8;
   const T* vb = xv + (((int64_t)b * n_head + h) * t_len << 6) + part * 8;
+  if (VAR) t_len = win_len[b];
   float mrun = -INFINITY, lrun = 0.f;
   float acc[8];
 #pragma unroll
@@ -940,10 +943,10 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_kernel(const T* __restr
 // The prompt pass feeds n_new = 2..4 tokens per window at once: their query rows read the SAME 7.7 MB of cross K/V per
 // layer, so one workgroup takes all NQ rows of a (window, head) and streams K/V once (row by row it was read NQ times:
 // 3 x 246 MB per layer at 32 windows).  Per row the arithmetic and its order are those of cross_attn_kernel (bit-identical).
-template <typename T, int NQ>
+template <typename T, int NQ, bool VAR>
 __global__ __launch_bounds__(XA_THREADS) void cross_attn_rows_kernel(const T* __restrict__ q, const T* __restrict__ xk, const T* __restrict__ xv,
                                                                      T* __restrict__ out, int n_head, int t_len,
-                                                                     const int32_t* __restrict__ done) {
+                                                                     const int32_t* __restrict__ done, const int32_t* __restrict__ win_len) {
   __shared__ float red_m[NQ][4], red_l[NQ][4];
   __shared__ float red_o[NQ][4][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -962,6 +965,7 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_rows_kernel(const T* __
   }
   const T* kb = xk + (((int64_t)b * n_head + h) * t_len << 6) + part * 8;
   const T* vb = xv + (((int64_t)b * n_head + h) * t_len << 6) + part * 8;
+  if (VAR) t_len = win_len[b];
   const int n_groups = (t_len + 7) / 8;
   for (int g0 = wave; g0 < n_groups; g0 += 4 * XA_UNROLL) {
     vec8_t<T> kf[XA_UNROLL], vf[XA_UNROLL];
@@ -1033,11 +1037,20 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_rows_kernel(const T* __
   }
 }
 
+template <typename T, int NQ>
+static void launch_xa_rows(dim3 grid, const T* q, const T* xk, const T* xv, T* out, int n_head, int t_len, const int32_t* done, const int32_t* win_len, hipStream_t s) {
+  if (win_len) hipLaunchKernelGGL((cross_attn_rows_kernel<T, NQ, true>), grid, dim3(XA_THREADS), 0, s, q, xk, xv, out, n_head, t_len, done, win_len);
+  else hipLaunchKernelGGL((cross_attn_rows_kernel<T, NQ, false>), grid, dim3(XA_THREADS), 0, s, q, xk, xv, out, n_head, t_len, done, win_len);
+}
+
 template <typename T>
 int launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, int M, int n_new, int n_head, int t_len, float* partials,
-                       unsigned* tickets, int max_split_rows, const int32_t* done, hipStream_t s, int kv_group, bool batch_invariant) {
+                       unsigned* tickets, int max_split_rows, const int32_t* done, hipStream_t s, int kv_group, bool batch_invariant, const int32_t* win_len) {
   // batch_invariant: the kernel variant (and with it the order of the softmax reduction) is picked from n_new alone, never
   // from the number of rows, so a window's result does not depend on how many windows share its batch
+  // win_len (per-window contexts): the same choice - the key slices of the split forms would have to cope with slices that
+  // a short window leaves empty, so they are never picked
+  if (win_len) batch_invariant = true;
   // beam search: kv_group consecutive rows are the beams of ONE window and read the same cross K/V: one workgroup per
   // (window, head) streams it once for all of them (done: per window)
   if (kv_group > 1) {
@@ -1048,17 +1061,17 @@ int launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, 
     if (!batch_invariant && partials && tickets && M <= max_split_rows && (int64_t)(M / kv_group) * n_head < 128) {
       int ks = 1;
       while (ks < XA_MAX_SPLIT && (int64_t)M * n_head * ks < 512 && t_len / (ks * 2) >= 64) ks *= 2;
-      hipLaunchKernelGGL((cross_attn_kernel<T>), dim3(n_head, M, ks), dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, kv_group,
-                         n_head, t_len, partials, tickets, done);
+      hipLaunchKernelGGL((cross_attn_kernel<T, false>), dim3(n_head, M, ks), dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, kv_group,
+                         n_head, t_len, partials, tickets, done, (const int32_t*)nullptr);
       HIP_CHECK(hipGetLastError());
       return XA_GROUP_SPLIT;
     }
     const dim3 grid(n_head, M / kv_group);
     switch (kv_group) {
-      case 2: hipLaunchKernelGGL((cross_attn_rows_kernel<T, 2>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done); break;
-      case 3: hipLaunchKernelGGL((cross_attn_rows_kernel<T, 3>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done); break;
-      case 4: hipLaunchKernelGGL((cross_attn_rows_kernel<T, 4>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done); break;
-      default: hipLaunchKernelGGL((cross_attn_rows_kernel<T, 5>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done); break;
+      case 2: launch_xa_rows<T, 2>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s); break;
+      case 3: launch_xa_rows<T, 3>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s); break;
+      case 4: launch_xa_rows<T, 4>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s); break;
+      default: launch_xa_rows<T, 5>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s); break;
     }
     HIP_CHECK(hipGetLastError());
     return XA_GROUP2 + (kv_group - 2);
@@ -1071,14 +1084,18 @@ int launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, 
   // several new tokens per window and enough windows to fill the chip: one workgroup per (window, head) streams K/V once
   if (n_new >= 2 && n_new <= 4 && M % n_new == 0 && ((int64_t)(M / n_new) * n_head >= 256 || batch_invariant)) {
     const dim3 grid(n_head, M / n_new);
-    if (n_new == 2) hipLaunchKernelGGL((cross_attn_rows_kernel<T, 2>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done);
-    else if (n_new == 3) hipLaunchKernelGGL((cross_attn_rows_kernel<T, 3>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done);
-    else hipLaunchKernelGGL((cross_attn_rows_kernel<T, 4>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done);
+    if (n_new == 2) launch_xa_rows<T, 2>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s);
+    else if (n_new == 3) launch_xa_rows<T, 3>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s);
+    else launch_xa_rows<T, 4>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s);
     HIP_CHECK(hipGetLastError());
     return XA_ROWS2 + (n_new - 2);
   }
-  hipLaunchKernelGGL((cross_attn_kernel<T>), dim3(n_head, M, ks), dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_new,
-                     n_head, t_len, partials, tickets, done);
+  if (win_len)
+    hipLaunchKernelGGL((cross_attn_kernel<T, true>), dim3(n_head, M, 1), dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_new,
+                       n_head, t_len, partials, tickets, done, win_len);
+  else
+    hipLaunchKernelGGL((cross_attn_kernel<T, false>), dim3(n_head, M, ks), dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_new,
+                       n_head, t_len, partials, tickets, done, win_len);
   HIP_CHECK(hipGetLastError());
   return ks > 1 ? XA_SPLIT : XA_PLAIN;
 }
@@ -1893,7 +1910,7 @@ void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_window
   template int launch_dec_gemm<T>(const DecGemmParams&, int, hipStream_t); \
   template void launch_embed<T>(const void*, const float*, const int32_t*, const int32_t*, float*, void*, float*, int, int, int, hipStream_t); \
   template int launch_self_attn<T>(const void*, const void*, const void*, const int32_t*, void*, int, int, int, int, hipStream_t, const int32_t*); \
-  template int launch_cross_attn<T>(const void*, const void*, const void*, void*, int, int, int, int, float*, unsigned*, int, const int32_t*, hipStream_t, int, bool);
+  template int launch_cross_attn<T>(const void*, const void*, const void*, void*, int, int, int, int, float*, unsigned*, int, const int32_t*, hipStream_t, int, bool, const int32_t*);
 INST(bf16_t)
 INST(f16_t)
 #undef INST

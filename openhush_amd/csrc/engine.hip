@@ -113,6 +113,14 @@ struct ohw_state {
   // reduced audio context (ohw_state_set_audio_ctx): encoder positions per window; 0 = the model's n_audio_ctx.  mel_ctx /
   // enc_ctx: the context the mel image / the cross K/V were made under - an encode or a decode under another one is refused
   int audio_ctx = 0, mel_ctx = 0, enc_ctx = 0;
+  // per-window contexts inside that envelope (ohw_state_set_window_ctx).  win_ctx: the setting, one length per window of the next
+  // mel / encode (empty: none); mel_win / enc_set: the setting the last mel / the last encode ran under; enc_win: the length of
+  // every decode-batch slot the encodes recorded (valid while enc_var).  wc_enc mirrors win_ctx on the device (the mel and the
+  // encoder's attention read it), wc_dec holds enc_win (every cross-attention reads it): the lengths are never launch arguments,
+  // so a captured step serves every mix of one envelope
+  std::vector<int32_t> win_ctx, mel_win, enc_set, enc_win;
+  bool enc_var = false;
+  DevBuf wc_enc, wc_dec;    // i32 [max_batch]
   bool gemm_small = false;  // OHW_GEMM_SMALL=1: short windows take the 64x64-tile encoder GEMM (gemm_small.hip; off until measured)
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -145,7 +153,7 @@ struct ohw_state {
   // one entry = the PAIR of graphs of a (windows, beam size, sampler parameters, CU budget, cross-attention variant) key: the
   // odd and the even iteration (the token-history and kv_slot double buffers alternate); made, looked up and evicted together,
   // so a call never holds an exec of an entry it then evicts
-  struct BeamGraph { hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr}; int windows = 0, K = 0, cus = 0, t_len = 0; bool invariant = false, persist = false; SamplerParams spar; };
+  struct BeamGraph { hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr}; int windows = 0, K = 0, cus = 0, t_len = 0; bool invariant = false, persist = false, var = false; SamplerParams spar; };
   std::vector<BeamGraph> beam_graphs;
   // the persistent small-batch decoder step (decode_persist.hip): per-layer pointer table, granule arena, epoch / abort words
   DevBuf ps_layers, ps_gran, ps_words;
@@ -176,7 +184,7 @@ struct ohw_state {
   // hipGraph of one greedy iteration {feed sampled token, single-token decoder step, sampler}
   // captured greedy iterations, one per (batch, sampler parameters, CU budget of the stream, audio context: t_len is a
   // captured kernel argument) seen; a handful at most
-  struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; int t_len = 0; bool invariant = false, persist = false, temp = false; SamplerParams spar{}; };
+  struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; int t_len = 0; bool invariant = false, persist = false, temp = false, var = false; SamplerParams spar{}; };
   bool batch_invariant = false;      // cross-attention variant picked from n_new alone (state_set_batch_invariant)
   std::vector<StepGraph> step_graphs;
   bool graphs_enabled = true;
@@ -224,6 +232,15 @@ void check_decode_ctx(const ohw_state* st, const char* what) {
   if (audio_ctx_of(st) != st->enc_ctx)
     throw Error(OHW_E_INVALID_ARG, std::string(what) + ": the audio context changed since the last ohw_encode (" + std::to_string(st->enc_ctx) + " -> " +
                                        std::to_string(audio_ctx_of(st)) + "): encode again");
+  if (st->win_ctx != st->enc_set)
+    throw Error(OHW_E_INVALID_ARG, std::string(what) + ": the per-window contexts changed since the last ohw_encode: encode again");
+}
+// the mel pass under the state's per-window contexts: they must name exactly its windows
+const int32_t* mel_win_ctx(ohw_state* st, int batch) {
+  if (st->win_ctx.empty()) return nullptr;
+  if ((int)st->win_ctx.size() != batch)
+    throw Error(OHW_E_INVALID_ARG, "mel: ohw_state_set_window_ctx named " + std::to_string(st->win_ctx.size()) + " windows, the call has " + std::to_string(batch));
+  return st->wc_enc.as<int32_t>();
 }
 
 void state_alloc(ohw_state* st) {
@@ -270,6 +287,9 @@ void state_alloc(ohw_state* st) {
   st->fuse_attn = env_int("OHW_DEC_FUSE_ATTN", 0, 0, 1) != 0;
   st->gemm_small = env_int("OHW_GEMM_SMALL", 0, 0, 1) != 0;
   st->mel_ctx = st->enc_ctx = hp.n_audio_ctx;
+  st->wc_enc.alloc((size_t)B * 4, true);
+  st->wc_dec.alloc((size_t)B * 4, true);
+  st->enc_win.assign((size_t)B, 0);
   st->attn_ticket.alloc((size_t)hp.n_text_head * 4, true);
   (void)hipDeviceGetAttribute(&st->n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
   st->postnorm = env_int("OHW_DEC_POSTNORM", 0, 0, 1) != 0 && dec_ksplit_long() == 1 && dec_ksplit_short() == 1 && dt % 32 == 0;
@@ -345,8 +365,10 @@ void run_mel(ohw_state* st, const float* pcm_dev, int64_t stride, int batch, int
   p.logmel = st->logmel.as<float>(); p.max_bits = st->max_bits.as<int32_t>(); p.mel_t = st->mel_t.p;
   p.n_mels = c->hp.n_mels; p.batch = batch; p.mode = mode;
   p.frame_limit = 2 * audio_ctx_of(st);
+  p.win_ctx = mel_win_ctx(st, batch);
   launch_mel<T>(p, st->stream);
   st->mel_ctx = audio_ctx_of(st);
+  st->mel_win = st->win_ctx;
 }
 
 // first / total: the cross K/V of these B windows go to windows [first, first + B) of a decode batch of `total` windows
@@ -360,6 +382,15 @@ void run_encode(ohw_state* st, int B, int first, int total) {
   const int64_t d = hp.n_audio_state, Tn = audio_ctx_of(st), M = (int64_t)B * Tn;
   // a short window: the 64x64-tile kernel where the 128x128 grid would leave more than half the compute units idle
   const bool reduced = Tn < hp.n_audio_ctx;
+  // per-window contexts: every buffer keeps the envelope's strides, the GEMMs and LayerNorms run all B * Tn rows (rows past a
+  // window's length hold unspecified values no valid row reads; a packed-row encoder is not attempted), the attention - the
+  // part that is quadratic in the length - runs each window at its own length
+  const bool var = !st->win_ctx.empty();
+  double attn_sq = (double)B * (double)Tn * (double)Tn;     // sum over the windows of (queries x keys)
+  if (var) {
+    attn_sq = 0.0;
+    for (int b = 0; b < B; ++b) attn_sq += (double)st->win_ctx[(size_t)b] * (double)st->win_ctx[(size_t)b];
+  }
   auto pick_small = [&](GemmParams& q) {
     const int64_t tiles128 = ((q.M + 127) / 128) * (q.N / 128);
     q.small_m = reduced && st->gemm_small && q.N % 64 == 0 && q.K % 64 == 0 && 2 * tiles128 < (st->n_cu > 0 ? st->n_cu : 256) ? 1 : 0;
@@ -398,8 +429,8 @@ void run_encode(ohw_state* st, int B, int first, int total) {
     launch_layernorm<T>(st->h.as<float>(), w.ln1.g.as<float>(), w.ln1.b.as<float>(), st->y.p, M, (int)d, s);
     dense(st->y.p, d, w.wqkv, w.bqkv, st->qkv.p, 3 * d, EPI_BIAS_T);
     {
-      ProfScope ps(st, OHW_PROF_ENC_ATTN, 4.0 * B * hp.n_audio_head * (double)Tn * (double)Tn * 64.0);
-      launch_encoder_attention<T>(st->qkv.p, st->att.p, B, (int)Tn, hp.n_audio_head, s);
+      ProfScope ps(st, OHW_PROF_ENC_ATTN, 4.0 * hp.n_audio_head * attn_sq * 64.0);
+      launch_encoder_attention<T>(st->qkv.p, st->att.p, B, (int)Tn, hp.n_audio_head, s, var ? st->wc_enc.as<int32_t>() : nullptr);
     }
     dense(st->att.p, d, w.wo, w.bo, st->h.p, d, EPI_BIAS_RESID_F32);
     launch_layernorm<T>(st->h.as<float>(), w.ln2.g.as<float>(), w.ln2.b.as<float>(), st->y.p, M, (int)d, s);
@@ -416,6 +447,8 @@ void run_encode(ohw_state* st, int B, int first, int total) {
   g.d_model = hp.n_text_state; g.n_head = hp.n_text_head; g.t_len = (int)Tn; g.batch = total; g.batch_offset = first;
   pick_small(g);
   { ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * g.M * g.N * g.K); launch_gemm<T>(g, EPI_CROSSKV_T, s); }
+  // the lengths of these windows into their decode-batch slots
+  if (var) HIP_CHECK(hipMemcpyAsync(st->wc_dec.as<int32_t>() + first, st->wc_enc.p, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
 }
 
 // one decoder pass over M = B * n_new rows; tokens in tok_src (default st->step_tok), positions from st->n_past
@@ -436,7 +469,8 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
   // ---- at most 16 single-token rows: the 32 layers in ONE persistent launch (decode_persist.hip) instead of 8 launches per
   // layer.  Not under ohw_state_set_batch_invariant (a window's bits must then not depend on which path its batch takes), not
   // while a kernel class is being profiled, not on the experimental post-norm / split-K paths.
-  if (st->persist && n_new == 1 && M <= 16 && kv_group <= 5 && M % kv_group == 0 && !st->batch_invariant && !pn && st->prof_class == 0 &&
+  const bool var = st->enc_var;   // per-window contexts: the launches below, the variant choice of batch-invariant mode
+  if (st->persist && n_new == 1 && M <= 16 && kv_group <= 5 && M % kv_group == 0 && !st->batch_invariant && !var && !pn && st->prof_class == 0 &&
       st->ksplit_long == 1 && st->ksplit_short == 1 && st->ps_gran.p) {
     const int grid = std::max(1, std::min(st->stream_cus > 0 ? st->stream_cus : st->n_cu, 256));
     PersistParams q = st->ps_layout;
@@ -524,11 +558,19 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     {
       // algorithmic bytes: K and V of every (query row, head); the prompt pass streams them once per (window, head)
       // for all its rows (cross_attn_rows_kernel: same condition as launch_cross_attn)
-      const bool rows_path = n_new >= 2 && n_new <= 4 && ((int64_t)B * H >= 256 || st->batch_invariant);
-      ProfScope psx(st, OHW_PROF_DEC_XATTN, 2.0 * 2.0 * (double)(kv_group > 1 ? B / kv_group : rows_path ? B : M) * H * Tn * 64.0);
+      const bool rows_path = n_new >= 2 && n_new <= 4 && ((int64_t)B * H >= 256 || st->batch_invariant || var);
+      // (window, head) streams x keys: under per-window contexts the sum of the windows' own lengths
+      double xa_keys = (double)(kv_group > 1 ? B / kv_group : rows_path ? B : M) * Tn;
+      if (var) {
+        xa_keys = 0.0;
+        const int Wn = B / kv_group;
+        for (int w = 0; w < Wn; ++w) xa_keys += (double)st->enc_win[(size_t)w] * (kv_group > 1 || rows_path ? 1 : n_new);
+      }
+      ProfScope psx(st, OHW_PROF_DEC_XATTN, 2.0 * 2.0 * xa_keys * H * 64.0);
       ++st->tally_xattn[launch_cross_attn<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab,
                                              st->da.p, M, n_new, H, Tn, st->xa_part.as<float>(), st->xa_ticket.as<unsigned>(), st->xa_rows,
-                                             kv_group > 1 ? win_done : (st->skip_done ? st->done.as<int32_t>() : nullptr), s, kv_group, st->batch_invariant)];
+                                             kv_group > 1 ? win_done : (st->skip_done ? st->done.as<int32_t>() : nullptr), s, kv_group, st->batch_invariant,
+                                             var ? st->wc_dec.as<int32_t>() : nullptr)];
     }
     gemm(DT_XO, st->da.p, nullptr, w.wxo, w.bxo, st->dx.p, d, d, DEPI_BIAS_RESID, d);
     gemm(DT_FC1, st->dx.p, &w.ln2, w.w1, w.b1, st->df.p, 4 * d, d, DEPI_BIAS_GELU_T, 4 * d, &w.s1);
@@ -868,7 +910,9 @@ int ohw_mel_seek(ohw_state* st, const int32_t* seek_frames, int batch, float* me
     p.n_mels = c->hp.n_mels; p.batch = batch; p.mode = OHW_MEL_ZERO_TAIL;
     p.offsets = st->rec_off.as<int64_t>(); p.n_total = st->rec_n; p.shared_max = 1; p.max_only = 0;
     p.frame_limit = 2 * audio_ctx_of(st);
+    p.win_ctx = mel_win_ctx(st, batch);
     st->mel_ctx = audio_ctx_of(st);
+    st->mel_win = st->win_ctx;
     Dispatch::run(c->dtype, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
       launch_mel<T>(p, s);
@@ -890,6 +934,10 @@ int ohw_encode_slice(ohw_state* st, int batch, int first, int total) {
     if (first < 0 || total < first + batch || total > st->max_batch) throw Error(OHW_E_INVALID_ARG, "encode: slice exceeds the state's max_batch");
     if (st->mel_ctx != audio_ctx_of(st)) throw Error(OHW_E_INVALID_ARG, "encode: the audio context changed since the last ohw_mel: run it again");
     if (first > 0 && st->enc_ctx != audio_ctx_of(st)) throw Error(OHW_E_INVALID_ARG, "encode: the slices of one decode batch must share one audio context");
+    if (st->win_ctx != st->mel_win) throw Error(OHW_E_INVALID_ARG, "encode: the per-window contexts changed since the last ohw_mel: run it again");
+    const bool var = !st->win_ctx.empty();
+    if (first > 0 && st->enc_var != var)
+      throw Error(OHW_E_INVALID_ARG, "encode: the slices of one decode batch run all with or all without per-window contexts");
     HIP_CHECK(hipSetDevice(st->ctx->device));
     HIP_CHECK(hipEventRecord(st->ev[2], st->stream));
     Dispatch::run(st->ctx->dtype, [&](auto* tag) {
@@ -899,6 +947,9 @@ int ohw_encode_slice(ohw_state* st, int batch, int first, int total) {
     HIP_CHECK(hipEventRecord(st->ev[3], st->stream));
     st->enc_batch = total;
     st->enc_ctx = audio_ctx_of(st);
+    st->enc_set = st->win_ctx;
+    st->enc_var = var;
+    if (var) std::copy(st->win_ctx.begin(), st->win_ctx.end(), st->enc_win.begin() + first);
   });
 }
 
@@ -1041,7 +1092,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
       hipGraphExec_t step_exec = nullptr;
       if (use_graph) {
         for (auto& g : st->step_graphs)
-          if (g.batch == batch && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.invariant == st->batch_invariant && g.persist == st->persist && g.temp == (tp != nullptr) && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
+          if (g.batch == batch && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant && g.persist == st->persist && g.temp == (tp != nullptr) && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
       }
       if (use_graph && !step_exec) {
         if (st->step_graphs.size() >= 8) {     // bounded: drop the oldest capture
@@ -1076,7 +1127,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
         HIP_CHECK(hipStreamEndCapture(cap, &ng.graph));
         hipError_t ie = hipGraphInstantiate(&ng.exec, ng.graph, nullptr, nullptr, 0);
         if (ie != hipSuccess) { (void)hipGraphDestroy(ng.graph); HIP_CHECK(ie); }
-        ng.batch = batch; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.temp = tp != nullptr; ng.spar = spar;
+        ng.batch = batch; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.var = st->enc_var; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.temp = tp != nullptr; ng.spar = spar;
         st->step_graphs.push_back(ng);
         ++st->step_captures;
         step_exec = ng.exec;
@@ -1214,7 +1265,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
       hipGraphExec_t exec[2] = {nullptr, nullptr};
       if (use_graph) {
         for (auto& g : st->beam_graphs)
-          if (g.windows == W && g.K == K && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.invariant == st->batch_invariant && g.persist == st->persist && std::memcmp(&g.spar, &base, sizeof base) == 0) {
+          if (g.windows == W && g.K == K && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant && g.persist == st->persist && std::memcmp(&g.spar, &base, sizeof base) == 0) {
             exec[0] = g.exec[0]; exec[1] = g.exec[1];
           }
       }
@@ -1267,7 +1318,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
           drop();
           throw;
         }
-        ng.windows = W; ng.K = K; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.invariant = st->batch_invariant; ng.persist = st->persist;
+        ng.windows = W; ng.K = K; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.var = st->enc_var; ng.invariant = st->batch_invariant; ng.persist = st->persist;
         std::memcpy(&ng.spar, &base, sizeof base);
         st->beam_graphs.push_back(ng);
         ++st->beam_captures;
@@ -1377,10 +1428,34 @@ int ohw_state_set_audio_ctx(ohw_state* st, int n_ctx) {
     const int full = st->ctx->hp.n_audio_ctx;
     if (n_ctx < 0 || n_ctx > full) throw Error(OHW_E_INVALID_ARG, "audio_ctx must be in 0.." + std::to_string(full) + " (0 = full context)");
     st->audio_ctx = n_ctx == full ? 0 : n_ctx;
+    st->win_ctx.clear();      // lengths are given inside an envelope: a new envelope starts without any
   });
 }
 
 int ohw_state_audio_ctx(const ohw_state* st) { return st ? audio_ctx_of(st) : OHW_E_INVALID_ARG; }
+
+int ohw_state_set_window_ctx(ohw_state* st, const int32_t* n_ctx, int batch) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    if (!n_ctx || batch == 0) { st->win_ctx.clear(); return; }
+    if (batch < 0 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "window_ctx: batch exceeds the state's max_batch");
+    const int E = audio_ctx_of(st);
+    for (int b = 0; b < batch; ++b)
+      if (n_ctx[b] < 1 || n_ctx[b] > E)
+        throw Error(OHW_E_INVALID_ARG, "window_ctx: window " + std::to_string(b) + " asks for " + std::to_string(n_ctx[b]) + " positions, the state's context is " +
+                                           std::to_string(E) + " (1.." + std::to_string(E) + ")");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    // in stream order behind the kernels that still read the previous lengths; the source is the caller's memory, so wait
+    HIP_CHECK(hipMemcpyAsync(st->wc_enc.p, n_ctx, (size_t)batch * 4, hipMemcpyHostToDevice, st->stream));
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    st->win_ctx.assign(n_ctx, n_ctx + batch);
+  });
+}
+
+int ohw_state_window_ctx(const ohw_state* st, int window) {
+  if (!st || window < 0 || window >= st->max_batch) return OHW_E_INVALID_ARG;
+  return st->enc_var && window < st->enc_batch ? st->enc_win[(size_t)window] : audio_ctx_of(st);
+}
 
 int32_t ohw_audio_ctx_for(int64_t n_samples) {
   if (n_samples < 0) n_samples = 0;

@@ -173,8 +173,10 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
   return e.release();
 }
 
-void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text_out, int64_t win_first, int64_t win_step) {
-  std::string& text = *text_out;
+void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text_out, int64_t win_first, int64_t win_step,
+                            const ohw_audio_span* recs, int n_recs) {
+  std::string own_text;
+  std::string& text = text_out ? *text_out : own_text;
   if (win_first < 0 || win_step < 1) throw Error(OHW_E_INVALID_ARG, "transcribe: window dealing must be first >= 0, step >= 1");
     ohw_sample_params sp;
     ohw_default_sample_params(e->ctx, &sp);
@@ -363,6 +365,71 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         throw Error(OHW_E_INVALID_ARG, "audio_ctx " + std::to_string(call_ctx) + " covers " + std::to_string((int64_t)call_ctx * 320) + " samples, window " +
                                            std::to_string(window) + " holds " + std::to_string(win_samples));
     };
+    // the decode of one batch on whatever stream the state is set to; fills sc.runs (and sc.trace); re-entrant per Scratch
+    auto decode_windows = [&](Scratch& sc, ohw_state* st, int64_t w0, int B, const int32_t* nsb) {
+      std::vector<int> zero((size_t)B, 0), ends((size_t)B);
+      for (int b = 0; b < B; ++b) ends[(size_t)b] = mel_frames(nsb[b]);
+      greedy_t0(sc, st, B, zero.data(), ends.data(), w0);
+      for (int b = 0; b < B; ++b) if (ends[(size_t)b] <= 100) { sc.runs[(size_t)b] = WindowRun(); sc.runs[(size_t)b].ev.result_len = 0; }
+      bool any = false;
+      for (int b = 0; b < B; ++b) any = any || sc.runs[(size_t)b].pending;
+      if (any) {
+        Rngs lr;
+        lr.reset((size_t)B);
+        run_ladder(sc, st, B, zero.data(), ends.data(), w0, lr.v);
+      }
+    };
+    if (recs) {
+      // ---- ohw_engine_transcribe_batch: every recording one window of its own; longest first, max_batch at a time, one batch
+      // after the other on the engine's own state.  Under the auto setting a batch's envelope is its largest context and every
+      // window runs at its own (ohw_state_set_window_ctx) - unless all of them equal the envelope, which is the uniform path
+      e->batch_records.assign((size_t)n_recs, ohw_engine::BatchRecord());
+      std::vector<int64_t> lens((size_t)n_recs);
+      for (int i = 0; i < n_recs; ++i) lens[(size_t)i] = recs[i].n;
+      const int MB = e->max_batch, n_b = (n_recs + MB - 1) / MB;
+      std::vector<int32_t> order((size_t)n_recs), rctx((size_t)n_recs), env((size_t)n_b);
+      const int prc = ohw_batch_plan(lens.data(), n_recs, MB, e->audio_ctx, order.data(), rctx.data(), env.data());
+      if (prc != OHW_OK) throw Error(prc, g_last_error);
+      struct Restore {
+        ohw_engine* e;
+        explicit Restore(ohw_engine* e_) : e(e_) { (void)ohw_state_set_batch_invariant(e->state, 1); }
+        ~Restore() { (void)ohw_state_set_window_ctx(e->state, nullptr, 0); (void)ohw_state_set_batch_invariant(e->state, 0); }
+      } restore_state(e);
+      Scratch sc(MB, max_tok);
+      std::vector<float> stage;
+      std::vector<int32_t> ns((size_t)MB), wl((size_t)MB);
+      for (int bi = 0; bi < n_b; ++bi) {
+        const int B = std::min(MB, n_recs - bi * MB);
+        const int32_t* ord = &order[(size_t)bi * MB];
+        const int E = std::min<int>(env[(size_t)bi], full_ctx);
+        bool ragged = false;
+        for (int b = 0; b < B; ++b) {
+          ns[(size_t)b] = (int32_t)recs[ord[b]].n;
+          wl[(size_t)b] = std::min<int>(rctx[(size_t)ord[b]], full_ctx);
+          ragged = ragged || wl[(size_t)b] != E;
+        }
+        const int64_t stride = ns[0];       // the longest of the batch
+        stage.assign((size_t)(stride * B), 0.0f);
+        for (int b = 0; b < B; ++b) std::memcpy(&stage[(size_t)(stride * b)], recs[ord[b]].samples, (size_t)ns[(size_t)b] * sizeof(float));
+        check(ohw_state_set_audio_ctx(e->state, E));
+        check(ohw_state_set_window_ctx(e->state, ragged ? wl.data() : nullptr, ragged ? B : 0));
+        check(ohw_mel(e->state, stage.data(), stride, ns.data(), B, 0, OHW_MEL_ZERO_TAIL, nullptr));
+        check(ohw_encode(e->state, B));
+        decode_windows(sc, e->state, (int64_t)bi * MB, B, ns.data());
+        sc.trace.clear();
+        for (int b = 0; b < B; ++b) {
+          text.clear(); e->last_tokens.clear(); e->last_quality.clear();
+          emit(sc.runs[(size_t)b]);
+          ohw_engine::BatchRecord& r = e->batch_records[(size_t)ord[b]];
+          const size_t b0 = text.find_first_not_of(" \t\r\n"), b1 = text.find_last_not_of(" \t\r\n");
+          r.text = b0 == std::string::npos ? std::string() : text.substr(b0, b1 - b0 + 1);
+          r.tokens = e->last_tokens;
+          r.quality = e->last_quality[0];
+        }
+      }
+      text.clear(); e->last_tokens.clear(); e->last_quality.clear();
+      return;
+    }
     if (e->window_mode == OHW_WINDOW_SEEK) {
       // whisper.cpp's seek loop as recalled: sequential windows, advanced by the last timestamp; one
       // generator for the whole call
@@ -420,20 +487,6 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         check(ohw_state_set_stream(st, stream));
         mel_windows(st, bi * e->max_batch, batch_of(bi), nsv.data());
         check(ohw_encode(st, batch_of(bi)));
-      };
-      // the decode of one batch on whatever stream the state is set to; fills sc.runs (and sc.trace); re-entrant per Scratch
-      auto decode_windows = [&](Scratch& sc, ohw_state* st, int64_t w0, int B, const int32_t* nsb) {
-        std::vector<int> zero((size_t)B, 0), ends((size_t)B);
-        for (int b = 0; b < B; ++b) ends[(size_t)b] = mel_frames(nsb[b]);
-        greedy_t0(sc, st, B, zero.data(), ends.data(), w0);
-        for (int b = 0; b < B; ++b) if (ends[(size_t)b] <= 100) { sc.runs[(size_t)b] = WindowRun(); sc.runs[(size_t)b].ev.result_len = 0; }
-        bool any = false;
-        for (int b = 0; b < B; ++b) any = any || sc.runs[(size_t)b].pending;
-        if (any) {
-          Rngs lr;
-          lr.reset((size_t)B);
-          run_ladder(sc, st, B, zero.data(), ends.data(), w0, lr.v);
-        }
       };
       auto decode_batch = [&](Scratch& sc, ohw_state* st, int64_t bi, const int32_t* nsb) { decode_windows(sc, st, bi * e->max_batch, batch_of(bi), nsb); };
       auto collect = [&](Scratch& sc, int B) {
@@ -932,6 +985,66 @@ int ohw_engine_transcribe(ohw_engine* e, const float* samples, int64_t n, uint32
     }
     if (duration_ms)
       *duration_ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
+  });
+}
+
+int ohw_batch_plan(const int64_t* n_samples, int n_recs, int max_batch, int audio_ctx_setting, int32_t* order_out, int32_t* ctx_out,
+                   int32_t* envelope_out) {
+  return guard([&] {
+    if (!n_samples || n_recs < 1 || max_batch < 1 || !order_out || !ctx_out || !envelope_out) throw Error(OHW_E_INVALID_ARG, "batch_plan: bad argument");
+    if (audio_ctx_setting < -1 || audio_ctx_setting > 1500) throw Error(OHW_E_INVALID_ARG, "batch_plan: audio_ctx must be 0, 1..1500 or -1 (auto)");
+    for (int i = 0; i < n_recs; ++i) {
+      const int64_t n = n_samples[i];
+      if (n < 0 || n > CHUNK_SAMPLES)
+        throw Error(OHW_E_INVALID_ARG, "recording " + std::to_string(i) + " holds " + std::to_string(n) + " samples: a recording of a batch is at most one 30 s window (480000)");
+      if (audio_ctx_setting > 0 && n > (int64_t)audio_ctx_setting * 320)
+        throw Error(OHW_E_INVALID_ARG, "audio_ctx " + std::to_string(audio_ctx_setting) + " covers " + std::to_string((int64_t)audio_ctx_setting * 320) +
+                                           " samples, recording " + std::to_string(i) + " holds " + std::to_string(n));
+      ctx_out[i] = audio_ctx_setting > 0 ? audio_ctx_setting : audio_ctx_setting < 0 ? ohw_audio_ctx_for(n) : 1500;
+    }
+    for (int i = 0; i < n_recs; ++i) order_out[i] = i;
+    std::stable_sort(order_out, order_out + n_recs, [&](int32_t a, int32_t b) { return n_samples[a] > n_samples[b]; });
+    for (int j = 0; j * max_batch < n_recs; ++j) {
+      int32_t m = 0;
+      for (int k = j * max_batch; k < std::min(n_recs, (j + 1) * max_batch); ++k) m = std::max(m, ctx_out[order_out[k]]);
+      envelope_out[j] = m;
+    }
+  });
+}
+
+int ohw_engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, uint32_t sample_rate) {
+  return guard([&] {
+    if (!e || !recs || n_recs < 1) throw Error(OHW_E_INVALID_ARG, "transcribe_batch: null engine or no recordings");
+    if (e->window_mode != OHW_WINDOW_FIXED) throw Error(OHW_E_INVALID_ARG, "transcribe_batch: recordings are cut as OHW_WINDOW_FIXED cuts; set that window mode");
+    e->batch_records.clear();
+    for (int i = 0; i < n_recs; ++i) {
+      ohw_audio_info info;
+      if (ohw_validate_audio(recs[i].samples, recs[i].n, sample_rate, &info) != OHW_OK) {
+        static const char* const names[] = {"ok", "Audio is empty (no samples)", "Unexpected sample rate", "Audio too long", "Audio too short",
+                                            "Audio contains NaN values", "Audio contains infinite values"};
+        throw Error(OHW_E_VALIDATION, "Audio validation failed for recording " + std::to_string(i) + ": " + names[info.error]);
+      }
+    }
+    engine_transcribe_core(e, nullptr, 0, nullptr, 0, 1, recs, n_recs);
+  });
+}
+
+int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* text_len, const int32_t** tokens, int* n_tokens,
+                            const ohw_window_quality** quality, char* language_out) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (i < 0 || i >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "batch_result: no recording " + std::to_string(i) + " in the last transcribe_batch");
+    const ohw_engine::BatchRecord& r = e->batch_records[(size_t)i];
+    if (text) *text = r.text.c_str();
+    if (text_len) *text_len = r.text.size();
+    if (tokens) *tokens = r.tokens.data();
+    if (n_tokens) *n_tokens = (int)r.tokens.size();
+    if (quality) *quality = &r.quality;
+    if (language_out) {
+      const std::string lang = e->language == "auto" ? ohw_lang_id_to_code(0) : e->language;
+      std::strncpy(language_out, lang.c_str(), 7);
+      language_out[7] = 0;
+    }
   });
 }
 

@@ -33,6 +33,9 @@ struct ohw_engine {
   ohw_decode_policy policy{0.2f, 2.4f, -1.0f, 0.6f};
   bool fallback_device = false;          // the temperature ladder samples on the device (ohw_engine_set_fallback_device)
   std::vector<int32_t> last_trace;   // every decode pass of the last transcribe: {window, temperature * 1000, n, tokens...}
+  // ohw_engine_transcribe_batch: one record per recording, in submission order (ohw_engine_batch_result)
+  struct BatchRecord { std::string text; std::vector<int32_t> tokens; ohw_window_quality quality{}; };
+  std::vector<BatchRecord> batch_records;
 };
 
 
@@ -42,5 +45,8 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
 // the path after validation: windows, decode policy, text assembly (untrimmed text in *text); fills the engine's last_* records
 // win_first / win_step (fixed-cut modes only): the engine takes windows win_first, win_first + win_step, ... of the recording
 // (the pool's round-robin deal); the records it leaves (last_tokens / last_quality) list its own windows in that order
-void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text, int64_t win_first = 0, int64_t win_step = 1);
+// recs != nullptr (ohw_engine_transcribe_batch; samples / n / text unused): n_recs validated recordings of at most one window each,
+// batched longest first on the engine's own state and decoded by the same per-window code; fills e->batch_records
+void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text, int64_t win_first = 0, int64_t win_step = 1,
+                            const ohw_audio_span* recs = nullptr, int n_recs = 0);
 }  // namespace ohw

@@ -45,6 +45,8 @@ struct MelParams {
   // reduced audio context: frames >= frame_limit go into the time-major image as zeros, the conv padding value (the fp32
   // log-mel output is untouched); 0 = all 3000 frames
   int32_t frame_limit = 0;
+  // per-window contexts (device i32 [batch], or null): window b's limit is 2 * win_ctx[b] instead of frame_limit
+  const int32_t* win_ctx = nullptr;
 };
 template <typename T> void launch_mel(const MelParams& p, hipStream_t s);
 
@@ -123,7 +125,9 @@ template <typename T> int launch_cross_attn(const void* q, const void* xk, const
                                              int n_head, int t_len, float* partials, unsigned* tickets, int max_split_rows,
                                              const int32_t* done /* [B] or null: windows whose rows are skipped */, hipStream_t s,
                                              int kv_group = 1 /* beam search: consecutive rows that share one window's K/V */,
-                                             bool batch_invariant = false /* pick the variant from n_new alone, never from M */);
+                                             bool batch_invariant = false /* pick the variant from n_new alone, never from M */,
+                                             const int32_t* win_len = nullptr /* device [windows] or null: window w streams its first
+                                                win_len[w] keys of a slab whose stride stays t_len; implies batch_invariant's variant choice */);
 
 // ---- the 32 decoder layers of a single-token step in ONE persistent launch, at most 16 rows (decode_persist.hip) ----------
 struct PersistLayer {

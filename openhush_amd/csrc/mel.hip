@@ -118,7 +118,8 @@ __global__ __launch_bounds__(256) void mel_normalize_kernel(MelParams p) {
   }
   __syncthreads();
   T* img = (T*)p.mel_t + (int64_t)b * MEL_ROWS * MEL_CPAD;
-  const int t_lim = p.frame_limit > 0 ? p.frame_limit : CHUNK_FRAMES;
+  // per-window contexts (ohw_state_set_window_ctx): window b ends at frame 2 * win_ctx[b], one uniform load per workgroup
+  const int t_lim = p.win_ctx ? 2 * p.win_ctx[b] : p.frame_limit > 0 ? p.frame_limit : CHUNK_FRAMES;
   for (int i = tid; i < 64 * (MEL_CPAD / 2); i += 256) {
     const int tt = i / (MEL_CPAD / 2), c2 = (i % (MEL_CPAD / 2)) * 2;
     const int t = t0 + tt;

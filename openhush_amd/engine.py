@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import os
+import time
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -113,6 +114,10 @@ class DecodePolicy(C.Structure):
     _fields_ = [("temperature_inc", C.c_float), ("entropy_thold", C.c_float), ("logprob_thold", C.c_float), ("no_speech_thold", C.c_float)]
 
 
+class AudioSpan(C.Structure):
+    _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_int64)]
+
+
 class Timings(C.Structure):
     _fields_ = [("mel_ms", C.c_float), ("encode_ms", C.c_float), ("decode_ms", C.c_float), ("total_ms", C.c_float), ("decode_steps", C.c_int32)]
 
@@ -147,6 +152,7 @@ EXPORTS = [
     "ohw_rng_uniforms", "ohw_rng_discard_draws", "ohw_sample_pass", "ohw_dbg_sample_t", "ohw_engine_set_fallback_device",
     "ohw_pool_set_fallback_device", "ohw_dequantize_host", "ohw_dbg_dequantize",
     "ohw_state_set_audio_ctx", "ohw_state_audio_ctx", "ohw_audio_ctx_for", "ohw_engine_set_audio_ctx", "ohw_pool_set_audio_ctx", "ohw_dbg_gemm_small",
+    "ohw_state_set_window_ctx", "ohw_state_window_ctx", "ohw_engine_transcribe_batch", "ohw_engine_batch_result", "ohw_batch_plan",
 ]
 
 
@@ -368,6 +374,13 @@ def lib():
         L.ohw_audio_ctx_for.restype = C.c_int32
         L.ohw_engine_set_audio_ctx.argtypes = [vp, C.c_int]
         L.ohw_pool_set_audio_ctx.argtypes = [vp, C.c_int]
+        L.ohw_state_set_window_ctx.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
+        L.ohw_state_window_ctx.argtypes = [vp, C.c_int]
+        L.ohw_engine_transcribe_batch.argtypes = [vp, C.POINTER(AudioSpan), C.c_int, C.c_uint32]
+        L.ohw_engine_batch_result.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(C.c_int32)),
+                                              C.POINTER(C.c_int), C.POINTER(C.POINTER(WindowQuality)), C.c_char_p]
+        L.ohw_batch_plan.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32)]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
         L.ohw_dequantize_host.argtypes = [C.c_int, vp, C.c_int64, fp]
         L.ohw_dbg_dequantize.argtypes = [C.c_int, C.c_int, vp, C.c_int64, fp]
@@ -393,6 +406,19 @@ def _audio_ctx_arg(n) -> int:
     if int(n) < -1:
         raise ValueError("audio_ctx must be 0 (off), a positive context or \"auto\"")
     return int(n)
+
+
+def batch_plan(n_samples: Sequence[int], max_batch: int, audio_ctx=0):
+    """ohw_batch_plan (host only): (order, ctx, envelopes) - the recordings' indices longest first, each recording's context
+    under the engine setting `audio_ctx` (0 / None, n or "auto"), and the envelope of every batch of max_batch"""
+    ns = np.asarray(list(n_samples), dtype=np.int64)
+    n = int(ns.size)
+    order = np.zeros(max(n, 1), dtype=np.int32)
+    ctx = np.zeros(max(n, 1), dtype=np.int32)
+    env = np.zeros(max((n + max(int(max_batch), 1) - 1) // max(int(max_batch), 1), 1), dtype=np.int32)
+    _check(lib().ohw_batch_plan(ns.ctypes.data_as(C.POINTER(C.c_int64)), n, int(max_batch), _audio_ctx_arg(audio_ctx), _ip(order), _ip(ctx),
+                                _ip(env)))
+    return order[:n].tolist(), ctx[:n].tolist(), env.tolist()
 
 
 def last_error() -> str:
@@ -763,6 +789,22 @@ class State:
     @property
     def audio_ctx(self) -> int:
         return int(lib().ohw_state_audio_ctx(self.h))
+
+    def set_window_ctx(self, n_ctx: Optional[Sequence[int]]):
+        """ohw_state_set_window_ctx: one context per window of the next mel / encode, each in 1..audio_ctx (the envelope); None
+        clears them.  Layouts stay those of the envelope: fetch returns [batch][audio_ctx][d], window b's first n_ctx[b] rows valid"""
+        if n_ctx is None or len(n_ctx) == 0:
+            _check(lib().ohw_state_set_window_ctx(self.h, C.cast(None, C.POINTER(C.c_int32)), 0))
+            return
+        a = np.ascontiguousarray(n_ctx, dtype=np.int32)
+        _check(lib().ohw_state_set_window_ctx(self.h, _ip(a), int(a.size)))
+
+    def window_ctx(self, b: int) -> int:
+        """ohw_state_window_ctx: the context of decode-batch slot b of the last encode (the envelope when it ran without lengths)"""
+        v = int(lib().ohw_state_window_ctx(self.h, int(b)))
+        if v < 0:
+            raise ValueError(b)
+        return v
 
     def set_persistent(self, on: bool = True):
         """ohw_state_set_persistent: the one-launch decoder step for at most 16 single-token rows (default off: slower than the launches it replaces)"""
@@ -1181,6 +1223,36 @@ class WhisperEngine:
         _check(lib().ohw_engine_last_text(self.h, C.byref(full), C.byref(n)))   # the fixed buffer may have truncated
         text = C.string_at(full, n.value).decode("utf-8", "replace") if n.value else ""
         return TranscriptionResult(text, lang.value.decode(), int(ms.value))
+
+    def transcribe_batch(self, audios: Sequence[AudioBuffer]) -> List[TranscriptionResult]:
+        """ohw_engine_transcribe_batch: independent recordings of at most 30 s each in one call, batched longest first; results in
+        submission order.  Tokens and quality of recording i: batch_result(i).  duration_ms is the whole call's"""
+        if not audios:
+            return []
+        rates = {int(a.sample_rate) for a in audios}
+        if len(rates) != 1:
+            raise ValueError("transcribe_batch: the recordings must share one sample rate")
+        bufs = [np.ascontiguousarray(a.samples, dtype=np.float32) for a in audios]
+        spans = (AudioSpan * len(bufs))()
+        for i, b in enumerate(bufs):
+            spans[i].samples = _fp(b) if b.size else C.cast(None, C.POINTER(C.c_float))
+            spans[i].n = b.size
+        t0 = time.perf_counter()
+        _check(lib().ohw_engine_transcribe_batch(self.h, spans, len(bufs), rates.pop()))
+        ms = int((time.perf_counter() - t0) * 1000)
+        return [TranscriptionResult(self.batch_result(i)[0], self.batch_result(i)[3], ms) for i in range(len(bufs))]
+
+    def batch_result(self, i: int):
+        """(text, tokens, quality dict, language) of recording i of the last transcribe_batch"""
+        text, n = C.c_char_p(), C.c_size_t(0)
+        toks, nt = C.POINTER(C.c_int32)(), C.c_int(0)
+        q = C.POINTER(WindowQuality)()
+        lang = C.create_string_buffer(8)
+        _check(lib().ohw_engine_batch_result(self.h, int(i), C.byref(text), C.byref(n), C.byref(toks), C.byref(nt), C.byref(q), lang))
+        d = {name: getattr(q[0], name) for name, _ in WindowQuality._fields_}
+        d["would_fallback"], d["no_speech"], d["failed"] = bool(d["would_fallback"]), bool(d["no_speech"]), bool(d["failed"])
+        return (C.string_at(text, n.value).decode("utf-8", "replace") if n.value else "", [int(toks[k]) for k in range(nt.value)], d,
+                lang.value.decode())
 
     def last_quality(self):
         """[(n_tokens, avg_logprob, entropy, would_fallback)] per window of the last transcribe"""

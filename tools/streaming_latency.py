@@ -8,6 +8,10 @@ cross-K/V + beam search of --tokens forced steps, detokenise) and the real-time 
 --audio-ctx N|auto runs the chunks under a reduced audio context (StreamingSession(audio_ctx=...)); every run also reports the
 state's own device times per chunk (encode_ms, decode ms per step).  --batch B leaves the session aside and takes B windows of
 --chunk seconds through mel -> encode -> greedy (--tokens forced steps) as ONE batch, --reps times: the server-shaped case.
+--mixed LO:HI (with --batch B): the B chunk lengths are drawn from a seeded uniform range of LO .. HI seconds (--seed) and the
+batch runs three legs, one JSON line each: `ragged` (State.set_window_ctx: every window at audio_ctx_for of its own length
+inside the largest of them), `envelope` (uniform at that largest context) and `off` (the full context); --legs picks a subset.
+LO = HI = 30 is the uniform mix at which `ragged` must not lose to `envelope`.
 --out FILE appends the JSON line to FILE as well (profiles/).
 """
 import argparse
@@ -34,6 +38,9 @@ def main():
     ap.add_argument("--audio-ctx", default="0", help="0 (full context), N encoder positions, or auto (engine.audio_ctx_for of the chunk)")
     ap.add_argument("--batch", type=int, default=0, help="B > 0: B windows as one greedy batch instead of the streaming session")
     ap.add_argument("--reps", type=int, default=5, help="timed repetitions of the --batch run (after 2 warm-up runs)")
+    ap.add_argument("--mixed", default=None, help="LO:HI seconds: per-window chunk lengths from a seeded uniform range (needs --batch)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the --mixed draw")
+    ap.add_argument("--legs", default="ragged,envelope,off", help="legs of a --mixed run, comma separated")
     ap.add_argument("--out", default=None, help="append the JSON result line to this file")
     a = ap.parse_args()
 
@@ -50,6 +57,42 @@ def main():
     else:
         p.force_len = a.tokens
     n = int(a.chunk * 16000)
+    if a.mixed:
+        if a.batch < 1:
+            ap.error("--mixed needs --batch B")
+        lo, hi = (float(x) for x in a.mixed.split(":"))
+        secs = np.random.default_rng(a.seed).uniform(lo, hi, a.batch)
+        ns = [int(min(max(x, 0.1), 30.0) * 16000) for x in secs]
+        lens = [min(E.audio_ctx_for(x), ctx.hp.n_audio_ctx) for x in ns]
+        env = max(lens)
+        st = E.State(ctx, a.batch)
+        p.force_len = a.tokens
+        pcm = np.zeros((a.batch, E.CHUNK_SAMPLES), np.float32)
+        for b in range(a.batch):
+            pcm[b, :ns[b]] = synth.synth_audio(40 + b)[:ns[b]]
+        for leg in a.legs.split(","):
+            if leg not in ("ragged", "envelope", "off"):
+                ap.error("--legs: ragged, envelope, off")
+            st.set_audio_ctx(0 if leg == "off" else env)
+            st.set_window_ctx(lens if leg == "ragged" else None)
+            enc, dec, wall, steps = [], [], [], 0
+            for r in range(a.reps + 2):
+                t0 = time.perf_counter()
+                st.mel(pcm, ns, E.OHW_MEL_ZERO_TAIL, want=False)
+                st.encode(a.batch)
+                st.greedy(a.batch, p)
+                t = st.timings()
+                if r >= 2:
+                    wall.append(time.perf_counter() - t0); enc.append(t.encode_ms); dec.append(t.decode_ms); steps = t.decode_steps
+            E_ = st.audio_ctx
+            emit({"workload": f"{a.model} batch of {a.batch} windows of {lo:g} .. {hi:g} s (seed {a.seed}), greedy, {a.tokens} decoder steps, {a.dtype}",
+                  "leg": leg, "envelope": E_, "sum_ctx_over_B_E": round(sum(lens) / (a.batch * E_), 4) if leg == "ragged" else 1.0,
+                  "sum_ctx2_over_B_E2": round(sum(x * x for x in lens) / (a.batch * E_ * E_), 4) if leg == "ragged" else 1.0, "reps": a.reps,
+                  "encode_ms": {"median": round(float(np.median(enc)), 3), "min": round(min(enc), 3), "max": round(max(enc), 3)},
+                  "decode_ms_per_step": {"median": round(float(np.median(dec)) / max(1, steps), 4), "min": round(min(dec) / max(1, steps), 4),
+                                         "max": round(max(dec) / max(1, steps), 4)},
+                  "batch_latency_ms": {"median": round(1e3 * float(np.median(wall)), 2), "min": round(1e3 * min(wall), 2), "max": round(1e3 * max(wall), 2)}})
+        return
     if a.batch > 0:
         n_ctx = E._audio_ctx_arg(a.audio_ctx)
         n_ctx = min(E.audio_ctx_for(n), ctx.hp.n_audio_ctx) if n_ctx < 0 else n_ctx
