@@ -425,7 +425,7 @@ int32_t ohw_audio_ctx_for(int64_t n_samples);
  * its first n_ctx[b] rows of each: its mel image ends at frame 2 * n_ctx[b], the encoder's attention runs n_ctx[b] queries
  * against n_ctx[b] keys, every cross-attention streams n_ctx[b] keys.  Rows from n_ctx[b] on are unspecified and no valid
  * row depends on them; the valid rows carry the bits of a uniform run at ohw_state_set_audio_ctx(n_ctx[b]).  The encoder's
- * GEMMs and LayerNorms still run B * E rows (no packed-row encoder).  The lengths live in device memory, so a captured
+ * GEMMs and LayerNorms still run B * E rows unless ohw_state_set_packed_encoder is on.  The lengths live in device memory, so a captured
  * greedy / beam step graph is reused across every mix of one envelope.  While lengths are set the cross-attention variant
  * is picked as under ohw_state_set_batch_invariant (never a key-split form) and the persistent step is not used.
  * An encode under other lengths than the last ohw_mel*'s, or a decode after the lengths changed without a new encode,
@@ -433,6 +433,21 @@ int32_t ohw_audio_ctx_for(int64_t n_samples);
  * the slices of one decode batch run all with or all without lengths.  ohw_state_set_audio_ctx clears the lengths.       */
 int ohw_state_set_window_ctx(ohw_state* st, const int32_t* n_ctx, int batch);
 int ohw_state_window_ctx(const ohw_state* st, int window);   /* the context of a decode-batch slot of the last encode; E when it ran without lengths */
+/* packed-row encoder (default 0; OHW_ENC_PACKED=1 turns it on for new states): an encode under per-window lengths runs the
+ * encoder on the sum of the lengths instead of B * E rows.  The setting is read at encode time and has no effect without
+ * lengths, or when every length equals E (that is the uniform layout: the unpacked path runs).
+ * Layout, inside the encoder only: off[b] = n_ctx[0] + .. + n_ctx[b - 1], Mp = off[B]; row off[b] + t of every encoder
+ * activation behind the conv stem (residual stream, LayerNorm output, q|k|v, attention output, mlp hidden, encoder output, the
+ * "block0" tap) is position t of window b; rows are neither padded nor tile-aligned, and Mp <= B * E fits the buffers as they
+ * are.  conv1 / conv2 and the "stem" tap keep the unpacked layout; one gather packs conv2's valid rows.  LayerNorms and dense
+ * GEMMs run Mp rows, the attention finds window b at off[b], the cross-K/V projection scatters its rows back, so everything
+ * behind the encoder is unchanged: cross K/V stay [2L][B][H][E][64], the decoder, its graphs and the refusals above too.
+ * The valid rows of the encoder output and of the cross K/V, and every token and log-probability decoded from them, carry
+ * the bits of the unpacked run.  ohw_state_fetch keeps returning [B][E][d] for "block0" / "enc" / "xk<l>" / "xv<l>" (the
+ * encoder taps are unpacked on the way out; rows from n_ctx[b] on are unspecified, as without packing).  set returns
+ * OHW_E_INVALID_ARG for a NULL state; the getter returns 0 / 1.                                                       */
+int ohw_state_set_packed_encoder(ohw_state* st, int on);
+int ohw_state_packed_encoder(const ohw_state* st);
 
 /* per-stage device time of the last calls on this state, in milliseconds (reference logs the     */
 /* same split per job: src/queue/worker.rs:170-180)                                               */
@@ -520,6 +535,10 @@ int ohw_engine_set_force_len(ohw_engine* e, int n_tokens);
  * (audio is never dropped silently); -1 = auto: a recording that fits one window runs at ohw_audio_ctx_for(n_samples),
  * anything longer at the full context.                                                                                   */
 int ohw_engine_set_audio_ctx(ohw_engine* e, int n);
+/* ohw_state_set_packed_encoder on the engine's own, pipeline and lane states, those made later included (default: what
+ * OHW_ENC_PACKED gave the engine's own state).  It matters for ohw_engine_transcribe_batch under the auto context (-1): a
+ * batch of mixed lengths then encodes the sum of its contexts; tokens, text and quality records do not change.             */
+int ohw_engine_set_packed_encoder(ohw_engine* e, int on);
 /* Several independent recordings in one call: each is its own whisper_full call of at most one 30 s window (cut as
  * OHW_WINDOW_FIXED cuts; another window mode returns OHW_E_INVALID_ARG), with its own std::mt19937(0) and its own frame count
  * as the end of the audio, decoded by the per-window policy of ohw_engine_transcribe.  Every recording passes
@@ -596,6 +615,7 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
+int ohw_pool_set_packed_encoder(ohw_pool* p, int on);                     /* ohw_engine_set_packed_encoder on every engine */
 /* "" or why the RCCL broadcast was given up for peer copies.  After either kind every replica's weight buffers are compared
  * with device_ids[0]'s (64-bit digests); a mismatch fails ohw_pool_create with OHW_E_LOAD_FAILED naming the device.          */
 const char* ohw_pool_broadcast_note(const ohw_pool* p);
@@ -635,6 +655,9 @@ int ohw_dbg_gemm(int dtype, const void* A, const void* W, const float* bias, voi
 int ohw_dbg_gemm_small(int dtype, const void* A, const void* W, const float* bias, void* out, int64_t M, int64_t N,
                        int64_t K, int epilogue, void* stream);
 int ohw_dbg_attention(int dtype, const void* qkv, void* out, int batch, int T, int n_head, void* stream);
+/* fill an encoder activation buffer of the state with NaN (every byte 0xff: a NaN in bf16 and in f16): what = "qkv" or "att".
+ * An encode overwrites every row it owns, so a test can tell a row that was never written, or written by a neighbour. */
+int ohw_dbg_poison(ohw_state* st, const char* what);
 /* the DEVICE sampler on caller-supplied rows: logits [batch][n_vocab] (host), history [batch][hist_stride] with
  * n_hist[b] tokens sampled so far in the window.  tokens_out [batch]: the pick (end-of-text included);
  * logprobs_out [batch] / no_speech_out [batch] may be NULL (no-speech is defined for rows with n_hist == 0). */
@@ -645,7 +668,8 @@ int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* p, const float* log
                      const int32_t* n_hist, int batch, float temperature, const double* uniforms, int32_t* tokens_out,
                      float* logprobs_out, float* no_speech_out);
 /* counters of a state's graph caches: "step_captures" / "beam_captures" (graphs / graph pairs captured so far),
- * "step_graphs" / "beam_graphs" (entries held now), "persist_launches" (persistent decoder steps launched or captured);
+ * "step_graphs" / "beam_graphs" (entries held now), "persist_launches" (persistent decoder steps launched or captured),
+ * "enc_rows" (rows M of the dense encoder GEMMs of the last encode: B * E, or the sum of the lengths when it ran packed);
  * OHW_E_INVALID_ARG for another name.  A second ohw_greedy /
  * ohw_beam_search with the same batch, parameters and stream must add no capture (tests/test_gpu_beam.py).
  * The decoder step's kernel variants, launches counted per state since its creation (host-side: a captured step

@@ -152,6 +152,9 @@ def main(argv=None) -> int:
     t.add_argument("--audio-ctx", default="0", metavar="N|auto",
                    help="reduced audio context (whisper.cpp's audio_ctx): 0 (default) the full 30 s context; N encoder positions per window "
                         "(320 samples each; audio past them is an error, never dropped); auto: sized to a recording of at most 30 s")
+    t.add_argument("--packed-encoder", action="store_true",
+                   help="run the encoder on the sum of the windows' contexts when a batch carries per-window contexts (the engine's "
+                        "transcribe_batch under --audio-ctx auto); same output, default off")
     args = ap.parse_args(argv)
 
     from . import engine as E
@@ -183,6 +186,8 @@ def main(argv=None) -> int:
         eng.set_window_mode(E.OHW_WINDOW_FIXED_RECORDING_MEL)
     if audio_ctx != 0:
         eng.set_audio_ctx(audio_ctx)
+    if args.packed_encoder:
+        eng.set_packed_encoder(True)
     t1 = time.perf_counter()
     res = eng.transcribe(audio)
     dt = time.perf_counter() - t1

@@ -15,6 +15,11 @@
 // win_len[b] queries and keys.  The workgroup loads its window's length once (a uniform load), a query block wholly past the
 // length writes zeros and leaves, the key loop ends at the window's own last key block and masks its tail as the uniform
 // kernel masks t_len: the valid rows get the bits of a uniform launch at t_len = win_len[b].
+//
+// PACKED (packed-row encoder, ohw_state_set_packed_encoder): the windows lie end to end, window b's rows start at row win_off[b]
+// (the exclusive prefix sum of win_len, one more uniform load per workgroup) instead of b * t_len.  The grid is still sized by
+// the envelope; a query block wholly past its window's length returns WITHOUT storing - in a packed buffer those rows belong
+// to the next window.  Key loop, masking and reduction order are VAR's, so the valid rows carry VAR's bits.
 #include <type_traits>
 
 #include "attention.hpp"
@@ -28,9 +33,11 @@ constexpr int ATT_KB = 64;      // keys per block
 __device__ __forceinline__ int k_swz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int v_swz(int row) { return ((row >> 1) & 1) << 2; }
 
-template <typename T, bool VAR>
-__global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const T* __restrict__ qkv, T* __restrict__ out,
-                                                                          int batch, int t_len, int n_head, const int32_t* __restrict__ win_len) {
+enum AttMode { ATT_UNIFORM = 0, ATT_VAR = 1, ATT_PACKED = 2 };
+
+template <typename T, int MODE>
+__device__ __forceinline__ void encoder_attention_body(const T* __restrict__ qkv, T* __restrict__ out, int batch, int t_len, int n_head,
+                                                       const int32_t* __restrict__ win_len, const int32_t* __restrict__ win_off) {
   using Ops = TypeOps<T>;
   using vec8 = typename Ops::vec8;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16384];  // stage: K 8 KiB | V 8 KiB
@@ -45,7 +52,13 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const
   const int h = bh % n_head, b = bh / n_head;
 
   const int t_stride = t_len;   // rows per window in memory
-  if (VAR) {
+  int64_t row0 = (int64_t)b * t_stride;   // the window's first row
+  if (MODE == ATT_PACKED) {
+    t_len = win_len[b];
+    if (qb * ATT_QROWS >= t_len) return;    // not this window's rows: nothing is stored
+    row0 = win_off[b];
+  }
+  if (MODE == ATT_VAR) {
     t_len = win_len[b];
     if (qb * ATT_QROWS >= t_len) {
       // nothing to attend: zeros for this block's rows (row = 2 threads x 64 bytes)
@@ -59,7 +72,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const
       return;
     }
   }
-  const T* base = qkv + (int64_t)b * t_stride * ld;
+  const T* base = qkv + row0 * ld;
   const int ql = lane & 31, hh = lane >> 5;
 
   // Q fragments: B operand of S^T = K Q^T: lane holds Q[q][16*ks + 8*hh + 0..7]
@@ -218,7 +231,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const
   l_run += __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_run;
   if (q_valid) {
-    T* o = out + ((int64_t)b * t_stride + q_row) * d + h * 64;
+    T* o = out + (row0 + q_row) * d + h * 64;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -231,17 +244,32 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const
   }
 }
 
+// the uniform / VAR kernel keeps its arguments; the packed form is a kernel of its own with the offsets beside the lengths
+template <typename T, bool VAR>
+__global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_kernel(const T* __restrict__ qkv, T* __restrict__ out,
+                                                                          int batch, int t_len, int n_head, const int32_t* __restrict__ win_len) {
+  encoder_attention_body<T, VAR ? ATT_VAR : ATT_UNIFORM>(qkv, out, batch, t_len, n_head, win_len, nullptr);
+}
 template <typename T>
-void launch_encoder_attention(const void* qkv, void* out, int batch, int t_len, int n_head, hipStream_t stream, const int32_t* win_len) {
+__global__ __launch_bounds__(ATT_THREADS, 2) void encoder_attention_packed_kernel(const T* __restrict__ qkv, T* __restrict__ out, int batch, int t_len, int n_head,
+                                                                                 const int32_t* __restrict__ win_len, const int32_t* __restrict__ win_off) {
+  encoder_attention_body<T, ATT_PACKED>(qkv, out, batch, t_len, n_head, win_len, win_off);
+}
+
+template <typename T>
+void launch_encoder_attention(const void* qkv, void* out, int batch, int t_len, int n_head, hipStream_t stream, const int32_t* win_len, const int32_t* win_off) {
   const int nqb = (t_len + ATT_QROWS - 1) / ATT_QROWS;
   const unsigned nwg = (unsigned)(nqb * n_head * batch);
-  if (win_len)
+  if (win_off && !win_len) throw Error(OHW_E_INVALID_ARG, "attention: packed rows need the windows' lengths");
+  if (win_off)
+    hipLaunchKernelGGL((encoder_attention_packed_kernel<T>), dim3(nwg), dim3(ATT_THREADS), 0, stream, (const T*)qkv, (T*)out, batch, t_len, n_head, win_len, win_off);
+  else if (win_len)
     hipLaunchKernelGGL((encoder_attention_kernel<T, true>), dim3(nwg), dim3(ATT_THREADS), 0, stream, (const T*)qkv, (T*)out, batch, t_len, n_head, win_len);
   else
     hipLaunchKernelGGL((encoder_attention_kernel<T, false>), dim3(nwg), dim3(ATT_THREADS), 0, stream, (const T*)qkv, (T*)out, batch, t_len, n_head, win_len);
   HIP_CHECK(hipGetLastError());
 }
-template void launch_encoder_attention<bf16_t>(const void*, void*, int, int, int, hipStream_t, const int32_t*);
-template void launch_encoder_attention<f16_t>(const void*, void*, int, int, int, hipStream_t, const int32_t*);
+template void launch_encoder_attention<bf16_t>(const void*, void*, int, int, int, hipStream_t, const int32_t*, const int32_t*);
+template void launch_encoder_attention<f16_t>(const void*, void*, int, int, int, hipStream_t, const int32_t*, const int32_t*);
 
 }  // namespace ohw

@@ -121,6 +121,15 @@ struct ohw_state {
   std::vector<int32_t> win_ctx, mel_win, enc_set, enc_win;
   bool enc_var = false;
   DevBuf wc_enc, wc_dec;    // i32 [max_batch]
+  // packed-row encoder (ohw_state_set_packed_encoder / OHW_ENC_PACKED=1; read at encode time, no effect without lengths): the
+  // encoder runs on the sum of the lengths, the windows laid end to end.  pk_off: the windows' first packed rows (exclusive prefix
+  // sum of wc_enc, then the row count); pk_map: packed row -> row b * envelope + t of the unpacked layout; both are filled on the
+  // stream by every packed encode.  enc_pk: the host's copy of the last encode's offsets (empty: it ran unpacked) - ohw_state_fetch
+  // unpacks the encoder taps with it.  enc_rows: rows of the last encode's dense GEMMs (ohw_dbg_counter "enc_rows")
+  bool packed = false;
+  DevBuf pk_off, pk_map;    // i32 [max_batch + 1], i32 [max_batch * n_audio_ctx]
+  std::vector<int64_t> enc_pk;
+  int64_t enc_rows = 0;
   bool gemm_small = false;  // OHW_GEMM_SMALL=1: short windows take the 64x64-tile encoder GEMM (gemm_small.hip; off until measured)
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -286,6 +295,9 @@ void state_alloc(ohw_state* st) {
   st->persist = env_int("OHW_DEC_PERSIST", 0, 0, 1) != 0;
   st->fuse_attn = env_int("OHW_DEC_FUSE_ATTN", 0, 0, 1) != 0;
   st->gemm_small = env_int("OHW_GEMM_SMALL", 0, 0, 1) != 0;
+  st->packed = env_int("OHW_ENC_PACKED", 0, 0, 1) != 0;
+  st->pk_off.alloc((size_t)(B + 1) * 4, true);
+  st->pk_map.alloc((size_t)B * T * 4, true);
   st->mel_ctx = st->enc_ctx = hp.n_audio_ctx;
   st->wc_enc.alloc((size_t)B * 4, true);
   st->wc_dec.alloc((size_t)B * 4, true);
@@ -383,13 +395,33 @@ void run_encode(ohw_state* st, int B, int first, int total) {
   // a short window: the 64x64-tile kernel where the 128x128 grid would leave more than half the compute units idle
   const bool reduced = Tn < hp.n_audio_ctx;
   // per-window contexts: every buffer keeps the envelope's strides, the GEMMs and LayerNorms run all B * Tn rows (rows past a
-  // window's length hold unspecified values no valid row reads; a packed-row encoder is not attempted), the attention - the
-  // part that is quadratic in the length - runs each window at its own length
+  // window's length hold unspecified values no valid row reads), the attention - the part that is quadratic in the length -
+  // runs each window at its own length
   const bool var = !st->win_ctx.empty();
   double attn_sq = (double)B * (double)Tn * (double)Tn;     // sum over the windows of (queries x keys)
+  int64_t Mp = 0;                                           // sum of the lengths
+  bool ragged = false;
   if (var) {
     attn_sq = 0.0;
-    for (int b = 0; b < B; ++b) attn_sq += (double)st->win_ctx[(size_t)b] * (double)st->win_ctx[(size_t)b];
+    for (int b = 0; b < B; ++b) {
+      attn_sq += (double)st->win_ctx[(size_t)b] * (double)st->win_ctx[(size_t)b];
+      Mp += st->win_ctx[(size_t)b];
+      ragged = ragged || st->win_ctx[(size_t)b] != Tn;
+    }
+  }
+  // packed rows (ohw_state_set_packed_encoder): behind the conv stem the windows lie end to end - row
+  // pk_off[b] + t of h, y, qkv, att, ffn, enc and the block0 tap is position t of window b - so the LayerNorms and the dense GEMMs
+  // (row-wise, hence the same bits per row) run Mp rows instead of B * Tn; the attention finds its window at pk_off[b], the
+  // cross-K/V GEMM scatters its rows to the unpacked [2L][B][H][Tn][64] through pk_map.  Lengths that all equal the envelope
+  // are the uniform layout already: the path as it stands
+  const bool packed = var && st->packed && ragged;
+  const int64_t Md = packed ? Mp : M;                       // rows of the dense stages
+  st->enc_rows = Md;
+  st->enc_pk.clear();
+  if (packed) {
+    int64_t o = 0;
+    for (int b = 0; b < B; ++b) { st->enc_pk.push_back(o); o += st->win_ctx[(size_t)b]; }
+    launch_pack_map(st->wc_enc.as<int32_t>(), B, (int)Tn, st->pk_off.as<int32_t>(), st->pk_map.as<int32_t>(), s);
   }
   auto pick_small = [&](GemmParams& q) {
     const int64_t tiles128 = ((q.M + 127) / 128) * (q.N / 128);
@@ -408,43 +440,50 @@ void run_encode(ohw_state* st, int B, int first, int total) {
   // conv2 (k=3, stride 2, pad 1): row t reads image rows 2t .. 2t+2 of conv1's padded output
   g = GemmParams{};
   g.A = st->c1.p; g.W = c->conv2_w.p; g.bias = c->conv2_b.as<float>(); g.pos = c->enc_pos.as<float>();
-  g.out = st->h.p;
+  // packed: conv2 writes its B * Tn rows into the ffn buffer (idle until block 0's mlp, and B * Tn * 4d 16-bit elements hold
+  // B * Tn * d floats twice over), the pack kernel gathers the valid ones from there into h: a second buffer, not an ordered copy
+  g.out = packed ? st->ffn.p : st->h.p;
   g.M = M; g.N = d; g.K = 3 * d;
   g.lda = 2 * d; g.a_batch_stride = (int64_t)MEL_ROWS * d; g.rows_per_batch = Tn;
   g.ldc = d; g.c_batch_stride = Tn * d;
   pick_small(g);
   { ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * g.M * g.N * g.K); launch_gemm<T>(g, EPI_GELU_POS_F32, s); }
-  if (st->taps) HIP_CHECK(hipMemcpyAsync(st->tap_stem.p, st->h.p, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+  if (st->taps) HIP_CHECK(hipMemcpyAsync(st->tap_stem.p, g.out, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+  if (packed) launch_pack_rows(st->ffn.as<float>(), st->pk_map.as<int32_t>(), st->h.as<float>(), Md, (int)d, s);
 
   auto dense = [&](const void* A, int64_t K, const DevBuf& W, const DevBuf& bias, void* out, int64_t N, int epi) {
     GemmParams q{};
     q.A = A; q.W = W.p; q.bias = bias.as<float>(); q.out = out;
-    q.M = M; q.N = N; q.K = K; q.lda = K; q.a_batch_stride = 0; q.rows_per_batch = M; q.ldc = N; q.c_batch_stride = 0;
+    q.M = Md; q.N = N; q.K = K; q.lda = K; q.a_batch_stride = 0; q.rows_per_batch = Md; q.ldc = N; q.c_batch_stride = 0;
     pick_small(q);
     ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * q.M * q.N * q.K);
     launch_gemm<T>(q, epi, s);
   };
   for (int l = 0; l < hp.n_audio_layer; ++l) {
     const EncLayerW& w = c->enc[l];
-    launch_layernorm<T>(st->h.as<float>(), w.ln1.g.as<float>(), w.ln1.b.as<float>(), st->y.p, M, (int)d, s);
+    launch_layernorm<T>(st->h.as<float>(), w.ln1.g.as<float>(), w.ln1.b.as<float>(), st->y.p, Md, (int)d, s);
     dense(st->y.p, d, w.wqkv, w.bqkv, st->qkv.p, 3 * d, EPI_BIAS_T);
     {
       ProfScope ps(st, OHW_PROF_ENC_ATTN, 4.0 * hp.n_audio_head * attn_sq * 64.0);
-      launch_encoder_attention<T>(st->qkv.p, st->att.p, B, (int)Tn, hp.n_audio_head, s, var ? st->wc_enc.as<int32_t>() : nullptr);
+      launch_encoder_attention<T>(st->qkv.p, st->att.p, B, (int)Tn, hp.n_audio_head, s, var ? st->wc_enc.as<int32_t>() : nullptr,
+                                  packed ? st->pk_off.as<int32_t>() : nullptr);
     }
     dense(st->att.p, d, w.wo, w.bo, st->h.p, d, EPI_BIAS_RESID_F32);
-    launch_layernorm<T>(st->h.as<float>(), w.ln2.g.as<float>(), w.ln2.b.as<float>(), st->y.p, M, (int)d, s);
+    launch_layernorm<T>(st->h.as<float>(), w.ln2.g.as<float>(), w.ln2.b.as<float>(), st->y.p, Md, (int)d, s);
     dense(st->y.p, d, w.w1, w.b1, st->ffn.p, 4 * d, EPI_BIAS_GELU_T);
     dense(st->ffn.p, 4 * d, w.w2, w.b2, st->h.p, d, EPI_BIAS_RESID_F32);
-    if (l == 0 && st->taps) HIP_CHECK(hipMemcpyAsync(st->tap_block0.p, st->h.p, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+    if (l == 0 && st->taps) HIP_CHECK(hipMemcpyAsync(st->tap_block0.p, st->h.p, (size_t)Md * d * 4, hipMemcpyDeviceToDevice, s));
   }
-  launch_layernorm<T>(st->h.as<float>(), c->ln_post.g.as<float>(), c->ln_post.b.as<float>(), st->enc.p, M, (int)d, s);
+  launch_layernorm<T>(st->h.as<float>(), c->ln_post.g.as<float>(), c->ln_post.b.as<float>(), st->enc.p, Md, (int)d, s);
   // cross-attention K/V of every decoder layer in one GEMM: N = 2 * L * d, head-major output
   g = GemmParams{};
   g.A = st->enc.p; g.W = c->xkv_w.p; g.bias = c->xkv_b.as<float>(); g.out = st->xkv.p;
   g.M = M; g.N = (int64_t)2 * hp.n_text_layer * hp.n_text_state; g.K = d;
   g.lda = d; g.a_batch_stride = Tn * d; g.rows_per_batch = Tn; g.ldc = 0; g.c_batch_stride = 0;
   g.d_model = hp.n_text_state; g.n_head = hp.n_text_head; g.t_len = (int)Tn; g.batch = total; g.batch_offset = first;
+  if (packed) {   // A packed and dense, every output row to its (window, position) of the unpacked slabs
+    g.M = Md; g.a_batch_stride = 0; g.rows_per_batch = Md; g.c_row_map = st->pk_map.as<int32_t>();
+  }
   pick_small(g);
   { ProfScope ps(st, OHW_PROF_ENC_GEMM, 2.0 * g.M * g.N * g.K); launch_gemm<T>(g, EPI_CROSSKV_T, s); }
   // the lengths of these windows into their decode-batch slots
@@ -1398,6 +1437,7 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "step_captures") return st->step_captures;
   if (n == "step_graphs") return (int)st->step_graphs.size();
   if (n == "persist_launches") return st->persist_launches;
+  if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
   auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
   for (int g = 0; g < DT_GEMMS; ++g)
     for (int f = 0; f < DT_FORMS; ++f)
@@ -1415,6 +1455,13 @@ int ohw_state_set_persistent(ohw_state* st, int on) {
   st->persist = on != 0;
   return OHW_OK;
 }
+
+int ohw_state_set_packed_encoder(ohw_state* st, int on) {
+  if (!st) return OHW_E_INVALID_ARG;
+  st->packed = on != 0;
+  return OHW_OK;
+}
+int ohw_state_packed_encoder(const ohw_state* st) { return st ? (st->packed ? 1 : 0) : OHW_E_INVALID_ARG; }
 
 int ohw_state_set_batch_invariant(ohw_state* st, int on) {
   if (!st) return OHW_E_INVALID_ARG;
@@ -1618,10 +1665,22 @@ int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int6
       HIP_CHECK(hipStreamSynchronize(s));
     };
     if (w == "mel") { from_f32(st->logmel.p, (int64_t)batch * hp.n_mels * CHUNK_FRAMES); return; }
-    if (w == "enc") { from_t(st->enc.p, (int64_t)batch * Tn * d); return; }
+    // the last encode ran packed: "enc" and "block0" lie end to end on the device; the caller gets the envelope layout [B][Tn][d],
+    // window b's first n_ctx[b] rows from its packed rows, the rows behind them as zeros
+    DevBuf unp;
+    auto unpacked = [&](const void* src, int es) -> const void* {
+      if (st->enc_pk.empty()) return src;
+      unp.alloc((size_t)batch * Tn * d * es);
+      HIP_CHECK(hipMemsetAsync(unp.p, 0, unp.bytes, s));
+      for (int b = 0; b < batch && b < (int)st->enc_pk.size(); ++b)
+        HIP_CHECK(hipMemcpyAsync((char*)unp.p + (size_t)b * Tn * d * es, (const char*)src + (size_t)st->enc_pk[(size_t)b] * d * es,
+                                 (size_t)st->enc_set[(size_t)b] * d * es, hipMemcpyDeviceToDevice, s));
+      return unp.p;
+    };
+    if (w == "enc") { from_t(unpacked(st->enc.p, 2), (int64_t)batch * Tn * d); return; }
     if (w == "stem" || w == "block0") {
       if (!st->taps) throw Error(OHW_E_INVALID_ARG, "fetch: taps are kept only for d_model <= 512");
-      from_f32(w == "stem" ? st->tap_stem.p : st->tap_block0.p, (int64_t)batch * Tn * d);
+      from_f32(w == "stem" ? st->tap_stem.p : unpacked(st->tap_block0.p, 4), (int64_t)batch * Tn * d);
       return;
     }
     if (w == "conv1") {
@@ -1784,6 +1843,17 @@ int ohw_dbg_dequantize(int device, int ttype, const void* blocks_host, int64_t n
     launch_dequant_blocks(ttype, raw.p, out.as<float>(), n, nullptr);
     HIP_CHECK(hipStreamSynchronize(nullptr));
     HIP_CHECK(hipMemcpy(out_host, out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int ohw_dbg_poison(ohw_state* st, const char* what) {
+  return guard([&] {
+    if (!st || !what) throw Error(OHW_E_INVALID_ARG, "null argument");
+    const std::string w = what;
+    const DevBuf* buf = w == "qkv" ? &st->qkv : w == "att" ? &st->att : nullptr;
+    if (!buf) throw Error(OHW_E_INVALID_ARG, std::string("poison: unknown buffer '") + what + "'");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    HIP_CHECK(hipMemsetAsync(buf->p, 0xff, buf->bytes, st->stream));
   });
 }
 

@@ -161,6 +161,7 @@ static void launch_one(const GemmParams& p, hipStream_t stream) {
 template <typename T>
 void launch_gemm(const GemmParams& p, int epilogue, hipStream_t stream) {
   if (p.M <= 0) return;
+  if (p.c_row_map && (epilogue != EPI_CROSSKV_T || p.t_len <= 0)) throw Error(OHW_E_INVALID_ARG, "gemm: a row map goes with the cross-K/V epilogue only");
   if (p.small_m) { launch_gemm_small<T>(p, epilogue, stream); return; }   // asked for by the caller only (gemm_small.hip)
   // big problems go to the 256x256 direct-to-LDS kernel (gemm256.hip); small N or small M stay here
   // ... and so do problems with fewer 256x256 tiles than half the CUs (one or two 30 s windows): four times as many

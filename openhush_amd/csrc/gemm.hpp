@@ -27,6 +27,9 @@ struct GemmParams {
   int32_t batch_offset;                    // first window of this GEMM's rows inside that decode batch (ohw_encode_slice)
   int32_t group_m;    // gemm256: m-tiles per L2-locality group (set by the launcher)
   int32_t small_m;    // != 0: the 64x64-tile kernel of gemm_small.hip (run_encode sets it for a short window; same bits)
+  // packed-row encoder (EPI_CROSSKV_T only; null: off): output row m is row c_row_map[m] = b * t_len + t of the unpacked batch,
+  // i.e. the store takes (b, rr) from the map instead of from m / rows_per_batch; A stays addressed by m (packed, dense)
+  const int32_t* c_row_map;
 };
 
 // N % 128 == 0, K % 64 == 0, lda/ldc/strides multiples of 8 elements (16-byte rows)

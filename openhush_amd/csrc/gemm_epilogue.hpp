@@ -10,6 +10,10 @@ __device__ __forceinline__ void gemm_store_row(const GemmParams& p, int64_t m, i
   // 64-bit division is ~100 instructions on the GPU and this runs once per output row per lane
   int64_t b = 0, rr = m;
   if (p.rows_per_batch < p.M) { const unsigned bb = (unsigned)m / (unsigned)p.rows_per_batch; b = bb; rr = m - (int64_t)bb * p.rows_per_batch; }
+  if constexpr (EPI == EPI_CROSSKV_T) {
+    // packed rows in, the unpacked cross-K/V layout out: the row's (window, position) comes from the map (gemm.hpp)
+    if (p.c_row_map) { const unsigned q = (unsigned)p.c_row_map[m]; const unsigned bb = q / (unsigned)p.t_len; b = bb; rr = q - bb * (unsigned)p.t_len; }
+  }
   if constexpr (EPI == EPI_BIAS_T || EPI == EPI_BIAS_GELU_T) {
     if constexpr (EPI == EPI_BIAS_GELU_T) {
 #pragma unroll

@@ -170,6 +170,7 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
   const int rc = ohw_state_create(ctx, e->max_batch, &e->state);
   if (rc != OHW_OK) throw Error(rc == OHW_E_OOM ? rc : OHW_E_LOAD_FAILED, "Failed to create state: " + g_last_error);
   e->ctx = ctx;
+  e->packed_encoder = ohw_state_packed_encoder(e->state) == 1;     // OHW_ENC_PACKED
   return e.release();
 }
 
@@ -509,7 +510,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
           while (rc == OHW_OK && (int)e->states.size() < 2) {
             ohw_state* st = nullptr;
             rc = ohw_state_create(e->ctx, e->max_batch, &st);
-            if (rc == OHW_OK) e->states.push_back(st);
+            if (rc == OHW_OK) { (void)ohw_state_set_packed_encoder(st, e->packed_encoder); e->states.push_back(st); }
           }
         }
         if (rc == OHW_OK && schedule == OHW_SCHEDULE_PIPELINE && !e->s_enc) {
@@ -530,6 +531,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
             ohw_state* st = nullptr;
             rc = ohw_state_create(e->ctx, e->lane_capacity, &st);
             if (rc == OHW_OK) {
+              (void)ohw_state_set_packed_encoder(st, e->packed_encoder);
               state_set_graph_max_batch(st, 16);      // see engine.hip: a capture on a lane waits for the other lanes' decodes
               e->lane_states.push_back(st);
             }
@@ -1097,6 +1099,15 @@ int ohw_engine_set_schedule(ohw_engine* e, int schedule, int lanes, int merge) {
 int ohw_engine_set_audio_ctx(ohw_engine* e, int n) {
   if (!e || n < -1 || n > e->ctx->hp.n_audio_ctx) return OHW_E_INVALID_ARG;
   e->audio_ctx = n == e->ctx->hp.n_audio_ctx ? 0 : n;
+  return OHW_OK;
+}
+
+int ohw_engine_set_packed_encoder(ohw_engine* e, int on) {
+  if (!e) return OHW_E_INVALID_ARG;
+  e->packed_encoder = on != 0;
+  (void)ohw_state_set_packed_encoder(e->state, on);
+  for (ohw_state* st : e->states) (void)ohw_state_set_packed_encoder(st, on);
+  for (ohw_state* st : e->lane_states) (void)ohw_state_set_packed_encoder(st, on);
   return OHW_OK;
 }
 

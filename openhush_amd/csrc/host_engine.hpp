@@ -14,6 +14,7 @@ struct ohw_engine {
   int max_batch = 1;
   int window_mode = OHW_WINDOW_FIXED;
   int audio_ctx = 0;                     // ohw_engine_set_audio_ctx: 0 off (full context), n > 0 fixed, -1 auto
+  bool packed_encoder = false;           // ohw_engine_set_packed_encoder: every state of the engine, those made later too
   int force_len = 0;                     // measurement knob (ohw_engine_set_force_len): every window decodes exactly this many tokens
   std::vector<int32_t> last_tokens;
   std::string last_text;

@@ -55,6 +55,11 @@ template <typename T> void launch_mel(const MelParams& p, hipStream_t s);
 template <typename T> void launch_layernorm(const float* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, hipStream_t s,
                                             bool tiled = false);
 template <typename T> void launch_to_f32(const void* src, float* dst, int64_t n, hipStream_t s);
+// packed-row encoder: off i32 [batch + 1] = exclusive prefix sum of win_len (device i32 [batch], each clamped to 0 .. t_len),
+// row_map i32 [off[batch]]: packed row off[b] + t -> unpacked row b * t_len + t
+void launch_pack_map(const int32_t* win_len, int batch, int t_len, int32_t* off, int32_t* row_map, hipStream_t s);
+// dst f32 [rows][d] = the rows row_map[r] of src f32 [..][d]; src and dst must not overlap
+void launch_pack_rows(const float* src, const int32_t* row_map, float* dst, int64_t rows, int d, hipStream_t s);
 
 // ---- decoder step (decode.hip) ---------------------------------------------------------------------
 enum DecEpilogue {

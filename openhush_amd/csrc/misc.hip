@@ -78,6 +78,47 @@ void launch_to_f32(const void* src, float* dst, int64_t n, hipStream_t s) {
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- packed-row encoder (engine.hip run_encode) ----------------------------------------------------------------------
+// one workgroup per window: off[b] = win_len[0] + .. + win_len[b - 1] (every thread sums the at most 256 lengths in front of its
+// window: uniform loads), off[batch] = the packed row count, row_map[off[b] + t] = b * t_len + t for t < win_len[b].  Lengths are
+// clamped to 0 .. t_len, so no index passes batch * t_len whatever the buffer holds.  Plain stores from vector lanes.
+__global__ __launch_bounds__(256) void pack_map_kernel(const int32_t* __restrict__ win_len, int batch, int t_len, int32_t* __restrict__ off,
+                                                       int32_t* __restrict__ row_map) {
+  const int b = blockIdx.x;
+  auto len = [&](int i) { const int n = win_len[i]; return n < 0 ? 0 : n > t_len ? t_len : n; };
+  int o = 0;
+  for (int i = 0; i < b; ++i) o += len(i);
+  const int n = len(b);
+  if (threadIdx.x == 0) {
+    off[b] = o;
+    if (b == batch - 1) off[batch] = o + n;
+  }
+  for (int t = threadIdx.x; t < n; t += 256) row_map[o + t] = b * t_len + t;
+}
+void launch_pack_map(const int32_t* win_len, int batch, int t_len, int32_t* off, int32_t* row_map, hipStream_t s) {
+  if (batch <= 0) return;
+  hipLaunchKernelGGL(pack_map_kernel, dim3((unsigned)batch), dim3(256), 0, s, win_len, batch, t_len, off, row_map);
+  HIP_CHECK(hipGetLastError());
+}
+
+// dst[r][0 .. d) = src[row_map[r]][0 .. d), fp32, one wave per row, 16 bytes per lane: one coalesced pass.  src and dst are two
+// buffers (the caller's choice, engine.hip): a gather in place would overwrite rows of a later window before they are read
+__global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ row_map, float* __restrict__ dst,
+                                                        int64_t rows, int d) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const f32x4* s4 = (const f32x4*)(src + (int64_t)row_map[r] * d);
+  f32x4* d4 = (f32x4*)(dst + r * d);
+  for (int c = lane; c < d / 4; c += 64) d4[c] = s4[c];
+}
+void launch_pack_rows(const float* src, const int32_t* row_map, float* dst, int64_t rows, int d, hipStream_t s) {
+  if (rows <= 0) return;
+  if (d % 4 != 0) throw Error(OHW_E_INVALID_ARG, "pack_rows: d must be a multiple of 4");
+  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, src, row_map, dst, rows, d);
+  HIP_CHECK(hipGetLastError());
+}
+
 #define INST(T) \
   template void launch_layernorm<T>(const float*, const float*, const float*, void*, int64_t, int, hipStream_t, bool); \
   template void launch_to_f32<T>(const void*, float*, int64_t, hipStream_t);

@@ -304,6 +304,14 @@ int ohw_pool_set_audio_ctx(ohw_pool* p, int n) {
   }
   return OHW_OK;
 }
+int ohw_pool_set_packed_encoder(ohw_pool* p, int on) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_packed_encoder(e, on);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
 int ohw_pool_set_schedule(ohw_pool* p, int schedule, int lanes, int merge) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {

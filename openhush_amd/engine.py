@@ -153,6 +153,7 @@ EXPORTS = [
     "ohw_pool_set_fallback_device", "ohw_dequantize_host", "ohw_dbg_dequantize",
     "ohw_state_set_audio_ctx", "ohw_state_audio_ctx", "ohw_audio_ctx_for", "ohw_engine_set_audio_ctx", "ohw_pool_set_audio_ctx", "ohw_dbg_gemm_small",
     "ohw_state_set_window_ctx", "ohw_state_window_ctx", "ohw_engine_transcribe_batch", "ohw_engine_batch_result", "ohw_batch_plan",
+    "ohw_state_set_packed_encoder", "ohw_state_packed_encoder", "ohw_engine_set_packed_encoder", "ohw_pool_set_packed_encoder", "ohw_dbg_poison",
 ]
 
 
@@ -376,6 +377,11 @@ def lib():
         L.ohw_pool_set_audio_ctx.argtypes = [vp, C.c_int]
         L.ohw_state_set_window_ctx.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
         L.ohw_state_window_ctx.argtypes = [vp, C.c_int]
+        L.ohw_state_set_packed_encoder.argtypes = [vp, C.c_int]
+        L.ohw_state_packed_encoder.argtypes = [vp]
+        L.ohw_engine_set_packed_encoder.argtypes = [vp, C.c_int]
+        L.ohw_pool_set_packed_encoder.argtypes = [vp, C.c_int]
+        L.ohw_dbg_poison.argtypes = [vp, C.c_char_p]
         L.ohw_engine_transcribe_batch.argtypes = [vp, C.POINTER(AudioSpan), C.c_int, C.c_uint32]
         L.ohw_engine_batch_result.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(C.c_int32)),
                                               C.POINTER(C.c_int), C.POINTER(C.POINTER(WindowQuality)), C.c_char_p]
@@ -666,7 +672,7 @@ class State:
         _check(lib().ohw_state_set_stream(self.h, C.c_void_p(stream_ptr or 0)))
 
     def counter(self, name: str) -> int:
-        """ohw_dbg_counter: step_captures, beam_captures, step_graphs, beam_graphs, persist_launches, and the decoder
+        """ohw_dbg_counter: step_captures, beam_captures, step_graphs, beam_graphs, persist_launches, enc_rows, and the decoder
         step's kernel-variant tally (dec_gemm.*, xattn.*, self_attn.*: the names are listed in include/ohw.h)"""
         v = int(lib().ohw_dbg_counter(self.h, name.encode()))
         if v < 0:
@@ -805,6 +811,20 @@ class State:
         if v < 0:
             raise ValueError(b)
         return v
+
+    def set_packed_encoder(self, on: bool = True):
+        """ohw_state_set_packed_encoder: an encode under per-window lengths (set_window_ctx) runs the encoder on sum(n_ctx) rows,
+        the windows laid end to end, instead of batch * audio_ctx; same bits, same fetch layouts; no effect without lengths
+        (default off, OHW_ENC_PACKED=1 turns it on for new states)"""
+        _check(lib().ohw_state_set_packed_encoder(self.h, int(bool(on))))
+
+    @property
+    def packed_encoder(self) -> bool:
+        return int(lib().ohw_state_packed_encoder(self.h)) == 1
+
+    def poison(self, what: str):
+        """ohw_dbg_poison (tests): fill the encoder's "qkv" or "att" buffer with NaN"""
+        _check(lib().ohw_dbg_poison(self.h, what.encode()))
 
     def set_persistent(self, on: bool = True):
         """ohw_state_set_persistent: the one-launch decoder step for at most 16 single-token rows (default off: slower than the launches it replaces)"""
@@ -1311,6 +1331,11 @@ class WhisperEngine:
         one window, full context beyond); a fixed context that does not cover a window's audio fails the transcribe"""
         _check(lib().ohw_engine_set_audio_ctx(self.h, _audio_ctx_arg(n)))
 
+    def set_packed_encoder(self, on: bool = True):
+        """ohw_engine_set_packed_encoder: State.set_packed_encoder on every state of the engine; under set_audio_ctx("auto")
+        transcribe_batch then encodes a mixed batch at the sum of its contexts (same tokens, text and quality records)"""
+        _check(lib().ohw_engine_set_packed_encoder(self.h, int(bool(on))))
+
     def last_tokens(self) -> List[int]:
         p = C.POINTER(C.c_int32)()
         n = C.c_int(0)
@@ -1376,6 +1401,10 @@ class EnginePool:
     def set_audio_ctx(self, n):
         """ohw_pool_set_audio_ctx: WhisperEngine.set_audio_ctx on every engine of the pool"""
         _check(lib().ohw_pool_set_audio_ctx(self.h, _audio_ctx_arg(n)))
+
+    def set_packed_encoder(self, on: bool = True):
+        """ohw_pool_set_packed_encoder: WhisperEngine.set_packed_encoder on every engine of the pool"""
+        _check(lib().ohw_pool_set_packed_encoder(self.h, int(bool(on))))
 
     def engine_handle(self, i: int):
         return lib().ohw_pool_engine(self.h, i)

@@ -10,7 +10,9 @@ state's own device times per chunk (encode_ms, decode ms per step).  --batch B l
 --chunk seconds through mel -> encode -> greedy (--tokens forced steps) as ONE batch, --reps times: the server-shaped case.
 --mixed LO:HI (with --batch B): the B chunk lengths are drawn from a seeded uniform range of LO .. HI seconds (--seed) and the
 batch runs three legs, one JSON line each: `ragged` (State.set_window_ctx: every window at audio_ctx_for of its own length
-inside the largest of them), `envelope` (uniform at that largest context) and `off` (the full context); --legs picks a subset.
+inside the largest of them), `envelope` (uniform at that largest context) and `off` (the full context); --legs picks a subset
+and also takes `packed`: the `ragged` leg with State.set_packed_encoder(True), the encoder on sum(n_ctx) rows ("enc_rows").
+--with-long K makes the first K windows of the mix 30 s long (a batch of short chunks behind one long recording).
 LO = HI = 30 is the uniform mix at which `ragged` must not lose to `envelope`.
 --out FILE appends the JSON line to FILE as well (profiles/).
 """
@@ -40,7 +42,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="timed repetitions of the --batch run (after 2 warm-up runs)")
     ap.add_argument("--mixed", default=None, help="LO:HI seconds: per-window chunk lengths from a seeded uniform range (needs --batch)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the --mixed draw")
-    ap.add_argument("--legs", default="ragged,envelope,off", help="legs of a --mixed run, comma separated")
+    ap.add_argument("--legs", default="ragged,envelope,off", help="legs of a --mixed run, comma separated: packed, ragged, envelope, off")
+    ap.add_argument("--with-long", type=int, default=0, help="the first K windows of a --mixed batch are 30 s long")
     ap.add_argument("--out", default=None, help="append the JSON result line to this file")
     a = ap.parse_args()
 
@@ -62,6 +65,7 @@ def main():
             ap.error("--mixed needs --batch B")
         lo, hi = (float(x) for x in a.mixed.split(":"))
         secs = np.random.default_rng(a.seed).uniform(lo, hi, a.batch)
+        secs[:max(0, min(a.with_long, a.batch))] = 30.0
         ns = [int(min(max(x, 0.1), 30.0) * 16000) for x in secs]
         lens = [min(E.audio_ctx_for(x), ctx.hp.n_audio_ctx) for x in ns]
         env = max(lens)
@@ -71,10 +75,11 @@ def main():
         for b in range(a.batch):
             pcm[b, :ns[b]] = synth.synth_audio(40 + b)[:ns[b]]
         for leg in a.legs.split(","):
-            if leg not in ("ragged", "envelope", "off"):
-                ap.error("--legs: ragged, envelope, off")
+            if leg not in ("packed", "ragged", "envelope", "off"):
+                ap.error("--legs: packed, ragged, envelope, off")
             st.set_audio_ctx(0 if leg == "off" else env)
-            st.set_window_ctx(lens if leg == "ragged" else None)
+            st.set_window_ctx(lens if leg in ("ragged", "packed") else None)
+            st.set_packed_encoder(leg == "packed")
             enc, dec, wall, steps = [], [], [], 0
             for r in range(a.reps + 2):
                 t0 = time.perf_counter()
@@ -86,8 +91,9 @@ def main():
                     wall.append(time.perf_counter() - t0); enc.append(t.encode_ms); dec.append(t.decode_ms); steps = t.decode_steps
             E_ = st.audio_ctx
             emit({"workload": f"{a.model} batch of {a.batch} windows of {lo:g} .. {hi:g} s (seed {a.seed}), greedy, {a.tokens} decoder steps, {a.dtype}",
-                  "leg": leg, "envelope": E_, "sum_ctx_over_B_E": round(sum(lens) / (a.batch * E_), 4) if leg == "ragged" else 1.0,
-                  "sum_ctx2_over_B_E2": round(sum(x * x for x in lens) / (a.batch * E_ * E_), 4) if leg == "ragged" else 1.0, "reps": a.reps,
+                  "leg": leg, "envelope": E_, "with_long": a.with_long, "enc_rows": st.counter("enc_rows"),
+                  "sum_ctx_over_B_E": round(sum(lens) / (a.batch * E_), 4) if leg in ("ragged", "packed") else 1.0,
+                  "sum_ctx2_over_B_E2": round(sum(x * x for x in lens) / (a.batch * E_ * E_), 4) if leg in ("ragged", "packed") else 1.0, "reps": a.reps,
                   "encode_ms": {"median": round(float(np.median(enc)), 3), "min": round(min(enc), 3), "max": round(max(enc), 3)},
                   "decode_ms_per_step": {"median": round(float(np.median(dec)) / max(1, steps), 4), "min": round(min(dec) / max(1, steps), 4),
                                          "max": round(max(dec) / max(1, steps), 4)},
