@@ -655,6 +655,38 @@ int ohw_dbg_gemm(int dtype, const void* A, const void* W, const float* bias, voi
 int ohw_dbg_gemm_small(int dtype, const void* A, const void* W, const float* bias, void* out, int64_t M, int64_t N,
                        int64_t K, int epilogue, void* stream);
 int ohw_dbg_attention(int dtype, const void* qkv, void* out, int batch, int T, int n_head, void* stream);
+/* The attention kernels on caller data (tests/test_gpu_attn_needles.py).  Large tensors are device pointers of `dtype`, the
+ * small integer tables are HOST arrays: each entry checks them, copies them to the device, launches, synchronises the stream
+ * and frees its copies.  A table outside the stated ranges is OHW_E_INVALID_ARG before any device work: no launch indexes
+ * outside the caller's buffers.
+ * ohw_dbg_attention_var: the encoder kernel with per-window lengths.  qkv [rows][3 * 64 * n_head], out [rows][64 * n_head].
+ *   win_len [batch], 1 <= win_len[b] <= T: window b attends over its first win_len[b] rows.  win_off null: rows = batch * T,
+ *   window b at row b * T; rows of query blocks (128 rows) wholly past win_len[b] are written as zeros, the other rows past it
+ *   are unspecified.  win_off [batch], the exclusive prefix sum of win_len: packed rows, window b at row win_off[b], rows = the
+ *   sum of the lengths; no other row is stored.  Both null: ohw_dbg_attention.                                               */
+int ohw_dbg_attention_var(int dtype, const void* qkv, void* out, int batch, int T, int n_head, const int32_t* win_len_host,
+                          const int32_t* win_off_host, void* stream);
+/* which kernel a decoder attention launch picked (ohw_dbg_counter's "xattn.*" / "self_attn.*" names, in this order) */
+enum { OHW_XA_PLAIN = 0, OHW_XA_SPLIT, OHW_XA_ROWS2, OHW_XA_ROWS3, OHW_XA_ROWS4, OHW_XA_GROUP2, OHW_XA_GROUP3, OHW_XA_GROUP4,
+       OHW_XA_GROUP5, OHW_XA_GROUP_SPLIT };
+enum { OHW_SA_PLAIN = 0, OHW_SA_SLOTS };
+/* ohw_dbg_cross_attn: q [M][d] row-major (d = 64 * n_head); xk / xv head-major [windows][n_head][t_len][64]; out in the decoder
+ *   GEMMs' activation-tile order, [ceil(M / 16)][d / 32][64][8] elements: element (m, k) at
+ *   ((((m / 16) * (d / 32) + k / 32) * 64 + m % 16 + 16 * ((k % 32) / 8)) * 8) + k % 8; rows >= M are never stored.
+ *   Row m reads window m / n_new, or m / kv_group for kv_group = 2 .. 5 beams per window (then n_new = 1); M % n_new == 0 and
+ *   M % kv_group == 0.  done [windows] or null: the rows of a window with done != 0 are not stored.  win_len [windows] or null,
+ *   1 <= win_len[w] <= t_len: window w's first win_len[w] keys.  partials f32 [max_split_rows][n_head][8][68] and tickets u32
+ *   [max_split_rows][n_head] (zero; the kernel leaves them zero), both or neither: scratch of the split forms; with them,
+ *   without batch_invariant and win_len, M <= max_split_rows.  *variant_out (may be null): OHW_XA_*.
+ * ohw_dbg_self_attn: q [M][d]; k_cache / v_cache [M / n_new][n_head][n_ctx][64]; n_past [M / n_new], 0 <= n_past[b] and
+ *   n_past[b] + n_new <= n_ctx: new token i of window b attends over positions 0 .. n_past[b] + i.  kv_slot
+ *   [M / n_new][n_ctx] or null, entries in 0 .. M / n_new - 1: the cache row that holds position j of window b's sequence.
+ *   out as above.  *variant_out (may be null): OHW_SA_*.                                                                     */
+int ohw_dbg_cross_attn(int dtype, const void* q, const void* xk, const void* xv, void* out, int M, int n_new, int n_head, int t_len,
+                       int kv_group, int batch_invariant, const int32_t* done_host, const int32_t* win_len_host, float* partials,
+                       unsigned* tickets, int max_split_rows, int* variant_out, void* stream);
+int ohw_dbg_self_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past_host, void* out, int M,
+                      int n_new, int n_head, int n_ctx, const int32_t* kv_slot_host, int* variant_out, void* stream);
 /* fill an encoder activation buffer of the state with NaN (every byte 0xff: a NaN in bf16 and in f16): what = "qkv" or "att".
  * An encode overwrites every row it owns, so a test can tell a row that was never written, or written by a neighbour. */
 int ohw_dbg_poison(ohw_state* st, const char* what);

@@ -1866,4 +1866,106 @@ int ohw_dbg_attention(int dtype, const void* qkv, void* out, int batch, int T, i
   });
 }
 
+// the small integer tables of the attention dbg entries arrive as host arrays: checked first, then copied to the device for
+// the launch; the entry synchronises the stream before the copies are freed
+static void dbg_upload(DevBuf& buf, const int32_t* host, size_t n) {
+  buf.alloc(n * sizeof(int32_t));
+  HIP_CHECK(hipMemcpy(buf.p, host, n * sizeof(int32_t), hipMemcpyHostToDevice));
+}
+static void dbg_check_dtype(int dtype, const char* what) {
+  if (dtype != OHW_DTYPE_BF16 && dtype != OHW_DTYPE_F16) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": dtype must be 0 (bf16) or 1 (f16)");
+}
+
+int ohw_dbg_attention_var(int dtype, const void* qkv, void* out, int batch, int T, int n_head, const int32_t* win_len_host,
+                          const int32_t* win_off_host, void* stream) {
+  return guard([&] {
+    dbg_check_dtype(dtype, "dbg_attention_var");
+    if (!qkv || !out || batch < 1 || T < 1 || n_head < 1) throw Error(OHW_E_INVALID_ARG, "dbg_attention_var: null buffer, or batch, T or n_head below 1");
+    if (win_off_host && !win_len_host) throw Error(OHW_E_INVALID_ARG, "dbg_attention_var: packed rows (win_off) need the windows' lengths (win_len)");
+    int64_t sum = 0;
+    for (int b = 0; win_len_host && b < batch; ++b) {
+      if (win_len_host[b] < 1 || win_len_host[b] > T)
+        throw Error(OHW_E_INVALID_ARG, "dbg_attention_var: win_len[" + std::to_string(b) + "] = " + std::to_string(win_len_host[b]) + " is outside 1 .. T = " + std::to_string(T));
+      if (win_off_host && win_off_host[b] != sum)
+        throw Error(OHW_E_INVALID_ARG, "dbg_attention_var: win_off[" + std::to_string(b) + "] = " + std::to_string(win_off_host[b]) +
+                                           " is not the exclusive prefix sum of win_len (" + std::to_string(sum) + ")");
+      sum += win_len_host[b];
+    }
+    DevBuf len, off;
+    if (win_len_host) dbg_upload(len, win_len_host, (size_t)batch);
+    if (win_off_host) dbg_upload(off, win_off_host, (size_t)batch);
+    Dispatch::run(dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      launch_encoder_attention<TT>(qkv, out, batch, T, n_head, (hipStream_t)stream, win_len_host ? len.as<int32_t>() : nullptr,
+                                   win_off_host ? off.as<int32_t>() : nullptr);
+    });
+    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int ohw_dbg_cross_attn(int dtype, const void* q, const void* xk, const void* xv, void* out, int M, int n_new, int n_head, int t_len,
+                       int kv_group, int batch_invariant, const int32_t* done_host, const int32_t* win_len_host, float* partials,
+                       unsigned* tickets, int max_split_rows, int* variant_out, void* stream) {
+  return guard([&] {
+    dbg_check_dtype(dtype, "dbg_cross_attn");
+    if (!q || !xk || !xv || !out || M < 1 || n_new < 1 || n_head < 1 || t_len < 1)
+      throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: null buffer, or M, n_new, n_head or t_len below 1");
+    if (kv_group < 1 || kv_group > 5) throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: kv_group must be 1 .. 5 (beams per window)");
+    if (kv_group > 1 && n_new != 1) throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: beams (kv_group > 1) are single-token rows: n_new must be 1");
+    if (M % n_new != 0) throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: M must be a multiple of n_new");
+    if (kv_group > 1 && M % kv_group != 0) throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: M must be a multiple of kv_group");
+    if ((partials == nullptr) != (tickets == nullptr)) throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: partials and tickets come together");
+    // a split form is picked only with scratch, without batch_invariant and without per-window lengths
+    if (partials && !batch_invariant && !win_len_host && (max_split_rows < 1 || M > max_split_rows))
+      throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: M = " + std::to_string(M) + " rows exceed max_split_rows = " + std::to_string(max_split_rows) +
+                                         ", the rows the partials and tickets hold");
+    const int windows = kv_group > 1 ? M / kv_group : M / n_new;
+    for (int w = 0; win_len_host && w < windows; ++w)
+      if (win_len_host[w] < 1 || win_len_host[w] > t_len)
+        throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn: win_len[" + std::to_string(w) + "] = " + std::to_string(win_len_host[w]) + " is outside 1 .. t_len = " + std::to_string(t_len));
+    DevBuf done, len;
+    if (done_host) dbg_upload(done, done_host, (size_t)windows);
+    if (win_len_host) dbg_upload(len, win_len_host, (size_t)windows);
+    int variant = -1;
+    Dispatch::run(dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      variant = launch_cross_attn<TT>(q, xk, xv, out, M, n_new, n_head, t_len, partials, tickets, max_split_rows,
+                                      done_host ? done.as<int32_t>() : nullptr, (hipStream_t)stream, kv_group, batch_invariant != 0,
+                                      win_len_host ? len.as<int32_t>() : nullptr);
+    });
+    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    if (variant_out) *variant_out = variant;
+  });
+}
+
+int ohw_dbg_self_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past_host, void* out, int M,
+                      int n_new, int n_head, int n_ctx, const int32_t* kv_slot_host, int* variant_out, void* stream) {
+  return guard([&] {
+    dbg_check_dtype(dtype, "dbg_self_attn");
+    if (!q || !k_cache || !v_cache || !n_past_host || !out || M < 1 || n_new < 1 || n_head < 1 || n_ctx < 1)
+      throw Error(OHW_E_INVALID_ARG, "dbg_self_attn: null buffer, or M, n_new, n_head or n_ctx below 1");
+    if (M % n_new != 0) throw Error(OHW_E_INVALID_ARG, "dbg_self_attn: M must be a multiple of n_new");
+    const int rows = M / n_new;
+    for (int b = 0; b < rows; ++b)
+      if (n_past_host[b] < 0 || (int64_t)n_past_host[b] + n_new > n_ctx)
+        throw Error(OHW_E_INVALID_ARG, "dbg_self_attn: n_past[" + std::to_string(b) + "] = " + std::to_string(n_past_host[b]) + " with n_new = " + std::to_string(n_new) +
+                                           " is outside the " + std::to_string(n_ctx) + " positions of the cache");
+    for (int64_t i = 0; kv_slot_host && i < (int64_t)rows * n_ctx; ++i)
+      if (kv_slot_host[i] < 0 || kv_slot_host[i] >= rows)
+        throw Error(OHW_E_INVALID_ARG, "dbg_self_attn: kv_slot[" + std::to_string(i / n_ctx) + "][" + std::to_string(i % n_ctx) + "] = " + std::to_string(kv_slot_host[i]) +
+                                           " names no cache row (0 .. " + std::to_string(rows - 1) + ")");
+    DevBuf past, slots;
+    dbg_upload(past, n_past_host, (size_t)rows);
+    if (kv_slot_host) dbg_upload(slots, kv_slot_host, (size_t)rows * n_ctx);
+    int variant = -1;
+    Dispatch::run(dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      variant = launch_self_attn<TT>(q, k_cache, v_cache, past.as<int32_t>(), out, M, n_new, n_head, n_ctx, (hipStream_t)stream,
+                                     kv_slot_host ? slots.as<int32_t>() : nullptr);
+    });
+    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    if (variant_out) *variant_out = variant;
+  });
+}
+
 }  // extern "C"

@@ -31,6 +31,9 @@ OHW_MEL_REFLECT, OHW_MEL_ZERO_TAIL = 0, 1
 OHW_WINDOW_FIXED, OHW_WINDOW_SEEK, OHW_WINDOW_FIXED_RECORDING_MEL = 0, 1, 2
 OHW_SCHEDULE_SEQUENTIAL, OHW_SCHEDULE_PIPELINE, OHW_SCHEDULE_LANES = 0, 1, 2
 EPI_BIAS_T, EPI_BIAS_GELU_T, EPI_BIAS_RESID_F32, EPI_F32 = 0, 1, 2, 4
+# which kernel ohw_dbg_cross_attn / ohw_dbg_self_attn launched (OHW_XA_* / OHW_SA_*, kernels.hpp's XattnVariant / SelfAttnVariant)
+XA_PLAIN, XA_SPLIT, XA_ROWS2, XA_ROWS3, XA_ROWS4, XA_GROUP2, XA_GROUP3, XA_GROUP4, XA_GROUP5, XA_GROUP_SPLIT = range(10)
+SA_PLAIN, SA_SLOTS = 0, 1
 
 OHW_E_MODEL_NOT_FOUND, OHW_E_LOAD_FAILED, OHW_E_TRANSCRIBE = -3001, -3002, -3003
 OHW_E_NO_GPU, OHW_E_OOM, OHW_E_INVALID_ARG, OHW_E_VALIDATION = -3004, -3005, -3006, -3007
@@ -154,6 +157,7 @@ EXPORTS = [
     "ohw_state_set_audio_ctx", "ohw_state_audio_ctx", "ohw_audio_ctx_for", "ohw_engine_set_audio_ctx", "ohw_pool_set_audio_ctx", "ohw_dbg_gemm_small",
     "ohw_state_set_window_ctx", "ohw_state_window_ctx", "ohw_engine_transcribe_batch", "ohw_engine_batch_result", "ohw_batch_plan",
     "ohw_state_set_packed_encoder", "ohw_state_packed_encoder", "ohw_engine_set_packed_encoder", "ohw_pool_set_packed_encoder", "ohw_dbg_poison",
+    "ohw_dbg_attention_var", "ohw_dbg_cross_attn", "ohw_dbg_self_attn",
 ]
 
 
@@ -369,6 +373,10 @@ def lib():
         L.ohw_dbg_gemm.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp]
         L.ohw_dbg_attention.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]
         L.ohw_dbg_gemm_small.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp]
+        L.ohw_dbg_attention_var.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, vp]
+        L.ohw_dbg_cross_attn.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, vp, vp, C.c_int,
+                                         C.POINTER(C.c_int), vp]
+        L.ohw_dbg_self_attn.argtypes = [C.c_int, vp, vp, vp, ip, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int), vp]
         L.ohw_state_set_audio_ctx.argtypes = [vp, C.c_int]
         L.ohw_state_audio_ctx.argtypes = [vp]
         L.ohw_audio_ctx_for.argtypes = [C.c_int64]
