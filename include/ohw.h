@@ -449,6 +449,33 @@ int ohw_state_window_ctx(const ohw_state* st, int window);   /* the context of a
 int ohw_state_set_packed_encoder(ohw_state* st, int on);
 int ohw_state_packed_encoder(const ohw_state* st);
 
+/* per-window language inside one decode batch (opt-in; with no table every call computes what it computed before).
+ * ohw_state_set_window_lang: lang_ids[b], b < batch, is a language id 0 .. n_langs - 1 ("explicit") or OHW_LANG_DETECT
+ * ("pending": ohw_state_detect_window_lang resolves it); NULL (or batch 0) clears the table.  OHW_E_INVALID_ARG for an id
+ * outside that range, for batch > max_batch and for an English-only model (n_vocab < 51865: its prompt has no language token).
+ * The table lives in device memory; the host keeps only which entries are explicit, pending or resolved.
+ * While a table is set, ohw_greedy, ohw_greedy_ex, ohw_sample_pass and ohw_beam_search ignore p->lang_id: a device kernel
+ * writes window b's prompt row with sot + 1 + table[b] (all beams of a window share it), so detected ids never reach the
+ * host.  The table's batch must equal the decode batch (for ohw_encode_slice: total), and a decode with a pending entry
+ * returns OHW_E_INVALID_ARG - it never silently becomes English.  The prompt is outside the replayed step graphs and the
+ * sampler parameters do not change, so decoding again with other languages captures nothing.
+ * ohw_state_detect_window_lang: for the windows of the last encode, one decoder step on [sot] at position 0 (the step of
+ * ohw_detect_language; it runs under audio_ctx, per-window lengths and the packed encoder as they stand), then the pick on
+ * the state's logits buffer: arg-max over the raw language columns (no logit bias, no filter), the lowest id on ties, and an
+ * fp32 soft-max over those columns.  Only pending entries are resolved; explicit ones are kept.  No logits leave the device.
+ * ohw_state_window_lang: ids_out [batch] (OHW_LANG_DETECT for an entry still pending); probs_out [batch][n_langs] or NULL:
+ * the soft-max of a resolved row, 1 at the id of an explicit row, zeros for a pending row.
+ * Every ohw_encode* turns resolved entries back into pending (they belonged to the old audio); explicit entries persist.
+ * ohw_state_set_audio_ctx and ohw_state_set_window_ctx do not touch the table.                                          */
+enum { OHW_LANG_DETECT = -1 };
+int ohw_state_set_window_lang(ohw_state* st, const int32_t* lang_ids, int batch);
+int ohw_state_detect_window_lang(ohw_state* st, int batch);
+int ohw_state_window_lang(ohw_state* st, int batch, int32_t* ids_out, float* probs_out);
+/* what the device pick computes, on the host: row is one logits row [n_vocab]; *id = arg-max of row[sot + 1 + i], i < n_langs
+ * (the first maximum), probs [n_langs] or NULL = soft-max over those columns in fp32 arithmetic.  No device needed.  A row
+ * whose language columns are all -inf or NaN gives id 0 and NaN probabilities, on the host and on the device alike.        */
+int ohw_lang_pick_host(const float* row, const ohw_special_tokens* tok, int32_t* id, float* probs);
+
 /* per-stage device time of the last calls on this state, in milliseconds (reference logs the     */
 /* same split per job: src/queue/worker.rs:170-180)                                               */
 typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t decode_steps; } ohw_timings;
@@ -553,6 +580,21 @@ int ohw_engine_set_packed_encoder(ohw_engine* e, int on);
 typedef struct { const float* samples; int64_t n; } ohw_audio_span;
 int ohw_engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, uint32_t sample_rate);
 /* result of recording i of the last ohw_engine_transcribe_batch; every out pointer may be NULL; language_out: >= 8 bytes */
+/* language detection in the engine (default 0: language "auto" stays "en", as in the reference).  It applies only when the
+ * engine's language is "auto"; an explicit language is unaffected, and an English-only model stays "en" without a detection.
+ * ohw_engine_transcribe then detects once per call, as whisper.cpp's whisper_full does: before the schedule starts the engine's
+ * own state runs the front end of window 0 alone, under the context window 0 is decoded in (the recording-wide spectrogram in
+ * the recording-mel and seek modes), and ohw_state_detect_window_lang; every window of every schedule runs at that id, so the
+ * tokens are those of an engine created with its code.  language_out reports the code; ohw_engine_last_language the id and
+ * the detection's probability of it (prob 1 when nothing was detected).  ohw_engine_transcribe_batch detects every recording
+ * on its own (all table entries OHW_LANG_DETECT after each batch's encode; greedy pass and ladder decode from the table, the
+ * host-sampled ladder from one read-back per batch); ohw_engine_batch_result's language_out is then each recording's code.
+ * ohw_engine_transcribe_batch_lang: the same call with lang_ids[i] = a language id or OHW_LANG_DETECT per recording, whatever
+ * the engine's language and setting (ignored on an English-only model); NULL = ohw_engine_transcribe_batch.
+ * ohw_pool_set_detect_language: the setting on every engine; the pool detects once, on its first engine, and hands the id on. */
+int ohw_engine_set_detect_language(ohw_engine* e, int on);
+int ohw_engine_last_language(ohw_engine* e, int32_t* id, float* prob);
+int ohw_engine_transcribe_batch_lang(ohw_engine* e, const ohw_audio_span* recs, const int32_t* lang_ids, int n_recs, uint32_t sample_rate);
 int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* text_len, const int32_t** tokens, int* n_tokens,
                             const ohw_window_quality** quality, char* language_out);
 /* host only: how ohw_engine_transcribe_batch batches n_recs recordings of n_samples[i] samples.  order_out [n_recs]: the
@@ -615,7 +657,8 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
-int ohw_pool_set_packed_encoder(ohw_pool* p, int on);                     /* ohw_engine_set_packed_encoder on every engine */
+int ohw_pool_set_packed_encoder(ohw_pool* p, int on);
+int ohw_pool_set_detect_language(ohw_pool* p, int on);                     /* ohw_engine_set_detect_language on every engine */                     /* ohw_engine_set_packed_encoder on every engine */
 /* "" or why the RCCL broadcast was given up for peer copies.  After either kind every replica's weight buffers are compared
  * with device_ids[0]'s (64-bit digests); a mismatch fails ohw_pool_create with OHW_E_LOAD_FAILED naming the device.          */
 const char* ohw_pool_broadcast_note(const ohw_pool* p);
@@ -699,6 +742,9 @@ int ohw_dbg_sample(ohw_state* st, const ohw_sample_params* p, const float* logit
 int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* p, const float* logits, const int32_t* history, int hist_stride,
                      const int32_t* n_hist, int batch, float temperature, const double* uniforms, int32_t* tokens_out,
                      float* logprobs_out, float* no_speech_out);
+/* the DEVICE language pick (ohw_state_detect_window_lang's kernel) on caller-supplied rows: logits [batch][n_vocab] (host);
+ * ids_out [batch], probs_out [batch][n_langs] or NULL.  Leaves the state's language table alone.                       */
+int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* ids_out, float* probs_out);
 /* counters of a state's graph caches: "step_captures" / "beam_captures" (graphs / graph pairs captured so far),
  * "step_graphs" / "beam_graphs" (entries held now), "persist_launches" (persistent decoder steps launched or captured),
  * "enc_rows" (rows M of the dense encoder GEMMs of the last encode: B * E, or the sum of the lengths when it ran packed);

@@ -105,6 +105,18 @@ def _transcribe_ranks(args, audio) -> int:
     if args.language != "auto":
         p.lang_id = E.lang_code_to_id(args.language)
     p.translate = 1 if args.translate else 0
+    lang = "en" if args.language == "auto" else args.language
+    if args.detect_language and args.language == "auto" and ctx.hp.n_vocab >= 51865:
+        # every rank detects on window 0 of the recording: the same arithmetic on the same samples, so the same id everywhere
+        st = E.State(ctx, 1)
+        w0 = audio.samples[:E.CHUNK_SAMPLES]
+        st.mel(w0[None, :], [len(w0)], E.OHW_MEL_ZERO_TAIL, want=False)
+        st.encode(1)
+        st.set_window_lang([E.OHW_LANG_DETECT])
+        st.detect_window_lang(1)
+        p.lang_id = int(st.window_lang(1)[0][0])
+        st.close()
+        lang = E.lang_id_to_code(p.lang_id)
     n_win = (len(audio.samples) + E.CHUNK_SAMPLES - 1) // E.CHUNK_SAMPLES
     t1 = time.perf_counter()
     by_index = args.mel == "recording"
@@ -114,7 +126,6 @@ def _transcribe_ranks(args, audio) -> int:
     dt = time.perf_counter() - t1
     if rank == 0:
         text = b"".join(ctx.token_text(t) for w in wins for t in w if t < ctx.tok.eot).decode("utf-8", "replace").strip()
-        lang = "en" if args.language == "auto" else args.language
         name = args.model or args.model_path.rsplit("/", 1)[-1].replace("ggml-", "").rsplit(".", 1)[0]
         if args.format == "json":
             print(json.dumps({"text": text, "language": lang, "duration_ms": int(dt * 1e3), "audio_duration_secs": audio.duration_secs(),
@@ -155,6 +166,9 @@ def main(argv=None) -> int:
     t.add_argument("--packed-encoder", action="store_true",
                    help="run the encoder on the sum of the windows' contexts when a batch carries per-window contexts (the engine's "
                         "transcribe_batch under --audio-ctx auto); same output, default off")
+    t.add_argument("--detect-language", action="store_true",
+                   help="with --language auto on a multilingual model: detect the language on the first 30 s window and decode in it "
+                        "(default: auto means en, as in the reference); the JSON language field carries the detected code")
     args = ap.parse_args(argv)
 
     from . import engine as E
@@ -188,6 +202,8 @@ def main(argv=None) -> int:
         eng.set_audio_ctx(audio_ctx)
     if args.packed_encoder:
         eng.set_packed_encoder(True)
+    if args.detect_language:
+        eng.set_detect_language(True)
     t1 = time.perf_counter()
     res = eng.transcribe(audio)
     dt = time.perf_counter() - t1

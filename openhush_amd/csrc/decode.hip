@@ -1906,6 +1906,63 @@ void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_window
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- per-window language -------------------------------------------------------------------------------------------------
+// One wave per window: n_langs is 99 or 100, two columns per lane.  The candidates of a lane come in rising index order and
+// the merge prefers the lower index among equal values, so the pick is the host loop's (first maximum).
+__global__ __launch_bounds__(64) void lang_pick_kernel(const float* __restrict__ logits, int64_t ld, int sot, int n_langs,
+                                                       int32_t* __restrict__ lang, float* __restrict__ lang_prob) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (lang[b] != LANG_PENDING) return;      // explicit and resolved entries keep their id and their probabilities
+  const float* row = logits + (int64_t)b * ld + sot + 1;
+  // the lane's two columns stay in registers (the launcher refuses more than 128 languages)
+  const int i0 = lane, i1 = lane + 64;
+  const float v0 = i0 < n_langs ? row[i0] : -INFINITY, v1 = i1 < n_langs ? row[i1] : -INFINITY;
+  float bv = -INFINITY;
+  int bi = n_langs;
+  if (v0 > bv) { bv = v0; bi = i0; }
+  if (v1 > bv) { bv = v1; bi = i1; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  const float e0 = i0 < n_langs ? expf(v0 - bv) : 0.f, e1 = i1 < n_langs ? expf(v1 - bv) : 0.f;
+  const float sum = wave_sum(e0 + e1);
+  if (i0 < n_langs) lang_prob[(int64_t)b * n_langs + i0] = e0 / sum;
+  if (i1 < n_langs) lang_prob[(int64_t)b * n_langs + i1] = e1 / sum;
+  if (lane == 0) lang[b] = bi < n_langs ? bi : 0;
+}
+
+void launch_lang_pick(const float* logits, int64_t ld, int sot, int n_langs, int32_t* lang, float* lang_prob, int batch, hipStream_t s) {
+  if (n_langs > 128) throw Error(OHW_E_INVALID_ARG, "lang_pick: more than 128 languages");
+  if (batch < 1 || n_langs < 1 || sot < 0 || (int64_t)sot + 1 + n_langs > ld) throw Error(OHW_E_INVALID_ARG, "lang_pick: the language columns leave the logits row");
+  hipLaunchKernelGGL(lang_pick_kernel, dim3(batch), dim3(64), 0, s, logits, ld, sot, n_langs, lang, lang_prob);
+  HIP_CHECK(hipGetLastError());
+}
+
+__global__ __launch_bounds__(256) void prompt_fill_kernel(const int32_t* __restrict__ lang, int32_t* __restrict__ step_tok, int batch, int sot,
+                                                          int multilingual, int task, int no_ts) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  const int n_prompt = 1 + (multilingual ? 2 : 0) + (no_ts >= 0 ? 1 : 0);
+  int32_t* out = step_tok + (int64_t)b * n_prompt;
+  int n = 0;
+  out[n++] = sot;
+  if (multilingual) {
+    out[n++] = sot + 1 + lang[b];
+    out[n++] = task;
+  }
+  if (no_ts >= 0) out[n++] = no_ts;
+}
+
+int launch_prompt_fill(const int32_t* lang, int32_t* step_tok, int batch, int sot, int multilingual, int task, int no_ts, hipStream_t s) {
+  if (batch < 1) throw Error(OHW_E_INVALID_ARG, "prompt_fill: empty batch");
+  hipLaunchKernelGGL(prompt_fill_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, lang, step_tok, batch, sot, multilingual, task, no_ts);
+  HIP_CHECK(hipGetLastError());
+  return 1 + (multilingual ? 2 : 0) + (no_ts >= 0 ? 1 : 0);
+}
+
 #define INST(T) \
   template int launch_dec_gemm<T>(const DecGemmParams&, int, hipStream_t); \
   template void launch_embed<T>(const void*, const float*, const int32_t*, const int32_t*, float*, void*, float*, int, int, int, hipStream_t); \

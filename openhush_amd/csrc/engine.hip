@@ -130,6 +130,13 @@ struct ohw_state {
   DevBuf pk_off, pk_map;    // i32 [max_batch + 1], i32 [max_batch * n_audio_ctx]
   std::vector<int64_t> enc_pk;
   int64_t enc_rows = 0;
+  // per-window language (ohw_state_set_window_lang).  lang_tab: one id per decode-batch slot, LANG_PENDING while it waits for a
+  // detection; lang_prob: the soft-max rows the detection wrote.  The decodes build their prompt rows from lang_tab on the
+  // device.  lang_kind is the host's whole knowledge of the table (empty: none set); lang_ids holds the explicit ids only
+  enum LangKind : int8_t { LANG_EXPLICIT, LANG_WAITING, LANG_RESOLVED };
+  std::vector<int8_t> lang_kind;
+  std::vector<int32_t> lang_ids;      // explicit id, else LANG_PENDING: what an encode uploads again
+  DevBuf lang_tab, lang_prob;         // i32 [max_batch], f32 [max_batch][n_langs]
   bool gemm_small = false;  // OHW_GEMM_SMALL=1: short windows take the 64x64-tile encoder GEMM (gemm_small.hip; off until measured)
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -244,6 +251,24 @@ void check_decode_ctx(const ohw_state* st, const char* what) {
   if (st->win_ctx != st->enc_set)
     throw Error(OHW_E_INVALID_ARG, std::string(what) + ": the per-window contexts changed since the last ohw_encode: encode again");
 }
+// a decode under a language table (ohw_state_set_window_lang): the table names exactly the decode batch and nothing waits
+void check_window_lang(const ohw_state* st, int windows, const std::string& what) {
+  if ((int)st->lang_kind.size() != windows)
+    throw Error(OHW_E_INVALID_ARG, what + ": ohw_state_set_window_lang named " + std::to_string(st->lang_kind.size()) + " windows, the decode batch has " +
+                                       std::to_string(windows));
+  for (int b = 0; b < windows; ++b)
+    if (st->lang_kind[(size_t)b] == ohw_state::LANG_WAITING)
+      throw Error(OHW_E_INVALID_ARG, what + ": window " + std::to_string(b) + "'s language is still to be detected: call ohw_state_detect_window_lang first");
+}
+// a new encode: what was detected belonged to the old audio and waits again; explicit entries stay
+void window_lang_after_encode(ohw_state* st) {
+  bool any = false;
+  for (auto& k : st->lang_kind)
+    if (k == ohw_state::LANG_RESOLVED) { k = ohw_state::LANG_WAITING; any = true; }
+  if (!any) return;
+  HIP_CHECK(hipMemcpyAsync(st->lang_tab.p, st->lang_ids.data(), st->lang_ids.size() * 4, hipMemcpyHostToDevice, st->stream));
+  HIP_CHECK(hipStreamSynchronize(st->stream));     // pageable source
+}
 // the mel pass under the state's per-window contexts: they must name exactly its windows
 const int32_t* mel_win_ctx(ohw_state* st, int batch) {
   if (st->win_ctx.empty()) return nullptr;
@@ -302,6 +327,8 @@ void state_alloc(ohw_state* st) {
   st->wc_enc.alloc((size_t)B * 4, true);
   st->wc_dec.alloc((size_t)B * 4, true);
   st->enc_win.assign((size_t)B, 0);
+  st->lang_tab.alloc((size_t)B * 4, true);
+  st->lang_prob.alloc((size_t)B * std::max(1, c->tok.n_langs) * 4, true);
   st->attn_ticket.alloc((size_t)hp.n_text_head * 4, true);
   (void)hipDeviceGetAttribute(&st->n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
   st->postnorm = env_int("OHW_DEC_POSTNORM", 0, 0, 1) != 0 && dec_ksplit_long() == 1 && dec_ksplit_short() == 1 && dt % 32 == 0;
@@ -661,6 +688,13 @@ int build_prompt(const ohw_ctx* c, const ohw_sample_params* sp, int32_t* out) {
   if (sp->no_timestamps) out[n++] = c->tok.no_timestamps;
   return n;
 }
+// the same rows under a language table, written on the device: step_tok[b][0 .. n_prompt) with window b's own language token
+void fill_prompt_rows(ohw_state* st, const ohw_sample_params* sp, int windows, int n_prompt) {
+  const ohw_ctx* c = st->ctx;
+  const int n = launch_prompt_fill(st->lang_tab.as<int32_t>(), st->step_tok.as<int32_t>(), windows, c->tok.sot, c->hp.n_vocab >= 51865 ? 1 : 0,
+                                   sp->translate ? c->tok.translate : c->tok.transcribe, sp->no_timestamps ? c->tok.no_timestamps : -1, st->stream);
+  if (n != n_prompt) throw Error(OHW_E_TRANSCRIBE, "prompt_fill: the device prompt has another length than build_prompt's");
+}
 
 }  // namespace
 
@@ -978,6 +1012,7 @@ int ohw_encode_slice(ohw_state* st, int batch, int first, int total) {
     if (first > 0 && st->enc_var != var)
       throw Error(OHW_E_INVALID_ARG, "encode: the slices of one decode batch run all with or all without per-window contexts");
     HIP_CHECK(hipSetDevice(st->ctx->device));
+    window_lang_after_encode(st);
     HIP_CHECK(hipEventRecord(st->ev[2], st->stream));
     Dispatch::run(st->ctx->dtype, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
@@ -1067,13 +1102,18 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
     if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": batch must equal the batch of the last ohw_encode");
     const ohw_ctx* c = st->ctx;
     check_decode_ctx(st, what);
-    if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": lang_id out of range");
+    // under a language table the rows' language tokens come from device memory and sp->lang_id is ignored
+    const bool lang_tab = !st->lang_kind.empty();
+    if (lang_tab) check_window_lang(st, batch, what);
+    else if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": lang_id out of range");
     if (tp && (!tp->active || !tp->uniforms || !(tp->temperature > 0.0f) || max_tokens < 1))
       throw Error(OHW_E_INVALID_ARG, "sample_pass: needs temperature > 0, active, uniforms and max_tokens >= 1");
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = st->stream;
     int32_t prompt[8];
-    const int n_prompt = build_prompt(c, sp, prompt);
+    ohw_sample_params psp = *sp;
+    if (lang_tab) psp.lang_id = 0;
+    const int n_prompt = build_prompt(c, &psp, prompt);
     const int n_max_raw = sp->force_len > 0 ? sp->force_len : sp->n_max;
     int n_max = std::min(std::min(n_max_raw, st->max_tokens), c->hp.n_text_ctx - n_prompt);
     if (tp) n_max = std::min(n_max, max_tokens);          // a row consumes at most max_tokens draws
@@ -1081,7 +1121,8 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
     std::vector<int32_t> ptoks((size_t)batch * n_prompt);
     for (int b = 0; b < batch; ++b) std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
     if (!tp) HIP_CHECK(hipEventRecord(st->ev[4], s));
-    HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
+    if (lang_tab) fill_prompt_rows(st, &psp, batch, n_prompt);
+    else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)batch * 4, s));
     HIP_CHECK(hipMemsetAsync(st->n_cur.p, 0, (size_t)batch * 4, s));
     // a temperature pass: windows with active[b] == 0 start finished (cross-attention and the sampler skip them)
@@ -1248,7 +1289,9 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
     if (R > st->max_batch) throw Error(OHW_E_INVALID_ARG, "beam search: the state needs max_batch >= n_windows * beam_size decoder rows");
     check_decode_ctx(st, "beam search");
     const ohw_ctx* c = st->ctx;
-    if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, "beam search: lang_id out of range");
+    const bool lang_tab = !st->lang_kind.empty();     // then sp->lang_id is ignored: all K rows of a window share its table entry
+    if (lang_tab) check_window_lang(st, W, "beam search");
+    else if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, "beam search: lang_id out of range");
     if (sp->force_len > 0) throw Error(OHW_E_INVALID_ARG, "beam search: force_len is a greedy-only knob");
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = st->stream;
@@ -1262,13 +1305,16 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
       st->bm_part.alloc((size_t)MB * BEAM_SPLIT * BEAM_PART_WORDS * 4, true); st->bm_ticket.alloc((size_t)MB * 4, true);
     }
     int32_t prompt[8];
-    const int n_prompt = build_prompt(c, sp, prompt);
+    ohw_sample_params psp = *sp;
+    if (lang_tab) psp.lang_id = 0;
+    const int n_prompt = build_prompt(c, &psp, prompt);
     const int n_max = std::min(std::min(sp->n_max, MT), C - n_prompt);
     if (n_max < 1) throw Error(OHW_E_INVALID_ARG, "beam search: n_max < 1");
     std::vector<int32_t> ptoks((size_t)W * n_prompt), np0((size_t)W, n_prompt - 1);
     for (int w = 0; w < W; ++w) std::memcpy(&ptoks[(size_t)w * n_prompt], prompt, (size_t)n_prompt * 4);
     HIP_CHECK(hipEventRecord(st->ev[4], s));
-    HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
+    if (lang_tab) fill_prompt_rows(st, &psp, W, n_prompt);
+    else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)MB * 4, s));
     HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
     for (DevBuf* b : {&st->bm_sum, &st->bm_ncur, &st->bm_done, &st->bm_fin_cnt, &st->bm_fin_len}) HIP_CHECK(hipMemsetAsync(b->p, 0, (size_t)MB * 4, s));
@@ -1502,6 +1548,103 @@ int ohw_state_set_window_ctx(ohw_state* st, const int32_t* n_ctx, int batch) {
 int ohw_state_window_ctx(const ohw_state* st, int window) {
   if (!st || window < 0 || window >= st->max_batch) return OHW_E_INVALID_ARG;
   return st->enc_var && window < st->enc_batch ? st->enc_win[(size_t)window] : audio_ctx_of(st);
+}
+
+int ohw_state_set_window_lang(ohw_state* st, const int32_t* lang_ids, int batch) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    if (!lang_ids || batch == 0) { st->lang_kind.clear(); st->lang_ids.clear(); return; }
+    const ohw_ctx* c = st->ctx;
+    if (c->hp.n_vocab < 51865) throw Error(OHW_E_INVALID_ARG, "window_lang: an English-only model has no language token");
+    if (batch < 0 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "window_lang: batch exceeds the state's max_batch");
+    for (int b = 0; b < batch; ++b)
+      if (lang_ids[b] != OHW_LANG_DETECT && (lang_ids[b] < 0 || lang_ids[b] >= c->tok.n_langs))
+        throw Error(OHW_E_INVALID_ARG, "window_lang: window " + std::to_string(b) + " asks for language id " + std::to_string(lang_ids[b]) + " (0.." +
+                                           std::to_string(c->tok.n_langs - 1) + ", or OHW_LANG_DETECT)");
+    static_assert(OHW_LANG_DETECT == LANG_PENDING, "the table stores OHW_LANG_DETECT as it is given");
+    HIP_CHECK(hipSetDevice(c->device));
+    // in stream order behind the kernels that still read the previous table; the source is the caller's memory, so wait
+    HIP_CHECK(hipMemcpyAsync(st->lang_tab.p, lang_ids, (size_t)batch * 4, hipMemcpyHostToDevice, st->stream));
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    st->lang_ids.assign(lang_ids, lang_ids + batch);
+    st->lang_kind.resize((size_t)batch);
+    for (int b = 0; b < batch; ++b) st->lang_kind[(size_t)b] = lang_ids[b] == OHW_LANG_DETECT ? ohw_state::LANG_WAITING : ohw_state::LANG_EXPLICIT;
+  });
+}
+
+int ohw_state_detect_window_lang(ohw_state* st, int batch) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    if (st->lang_kind.empty()) throw Error(OHW_E_INVALID_ARG, "detect_window_lang: no language table is set (ohw_state_set_window_lang)");
+    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "detect_window_lang: batch must equal the batch of the last ohw_encode");
+    if ((int)st->lang_kind.size() != batch)
+      throw Error(OHW_E_INVALID_ARG, "detect_window_lang: ohw_state_set_window_lang named " + std::to_string(st->lang_kind.size()) + " windows, the batch has " +
+                                         std::to_string(batch));
+    check_decode_ctx(st, "detect_window_lang");
+    bool waiting = false;
+    for (int8_t k : st->lang_kind) waiting = waiting || k == ohw_state::LANG_WAITING;
+    if (!waiting) return;
+    const ohw_ctx* c = st->ctx;
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = st->stream;
+    // the step of ohw_detect_language: [sot] at position 0 for every window of the batch
+    const std::vector<int32_t> toks((size_t)batch, c->tok.sot);
+    HIP_CHECK(hipMemcpyAsync(st->step_tok.p, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)batch * 4, s));
+    Dispatch::run(c->dtype, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      run_decoder_step<T>(st, batch, 1);
+    });
+    launch_lang_pick(st->logits.as<float>(), st->logits_ld, c->tok.sot, c->tok.n_langs, st->lang_tab.as<int32_t>(), st->lang_prob.as<float>(), batch, s);
+    HIP_CHECK(hipStreamSynchronize(s));     // toks is a stack-lifetime source
+    persist_check(st);
+    for (auto& k : st->lang_kind)
+      if (k == ohw_state::LANG_WAITING) k = ohw_state::LANG_RESOLVED;
+  });
+}
+
+int ohw_state_window_lang(ohw_state* st, int batch, int32_t* ids_out, float* probs_out) {
+  return guard([&] {
+    if (!st || !ids_out) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (st->lang_kind.empty()) throw Error(OHW_E_INVALID_ARG, "window_lang: no language table is set (ohw_state_set_window_lang)");
+    if (batch != (int)st->lang_kind.size()) throw Error(OHW_E_INVALID_ARG, "window_lang: batch must equal the batch of ohw_state_set_window_lang");
+    const int nl = st->ctx->tok.n_langs;
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    HIP_CHECK(hipMemcpyAsync(ids_out, st->lang_tab.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+    if (probs_out) HIP_CHECK(hipMemcpyAsync(probs_out, st->lang_prob.p, (size_t)batch * nl * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (!probs_out) return;
+    for (int b = 0; b < batch; ++b) {
+      if (st->lang_kind[(size_t)b] == ohw_state::LANG_RESOLVED) continue;
+      float* row = probs_out + (size_t)b * nl;
+      std::fill(row, row + nl, 0.f);
+      if (st->lang_kind[(size_t)b] == ohw_state::LANG_EXPLICIT) row[ids_out[b]] = 1.f;
+    }
+  });
+}
+
+// test entry: the device language pick on caller-supplied rows, logits [batch][n_vocab] (host), with a table of its own
+int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* ids_out, float* probs_out) {
+  return guard([&] {
+    if (!st || !logits || !ids_out) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (batch < 1 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "dbg_lang_pick: batch exceeds the state's max_batch");
+    const ohw_ctx* c = st->ctx;
+    const int V = c->hp.n_vocab, nl = c->tok.n_langs;
+    if (V < 51865) throw Error(OHW_E_INVALID_ARG, "dbg_lang_pick: an English-only model has no language tokens");
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = st->stream;
+    DevBuf tab, prob;
+    tab.alloc((size_t)batch * 4);
+    prob.alloc((size_t)batch * nl * 4);       // the kernel writes every element of a pending row
+    const std::vector<int32_t> pending((size_t)batch, LANG_PENDING);
+    HIP_CHECK(hipMemcpyAsync(tab.p, pending.data(), pending.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpy2DAsync(st->logits.p, (size_t)st->logits_ld * 4, logits, (size_t)V * 4, (size_t)V * 4, (size_t)batch, hipMemcpyHostToDevice, s));
+    launch_lang_pick(st->logits.as<float>(), st->logits_ld, c->tok.sot, nl, tab.as<int32_t>(), prob.as<float>(), batch, s);
+    HIP_CHECK(hipMemcpyAsync(ids_out, tab.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+    if (probs_out) HIP_CHECK(hipMemcpyAsync(probs_out, prob.p, (size_t)batch * nl * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
 }
 
 int32_t ohw_audio_ctx_for(int64_t n_samples) {

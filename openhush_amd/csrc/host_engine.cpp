@@ -174,8 +174,39 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
   return e.release();
 }
 
+bool engine_detects(const ohw_engine* e) { return e->detect_language && e->language == "auto" && e->ctx->hp.n_vocab >= 51865; }
+
+int32_t engine_detect_first_window(ohw_engine* e, const float* samples, int64_t n, float* prob) {
+  auto check = [&](int rc) { if (rc != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Language detection failed: " + g_last_error); };
+  if (prob) *prob = 0.f;
+  if (mel_frames(n) < 100) return 0;          // less than 1 s: the call yields nothing, whatever the language
+  const int full_ctx = e->ctx->hp.n_audio_ctx;
+  const int call_ctx = e->audio_ctx > 0 ? e->audio_ctx : (e->audio_ctx < 0 && n <= CHUNK_SAMPLES) ? std::min<int>(ohw_audio_ctx_for(n), full_ctx) : 0;
+  ohw_state* st = e->state;
+  check(ohw_state_set_stream(st, nullptr));
+  check(ohw_state_set_audio_ctx(st, call_ctx));
+  if (e->window_mode == OHW_WINDOW_FIXED) {
+    const int32_t n0 = (int32_t)std::min<int64_t>(CHUNK_SAMPLES, n);
+    check(ohw_mel(st, samples, n0, &n0, 1, 0, OHW_MEL_ZERO_TAIL, nullptr));
+  } else {
+    const int32_t seek0 = 0;
+    check(ohw_recording_set(st, samples, n, 0, nullptr));
+    check(ohw_mel_seek(st, &seek0, 1, nullptr));
+  }
+  check(ohw_encode(st, 1));
+  struct Clear { ohw_state* st; ~Clear() { (void)ohw_state_set_window_lang(st, nullptr, 0); } } clear{st};
+  int32_t id = OHW_LANG_DETECT;
+  check(ohw_state_set_window_lang(st, &id, 1));
+  check(ohw_state_detect_window_lang(st, 1));
+  std::vector<float> probs((size_t)e->ctx->tok.n_langs);
+  check(ohw_state_window_lang(st, 1, &id, probs.data()));
+  if (id < 0 || id >= e->ctx->tok.n_langs) throw Error(OHW_E_TRANSCRIBE, "Language detection failed: no id");
+  if (prob) *prob = probs[(size_t)id];
+  return id;
+}
+
 void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text_out, int64_t win_first, int64_t win_step,
-                            const ohw_audio_span* recs, int n_recs) {
+                            const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs) {
   std::string own_text;
   std::string& text = text_out ? *text_out : own_text;
   if (win_first < 0 || win_step < 1) throw Error(OHW_E_INVALID_ARG, "transcribe: window dealing must be first >= 0, step >= 1");
@@ -189,6 +220,17 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
     if (e->force_len > 0) { sp.force_len = std::min(e->force_len, sp.n_max); sp.n_max = sp.force_len; }      // bench: fixed decode length
     const ohw_special_tokens& tk = e->ctx->tok;
     if (sp.lang_id >= tk.n_langs) throw Error(OHW_E_TRANSCRIBE, "language is not supported by this model");
+    // ohw_engine_set_detect_language: one detection per call, on the first window (or the id the pool detected); every window
+    // of every schedule then runs at that id, exactly as an engine created with its code
+    e->last_lang_id = sp.lang_id;
+    e->last_lang_prob = 1.f;
+    if (!recs && engine_detects(e)) {
+      if (e->given_lang >= 0) { e->last_lang_id = e->given_lang; e->last_lang_prob = e->given_prob; }
+      else e->last_lang_id = engine_detect_first_window(e, samples, n, &e->last_lang_prob);
+      sp.lang_id = e->last_lang_id;
+    }
+    // ohw_engine_transcribe_batch with languages per recording: the ids of the batch being decoded (empty: sp.lang_id for all)
+    std::vector<int32_t> batch_lang;
 
     e->last_tokens.clear();
     e->last_quality.clear();
@@ -283,7 +325,10 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         } else {
           logits.resize((size_t)B * V);
           std::vector<int32_t> ptoks((size_t)B * n_prompt), past((size_t)B, 0), feed((size_t)B, tk.eot), npast((size_t)B, n_prompt), live = active;
-          for (int b = 0; b < B; ++b) std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
+          for (int b = 0; b < B; ++b) {
+            std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
+            if (!batch_lang.empty() && V >= 51865) ptoks[(size_t)b * n_prompt + 1] = tk.sot + 1 + batch_lang[(size_t)b];   // the table's ids, read back once per batch
+          }
           check(ohw_decode_active(st, ptoks.data(), n_prompt, past.data(), B, active.data(), logits.data()));
           for (int i = 0; i < n_max; ++i) {
             bool any_live = false;
@@ -394,11 +439,21 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       struct Restore {
         ohw_engine* e;
         explicit Restore(ohw_engine* e_) : e(e_) { (void)ohw_state_set_batch_invariant(e->state, 1); }
-        ~Restore() { (void)ohw_state_set_window_ctx(e->state, nullptr, 0); (void)ohw_state_set_batch_invariant(e->state, 0); }
+        ~Restore() {
+          (void)ohw_state_set_window_ctx(e->state, nullptr, 0); (void)ohw_state_set_batch_invariant(e->state, 0);
+          (void)ohw_state_set_window_lang(e->state, nullptr, 0);
+        }
       } restore_state(e);
       Scratch sc(MB, max_tok);
       std::vector<float> stage;
       std::vector<int32_t> ns((size_t)MB), wl((size_t)MB);
+      // a language per recording: the caller's ids, or a detection per recording when the engine detects; an English-only model
+      // has no language token and stays as it is
+      const bool per_rec = V >= 51865 && (rec_langs != nullptr || engine_detects(e));
+      if (rec_langs)
+        for (int i = 0; i < n_recs; ++i)
+          if (rec_langs[i] != OHW_LANG_DETECT && (rec_langs[i] < 0 || rec_langs[i] >= tk.n_langs))
+            throw Error(OHW_E_INVALID_ARG, "transcribe_batch: recording " + std::to_string(i) + " asks for language id " + std::to_string(rec_langs[i]));
       for (int bi = 0; bi < n_b; ++bi) {
         const int B = std::min(MB, n_recs - bi * MB);
         const int32_t* ord = &order[(size_t)bi * MB];
@@ -416,6 +471,17 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         check(ohw_state_set_window_ctx(e->state, ragged ? wl.data() : nullptr, ragged ? B : 0));
         check(ohw_mel(e->state, stage.data(), stride, ns.data(), B, 0, OHW_MEL_ZERO_TAIL, nullptr));
         check(ohw_encode(e->state, B));
+        if (per_rec) {
+          batch_lang.assign((size_t)B, OHW_LANG_DETECT);
+          bool any_detect = false;
+          for (int b = 0; b < B; ++b) {
+            if (rec_langs) batch_lang[(size_t)b] = rec_langs[ord[b]];
+            any_detect = any_detect || batch_lang[(size_t)b] == OHW_LANG_DETECT;
+          }
+          check(ohw_state_set_window_lang(e->state, batch_lang.data(), B));
+          if (any_detect) check(ohw_state_detect_window_lang(e->state, B));
+          check(ohw_state_window_lang(e->state, B, batch_lang.data(), nullptr));      // the one read-back of the batch
+        }
         decode_windows(sc, e->state, (int64_t)bi * MB, B, ns.data());
         sc.trace.clear();
         for (int b = 0; b < B; ++b) {
@@ -426,6 +492,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
           r.text = b0 == std::string::npos ? std::string() : text.substr(b0, b1 - b0 + 1);
           r.tokens = e->last_tokens;
           r.quality = e->last_quality[0];
+          r.lang_id = per_rec ? batch_lang[(size_t)b] : -1;
         }
       }
       text.clear(); e->last_tokens.clear(); e->last_quality.clear();
@@ -903,6 +970,24 @@ int ohw_detect_language(ohw_state* st, int batch, int32_t* lang_ids_out, float* 
   });
 }
 
+// the definition of lang_pick_kernel's result (decode.hip): the first maximum of the raw language columns and their soft-max
+// in fp32 (ohw_detect_language above keeps its double sums: its results must not move)
+int ohw_lang_pick_host(const float* row, const ohw_special_tokens* tok, int32_t* id, float* probs) {
+  if (!row || !tok || !id || tok->n_langs < 1) return OHW_E_INVALID_ARG;
+  const float* lg = row + tok->sot + 1;
+  const int nl = tok->n_langs;
+  float mx = -INFINITY;
+  int best = 0;
+  for (int i = 0; i < nl; ++i) if (lg[i] > mx) { mx = lg[i]; best = i; }
+  *id = best;
+  if (probs) {
+    float sum = 0.f;
+    for (int i = 0; i < nl; ++i) sum += std::exp(lg[i] - mx);
+    for (int i = 0; i < nl; ++i) probs[i] = std::exp(lg[i] - mx) / sum;
+  }
+  return OHW_OK;
+}
+
 int ohw_engine_new(const char* model_path, const char* language, int translate, int use_gpu, int device, int dtype, int max_batch,
                    ohw_engine** out) {
   return guard([&] {
@@ -980,8 +1065,9 @@ int ohw_engine_transcribe(ohw_engine* e, const float* samples, int64_t n, uint32
       text_buf[ncopy] = 0;
     }
     if (language_out) {
-      // reference :288-296: "auto" reports the state's language id (whisper.cpp default "en" -> 0)
-      const std::string lang = e->language == "auto" ? ohw_lang_id_to_code(0) : e->language;
+      // reference :288-296: "auto" reports the state's language id (whisper.cpp default "en" -> 0; the detected one with
+      // ohw_engine_set_detect_language)
+      const std::string lang = e->language == "auto" ? ohw_lang_id_to_code(e->last_lang_id) : e->language;
       std::strncpy(language_out, lang.c_str(), 7);
       language_out[7] = 0;
     }
@@ -1015,6 +1101,23 @@ int ohw_batch_plan(const int64_t* n_samples, int n_recs, int max_batch, int audi
 }
 
 int ohw_engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, uint32_t sample_rate) {
+  return ohw_engine_transcribe_batch_lang(e, recs, nullptr, n_recs, sample_rate);
+}
+
+int ohw_engine_set_detect_language(ohw_engine* e, int on) {
+  if (!e) return OHW_E_INVALID_ARG;
+  e->detect_language = on != 0;
+  return OHW_OK;
+}
+
+int ohw_engine_last_language(ohw_engine* e, int32_t* id, float* prob) {
+  if (!e) return OHW_E_INVALID_ARG;
+  if (id) *id = e->last_lang_id;
+  if (prob) *prob = e->last_lang_prob;
+  return OHW_OK;
+}
+
+int ohw_engine_transcribe_batch_lang(ohw_engine* e, const ohw_audio_span* recs, const int32_t* lang_ids, int n_recs, uint32_t sample_rate) {
   return guard([&] {
     if (!e || !recs || n_recs < 1) throw Error(OHW_E_INVALID_ARG, "transcribe_batch: null engine or no recordings");
     if (e->window_mode != OHW_WINDOW_FIXED) throw Error(OHW_E_INVALID_ARG, "transcribe_batch: recordings are cut as OHW_WINDOW_FIXED cuts; set that window mode");
@@ -1027,7 +1130,7 @@ int ohw_engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n
         throw Error(OHW_E_VALIDATION, "Audio validation failed for recording " + std::to_string(i) + ": " + names[info.error]);
       }
     }
-    engine_transcribe_core(e, nullptr, 0, nullptr, 0, 1, recs, n_recs);
+    engine_transcribe_core(e, nullptr, 0, nullptr, 0, 1, recs, n_recs, lang_ids);
   });
 }
 
@@ -1043,7 +1146,7 @@ int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* tex
     if (n_tokens) *n_tokens = (int)r.tokens.size();
     if (quality) *quality = &r.quality;
     if (language_out) {
-      const std::string lang = e->language == "auto" ? ohw_lang_id_to_code(0) : e->language;
+      const std::string lang = r.lang_id >= 0 ? ohw_lang_id_to_code(r.lang_id) : e->language == "auto" ? ohw_lang_id_to_code(0) : e->language;
       std::strncpy(language_out, lang.c_str(), 7);
       language_out[7] = 0;
     }

@@ -35,8 +35,17 @@ struct ohw_engine {
   bool fallback_device = false;          // the temperature ladder samples on the device (ohw_engine_set_fallback_device)
   std::vector<int32_t> last_trace;   // every decode pass of the last transcribe: {window, temperature * 1000, n, tokens...}
   // ohw_engine_transcribe_batch: one record per recording, in submission order (ohw_engine_batch_result)
-  struct BatchRecord { std::string text; std::vector<int32_t> tokens; ohw_window_quality quality{}; };
+  // lang_id: the language the recording was decoded in when it had one of its own (detected or caller-given), else -1
+  struct BatchRecord { std::string text; std::vector<int32_t> tokens; ohw_window_quality quality{}; int32_t lang_id = -1; };
   std::vector<BatchRecord> batch_records;
+  // language detection (ohw_engine_set_detect_language; only with language "auto" on a multilingual model).  given_lang: the pool
+  // detected on its first engine and hands the id to this one (-1: detect yourself).  last_lang_id / last_lang_prob: what the
+  // last transcribe decoded in and the detection's probability of it (1 when nothing was detected)
+  bool detect_language = false;
+  int32_t given_lang = -1;
+  float given_prob = 0.f;
+  int32_t last_lang_id = 0;
+  float last_lang_prob = 1.f;
 };
 
 
@@ -48,6 +57,13 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
 // (the pool's round-robin deal); the records it leaves (last_tokens / last_quality) list its own windows in that order
 // recs != nullptr (ohw_engine_transcribe_batch; samples / n / text unused): n_recs validated recordings of at most one window each,
 // batched longest first on the engine's own state and decoded by the same per-window code; fills e->batch_records
+// rec_langs (with recs; may be null): one language id or OHW_LANG_DETECT per recording
 void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text, int64_t win_first = 0, int64_t win_step = 1,
-                            const ohw_audio_span* recs = nullptr, int n_recs = 0);
+                            const ohw_audio_span* recs = nullptr, int n_recs = 0, const int32_t* rec_langs = nullptr);
+// does a transcribe of this engine detect?  (the setting, language "auto", a multilingual model)
+bool engine_detects(const ohw_engine* e);
+// whisper.cpp detects once per whisper_full call, on the first window: the front end of window 0 of the recording alone on the
+// engine's own state, under the context window 0 will be decoded in (recording-wide spectrogram in the recording-mel and seek
+// modes), then ohw_state_detect_window_lang.  Returns the id, its probability in *prob; throws Error
+int32_t engine_detect_first_window(ohw_engine* e, const float* samples, int64_t n, float* prob);
 }  // namespace ohw

@@ -212,4 +212,14 @@ void launch_sampler(const SamplerParams& p, hipStream_t s);
 // uniforms [batch][p.max_tokens] (the canonical double of step n_cur of row b) are read from device memory
 void launch_sampler_t(const SamplerParams& p, const float* temperature, const double* uniforms, hipStream_t s);
 
+// ---- per-window language (decode.hip; ohw_state_set_window_lang) -------------------------------------------------------
+constexpr int32_t LANG_PENDING = -1;   // table entry that waits for a detection (OHW_LANG_DETECT)
+// one workgroup per window whose table entry lang[b] is LANG_PENDING (the others are left alone): over the raw columns
+// logits[b * ld + sot + 1 + i], i < n_langs (no bias, no filter), lang[b] = the arg-max, the lowest index on ties, and
+// lang_prob[b][0 .. n_langs) = the fp32 soft-max over those columns only (n_langs <= 128: two columns per lane).  ohw_lang_pick_host (host_engine.cpp) defines the result
+void launch_lang_pick(const float* logits, int64_t ld, int sot, int n_langs, int32_t* lang, float* lang_prob, int batch, hipStream_t s);
+// step_tok[b][0 .. n_prompt) = {sot, then sot + 1 + lang[b] and task when multilingual, then no_ts when no_ts >= 0} for b < batch:
+// the prompt rows of a decode under a language table, built where the table lives.  Returns n_prompt
+int launch_prompt_fill(const int32_t* lang, int32_t* step_tok, int batch, int sot, int multilingual, int task, int no_ts, hipStream_t s);
+
 }  // namespace ohw

@@ -36,6 +36,7 @@ struct ohw_pool {
   std::vector<ohw_engine*> engines;    // engines[0] owns the context that read the file (and the vocabulary)
   std::vector<int> devices;
   std::string language;
+  int32_t last_lang_id = 0;            // what the last transcribe decoded in (detected with ohw_pool_set_detect_language)
   std::string last_text, broadcast;    // broadcast: "none" | "rccl" | "peer"
   std::string broadcast_note;          // why RCCL was given up, if it was
   std::vector<int32_t> last_tokens;
@@ -312,6 +313,14 @@ int ohw_pool_set_packed_encoder(ohw_pool* p, int on) {
   }
   return OHW_OK;
 }
+int ohw_pool_set_detect_language(ohw_pool* p, int on) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_detect_language(e, on);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
 int ohw_pool_set_schedule(ohw_pool* p, int schedule, int lanes, int merge) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {
@@ -358,6 +367,17 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
     std::vector<std::thread> th;
     const bool seek = mode == OHW_WINDOW_SEEK;     // the seek loop is sequential by nature: device 0 alone
     const int used = seek ? 1 : (int)std::min<int64_t>(G, n_win);
+    // language detection: once, on the first engine, window 0 of the recording; the id goes to every engine that takes windows
+    struct Given {
+      ohw_pool* p;
+      ~Given() { for (ohw_engine* e : p->engines) e->given_lang = -1; }
+    } given{p};
+    if (engine_detects(p->engines[0])) {
+      float prob = 0.f;
+      int32_t id = 0;
+      id = engine_detect_first_window(p->engines[0], samples, n, &prob);     // C-ABI entries only: each takes the gate itself
+      for (ohw_engine* e : p->engines) { e->given_lang = id; e->given_prob = prob; }
+    }
     for (int g = 0; g < used; ++g) {
       th.emplace_back([&, g] {
         try {
@@ -403,8 +423,9 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
       std::memcpy(text_buf, text.data(), nc);
       text_buf[nc] = 0;
     }
+    p->last_lang_id = used > 0 ? p->engines[0]->last_lang_id : 0;
     if (language_out) {
-      const std::string lang = p->language == "auto" ? ohw_lang_id_to_code(0) : p->language;
+      const std::string lang = p->language == "auto" ? ohw_lang_id_to_code(p->last_lang_id) : p->language;
       std::strncpy(language_out, lang.c_str(), 7);
       language_out[7] = 0;
     }

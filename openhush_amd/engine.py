@@ -158,6 +158,8 @@ EXPORTS = [
     "ohw_state_set_window_ctx", "ohw_state_window_ctx", "ohw_engine_transcribe_batch", "ohw_engine_batch_result", "ohw_batch_plan",
     "ohw_state_set_packed_encoder", "ohw_state_packed_encoder", "ohw_engine_set_packed_encoder", "ohw_pool_set_packed_encoder", "ohw_dbg_poison",
     "ohw_dbg_attention_var", "ohw_dbg_cross_attn", "ohw_dbg_self_attn",
+    "ohw_engine_set_detect_language", "ohw_engine_last_language", "ohw_engine_transcribe_batch_lang", "ohw_pool_set_detect_language",
+    "ohw_state_set_window_lang", "ohw_state_detect_window_lang", "ohw_state_window_lang", "ohw_lang_pick_host", "ohw_dbg_lang_pick",
 ]
 
 
@@ -395,11 +397,33 @@ def lib():
                                               C.POINTER(C.c_int), C.POINTER(C.POINTER(WindowQuality)), C.c_char_p]
         L.ohw_batch_plan.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32)]
+        L.ohw_engine_set_detect_language.argtypes = [vp, C.c_int]
+        L.ohw_engine_last_language.argtypes = [vp, ip, fp]
+        L.ohw_engine_transcribe_batch_lang.argtypes = [vp, C.POINTER(AudioSpan), ip, C.c_int, C.c_uint32]
+        L.ohw_pool_set_detect_language.argtypes = [vp, C.c_int]
+        L.ohw_state_set_window_lang.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
+        L.ohw_state_detect_window_lang.argtypes = [vp, C.c_int]
+        L.ohw_state_window_lang.argtypes = [vp, C.c_int, ip, fp]
+        L.ohw_lang_pick_host.argtypes = [fp, C.POINTER(SpecialTokens), ip, fp]
+        L.ohw_dbg_lang_pick.argtypes = [vp, fp, C.c_int, ip, fp]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
         L.ohw_dequantize_host.argtypes = [C.c_int, vp, C.c_int64, fp]
         L.ohw_dbg_dequantize.argtypes = [C.c_int, C.c_int, vp, C.c_int64, fp]
         _lib = L
     return _lib
+
+
+OHW_LANG_DETECT = -1
+
+
+def lang_pick_host(row: np.ndarray, tok: "SpecialTokens"):
+    """ohw_lang_pick_host (host only): one logits row [n_vocab] -> (id, probs [n_langs]); the definition of the device pick"""
+    r = np.ascontiguousarray(row, dtype=np.float32)
+    assert r.ndim == 1 and r.size >= tok.sot + 1 + tok.n_langs
+    i = C.c_int32(0)
+    probs = np.zeros(tok.n_langs, dtype=np.float32)
+    _check(lib().ohw_lang_pick_host(_fp(r), C.byref(tok), C.byref(i), _fp(probs)))
+    return int(i.value), probs
 
 
 def audio_ctx_for(n_samples: int) -> int:
@@ -830,6 +854,36 @@ class State:
     def packed_encoder(self) -> bool:
         return int(lib().ohw_state_packed_encoder(self.h)) == 1
 
+    def set_window_lang(self, lang_ids: Optional[Sequence[int]]):
+        """ohw_state_set_window_lang: one language id per decode-batch slot, or OHW_LANG_DETECT (-1) for an entry that
+        detect_window_lang() resolves; None clears the table.  While it is set the decodes ignore p.lang_id"""
+        if lang_ids is None or len(lang_ids) == 0:
+            _check(lib().ohw_state_set_window_lang(self.h, C.cast(None, C.POINTER(C.c_int32)), 0))
+            return
+        a = np.ascontiguousarray(lang_ids, dtype=np.int32)
+        _check(lib().ohw_state_set_window_lang(self.h, _ip(a), int(a.size)))
+
+    def detect_window_lang(self, batch: int):
+        """ohw_state_detect_window_lang: resolve the table's pending entries for the windows of the last encode, on the device"""
+        _check(lib().ohw_state_detect_window_lang(self.h, int(batch)))
+
+    def window_lang(self, batch: int):
+        """ohw_state_window_lang -> (ids [B] (-1: still pending), probs [B][n_langs])"""
+        ids = np.zeros(batch, dtype=np.int32)
+        probs = np.zeros((batch, self.ctx.tok.n_langs), dtype=np.float32)
+        _check(lib().ohw_state_window_lang(self.h, int(batch), _ip(ids), _fp(probs)))
+        return ids, probs
+
+    def dbg_lang_pick(self, logits: np.ndarray):
+        """the DEVICE language pick on caller-supplied rows [B][n_vocab] -> (ids [B], probs [B][n_langs])"""
+        lg = np.ascontiguousarray(np.atleast_2d(logits), dtype=np.float32)
+        assert lg.shape[1] == self.ctx.hp.n_vocab
+        B = lg.shape[0]
+        ids = np.zeros(B, dtype=np.int32)
+        probs = np.zeros((B, self.ctx.tok.n_langs), dtype=np.float32)
+        _check(lib().ohw_dbg_lang_pick(self.h, _fp(lg), B, _ip(ids), _fp(probs)))
+        return ids, probs
+
     def poison(self, what: str):
         """ohw_dbg_poison (tests): fill the encoder's "qkv" or "att" buffer with NaN"""
         _check(lib().ohw_dbg_poison(self.h, what.encode()))
@@ -1252,11 +1306,40 @@ class WhisperEngine:
         text = C.string_at(full, n.value).decode("utf-8", "replace") if n.value else ""
         return TranscriptionResult(text, lang.value.decode(), int(ms.value))
 
-    def transcribe_batch(self, audios: Sequence[AudioBuffer]) -> List[TranscriptionResult]:
+    def set_detect_language(self, on: bool = True):
+        """ohw_engine_set_detect_language: with language "auto" on a multilingual model, transcribe detects the language on its
+        first window and transcribe_batch on every recording (default off: "auto" is "en", as in the reference)"""
+        _check(lib().ohw_engine_set_detect_language(self.h, int(bool(on))))
+
+    def last_language(self):
+        """ohw_engine_last_language -> (id, code, probability) of the last transcribe (probability 1 when nothing was detected)"""
+        i, pr = C.c_int32(0), C.c_float(0.0)
+        _check(lib().ohw_engine_last_language(self.h, C.byref(i), C.byref(pr)))
+        return int(i.value), lib().ohw_lang_id_to_code(i.value).decode(), float(pr.value)
+
+    def transcribe_batch(self, audios: Sequence[AudioBuffer], languages: Optional[Sequence] = None) -> List[TranscriptionResult]:
         """ohw_engine_transcribe_batch: independent recordings of at most 30 s each in one call, batched longest first; results in
-        submission order.  Tokens and quality of recording i: batch_result(i).  duration_ms is the whole call's"""
+        submission order.  Tokens and quality of recording i: batch_result(i).  duration_ms is the whole call's.
+        languages (ohw_engine_transcribe_batch_lang): one entry per recording - a language id, a code, or None / "auto" / -1 to
+        detect that recording"""
         if not audios:
             return []
+        langs = None
+        if languages is not None:
+            if len(languages) != len(audios):
+                raise ValueError("transcribe_batch: one language per recording")
+            ids = []
+            for x in languages:
+                if x is None or x == "auto":
+                    ids.append(OHW_LANG_DETECT)
+                elif isinstance(x, str):
+                    i = int(lib().ohw_lang_code_to_id(x.encode()))
+                    if i < 0:
+                        raise ValueError(f"unknown language code {x!r}")
+                    ids.append(i)
+                else:
+                    ids.append(int(x))
+            langs = np.asarray(ids, dtype=np.int32)
         rates = {int(a.sample_rate) for a in audios}
         if len(rates) != 1:
             raise ValueError("transcribe_batch: the recordings must share one sample rate")
@@ -1266,7 +1349,10 @@ class WhisperEngine:
             spans[i].samples = _fp(b) if b.size else C.cast(None, C.POINTER(C.c_float))
             spans[i].n = b.size
         t0 = time.perf_counter()
-        _check(lib().ohw_engine_transcribe_batch(self.h, spans, len(bufs), rates.pop()))
+        if langs is None:
+            _check(lib().ohw_engine_transcribe_batch(self.h, spans, len(bufs), rates.pop()))
+        else:
+            _check(lib().ohw_engine_transcribe_batch_lang(self.h, spans, _ip(langs), len(bufs), rates.pop()))
         ms = int((time.perf_counter() - t0) * 1000)
         return [TranscriptionResult(self.batch_result(i)[0], self.batch_result(i)[3], ms) for i in range(len(bufs))]
 
@@ -1414,6 +1500,10 @@ class EnginePool:
         """ohw_pool_set_packed_encoder: WhisperEngine.set_packed_encoder on every engine of the pool"""
         _check(lib().ohw_pool_set_packed_encoder(self.h, int(bool(on))))
 
+    def set_detect_language(self, on: bool = True):
+        """ohw_pool_set_detect_language: WhisperEngine.set_detect_language on every engine; the pool detects once, on its first"""
+        _check(lib().ohw_pool_set_detect_language(self.h, int(bool(on))))
+
     def engine_handle(self, i: int):
         return lib().ohw_pool_engine(self.h, i)
 
@@ -1523,3 +1613,6 @@ def format_size(n: int) -> str:
     if n >= kb:
         return f"{n / kb:.0f} KB"
     return f"{n} B"
+
+
+Pool = EnginePool
