@@ -476,6 +476,101 @@ int ohw_state_window_lang(ohw_state* st, int batch, int32_t* ids_out, float* pro
  * whose language columns are all -inf or NaN gives id 0 and NaN probabilities, on the host and on the device alike.        */
 int ohw_lang_pick_host(const float* row, const ohw_special_tokens* tok, int32_t* id, float* probs);
 
+/* ---- word timestamps: cross-attention alignment (the published openai-whisper find_alignment; whisper.cpp's
+ *      dtw_token_timestamps), on the device, for windows whose cross K/V is still resident.  The reference sets no such
+ *      option; its user guide lists video captions as a use, and a caption needs times.
+ * ohw_state_set_align_heads: the (decoder layer, head) pairs whose cross-attention carries the alignment, at most
+ *   OHW_ALIGN_MAX_HEADS; there is no built-in preset (INTEGRATION.md says where upstream lists them per checkpoint).  NULL or
+ *   n = 0 clears the list and frees the buffers below.  OHW_E_INVALID_ARG for a pair outside the model (the message names its
+ *   index) and for n > OHW_ALIGN_MAX_HEADS.  Until a list is set ohw_state_align returns OHW_E_INVALID_ARG.
+ *   The buffers are made here, on the first list and again when the number of pairs A changes: probabilities f32
+ *   [max_batch][A][n_text_ctx / 2 + 8][n_audio_ctx], the tapped queries f32 [max_batch][n_text_ctx / 2 + 8][A][64], column
+ *   statistics f32 [max_batch][A][n_audio_ctx][2], m f32 [max_batch][n_text_ctx / 2 + 1][n_audio_ctx], trace bytes
+ *   [max_batch][(n_text_ctx / 2 + 2) * (n_audio_ctx + 1)], indices i32 [max_batch][n_text_ctx / 2 + 1].  At large-v3 with
+ *   max_batch 32 and 10 pairs: 445.4 MB + 19.0 MB + 3.8 MB + 43.2 MB + 10.9 MB + 0.03 MB = 522 MB (1.55 GB with 32 pairs).
+ * ohw_state_align: for the windows of the last encode (batch = its batch).  tokens [batch][stride]: the first n_tokens[b]
+ *   entries of row b are window b's text tokens (ids 0 .. eot - 1), in order; n_tokens[b] = 0 skips the window (its row of
+ *   start_idx_out is left alone); n_frames[b] = the window's 10 ms frames of real audio.  start_idx_out [batch][stride + 1]:
+ *   entry k < n_tokens[b] is the encoder position (20 ms each) at which text token k starts, entry n_tokens[b] the position
+ *   at which the last token ends.  Time in seconds = index * 0.02 + the window's offset in the recording.
+ *   The method, per window:
+ *     sequence   the window's prompt as it was decoded - sot, the language token (from the per-window language table when one
+ *                is set, else p->lang_id) and the task token (p->translate) on a multilingual model - then [no_timestamps],
+ *                the text tokens, [eot]: N_all tokens, the first P of them the prompt with [no_timestamps];
+ *     replay     the sequence is fed through the decoder in chunks of 8 tokens per window from position 0 of the state's self
+ *                K/V cache (a window's tail is padded with eot: causality keeps padding from reaching real rows), always on
+ *                the launch-per-kernel step, never the persistent or the fused-attention one, and without capturing a graph.
+ *                AFTER THE CALL THE STATE'S SELF K/V IS STALE; every decode entry starts at position 0 and rewrites it;
+ *     tap        behind the cross-query GEMM of each listed layer: p[a][i][t] = soft-max over t < n_keys of the logits
+ *                (q_i * 0.125) . k_t the layer's cross-attention uses, fp32; n_keys = max(1, min(the window's audio context
+ *                in effect, n_frames / 2)); keys from n_keys on have probability exactly 0 and influence nothing;
+ *     reduce     per head and key column the mean and the population standard deviation over the N_all rows,
+ *                z = (p - mean) / std (a column with std == 0 becomes 0), a median of width 7 along t with the edges padded as
+ *                numpy.pad(mode = "reflect") pads, the mean over the heads, rows P .. N_all - 1 kept: m [N][n_keys] fp32,
+ *                N = n_tokens + 1;
+ *     DTW        on x = -m in fp32: cost[0][0] = 0, the rest of row 0 and column 0 +inf, cost[i][j] = x[i-1][j-1] + c with
+ *                c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1]: c0 (trace 0) if c0 < c1 && c0 < c2, else c1
+ *                (trace 1) if c1 < c0 && c1 < c2, else c2 (trace 2); walked back from (N, n_keys) with trace[0][*] = 2 and
+ *                trace[*][0] = 1; a row's index is the key at which the path first enters it.
+ *   It honours ohw_state_set_audio_ctx, ohw_state_set_window_ctx, the packed encoder and the language table.  Refused with
+ *   OHW_E_INVALID_ARG before any launch: no head list; batch other than the last encode's; a token id < 0 or >= eot (window and
+ *   position named); n_tokens[b] < 0, > stride or > n_text_ctx / 2 (window named); n_frames[b] < 0; a call under another audio
+ *   context or other per-window contexts than the last encode; a language table with a pending entry (window named).
+ * ohw_align_reduce_host / ohw_dtw_host: the reduction and the DTW above on the host, no device needed; the device kernels
+ *   run the same fp32 operations in the same order.  p [n_heads][n_all][n_keys], m_out [n_all - n_prompt][n_keys];
+ *   m [n][n_keys], start_idx_out [n].
+ * Cost and side effects: every chunk is a whole run_decoder_step - the layers behind the last listed one, the final LayerNorm
+ *   and the logits GEMM of its 8 rows per window run too and their results are not read - and it counts in ohw_dbg_counter's
+ *   "dec_gemm.*" / "xattn.*" / "self_attn.*" tallies like any other step.  An ohw_encode* ends the validity of "align_*".
+ * ohw_state_fetch gains "align_q" [N_all][A][64] (the tapped query rows, scaled so that the logits are exactly q . k),
+ *   "align_p" [A][N_all][n_keys] and "align_m" [N][n_keys] of window batch - 1 of the last ohw_state_align.            */
+#define OHW_ALIGN_MAX_HEADS 32
+typedef struct { int32_t layer, head; } ohw_align_head;
+int ohw_state_set_align_heads(ohw_state* st, const ohw_align_head* heads, int n);
+int ohw_state_align(ohw_state* st, const ohw_sample_params* p, const int32_t* tokens, int stride, const int32_t* n_tokens,
+                    const int32_t* n_frames, int batch, int32_t* start_idx_out);
+int ohw_align_reduce_host(const float* p, int n_heads, int n_all, int n_prompt, int n_keys, float* m_out);
+int ohw_dtw_host(const float* m, int n, int n_keys, int32_t* start_idx_out);
+/* ---- times in the engine.  ohw_engine_set_word_timestamps(e, heads, n): the alignment heads of every state the engine decodes
+ *      on; NULL / 0 = off (the default).  When on, every schedule and the seek loop align the kept pass of each window on the
+ *      state that decoded it, before that state's next encode (ohw_state_align; beam or ladder results alike); windows dropped
+ *      by the no-speech rule or without a text token are skipped.  Tokens and text do not change.  Results of the last
+ *      ohw_engine_transcribe, valid until the next call:
+ *   token times  one entry per aligned text token: its id, the index of its window (as in ohw_engine_last_quality), t0 / t1 in
+ *                seconds = the alignment's start / end index * 0.02 + the window's offset in the recording; empty when off;
+ *   words        (needs the alignment; empty when off) a word starts at the first text token of a window, and at any token whose
+ *                bytes begin with a space provided the bytes in front of it end on a complete UTF-8 sequence; t0 / t1 are those of
+ *                its first / last token; punctuation is not merged.  ohw_word_starts_host is the rule: bytes = the tokens' bytes
+ *                of ONE window concatenated, lens[i] = bytes of token i, starts_out[i] = 1 where a word starts;
+ *   segments     (always available, no alignment needed) within a window's kept tokens the text between consecutive timestamp
+ *                tokens is one segment, t0 / t1 = (ts - timestamp_begin) * 0.02 + the window's offset; text in front of the
+ *                first timestamp starts at the window's offset; text with no closing timestamp ends at the earlier of the
+ *                window's end and the recording's end.  ohw_segments_host is the rule on one window's tokens: it returns the
+ *                number of segments (at most cap are written): tokens [first, end) of the list, t0, t1.
+ *   text_off / text_len index ohw_engine_last_text (the trimmed text).  ohw_engine_batch_times: the same three arrays for
+ *   recording i of the last ohw_engine_transcribe_batch (any pointer may be NULL), indexing ohw_engine_batch_result's text.
+ *   Turning the setting off also frees the alignment buffers of every state of the engine.
+ *   ohw_pool_set_word_timestamps: the setting on every engine of the pool; ohw_pool_transcribe gathers the three arrays in
+ *   recording order next to the tokens (window = the window of the recording, offsets into ohw_pool_last_text):
+ *   ohw_pool_last_token_times / _last_words / _last_segments.                                                            */
+typedef struct { int32_t id, window; float t0, t1; } ohw_token_time;
+typedef struct { size_t text_off, text_len; float t0, t1; } ohw_span_time;
+typedef struct { int32_t first, end; float t0, t1; } ohw_token_span;
+struct ohw_engine;
+int ohw_engine_set_word_timestamps(struct ohw_engine* e, const ohw_align_head* heads, int n);
+int ohw_engine_last_token_times(struct ohw_engine* e, const ohw_token_time** t, int* n);
+int ohw_engine_last_words(struct ohw_engine* e, const ohw_span_time** w, int* n);
+int ohw_engine_last_segments(struct ohw_engine* e, const ohw_span_time** s, int* n);
+int ohw_engine_batch_times(struct ohw_engine* e, int i, const ohw_token_time** token_times, int* n_token_times,
+                           const ohw_span_time** words, int* n_words, const ohw_span_time** segments, int* n_segments);
+struct ohw_pool;
+int ohw_pool_set_word_timestamps(struct ohw_pool* p, const ohw_align_head* heads, int n);
+int ohw_pool_last_token_times(struct ohw_pool* p, const ohw_token_time** t, int* n);
+int ohw_pool_last_words(struct ohw_pool* p, const ohw_span_time** w, int* n);
+int ohw_pool_last_segments(struct ohw_pool* p, const ohw_span_time** s, int* n);
+int ohw_word_starts_host(const char* bytes, const int32_t* lens, int n, int32_t* starts_out);
+int ohw_segments_host(const int32_t* tokens, int n, const ohw_special_tokens* tok, float t_off, float t_end, ohw_token_span* out, int cap);
+
 /* per-stage device time of the last calls on this state, in milliseconds (reference logs the     */
 /* same split per job: src/queue/worker.rs:170-180)                                               */
 typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t decode_steps; } ohw_timings;
@@ -730,6 +825,15 @@ int ohw_dbg_cross_attn(int dtype, const void* q, const void* xk, const void* xv,
                        unsigned* tickets, int max_split_rows, int* variant_out, void* stream);
 int ohw_dbg_self_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past_host, void* out, int M,
                       int n_new, int n_head, int n_ctx, const int32_t* kv_slot_host, int* variant_out, void* stream);
+/* The alignment kernels on caller data (tests/test_gpu_align.py).
+ * ohw_dbg_align_probs: q [rows][64 * n_head] and xk [n_head][t_len][64] are device pointers of `dtype`, 1 <= rows <= 8,
+ *   1 <= n_keys <= t_len; heads [n_heads] (host) picks the heads; p_out [n_heads][rows][t_len] (host): the tap's soft-max over
+ *   keys 0 .. n_keys - 1, exactly 0 from n_keys on (those keys are never read).
+ * ohw_dbg_align_reduce / ohw_dbg_dtw: the device twins of ohw_align_reduce_host / ohw_dtw_host on host arrays.          */
+int ohw_dbg_align_probs(int dtype, const void* q, const void* xk, int rows, int n_head, int t_len, int n_keys,
+                        const int32_t* heads_host, int n_heads, float* p_out_host, void* stream);
+int ohw_dbg_align_reduce(int device, const float* p_host, int n_heads, int n_all, int n_prompt, int n_keys, float* m_out_host);
+int ohw_dbg_dtw(int device, const float* m_host, int n, int n_keys, int32_t* start_idx_out);
 /* fill an encoder activation buffer of the state with NaN (every byte 0xff: a NaN in bf16 and in f16): what = "qkv" or "att".
  * An encode overwrites every row it owns, so a test can tell a row that was never written, or written by a neighbour. */
 int ohw_dbg_poison(ohw_state* st, const char* what);

@@ -169,7 +169,25 @@ def main(argv=None) -> int:
     t.add_argument("--detect-language", action="store_true",
                    help="with --language auto on a multilingual model: detect the language on the first 30 s window and decode in it "
                         "(default: auto means en, as in the reference); the JSON language field carries the detected code")
+    t.add_argument("--word-timestamps", action="store_true",
+                   help="align every window's tokens on the device and add \"segments\" and \"words\" arrays (text, t0, t1 in seconds) to "
+                        "the JSON; needs --align-heads")
+    t.add_argument("--align-heads", default="", metavar="L.H,L.H,...",
+                   help="the (decoder layer, head) pairs whose cross-attention carries the alignment, at most 32; no preset ships "
+                        "(INTEGRATION.md says where upstream lists them per checkpoint)")
     args = ap.parse_args(argv)
+    align_heads = []
+    if args.word_timestamps:
+        try:
+            align_heads = [(int(x.split(".")[0]), int(x.split(".")[1])) for x in args.align_heads.split(",") if x.strip()]
+        except (ValueError, IndexError):
+            align_heads = []
+        if not align_heads:
+            print("error: --word-timestamps needs --align-heads L.H,L.H,... (decoder layer . head)", file=sys.stderr)
+            return 1
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            print("error: --word-timestamps is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+            return 1
 
     from . import engine as E
     try:
@@ -204,15 +222,25 @@ def main(argv=None) -> int:
         eng.set_packed_encoder(True)
     if args.detect_language:
         eng.set_detect_language(True)
+    if align_heads:
+        try:
+            eng.set_word_timestamps(align_heads)
+        except E.WhisperError as ex:
+            print(f"error: {ex}", file=sys.stderr)
+            return 1
     t1 = time.perf_counter()
     res = eng.transcribe(audio)
     dt = time.perf_counter() - t1
     rtf = dt / audio.duration_secs()
     name = args.model or args.model_path.rsplit("/", 1)[-1].replace("ggml-", "").rsplit(".", 1)[0]
     if args.format == "json":
-        print(json.dumps({"text": res.text, "language": res.language, "duration_ms": res.duration_ms,
-                          "audio_duration_secs": audio.duration_secs(), "transcription_time_ms": int(dt * 1e3),
-                          "real_time_factor": rtf, "model": name.lower()}, indent=2))
+        doc = {"text": res.text, "language": res.language, "duration_ms": res.duration_ms,
+               "audio_duration_secs": audio.duration_secs(), "transcription_time_ms": int(dt * 1e3),
+               "real_time_factor": rtf, "model": name.lower()}
+        if align_heads:
+            doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in eng.last_segments()]
+            doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in eng.last_words()]
+        print(json.dumps(doc, indent=2))
     else:
         print("\n--- Transcription ---")
         print(res.text)

@@ -205,6 +205,17 @@ struct ohw_state {
   std::vector<StepGraph> step_graphs;
   bool graphs_enabled = true;
   int graph_max_batch = 32;         // graphs for batches below this (OHW_GRAPH_MAX_BATCH)
+  // word timestamps (ohw_state_set_align_heads / ohw_state_align; align.hip).  al_heads: the caller's list; the buffers are made
+  // when a list is set.  al_rows = n_text_ctx / 2 + 8 token rows per (window, head).  al_tap is set only while ohw_state_align
+  // replays a window's tokens: run_decoder_step then taps the listed heads behind each layer's cross-query GEMM, row al_row0 on.
+  // al_nall / al_nk / al_prompt / al_batch describe the last alignment (ohw_state_fetch "align_*")
+  std::vector<ohw_align_head> al_heads;
+  DevBuf al_p, al_q, al_stats, al_m, al_trace, al_idx, al_cnt, al_tok;   // al_cnt i32 [3][max_batch]: n_all, n_keys, N
+  int al_rows = 0;
+  bool al_tap = false;
+  int al_row0 = 0, al_lds = 0;
+  std::vector<int32_t> al_nall, al_nk;
+  int al_prompt = 0, al_batch = 0;
   // timing
   hipEvent_t ev[6]{};
   ohw_timings last{};
@@ -621,6 +632,21 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     else ++st->tally_self[2 + (kv_slot ? SA_SLOTS : SA_PLAIN)];
     gemm(DT_O, st->da.p, nullptr, w.wo, w.bo, st->dx.p, d, d, DEPI_BIAS_RESID, d);
     gemm(DT_XQ, st->dx.p, &w.lnx, w.wxq, w.bxq, st->dq.p, d, d, DEPI_BIAS_T, d, &w.sxq);
+    if (st->al_tap) {     // ohw_state_align's replay: the listed heads of this layer read the queries just written and the layer's K
+      AlignTapList list{};
+      for (size_t a = 0; a < st->al_heads.size(); ++a)
+        if (st->al_heads[a].layer == l) { list.slot[list.n] = (int16_t)a; list.head[list.n] = (int16_t)st->al_heads[a].head; ++list.n; }
+      if (list.n > 0) {
+        const int A = (int)st->al_heads.size();
+        AlignTapParams tp{};
+        tp.q = st->dq.p; tp.xk = (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab; tp.n_head = H; tp.t_len = Tn;
+        tp.rows = n_new; tp.row0 = st->al_row0; tp.row_cap = st->al_rows; tp.lds_stride = st->al_lds;
+        tp.n_all = st->al_cnt.as<int32_t>(); tp.n_keys = st->al_cnt.as<int32_t>() + st->max_batch;
+        tp.p = st->al_p.as<float>(); tp.p_row = hp.n_audio_ctx; tp.p_head = (int64_t)st->al_rows * tp.p_row; tp.p_win = (int64_t)A * tp.p_head;
+        tp.p_fill = Tn; tp.q_out = st->al_q.as<float>(); tp.n_slots = A;
+        launch_align_tap<T>(tp, list, B, s);
+      }
+    }
     {
       // algorithmic bytes: K and V of every (query row, head); the prompt pass streams them once per (window, head)
       // for all its rows (cross_attn_rows_kernel: same condition as launch_cross_attn)
@@ -1020,6 +1046,7 @@ int ohw_encode_slice(ohw_state* st, int batch, int first, int total) {
     });
     HIP_CHECK(hipEventRecord(st->ev[3], st->stream));
     st->enc_batch = total;
+    st->al_batch = 0;                  // the aligned windows are no longer resident: "align_*" fetches end here
     st->enc_ctx = audio_ctx_of(st);
     st->enc_set = st->win_ctx;
     st->enc_var = var;
@@ -1733,6 +1760,158 @@ int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* sp, const float* lo
   });
 }
 
+// ---- word timestamps (include/ohw.h; kernels in align.hip) ---------------------------------------------------------------
+int ohw_state_set_align_heads(ohw_state* st, const ohw_align_head* heads, int n) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    const ohw_hparams& hp = st->ctx->hp;
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    if (n < 0) throw Error(OHW_E_INVALID_ARG, "set_align_heads: n < 0");
+    if (n > OHW_ALIGN_MAX_HEADS)
+      throw Error(OHW_E_INVALID_ARG, "set_align_heads: " + std::to_string(n) + " heads, at most " + std::to_string(OHW_ALIGN_MAX_HEADS) + " (OHW_ALIGN_MAX_HEADS)");
+    if (heads)
+      for (int i = 0; i < n; ++i)
+        if (heads[i].layer < 0 || heads[i].layer >= hp.n_text_layer || heads[i].head < 0 || heads[i].head >= hp.n_text_head)
+          throw Error(OHW_E_INVALID_ARG, "set_align_heads: entry " + std::to_string(i) + " (layer " + std::to_string(heads[i].layer) + ", head " +
+                                             std::to_string(heads[i].head) + ") is outside the model (" + std::to_string(hp.n_text_layer) + " layers, " +
+                                             std::to_string(hp.n_text_head) + " heads)");
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    st->al_batch = 0;
+    if (!heads || n == 0) {
+      st->al_heads.clear();
+      for (DevBuf* b : {&st->al_p, &st->al_q, &st->al_stats, &st->al_m, &st->al_trace, &st->al_idx, &st->al_cnt, &st->al_tok}) b->release();
+      return;
+    }
+    if ((size_t)n != st->al_heads.size() || !st->al_p.p) {
+      const size_t B = (size_t)st->max_batch, A = (size_t)n, T = (size_t)hp.n_audio_ctx, half = (size_t)hp.n_text_ctx / 2;
+      st->al_rows = (int)half + 8;
+      st->al_p.alloc(B * A * (half + 8) * T * 4);
+      st->al_q.alloc(B * (half + 8) * A * 64 * 4);
+      st->al_stats.alloc(B * A * T * 2 * 4);
+      st->al_m.alloc(B * (half + 1) * T * 4);
+      st->al_trace.alloc(B * (half + 2) * (T + 1));
+      st->al_idx.alloc(B * (half + 1) * 4, true);
+      st->al_cnt.alloc(3 * B * 4, true);
+      st->al_tok.alloc(((half + 8) / 8 + 1) * B * 8 * 4);
+    }
+    st->al_heads.assign(heads, heads + n);
+  });
+}
+
+int ohw_state_align(ohw_state* st, const ohw_sample_params* sp, const int32_t* tokens, int stride, const int32_t* n_tokens, const int32_t* n_frames,
+                    int batch, int32_t* start_idx_out) {
+  return guard([&] {
+    if (!st || !sp || !tokens || !n_tokens || !n_frames || !start_idx_out) throw Error(OHW_E_INVALID_ARG, "align: null argument");
+    if (st->al_heads.empty()) throw Error(OHW_E_INVALID_ARG, "align: no alignment heads are set (ohw_state_set_align_heads)");
+    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "align: batch must equal the batch of the last ohw_encode");
+    check_decode_ctx(st, "align");
+    const ohw_ctx* c = st->ctx;
+    const ohw_hparams& hp = c->hp;
+    const bool multilingual = hp.n_vocab >= 51865, lang_tab = !st->lang_kind.empty();
+    if (lang_tab) check_window_lang(st, batch, "align");
+    else if (multilingual && (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs)) throw Error(OHW_E_INVALID_ARG, "align: lang_id out of range");
+    const int half = hp.n_text_ctx / 2, eot = c->tok.eot;
+    if (stride < 0) throw Error(OHW_E_INVALID_ARG, "align: stride < 0");
+    for (int b = 0; b < batch; ++b) {
+      const int nt = n_tokens[b];
+      if (nt < 0 || nt > stride || nt > half)
+        throw Error(OHW_E_INVALID_ARG, "align: window " + std::to_string(b) + " has n_tokens " + std::to_string(nt) + ", outside 0 .. min(stride " +
+                                           std::to_string(stride) + ", n_text_ctx / 2 = " + std::to_string(half) + ")");
+      if (n_frames[b] < 0) throw Error(OHW_E_INVALID_ARG, "align: window " + std::to_string(b) + " has n_frames < 0");
+      for (int k = 0; k < nt; ++k) {
+        const int32_t id = tokens[(size_t)b * stride + k];
+        if (id < 0 || id >= eot)
+          throw Error(OHW_E_INVALID_ARG, "align: window " + std::to_string(b) + ", token " + std::to_string(k) + ": id " + std::to_string(id) +
+                                             " is not a text token (0 .. " + std::to_string(eot - 1) + ")");
+      }
+    }
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = st->stream;
+    // the windows' language tokens: the table's ids (one read-back), else the caller's
+    std::vector<int32_t> lang((size_t)batch, sp->lang_id);
+    if (lang_tab && multilingual) {
+      HIP_CHECK(hipMemcpyAsync(lang.data(), st->lang_tab.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    const int P = 1 + (multilingual ? 2 : 0) + 1;
+    const int MB = st->max_batch, Tn = st->enc_ctx;
+    std::vector<int32_t> cnt((size_t)3 * MB, 0);      // n_all, n_keys, N
+    int max_all = 0, max_nk = 1;
+    for (int b = 0; b < batch; ++b) {
+      const int nt = n_tokens[b];
+      const int ctx_b = st->enc_var ? st->enc_win[(size_t)b] : Tn;
+      const int nk = std::max(1, std::min(ctx_b, n_frames[b] / 2));
+      cnt[(size_t)b] = nt > 0 ? P + nt + 1 : 0;
+      cnt[(size_t)MB + b] = nk;
+      cnt[(size_t)2 * MB + b] = nt > 0 ? nt + 1 : 0;
+      max_all = std::max(max_all, cnt[(size_t)b]);
+      if (nt > 0) max_nk = std::max(max_nk, nk);
+    }
+    const int chunks = (max_all + 7) / 8;
+    if (chunks * 8 > hp.n_text_ctx || chunks * 8 > st->al_rows + 7 || (size_t)chunks * batch * 8 * 4 > st->al_tok.bytes)
+      throw Error(OHW_E_INVALID_ARG, "align: the sequence does not fit n_text_ctx");
+    // nothing below refuses: from here on the "align_*" fetches describe this call (a failed launch ends their validity)
+    st->al_batch = 0;
+    st->al_nall.assign(cnt.begin(), cnt.begin() + batch);
+    st->al_nk.assign(cnt.begin() + MB, cnt.begin() + MB + batch);
+    st->al_prompt = P;
+    if (max_all == 0) { st->al_batch = batch; return; }     // every window skipped
+    std::vector<int32_t> toks((size_t)chunks * batch * 8, eot), npast((size_t)chunks * batch);
+    for (int b = 0; b < batch; ++b) {
+      const int nt = n_tokens[b];
+      if (nt == 0) continue;
+      std::vector<int32_t> seq;
+      seq.push_back(c->tok.sot);
+      if (multilingual) { seq.push_back(c->tok.sot + 1 + lang[(size_t)b]); seq.push_back(sp->translate ? c->tok.translate : c->tok.transcribe); }
+      seq.push_back(c->tok.no_timestamps);
+      seq.insert(seq.end(), tokens + (size_t)b * stride, tokens + (size_t)b * stride + nt);
+      for (size_t i = 0; i < seq.size(); ++i) toks[((i / 8) * batch + b) * 8 + i % 8] = seq[i];       // the tail stays eot
+    }
+    for (int ch = 0; ch < chunks; ++ch)
+      for (int b = 0; b < batch; ++b) npast[(size_t)ch * batch + b] = ch * 8;
+    HIP_CHECK(hipMemcpyAsync(st->al_tok.p, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->al_cnt.p, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, s));
+    {
+      // the replay: launch-per-kernel steps only, every window's cross-attention runs, nothing is captured
+      struct Replay {
+        ohw_state* st; bool persist, fuse, skip;
+        explicit Replay(ohw_state* s_) : st(s_), persist(s_->persist), fuse(s_->fuse_attn), skip(s_->skip_done) {
+          st->persist = false; st->fuse_attn = false; st->skip_done = false; st->al_tap = true;
+        }
+        ~Replay() { st->persist = persist; st->fuse_attn = fuse; st->skip_done = skip; st->al_tap = false; }
+      } replay(st);
+      st->al_lds = max_nk;
+      Dispatch::run(c->dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        for (int ch = 0; ch < chunks; ++ch) {
+          HIP_CHECK(hipMemcpyAsync(st->n_past.p, &npast[(size_t)ch * batch], (size_t)batch * 4, hipMemcpyHostToDevice, s));
+          st->al_row0 = ch * 8;
+          run_decoder_step<T>(st, batch, 8, st->al_tok.as<int32_t>() + (size_t)ch * batch * 8);
+        }
+      });
+    }
+    const int A = (int)st->al_heads.size();
+    const int64_t T = hp.n_audio_ctx;
+    AlignReduceParams rp{};
+    rp.p = st->al_p.as<float>(); rp.p_row = T; rp.p_head = (int64_t)st->al_rows * T; rp.p_win = (int64_t)A * rp.p_head;
+    rp.stats = st->al_stats.as<float>(); rp.ld_stat = T; rp.n_heads = A; rp.n_prompt = P; rp.max_rows = half + 1; rp.max_keys = Tn;
+    rp.n_all = st->al_cnt.as<int32_t>(); rp.n_keys = st->al_cnt.as<int32_t>() + MB;
+    rp.m = st->al_m.as<float>(); rp.m_row = T; rp.m_win = (int64_t)(half + 1) * T;
+    launch_align_reduce(rp, batch, s);
+    AlignDtwParams dp{};
+    dp.m = rp.m; dp.m_win = rp.m_win; dp.m_row = rp.m_row; dp.n_rows = st->al_cnt.as<int32_t>() + 2 * MB; dp.n_keys = rp.n_keys;
+    dp.trace = st->al_trace.as<uint8_t>(); dp.trace_win = (int64_t)(half + 2) * (T + 1); dp.idx = st->al_idx.as<int32_t>(); dp.idx_win = half + 1;
+    dp.max_rows = half + 1; dp.max_keys = Tn;
+    launch_align_dtw(dp, batch, s);
+    std::vector<int32_t> idx((size_t)batch * (half + 1));
+    HIP_CHECK(hipMemcpyAsync(idx.data(), st->al_idx.p, idx.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));     // also keeps toks / cnt / npast alive until their copies have run
+    st->al_batch = batch;
+    for (int b = 0; b < batch; ++b)
+      if (n_tokens[b] > 0) std::memcpy(start_idx_out + (size_t)b * (stride + 1), &idx[(size_t)b * (half + 1)], (size_t)(n_tokens[b] + 1) * 4);
+  });
+}
+
 int ohw_state_timings(ohw_state* st, ohw_timings* t) {
   return guard([&] {
     if (!st || !t) throw Error(OHW_E_INVALID_ARG, "null argument");
@@ -1808,6 +1987,27 @@ int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int6
       HIP_CHECK(hipStreamSynchronize(s));
     };
     if (w == "mel") { from_f32(st->logmel.p, (int64_t)batch * hp.n_mels * CHUNK_FRAMES); return; }
+    if (w == "align_q" || w == "align_p" || w == "align_m") {
+      // window batch - 1 of the last ohw_state_align
+      const int b = batch - 1;
+      if (st->al_heads.empty() || batch > st->al_batch || st->al_nall[(size_t)b] == 0)
+        throw Error(OHW_E_INVALID_ARG, "fetch: window " + std::to_string(b) + " was not aligned by the last ohw_state_align");
+      const int64_t A = (int64_t)st->al_heads.size(), n_all = st->al_nall[(size_t)b], nk = st->al_nk[(size_t)b], R = st->al_rows, T = hp.n_audio_ctx;
+      const int64_t n_m = n_all - st->al_prompt, half = hp.n_text_ctx / 2;
+      if (w == "align_q") { from_f32(st->al_q.as<float>() + (int64_t)b * R * A * 64, n_all * A * 64); return; }
+      if (w == "align_p") {
+        need(A * n_all * nk);
+        for (int64_t a = 0; a < A; ++a)
+          HIP_CHECK(hipMemcpy2DAsync(out + a * n_all * nk, (size_t)nk * 4, st->al_p.as<float>() + ((int64_t)b * A + a) * R * T, (size_t)T * 4, (size_t)nk * 4,
+                                     (size_t)n_all, hipMemcpyDeviceToHost, s));
+      } else {
+        need(n_m * nk);
+        HIP_CHECK(hipMemcpy2DAsync(out, (size_t)nk * 4, st->al_m.as<float>() + (int64_t)b * (half + 1) * T, (size_t)T * 4, (size_t)nk * 4, (size_t)n_m,
+                                   hipMemcpyDeviceToHost, s));
+      }
+      HIP_CHECK(hipStreamSynchronize(s));
+      return;
+    }
     // the last encode ran packed: "enc" and "block0" lie end to end on the device; the caller gets the envelope layout [B][Tn][d],
     // window b's first n_ctx[b] rows from its packed rows, the rows behind them as zeros
     DevBuf unp;

@@ -141,6 +141,7 @@ struct WindowRun {
   float nosp = 0.f, temp = 0.f;
   SeqEval ev;
   bool pending = false, t0_failed = false;
+  std::vector<int32_t> al_idx;   // word timestamps: start index of every kept text token, then the end of the last (empty: not aligned)
 };
 
 std::vector<float> ladder(const ohw_decode_policy& q) {
@@ -172,6 +173,14 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
   e->ctx = ctx;
   e->packed_encoder = ohw_state_packed_encoder(e->state) == 1;     // OHW_ENC_PACKED
   return e.release();
+}
+
+void trim_spans(std::vector<ohw_span_time>& v, size_t lead, size_t new_len) {
+  for (ohw_span_time& s : v) {
+    size_t o0 = std::max(s.text_off, lead) - lead, o1 = std::max(s.text_off + s.text_len, lead) - lead;
+    o0 = std::min(o0, new_len); o1 = std::min(o1, new_len);
+    s.text_off = o0; s.text_len = o1 - o0;
+  }
 }
 
 bool engine_detects(const ohw_engine* e) { return e->detect_language && e->language == "auto" && e->ctx->hp.n_vocab >= 51865; }
@@ -235,6 +244,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
     e->last_tokens.clear();
     e->last_quality.clear();
     e->last_trace.clear();
+    e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
     const int max_tok = e->ctx->hp.n_text_ctx;
     const int V = e->ctx->hp.n_vocab;
     const int n_max = sp.n_max;
@@ -363,18 +373,88 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         }
       }
     };
-    auto emit = [&](const WindowRun& r) {
+    // word timestamps: the kept pass of every window of a batch is aligned on the state that decoded it, while its cross K/V
+    // is resident (before that state's next encode); windows with no kept text token are skipped.  frames: 10 ms frames of audio
+    auto kept_tokens = [&](const WindowRun& r) {
+      const bool no_speech = r.nosp > pol.no_speech_thold && r.ev.avg_logprob < pol.logprob_thold;
+      return no_speech ? 0 : r.ev.n_keep;
+    };
+    auto align_runs = [&](Scratch& sc, ohw_state* st, int B, const int* frames) {
+      if (e->wt_heads.empty()) return;
+      const int half = e->ctx->hp.n_text_ctx / 2;
+      std::vector<int32_t> atok((size_t)B * half, 0), nt((size_t)B, 0), nf((size_t)B, 0), out((size_t)B * (half + 1), 0);
+      bool any = false;
+      for (int b = 0; b < B; ++b) {
+        WindowRun& r = sc.runs[(size_t)b];
+        r.al_idx.clear();
+        const int keep = kept_tokens(r);
+        int k = 0;
+        for (int i = 0; i < keep && k < half; ++i)
+          if (r.tok[(size_t)i] < tk.eot) atok[(size_t)b * half + k++] = r.tok[(size_t)i];
+        nt[(size_t)b] = k;
+        nf[(size_t)b] = std::max(0, frames[b]);
+        any = any || k > 0;
+      }
+      if (!any) return;
+      check(ohw_state_set_align_heads(st, e->wt_heads.data(), (int)e->wt_heads.size()));
+      check(ohw_state_align(st, &sp, atok.data(), half, nt.data(), nf.data(), B, out.data()));
+      for (int b = 0; b < B; ++b)
+        if (nt[(size_t)b] > 0) sc.runs[(size_t)b].al_idx.assign(&out[(size_t)b * (half + 1)], &out[(size_t)b * (half + 1)] + nt[(size_t)b] + 1);
+    };
+    // t_off: the window's offset in the recording, t_end: the earlier of the window's end and the recording's end (seconds)
+    auto emit = [&](const WindowRun& r, double t_off, double t_end) {
       // whisper.cpp (>= 1.7.3 as recalled): a window whose no-speech probability is high AND whose text is unlikely is dropped
       const bool no_speech = r.nosp > pol.no_speech_thold && r.ev.avg_logprob < pol.logprob_thold;
       const int keep = no_speech ? 0 : r.ev.n_keep;
+      ohw_engine::WindowMark mark;
+      mark.text0 = text.size();
+      const size_t tt0 = e->last_token_times.size(), wd0 = e->last_words.size(), sg0 = e->last_segments.size();
+      std::vector<size_t> byte_off((size_t)keep + 1, text.size());       // text offset in front of every kept token
+      std::vector<int32_t> tlen;                                         // byte length of every kept TEXT token
+      std::vector<int> tpos;                                             //   and its position among the kept tokens
+      const size_t win_text0 = text.size();
       for (int i = 0; i < keep; ++i) {
+        byte_off[(size_t)i] = text.size();
         e->last_tokens.push_back(r.tok[(size_t)i]);
         if (r.tok[(size_t)i] < tk.eot) {                                    // segment text = text tokens only (:271-279)
           const char* sp_ = nullptr;
           const int len = ohw_token_text(e->ctx, r.tok[(size_t)i], &sp_);
           text.append(sp_, (size_t)len);
+          tlen.push_back(len); tpos.push_back(i);
         }
       }
+      byte_off[(size_t)keep] = text.size();
+      if (keep > 0) {
+        // segments (always): the text between consecutive timestamp tokens
+        std::vector<ohw_token_span> spans((size_t)keep);
+        const int ns_ = ohw_segments_host(r.tok.data(), keep, &tk, (float)t_off, (float)t_end, spans.data(), keep);
+        for (int s = 0; s < ns_; ++s) {
+          const size_t o0 = byte_off[(size_t)spans[(size_t)s].first], o1 = byte_off[(size_t)spans[(size_t)s].end];
+          e->last_segments.push_back(ohw_span_time{o0, o1 - o0, spans[(size_t)s].t0, spans[(size_t)s].t1});
+        }
+      }
+      if (!r.al_idx.empty() && r.al_idx.size() == tlen.size() + 1) {
+        // token times, and words by the host rule (include/ohw.h)
+        const int32_t window = (int32_t)e->last_quality.size();
+        const size_t first_tt = e->last_token_times.size();
+        for (size_t k = 0; k < tlen.size(); ++k)
+          e->last_token_times.push_back(ohw_token_time{r.tok[(size_t)tpos[k]], window, (float)t_off + (float)r.al_idx[k] * 0.02f,
+                                                       (float)t_off + (float)r.al_idx[k + 1] * 0.02f});
+        std::vector<int32_t> starts(tlen.size(), 0);
+        (void)ohw_word_starts_host(text.data() + win_text0, tlen.data(), (int)tlen.size(), starts.data());
+        for (size_t k = 0; k < tlen.size(); ++k) {
+          const ohw_token_time& tt = e->last_token_times[first_tt + k];
+          const size_t o0 = byte_off[(size_t)tpos[k]];
+          if (starts[k] || e->last_words.size() == wd0) e->last_words.push_back(ohw_span_time{o0, 0, tt.t0, tt.t1});
+          ohw_span_time& w = e->last_words.back();
+          w.text_len = o0 + (size_t)tlen[k] - w.text_off;
+          w.t1 = tt.t1;
+        }
+      }
+      mark.n_token_times = (int32_t)(e->last_token_times.size() - tt0);
+      mark.n_words = (int32_t)(e->last_words.size() - wd0);
+      mark.n_segments = (int32_t)(e->last_segments.size() - sg0);
+      e->last_marks.push_back(mark);
       ohw_window_quality q{};
       q.n_tokens = keep; q.avg_logprob = r.ev.avg_logprob; q.entropy = r.ev.entropy; q.would_fallback = r.t0_failed ? 1 : 0;
       q.temperature = r.temp; q.no_speech_prob = r.nosp; q.no_speech = no_speech ? 1 : 0; q.seek_delta = r.ev.seek_delta;
@@ -424,7 +504,9 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         lr.reset((size_t)B);
         run_ladder(sc, st, B, zero.data(), ends.data(), w0, lr.v);
       }
+      align_runs(sc, st, B, ends.data());
     };
+
     if (recs) {
       // ---- ohw_engine_transcribe_batch: every recording one window of its own; longest first, max_batch at a time, one batch
       // after the other on the engine's own state.  Under the auto setting a batch's envelope is its largest context and every
@@ -486,16 +568,21 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         sc.trace.clear();
         for (int b = 0; b < B; ++b) {
           text.clear(); e->last_tokens.clear(); e->last_quality.clear();
-          emit(sc.runs[(size_t)b]);
+          e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
+          emit(sc.runs[(size_t)b], 0.0, (double)recs[ord[b]].n / 16000.0);
           ohw_engine::BatchRecord& r = e->batch_records[(size_t)ord[b]];
           const size_t b0 = text.find_first_not_of(" \t\r\n"), b1 = text.find_last_not_of(" \t\r\n");
           r.text = b0 == std::string::npos ? std::string() : text.substr(b0, b1 - b0 + 1);
+          trim_spans(e->last_words, b0 == std::string::npos ? 0 : b0, r.text.size());
+          trim_spans(e->last_segments, b0 == std::string::npos ? 0 : b0, r.text.size());
+          r.token_times = e->last_token_times; r.words = e->last_words; r.segments = e->last_segments;
           r.tokens = e->last_tokens;
           r.quality = e->last_quality[0];
           r.lang_id = per_rec ? batch_lang[(size_t)b] : -1;
         }
       }
       text.clear(); e->last_tokens.clear(); e->last_quality.clear();
+      e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
       return;
     }
     if (e->window_mode == OHW_WINDOW_SEEK) {
@@ -517,8 +604,10 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         check(ohw_encode(e->state, 1));
         greedy_t0(sc, e->state, 1, &seek, &seek_end, w);
         run_ladder(sc, e->state, 1, &seek, &seek_end, w, rngs.v);
+        const int win_frames = std::min(CHUNK_FRAMES, seek_end - seek);
+        align_runs(sc, e->state, 1, &win_frames);
         flush_trace(sc);
-        emit(sc.runs[0]);
+        emit(sc.runs[0], seek * 0.01, std::min(seek * 0.01 + 30.0, (double)n / 16000.0));
         seek += sc.runs[0].ev.seek_delta > 0 ? sc.runs[0].ev.seek_delta : 3000;
         ++w;
       }
@@ -557,9 +646,12 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         check(ohw_encode(st, batch_of(bi)));
       };
       auto decode_batch = [&](Scratch& sc, ohw_state* st, int64_t bi, const int32_t* nsb) { decode_windows(sc, st, bi * e->max_batch, batch_of(bi), nsb); };
-      auto collect = [&](Scratch& sc, int B) {
+      auto collect = [&](Scratch& sc, int B, int64_t w0) {
         flush_trace(sc);
-        for (int b = 0; b < B; ++b) emit(sc.runs[(size_t)b]);
+        for (int b = 0; b < B; ++b) {
+          const double t_off = (double)rec_win(w0 + b) * 30.0;
+          emit(sc.runs[(size_t)b], t_off, std::min(t_off + 30.0, (double)n / 16000.0));
+        }
       };
       int schedule = n_batches > 1 ? e->schedule : OHW_SCHEDULE_SEQUENTIAL;
       if (schedule == OHW_SCHEDULE_LANES && e->lanes < 2) schedule = OHW_SCHEDULE_SEQUENTIAL;
@@ -639,7 +731,9 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         }
         Invariant(ohw_engine* e_, bool on_) : e(e_), on(on_) { if (on) set(true); }
         ~Invariant() { if (on) set(false); }
-      } invariant(e, n_batches > 1);
+        // an engine of a pool that aligns: its share may be one batch while the recording is several, and the alignment's path is
+        // sensitive to last bits, so the times must not depend on how the windows were dealt
+      } invariant(e, n_batches > 1 || (!e->wt_heads.empty() && win_step > 1));
       struct SharedRecording {      // every state of this transcribe reads the recording e->state holds
         ohw_engine* e; bool on;
         SharedRecording(ohw_engine* e_, bool on_) : e(e_), on(on_) {
@@ -682,7 +776,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
           mel_windows(e->state, bi * e->max_batch, batch_of(bi), ns.data());
           check(ohw_encode(e->state, batch_of(bi)));
           decode_batch(sc, e->state, bi, ns.data());
-          collect(sc, batch_of(bi));
+          collect(sc, batch_of(bi), bi * e->max_batch);
         }
       } else if (schedule == OHW_SCHEDULE_PIPELINE) {
         // mel + encoder + cross-K/V of batch i+1 (MFMA-bound) run beside the greedy decode of batch i (HBM- and
@@ -703,7 +797,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
             }
             check(ohw_state_set_stream(e->states[bi & 1], dstream));
             decode_batch(sc, e->states[bi & 1], bi, ns2[bi & 1].data());
-            collect(sc, batch_of(bi));
+            collect(sc, batch_of(bi), bi * e->max_batch);
           }
         } catch (...) {
           (void)hipDeviceSynchronize();
@@ -754,7 +848,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
             }
             if (grp == 1) {
               decode_windows(*scs[0], e->lane_states[0], lane_w0[0], lane_w[0], nss[0].data());
-              collect(*scs[0], lane_w[0]);
+              collect(*scs[0], lane_w[0], lane_w0[0]);
               continue;
             }
             std::vector<std::string> errs((size_t)grp);
@@ -781,7 +875,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
             for (int j = 0; j < grp; ++j) if (!errs[(size_t)j].empty()) throw Error(OHW_E_TRANSCRIBE, errs[(size_t)j]);
             for (int j = 0; j < grp; ++j) {
               check(ohw_stream_wait(e->s_full, e->lane_streams[(size_t)j]));
-              collect(*scs[(size_t)j], lane_w[(size_t)j]);
+              collect(*scs[(size_t)j], lane_w[(size_t)j], lane_w0[(size_t)j]);
             }
           }
         } catch (...) {
@@ -1059,6 +1153,8 @@ int ohw_engine_transcribe(ohw_engine* e, const float* samples, int64_t n, uint32
     const size_t b1 = text.find_last_not_of(" \t\r\n");
     text = b0 == std::string::npos ? std::string() : text.substr(b0, b1 - b0 + 1);
     e->last_text = text;
+    trim_spans(e->last_words, b0 == std::string::npos ? 0 : b0, text.size());       // the spans index the trimmed text
+    trim_spans(e->last_segments, b0 == std::string::npos ? 0 : b0, text.size());
     if (text_buf && text_cap > 0) {
       const size_t ncopy = std::min(text.size(), text_cap - 1);
       std::memcpy(text_buf, text.data(), ncopy);
@@ -1102,6 +1198,107 @@ int ohw_batch_plan(const int64_t* n_samples, int n_recs, int max_batch, int audi
 
 int ohw_engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, uint32_t sample_rate) {
   return ohw_engine_transcribe_batch_lang(e, recs, nullptr, n_recs, sample_rate);
+}
+
+int ohw_engine_set_word_timestamps(ohw_engine* e, const ohw_align_head* heads, int n) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (!heads || n == 0) {
+      // off: every state of the engine that may have aligned gives its buffers back
+      e->wt_heads.clear();
+      (void)ohw_state_set_align_heads(e->state, nullptr, 0);
+      for (ohw_state* st : e->states) if (st != e->state) (void)ohw_state_set_align_heads(st, nullptr, 0);
+      for (ohw_state* st : e->lane_states) (void)ohw_state_set_align_heads(st, nullptr, 0);
+      return;
+    }
+    // checked here against the model, as ohw_state_set_align_heads checks it; a state allocates when it first aligns
+    const ohw_hparams& hp = e->ctx->hp;
+    if (n < 0 || n > OHW_ALIGN_MAX_HEADS)
+      throw Error(OHW_E_INVALID_ARG, "set_word_timestamps: " + std::to_string(n) + " heads, at most " + std::to_string(OHW_ALIGN_MAX_HEADS) + " (OHW_ALIGN_MAX_HEADS)");
+    for (int i = 0; i < n; ++i)
+      if (heads[i].layer < 0 || heads[i].layer >= hp.n_text_layer || heads[i].head < 0 || heads[i].head >= hp.n_text_head)
+        throw Error(OHW_E_INVALID_ARG, "set_word_timestamps: entry " + std::to_string(i) + " (layer " + std::to_string(heads[i].layer) + ", head " +
+                                           std::to_string(heads[i].head) + ") is outside the model (" + std::to_string(hp.n_text_layer) + " layers, " +
+                                           std::to_string(hp.n_text_head) + " heads)");
+    e->wt_heads.assign(heads, heads + n);
+  });
+}
+
+static int spans_out(const std::vector<ohw_token_time>& tt, const std::vector<ohw_span_time>& w, const std::vector<ohw_span_time>& s,
+                     const ohw_token_time** tp, int* tn, const ohw_span_time** wp, int* wn, const ohw_span_time** sp_, int* sn) {
+  if (tp) *tp = tt.data();
+  if (tn) *tn = (int)tt.size();
+  if (wp) *wp = w.data();
+  if (wn) *wn = (int)w.size();
+  if (sp_) *sp_ = s.data();
+  if (sn) *sn = (int)s.size();
+  return OHW_OK;
+}
+int ohw_engine_last_token_times(ohw_engine* e, const ohw_token_time** t, int* n) {
+  if (!e || !t || !n) return OHW_E_INVALID_ARG;
+  return spans_out(e->last_token_times, e->last_words, e->last_segments, t, n, nullptr, nullptr, nullptr, nullptr);
+}
+int ohw_engine_last_words(ohw_engine* e, const ohw_span_time** w, int* n) {
+  if (!e || !w || !n) return OHW_E_INVALID_ARG;
+  return spans_out(e->last_token_times, e->last_words, e->last_segments, nullptr, nullptr, w, n, nullptr, nullptr);
+}
+int ohw_engine_last_segments(ohw_engine* e, const ohw_span_time** s, int* n) {
+  if (!e || !s || !n) return OHW_E_INVALID_ARG;
+  return spans_out(e->last_token_times, e->last_words, e->last_segments, nullptr, nullptr, nullptr, nullptr, s, n);
+}
+int ohw_engine_batch_times(ohw_engine* e, int i, const ohw_token_time** token_times, int* n_token_times, const ohw_span_time** words, int* n_words,
+                           const ohw_span_time** segments, int* n_segments) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (i < 0 || i >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "batch_times: no recording " + std::to_string(i) + " in the last transcribe_batch");
+    const ohw_engine::BatchRecord& r = e->batch_records[(size_t)i];
+    spans_out(r.token_times, r.words, r.segments, token_times, n_token_times, words, n_words, segments, n_segments);
+  });
+}
+
+int ohw_word_starts_host(const char* bytes, const int32_t* lens, int n, int32_t* starts_out) {
+  return guard([&] {
+    if (n < 0 || (n > 0 && (!bytes || !lens || !starts_out))) throw Error(OHW_E_INVALID_ARG, "word_starts: bad argument");
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+      if (lens[i] < 0) throw Error(OHW_E_INVALID_ARG, "word_starts: token " + std::to_string(i) + " has a negative length");
+      bool start = i == 0;
+      if (!start && lens[i] > 0 && bytes[off] == ' ') {
+        // do the bytes in front end on a complete UTF-8 sequence?  walk back over continuation bytes to the lead byte
+        size_t k = off, cont = 0;
+        while (k > 0 && cont < 3 && ((unsigned char)bytes[k - 1] & 0xC0) == 0x80) { --k; ++cont; }
+        if (k == 0) start = cont == 0;
+        else {
+          const unsigned char lead = (unsigned char)bytes[k - 1];
+          const size_t want = lead < 0x80 ? 0 : (lead & 0xE0) == 0xC0 ? 1 : (lead & 0xF0) == 0xE0 ? 2 : (lead & 0xF8) == 0xF0 ? 3 : 99;
+          start = want == cont;
+        }
+      }
+      starts_out[i] = start ? 1 : 0;
+      off += (size_t)lens[i];
+    }
+  });
+}
+
+int ohw_segments_host(const int32_t* tokens, int n, const ohw_special_tokens* tok, float t_off, float t_end, ohw_token_span* out, int cap) {
+  if (n < 0 || (n > 0 && !tokens) || !tok || cap < 0 || (cap > 0 && !out)) return OHW_E_INVALID_ARG;
+  int count = 0, first = -1;
+  float t0 = t_off;
+  auto put = [&](int end, float t1) {
+    if (count < cap) out[count] = ohw_token_span{first, end, t0, t1};
+    ++count;
+    first = -1;
+  };
+  for (int i = 0; i < n; ++i) {
+    const int32_t id = tokens[i];
+    if (id >= tok->timestamp_begin) {
+      const float t = t_off + (float)(id - tok->timestamp_begin) * 0.02f;
+      if (first >= 0) put(i, t);
+      t0 = t;
+    } else if (id < tok->eot && first < 0) first = i;
+  }
+  if (first >= 0) put(n, t_end);
+  return count;
 }
 
 int ohw_engine_set_detect_language(ohw_engine* e, int on) {

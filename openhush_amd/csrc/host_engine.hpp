@@ -36,11 +36,23 @@ struct ohw_engine {
   std::vector<int32_t> last_trace;   // every decode pass of the last transcribe: {window, temperature * 1000, n, tokens...}
   // ohw_engine_transcribe_batch: one record per recording, in submission order (ohw_engine_batch_result)
   // lang_id: the language the recording was decoded in when it had one of its own (detected or caller-given), else -1
-  struct BatchRecord { std::string text; std::vector<int32_t> tokens; ohw_window_quality quality{}; int32_t lang_id = -1; };
+  struct BatchRecord {
+    std::string text; std::vector<int32_t> tokens; ohw_window_quality quality{}; int32_t lang_id = -1;
+    std::vector<ohw_token_time> token_times; std::vector<ohw_span_time> words, segments;
+  };
   std::vector<BatchRecord> batch_records;
   // language detection (ohw_engine_set_detect_language; only with language "auto" on a multilingual model).  given_lang: the pool
   // detected on its first engine and hands the id to this one (-1: detect yourself).  last_lang_id / last_lang_prob: what the
   // last transcribe decoded in and the detection's probability of it (1 when nothing was detected)
+  // word timestamps (ohw_engine_set_word_timestamps): the heads every state of the engine aligns with (empty: off), and the
+  // times of the last transcribe; words / segments index last_text
+  std::vector<ohw_align_head> wt_heads;
+  std::vector<ohw_token_time> last_token_times;
+  std::vector<ohw_span_time> last_words, last_segments;
+  // one mark per window record of last_quality: where the window's text starts in the UNTRIMMED text the spans index while
+  // engine_transcribe_core runs, and how many token times / words / segments it added (the pool re-indexes with these)
+  struct WindowMark { size_t text0 = 0; int32_t n_token_times = 0, n_words = 0, n_segments = 0; };
+  std::vector<WindowMark> last_marks;
   bool detect_language = false;
   int32_t given_lang = -1;
   float given_prob = 0.f;
@@ -60,6 +72,8 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
 // rec_langs (with recs; may be null): one language id or OHW_LANG_DETECT per recording
 void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text, int64_t win_first = 0, int64_t win_step = 1,
                             const ohw_audio_span* recs = nullptr, int n_recs = 0, const int32_t* rec_langs = nullptr);
+// a text lost `lead` bytes at its front and now holds new_len bytes: move and cut the spans that index it
+void trim_spans(std::vector<ohw_span_time>& v, size_t lead, size_t new_len);
 // does a transcribe of this engine detect?  (the setting, language "auto", a multilingual model)
 bool engine_detects(const ohw_engine* e);
 // whisper.cpp detects once per whisper_full call, on the first window: the front end of window 0 of the recording alone on the

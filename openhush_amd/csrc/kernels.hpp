@@ -222,4 +222,52 @@ void launch_lang_pick(const float* logits, int64_t ld, int sot, int n_langs, int
 // the prompt rows of a decode under a language table, built where the table lives.  Returns n_prompt
 int launch_prompt_fill(const int32_t* lang, int32_t* step_tok, int batch, int sot, int multilingual, int task, int no_ts, hipStream_t s);
 
+// ---- word timestamps (align.hip; ohw_state_align) -----------------------------------------------------------------------
+// the listed heads of ONE decoder layer: workgroup x of the tap serves head head[x] and writes slot slot[x] of the caller's list
+struct AlignTapList { int32_t n; int16_t slot[OHW_ALIGN_MAX_HEADS]; int16_t head[OHW_ALIGN_MAX_HEADS]; };
+struct AlignTapParams {
+  const void* q;            // T [windows * rows][64 * n_head]: the layer's cross-attention queries of this chunk (st->dq)
+  const void* xk;           // T [windows][n_head][t_len][64]: the layer's cross K
+  int32_t n_head, t_len;
+  int32_t rows, row0;       // query rows per window in this launch (1..8); their first row index in p
+  int32_t row_cap;          // rows of p per (window, head): rows from row_cap on are not stored
+  int32_t lds_stride;       // >= every window's n_keys (more keys than that are not read), <= t_len
+  const int32_t* n_keys;    // device [windows]: soft-max over keys 0 .. n_keys - 1
+  const int32_t* n_all;     // device [windows] or null: rows from n_all[b] on are not stored
+  float* p;                 // f32: p[b * p_win + a * p_head + row * p_row + t]
+  int64_t p_win, p_head, p_row;
+  int32_t p_fill;           // keys n_keys .. p_fill - 1 of a stored row are written as 0; p_fill <= p_row
+  float* q_out;             // f32 [windows][row_cap][n_slots][64] or null: the rows as the logits use them (q * 0.125)
+  int32_t n_slots;
+};
+template <typename T> void launch_align_tap(const AlignTapParams& p, const AlignTapList& list, int windows, hipStream_t s);
+struct AlignReduceParams {
+  const float* p;           // as AlignTapParams::p
+  int64_t p_win, p_head, p_row;
+  float* stats;             // f32 scratch [windows][n_heads][ld_stat][2]: mean and standard deviation of every key column
+  int64_t ld_stat;
+  int32_t n_heads, n_prompt;
+  int32_t max_rows, max_keys;   // bounds of m: a window's n_all - n_prompt and n_keys are clamped to them
+  const int32_t* n_all;     // device [windows]: token rows of the window (0: the window is skipped)
+  const int32_t* n_keys;    // device [windows]
+  float* m;                 // f32: m[b * m_win + k * m_row + t], k < n_all[b] - n_prompt
+  int64_t m_win, m_row;
+};
+void launch_align_reduce(const AlignReduceParams& p, int windows, hipStream_t s);
+struct AlignDtwParams {
+  const float* m;           // as AlignReduceParams::m
+  int64_t m_win, m_row;
+  const int32_t* n_rows;    // device [windows]: rows of m (0: the window is skipped), clamped to max_rows
+  const int32_t* n_keys;    // device [windows], clamped to max_keys
+  uint8_t* trace;           // scratch [windows][trace_win], trace_win >= (max_rows + 1) * (max_keys + 1)
+  int64_t trace_win;
+  int32_t* idx;             // i32 [windows][idx_win]: the first key of every row, idx_win >= max_rows
+  int64_t idx_win;
+  int32_t max_rows, max_keys;
+};
+void launch_align_dtw(const AlignDtwParams& p, int windows, hipStream_t s);
+// the host twins (no device): what the two launches above compute, bit for bit
+void align_reduce_host(const float* p, int n_heads, int n_all, int n_prompt, int n_keys, float* m_out);
+void dtw_host(const float* m, int n, int n_keys, int32_t* start_idx_out);
+
 }  // namespace ohw

@@ -41,6 +41,9 @@ struct ohw_pool {
   std::string broadcast_note;          // why RCCL was given up, if it was
   std::vector<int32_t> last_tokens;
   std::vector<ohw_window_quality> last_quality;
+  // times of the last transcribe, gathered in recording order; words / segments index last_text (ohw_pool_set_word_timestamps)
+  std::vector<ohw_token_time> last_token_times;
+  std::vector<ohw_span_time> last_words, last_segments;
 };
 
 namespace {
@@ -232,6 +235,9 @@ ohw_pool* pool_build(const char* language, int translate, const int* device_ids,
     } catch (const Error& e) {
       throw Error(e.code, std::string("pool: weight broadcast: ") + e.what());
     }
+    // a shell has no vocabulary strings; the engines' words and segments index the text they assemble, so every replica gets
+    // the host-side copy of the first context's token bytes
+    for (int i = 1; i < n_devices; ++i) ctxs[(size_t)i]->vocab = ctxs[0]->vocab;
     for (int i = 0; i < n_devices; ++i) {
       ohw_engine* e = engine_wrap_ctx(ctxs[(size_t)i], lang, translate != 0, max_batch, device_ids[i]);
       ctxs[(size_t)i] = nullptr;                 // owned by the engine now
@@ -321,6 +327,32 @@ int ohw_pool_set_detect_language(ohw_pool* p, int on) {
   }
   return OHW_OK;
 }
+int ohw_pool_set_word_timestamps(ohw_pool* p, const ohw_align_head* heads, int n) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_word_timestamps(e, heads, n);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
+int ohw_pool_last_token_times(ohw_pool* p, const ohw_token_time** t, int* n) {
+  if (!p || !t || !n) return OHW_E_INVALID_ARG;
+  *t = p->last_token_times.data();
+  *n = (int)p->last_token_times.size();
+  return OHW_OK;
+}
+int ohw_pool_last_words(ohw_pool* p, const ohw_span_time** w, int* n) {
+  if (!p || !w || !n) return OHW_E_INVALID_ARG;
+  *w = p->last_words.data();
+  *n = (int)p->last_words.size();
+  return OHW_OK;
+}
+int ohw_pool_last_segments(ohw_pool* p, const ohw_span_time** s, int* n) {
+  if (!p || !s || !n) return OHW_E_INVALID_ARG;
+  *s = p->last_segments.data();
+  *n = (int)p->last_segments.size();
+  return OHW_OK;
+}
 int ohw_pool_set_schedule(ohw_pool* p, int schedule, int lanes, int merge) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {
@@ -395,13 +427,33 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
     // gather in recording order: device g's k-th window record is window g + k * G
     p->last_tokens.clear();
     p->last_quality.clear();
+    p->last_token_times.clear(); p->last_words.clear(); p->last_segments.clear();
     std::string text;
-    std::vector<size_t> tok_pos((size_t)G, 0), win_pos((size_t)G, 0);
+    std::vector<size_t> tok_pos((size_t)G, 0), win_pos((size_t)G, 0), tt_pos((size_t)G, 0), wd_pos((size_t)G, 0), sg_pos((size_t)G, 0);
     const int64_t n_rec = seek ? (int64_t)p->engines[0]->last_quality.size() : n_win;
     for (int64_t w = 0; w < n_rec; ++w) {
       const int g = seek ? 0 : (int)(w % used);
       ohw_engine* e = p->engines[(size_t)g];
       if (win_pos[(size_t)g] >= e->last_quality.size()) throw Error(OHW_E_TRANSCRIBE, "pool: a device returned fewer windows than it was dealt");
+      // the window's times: its engine indexed them against its own untrimmed text and counted its own windows
+      if (win_pos[(size_t)g] < e->last_marks.size()) {
+        const ohw_engine::WindowMark& mk = e->last_marks[win_pos[(size_t)g]];
+        for (int i = 0; i < mk.n_token_times; ++i) {
+          ohw_token_time t = e->last_token_times[tt_pos[(size_t)g]++];
+          t.window = (int32_t)w;
+          p->last_token_times.push_back(t);
+        }
+        for (int i = 0; i < mk.n_words; ++i) {
+          ohw_span_time s = e->last_words[wd_pos[(size_t)g]++];
+          s.text_off = s.text_off - mk.text0 + text.size();
+          p->last_words.push_back(s);
+        }
+        for (int i = 0; i < mk.n_segments; ++i) {
+          ohw_span_time s = e->last_segments[sg_pos[(size_t)g]++];
+          s.text_off = s.text_off - mk.text0 + text.size();
+          p->last_segments.push_back(s);
+        }
+      }
       const ohw_window_quality& q = e->last_quality[win_pos[(size_t)g]++];
       p->last_quality.push_back(q);
       for (int i = 0; i < q.n_tokens; ++i) {
@@ -418,6 +470,8 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
     const size_t b1 = text.find_last_not_of(" \t\r\n");
     text = b0 == std::string::npos ? std::string() : text.substr(b0, b1 - b0 + 1);
     p->last_text = text;
+    trim_spans(p->last_words, b0 == std::string::npos ? 0 : b0, text.size());
+    trim_spans(p->last_segments, b0 == std::string::npos ? 0 : b0, text.size());
     if (text_buf && text_cap > 0) {
       const size_t nc = std::min(text.size(), text_cap - 1);
       std::memcpy(text_buf, text.data(), nc);

@@ -121,6 +121,22 @@ class AudioSpan(C.Structure):
     _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_int64)]
 
 
+class AlignHead(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("head", C.c_int32)]
+
+
+class TokenTime(C.Structure):
+    _fields_ = [("id", C.c_int32), ("window", C.c_int32), ("t0", C.c_float), ("t1", C.c_float)]
+
+
+class SpanTime(C.Structure):
+    _fields_ = [("text_off", C.c_size_t), ("text_len", C.c_size_t), ("t0", C.c_float), ("t1", C.c_float)]
+
+
+class TokenSpan(C.Structure):
+    _fields_ = [("first", C.c_int32), ("end", C.c_int32), ("t0", C.c_float), ("t1", C.c_float)]
+
+
 class Timings(C.Structure):
     _fields_ = [("mel_ms", C.c_float), ("encode_ms", C.c_float), ("decode_ms", C.c_float), ("total_ms", C.c_float), ("decode_steps", C.c_int32)]
 
@@ -160,6 +176,10 @@ EXPORTS = [
     "ohw_dbg_attention_var", "ohw_dbg_cross_attn", "ohw_dbg_self_attn",
     "ohw_engine_set_detect_language", "ohw_engine_last_language", "ohw_engine_transcribe_batch_lang", "ohw_pool_set_detect_language",
     "ohw_state_set_window_lang", "ohw_state_detect_window_lang", "ohw_state_window_lang", "ohw_lang_pick_host", "ohw_dbg_lang_pick",
+    "ohw_state_set_align_heads", "ohw_state_align", "ohw_align_reduce_host", "ohw_dtw_host", "ohw_dbg_align_probs", "ohw_dbg_align_reduce",
+    "ohw_dbg_dtw", "ohw_engine_set_word_timestamps", "ohw_engine_last_token_times", "ohw_engine_last_words", "ohw_engine_last_segments",
+    "ohw_engine_batch_times", "ohw_word_starts_host", "ohw_segments_host",
+    "ohw_pool_set_word_timestamps", "ohw_pool_last_token_times", "ohw_pool_last_words", "ohw_pool_last_segments",
 ]
 
 
@@ -407,6 +427,25 @@ def lib():
         L.ohw_lang_pick_host.argtypes = [fp, C.POINTER(SpecialTokens), ip, fp]
         L.ohw_dbg_lang_pick.argtypes = [vp, fp, C.c_int, ip, fp]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
+        L.ohw_state_set_align_heads.argtypes = [vp, C.POINTER(AlignHead), C.c_int]
+        L.ohw_state_align.argtypes = [vp, C.POINTER(SampleParams), ip, C.c_int, ip, ip, C.c_int, ip]
+        L.ohw_align_reduce_host.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
+        L.ohw_dtw_host.argtypes = [fp, C.c_int, C.c_int, ip]
+        L.ohw_dbg_align_probs.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, fp, vp]
+        L.ohw_dbg_align_reduce.argtypes = [C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
+        L.ohw_dbg_dtw.argtypes = [C.c_int, fp, C.c_int, C.c_int, ip]
+        ptt, pst = C.POINTER(C.POINTER(TokenTime)), C.POINTER(C.POINTER(SpanTime))
+        L.ohw_engine_set_word_timestamps.argtypes = [vp, C.POINTER(AlignHead), C.c_int]
+        L.ohw_engine_last_token_times.argtypes = [vp, ptt, C.POINTER(C.c_int)]
+        L.ohw_engine_last_words.argtypes = [vp, pst, C.POINTER(C.c_int)]
+        L.ohw_engine_last_segments.argtypes = [vp, pst, C.POINTER(C.c_int)]
+        L.ohw_engine_batch_times.argtypes = [vp, C.c_int, ptt, C.POINTER(C.c_int), pst, C.POINTER(C.c_int), pst, C.POINTER(C.c_int)]
+        L.ohw_word_starts_host.argtypes = [C.c_char_p, ip, C.c_int, ip]
+        L.ohw_pool_set_word_timestamps.argtypes = [vp, C.POINTER(AlignHead), C.c_int]
+        L.ohw_pool_last_token_times.argtypes = [vp, ptt, C.POINTER(C.c_int)]
+        L.ohw_pool_last_words.argtypes = [vp, pst, C.POINTER(C.c_int)]
+        L.ohw_pool_last_segments.argtypes = [vp, pst, C.POINTER(C.c_int)]
+        L.ohw_segments_host.argtypes = [ip, C.c_int, C.POINTER(SpecialTokens), C.c_float, C.c_float, C.POINTER(TokenSpan), C.c_int]
         L.ohw_dequantize_host.argtypes = [C.c_int, vp, C.c_int64, fp]
         L.ohw_dbg_dequantize.argtypes = [C.c_int, C.c_int, vp, C.c_int64, fp]
         _lib = L
@@ -424,6 +463,75 @@ def lang_pick_host(row: np.ndarray, tok: "SpecialTokens"):
     probs = np.zeros(tok.n_langs, dtype=np.float32)
     _check(lib().ohw_lang_pick_host(_fp(r), C.byref(tok), C.byref(i), _fp(probs)))
     return int(i.value), probs
+
+
+OHW_ALIGN_MAX_HEADS = 32
+ALIGN_SECONDS_PER_INDEX = 0.02      # one encoder position
+
+
+def align_reduce(p: np.ndarray, n_prompt: int, device: Optional[int] = None) -> np.ndarray:
+    """ohw_align_reduce_host (device None; no GPU needed) or ohw_dbg_align_reduce: probabilities [A][n_all][n_keys] -> the
+    alignment matrix m [n_all - n_prompt][n_keys] (z-score per head and key, median of 7 along the keys, mean over the heads)"""
+    p = np.ascontiguousarray(p, dtype=np.float32)
+    assert p.ndim == 3
+    A, n_all, n_keys = p.shape
+    m = np.zeros((max(n_all - int(n_prompt), 0), n_keys), dtype=np.float32)
+    if device is None:
+        _check(lib().ohw_align_reduce_host(_fp(p), A, n_all, int(n_prompt), n_keys, _fp(m)))
+    else:
+        _check(lib().ohw_dbg_align_reduce(int(device), _fp(p), A, n_all, int(n_prompt), n_keys, _fp(m)))
+    return m
+
+
+def dtw(m: np.ndarray, device: Optional[int] = None) -> np.ndarray:
+    """ohw_dtw_host (device None; no GPU needed) or ohw_dbg_dtw: m [n][n_keys] -> the key at which the path first enters each row"""
+    m = np.ascontiguousarray(m, dtype=np.float32)
+    assert m.ndim == 2
+    n, n_keys = m.shape
+    idx = np.zeros(max(n, 1), dtype=np.int32)
+    if device is None:
+        _check(lib().ohw_dtw_host(_fp(m), n, n_keys, _ip(idx)))
+    else:
+        _check(lib().ohw_dbg_dtw(int(device), _fp(m), n, n_keys, _ip(idx)))
+    return idx[:n]
+
+
+def dbg_align_probs(dtype: int, q_ptr: int, xk_ptr: int, rows: int, n_head: int, t_len: int, n_keys: int, heads: Sequence[int],
+                    stream: int = 0) -> np.ndarray:
+    """ohw_dbg_align_probs: the tap kernel on device tensors q [rows][64 * n_head], xk [n_head][t_len][64] -> p [len(heads)][rows][t_len]"""
+    hd = np.asarray(list(heads), dtype=np.int32)
+    out = np.full((len(hd), rows, t_len), np.nan, dtype=np.float32)
+    _check(lib().ohw_dbg_align_probs(int(dtype), C.c_void_p(q_ptr), C.c_void_p(xk_ptr), rows, n_head, t_len, n_keys, _ip(hd), len(hd), _fp(out),
+                                     C.c_void_p(stream or 0)))
+    return out
+
+
+def word_starts(token_bytes: Sequence[bytes]) -> List[bool]:
+    """ohw_word_starts_host (host only): the bytes of one window's text tokens -> which tokens start a word"""
+    lens = np.asarray([len(b) for b in token_bytes], dtype=np.int32)
+    out = np.zeros(max(len(lens), 1), dtype=np.int32)
+    _check(lib().ohw_word_starts_host(b"".join(token_bytes), _ip(lens) if len(lens) else None, len(lens), _ip(out)))
+    return [bool(v) for v in out[:len(lens)]]
+
+
+def segments_host(tokens: Sequence[int], tok: "SpecialTokens", t_off: float, t_end: float):
+    """ohw_segments_host (host only): one window's kept tokens -> [(first, end, t0, t1)], tokens [first, end) of the list"""
+    t = np.asarray(list(tokens), dtype=np.int32)
+    cap = max(len(t), 1)
+    out = (TokenSpan * cap)()
+    n = int(lib().ohw_segments_host(_ip(t) if len(t) else None, len(t), C.byref(tok), float(t_off), float(t_end), out, cap))
+    if n < 0:
+        _raise(n)
+    return [(out[i].first, out[i].end, float(out[i].t0), float(out[i].t1)) for i in range(n)]
+
+
+def _token_times(p, n):
+    return [{"id": int(p[i].id), "window": int(p[i].window), "t0": float(p[i].t0), "t1": float(p[i].t1)} for i in range(n)]
+
+
+def _spans(p, n, text_bytes: bytes):
+    return [{"text": text_bytes[p[i].text_off:p[i].text_off + p[i].text_len].decode("utf-8", "replace"), "text_off": int(p[i].text_off),
+             "text_len": int(p[i].text_len), "t0": float(p[i].t0), "t1": float(p[i].t1)} for i in range(n)]
 
 
 def audio_ctx_for(n_samples: int) -> int:
@@ -688,6 +796,8 @@ class State:
         _check(lib().ohw_state_create(ctx.h, max_batch, C.byref(h)))
         self.h = h
         self.max_batch = max_batch
+        self._align_heads = 0
+        self._align_shape = []
 
     def close(self):
         if getattr(self, "h", None):
@@ -874,6 +984,37 @@ class State:
         _check(lib().ohw_state_window_lang(self.h, int(batch), _ip(ids), _fp(probs)))
         return ids, probs
 
+    def set_align_heads(self, heads: Optional[Sequence[Tuple[int, int]]]):
+        """ohw_state_set_align_heads: the (decoder layer, head) pairs the alignment reads; None / empty clears and frees"""
+        hs = list(heads) if heads is not None else []
+        self._align_heads = len(hs)
+        if not hs:
+            _check(lib().ohw_state_set_align_heads(self.h, None, 0))
+            return
+        arr = (AlignHead * len(hs))(*[AlignHead(int(l), int(h)) for l, h in hs])
+        _check(lib().ohw_state_set_align_heads(self.h, arr, len(hs)))
+
+    def align(self, tokens: Sequence[Sequence[int]], n_frames: Sequence[int], p: Optional[SampleParams] = None) -> List[np.ndarray]:
+        """ohw_state_align for the windows of the last encode: tokens[b] = window b's text tokens (empty: skip the window),
+        n_frames[b] its 10 ms frames of real audio -> per window the start index (20 ms units) of every token, then the end of
+        the last one ([] for a skipped window).  The state's self K/V is stale afterwards; every decode rewrites it."""
+        p = p or self.ctx.default_params()
+        B = len(tokens)
+        stride = max([len(t) for t in tokens] + [1])
+        tk = np.zeros((B, stride), dtype=np.int32)
+        nt = np.zeros(B, dtype=np.int32)
+        for b, t in enumerate(tokens):
+            nt[b] = len(t)
+            tk[b, :len(t)] = np.asarray(t, dtype=np.int32)
+        nf = np.asarray(list(n_frames), dtype=np.int32)
+        assert nf.size == B
+        out = np.full((B, stride + 1), -1, dtype=np.int32)
+        _check(lib().ohw_state_align(self.h, C.byref(p), _ip(tk), stride, _ip(nt), _ip(nf), B, _ip(out)))
+        # what fetch("align_*") needs to shape its result: (prompt length with [no_timestamps], text tokens, n_keys) per window
+        n_prompt = 4 if self.ctx.hp.n_vocab >= 51865 else 2
+        self._align_shape = [(n_prompt, int(nt[b]), max(1, min(self.window_ctx(b), int(nf[b]) // 2))) for b in range(B)]
+        return [out[b, :nt[b] + 1].copy() if nt[b] else np.zeros(0, np.int32) for b in range(B)]
+
     def dbg_lang_pick(self, logits: np.ndarray):
         """the DEVICE language pick on caller-supplied rows [B][n_vocab] -> (ids [B], probs [B][n_langs])"""
         lg = np.ascontiguousarray(np.atleast_2d(logits), dtype=np.float32)
@@ -1000,6 +1141,20 @@ class State:
 
     def fetch(self, what: str, batch: int) -> np.ndarray:
         hp = self.ctx.hp
+        if what in ("align_q", "align_p", "align_m"):
+            # window batch - 1 of the last align(): "align_q" [N_all][A][64], "align_p" [A][N_all][n_keys], "align_m" [N][n_keys]
+            A = self._align_heads
+            if not A or not 1 <= batch <= len(self._align_shape):
+                raise WhisperError(OHW_E_INVALID_ARG, f"fetch: window {batch - 1} was not aligned by the last align() of this State")
+            n_prompt, n_text, n_keys = self._align_shape[batch - 1]
+            n_all = n_prompt + n_text + 1
+            out = np.empty(max(A * n_all * hp.n_audio_ctx, n_all * A * 64), dtype=np.float32)
+            _check(lib().ohw_state_fetch(self.h, what.encode(), batch, _fp(out), out.size))
+            if what == "align_q":
+                return out[:n_all * A * 64].reshape(n_all, A, 64).copy()
+            if what == "align_p":
+                return out[:A * n_all * n_keys].reshape(A, n_all, n_keys).copy()
+            return out[:(n_text + 1) * n_keys].reshape(n_text + 1, n_keys).copy()
         d, T = hp.n_audio_state, hp.n_audio_ctx
         shape = {"mel": (batch, hp.n_mels, CHUNK_FRAMES), "conv1": (batch, CHUNK_FRAMES, d)}.get(what, (batch, T, d))
         out = np.empty(shape, dtype=np.float32)
@@ -1254,6 +1409,11 @@ class TranscriptionResult:
     text: str
     language: str
     duration_ms: int
+    # transcribe_batch only: the recording's times (WhisperEngine.batch_times); token_times and words stay empty unless
+    # set_word_timestamps is on
+    token_times: list = dataclasses.field(default_factory=list)
+    words: list = dataclasses.field(default_factory=list)
+    segments: list = dataclasses.field(default_factory=list)
 
 
 @dataclasses.dataclass
@@ -1306,6 +1466,47 @@ class WhisperEngine:
         text = C.string_at(full, n.value).decode("utf-8", "replace") if n.value else ""
         return TranscriptionResult(text, lang.value.decode(), int(ms.value))
 
+    def set_word_timestamps(self, heads: Optional[Sequence[Tuple[int, int]]]):
+        """ohw_engine_set_word_timestamps: the (decoder layer, head) pairs to align with; None / empty = off (the default)"""
+        hs = list(heads) if heads is not None else []
+        if not hs:
+            _check(lib().ohw_engine_set_word_timestamps(self.h, None, 0))
+            return
+        arr = (AlignHead * len(hs))(*[AlignHead(int(l), int(h)) for l, h in hs])
+        _check(lib().ohw_engine_set_word_timestamps(self.h, arr, len(hs)))
+
+    def _last_text_bytes(self) -> bytes:
+        full, n = C.c_char_p(), C.c_size_t(0)
+        _check(lib().ohw_engine_last_text(self.h, C.byref(full), C.byref(n)))
+        return C.string_at(full, n.value) if n.value else b""
+
+    def last_token_times(self):
+        """[{id, window, t0, t1}] per aligned text token of the last transcribe (empty unless word timestamps are on)"""
+        p, n = C.POINTER(TokenTime)(), C.c_int(0)
+        _check(lib().ohw_engine_last_token_times(self.h, C.byref(p), C.byref(n)))
+        return _token_times(p, n.value)
+
+    def last_words(self):
+        """[{text, text_off, text_len, t0, t1}] of the last transcribe; offsets index the UTF-8 bytes of its text"""
+        p, n = C.POINTER(SpanTime)(), C.c_int(0)
+        _check(lib().ohw_engine_last_words(self.h, C.byref(p), C.byref(n)))
+        return _spans(p, n.value, self._last_text_bytes())
+
+    def last_segments(self):
+        """the same for the segments between timestamp tokens (always available)"""
+        p, n = C.POINTER(SpanTime)(), C.c_int(0)
+        _check(lib().ohw_engine_last_segments(self.h, C.byref(p), C.byref(n)))
+        return _spans(p, n.value, self._last_text_bytes())
+
+    def batch_times(self, i: int):
+        """(token_times, words, segments) of recording i of the last transcribe_batch"""
+        tp, tn = C.POINTER(TokenTime)(), C.c_int(0)
+        wp, wn = C.POINTER(SpanTime)(), C.c_int(0)
+        sp, sn = C.POINTER(SpanTime)(), C.c_int(0)
+        _check(lib().ohw_engine_batch_times(self.h, int(i), C.byref(tp), C.byref(tn), C.byref(wp), C.byref(wn), C.byref(sp), C.byref(sn)))
+        tb = self.batch_result(i)[0].encode("utf-8")
+        return _token_times(tp, tn.value), _spans(wp, wn.value, tb), _spans(sp, sn.value, tb)
+
     def set_detect_language(self, on: bool = True):
         """ohw_engine_set_detect_language: with language "auto" on a multilingual model, transcribe detects the language on its
         first window and transcribe_batch on every recording (default off: "auto" is "en", as in the reference)"""
@@ -1354,7 +1555,12 @@ class WhisperEngine:
         else:
             _check(lib().ohw_engine_transcribe_batch_lang(self.h, spans, _ip(langs), len(bufs), rates.pop()))
         ms = int((time.perf_counter() - t0) * 1000)
-        return [TranscriptionResult(self.batch_result(i)[0], self.batch_result(i)[3], ms) for i in range(len(bufs))]
+        out = []
+        for i in range(len(bufs)):
+            r = self.batch_result(i)
+            tt, words, segs = self.batch_times(i)
+            out.append(TranscriptionResult(r[0], r[3], ms, tt, words, segs))
+        return out
 
     def batch_result(self, i: int):
         """(text, tokens, quality dict, language) of recording i of the last transcribe_batch"""
@@ -1503,6 +1709,33 @@ class EnginePool:
     def set_detect_language(self, on: bool = True):
         """ohw_pool_set_detect_language: WhisperEngine.set_detect_language on every engine; the pool detects once, on its first"""
         _check(lib().ohw_pool_set_detect_language(self.h, int(bool(on))))
+
+    def set_word_timestamps(self, heads: Optional[Sequence[Tuple[int, int]]]):
+        """ohw_pool_set_word_timestamps: WhisperEngine.set_word_timestamps on every engine; None / empty = off"""
+        hs = list(heads) if heads is not None else []
+        arr = (AlignHead * len(hs))(*[AlignHead(int(l), int(h)) for l, h in hs]) if hs else None
+        _check(lib().ohw_pool_set_word_timestamps(self.h, arr, len(hs)))
+
+    def _last_text_bytes(self) -> bytes:
+        full, n = C.c_char_p(), C.c_size_t(0)
+        _check(lib().ohw_pool_last_text(self.h, C.byref(full), C.byref(n)))
+        return C.string_at(full, n.value) if n.value else b""
+
+    def last_token_times(self):
+        """as WhisperEngine.last_token_times, gathered in recording order (window = the window of the recording)"""
+        p, n = C.POINTER(TokenTime)(), C.c_int(0)
+        _check(lib().ohw_pool_last_token_times(self.h, C.byref(p), C.byref(n)))
+        return _token_times(p, n.value)
+
+    def last_words(self):
+        p, n = C.POINTER(SpanTime)(), C.c_int(0)
+        _check(lib().ohw_pool_last_words(self.h, C.byref(p), C.byref(n)))
+        return _spans(p, n.value, self._last_text_bytes())
+
+    def last_segments(self):
+        p, n = C.POINTER(SpanTime)(), C.c_int(0)
+        _check(lib().ohw_pool_last_segments(self.h, C.byref(p), C.byref(n)))
+        return _spans(p, n.value, self._last_text_bytes())
 
     def engine_handle(self, i: int):
         return lib().ohw_pool_engine(self.h, i)
