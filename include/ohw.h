@@ -867,6 +867,45 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  * The persistent step (ohw_state_set_persistent) counts only its logits GEMM.                                    */
 int ohw_dbg_counter(const ohw_state* st, const char* name);
 
+/* ONE beam step (beam_topk_kernel + beam_update_kernel, as ohw_beam_search launches them) on caller-supplied host data; the
+ * whole resulting state comes back.  No decoder runs.  Rows: beam j of window w is row w * K + j, R = W * K rows.
+ * side (0 / 1): which half of the token-history and kv_slot double buffers holds the input; the step writes the other half,
+ * as ohw_beam_search alternates them.  The state's logit bias applies; p->n_max is used as given (not clamped).
+ * Every range is checked on the host before any device work (OHW_E_INVALID_ARG): K in 2..5, R <= max_batch,
+ * 0 <= n_cur[w] < n_text_ctx (the state's token capacity), 0 <= n_past_w[w] and n_past_w[w] + 2 <= n_text_ctx,
+ * fin_cnt[w] in 0..K, fin_len of the used pool slots in 0..n_text_ctx, history tokens (the first n_cur[w] of a row) in
+ * 0..n_vocab - 1 and, when first == 0, the kv_slot entries of positions 0..n_past_w[w] in 0..R - 1 (of a window with win_done
+ * set only fin_cnt and fin_len are checked: the kernels read nothing else of it).
+ * Before the launch tokens_next, kv_slot_next, cand_tok / cand_lp, next_tok, n_past and the pool slots from fin_cnt[w] on
+ * are filled with OHW_DBG_SENTINEL_I32 / OHW_DBG_SENTINEL_F32 and then copied back whole: what holds the sentinel afterwards
+ * was not written.  tickets_out: the top-k's ticket words, zero after every launch.  A later ohw_beam_search on the state
+ * is not disturbed (it re-initialises what it uses). */
+#define OHW_DBG_SENTINEL_I32 (-7777777)
+#define OHW_DBG_SENTINEL_F32 (-12345.0f)
+typedef struct {
+  int32_t first, K, W, side;
+  const float* logits;     /* in  [first ? W : R][n_vocab] */
+  const int32_t* tokens;   /* in  [R][n_text_ctx] token histories, n_cur[w] of them used per row */
+  const int32_t* kv_slot;  /* in  [R][n_text_ctx] */
+  int32_t* n_cur;          /* in / out [W] */
+  int32_t* n_past_w;       /* in / out [W] position the step that just ran wrote */
+  int32_t* win_done;       /* in / out [W] */
+  float* beam_sum;         /* in / out [R] */
+  int32_t* fin_cnt;        /* in / out [W] */
+  int32_t* fin_tok;        /* in / out [R][n_text_ctx] */
+  int32_t* fin_len;        /* in / out [R] */
+  float* fin_sum;          /* in / out [R] */
+  int32_t* cand_tok;       /* out [R][K + 1] */
+  float* cand_lp;          /* out [R][K + 1] */
+  int32_t* tokens_next;    /* out [R][n_text_ctx] */
+  int32_t* kv_slot_next;   /* out [R][n_text_ctx] */
+  int32_t* next_tok;       /* out [R] */
+  int32_t* n_past;         /* out [R] */
+  int32_t* n_done;         /* out [1] windows that finished in this step */
+  uint32_t* tickets_out;   /* out [R] */
+} ohw_dbg_beam_io;
+int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* p, const ohw_dbg_beam_io* io);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1825,7 +1825,10 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SamplerParams p, BeamP
   const int nb = first ? 1 : K;          // first step: the K beams are identical - only beam 0 proposes
   if (tid < nb * (K + 1)) {
     const int j = tid / (K + 1), c = tid % (K + 1), r = w * K + j;
-    s_ctok[tid] = bp.cand_tok[(int64_t)r * (K + 1) + c];
+    // a dead beam (sum -inf: a duplicate written below for j >= saved) proposes nothing, as in the oracle's ref_beam_search: ranked
+    // at -inf, its end-of-text candidate could fill the finished pool and its continuations count as saved
+    const bool dead = !first && !(bp.beam_sum[r] > -INFINITY);
+    s_ctok[tid] = dead ? -1 : bp.cand_tok[(int64_t)r * (K + 1) + c];
     s_csc[tid] = (first ? 0.f : bp.beam_sum[r]) + bp.cand_lp[(int64_t)r * (K + 1) + c];
   }
   __syncthreads();

@@ -1307,6 +1307,18 @@ int ohw_greedy(ohw_state* st, const ohw_sample_params* sp, int batch, int32_t* t
 // OHW_DEBUG_MARKS=1: progress lines on stderr (which HIP call a tool died under)
 #define BMARK(what, i) do { static const bool on_ = env_int("OHW_DEBUG_MARKS", 0, 0, 1) != 0; if (on_) { std::fprintf(stderr, "[ohw beam] %s %d\n", what, (int)(i)); std::fflush(stderr); } } while (0)
 
+// the beam search's buffers of a state, allocated at first use (ohw_beam_search, ohw_dbg_beam_step)
+static void alloc_beam_buffers(ohw_state* st) {
+  if (st->bm_sum.p) return;
+  const size_t MT = (size_t)st->max_tokens, C = (size_t)st->ctx->hp.n_text_ctx, MB = (size_t)st->max_batch;
+  st->bm_cand_lp.alloc(MB * 6 * 4); st->bm_cand_tok.alloc(MB * 6 * 4); st->bm_sum.alloc(MB * 4, true);
+  st->bm_slot[0].alloc(MB * C * 4, true); st->bm_slot[1].alloc(MB * C * 4, true); st->bm_tok2.alloc(MB * MT * 4, true);
+  st->bm_ncur.alloc(MB * 4, true); st->bm_npast.alloc(MB * 4, true); st->bm_done.alloc(MB * 4, true);
+  st->bm_fin_cnt.alloc(MB * 4, true); st->bm_fin_tok.alloc(MB * MT * 4, true); st->bm_fin_len.alloc(MB * 4, true);
+  st->bm_fin_sum.alloc(MB * 4, true);
+  st->bm_part.alloc(MB * BEAM_SPLIT * BEAM_PART_WORDS * 4, true); st->bm_ticket.alloc(MB * 4, true);
+}
+
 int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, int beam_size, int max_tokens, const ohw_beam_result* res) {
   return guard([&] {
     if (!st || !sp || !res || !res->tokens || !res->n_tokens) throw Error(OHW_E_INVALID_ARG, "null argument");
@@ -1323,14 +1335,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = st->stream;
     const int MT = st->max_tokens, C = c->hp.n_text_ctx, MB = st->max_batch;
-    if (!st->bm_sum.p) {
-      st->bm_cand_lp.alloc((size_t)MB * 6 * 4); st->bm_cand_tok.alloc((size_t)MB * 6 * 4); st->bm_sum.alloc((size_t)MB * 4, true);
-      st->bm_slot[0].alloc((size_t)MB * C * 4, true); st->bm_slot[1].alloc((size_t)MB * C * 4, true); st->bm_tok2.alloc((size_t)MB * MT * 4, true);
-      st->bm_ncur.alloc((size_t)MB * 4, true); st->bm_npast.alloc((size_t)MB * 4, true); st->bm_done.alloc((size_t)MB * 4, true);
-      st->bm_fin_cnt.alloc((size_t)MB * 4, true); st->bm_fin_tok.alloc((size_t)MB * MT * 4, true); st->bm_fin_len.alloc((size_t)MB * 4, true);
-      st->bm_fin_sum.alloc((size_t)MB * 4, true);
-      st->bm_part.alloc((size_t)MB * BEAM_SPLIT * BEAM_PART_WORDS * 4, true); st->bm_ticket.alloc((size_t)MB * 4, true);
-    }
+    alloc_beam_buffers(st);
     int32_t prompt[8];
     ohw_sample_params psp = *sp;
     if (lang_tab) psp.lang_id = 0;
@@ -1757,6 +1762,105 @@ int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* sp, const float* lo
   return guard([&] {
     if (!(temperature > 0.0f)) throw Error(OHW_E_INVALID_ARG, "dbg_sample_t: temperature must be > 0");
     dbg_sample(st, sp, logits, history, hist_stride, n_hist, batch, temperature, uniforms, tokens_out, logprobs_out, no_speech_out);
+  });
+}
+
+// test entry: one beam step on caller-supplied rows and state (include/ohw.h).  Everything is range-checked first: the
+// kernels index with these values.
+int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_beam_io* io) {
+  return guard([&] {
+    if (!st || !sp || !io) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (!io->logits || !io->tokens || !io->kv_slot || !io->n_cur || !io->n_past_w || !io->win_done || !io->beam_sum || !io->fin_cnt ||
+        !io->fin_tok || !io->fin_len || !io->fin_sum || !io->cand_tok || !io->cand_lp || !io->tokens_next || !io->kv_slot_next ||
+        !io->next_tok || !io->n_past || !io->n_done || !io->tickets_out)
+      throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: null array");
+    const ohw_ctx* c = st->ctx;
+    const int K = io->K, W = io->W, first = io->first != 0, q = io->side;
+    const int V = c->hp.n_vocab, C = c->hp.n_text_ctx, MT = st->max_tokens;
+    if (K < 2 || K > 5) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: K must be in 2..5");
+    if (W < 1 || (int64_t)W * K > st->max_batch) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: W * K exceeds the state's max_batch");
+    if (q != 0 && q != 1) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: side must be 0 or 1");
+    if (sp->force_len > 0) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: force_len is a greedy-only knob");
+    if (MT != C) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: the state's token capacity is not n_text_ctx");
+    const int R = W * K, K1 = K + 1;
+    for (int w = 0; w < W; ++w) {
+      if (io->fin_cnt[w] < 0 || io->fin_cnt[w] > K) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: fin_cnt out of range");
+      for (int f = 0; f < io->fin_cnt[w]; ++f)
+        if (io->fin_len[w * K + f] < 0 || io->fin_len[w * K + f] > MT) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: fin_len out of range");
+      // both kernels leave a finished window at once: its counters (which may stand at a limit) and rows are never read
+      if (io->win_done[w]) continue;
+      if (io->n_cur[w] < 0 || io->n_cur[w] >= MT) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: n_cur out of range");
+      if (io->n_past_w[w] < 0 || io->n_past_w[w] + 2 > C) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: n_past_w out of range");
+      for (int j = 0; j < K; ++j) {
+        const size_t r = (size_t)(w * K + j);
+        for (int i = 0; i < io->n_cur[w]; ++i)
+          if (io->tokens[r * MT + i] < 0 || io->tokens[r * MT + i] >= V) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: history token out of range");
+        if (!first)
+          for (int i = 0; i <= io->n_past_w[w]; ++i)
+            if (io->kv_slot[r * C + i] < 0 || io->kv_slot[r * C + i] >= R) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step: kv_slot entry out of range");
+      }
+    }
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = st->stream;
+    alloc_beam_buffers(st);
+    int32_t* tokbuf[2] = {st->tokens.as<int32_t>(), st->bm_tok2.as<int32_t>()};
+    // inputs; the pool slots from fin_cnt[w] on hold the sentinel
+    std::vector<int32_t> fin_tok(io->fin_tok, io->fin_tok + (size_t)R * MT), fin_len(io->fin_len, io->fin_len + R);
+    std::vector<float> fin_sum(io->fin_sum, io->fin_sum + R);
+    for (int w = 0; w < W; ++w)
+      for (int f = io->fin_cnt[w]; f < K; ++f) {
+        std::fill_n(&fin_tok[(size_t)(w * K + f) * MT], (size_t)MT, OHW_DBG_SENTINEL_I32);
+        fin_len[(size_t)(w * K + f)] = OHW_DBG_SENTINEL_I32;
+        fin_sum[(size_t)(w * K + f)] = OHW_DBG_SENTINEL_F32;
+      }
+    const std::vector<int32_t> sent_i((size_t)R * std::max(MT, C), OHW_DBG_SENTINEL_I32);
+    const std::vector<float> sent_f((size_t)R * K1, OHW_DBG_SENTINEL_F32);
+    HIP_CHECK(hipMemcpy2DAsync(st->logits.p, (size_t)st->logits_ld * 4, io->logits, (size_t)V * 4, (size_t)V * 4, (size_t)(first ? W : R), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(tokbuf[q], io->tokens, (size_t)R * MT * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(tokbuf[q ^ 1], sent_i.data(), (size_t)R * MT * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_slot[q].p, io->kv_slot, (size_t)R * C * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_slot[q ^ 1].p, sent_i.data(), (size_t)R * C * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_cand_tok.p, sent_i.data(), (size_t)R * K1 * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_cand_lp.p, sent_f.data(), (size_t)R * K1 * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->next_tok.p, sent_i.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->n_past.p, sent_i.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_ncur.p, io->n_cur, (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_npast.p, io->n_past_w, (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_done.p, io->win_done, (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_sum.p, io->beam_sum, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_cnt.p, io->fin_cnt, (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_tok.p, fin_tok.data(), (size_t)R * MT * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_len.p, fin_len.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_sum.p, fin_sum.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
+    SamplerParams p;
+    fill_sampler(st, sp, R, &p);
+    p.tokens = tokbuf[q];
+    BeamParams bp{};
+    bp.K = K; bp.cand_lp = st->bm_cand_lp.as<float>(); bp.cand_tok = st->bm_cand_tok.as<int32_t>(); bp.beam_sum = st->bm_sum.as<float>();
+    bp.kv_slot = st->bm_slot[q].as<int32_t>(); bp.kv_slot_next = st->bm_slot[q ^ 1].as<int32_t>(); bp.tokens_next = tokbuf[q ^ 1];
+    bp.n_cur = st->bm_ncur.as<int32_t>(); bp.n_past_w = st->bm_npast.as<int32_t>(); bp.win_done = st->bm_done.as<int32_t>();
+    bp.fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp.fin_tok = st->bm_fin_tok.as<int32_t>(); bp.fin_len = st->bm_fin_len.as<int32_t>();
+    bp.fin_sum = st->bm_fin_sum.as<float>();
+    bp.part = st->bm_part.as<unsigned>(); bp.tickets = st->bm_ticket.as<unsigned>();
+    launch_beam_step(p, bp, W, first, s);
+    HIP_CHECK(hipMemcpyAsync(io->cand_tok, st->bm_cand_tok.p, (size_t)R * K1 * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->cand_lp, st->bm_cand_lp.p, (size_t)R * K1 * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->tokens_next, tokbuf[q ^ 1], (size_t)R * MT * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->kv_slot_next, st->bm_slot[q ^ 1].p, (size_t)R * C * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->next_tok, st->next_tok.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_past, st->n_past.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_done, st->n_done.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->tickets_out, st->bm_ticket.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_cur, st->bm_ncur.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_past_w, st->bm_npast.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->win_done, st->bm_done.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->beam_sum, st->bm_sum.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->fin_cnt, st->bm_fin_cnt.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->fin_tok, st->bm_fin_tok.p, (size_t)R * MT * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->fin_len, st->bm_fin_len.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->fin_sum, st->bm_fin_sum.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
   });
 }
 

@@ -106,6 +106,19 @@ class BeamResult(C.Structure):
                 ("n_finished", C.POINTER(C.c_int32))]
 
 
+class DbgBeamIO(C.Structure):
+    """ohw_dbg_beam_io"""
+    _fields_ = ([(n, C.c_int32) for n in ("first", "K", "W", "side")] + [("logits", C.POINTER(C.c_float))] +
+                [(n, C.POINTER(C.c_float) if n in ("beam_sum", "fin_sum", "cand_lp") else C.POINTER(C.c_int32))
+                 for n in ("tokens", "kv_slot", "n_cur", "n_past_w", "win_done", "beam_sum", "fin_cnt", "fin_tok", "fin_len", "fin_sum",
+                           "cand_tok", "cand_lp", "tokens_next", "kv_slot_next", "next_tok", "n_past", "n_done")] +
+                [("tickets_out", C.POINTER(C.c_uint32))])
+
+
+OHW_DBG_SENTINEL_I32 = -7777777
+OHW_DBG_SENTINEL_F32 = -12345.0
+
+
 class WindowQuality(C.Structure):
     _fields_ = [("n_tokens", C.c_int32), ("avg_logprob", C.c_float), ("entropy", C.c_float), ("would_fallback", C.c_int32),
                 ("temperature", C.c_float), ("no_speech_prob", C.c_float), ("no_speech", C.c_int32), ("seek_delta", C.c_int32),
@@ -180,6 +193,7 @@ EXPORTS = [
     "ohw_dbg_dtw", "ohw_engine_set_word_timestamps", "ohw_engine_last_token_times", "ohw_engine_last_words", "ohw_engine_last_segments",
     "ohw_engine_batch_times", "ohw_word_starts_host", "ohw_segments_host",
     "ohw_pool_set_word_timestamps", "ohw_pool_last_token_times", "ohw_pool_last_words", "ohw_pool_last_segments",
+    "ohw_dbg_beam_step",
 ]
 
 
@@ -427,6 +441,7 @@ def lib():
         L.ohw_lang_pick_host.argtypes = [fp, C.POINTER(SpecialTokens), ip, fp]
         L.ohw_dbg_lang_pick.argtypes = [vp, fp, C.c_int, ip, fp]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
+        L.ohw_dbg_beam_step.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIO)]
         L.ohw_state_set_align_heads.argtypes = [vp, C.POINTER(AlignHead), C.c_int]
         L.ohw_state_align.argtypes = [vp, C.POINTER(SampleParams), ip, C.c_int, ip, ip, C.c_int, ip]
         L.ohw_align_reduce_host.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
@@ -1072,6 +1087,35 @@ class State:
         _check(lib().ohw_dbg_sample_t(self.h, C.byref(p), _fp(lg), _ip(hist), stride, _ip(nh), B, temperature,
                                       u.ctypes.data_as(C.POINTER(C.c_double)), _ip(tok), _fp(lp), _fp(ns)))
         return tok, lp, ns
+
+    def dbg_beam_step(self, p: SampleParams, K: int, first: bool, state: dict, logits: np.ndarray, side: int = 0) -> dict:
+        """ohw_dbg_beam_step: ONE beam step of the device on host data.  state: tokens [R][n_text_ctx], kv_slot [R][n_text_ctx],
+        beam_sum [R], n_cur / n_past_w / win_done / fin_cnt [W], fin_tok [R][n_text_ctx], fin_len / fin_sum [R] (R = W * K);
+        logits [W][V] when first, else [R][V]; side: the half of the double buffers that holds the input.
+        -> the complete next state under the same keys (tokens / kv_slot: the other half), plus cand_tok, cand_lp [R][K + 1],
+        next_tok, n_past [R], n_done and tickets [R]; what the step did not write holds OHW_DBG_SENTINEL_*"""
+        W = int(np.asarray(state["n_cur"]).size)
+        R, Cx, V = W * K, self.ctx.hp.n_text_ctx, self.ctx.hp.n_vocab
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        assert lg.shape == ((W if first else R), V), lg.shape
+        i32 = lambda k, shape: np.array(state[k], dtype=np.int32, order="C").reshape(shape)
+        f32 = lambda k, shape: np.array(state[k], dtype=np.float32, order="C").reshape(shape)
+        a = dict(tokens=i32("tokens", (R, Cx)), kv_slot=i32("kv_slot", (R, Cx)), n_cur=i32("n_cur", W), n_past_w=i32("n_past_w", W),
+                 win_done=i32("win_done", W), beam_sum=f32("beam_sum", R), fin_cnt=i32("fin_cnt", W), fin_tok=i32("fin_tok", (R, Cx)),
+                 fin_len=i32("fin_len", R), fin_sum=f32("fin_sum", R),
+                 cand_tok=np.zeros((R, K + 1), np.int32), cand_lp=np.zeros((R, K + 1), np.float32),
+                 tokens_next=np.zeros((R, Cx), np.int32), kv_slot_next=np.zeros((R, Cx), np.int32),
+                 next_tok=np.zeros(R, np.int32), n_past=np.zeros(R, np.int32), n_done=np.zeros(1, np.int32))
+        tickets = np.ones(R, np.uint32)
+        io = DbgBeamIO(int(bool(first)), K, W, side, _fp(lg),
+                       *[(_fp(a[n]) if a[n].dtype == np.float32 else _ip(a[n])) for n, _ in DbgBeamIO._fields_[5:-1]],
+                       tickets.ctypes.data_as(C.POINTER(C.c_uint32)))
+        _check(lib().ohw_dbg_beam_step(self.h, C.byref(p), C.byref(io)))
+        out = {k: a[k] for k in ("n_cur", "n_past_w", "win_done", "beam_sum", "fin_cnt", "fin_tok", "fin_len", "fin_sum", "cand_tok",
+                                 "cand_lp", "next_tok", "n_past")}
+        out["tokens"], out["kv_slot"] = a["tokens_next"], a["kv_slot_next"]
+        out["n_done"], out["tickets"] = int(a["n_done"][0]), tickets
+        return out
 
     def sample_pass(self, batch: int, temperature: float, active: Sequence[int], uniforms: np.ndarray, p: Optional[SampleParams] = None):
         """ohw_sample_pass: one temperature pass on the device; uniforms [batch][n_text_ctx] -> greedy_ex's dicts (zeros for
