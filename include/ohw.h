@@ -858,7 +858,7 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  * counts once, at its capture; saturates at INT32_MAX):
  *   "dec_gemm.<gemm><form>.<NT>x<MT>"  gemm: qkv, o (self-attention out), xq, xo (cross-attention q / out), fc1, fc2,
  *                                      logits; form: ".ln" (LayerNorm in the prologue), ".pn" (post-norm), ".ks"
- *                                      (split-K), "" (none); NT x MT n-tiles x m-tiles per workgroup: 1x1 2x1 1x2 2x2 4x2
+ *                                      (split-K), "" (none); NT x MT n-tiles x m-tiles per workgroup: 1x1 2x1 1x2 2x2 4x2 1x6
  *   "xattn.plain" / "xattn.split"      cross-attention, one workgroup per (row, head) / keys cut over gridDim.z > 1
  *   "xattn.rows2" .. "xattn.rows4"     one workgroup per (window, head) for 2..4 new tokens
  *   "xattn.group2" .. "xattn.group5"   the same for 2..5 beams of a window; "xattn.group_split": beams, keys cut

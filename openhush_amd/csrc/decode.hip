@@ -597,6 +597,105 @@ static int dec_gemm_launch(const DecGemmParams& p, hipStream_t s) {
   return NT == 4 ? DG_SHAPE_4x2 : NT == 2 ? (MT == 1 ? DG_SHAPE_2x1 : DG_SHAPE_2x2) : (MT == 1 ? DG_SHAPE_1x1 : DG_SHAPE_1x2);
 }
 
+// Many rows on few CUs with a long K (mlp.2 on a lane of the LANES schedule: 96 rows, K = 5120, 64 CUs): the RESID GEMM with
+// MTW m-tiles per workgroup.  dec_gemm_kernel<RESID, 1, 2> launches n_tiles x ceil(m-tiles / 2) workgroups there, and every row
+// block streams the n-tile's weights again.  Here a workgroup takes MTW m-tiles of its n-tile: a wave requests the weight
+// blocks of its K share once and applies each to every m-tile's activation fragment (L2 hits, fetched G k-blocks at a time).
+// Per (m-tile, n-tile) everything is dec_gemm_kernel's: the 8 waves' interleaved K split, a wave's k-blocks in ascending
+// order through one accumulator, the LDS reduction over the waves in wave order from 0.f, bias, then residual + v.  The
+// bits of the output therefore do not depend on which of the two kernels ran.  No split-K, no statistics, no post-norm.
+template <typename T, int MTW, int G>
+__global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_rows_kernel(DecGemmParams p) {
+  using Ops = TypeOps<T>;
+  using vec8 = typename Ops::vec8;
+  extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+  f32x4* part = (f32x4*)dg_smem;                                      // [8 waves][MTW][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nt = blockIdx.x;
+  const int mt0 = blockIdx.y * MTW;
+  const int kblocks = p.K / 32;
+  TRACE(16 + DEPI_BIAS_RESID * 2, 0);
+  // epilogue coordinates: MTW x 256 outputs over 512 threads; the residual is read now, under the weight stream
+  constexpr int NE = (MTW * 256 + DG_THREADS - 1) / DG_THREADS;
+  float resid_old[NE];
+#pragma unroll
+  for (int i = 0; i < NE; ++i) {
+    const int idx = tid + DG_THREADS * i, ll = (idx >> 2) & 63;
+    const int m = (mt0 + (idx >> 8)) * 16 + (ll & 15), n = nt * 16 + 4 * (ll >> 4) + (idx & 3);
+    resid_old[i] = (idx < MTW * 256 && m < p.M && n < p.N) ? ((const float*)p.out)[(int64_t)m * p.ld_out + n] : 0.f;
+  }
+  const vec8* wt = (const vec8*)p.w + (int64_t)nt * kblocks * 64 + lane;
+  // activation tiles: k-block kk of the 16-row tile mt is the 1 KiB at ((mt * kblocks + kk) * 64 + lane) * 8 elements
+  const T* x0 = (const T*)p.x + ((int64_t)mt0 * kblocks * 64 + lane) * 8;
+  bool ok[MTW];
+#pragma unroll
+  for (int q = 0; q < MTW; ++q) ok[q] = (mt0 + q) * 16 + (lane & 15) < p.M;
+  f32x4 acc[MTW];
+#pragma unroll
+  for (int q = 0; q < MTW; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  auto run = [&](auto ucount, int kb) {
+    constexpr int U = decltype(ucount)::value;
+    constexpr int GG = U < G ? U : G;
+    static_assert(U % GG == 0, "U");
+    vec8 w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) w[u] = __builtin_nontemporal_load(&wt[(int64_t)(kb + DG_WAVES * u) * 64]);
+#pragma unroll
+    for (int g = 0; g < U; g += GG) {
+      // lanes whose row lies past M stay zero and load nothing (one exec-masked batch of loads per m-tile)
+      vec8 a[MTW][GG];
+#pragma unroll
+      for (int q = 0; q < MTW; ++q) {
+#pragma unroll
+        for (int u = 0; u < GG; ++u)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) a[q][u][e] = 0;
+        if (ok[q]) {
+#pragma unroll
+          for (int u = 0; u < GG; ++u) a[q][u] = *(const vec8*)(x0 + ((int64_t)q * kblocks + kb + DG_WAVES * (g + u)) * 512);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < GG; ++u)
+#pragma unroll
+        for (int q = 0; q < MTW; ++q) acc[q] = Ops::mfma16(w[g + u], a[q][u], acc[q]);
+    }
+  };
+  int kb = wave;
+  for (; kb + DG_WAVES * 19 < kblocks; kb += DG_WAVES * 20) run(std::integral_constant<int, 20>{}, kb);
+  for (; kb + DG_WAVES * 3 < kblocks; kb += DG_WAVES * 4) run(std::integral_constant<int, 4>{}, kb);
+  for (; kb < kblocks; kb += DG_WAVES) run(std::integral_constant<int, 1>{}, kb);
+
+  TRACE(16 + DEPI_BIAS_RESID * 2, 2);
+#pragma unroll
+  for (int q = 0; q < MTW; ++q) part[(wave * MTW + q) * 64 + lane] = acc[q];
+  __syncthreads();
+  // D layout: n = 4*(lane'>>4) + reg, m = mt*16 + (lane' & 15)
+  const float* pp = (const float*)part;
+#pragma unroll
+  for (int i = 0; i < NE; ++i) {
+    const int idx = tid + DG_THREADS * i, q = idx >> 8, ll = (idx >> 2) & 63, reg = idx & 3;
+    if (idx >= MTW * 256) continue;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < DG_WAVES; ++w) v += pp[((w * MTW + q) * 64 + ll) * 4 + reg];
+    const int m = (mt0 + q) * 16 + (ll & 15), n = nt * 16 + 4 * (ll >> 4) + reg;
+    if (m >= p.M || n >= p.N) continue;
+    if (p.bias) v += p.bias[n];
+    ((float*)p.out)[(int64_t)m * p.ld_out + n] = resid_old[i] + v;
+  }
+  TRACE(16 + DEPI_BIAS_RESID * 2, 3);
+}
+
+template <typename T, int MTW, int G>
+static int dec_gemm_rows_launch(const DecGemmParams& p, hipStream_t s) {
+  const int n_tiles = (p.N + 15) / 16, mt = (p.M + 15) / 16;
+  hipLaunchKernelGGL((dec_gemm_rows_kernel<T, MTW, G>), dim3(n_tiles, (mt + MTW - 1) / MTW), dim3(DG_THREADS), (size_t)DG_WAVES * MTW * 64 * 16, s, p);
+  return DG_SHAPE_1x6;
+}
+
 template <typename T, int EPI, bool LN>
 static int dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
   // with the LayerNorm image in LDS one workgroup fills a CU: keep the grid within one wave of the CUs this
@@ -638,7 +737,14 @@ static int dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
   if constexpr ((LN && (EPI == DEPI_QKV || EPI == DEPI_BIAS_T || EPI == DEPI_BIAS_GELU_T)) || (!LN && (EPI == DEPI_BIAS_RESID || EPI == DEPI_LOGITS))) {
     const int64_t wgs = LN ? (int64_t)((n_tiles + 1) / 2) * ((mt + 1) / 2) : (int64_t)n_tiles * ((mt + 1) / 2);
     if (nt4 && mt > 2 && p.ksplit <= 1 && !p.pn && !p.stat_out && p.K <= DG_LN_MAXK && wgs > 2 * cus) return dec_gemm_launch<T, EPI, LN, 4, 2>(p, s);
-    // (mlp.2, K = 5120, keeps its single-tile workgroups: two tiles per workgroup measured the same within the run-to-run noise)
+    // (mlp.2, K = 5120, keeps one n-tile per workgroup: two n-tiles measured the same within the run-to-run noise; its rows form follows)
+  }
+  // the same rows-on-few-CUs condition with a K beyond the four-tile form (mlp.2): a workgroup takes up to six m-tiles of
+  // its n-tile and streams the weights once (dec_gemm_rows_kernel; OHW_DEC_ROWS=0: off)
+  if constexpr (EPI == DEPI_BIAS_RESID && !LN) {
+    static const int rows = getenv("OHW_DEC_ROWS") ? atoi(getenv("OHW_DEC_ROWS")) : 1;
+    if (rows && mt > 2 && p.ksplit <= 1 && !p.pn && !p.stat_out && p.K > DG_LN_MAXK && (int64_t)n_tiles * ((mt + 1) / 2) > 2 * cus)
+      return dec_gemm_rows_launch<T, 6, 4>(p, s);
   }
   if ((LN && n_tiles > cus) || (EPI == DEPI_LOGITS && logits_nt == 2)) return dec_gemm_launch<T, EPI, LN, 2, 2>(p, s);
   return dec_gemm_launch<T, EPI, LN, 1, 2>(p, s);

@@ -101,7 +101,7 @@ enum DecTallyGemm { DT_QKV, DT_O, DT_XQ, DT_XO, DT_FC1, DT_FC2, DT_LOGITS, DT_GE
 enum DecTallyForm { DT_PLAIN, DT_LN, DT_PN, DT_KSPLIT, DT_FORMS };
 static const char* const kDecTallyGemm[DT_GEMMS] = {"qkv", "o", "xq", "xo", "fc1", "fc2", "logits"};
 static const char* const kDecTallyForm[DT_FORMS] = {"", ".ln", ".pn", ".ks"};
-static const char* const kDecTallyShape[DG_N_SHAPES] = {"1x1", "2x1", "1x2", "2x2", "4x2"};
+static const char* const kDecTallyShape[DG_N_SHAPES] = {"1x1", "2x1", "1x2", "2x2", "4x2", "1x6"};
 static const char* const kXattnTally[XA_N_VARIANTS] = {"plain", "split", "rows2", "rows3", "rows4", "group2", "group3", "group4", "group5", "group_split"};
 static const char* const kSelfAttnTally[4] = {"plain", "slots", "fused", "fused_slots"};
 

@@ -106,7 +106,7 @@ struct DecGemmParams {
 };
 // the launchers below return which instantiation they launched (the state tallies them: ohw_dbg_counter); the pick itself
 // does not depend on the tally
-enum DecGemmShape { DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_N_SHAPES };   // n-tiles x m-tiles per workgroup
+enum DecGemmShape { DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_SHAPE_1x6, DG_N_SHAPES };   // n-tiles x m-tiles per workgroup
 template <typename T> int launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s);
 
 // x f32 [M][d] = token_embedding[tok[m]] + pos_emb[n_past[m / n_new] + m % n_new]

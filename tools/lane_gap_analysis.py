@@ -13,7 +13,7 @@ from collections import defaultdict
 
 
 def short(name):
-    m = re.search(r"(cross_attn_rows_kernel|cross_attn_kernel|self_attn_kernel|dec_gemm_kernel|sampler_kernel|embed_kernel|gemm256_kernel|"
+    m = re.search(r"(cross_attn_rows_kernel|cross_attn_kernel|self_attn_lane_kernel|self_attn_kernel|dec_gemm_rows_kernel|dec_gemm_kernel|sampler_kernel|embed_kernel|gemm256_kernel|"
                   r"encoder_attention_kernel|layernorm_kernel|mel_\w+_kernel|beam_\w+_kernel)", name)
     base = m.group(1) if m else name[:40]
     if base == "dec_gemm_kernel":
