@@ -471,6 +471,39 @@ enum { OHW_LANG_DETECT = -1 };
 int ohw_state_set_window_lang(ohw_state* st, const int32_t* lang_ids, int batch);
 int ohw_state_detect_window_lang(ohw_state* st, int batch);
 int ohw_state_window_lang(ohw_state* st, int batch, int32_t* ids_out, float* probs_out);
+/* per-window text context ("prompted decoding"; opt-in: with no table every call computes what it computed before).
+ * ohw_state_set_window_prompt: tokens [batch][stride], n_tokens [batch]: decode-batch slot b decodes behind n_tokens[b] context
+ * tokens - text so far: an initial prompt, or the text of the chunk before - with ids in 0 .. n_vocab - 1 and
+ * 0 <= n_tokens[b] <= n_text_ctx / 2 - 1 (OHW_E_INVALID_ARG otherwise, and for batch > max_batch); tokens NULL (or batch 0) clears
+ * the table.  A slot with n_tokens[b] = 0 has no context and gets no [prev] token; a slot with n > 0 occupies n + 1 positions:
+ * [prev], then its tokens.  The table is uploaded once and lives in device memory.
+ * ohw_state_window_prompt_len: the positions slot `window`'s context occupies, 0 or n + 1.
+ * ohw_state_prefill: for the windows of the last encode (batch must equal its batch and the table's; active [batch] or NULL: the
+ * windows to serve), runs the context through the decoder in chunks of 8 positions at n_past = 0, 8, .. and leaves every
+ * layer's self K/V of positions 0 .. len[b] - 1 in cache row b; no logits.  A window whose context ends inside a chunk is fed
+ * [eot] in the surplus rows: they write cache positions at or past len[b], which a decode that starts at n_past = len[b]
+ * overwrites before it reads them.  Windows a chunk has nothing for are skipped by its cross-attention.  A no-op while no table
+ * is set.  Callers of ohw_decode / ohw_decode_active call it themselves and start at n_past = len[b].
+ * While a table is set, ohw_greedy, ohw_greedy_ex, ohw_sample_pass (for its active windows) and ohw_beam_search run the prefill
+ * first and start window b at position len[b]; n_max is capped by n_text_ctx - n_prompt - the largest len.  The context is not
+ * part of the returned tokens, log-probabilities or counts, and the timestamp and blank rules see the window's own tokens only.
+ * ohw_beam_search keeps window w's context and prompt in cache row w * beam_size, which only w's beams write.
+ * Positions are device data: decoding again under other lengths captures no graph, as long as p->n_max does not exceed the cap
+ * above (the capped value is one of the sampler parameters a captured step is keyed by; the default n_max never exceeds it).  ohw_state_align replays without the context.
+ * OHW_PREFILL_XA=0 (read when a state is created) sends the chunks' cross-attention through the single-row kernels (an A/B knob). */
+int ohw_state_set_window_prompt(ohw_state* st, const int32_t* tokens, int stride, const int32_t* n_tokens, int batch);
+int ohw_state_window_prompt_len(const ohw_state* st, int window);
+int ohw_state_prefill(ohw_state* st, int batch, const int32_t* active);
+/* text -> token ids, the scheme of whisper.cpp's tokenizer restated (csrc/tokenize.cpp states the rule): the text is split into
+ * pieces (contractions; an optional space and a run of letters, of digits, or of other non-space bytes; runs of white space), and
+ * inside a piece the longest vocabulary entry that is a prefix of the rest is taken, again and again; a byte no entry starts
+ * with is skipped.  Both return the number of tokens written to out [cap], or OHW_E_INVALID_ARG when cap is too small.
+ * ohw_tokenize_host: the vocabulary is n_vocab entries laid end to end in vocab_bytes, entry i of lens[i] bytes and id i.
+ * ohw_tokenize: the model's text tokens (ids below end-of-text).  No device needed.
+ * ohw_prompt_clip_host: a prompt keeps its LAST n_text_ctx / 2 - 1 tokens; out [min(n, n_text_ctx / 2 - 1)]; returns the count. */
+int ohw_tokenize_host(const char* vocab_bytes, const int32_t* lens, int n_vocab, const char* text, int32_t* out, int cap);
+int ohw_tokenize(const ohw_ctx* ctx, const char* text, int32_t* out, int cap);
+int ohw_prompt_clip_host(const int32_t* in, int n, int n_text_ctx, int32_t* out);
 /* what the device pick computes, on the host: row is one logits row [n_vocab]; *id = arg-max of row[sot + 1 + i], i < n_langs
  * (the first maximum), probs [n_langs] or NULL = soft-max over those columns in fp32 arithmetic.  No device needed.  A row
  * whose language columns are all -inf or NaN gives id 0 and NaN probabilities, on the host and on the device alike.        */
@@ -657,6 +690,14 @@ int ohw_engine_set_force_len(ohw_engine* e, int n_tokens);
  * (audio is never dropped silently); -1 = auto: a recording that fits one window runs at ohw_audio_ctx_for(n_samples),
  * anything longer at the full context.                                                                                   */
 int ohw_engine_set_audio_ctx(ohw_engine* e, int n);
+/* an initial prompt (whisper.cpp's initial_prompt / prompt_tokens: names, jargon, spelling hints): text (tokenized with
+ * ohw_tokenize; NULL or "" clears) or token ids (n = 0 clears; ids outside the vocabulary: OHW_E_INVALID_ARG).  A prompt longer
+ * than n_text_ctx / 2 - 1 tokens keeps its last n_text_ctx / 2 - 1.  Every window of every schedule (fixed cuts, the seek loop,
+ * ohw_engine_transcribe_batch, lanes, the pool) decodes behind it through ohw_state_set_window_prompt; it is not part of the
+ * result.  Temperature ladder: passes with T < 0.5 decode behind the prompt, the table is cleared before the first pass with
+ * T >= 0.5 and set again for the next batch.  Off by default: with no prompt ever set nothing takes a new path.             */
+int ohw_engine_set_initial_prompt(ohw_engine* e, const char* text);
+int ohw_engine_set_initial_prompt_tokens(ohw_engine* e, const int32_t* tokens, int n);
 /* ohw_state_set_packed_encoder on the engine's own, pipeline and lane states, those made later included (default: what
  * OHW_ENC_PACKED gave the engine's own state).  It matters for ohw_engine_transcribe_batch under the auto context (-1): a
  * batch of mixed lengths then encodes the sum of its contexts; tokens, text and quality records do not change.             */
@@ -751,6 +792,7 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
  * disagree.  All three modes give the single engine's tokens: each device is handed the whole recording and cuts its own
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
+int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text);           /* ohw_engine_set_initial_prompt on every engine */
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
 int ohw_pool_set_packed_encoder(ohw_pool* p, int on);
 int ohw_pool_set_detect_language(ohw_pool* p, int on);                     /* ohw_engine_set_detect_language on every engine */                     /* ohw_engine_set_packed_encoder on every engine */
@@ -823,6 +865,13 @@ enum { OHW_SA_PLAIN = 0, OHW_SA_SLOTS };
 int ohw_dbg_cross_attn(int dtype, const void* q, const void* xk, const void* xv, void* out, int M, int n_new, int n_head, int t_len,
                        int kv_group, int batch_invariant, const int32_t* done_host, const int32_t* win_len_host, float* partials,
                        unsigned* tickets, int max_split_rows, int* variant_out, void* stream);
+/* ohw_dbg_cross_attn_chunk: the prefill's cross-attention (cross_attn_chunk_kernel: ohw_state_prefill) on caller data.  q
+ *   [windows * 8][d] row-major, row b * 8 + i is query i of window b; xk / xv, win_len and done as above; out in activation-tile
+ *   order, ceil(windows * 8 / 16) tiles.  The caller pre-fills out: the rows of a window with done != 0, and the rows of the
+ *   last tile past windows * 8, keep what they held.  OHW_E_INVALID_ARG for windows < 1, t_len < 1 and a win_len entry outside
+ *   1 .. t_len.                                                                                                             */
+int ohw_dbg_cross_attn_chunk(int dtype, const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
+                             const int32_t* win_len_host, const int32_t* done_host, void* stream);
 int ohw_dbg_self_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past_host, void* out, int M,
                       int n_new, int n_head, int n_ctx, const int32_t* kv_slot_host, int* variant_out, void* stream);
 /* The alignment kernels on caller data (tests/test_gpu_align.py).
@@ -861,6 +910,7 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  *                                      (split-K), "" (none); NT x MT n-tiles x m-tiles per workgroup: 1x1 2x1 1x2 2x2 4x2 1x6
  *   "xattn.plain" / "xattn.split"      cross-attention, one workgroup per (row, head) / keys cut over gridDim.z > 1
  *   "xattn.rows2" .. "xattn.rows4"     one workgroup per (window, head) for 2..4 new tokens
+ *   "xattn.chunk"                      the prefill's 8 rows per window on the MFMA units (ohw_state_prefill)
  *   "xattn.group2" .. "xattn.group5"   the same for 2..5 beams of a window; "xattn.group_split": beams, keys cut
  *   "self_attn.plain" / ".slots"       masked self-attention, without / with the beam kv_slot table; ".fused" /
  *                                      ".fused_slots": the same inside the QKV launch (OHW_DEC_FUSE_ATTN=1)

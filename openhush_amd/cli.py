@@ -163,6 +163,8 @@ def main(argv=None) -> int:
     t.add_argument("--audio-ctx", default="0", metavar="N|auto",
                    help="reduced audio context (whisper.cpp's audio_ctx): 0 (default) the full 30 s context; N encoder positions per window "
                         "(320 samples each; audio past them is an error, never dropped); auto: sized to a recording of at most 30 s")
+    t.add_argument("--prompt", default="", metavar="TEXT",
+                   help="initial prompt (whisper.cpp's initial_prompt): names, jargon and spelling hints every window is decoded behind")
     t.add_argument("--packed-encoder", action="store_true",
                    help="run the encoder on the sum of the windows' contexts when a batch carries per-window contexts (the engine's "
                         "transcribe_batch under --audio-ctx auto); same output, default off")
@@ -207,6 +209,9 @@ def main(argv=None) -> int:
         if audio_ctx != 0:
             print("error: --audio-ctx is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
             return 1
+        if args.prompt:
+            print("error: --prompt is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+            return 1
         return _transcribe_ranks(args, audio)
     use_gpu = args.device.lower() != "cpu"                    # reference src/main.rs:1037
     dev = int(args.device.split(":")[1]) if ":" in args.device else 0
@@ -218,6 +223,8 @@ def main(argv=None) -> int:
         eng.set_window_mode(E.OHW_WINDOW_FIXED_RECORDING_MEL)
     if audio_ctx != 0:
         eng.set_audio_ctx(audio_ctx)
+    if args.prompt:
+        eng.set_initial_prompt(args.prompt)
     if args.packed_encoder:
         eng.set_packed_encoder(True)
     if args.detect_language:

@@ -1207,6 +1207,183 @@ int launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// cross-attention of the 8 query rows of one prefill chunk (ohw_state_prefill): one workgroup per (head, window) streams the
+// window's K and V ONCE for all 8 rows (row by row, cross_attn_kernel reads them 8 times), and both products run on the MFMA
+// units - 8 rows x 1500 keys is a small matrix product, on the VALU its arithmetic per key costs what the stream costs.
+//
+// Wave w of the 4 takes the 32-key blocks w, w + 4, ... (XAC_KB keys; the workgroup advances 4 * XAC_KB per round):
+//   S^T = K Q^T   two v_mfma_f32_16x16x32 per 16-key tile.  A = K straight from HBM: the operand map (lane l: row l & 15,
+//                 k = 8 (l >> 4) + j) is 16 contiguous bytes of key row l & 15.  B = Q^T, the 8 rows in columns 0..7, the
+//                 columns 8..15 zero.  A lane then holds, for query l & 15, keys 4g .. 4g + 3 (g = l >> 4) of each tile.
+//   softmax       fp32, exp2 domain; the block maximum of a query over its 4 lanes (xor 16, 32), so the query's lanes share
+//                 one running maximum and O^T (query on the lane) is rescaled lane-locally; the sum stays per lane until the end.
+//   O^T += V^T P^T  the 8 probabilities of a lane (2 tiles x 4 registers), rounded to T, ARE the B operand of one 32-key
+//                 k-step when k = 8g + j stands for key 16 (j >> 2) + 4g + (j & 3): a sum over keys does not care about their
+//                 order.  V^T (A operand, 4 tiles of 16 columns) is read in that permutation from the wave's own LDS image of
+//                 its 32 V rows with ds_read_b64_tr_b16: group g of 16 lanes takes rows 16t + 4g .. + 3, t = 0, 1.
+// The image has 160-byte rows (the 8 rows a 32-lane half reads start 8 banks apart: conflict-free) and belongs to one wave:
+// LDS instructions of a wave complete in order, so no workgroup barrier stands in the key loop.  Keys past the length are
+// loaded from the last valid row (finite data) and masked to -inf before the maximum; a wave only enters blocks that hold a
+// valid key, so its maximum is finite from its first block on, and a wave without blocks keeps (-inf, 0), which the merge
+// of the 4 waves' states (as in cross_attn_rows_kernel) gives weight 0.
+// ------------------------------------------------------------------------------------------------
+constexpr int XAC_KB = 32;                 // keys per wave and block
+constexpr int XAC_VROW = 160;              // bytes per V row in LDS (128 of data)
+
+template <typename T, bool VAR>
+__global__ __launch_bounds__(XA_THREADS) void cross_attn_chunk_kernel(const T* __restrict__ q, const T* __restrict__ xk, const T* __restrict__ xv,
+                                                                      T* __restrict__ out, int n_head, int t_len,
+                                                                      const int32_t* __restrict__ done, const int32_t* __restrict__ win_len) {
+  using Ops = TypeOps<T>;
+  using vec8 = typename Ops::vec8;
+  __shared__ __attribute__((aligned(16))) unsigned char vimg[4][XAC_KB * XAC_VROW];
+  __shared__ float red_m[4][8], red_l[4][8];
+  __shared__ float red_o[4][8][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = blockIdx.x, b = blockIdx.y;
+  if (done && done[b]) return;
+  const int d = n_head * 64;
+  const int c = lane & 15, g = lane >> 4;
+  const float sc = 0.125f * 1.44269504088896340736f;
+  const T* kb = xk + (((int64_t)b * n_head + h) * t_len << 6);
+  const T* vb = xv + (((int64_t)b * n_head + h) * t_len << 6);
+  if (VAR) t_len = max(win_len[b], 1);      // a length is at least 1 (the setters refuse 0); with no key at all the merge would divide 0 by 0
+
+  vec8 qf[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qf[ks][e] = (T)0.f;
+    if (c < 8) qf[ks] = *(const vec8*)(q + (int64_t)(b * 8 + c) * d + h * 64 + ks * 32 + g * 8);
+  }
+
+  f32x4 oacc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;
+
+  unsigned char* img = vimg[wave];
+  // V staging: load i of a lane is 16 bytes of row 8i + lane / 8 (a wave-instruction covers 1 KiB contiguous)
+  const int vrow = lane >> 3, vchunk = lane & 7;
+  // transposed reads: lane 4q + p of group g supplies row 16t + 4g + q, columns 16dt + 4p .. + 3
+  const int tr_off = (4 * g + (c >> 2)) * XAC_VROW + (c & 3) * 8;
+
+  const int nblk = (t_len + XAC_KB - 1) / XAC_KB;
+  vec8 kf[2][2], vf[4];
+  auto gload = [&](int blk) {
+    const int key0 = blk * XAC_KB;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      int key = key0 + 16 * t + c;
+      if (key > t_len - 1) key = t_len - 1;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) kf[t][ks] = __builtin_nontemporal_load((const vec8*)(kb + ((int64_t)key << 6) + ks * 32 + g * 8));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int key = key0 + 8 * i + vrow;
+      if (key > t_len - 1) key = t_len - 1;
+      vf[i] = __builtin_nontemporal_load((const vec8*)(vb + ((int64_t)key << 6) + vchunk * 8));
+    }
+  };
+  if (wave < nblk) gload(wave);
+  for (int blk = wave; blk < nblk; blk += 4) {
+    const int key0 = blk * XAC_KB;
+    // the block's V rows into the wave's image (the reads of the block before are complete: in-order LDS), its K into
+    // the products; then the next block's loads fly under this block's arithmetic
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *(vec8*)(img + (8 * i + vrow) * XAC_VROW + vchunk * 16) = vf[i];
+    __builtin_amdgcn_wave_barrier();
+    f32x4 sacc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      sacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) sacc[t] = Ops::mfma16(kf[t][ks], qf[ks], sacc[t]);
+    }
+    if (blk + 4 < nblk) gload(blk + 4);
+    if (key0 + XAC_KB > t_len) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sacc[t][r] = key0 + 16 * t + 4 * g + r < t_len ? sacc[t][r] : -INFINITY;
+    }
+    float bmax = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bmax = fmaxf(bmax, sacc[t][r]);
+    bmax = fmaxf(bmax, __shfl_xor(bmax, 16, 64));
+    bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
+    const float m_new = fmaxf(m_run, bmax);      // raw-score units; finite: key key0 is valid
+    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sc);   // exp2(-inf) = 0 on the first block, where O and l are 0
+    m_run = m_new;
+    l_run *= alpha;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) oacc[dt][r] *= alpha;
+    const float m_sc = m_new * sc;
+    union { vec8 v; unsigned u[4]; } pf;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float p[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        p[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[t][r], sc, -m_sc));    // exp2(-inf) = 0 for masked keys
+        l_run += p[r];
+      }
+      pf.u[2 * t] = pack2<T>(p[0], p[1]);
+      pf.u[2 * t + 1] = pack2<T>(p[2], p[3]);
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      union { vec8 v; s16x4 h4[2]; } vt;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+        vt.h4[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + tr_off + 16 * t * XAC_VROW + dt * 32));
+      oacc[dt] = Ops::mfma16(vt.v, pf.v, oacc[dt]);
+    }
+  }
+  // the query's sum over its 4 lanes (they share m_run), then this wave's state of the 8 real rows
+  l_run += __shfl_xor(l_run, 16, 64);
+  l_run += __shfl_xor(l_run, 32, 64);
+  if (c < 8) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red_o[wave][c][dt * 16 + 4 * g + r] = oacc[dt][r];
+    if (g == 0) { red_m[wave][c] = m_run; red_l[wave][c] = l_run; }
+  }
+  __syncthreads();
+  // thread -> rows tid / 64 and tid / 64 + 4, column tid % 64
+  for (int i = wave; i < 8; i += 4) {
+    const float mn = fmaxf(fmaxf(red_m[0][i], red_m[1][i]), fmaxf(red_m[2][i], red_m[3][i]));
+    float l = 0.f, o = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float a = red_m[w][i] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f((red_m[w][i] - mn) * sc);
+      l += red_l[w][i] * a;
+      o += red_o[w][i][lane] * a;
+    }
+    out[act_tiled_offset(b * 8 + i, h * 64 + lane, d)] = (T)(o / l);
+  }
+}
+
+template <typename T>
+void launch_cross_attn_chunk(const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len, const int32_t* done,
+                             const int32_t* win_len, hipStream_t s) {
+  if (windows < 1 || n_head < 1 || t_len < 1) throw Error(OHW_E_INVALID_ARG, "cross-attention chunk: windows, n_head or t_len below 1");
+  const dim3 grid(n_head, windows);
+  if (win_len)
+    hipLaunchKernelGGL((cross_attn_chunk_kernel<T, true>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len);
+  else
+    hipLaunchKernelGGL((cross_attn_chunk_kernel<T, false>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // logits filter + greedy arg-max on the device: restates oracle ref_process_logits / ref_greedy
 // (whisper.cpp defaults).  One workgroup per window.
 // ------------------------------------------------------------------------------------------------
@@ -1989,7 +2166,7 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SamplerParams p, BeamP
   }
   for (int idx = tid; idx < K * (P + 1); idx += 256) {
     const int j = idx / (P + 1), i = idx - j * (P + 1);
-    bp.kv_slot_next[(int64_t)(w * K + j) * p.n_text_ctx + i] = first ? w : bp.kv_slot[(int64_t)(w * K + s_src[j]) * p.n_text_ctx + i];   // after the prompt pass every position lives in slot w
+    bp.kv_slot_next[(int64_t)(w * K + j) * p.n_text_ctx + i] = first ? w * bp.prefix_stride : bp.kv_slot[(int64_t)(w * K + s_src[j]) * p.n_text_ctx + i];   // after the prompt pass every position lives in slot w
   }
   if (tid < K) {
     const int j = tid, r = w * K + j;
@@ -2004,6 +2181,23 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SamplerParams p, BeamP
     bp.n_past_w[w] = P + 1;
     if (s_done) { bp.win_done[w] = 1; atomicAdd(p.n_done, 1); }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void kv_prefix_move_kernel(T* __restrict__ kv, int64_t plane, int64_t row, int n_ctx, int src, int dst, int n_pos) {
+  // one workgroup per (head, plane): n_pos * 64 contiguous elements, 16 bytes per thread and round
+  const int64_t base = (int64_t)blockIdx.y * plane + ((int64_t)blockIdx.x * n_ctx << 6);
+  const u32x4* from = (const u32x4*)(kv + base + src * row);
+  u32x4* to = (u32x4*)(kv + base + dst * row);
+  for (int i = threadIdx.x; i < n_pos * 8; i += 256) to[i] = from[i];
+}
+template <typename T>
+void launch_kv_prefix_move(void* self_kv, int planes, int max_batch, int n_head, int n_ctx, int src, int dst, int n_pos, hipStream_t s) {
+  if (src < 0 || dst < 0 || src >= max_batch || dst >= max_batch || n_pos < 0 || n_pos > n_ctx) throw Error(OHW_E_INVALID_ARG, "kv_prefix_move: row or position out of range");
+  if (src == dst || n_pos == 0) return;
+  const int64_t row = (int64_t)n_head * n_ctx * 64;
+  hipLaunchKernelGGL((kv_prefix_move_kernel<T>), dim3(n_head, planes), dim3(256), 0, s, (T*)self_kv, row * max_batch, row, n_ctx, src, dst, n_pos);
+  HIP_CHECK(hipGetLastError());
 }
 
 void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_windows, int first, hipStream_t s) {
@@ -2076,7 +2270,9 @@ int launch_prompt_fill(const int32_t* lang, int32_t* step_tok, int batch, int so
   template int launch_dec_gemm<T>(const DecGemmParams&, int, hipStream_t); \
   template void launch_embed<T>(const void*, const float*, const int32_t*, const int32_t*, float*, void*, float*, int, int, int, hipStream_t); \
   template int launch_self_attn<T>(const void*, const void*, const void*, const int32_t*, void*, int, int, int, int, hipStream_t, const int32_t*); \
-  template int launch_cross_attn<T>(const void*, const void*, const void*, void*, int, int, int, int, float*, unsigned*, int, const int32_t*, hipStream_t, int, bool, const int32_t*);
+  template int launch_cross_attn<T>(const void*, const void*, const void*, void*, int, int, int, int, float*, unsigned*, int, const int32_t*, hipStream_t, int, bool, const int32_t*); \
+  template void launch_kv_prefix_move<T>(void*, int, int, int, int, int, int, int, hipStream_t); \
+  template void launch_cross_attn_chunk<T>(const void*, const void*, const void*, void*, int, int, int, const int32_t*, const int32_t*, hipStream_t);
 INST(bf16_t)
 INST(f16_t)
 #undef INST

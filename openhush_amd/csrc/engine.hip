@@ -137,6 +137,15 @@ struct ohw_state {
   std::vector<int8_t> lang_kind;
   std::vector<int32_t> lang_ids;      // explicit id, else LANG_PENDING: what an encode uploads again
   DevBuf lang_tab, lang_prob;         // i32 [max_batch], f32 [max_batch][n_langs]
+  // per-window text context (ohw_state_set_window_prompt).  wp_len: the positions the context of every decode-batch slot occupies
+  // (0, or its tokens + 1 for [prev]); empty: no table.  The table lives on the device, laid out as the prefill feeds it: wp_feed
+  // [chunk][table batch][8] tokens ([eot] in the surplus rows), wp_pos [chunk][max_batch] = 8 * chunk, wp_lens [max_batch]; wp_done
+  // [chunk][max_batch] is the done mask of the prefill under way (it depends on the call's active windows)
+  std::vector<int32_t> wp_len;
+  DevBuf wp_feed, wp_pos, wp_done, wp_lens;
+  int wp_chunks = 0;                 // chunks the buffers hold: ceil(n_text_ctx / 2 / 8)
+  bool prefill_xa = true;            // OHW_PREFILL_XA=0: the prefill's cross-attention through launch_cross_attn's kernels (A/B knob)
+  int64_t tally_xchunk = 0;          // cross_attn_chunk_kernel launches (ohw_dbg_counter "xattn.chunk")
   bool gemm_small = false;  // OHW_GEMM_SMALL=1: short windows take the 64x64-tile encoder GEMM (gemm_small.hip; off until measured)
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -341,6 +350,12 @@ void state_alloc(ohw_state* st) {
   st->lang_tab.alloc((size_t)B * 4, true);
   st->lang_prob.alloc((size_t)B * std::max(1, c->tok.n_langs) * 4, true);
   st->attn_ticket.alloc((size_t)hp.n_text_head * 4, true);
+  st->wp_chunks = (hp.n_text_ctx / 2 + 7) / 8;
+  st->wp_feed.alloc((size_t)st->wp_chunks * B * 8 * 4, true);
+  st->wp_pos.alloc((size_t)st->wp_chunks * B * 4, true);
+  st->wp_done.alloc((size_t)st->wp_chunks * B * 4, true);
+  st->wp_lens.alloc((size_t)B * 4, true);
+  st->prefill_xa = env_int("OHW_PREFILL_XA", 1, 0, 1) != 0;
   (void)hipDeviceGetAttribute(&st->n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
   st->postnorm = env_int("OHW_DEC_POSTNORM", 0, 0, 1) != 0 && dec_ksplit_long() == 1 && dec_ksplit_short() == 1 && dt % 32 == 0;
   st->dx16.alloc(m_tiles * dt * 2, true);
@@ -531,9 +546,11 @@ void run_encode(ohw_state* st, int B, int first, int total) {
 // one decoder pass over M = B * n_new rows; tokens in tok_src (default st->step_tok), positions from st->n_past
 // kv_group > 1 (beam search): B rows are kv_group beams per window - cross K/V is per window, self K/V goes through kv_slot,
 // win_done flags whole windows
+// want_logits = false (the prefill's chunks): the pass ends behind the last layer - only the self K/V it leaves in the cache is wanted
+// chunk_xa (the prefill's chunks, n_new = 8): cross-attention through cross_attn_chunk_kernel under the rule of the rows path
 template <typename T>
 void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = nullptr, int kv_group = 1, const int32_t* kv_slot = nullptr,
-                      const int32_t* win_done = nullptr) {
+                      const int32_t* win_done = nullptr, bool want_logits = true, bool chunk_xa = false) {
   const ohw_ctx* c = st->ctx;
   const ohw_hparams& hp = c->hp;
   hipStream_t s = st->stream;
@@ -650,7 +667,8 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     {
       // algorithmic bytes: K and V of every (query row, head); the prompt pass streams them once per (window, head)
       // for all its rows (cross_attn_rows_kernel: same condition as launch_cross_attn)
-      const bool rows_path = n_new >= 2 && n_new <= 4 && ((int64_t)B * H >= 256 || st->batch_invariant || var);
+      const bool chunk_path = chunk_xa && st->prefill_xa && n_new == 8 && kv_group == 1 && ((int64_t)B * H >= 256 || st->batch_invariant || var);
+      const bool rows_path = chunk_path || (n_new >= 2 && n_new <= 4 && ((int64_t)B * H >= 256 || st->batch_invariant || var));
       // (window, head) streams x keys: under per-window contexts the sum of the windows' own lengths
       double xa_keys = (double)(kv_group > 1 ? B / kv_group : rows_path ? B : M) * Tn;
       if (var) {
@@ -659,18 +677,64 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
         for (int w = 0; w < Wn; ++w) xa_keys += (double)st->enc_win[(size_t)w] * (kv_group > 1 || rows_path ? 1 : n_new);
       }
       ProfScope psx(st, OHW_PROF_DEC_XATTN, 2.0 * 2.0 * xa_keys * H * 64.0);
-      ++st->tally_xattn[launch_cross_attn<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab,
-                                             st->da.p, M, n_new, H, Tn, st->xa_part.as<float>(), st->xa_ticket.as<unsigned>(), st->xa_rows,
-                                             kv_group > 1 ? win_done : (st->skip_done ? st->done.as<int32_t>() : nullptr), s, kv_group, st->batch_invariant,
-                                             var ? st->wc_dec.as<int32_t>() : nullptr)];
+      if (chunk_path) {
+        launch_cross_attn_chunk<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab, st->da.p, B, H, Tn,
+                                   st->skip_done ? st->done.as<int32_t>() : nullptr, var ? st->wc_dec.as<int32_t>() : nullptr, s);
+        ++st->tally_xchunk;
+      } else {
+        ++st->tally_xattn[launch_cross_attn<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab,
+                                               st->da.p, M, n_new, H, Tn, st->xa_part.as<float>(), st->xa_ticket.as<unsigned>(), st->xa_rows,
+                                               kv_group > 1 ? win_done : (st->skip_done ? st->done.as<int32_t>() : nullptr), s, kv_group, st->batch_invariant,
+                                               var ? st->wc_dec.as<int32_t>() : nullptr)];
+      }
     }
     gemm(DT_XO, st->da.p, nullptr, w.wxo, w.bxo, st->dx.p, d, d, DEPI_BIAS_RESID, d);
     gemm(DT_FC1, st->dx.p, &w.ln2, w.w1, w.b1, st->df.p, 4 * d, d, DEPI_BIAS_GELU_T, 4 * d, &w.s1);
     gemm(DT_FC2, st->df.p, nullptr, w.w2, w.b2, st->dx.p, d, 4 * d, DEPI_BIAS_RESID, d);
   }
+  if (!want_logits) return;
   launch_layernorm<T>(st->dx.as<float>(), c->dec_ln.g.as<float>(), c->dec_ln.b.as<float>(), st->dy.p, M, d, s, true);
   DevBuf none;
   gemm(DT_LOGITS, st->dy.p, nullptr, c->emb, none, st->logits.p, hp.n_vocab, d, DEPI_LOGITS, st->logits_ld);
+}
+
+// the text context of the table (ohw_state_set_window_prompt) through the decoder in chunks of 8 positions: chunk j feeds positions
+// 8j .. 8j + 7 of every window at n_past = 8j ([eot] where a window's context has ended: those rows write cache positions at or
+// past the window's length, which the decode overwrites one by one before a query reads them), and names the windows it has
+// nothing for - 8j >= len[b], or not active - in the done mask, so their cross K/V is not streamed.  No logits.  Leaves every
+// layer's self K/V of positions 0 .. len[b] - 1 in cache row b; st->n_past and st->done are the caller's to set afterwards.
+void run_prefill(ohw_state* st, int batch, const int32_t* active, const std::string& what) {
+  if (st->wp_len.empty()) return;
+  if ((int)st->wp_len.size() != batch)
+    throw Error(OHW_E_INVALID_ARG, what + ": ohw_state_set_window_prompt named " + std::to_string(st->wp_len.size()) + " windows, the decode batch has " +
+                                       std::to_string(batch));
+  int max_len = 0;
+  for (int b = 0; b < batch; ++b)
+    if (!active || active[b]) max_len = std::max(max_len, st->wp_len[(size_t)b]);
+  const int nc = (max_len + 7) / 8;
+  if (nc == 0) return;
+  const size_t MB = (size_t)st->max_batch;
+  hipStream_t s = st->stream;
+  std::vector<int32_t> done((size_t)nc * MB, 1);
+  for (int j = 0; j < nc; ++j)
+    for (int b = 0; b < batch; ++b) done[(size_t)j * MB + b] = ((active && !active[b]) || 8 * j >= st->wp_len[(size_t)b]) ? 1 : 0;
+  HIP_CHECK(hipMemcpyAsync(st->wp_done.p, done.data(), done.size() * 4, hipMemcpyHostToDevice, s));
+  struct SkipDone { bool& f; bool keep; explicit SkipDone(bool& r) : f(r), keep(r) { f = true; } ~SkipDone() { f = keep; } } skip_done(st->skip_done);
+  Dispatch::run(st->ctx->dtype, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    for (int j = 0; j < nc; ++j) {
+      HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_pos.as<int32_t>() + (size_t)j * MB, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->done.p, st->wp_done.as<int32_t>() + (size_t)j * MB, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
+      run_decoder_step<T>(st, batch, 8, st->wp_feed.as<int32_t>() + (size_t)j * batch * 8, 1, nullptr, nullptr, false, true);
+    }
+  });
+  HIP_CHECK(hipStreamSynchronize(s));     // `done` is a stack-lifetime source
+}
+// the largest context of the table (0: none set)
+int window_prompt_max(const ohw_state* st) {
+  int m = 0;
+  for (int32_t n : st->wp_len) m = std::max(m, (int)n);
+  return m;
 }
 
 // after a stream synchronisation: did a workgroup of a persistent decoder step give up waiting (decode_persist.hip)?  Loud.
@@ -1141,16 +1205,20 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
     ohw_sample_params psp = *sp;
     if (lang_tab) psp.lang_id = 0;
     const int n_prompt = build_prompt(c, &psp, prompt);
+    // under a text-context table (ohw_state_set_window_prompt) window b starts at position wp_len[b]: the prefill puts the context there
+    const bool wp = !st->wp_len.empty();
     const int n_max_raw = sp->force_len > 0 ? sp->force_len : sp->n_max;
-    int n_max = std::min(std::min(n_max_raw, st->max_tokens), c->hp.n_text_ctx - n_prompt);
+    int n_max = std::min(std::min(n_max_raw, st->max_tokens), c->hp.n_text_ctx - n_prompt - window_prompt_max(st));
     if (tp) n_max = std::min(n_max, max_tokens);          // a row consumes at most max_tokens draws
     if (n_max < 1) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": n_max < 1");
     std::vector<int32_t> ptoks((size_t)batch * n_prompt);
     for (int b = 0; b < batch; ++b) std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
     if (!tp) HIP_CHECK(hipEventRecord(st->ev[4], s));
+    run_prefill(st, batch, tp ? tp->active : nullptr, what);
     if (lang_tab) fill_prompt_rows(st, &psp, batch, n_prompt);
     else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)batch * 4, s));
+    if (wp) HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_lens.p, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
+    else HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)batch * 4, s));
     HIP_CHECK(hipMemsetAsync(st->n_cur.p, 0, (size_t)batch * 4, s));
     // a temperature pass: windows with active[b] == 0 start finished (cross-attention and the sampler skip them)
     std::vector<int32_t> done0;
@@ -1182,6 +1250,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
       using T = std::remove_pointer_t<decltype(tag)>;
       run_decoder_step<T>(st, batch, n_prompt);
       std::vector<int32_t> np((size_t)batch, n_prompt);
+      for (int b = 0; wp && b < batch; ++b) np[(size_t)b] += st->wp_len[(size_t)b];
       HIP_CHECK(hipMemcpyAsync(st->n_past.p, np.data(), np.size() * 4, hipMemcpyHostToDevice, s));
       HIP_CHECK(hipStreamSynchronize(s));  // np (and a temperature pass's done0, n_done0, T, draws) are stack-lifetime sources
       ++steps;
@@ -1340,14 +1409,20 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
     ohw_sample_params psp = *sp;
     if (lang_tab) psp.lang_id = 0;
     const int n_prompt = build_prompt(c, &psp, prompt);
-    const int n_max = std::min(std::min(sp->n_max, MT), C - n_prompt);
+    // under a text-context table window w's prompt starts at position wp_len[w]; the context's K/V lives in slot w like the prompt's
+    const bool wp = !st->wp_len.empty();
+    const int n_max = std::min(std::min(sp->n_max, MT), C - n_prompt - window_prompt_max(st));
     if (n_max < 1) throw Error(OHW_E_INVALID_ARG, "beam search: n_max < 1");
     std::vector<int32_t> ptoks((size_t)W * n_prompt), np0((size_t)W, n_prompt - 1);
+    if (wp && (int)st->wp_len.size() == W)
+      for (int w = 0; w < W; ++w) np0[(size_t)w] += st->wp_len[(size_t)w];
     for (int w = 0; w < W; ++w) std::memcpy(&ptoks[(size_t)w * n_prompt], prompt, (size_t)n_prompt * 4);
     HIP_CHECK(hipEventRecord(st->ev[4], s));
+    run_prefill(st, W, nullptr, "beam search");
     if (lang_tab) fill_prompt_rows(st, &psp, W, n_prompt);
     else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)MB * 4, s));
+    if (wp) HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_lens.p, (size_t)W * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
     for (DevBuf* b : {&st->bm_sum, &st->bm_ncur, &st->bm_done, &st->bm_fin_cnt, &st->bm_fin_len}) HIP_CHECK(hipMemsetAsync(b->p, 0, (size_t)MB * 4, s));
     HIP_CHECK(hipMemcpyAsync(st->bm_npast.p, np0.data(), np0.size() * 4, hipMemcpyHostToDevice, s));
@@ -1360,7 +1435,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
       std::memcpy(p, &base, sizeof base);
       p->tokens = tokbuf[q];
       *bp = BeamParams{};
-      bp->K = K; bp->cand_lp = st->bm_cand_lp.as<float>(); bp->cand_tok = st->bm_cand_tok.as<int32_t>(); bp->beam_sum = st->bm_sum.as<float>();
+      bp->K = K; bp->prefix_stride = (wp && W > 1) ? K : 1; bp->cand_lp = st->bm_cand_lp.as<float>(); bp->cand_tok = st->bm_cand_tok.as<int32_t>(); bp->beam_sum = st->bm_sum.as<float>();
       bp->kv_slot = st->bm_slot[q].as<int32_t>(); bp->kv_slot_next = st->bm_slot[q ^ 1].as<int32_t>(); bp->tokens_next = tokbuf[q ^ 1];
       bp->n_cur = st->bm_ncur.as<int32_t>(); bp->n_past_w = st->bm_npast.as<int32_t>(); bp->win_done = st->bm_done.as<int32_t>();
       bp->fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp->fin_tok = st->bm_fin_tok.as<int32_t>(); bp->fin_len = st->bm_fin_len.as<int32_t>();
@@ -1371,6 +1446,12 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
     Dispatch::run(c->dtype, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
       run_decoder_step<T>(st, W, n_prompt);                       // the prompt once per window; its K/V stays in cache rows 0 .. W-1
+      // under a context table the windows' pasts differ in length, and cache row w (1 <= w < W) is also the own row of beam w % K of
+      // window w / K, which writes from ITS past's end upward - into window w's context where that is longer.  So window w's past
+      // moves to row w * K, which only w's beams write.  From the last window down: row w * K < W is a later window's source
+      if (wp && W > 1)
+        for (int w = W - 1; w >= 1; --w)
+          launch_kv_prefix_move<T>(st->self_kv.p, 2 * c->hp.n_text_layer, st->max_batch, c->hp.n_text_head, C, w, w * K, np0[(size_t)w] + 1, s);
       HIP_CHECK(hipStreamSynchronize(s));                         // ptoks / np0 are stack-lifetime sources
       ++steps;
       SamplerParams p0; BeamParams b0;
@@ -1515,6 +1596,7 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "step_captures") return st->step_captures;
   if (n == "step_graphs") return (int)st->step_graphs.size();
   if (n == "persist_launches") return st->persist_launches;
+  if (n == "xattn.chunk") return (int)std::min<int64_t>(st->tally_xchunk, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
   auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
   for (int g = 0; g < DT_GEMMS; ++g)
@@ -1601,6 +1683,64 @@ int ohw_state_set_window_lang(ohw_state* st, const int32_t* lang_ids, int batch)
     st->lang_ids.assign(lang_ids, lang_ids + batch);
     st->lang_kind.resize((size_t)batch);
     for (int b = 0; b < batch; ++b) st->lang_kind[(size_t)b] = lang_ids[b] == OHW_LANG_DETECT ? ohw_state::LANG_WAITING : ohw_state::LANG_EXPLICIT;
+  });
+}
+
+int ohw_state_set_window_prompt(ohw_state* st, const int32_t* tokens, int stride, const int32_t* n_tokens, int batch) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    if (!tokens || batch == 0) { st->wp_len.clear(); return; }
+    const ohw_ctx* c = st->ctx;
+    const int C = c->hp.n_text_ctx, cap = C / 2 - 1;
+    if (!n_tokens) throw Error(OHW_E_INVALID_ARG, "window_prompt: n_tokens is null");
+    if (batch < 0 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "window_prompt: batch exceeds the state's max_batch");
+    if (cap < 1 || st->wp_chunks * 8 > C) throw Error(OHW_E_INVALID_ARG, "window_prompt: the model's text context is too short for a prompt");
+    for (int b = 0; b < batch; ++b) {
+      if (n_tokens[b] < 0 || n_tokens[b] > cap)
+        throw Error(OHW_E_INVALID_ARG, "window_prompt: window " + std::to_string(b) + " has " + std::to_string(n_tokens[b]) + " context tokens (0.." +
+                                           std::to_string(cap) + " = n_text_ctx / 2 - 1)");
+      if (n_tokens[b] > stride) throw Error(OHW_E_INVALID_ARG, "window_prompt: window " + std::to_string(b) + " has more tokens than the stride");
+      for (int i = 0; i < n_tokens[b]; ++i) {
+        const int32_t t = tokens[(size_t)b * stride + i];
+        if (t < 0 || t >= c->hp.n_vocab)
+          throw Error(OHW_E_INVALID_ARG, "window_prompt: window " + std::to_string(b) + ", token " + std::to_string(i) + " = " + std::to_string(t) +
+                                             " is outside 0.." + std::to_string(c->hp.n_vocab - 1));
+      }
+    }
+    const size_t NC = (size_t)st->wp_chunks, MB = (size_t)st->max_batch;
+    std::vector<int32_t> feed(NC * batch * 8, c->tok.eot), pos(NC * MB), lens(MB, 0);
+    for (int b = 0; b < batch; ++b) {
+      const int n = n_tokens[b];
+      lens[(size_t)b] = n > 0 ? n + 1 : 0;
+      for (int p = 0; p < lens[(size_t)b]; ++p)
+        feed[((size_t)(p / 8) * batch + b) * 8 + p % 8] = p == 0 ? c->tok.prev : tokens[(size_t)b * stride + p - 1];
+    }
+    for (size_t j = 0; j < NC; ++j)
+      for (size_t b = 0; b < MB; ++b) pos[j * MB + b] = (int32_t)(8 * j);
+    HIP_CHECK(hipSetDevice(c->device));
+    // in stream order behind the kernels that still read the previous table; the sources are vectors of this call, so wait
+    HIP_CHECK(hipMemcpyAsync(st->wp_feed.p, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, st->stream));
+    HIP_CHECK(hipMemcpyAsync(st->wp_pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st->stream));
+    HIP_CHECK(hipMemcpyAsync(st->wp_lens.p, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, st->stream));
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    st->wp_len.assign(lens.begin(), lens.begin() + batch);
+  });
+}
+
+int ohw_state_window_prompt_len(const ohw_state* st, int window) {
+  if (!st || window < 0 || window >= st->max_batch) return OHW_E_INVALID_ARG;
+  return window < (int)st->wp_len.size() ? st->wp_len[(size_t)window] : 0;
+}
+
+int ohw_state_prefill(ohw_state* st, int batch, const int32_t* active) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    if (st->wp_len.empty()) return;
+    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "prefill: batch must equal the batch of the last ohw_encode");
+    check_decode_ctx(st, "prefill");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    run_prefill(st, batch, active, "prefill");
+    persist_check(st);
   });
 }
 
@@ -1837,7 +1977,7 @@ int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_
     fill_sampler(st, sp, R, &p);
     p.tokens = tokbuf[q];
     BeamParams bp{};
-    bp.K = K; bp.cand_lp = st->bm_cand_lp.as<float>(); bp.cand_tok = st->bm_cand_tok.as<int32_t>(); bp.beam_sum = st->bm_sum.as<float>();
+    bp.K = K; bp.prefix_stride = 1; bp.cand_lp = st->bm_cand_lp.as<float>(); bp.cand_tok = st->bm_cand_tok.as<int32_t>(); bp.beam_sum = st->bm_sum.as<float>();
     bp.kv_slot = st->bm_slot[q].as<int32_t>(); bp.kv_slot_next = st->bm_slot[q ^ 1].as<int32_t>(); bp.tokens_next = tokbuf[q ^ 1];
     bp.n_cur = st->bm_ncur.as<int32_t>(); bp.n_past_w = st->bm_npast.as<int32_t>(); bp.win_done = st->bm_done.as<int32_t>();
     bp.fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp.fin_tok = st->bm_fin_tok.as<int32_t>(); bp.fin_len = st->bm_fin_len.as<int32_t>();
@@ -2382,6 +2522,27 @@ int ohw_dbg_cross_attn(int dtype, const void* q, const void* xk, const void* xv,
     });
     HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     if (variant_out) *variant_out = variant;
+  });
+}
+
+int ohw_dbg_cross_attn_chunk(int dtype, const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
+                             const int32_t* win_len_host, const int32_t* done_host, void* stream) {
+  return guard([&] {
+    dbg_check_dtype(dtype, "dbg_cross_attn_chunk");
+    if (!q || !xk || !xv || !out || windows < 1 || n_head < 1 || t_len < 1)
+      throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn_chunk: null buffer, or windows, n_head or t_len below 1");
+    for (int w = 0; win_len_host && w < windows; ++w)
+      if (win_len_host[w] < 1 || win_len_host[w] > t_len)
+        throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn_chunk: win_len[" + std::to_string(w) + "] = " + std::to_string(win_len_host[w]) + " is outside 1 .. t_len = " + std::to_string(t_len));
+    DevBuf done, len;
+    if (done_host) dbg_upload(done, done_host, (size_t)windows);
+    if (win_len_host) dbg_upload(len, win_len_host, (size_t)windows);
+    Dispatch::run(dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      launch_cross_attn_chunk<TT>(q, xk, xv, out, windows, n_head, t_len, done_host ? done.as<int32_t>() : nullptr,
+                                  win_len_host ? len.as<int32_t>() : nullptr, (hipStream_t)stream);
+    });
+    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   });
 }
 

@@ -268,8 +268,22 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       sc.trace.insert(sc.trace.end(), t.begin(), t.end());
     };
 
+    // the initial prompt (ohw_engine_set_initial_prompt) as the context of every window of the batch; with none set and none
+    // ever set, nothing is called.  The ladder clears the table before its first pass with T >= 0.5 (whisper.cpp's rule, as
+    // recalled), so every batch sets it again here
+    auto apply_prompt = [&](ohw_state* st, int B) {
+      if (e->prompt.empty()) {
+        if (e->prompt_used) check(ohw_state_set_window_prompt(st, nullptr, 0, nullptr, 0));
+        return;
+      }
+      const int np = (int)e->prompt.size();
+      std::vector<int32_t> tab((size_t)B * np), cnt((size_t)B, np);
+      for (int b = 0; b < B; ++b) std::memcpy(&tab[(size_t)b * np], e->prompt.data(), (size_t)np * 4);
+      check(ohw_state_set_window_prompt(st, tab.data(), np, cnt.data(), B));
+    };
     // T = 0: the device-resident greedy loop for B windows; then whisper.cpp's bookkeeping per window
     auto greedy_t0 = [&](Scratch& sc, ohw_state* st, int B, const int* seek, const int* seek_end, int64_t w0) {
+      apply_prompt(st, B);
       std::vector<int32_t>&toks = sc.toks, &ntok = sc.ntok, &eot = sc.eot;
       std::vector<float>&lps = sc.lps, &nsp = sc.nsp;
       std::vector<WindowRun>& runs = sc.runs;
@@ -330,6 +344,8 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         const float T = temps[ti];
         const bool is_last = ti + 1 == temps.size();
         std::vector<WindowRun> pass((size_t)B);
+        // passes with T < 0.5 decode behind the context; from the first pass with T >= 0.5 on the table is gone
+        if (T >= 0.5f && !e->prompt.empty()) check(ohw_state_set_window_prompt(st, nullptr, 0, nullptr, 0));
         if (e->fallback_device) {
           device_pass(sc, st, B, seek, seek_end, active, T, rngs, pass);
         } else {
@@ -338,6 +354,12 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
           for (int b = 0; b < B; ++b) {
             std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
             if (!batch_lang.empty() && V >= 51865) ptoks[(size_t)b * n_prompt + 1] = tk.sot + 1 + batch_lang[(size_t)b];   // the table's ids, read back once per batch
+          }
+          // under a context table: the prefill for the pending windows, then the prompt at the context's length
+          check(ohw_state_prefill(st, B, active.data()));
+          for (int b = 0; b < B; ++b) {
+            past[(size_t)b] = std::max(0, ohw_state_window_prompt_len(st, b));
+            npast[(size_t)b] += past[(size_t)b];
           }
           check(ohw_decode_active(st, ptoks.data(), n_prompt, past.data(), B, active.data(), logits.data()));
           for (int i = 0; i < n_max; ++i) {
@@ -1400,6 +1422,28 @@ int ohw_engine_set_audio_ctx(ohw_engine* e, int n) {
   if (!e || n < -1 || n > e->ctx->hp.n_audio_ctx) return OHW_E_INVALID_ARG;
   e->audio_ctx = n == e->ctx->hp.n_audio_ctx ? 0 : n;
   return OHW_OK;
+}
+
+int ohw_engine_set_initial_prompt_tokens(ohw_engine* e, const int32_t* tokens, int n) {
+  return guard([&] {
+    if (!e || n < 0 || (n > 0 && !tokens)) throw Error(OHW_E_INVALID_ARG, "initial_prompt: bad argument");
+    for (int i = 0; i < n; ++i)
+      if (tokens[i] < 0 || tokens[i] >= e->ctx->hp.n_vocab)
+        throw Error(OHW_E_INVALID_ARG, "initial_prompt: token " + std::to_string(i) + " = " + std::to_string(tokens[i]) + " is outside the vocabulary");
+    std::vector<int32_t> kept((size_t)std::max(n, 1));
+    const int k = n > 0 ? ohw_prompt_clip_host(tokens, n, e->ctx->hp.n_text_ctx, kept.data()) : 0;
+    if (k < 0) throw Error(OHW_E_INVALID_ARG, "initial_prompt: " + g_last_error);
+    e->prompt.assign(kept.begin(), kept.begin() + k);
+    if (k > 0) e->prompt_used = true;
+  });
+}
+int ohw_engine_set_initial_prompt(ohw_engine* e, const char* text) {
+  if (!e) return OHW_E_INVALID_ARG;
+  if (!text || !*text) return ohw_engine_set_initial_prompt_tokens(e, nullptr, 0);
+  std::vector<int32_t> toks(std::strlen(text) + 1);       // at most one token per byte
+  const int n = ohw_tokenize(e->ctx, text, toks.data(), (int)toks.size());
+  if (n < 0) return n;
+  return ohw_engine_set_initial_prompt_tokens(e, toks.data(), n);
 }
 
 int ohw_engine_set_packed_encoder(ohw_engine* e, int on) {

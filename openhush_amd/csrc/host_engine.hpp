@@ -15,6 +15,10 @@ struct ohw_engine {
   int window_mode = OHW_WINDOW_FIXED;
   int audio_ctx = 0;                     // ohw_engine_set_audio_ctx: 0 off (full context), n > 0 fixed, -1 auto
   bool packed_encoder = false;           // ohw_engine_set_packed_encoder: every state of the engine, those made later too
+  // ohw_engine_set_initial_prompt: context tokens (clipped to the last n_text_ctx / 2 - 1) in front of every window of every
+  // schedule; empty: none.  prompt_used: a prompt has been set at some time, so states may still hold a table to clear
+  std::vector<int32_t> prompt;
+  bool prompt_used = false;
   int force_len = 0;                     // measurement knob (ohw_engine_set_force_len): every window decodes exactly this many tokens
   std::vector<int32_t> last_tokens;
   std::string last_text;

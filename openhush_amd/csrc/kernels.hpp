@@ -133,6 +133,10 @@ template <typename T> int launch_cross_attn(const void* q, const void* xk, const
                                              bool batch_invariant = false /* pick the variant from n_new alone, never from M */,
                                              const int32_t* win_len = nullptr /* device [windows] or null: window w streams its first
                                                 win_len[w] keys of a slab whose stride stays t_len; implies batch_invariant's variant choice */);
+// the 8 query rows per window of one prefill chunk (ohw_state_prefill): q T [windows * 8][d], row b * 8 + i; one workgroup per
+// (head, window) streams K/V once for the 8 rows, both products on the MFMA units (cross_attn_chunk_kernel).  done / win_len as above
+template <typename T> void launch_cross_attn_chunk(const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
+                                                   const int32_t* done, const int32_t* win_len, hipStream_t s);
 
 // ---- the 32 decoder layers of a single-token step in ONE persistent launch, at most 16 rows (decode_persist.hip) ----------
 struct PersistLayer {
@@ -186,6 +190,8 @@ struct SamplerParams {
 // beam search state of a batch of windows (decode.hip): beam j of window w is decoder row w * K + j
 struct BeamParams {
   int32_t K;              // beam size, 2..5
+  int32_t prefix_stride;  // first step: the shared past of window w (prompt pass, context) lives in cache row w * prefix_stride:
+                          //   1, or K under a context table (ohw_beam_search moves it there: launch_kv_prefix_move)
   float* cand_lp;         // [rows][K + 1] log-probabilities of every row's best next tokens
   int32_t* cand_tok;      // [rows][K + 1]
   float* beam_sum;        // [rows] cumulative log-probability
@@ -205,6 +211,10 @@ struct BeamParams {
 constexpr int BEAM_SPLIT = 8;         // workgroups per logits row
 constexpr int BEAM_PART_WORDS = 32;   // max, sum, timestamp sum, best text logit, then (K + 1) text and (K + 1) timestamp candidates (value, index)
 void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_windows, int first, hipStream_t s);
+// self K/V cache T [planes][max_batch][n_head][n_ctx][64] (planes = 2 * layers): positions 0 .. n_pos - 1 of cache row src are
+// copied to row dst in every plane and head.  Beam search under a context table: window w's shared past goes from row w to row
+// w * K, a row only w's own beams write - row w is also the own row of a beam of window w / K, which would write into a longer context
+template <typename T> void launch_kv_prefix_move(void* self_kv, int planes, int max_batch, int n_head, int n_ctx, int src, int dst, int n_pos, hipStream_t s);
 constexpr int SAMPLER_SPLIT = 8;
 constexpr int SAMPLER_PART_WORDS = 12;
 void launch_sampler(const SamplerParams& p, hipStream_t s);

@@ -311,6 +311,14 @@ int ohw_pool_set_audio_ctx(ohw_pool* p, int n) {
   }
   return OHW_OK;
 }
+int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_initial_prompt(e, text);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
 int ohw_pool_set_packed_encoder(ohw_pool* p, int on) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {

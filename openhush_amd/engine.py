@@ -194,6 +194,9 @@ EXPORTS = [
     "ohw_engine_batch_times", "ohw_word_starts_host", "ohw_segments_host",
     "ohw_pool_set_word_timestamps", "ohw_pool_last_token_times", "ohw_pool_last_words", "ohw_pool_last_segments",
     "ohw_dbg_beam_step",
+    "ohw_dbg_cross_attn_chunk",
+    "ohw_state_set_window_prompt", "ohw_state_window_prompt_len", "ohw_state_prefill", "ohw_tokenize_host", "ohw_tokenize", "ohw_prompt_clip_host",
+    "ohw_engine_set_initial_prompt", "ohw_engine_set_initial_prompt_tokens", "ohw_pool_set_initial_prompt",
 ]
 
 
@@ -412,6 +415,16 @@ def lib():
         L.ohw_dbg_attention_var.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, vp]
         L.ohw_dbg_cross_attn.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, vp, vp, C.c_int,
                                          C.POINTER(C.c_int), vp]
+        L.ohw_dbg_cross_attn_chunk.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, vp]
+        L.ohw_state_set_window_prompt.argtypes = [vp, ip, C.c_int, ip, C.c_int]
+        L.ohw_state_window_prompt_len.argtypes = [vp, C.c_int]
+        L.ohw_state_prefill.argtypes = [vp, C.c_int, ip]
+        L.ohw_tokenize_host.argtypes = [C.c_char_p, ip, C.c_int, C.c_char_p, ip, C.c_int]
+        L.ohw_tokenize.argtypes = [vp, C.c_char_p, ip, C.c_int]
+        L.ohw_prompt_clip_host.argtypes = [ip, C.c_int, C.c_int, ip]
+        L.ohw_engine_set_initial_prompt.argtypes = [vp, C.c_char_p]
+        L.ohw_engine_set_initial_prompt_tokens.argtypes = [vp, ip, C.c_int]
+        L.ohw_pool_set_initial_prompt.argtypes = [vp, C.c_char_p]
         L.ohw_dbg_self_attn.argtypes = [C.c_int, vp, vp, vp, ip, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int), vp]
         L.ohw_state_set_audio_ctx.argtypes = [vp, C.c_int]
         L.ohw_state_audio_ctx.argtypes = [vp]
@@ -468,6 +481,36 @@ def lib():
 
 
 OHW_LANG_DETECT = -1
+
+
+def _text_bytes(text) -> bytes:
+    b = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    if b"\0" in b:
+        raise ValueError("text to tokenize must not contain a NUL byte")
+    return b
+
+
+def tokenize_host(vocab: Sequence[bytes], text, cap: Optional[int] = None) -> List[int]:
+    """ohw_tokenize_host: `text` (str or bytes) in ids of `vocab` (entry i has id i).  cap: the output buffer's size (default: one
+    token per byte always fits); a text with more tokens than cap raises"""
+    b = _text_bytes(text)
+    lens = np.asarray([len(v) for v in vocab] or [0], dtype=np.int32)
+    cap = max(len(b), 1) if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), dtype=np.int32)
+    n = lib().ohw_tokenize_host(b"".join(vocab), _ip(lens), len(vocab), b, _ip(out), cap)
+    if n < 0:
+        _raise(n)
+    return [int(t) for t in out[:n]]
+
+
+def prompt_clip(tokens: Sequence[int], n_text_ctx: int) -> List[int]:
+    """ohw_prompt_clip_host: the last n_text_ctx / 2 - 1 tokens of a prompt"""
+    a = np.ascontiguousarray(list(tokens) or [0], dtype=np.int32)
+    out = np.zeros(a.size, dtype=np.int32)
+    n = lib().ohw_prompt_clip_host(_ip(a), len(tokens), int(n_text_ctx), _ip(out))
+    if n < 0:
+        _raise(n)
+    return [int(t) for t in out[:n]]
 
 
 def lang_pick_host(row: np.ndarray, tok: "SpecialTokens"):
@@ -722,6 +765,15 @@ class Context:
         s = C.c_char_p()
         n = lib().ohw_token_text(self.h, i, C.byref(s))
         return s.value[:n] if n else b""
+
+    def tokenize(self, text) -> List[int]:
+        """ohw_tokenize: `text` (str or bytes) in the model's text tokens"""
+        b = _text_bytes(text)
+        out = np.zeros(max(len(b), 1), dtype=np.int32)
+        n = lib().ohw_tokenize(self.h, b, _ip(out), int(out.size))
+        if n < 0:
+            _raise(n)
+        return [int(t) for t in out[:n]]
 
     def sample_greedy_host(self, p: SampleParams, logits: np.ndarray, cur: List[int]) -> Tuple[int, float]:
         lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
@@ -988,6 +1040,31 @@ class State:
         a = np.ascontiguousarray(lang_ids, dtype=np.int32)
         _check(lib().ohw_state_set_window_lang(self.h, _ip(a), int(a.size)))
 
+    def set_window_prompt(self, contexts: Optional[Sequence[Sequence[int]]]):
+        """ohw_state_set_window_prompt: the context tokens (text so far) of every decode-batch slot, an empty list for a slot
+        without context; None clears the table"""
+        if contexts is None:
+            _check(lib().ohw_state_set_window_prompt(self.h, C.cast(None, C.POINTER(C.c_int32)), 0, C.cast(None, C.POINTER(C.c_int32)), 0))
+            return
+        n = np.asarray([len(t) for t in contexts], dtype=np.int32)
+        stride = max(1, int(n.max()) if n.size else 1)
+        tok = np.zeros((max(1, len(contexts)), stride), dtype=np.int32)
+        for b, t in enumerate(contexts):
+            tok[b, :len(t)] = np.asarray(t, dtype=np.int32)
+        _check(lib().ohw_state_set_window_prompt(self.h, _ip(tok), stride, _ip(n), len(contexts)))
+
+    def window_prompt_len(self, b: int) -> int:
+        """ohw_state_window_prompt_len: the positions slot b's context occupies (0, or its tokens + 1)"""
+        n = lib().ohw_state_window_prompt_len(self.h, int(b))
+        if n < 0:
+            raise WhisperError(n, "window_prompt_len: window index out of range")
+        return int(n)
+
+    def prefill(self, batch: int, active: Optional[Sequence[int]] = None):
+        """ohw_state_prefill: the table's contexts through the decoder; afterwards decode window b from n_past = window_prompt_len(b)"""
+        a = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        _check(lib().ohw_state_prefill(self.h, int(batch), None if a is None else _ip(a)))
+
     def detect_window_lang(self, batch: int):
         """ohw_state_detect_window_lang: resolve the table's pending entries for the windows of the last encode, on the device"""
         _check(lib().ohw_state_detect_window_lang(self.h, int(batch)))
@@ -1039,6 +1116,16 @@ class State:
         probs = np.zeros((B, self.ctx.tok.n_langs), dtype=np.float32)
         _check(lib().ohw_dbg_lang_pick(self.h, _fp(lg), B, _ip(ids), _fp(probs)))
         return ids, probs
+
+    @staticmethod
+    def dbg_cross_attn_chunk(dtype: int, q_ptr: int, xk_ptr: int, xv_ptr: int, out_ptr: int, windows: int, n_head: int, t_len: int,
+                             win_len: Optional[Sequence[int]] = None, done: Optional[Sequence[int]] = None, stream: Optional[int] = None):
+        """ohw_dbg_cross_attn_chunk: the prefill's cross-attention kernel on device buffers of the caller (8 query rows per window;
+        out in activation-tile order, pre-filled by the caller: the rows of a done window keep what they held)"""
+        wl = None if win_len is None else np.ascontiguousarray(win_len, dtype=np.int32)
+        dn = None if done is None else np.ascontiguousarray(done, dtype=np.int32)
+        _check(lib().ohw_dbg_cross_attn_chunk(int(dtype), q_ptr, xk_ptr, xv_ptr, out_ptr, int(windows), int(n_head), int(t_len),
+                                              None if wl is None else _ip(wl), None if dn is None else _ip(dn), stream))
 
     def poison(self, what: str):
         """ohw_dbg_poison (tests): fill the encoder's "qkv" or "att" buffer with NaN"""
@@ -1670,6 +1757,15 @@ class WhisperEngine:
         """OHW_SCHEDULE_SEQUENTIAL / _PIPELINE / _LANES (default) for audio longer than max_batch windows"""
         _check(lib().ohw_engine_set_schedule(self.h, schedule, lanes, merge))
 
+    def set_initial_prompt(self, prompt):
+        """ohw_engine_set_initial_prompt / _tokens: text (str or bytes) or a list of token ids every window of every schedule is
+        decoded behind (clipped to the last n_text_ctx / 2 - 1 tokens); "", None or [] clears it"""
+        if prompt is None or isinstance(prompt, (str, bytes)):
+            _check(lib().ohw_engine_set_initial_prompt(self.h, _text_bytes(prompt or "")))
+        else:
+            a = np.ascontiguousarray(list(prompt) or [0], dtype=np.int32)
+            _check(lib().ohw_engine_set_initial_prompt_tokens(self.h, _ip(a), len(prompt)))
+
     def set_audio_ctx(self, n):
         """ohw_engine_set_audio_ctx: 0 (default, off), a fixed context n, or "auto" (audio_ctx_for(len) for a recording of at most
         one window, full context beyond); a fixed context that does not cover a window's audio fails the transcribe"""
@@ -1741,6 +1837,10 @@ class EnginePool:
 
     def set_window_mode(self, mode: int):
         _check(lib().ohw_pool_set_window_mode(self.h, mode))
+
+    def set_initial_prompt(self, text):
+        """ohw_pool_set_initial_prompt: WhisperEngine.set_initial_prompt(text) on every engine of the pool"""
+        _check(lib().ohw_pool_set_initial_prompt(self.h, _text_bytes(text or "")))
 
     def set_audio_ctx(self, n):
         """ohw_pool_set_audio_ctx: WhisperEngine.set_audio_ctx on every engine of the pool"""

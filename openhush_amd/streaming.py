@@ -139,7 +139,7 @@ class StreamingSession:
     def __init__(self, ctx: E.Context, beam_size: int = 5, vad: Optional[Callable[[np.ndarray], float]] = None, vad_threshold: float = 0.5,
                  sequence_id: int = 1, tracker: Optional[TranscriptionTracker] = None, params: Optional[E.SampleParams] = None,
                  audio_config: Optional[E.PreprocessConfig] = None, noise_reduction: bool = False, noise_reduction_strength: float = 1.0,
-                 denoiser: Optional["E.Denoiser"] = None, audio_ctx=0):
+                 denoiser: Optional["E.Denoiser"] = None, audio_ctx=0, carry_context: bool = False):
         self.ctx = ctx
         self.audio_ctx = E._audio_ctx_arg(audio_ctx)
         if self.audio_ctx > ctx.hp.n_audio_ctx:
@@ -156,6 +156,10 @@ class StreamingSession:
             raise E.WhisperError(E.OHW_E_INVALID_ARG, "noise reduction is enabled but no denoise engine is plugged in")
         self.skipped_silent = 0
         self.windows_decoded = 0
+        # carry_context: the text tokens of the window just decoded are the next window's context (ohw_state_set_window_prompt),
+        # clipped to the last n_text_ctx / 2 - 1; carried across the jobs of the session, reset by a job the VAD skips
+        self.carry_context = carry_context
+        self.context: List[int] = []
 
     def _text(self, tokens: List[int]) -> str:
         return b"".join(self.ctx.token_text(t) for t in tokens if t < self.ctx.tok.eot).decode("utf-8", "replace").strip()
@@ -172,6 +176,7 @@ class StreamingSession:
         s_all = self.preprocess(job.samples)
         if self.vad is not None and float(self.vad(s_all)) < self.vad_threshold:
             self.skipped_silent += 1
+            self.context = []
             text = ""
         else:
             # the worker hands the WHOLE buffer to engine.transcribe (worker.rs:152): a job longer than 30 s (a late timer
@@ -186,11 +191,15 @@ class StreamingSession:
                     raise E.WhisperError(E.OHW_E_INVALID_ARG, f"audio_ctx {n_ctx} covers {n_ctx * 320} samples, window {off // E.CHUNK_SAMPLES} holds {len(s)}")
                 self.state.mel(s[None, :], [len(s)], E.OHW_MEL_ZERO_TAIL, want=False)
                 self.state.encode(1)
+                if self.carry_context:
+                    self.state.set_window_prompt([self.context] if self.context else None)
                 if self.beam_size >= 2:
                     toks = self.state.beam_search(1, self.beam_size, self.params)[0]["tokens"]
                 else:
                     toks = self.state.greedy(1, self.params)[0][0]
                 parts.append(b"".join(self.ctx.token_text(t) for t in toks if t < self.ctx.tok.eot))
+                if self.carry_context:
+                    self.context = E.prompt_clip([t for t in toks if t < self.ctx.tok.eot], self.ctx.hp.n_text_ctx)
                 self.windows_decoded += 1
             text = b"".join(parts).decode("utf-8", "replace").strip()
         return ChunkResult(text, job.sequence_id, job.chunk_id, job.is_final, len(job.samples) / SAMPLE_RATE)
