@@ -277,6 +277,21 @@ int ohw_mel(ohw_state* st, const float* pcm, int64_t pcm_stride, const int32_t* 
  *     ohw_mel; mel_out as there.  The engine's OHW_WINDOW_SEEK mode runs on these two. */
 int ohw_recording_set(ohw_state* st, const float* pcm, int64_t n, int pcm_on_device, float* log_max_out);
 int ohw_mel_seek(ohw_state* st, const int32_t* seek_frames, int batch, float* mel_out);
+/* Recording slots: a state holds up to max_batch recordings side by side, next to the single one above (which keeps its
+ * behaviour and its bits), so that one window of each of several recordings can go through one encode and one decode batch.
+ *   ohw_recording_set_slot: ohw_recording_set into slot `slot` (0 .. max_batch - 1), with the same limits per slot; the
+ *     recording's own log-mel maximum is found in one pass and kept in that slot's entry of a per-slot table.  Setting a slot
+ *     again replaces its recording (a shorter one never sees the old samples: every read is bounded by the new length).
+ *   ohw_mel_seek_slots: window b is frames [seek_frames[b], +3000) of the spectrogram of the recording in slots[b], clamped
+ *     with THAT recording's maximum, reflected only at that recording's start, zeros only after that recording's end.  A slot
+ *     may appear more than once.  An empty slot, a slot outside the state, or a seek outside that recording's frames returns
+ *     OHW_E_INVALID_ARG.  Afterwards the state is as after ohw_mel_seek(batch): ready for ohw_encode(batch), under the same
+ *     ohw_state_set_audio_ctx / ohw_state_set_window_ctx rules.
+ * The arithmetic is ohw_recording_set's / ohw_mel_seek's: a window is bit-identical to the one those two give for the same
+ * recording and seek.  Slot storage is allocated when a slot is first set, sized by the largest recording the state has seen;
+ * a state that never sets a slot allocates nothing. */
+int ohw_recording_set_slot(ohw_state* st, int slot, const float* pcm, int64_t n, int pcm_on_device, float* log_max_out);
+int ohw_mel_seek_slots(ohw_state* st, const int32_t* slots, const int32_t* seek_frames, int batch, float* mel_out);
 /* encoder + cross-attention K/V of every decoder layer, for the windows of the last ohw_mel      */
 int ohw_encode(ohw_state* st, int batch);
 /* the same into windows [first, first + batch) of a decode batch of `total` windows (total <= max_batch): several front-end
@@ -733,6 +748,42 @@ int ohw_engine_last_language(ohw_engine* e, int32_t* id, float* prob);
 int ohw_engine_transcribe_batch_lang(ohw_engine* e, const ohw_audio_span* recs, const int32_t* lang_ids, int n_recs, uint32_t sample_rate);
 int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* text_len, const int32_t** tokens, int* n_tokens,
                             const ohw_window_quality** quality, char* language_out);
+/* host only: the bookkeeping of many seek loops (OHW_WINDOW_SEEK) run side by side, one window of every live recording per
+ * round.  ohw_engine_transcribe_long_batch runs on this object; it can be driven without a GPU.  The rule is deterministic:
+ *   - recording i ends at seek_end = 1 + (n_samples[i] - 200) / 160 frames of 10 ms and starts at seek 0;
+ *   - it is live while seek_end >= 100 && seek + 100 < seek_end (a recording under 1 s is never live and takes no slot);
+ *   - the live recordings wait longest first, equal lengths in submission order; there are max_batch slots, all free at first;
+ *   - ohw_seek_sched_round first gives every free slot, lowest slot first, to the next waiting recording, then lists the taken
+ *     slots in slot order: rec_out[b] the recording, slot_out[b] its slot, seek_out[b] its seek, fresh_out[b] = 1 when the
+ *     recording has taken the slot since the last round (its samples must be uploaded).  It returns the number of entries B
+ *     (the four arrays hold max_batch entries), 0 when every recording has ended, -1 on a null argument;
+ *   - ohw_seek_sched_advance(s, b, seek_delta), once per entry b of the last round, moves that recording on by
+ *     seek_delta > 0 ? seek_delta : 3000; a recording that is no longer live frees its slot, which the next waiting recording
+ *     takes in the following round.                                                                                        */
+typedef struct ohw_seek_sched ohw_seek_sched;
+int ohw_seek_sched_new(const int64_t* n_samples, int n_recs, int max_batch, ohw_seek_sched** out);
+int ohw_seek_sched_round(ohw_seek_sched* s, int32_t* rec_out, int32_t* slot_out, int32_t* seek_out, int32_t* fresh_out);
+int ohw_seek_sched_advance(ohw_seek_sched* s, int b, int seek_delta);
+void ohw_seek_sched_free(ohw_seek_sched* s);
+/* Long-form batch: several independent recordings of ANY length (up to a recording slot's two hours), each through the seek
+ * loop of OHW_WINDOW_SEEK, one window of every live recording in the same encode and decode batch.  The call always runs the seek
+ * loop, whatever ohw_engine_set_window_mode says, on the engine's own state with ohw_state_set_batch_invariant on for the call
+ * (no lanes, no pipeline, no pool).  Every recording passes ohw_validate_audio before any device work (OHW_E_VALIDATION,
+ * ohw_last_error() names the index).  Per round (ohw_seek_sched_*): the fresh recordings go into their slots
+ * (ohw_recording_set_slot), ohw_mel_seek_slots, ohw_encode, the greedy pass and the temperature ladder with every slot's seek,
+ * end and generator, the alignment when word timestamps are on, then each window's records with its offset seek * 0.01 s.  Each
+ * recording is one whisper_full call in whisper.cpp terms: its own std::mt19937(0) across all its windows, its own frame count
+ * as the end of the audio, the full audio context (ohw_engine_set_audio_ctx does not apply), the initial prompt in front of every
+ * window.  Language: lang_ids as in ohw_engine_transcribe_batch_lang (NULL: the engine's language, or - with
+ * ohw_engine_set_detect_language - one detection per recording, on its first window, read back once and kept for its later ones).
+ * CONTRACT: recording i's text, tokens, per-window quality records (seek_delta and temperature included), segments, token and
+ * word times and language are exactly those of ohw_engine_transcribe on it alone in OHW_WINDOW_SEEK at the full audio context
+ * with ohw_state_set_batch_invariant on, whatever it was submitted with and in whatever order.
+ * Results: ohw_engine_batch_result / ohw_engine_batch_times per recording in submission order (quality there points at the
+ * recording's first window record); ohw_engine_long_batch_quality gives all of them, one per window (q NULL-able data of
+ * n_windows records; 0 windows for a recording under 1 s).  ohw_engine_last_* are empty after this call.                 */
+int ohw_engine_transcribe_long_batch(ohw_engine* e, const ohw_audio_span* recs, const int32_t* lang_ids, int n_recs, uint32_t sample_rate);
+int ohw_engine_long_batch_quality(ohw_engine* e, int i, const ohw_window_quality** q, int* n_windows);
 /* host only: how ohw_engine_transcribe_batch batches n_recs recordings of n_samples[i] samples.  order_out [n_recs]: the
  * recordings' indices, longest first (equal lengths keep submission order); batch j holds order_out[j * max_batch ..];
  * ctx_out [n_recs]: the context of recording i under audio_ctx_setting (0 -> 1500, n -> n, -1 -> ohw_audio_ctx_for);

@@ -146,6 +146,18 @@ def main(argv=None) -> int:
     sub = ap.add_subparsers(dest="cmd", required=True)
     t = sub.add_parser("transcribe")
     t.add_argument("file")
+    many = sub.add_parser("transcribe-many", help="several recordings of any length in one call, each through whisper.cpp's seek loop, one "
+                                                  "window of every recording per decode batch; prints one JSON object per line, in argument order")
+    many.add_argument("files", nargs="+", metavar="FILE")
+    for sp_ in (t, many):
+        _add_transcribe_options(sp_)
+    args = ap.parse_args(argv)
+    if args.cmd == "transcribe-many":
+        return _transcribe_many(args)
+    return _transcribe_one(args)
+
+
+def _add_transcribe_options(t):
     t.add_argument("--model-path", required=True, help="ggml-*.bin model file")
     t.add_argument("--model", default=None, help="name printed in the JSON (default: derived from the file name)")
     t.add_argument("--language", default="auto")
@@ -177,19 +189,95 @@ def main(argv=None) -> int:
     t.add_argument("--align-heads", default="", metavar="L.H,L.H,...",
                    help="the (decoder layer, head) pairs whose cross-attention carries the alignment, at most 32; no preset ships "
                         "(INTEGRATION.md says where upstream lists them per checkpoint)")
-    args = ap.parse_args(argv)
-    align_heads = []
-    if args.word_timestamps:
+
+
+def _align_heads(args):
+    """the --align-heads pairs when --word-timestamps is on ([] when off); None after printing an error"""
+    if not args.word_timestamps:
+        return []
+    try:
+        align_heads = [(int(x.split(".")[0]), int(x.split(".")[1])) for x in args.align_heads.split(",") if x.strip()]
+    except (ValueError, IndexError):
+        align_heads = []
+    if not align_heads:
+        print("error: --word-timestamps needs --align-heads L.H,L.H,... (decoder layer . head)", file=sys.stderr)
+        return None
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        print("error: --word-timestamps is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+        return None
+    return align_heads
+
+
+def _transcribe_many(args) -> int:
+    """`transcribe-many FILE [FILE ...]`: WhisperEngine.transcribe_long_batch over the files; one JSON object per line with the
+    fields of `transcribe --format json`.  The times are the whole call's: transcription_time_ms and duration_ms are the same in
+    every line, real_time_factor is that time over the summed duration of all files."""
+    align_heads = _align_heads(args)
+    if align_heads is None:
+        return 1
+    from . import engine as E
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        print("error: transcribe-many is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+        return 1
+    try:
+        if E._audio_ctx_arg(args.audio_ctx) != 0:
+            raise ValueError
+    except ValueError:
+        print("error: transcribe-many runs every window at the full audio context; --audio-ctx does not apply", file=sys.stderr)
+        return 1
+    audios = []
+    for f in args.files:
+        if not os.path.isfile(f):
+            print(f"error: File not found: {f}", file=sys.stderr)
+            return 1
         try:
-            align_heads = [(int(x.split(".")[0]), int(x.split(".")[1])) for x in args.align_heads.split(",") if x.strip()]
-        except (ValueError, IndexError):
-            align_heads = []
-        if not align_heads:
-            print("error: --word-timestamps needs --align-heads L.H,L.H,... (decoder layer . head)", file=sys.stderr)
+            audios.append(E.AudioBuffer(load_wav_file(f, args.resampling_quality), SAMPLE_RATE))
+        except (ValueError, struct.error, EOFError) as ex:
+            print(f"error: {ex}", file=sys.stderr)
             return 1
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            print("error: --word-timestamps is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+    use_gpu = args.device.lower() != "cpu"
+    dev = int(args.device.split(":")[1]) if ":" in args.device else 0
+    t0 = time.perf_counter()
+    eng = E.WhisperEngine.new(args.model_path, args.language, args.translate, use_gpu, dev,
+                              {"auto": E.OHW_DTYPE_AUTO, "bf16": E.OHW_DTYPE_BF16, "f16": E.OHW_DTYPE_F16}[args.dtype], args.max_batch)
+    print(f"Model loaded in {1e3 * (time.perf_counter() - t0):.0f}ms", file=sys.stderr)
+    if args.prompt:
+        eng.set_initial_prompt(args.prompt)
+    if args.packed_encoder:
+        eng.set_packed_encoder(True)
+    if args.detect_language:
+        eng.set_detect_language(True)
+    if align_heads:
+        try:
+            eng.set_word_timestamps(align_heads)
+        except E.WhisperError as ex:
+            print(f"error: {ex}", file=sys.stderr)
             return 1
+    t1 = time.perf_counter()
+    try:
+        results = eng.transcribe_long_batch(audios)
+    except E.WhisperError as ex:
+        print(f"error: {ex}", file=sys.stderr)
+        return 1
+    dt = time.perf_counter() - t1
+    total = sum(a.duration_secs() for a in audios)
+    name = args.model or args.model_path.rsplit("/", 1)[-1].replace("ggml-", "").rsplit(".", 1)[0]
+    for a, res in zip(audios, results):
+        doc = {"text": res.text, "language": res.language, "duration_ms": res.duration_ms,
+               "audio_duration_secs": a.duration_secs(), "transcription_time_ms": int(dt * 1e3),
+               "real_time_factor": dt / total, "model": name.lower()}
+        if align_heads:
+            doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in res.segments]
+            doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in res.words]
+        print(json.dumps(doc))
+    eng.close()
+    return 0
+
+
+def _transcribe_one(args) -> int:
+    align_heads = _align_heads(args)
+    if align_heads is None:
+        return 1
 
     from . import engine as E
     try:

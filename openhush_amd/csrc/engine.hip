@@ -153,6 +153,14 @@ struct ohw_state {
   DevBuf pcm, n_samples, logmel, max_bits, mel_t;
   DevBuf rec_pcm, rec_max, rec_off;   // a whole recording, the maximum of its log-mel spectrogram, window offsets (ohw_recording_set)
   int64_t rec_n = 0;
+  // recording slots (ohw_recording_set_slot / ohw_mel_seek_slots), nothing until a slot is first set: one recording per slot,
+  // each buffer sized by the largest recording the state has seen when it was (re)allocated; slot_n: samples held (0: empty);
+  // slot_max: i32 [max_batch] ordered-int maxima; slot_tab: the call's tables, [entries] each of offsets i64, pointers,
+  // lengths i64, maximum indices i32
+  std::vector<DevBuf> slot_pcm;
+  std::vector<int64_t> slot_n;
+  int64_t slot_cap = 0, slot_tab_entries = 0;
+  DevBuf slot_max, slot_tab;
   // encoder activations
   DevBuf c1, h, y, qkv, att, ffn, enc;
   // taps kept for diagnostics (small models / tests only)
@@ -1072,6 +1080,126 @@ int ohw_mel_seek(ohw_state* st, const int32_t* seek_frames, int batch, float* me
     p.logmel = st->logmel.as<float>(); p.max_bits = st->rec_max.as<int32_t>(); p.mel_t = st->mel_t.p;
     p.n_mels = c->hp.n_mels; p.batch = batch; p.mode = OHW_MEL_ZERO_TAIL;
     p.offsets = st->rec_off.as<int64_t>(); p.n_total = st->rec_n; p.shared_max = 1; p.max_only = 0;
+    p.frame_limit = 2 * audio_ctx_of(st);
+    p.win_ctx = mel_win_ctx(st, batch);
+    st->mel_ctx = audio_ctx_of(st);
+    st->mel_win = st->win_ctx;
+    Dispatch::run(c->dtype, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      launch_mel<T>(p, s);
+    });
+    HIP_CHECK(hipEventRecord(st->ev[1], s));
+    st->mel_batch = batch;
+    st->enc_batch = batch;
+    if (mel_out) {
+      HIP_CHECK(hipMemcpyAsync(mel_out, st->logmel.p, (size_t)batch * c->hp.n_mels * CHUNK_FRAMES * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+  });
+}
+
+// the slot calls' table buffer: four tables of `entries` rows each, one upload per call
+static void slot_tab_reserve(ohw_state* st, int64_t entries) {
+  if (st->slot_tab_entries >= entries) return;
+  st->slot_tab.alloc((size_t)entries * 28);
+  st->slot_tab_entries = entries;
+}
+
+int ohw_recording_set_slot(ohw_state* st, int slot, const float* pcm, int64_t n, int pcm_on_device, float* log_max_out) {
+  return guard([&] {
+    if (!st || !pcm || n < 1) throw Error(OHW_E_INVALID_ARG, "recording slot: null or empty");
+    if (slot < 0 || slot >= st->max_batch)
+      throw Error(OHW_E_INVALID_ARG, "recording slot: slot " + std::to_string(slot) + " of a state of " + std::to_string(st->max_batch));
+    if (n > (int64_t)7200 * 16000) throw Error(OHW_E_INVALID_ARG, "recording slot: more than two hours");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    if (st->slot_pcm.empty()) {
+      st->slot_pcm.resize((size_t)st->max_batch);
+      st->slot_n.assign((size_t)st->max_batch, 0);
+      st->slot_max.alloc((size_t)st->max_batch * 4);
+    }
+    st->slot_cap = std::max(st->slot_cap, n);
+    DevBuf& buf = st->slot_pcm[(size_t)slot];
+    st->slot_n[(size_t)slot] = 0;                    // empty until the new recording and its maximum are in place
+    if (buf.bytes < (size_t)n * 4) {
+      HIP_CHECK(hipStreamSynchronize(s));            // windows of the old recording may still be in flight
+      buf.alloc((size_t)st->slot_cap * 4);
+    }
+    HIP_CHECK(hipMemcpyAsync(buf.p, pcm, (size_t)n * 4, pcm_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    // the maximum pass of ohw_recording_set, on this slot's samples and this slot's entry of the table
+    const int64_t n_audio = (n + N_FFT / 2) / HOP + 1;
+    const int chunks = (int)((n_audio + CHUNK_FRAMES - 1) / CHUNK_FRAMES);
+    slot_tab_reserve(st, std::max(chunks, st->max_batch));
+    std::vector<int64_t> offs((size_t)chunks);
+    for (int i = 0; i < chunks; ++i) offs[(size_t)i] = (int64_t)i * CHUNK_SAMPLES;
+    const float floor_v = -10.0f;
+    int32_t floor_bits;
+    std::memcpy(&floor_bits, &floor_v, 4);
+    floor_bits ^= 0x7fffffff;
+    int32_t* max_entry = st->slot_max.as<int32_t>() + slot;
+    HIP_CHECK(hipMemcpyAsync(max_entry, &floor_bits, 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->slot_tab.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));              // offs and floor_bits are stack-lifetime sources
+    const ohw_ctx* c = st->ctx;
+    MelParams p{};
+    p.pcm = buf.as<float>(); p.n_samples = st->n_samples.as<int32_t>();
+    p.filters = c->mel_filters.as<float>(); p.twiddle = c->twiddle.as<float>(); p.window = c->window.as<float>();
+    p.logmel = st->logmel.as<float>(); p.max_bits = max_entry; p.mel_t = st->mel_t.p;
+    p.n_mels = c->hp.n_mels; p.batch = chunks; p.mode = OHW_MEL_ZERO_TAIL;
+    p.offsets = st->slot_tab.as<int64_t>(); p.n_total = n; p.shared_max = 1; p.max_only = 1;
+    Dispatch::run(c->dtype, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      launch_mel<T>(p, s);
+    });
+    st->slot_n[(size_t)slot] = n;
+    if (log_max_out) {
+      int32_t bits = 0;
+      HIP_CHECK(hipMemcpyAsync(&bits, max_entry, 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (bits < 0) bits ^= 0x7fffffff;
+      std::memcpy(log_max_out, &bits, 4);
+    }
+  });
+}
+
+int ohw_mel_seek_slots(ohw_state* st, const int32_t* slots, const int32_t* seek_frames, int batch, float* mel_out) {
+  return guard([&] {
+    if (!st || !slots || !seek_frames) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (batch < 1 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "batch exceeds the state's max_batch");
+    const int64_t E = st->slot_tab_entries;
+    std::vector<char> tab((size_t)std::max<int64_t>(E, 1) * 28);
+    int64_t* offs = (int64_t*)tab.data();
+    const float** ptrs = (const float**)(tab.data() + E * 8);
+    int64_t* lens = (int64_t*)(tab.data() + E * 16);
+    int32_t* midx = (int32_t*)(tab.data() + E * 24);
+    for (int b = 0; b < batch; ++b) {
+      const int sl = slots[b];
+      if (sl < 0 || sl >= st->max_batch)
+        throw Error(OHW_E_INVALID_ARG, "mel_seek_slots: window " + std::to_string(b) + " names slot " + std::to_string(sl) + " of a state of " + std::to_string(st->max_batch));
+      if (st->slot_n.empty() || st->slot_n[(size_t)sl] < 1)
+        throw Error(OHW_E_INVALID_ARG, "mel_seek_slots: slot " + std::to_string(sl) + " holds no recording (ohw_recording_set_slot)");
+      const int64_t n_len = (st->slot_n[(size_t)sl] + CHUNK_SAMPLES) / HOP;
+      if (seek_frames[b] < 0 || seek_frames[b] >= n_len)
+        throw Error(OHW_E_INVALID_ARG, "mel_seek_slots: window " + std::to_string(b) + " seeks outside its recording's frames");
+      offs[b] = (int64_t)seek_frames[b] * HOP;
+      ptrs[b] = st->slot_pcm[(size_t)sl].as<float>();
+      lens[b] = st->slot_n[(size_t)sl];
+      midx[b] = sl;
+    }
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    HIP_CHECK(hipEventRecord(st->ev[0], s));
+    HIP_CHECK(hipMemcpyAsync(st->slot_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const ohw_ctx* c = st->ctx;
+    const char* dtab = st->slot_tab.as<char>();
+    MelParams p{};
+    p.pcm = nullptr; p.n_samples = st->n_samples.as<int32_t>();
+    p.filters = c->mel_filters.as<float>(); p.twiddle = c->twiddle.as<float>(); p.window = c->window.as<float>();
+    p.logmel = st->logmel.as<float>(); p.max_bits = st->slot_max.as<int32_t>(); p.mel_t = st->mel_t.p;
+    p.n_mels = c->hp.n_mels; p.batch = batch; p.mode = OHW_MEL_ZERO_TAIL;
+    p.offsets = (const int64_t*)dtab; p.n_total = 0; p.shared_max = 1; p.max_only = 0;
+    p.win_pcm = (const float* const*)(dtab + E * 8); p.win_len = (const int64_t*)(dtab + E * 16); p.win_max = (const int32_t*)(dtab + E * 24);
     p.frame_limit = 2 * audio_ctx_of(st);
     p.win_ctx = mel_win_ctx(st, batch);
     st->mel_ctx = audio_ctx_of(st);

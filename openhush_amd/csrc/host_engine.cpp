@@ -62,6 +62,19 @@ int guard(F&& f) {
 
 #include "host_engine.hpp"
 
+// ---- the seek loops of many recordings, one window of each live one per round (include/ohw.h, ohw_seek_sched_*) -----------
+// Host only.  The engine's long-form batch runs on this object and holds no second copy of the bookkeeping.
+struct ohw_seek_sched {
+  int max_batch = 1;
+  std::vector<int32_t> seek, seek_end;     // per recording, 10 ms frames
+  std::vector<int32_t> waiting;            // live recordings that hold no slot yet: longest first, equal lengths in submission order
+  size_t next_waiting = 0;
+  std::vector<int32_t> slot_rec;           // per slot: the recording it holds, -1 = free
+  std::vector<int32_t> slot_fresh;         // per slot: taken since the last round
+  std::vector<int32_t> round_rec;          // the last round: recording of entry b
+  bool live(int r) const { return seek_end[(size_t)r] >= 100 && seek[(size_t)r] + 100 < seek_end[(size_t)r]; }
+};
+
 namespace {
 // ---- whisper.cpp's per-window bookkeeping (whisper_full_with_state as recalled) ---------
 struct SeqEval {
@@ -215,7 +228,7 @@ int32_t engine_detect_first_window(ohw_engine* e, const float* samples, int64_t 
 }
 
 void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text_out, int64_t win_first, int64_t win_step,
-                            const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs) {
+                            const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs, bool long_batch) {
   std::string own_text;
   std::string& text = text_out ? *text_out : own_text;
   if (win_first < 0 || win_step < 1) throw Error(OHW_E_INVALID_ARG, "transcribe: window dealing must be first >= 0, step >= 1");
@@ -529,6 +542,109 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       align_runs(sc, st, B, ends.data());
     };
 
+    if (recs && long_batch) {
+      // ---- ohw_engine_transcribe_long_batch: the seek loop of every recording, one window of each live recording per round,
+      // on the engine's own state.  Each recording is one whisper_full call: its own generator across all its windows, its own
+      // frame count as the end of the audio, the full audio context (what the single loop runs anything longer than a window
+      // at).  The caller has set e->window_mode to OHW_WINDOW_SEEK for the call.
+      e->batch_records.assign((size_t)n_recs, ohw_engine::BatchRecord());
+      const int MB = e->max_batch;
+      std::vector<int64_t> lens((size_t)n_recs);
+      for (int i = 0; i < n_recs; ++i) lens[(size_t)i] = recs[i].n;
+      ohw_seek_sched* sched_raw = nullptr;
+      const int src = ohw_seek_sched_new(lens.data(), n_recs, MB, &sched_raw);
+      if (src != OHW_OK) throw Error(src, g_last_error);
+      struct SchedFree { ohw_seek_sched* s; ~SchedFree() { ohw_seek_sched_free(s); } } sched_free{sched_raw};
+      struct Restore {
+        ohw_engine* e;
+        explicit Restore(ohw_engine* e_) : e(e_) { (void)ohw_state_set_batch_invariant(e->state, 1); }
+        ~Restore() { (void)ohw_state_set_batch_invariant(e->state, 0); (void)ohw_state_set_window_lang(e->state, nullptr, 0); }
+      } restore_state(e);
+      const bool per_rec = V >= 51865 && (rec_langs != nullptr || engine_detects(e));
+      if (rec_langs)
+        for (int i = 0; i < n_recs; ++i)
+          if (rec_langs[i] != OHW_LANG_DETECT && (rec_langs[i] < 0 || rec_langs[i] >= tk.n_langs))
+            throw Error(OHW_E_INVALID_ARG, "transcribe_long_batch: recording " + std::to_string(i) + " asks for language id " + std::to_string(rec_langs[i]));
+      check(ohw_state_set_stream(e->state, nullptr));
+      check(ohw_state_set_audio_ctx(e->state, 0));
+      check(ohw_state_set_window_ctx(e->state, nullptr, 0));
+      // what emit() appends to, per recording: swapped into the engine's last_* records around every emit
+      struct Acc {
+        std::string text; std::vector<int32_t> tokens; std::vector<ohw_window_quality> quality;
+        std::vector<ohw_token_time> token_times; std::vector<ohw_span_time> words, segments; std::vector<ohw_engine::WindowMark> marks;
+      };
+      std::vector<Acc> acc((size_t)n_recs);
+      auto swap_acc = [&](Acc& a) {
+        text.swap(a.text); e->last_tokens.swap(a.tokens); e->last_quality.swap(a.quality); e->last_token_times.swap(a.token_times);
+        e->last_words.swap(a.words); e->last_segments.swap(a.segments); e->last_marks.swap(a.marks);
+      };
+      // a recording's language: the caller's id, or OHW_LANG_DETECT until its first window has been detected (with no table: -1)
+      std::vector<int32_t> rec_lang((size_t)n_recs, -1);
+      if (per_rec) for (int i = 0; i < n_recs; ++i) rec_lang[(size_t)i] = rec_langs ? rec_langs[i] : OHW_LANG_DETECT;
+      rngs.reset((size_t)n_recs);
+      Scratch sc(MB, max_tok);
+      std::vector<int32_t> r_rec((size_t)MB), r_slot((size_t)MB), r_seek((size_t)MB), r_fresh((size_t)MB);
+      std::vector<int> seeks((size_t)MB), ends((size_t)MB), frames((size_t)MB);
+      std::vector<ohw_rng*> round_rngs((size_t)MB);
+      for (;;) {
+        const int B = ohw_seek_sched_round(sched_raw, r_rec.data(), r_slot.data(), r_seek.data(), r_fresh.data());
+        if (B < 0) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: " + g_last_error);
+        if (B == 0) break;
+        for (int b = 0; b < B; ++b) {
+          const int i = r_rec[(size_t)b];
+          if (r_fresh[(size_t)b]) check(ohw_recording_set_slot(e->state, r_slot[(size_t)b], recs[i].samples, recs[i].n, 0, nullptr));
+          seeks[(size_t)b] = r_seek[(size_t)b];
+          ends[(size_t)b] = mel_frames(recs[i].n);
+          frames[(size_t)b] = std::min(CHUNK_FRAMES, ends[(size_t)b] - seeks[(size_t)b]);
+          round_rngs[(size_t)b] = rngs.v[(size_t)i];
+        }
+        check(ohw_mel_seek_slots(e->state, r_slot.data(), r_seek.data(), B, nullptr));
+        check(ohw_encode(e->state, B));
+        if (per_rec) {
+          batch_lang.assign((size_t)B, OHW_LANG_DETECT);
+          bool any_detect = false;
+          for (int b = 0; b < B; ++b) {
+            batch_lang[(size_t)b] = rec_lang[(size_t)r_rec[(size_t)b]];
+            any_detect = any_detect || batch_lang[(size_t)b] == OHW_LANG_DETECT;
+          }
+          check(ohw_state_set_window_lang(e->state, batch_lang.data(), B));
+          if (any_detect) {
+            // whisper.cpp detects once per whisper_full call, on the first window: read back once, kept for the later windows
+            check(ohw_state_detect_window_lang(e->state, B));
+            check(ohw_state_window_lang(e->state, B, batch_lang.data(), nullptr));
+            for (int b = 0; b < B; ++b) rec_lang[(size_t)r_rec[(size_t)b]] = batch_lang[(size_t)b];
+          }
+        }
+        greedy_t0(sc, e->state, B, seeks.data(), ends.data(), 0);
+        run_ladder(sc, e->state, B, seeks.data(), ends.data(), 0, round_rngs);
+        align_runs(sc, e->state, B, frames.data());
+        sc.trace.clear();
+        for (int b = 0; b < B; ++b) {
+          const int i = r_rec[(size_t)b];
+          const WindowRun& r = sc.runs[(size_t)b];
+          swap_acc(acc[(size_t)i]);
+          emit(r, seeks[(size_t)b] * 0.01, std::min(seeks[(size_t)b] * 0.01 + 30.0, (double)recs[i].n / 16000.0));
+          swap_acc(acc[(size_t)i]);
+          check(ohw_seek_sched_advance(sched_raw, b, r.ev.seek_delta));
+        }
+      }
+      for (int i = 0; i < n_recs; ++i) {
+        Acc& a = acc[(size_t)i];
+        ohw_engine::BatchRecord& r = e->batch_records[(size_t)i];
+        const size_t b0 = a.text.find_first_not_of(" \t\r\n"), b1 = a.text.find_last_not_of(" \t\r\n");
+        r.text = b0 == std::string::npos ? std::string() : a.text.substr(b0, b1 - b0 + 1);
+        trim_spans(a.words, b0 == std::string::npos ? 0 : b0, r.text.size());
+        trim_spans(a.segments, b0 == std::string::npos ? 0 : b0, r.text.size());
+        r.tokens = std::move(a.tokens); r.qualities = std::move(a.quality);
+        r.token_times = std::move(a.token_times); r.words = std::move(a.words); r.segments = std::move(a.segments);
+        if (!r.qualities.empty()) r.quality = r.qualities[0];
+        // a recording that never ran a window (under 1 s) was never detected: id 0, as the single loop reports it
+        r.lang_id = !per_rec ? -1 : rec_lang[(size_t)i] == OHW_LANG_DETECT ? 0 : rec_lang[(size_t)i];
+      }
+      text.clear(); e->last_tokens.clear(); e->last_quality.clear();
+      e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
+      return;
+    }
     if (recs) {
       // ---- ohw_engine_transcribe_batch: every recording one window of its own; longest first, max_batch at a time, one batch
       // after the other on the engine's own state.  Under the auto setting a batch's envelope is its largest context and every
@@ -1353,6 +1469,92 @@ int ohw_engine_transcribe_batch_lang(ohw_engine* e, const ohw_audio_span* recs, 
   });
 }
 
+// ---- ohw_seek_sched_*: host only -------------------------------------------------------------------------------------------
+int ohw_seek_sched_new(const int64_t* n_samples, int n_recs, int max_batch, ohw_seek_sched** out) {
+  return guard([&] {
+    if (!n_samples || n_recs < 1 || max_batch < 1 || !out) throw Error(OHW_E_INVALID_ARG, "seek_sched: bad argument");
+    *out = nullptr;
+    std::unique_ptr<ohw_seek_sched> s(new ohw_seek_sched());
+    s->max_batch = max_batch;
+    s->seek.assign((size_t)n_recs, 0);
+    s->seek_end.resize((size_t)n_recs);
+    for (int i = 0; i < n_recs; ++i) {
+      if (n_samples[i] < 0 || n_samples[i] > (int64_t)7200 * 16000)
+        throw Error(OHW_E_INVALID_ARG, "seek_sched: recording " + std::to_string(i) + " holds " + std::to_string(n_samples[i]) + " samples (0 .. two hours)");
+      s->seek_end[(size_t)i] = mel_frames(n_samples[i]);
+      if (s->live(i)) s->waiting.push_back(i);
+    }
+    std::stable_sort(s->waiting.begin(), s->waiting.end(), [&](int32_t a, int32_t b) { return n_samples[a] > n_samples[b]; });
+    s->slot_rec.assign((size_t)max_batch, -1);
+    s->slot_fresh.assign((size_t)max_batch, 0);
+    *out = s.release();
+  });
+}
+
+int ohw_seek_sched_round(ohw_seek_sched* s, int32_t* rec_out, int32_t* slot_out, int32_t* seek_out, int32_t* fresh_out) {
+  if (!s || !rec_out || !slot_out || !seek_out || !fresh_out) { g_last_error = "seek_sched_round: null argument"; return -1; }
+  // free slots, lowest first, go to the waiting recordings in their order
+  for (int k = 0; k < s->max_batch && s->next_waiting < s->waiting.size(); ++k)
+    if (s->slot_rec[(size_t)k] < 0) { s->slot_rec[(size_t)k] = s->waiting[s->next_waiting++]; s->slot_fresh[(size_t)k] = 1; }
+  s->round_rec.clear();
+  int B = 0;
+  for (int k = 0; k < s->max_batch; ++k) {
+    const int r = s->slot_rec[(size_t)k];
+    if (r < 0) continue;
+    rec_out[B] = r; slot_out[B] = k; seek_out[B] = s->seek[(size_t)r]; fresh_out[B] = s->slot_fresh[(size_t)k];
+    s->slot_fresh[(size_t)k] = 0;
+    s->round_rec.push_back(r);
+    ++B;
+  }
+  return B;
+}
+
+int ohw_seek_sched_advance(ohw_seek_sched* s, int b, int seek_delta) {
+  return guard([&] {
+    if (!s) throw Error(OHW_E_INVALID_ARG, "seek_sched_advance: null scheduler");
+    if (b < 0 || b >= (int)s->round_rec.size() || s->round_rec[(size_t)b] < 0)
+      throw Error(OHW_E_INVALID_ARG, "seek_sched_advance: no entry " + std::to_string(b) + " to advance in the last round");
+    const int r = s->round_rec[(size_t)b];
+    s->round_rec[(size_t)b] = -1;             // one advance per entry and round
+    s->seek[(size_t)r] += seek_delta > 0 ? seek_delta : 3000;
+    if (!s->live(r))
+      for (auto& sr : s->slot_rec) if (sr == r) sr = -1;
+  });
+}
+
+void ohw_seek_sched_free(ohw_seek_sched* s) { delete s; }
+
+int ohw_engine_transcribe_long_batch(ohw_engine* e, const ohw_audio_span* recs, const int32_t* lang_ids, int n_recs, uint32_t sample_rate) {
+  return guard([&] {
+    if (!e || !recs || n_recs < 1) throw Error(OHW_E_INVALID_ARG, "transcribe_long_batch: null engine or no recordings");
+    e->batch_records.clear();
+    for (int i = 0; i < n_recs; ++i) {
+      ohw_audio_info info;
+      if (ohw_validate_audio(recs[i].samples, recs[i].n, sample_rate, &info) != OHW_OK) {
+        static const char* const names[] = {"ok", "Audio is empty (no samples)", "Unexpected sample rate", "Audio too long", "Audio too short",
+                                            "Audio contains NaN values", "Audio contains infinite values"};
+        throw Error(OHW_E_VALIDATION, "Audio validation failed for recording " + std::to_string(i) + ": " + names[info.error]);
+      }
+      if (recs[i].n > (int64_t)7200 * 16000)
+        throw Error(OHW_E_INVALID_ARG, "transcribe_long_batch: recording " + std::to_string(i) + " is longer than two hours, the limit of a recording slot");
+    }
+    // the seek loop whatever ohw_engine_set_window_mode says: the per-window bookkeeping reads the mode
+    struct Mode { ohw_engine* e; int was; ~Mode() { e->window_mode = was; } } mode{e, e->window_mode};
+    e->window_mode = OHW_WINDOW_SEEK;
+    engine_transcribe_core(e, nullptr, 0, nullptr, 0, 1, recs, n_recs, lang_ids, true);
+  });
+}
+
+int ohw_engine_long_batch_quality(ohw_engine* e, int i, const ohw_window_quality** q, int* n_windows) {
+  return guard([&] {
+    if (!e || !q || !n_windows) throw Error(OHW_E_INVALID_ARG, "long_batch_quality: null argument");
+    if (i < 0 || i >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "long_batch_quality: no recording " + std::to_string(i) + " in the last batch call");
+    const ohw_engine::BatchRecord& r = e->batch_records[(size_t)i];
+    *q = r.qualities.data();
+    *n_windows = (int)r.qualities.size();
+  });
+}
+
 int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* text_len, const int32_t** tokens, int* n_tokens,
                             const ohw_window_quality** quality, char* language_out) {
   return guard([&] {
@@ -1363,7 +1565,7 @@ int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* tex
     if (text_len) *text_len = r.text.size();
     if (tokens) *tokens = r.tokens.data();
     if (n_tokens) *n_tokens = (int)r.tokens.size();
-    if (quality) *quality = &r.quality;
+    if (quality) *quality = r.qualities.empty() ? &r.quality : r.qualities.data();     // long batch: one record per window
     if (language_out) {
       const std::string lang = r.lang_id >= 0 ? ohw_lang_id_to_code(r.lang_id) : e->language == "auto" ? ohw_lang_id_to_code(0) : e->language;
       std::strncpy(language_out, lang.c_str(), 7);

@@ -42,6 +42,7 @@ struct ohw_engine {
   // lang_id: the language the recording was decoded in when it had one of its own (detected or caller-given), else -1
   struct BatchRecord {
     std::string text; std::vector<int32_t> tokens; ohw_window_quality quality{}; int32_t lang_id = -1;
+    std::vector<ohw_window_quality> qualities;      // ohw_engine_transcribe_long_batch: one record per window (else empty)
     std::vector<ohw_token_time> token_times; std::vector<ohw_span_time> words, segments;
   };
   std::vector<BatchRecord> batch_records;
@@ -74,8 +75,10 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
 // recs != nullptr (ohw_engine_transcribe_batch; samples / n / text unused): n_recs validated recordings of at most one window each,
 // batched longest first on the engine's own state and decoded by the same per-window code; fills e->batch_records
 // rec_langs (with recs; may be null): one language id or OHW_LANG_DETECT per recording
+// long_batch (with recs; ohw_engine_transcribe_long_batch): recordings of any length, each through the seek loop, one window of
+// every live recording per round (ohw_seek_sched_*); the caller sets e->window_mode to OHW_WINDOW_SEEK for the call
 void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std::string* text, int64_t win_first = 0, int64_t win_step = 1,
-                            const ohw_audio_span* recs = nullptr, int n_recs = 0, const int32_t* rec_langs = nullptr);
+                            const ohw_audio_span* recs = nullptr, int n_recs = 0, const int32_t* rec_langs = nullptr, bool long_batch = false);
 // a text lost `lead` bytes at its front and now holds new_len bytes: move and cut the spans that index it
 void trim_spans(std::vector<ohw_span_time>& v, size_t lead, size_t new_len);
 // does a transcribe of this engine detect?  (the setting, language "auto", a multilingual model)

@@ -42,6 +42,12 @@ struct MelParams {
   const int64_t* offsets = nullptr;
   int64_t n_total = 0;
   int32_t shared_max = 0, max_only = 0;
+  // recording slots (ohw_recording_set_slot / ohw_mel_seek_slots): small device tables [batch]; window b reads the recording
+  // win_pcm[b] of win_len[b] samples at offsets[b] and is clamped with max_bits[win_max[b]] (each slot's own maximum); null:
+  // the one recording above (pcm, n_total, max_bits[0])
+  const float* const* win_pcm = nullptr;
+  const int64_t* win_len = nullptr;
+  const int32_t* win_max = nullptr;
   // reduced audio context: frames >= frame_limit go into the time-major image as zeros, the conv padding value (the fp32
   // log-mel output is untouched); 0 = all 3000 frames
   int32_t frame_limit = 0;

@@ -30,9 +30,10 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_power_kernel(MelParams p) {
   const int t0 = blockIdx.x * MEL_FR;
   const int tid = threadIdx.x;
   const bool rec = p.offsets != nullptr;
+  const bool slots = p.win_pcm != nullptr;     // window b of its own recording (uniform loads from the slot tables)
   const int64_t off = rec ? p.offsets[b] : 0;
-  const int64_t n = rec ? p.n_total : (p.n_samples[b] < CHUNK_SAMPLES ? p.n_samples[b] : CHUNK_SAMPLES);
-  const float* pcm = rec ? p.pcm : p.pcm + (int64_t)b * p.pcm_stride;
+  const int64_t n = rec ? (slots ? p.win_len[b] : p.n_total) : (p.n_samples[b] < CHUNK_SAMPLES ? p.n_samples[b] : CHUNK_SAMPLES);
+  const float* pcm = rec ? (slots ? p.win_pcm[b] : p.pcm) : p.pcm + (int64_t)b * p.pcm_stride;
   for (int i = tid; i < N_FFT; i += MEL_THREADS) { tw[0][i] = p.twiddle[i]; tw[1][i] = p.twiddle[N_FFT + i]; }
   for (int i = tid; i < N_FFT * MEL_FR; i += MEL_THREADS) {
     const int f = i / N_FFT, j = i % N_FFT;
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_power_kernel(MelParams p) {
   if (tid == 0) {
     float m = red[0];
     for (int i = 1; i < MEL_THREADS / 64; ++i) m = fmaxf(m, red[i]);
-    if (m > -INFINITY) atomicMax(&p.max_bits[p.shared_max ? 0 : b], ordered_bits(m));
+    if (m > -INFINITY) atomicMax(&p.max_bits[slots ? p.win_max[b] : p.shared_max ? 0 : b], ordered_bits(m));
   }
 }
 
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(256) void mel_normalize_kernel(MelParams p) {
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * 64;
   const int tid = threadIdx.x;
-  const float mx = from_ordered_bits(p.max_bits[p.shared_max ? 0 : b]);
+  const float mx = from_ordered_bits(p.max_bits[p.win_max ? p.win_max[b] : p.shared_max ? 0 : b]);
   const float floor_v = mx - 8.0f;
   for (int i = tid; i < p.n_mels * 64; i += 256) {
     const int c = i / 64, tt = i % 64;

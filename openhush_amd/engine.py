@@ -197,6 +197,8 @@ EXPORTS = [
     "ohw_dbg_cross_attn_chunk",
     "ohw_state_set_window_prompt", "ohw_state_window_prompt_len", "ohw_state_prefill", "ohw_tokenize_host", "ohw_tokenize", "ohw_prompt_clip_host",
     "ohw_engine_set_initial_prompt", "ohw_engine_set_initial_prompt_tokens", "ohw_pool_set_initial_prompt",
+    "ohw_recording_set_slot", "ohw_mel_seek_slots", "ohw_seek_sched_new", "ohw_seek_sched_round", "ohw_seek_sched_advance", "ohw_seek_sched_free",
+    "ohw_engine_transcribe_long_batch", "ohw_engine_long_batch_quality",
 ]
 
 
@@ -344,6 +346,15 @@ def lib():
         L.ohw_mel.argtypes = [vp, vp, C.c_int64, ip, C.c_int, C.c_int, C.c_int, fp]
         L.ohw_recording_set.argtypes = [vp, vp, C.c_int64, C.c_int, fp]
         L.ohw_mel_seek.argtypes = [vp, ip, C.c_int, fp]
+        L.ohw_recording_set_slot.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, fp]
+        L.ohw_mel_seek_slots.argtypes = [vp, ip, ip, C.c_int, fp]
+        L.ohw_seek_sched_new.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(vp)]
+        L.ohw_seek_sched_round.argtypes = [vp, ip, ip, ip, ip]
+        L.ohw_seek_sched_advance.argtypes = [vp, C.c_int, C.c_int]
+        L.ohw_seek_sched_free.argtypes = [vp]
+        L.ohw_seek_sched_free.restype = None
+        L.ohw_engine_transcribe_long_batch.argtypes = [vp, C.POINTER(AudioSpan), ip, C.c_int, C.c_uint32]
+        L.ohw_engine_long_batch_quality.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(WindowQuality)), C.POINTER(C.c_int)]
         L.ohw_encode.argtypes = [vp, C.c_int]
         L.ohw_encode_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.ohw_detect_language.argtypes = [vp, C.c_int, ip, fp]
@@ -854,6 +865,39 @@ class Stream:
             pass
 
 
+class SeekSched:
+    """ohw_seek_sched (host only): which recordings run a window in each round of the long-form batch, and where.  round() ->
+    [(rec, slot, seek, fresh)] in slot order ([] when every recording has ended); advance(b, seek_delta) once per entry"""
+
+    def __init__(self, n_samples: Sequence[int], max_batch: int):
+        ns = np.ascontiguousarray(list(n_samples), dtype=np.int64)
+        self.max_batch = int(max_batch)
+        h = C.c_void_p()
+        _check(lib().ohw_seek_sched_new(ns.ctypes.data_as(C.POINTER(C.c_int64)), len(ns), self.max_batch, C.byref(h)))
+        self.h = h
+
+    def round(self):
+        a = [np.zeros(max(1, self.max_batch), dtype=np.int32) for _ in range(4)]
+        n = int(lib().ohw_seek_sched_round(self.h, *[_ip(x) for x in a]))
+        if n < 0:
+            _raise(OHW_E_INVALID_ARG)
+        return [tuple(int(x[b]) for x in a) for b in range(n)]
+
+    def advance(self, b: int, seek_delta: int):
+        _check(lib().ohw_seek_sched_advance(self.h, int(b), int(seek_delta)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ohw_seek_sched_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class State:
     """ohw_state: activations + KV caches for up to max_batch 30 s windows"""
 
@@ -915,6 +959,23 @@ class State:
         sk = np.asarray(seek_frames, dtype=np.int32)
         out = np.empty((len(sk), self.ctx.hp.n_mels, CHUNK_FRAMES), dtype=np.float32) if want else None
         _check(lib().ohw_mel_seek(self.h, _ip(sk), len(sk), _fp(out) if want else C.cast(None, C.POINTER(C.c_float))))
+        return out
+
+    def recording_set_slot(self, slot: int, pcm: np.ndarray) -> float:
+        """ohw_recording_set_slot: a recording into slot `slot` of the state -> log10 of the largest mel power over its frames"""
+        x = np.ascontiguousarray(pcm, dtype=np.float32)
+        mx = C.c_float(0.0)
+        _check(lib().ohw_recording_set_slot(self.h, int(slot), x.ctypes.data_as(C.c_void_p), x.size, 0, C.byref(mx)))
+        return float(mx.value)
+
+    def mel_seek_slots(self, slots: Sequence[int], seek_frames: Sequence[int], want: bool = True):
+        """ohw_mel_seek_slots: window b = frames [seek_frames[b], +3000) of the recording in slots[b] -> [B][n_mels][3000] (or None)"""
+        sl = np.asarray(slots, dtype=np.int32)
+        sk = np.asarray(seek_frames, dtype=np.int32)
+        if sl.shape != sk.shape:
+            raise ValueError("mel_seek_slots: one seek per slot entry")
+        out = np.empty((len(sk), self.ctx.hp.n_mels, CHUNK_FRAMES), dtype=np.float32) if want else None
+        _check(lib().ohw_mel_seek_slots(self.h, _ip(sl), _ip(sk), len(sk), _fp(out) if want else C.cast(None, C.POINTER(C.c_float))))
         return out
 
     def encode(self, batch: int):
@@ -1649,17 +1710,13 @@ class WhisperEngine:
         _check(lib().ohw_engine_last_language(self.h, C.byref(i), C.byref(pr)))
         return int(i.value), lib().ohw_lang_id_to_code(i.value).decode(), float(pr.value)
 
-    def transcribe_batch(self, audios: Sequence[AudioBuffer], languages: Optional[Sequence] = None) -> List[TranscriptionResult]:
-        """ohw_engine_transcribe_batch: independent recordings of at most 30 s each in one call, batched longest first; results in
-        submission order.  Tokens and quality of recording i: batch_result(i).  duration_ms is the whole call's.
-        languages (ohw_engine_transcribe_batch_lang): one entry per recording - a language id, a code, or None / "auto" / -1 to
-        detect that recording"""
-        if not audios:
-            return []
+    def _batch_call(self, what: str, audios: Sequence[AudioBuffer], languages: Optional[Sequence], call) -> List[TranscriptionResult]:
+        """the shared body of transcribe_batch / transcribe_long_batch: language ids, audio spans, call(spans, langs or None, n,
+        rate), then every recording's result and times"""
         langs = None
         if languages is not None:
             if len(languages) != len(audios):
-                raise ValueError("transcribe_batch: one language per recording")
+                raise ValueError(f"{what}: one language per recording")
             ids = []
             for x in languages:
                 if x is None or x == "auto":
@@ -1674,23 +1731,58 @@ class WhisperEngine:
             langs = np.asarray(ids, dtype=np.int32)
         rates = {int(a.sample_rate) for a in audios}
         if len(rates) != 1:
-            raise ValueError("transcribe_batch: the recordings must share one sample rate")
+            raise ValueError(f"{what}: the recordings must share one sample rate")
         bufs = [np.ascontiguousarray(a.samples, dtype=np.float32) for a in audios]
         spans = (AudioSpan * len(bufs))()
         for i, b in enumerate(bufs):
             spans[i].samples = _fp(b) if b.size else C.cast(None, C.POINTER(C.c_float))
             spans[i].n = b.size
         t0 = time.perf_counter()
-        if langs is None:
-            _check(lib().ohw_engine_transcribe_batch(self.h, spans, len(bufs), rates.pop()))
-        else:
-            _check(lib().ohw_engine_transcribe_batch_lang(self.h, spans, _ip(langs), len(bufs), rates.pop()))
+        _check(call(spans, langs, len(bufs), rates.pop()))
         ms = int((time.perf_counter() - t0) * 1000)
         out = []
         for i in range(len(bufs)):
             r = self.batch_result(i)
             tt, words, segs = self.batch_times(i)
             out.append(TranscriptionResult(r[0], r[3], ms, tt, words, segs))
+        return out
+
+    def transcribe_batch(self, audios: Sequence[AudioBuffer], languages: Optional[Sequence] = None) -> List[TranscriptionResult]:
+        """ohw_engine_transcribe_batch: independent recordings of at most 30 s each in one call, batched longest first; results in
+        submission order.  Tokens and quality of recording i: batch_result(i).  duration_ms is the whole call's.
+        languages (ohw_engine_transcribe_batch_lang): one entry per recording - a language id, a code, or None / "auto" / -1 to
+        detect that recording"""
+        if not audios:
+            return []
+
+        def call(spans, langs, n, rate):
+            if langs is None:
+                return lib().ohw_engine_transcribe_batch(self.h, spans, n, rate)
+            return lib().ohw_engine_transcribe_batch_lang(self.h, spans, _ip(langs), n, rate)
+        return self._batch_call("transcribe_batch", audios, languages, call)
+
+    def transcribe_long_batch(self, audios: Sequence[AudioBuffer], languages: Optional[Sequence] = None) -> List[TranscriptionResult]:
+        """ohw_engine_transcribe_long_batch: independent recordings of any length in one call, each through the seek loop
+        (OHW_WINDOW_SEEK, whatever set_window_mode says), one window of every live recording per decode batch.  Recording i's
+        result equals transcribe() of it alone in the seek mode with batch invariance on.  Results in submission order; tokens,
+        first window's quality and language: batch_result(i); every window's quality: long_batch_quality(i); times:
+        batch_times(i).  languages as in transcribe_batch"""
+        if not audios:
+            return []
+
+        def call(spans, langs, n, rate):
+            return lib().ohw_engine_transcribe_long_batch(self.h, spans, _ip(langs) if langs is not None else None, n, rate)
+        return self._batch_call("transcribe_long_batch", audios, languages, call)
+
+    def long_batch_quality(self, i: int):
+        """one dict per window of recording i of the last transcribe_long_batch with every ohw_window_quality field"""
+        q, n = C.POINTER(WindowQuality)(), C.c_int(0)
+        _check(lib().ohw_engine_long_batch_quality(self.h, int(i), C.byref(q), C.byref(n)))
+        out = []
+        for k in range(n.value):
+            d = {name: getattr(q[k], name) for name, _ in WindowQuality._fields_}
+            d["would_fallback"], d["no_speech"], d["failed"] = bool(d["would_fallback"]), bool(d["no_speech"]), bool(d["failed"])
+            out.append(d)
         return out
 
     def batch_result(self, i: int):
