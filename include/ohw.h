@@ -393,6 +393,26 @@ typedef struct {
 } ohw_beam_result;
 int ohw_beam_search(ohw_state* st, const ohw_sample_params* p, int n_windows, int beam_size, int max_tokens, const ohw_beam_result* out);
 
+/* the same search with what a decode policy needs to judge the result (the engine's beam pass: ohw_engine_set_beam_size).  The
+ * search is ohw_beam_search's, step for step: tokens, n_tokens, sum_logprob and n_finished are the same bits.  On top of it
+ * every beam carries the log-probability of each of its tokens (gathered with the token history when beams are reordered),
+ * the first step also computes the window's no-speech probability from the unfiltered prompt row (bias added, no mask: what
+ * ohw_greedy_ex reports), and the final ranking - the pool's sequences, topped up with the live beams by descending sum until
+ * there are beam_size; best sum / max(1, n) in fp32, the first maximum - runs on the device, so only n_windows rows are
+ * read back.  token_logprobs: the winner's per-token values; when it ended with end-of-text (ended_by_eot = 1: it came from
+ * the finished pool) that token's value follows at index n_tokens.  Every field but tokens and n_tokens may be NULL.
+ * The captured step graphs of this form are cached apart from ohw_beam_search's (they bake other pointers in).            */
+typedef struct {
+  int32_t* tokens;         /* [n_windows][max_tokens] */
+  int32_t* n_tokens;       /* [n_windows] */
+  float* sum_logprob;      /* [n_windows] or NULL */
+  int32_t* n_finished;     /* [n_windows] or NULL */
+  float* token_logprobs;   /* [n_windows][max_tokens + 1] or NULL */
+  int32_t* ended_by_eot;   /* [n_windows] or NULL */
+  float* no_speech_prob;   /* [n_windows] or NULL */
+} ohw_beam_result_ex;
+int ohw_beam_search_ex(ohw_state* st, const ohw_sample_params* p, int n_windows, int beam_size, int max_tokens, const ohw_beam_result_ex* out);
+
 /* additive bias on every logits row before the filter, bias[n_vocab] (host; copied), NULL clears it.  This is the
  * engine's form of whisper.cpp's logits_filter_callback (whisper_full_params; the reference sets none,
  * src/engine/whisper.rs:243-263, so the default is no bias); tests use it to make end-of-text and timestamps win.
@@ -699,6 +719,19 @@ int ohw_engine_set_window_mode(ohw_engine* e, int mode);
  * that many tokens with end-of-text suppressed (ohw_sample_params.force_len; use with temperature_inc = 0: a forced sequence
  * fails whisper.cpp's acceptance test by construction); 0 (default) = the reference's behaviour.                         */
 int ohw_engine_set_force_len(ohw_engine* e, int n_tokens);
+/* beam search as the T = 0 strategy of every transcribe of the engine (whisper.cpp's WHISPER_SAMPLING_BEAM_SEARCH): k = 0
+ * (default) = greedy, k = 2..5 = ohw_beam_search_ex with k beams per window.  OHW_E_INVALID_ARG for another k, for
+ * k > max_batch, and together with ohw_engine_set_force_len (whichever setter comes second fails).  Everything else of a
+ * transcribe stays: window modes and the seek loop, ohw_engine_transcribe_batch(_lang) and _long_batch, the acceptance test,
+ * the no-speech rule, the temperature ladder, segments, word timestamps, prompts, languages and audio contexts per window.
+ *   - a decode batch holds floor(max_batch / k) windows (k decoder rows per window); batch cutting takes that number
+ *   - the search's winner - with end-of-text when it came from the finished pool - is judged by whisper.cpp's bookkeeping and
+ *     cut at the first of its loop exits, like a sampled pass; it is traced at temperature 0 (ohw_engine_last_trace).
+ *     DEVIATION: whisper.cpp applies its loop exits to every decoder during the search; beam search is not causal, so here they
+ *     are applied to the winner after it
+ *   - passes at T > 0 are the unchanged ladder (whisper.cpp as recalled: at t_cur > 0 the beam strategy samples, best_of)
+ *   - the LANES / PIPELINE schedules are not used: a call with beam on runs one batch after the other on the engine's own state */
+int ohw_engine_set_beam_size(ohw_engine* e, int k);
 /* reduced audio context of every window ohw_engine_transcribe runs (ohw_state_set_audio_ctx on the engine's own, pipeline
  * and lane states): 0 (default) = off, the full context; n > 0 = that context for every window of every window mode and
  * schedule - a transcribe in which some window holds samples past n * 320 fails with OHW_E_INVALID_ARG naming the window
@@ -831,6 +864,7 @@ int ohw_pool_create(const char* model_path, const char* language, int translate,
 int ohw_pool_create_synthetic(const ohw_hparams* hp, uint32_t seed, const char* language, int translate, const int* device_ids,
                               int n_devices, int dtype, int max_batch, ohw_pool** out);
 int ohw_pool_set_force_len(ohw_pool* p, int n_tokens);                     /* ohw_engine_set_force_len on every engine */
+int ohw_pool_set_beam_size(ohw_pool* p, int k);                              /* ohw_engine_set_beam_size on every engine */
 int ohw_pool_set_schedule(ohw_pool* p, int schedule, int lanes, int merge); /* ohw_engine_set_schedule on every engine */
 int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t sample_rate, char* text_buf, size_t text_cap,
                         char* language_out, uint64_t* duration_ms, ohw_audio_info* info);
@@ -1006,6 +1040,51 @@ typedef struct {
   uint32_t* tickets_out;   /* out [R] */
 } ohw_dbg_beam_io;
 int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* p, const ohw_dbg_beam_io* io);
+
+/* ohw_dbg_beam_step with the log-probability history and the no-speech probability of ohw_beam_search_ex.  base: as above.
+ * plog NULL: the kernels touch no history (plog_next and fin_plog are then left alone) and the call is ohw_dbg_beam_step.
+ * Otherwise plog_next is filled with OHW_DBG_SENTINEL_F32 before the launch, as are fin_plog's rows from fin_cnt[w] on, and
+ * both come back whole.  nosp_prob (or NULL): sentinel-filled; written for the windows of a first step only.               */
+typedef struct {
+  ohw_dbg_beam_io base;
+  const float* plog;       /* in  [R][n_text_ctx + 1] or NULL: log-probability of every history token, n_cur[w] used per row */
+  float* plog_next;        /* out [R][n_text_ctx + 1] */
+  float* fin_plog;         /* in / out [R][n_text_ctx + 1]: fin_len values per used pool slot, end-of-text's at index fin_len */
+  float* nosp_prob;        /* out [W] or NULL */
+} ohw_dbg_beam_io_ex;
+int ohw_dbg_beam_step_ex(ohw_state* st, const ohw_sample_params* p, const ohw_dbg_beam_io_ex* io);
+
+/* the final ranking of a beam search on caller-supplied pool and live state (host arrays), R = W * K rows:
+ * candidates are window w's pool entries 0 .. fin_cnt[w] - 1 in pool order; if fewer than K, its live beams join by
+ * descending beam_sum (equal sums: the lower beam index; -inf skipped) until there are K; score = sum / max(1, n) in fp32
+ * with a correctly rounded division; the first strict maximum wins.  Written per window: the winner's first
+ * min(n, max_tokens) tokens and log-probabilities, end-of-text's log-probability after them when it came from the pool
+ * (ended_by_eot = 1), n_tokens, sum_logprob, n_finished = fin_cnt[w]; a window without any candidate gives n_tokens 0,
+ * sum_logprob 0, ended_by_eot 0.  Checked first (OHW_E_INVALID_ARG): K in 2..5, W >= 1, 1 <= stride, 0 <= max_tokens <= stride,
+ * fin_cnt in 0..K, fin_len of the used slots and n_cur in 0..stride.
+ * ohw_dbg_beam_finish runs beam_finish_kernel (needs W * K <= max_batch and stride == n_text_ctx, the state's token capacity);
+ * out_tokens / out_logprobs / n_tokens / sum_logprob / ended_by_eot / n_finished are filled with the sentinels first, so what
+ * the kernel did not write shows.  ohw_beam_finish_host is the same rule on the host, no GPU, with the same sentinel fill.  */
+typedef struct {
+  int32_t K, W, stride, max_tokens;
+  const int32_t* fin_cnt;  /* [W] */
+  const int32_t* fin_len;  /* [R] */
+  const float* fin_sum;    /* [R] */
+  const int32_t* fin_tok;  /* [R][stride] */
+  const float* fin_plog;   /* [R][stride + 1] */
+  const int32_t* n_cur;    /* [W] length of every live beam */
+  const int32_t* tokens;   /* [R][stride] live histories */
+  const float* plog;       /* [R][stride + 1] */
+  const float* beam_sum;   /* [R] */
+  int32_t* out_tokens;     /* out [W][max_tokens] */
+  float* out_logprobs;     /* out [W][max_tokens + 1] */
+  int32_t* n_tokens;       /* out [W] */
+  float* sum_logprob;      /* out [W] */
+  int32_t* ended_by_eot;   /* out [W] */
+  int32_t* n_finished;     /* out [W] */
+} ohw_beam_finish_io;
+int ohw_dbg_beam_finish(ohw_state* st, const ohw_beam_finish_io* io);
+int ohw_beam_finish_host(const ohw_beam_finish_io* io);
 
 #ifdef __cplusplus
 }

@@ -183,12 +183,38 @@ def _add_transcribe_options(t):
     t.add_argument("--detect-language", action="store_true",
                    help="with --language auto on a multilingual model: detect the language on the first 30 s window and decode in it "
                         "(default: auto means en, as in the reference); the JSON language field carries the detected code")
+    t.add_argument("--beam-size", type=_beam_size_arg, default=0, metavar="K",
+                   help="beam search with K beams (2..5) as the temperature-0 strategy (whisper.cpp's beam_size); 0 (default): greedy. "
+                        "A decode batch then holds max-batch / K windows; the fallback temperatures sample as before")
     t.add_argument("--word-timestamps", action="store_true",
                    help="align every window's tokens on the device and add \"segments\" and \"words\" arrays (text, t0, t1 in seconds) to "
                         "the JSON; needs --align-heads")
     t.add_argument("--align-heads", default="", metavar="L.H,L.H,...",
                    help="the (decoder layer, head) pairs whose cross-attention carries the alignment, at most 32; no preset ships "
                         "(INTEGRATION.md says where upstream lists them per checkpoint)")
+
+
+def _beam_size_arg(v: str) -> int:
+    try:
+        k = int(v)
+    except ValueError:
+        k = -1
+    if k != 0 and not 2 <= k <= 5:
+        raise argparse.ArgumentTypeError(f"takes 0 (greedy) or a beam size in 2..5, not '{v}'")
+    return k
+
+
+def _check_beam(args) -> bool:
+    """--beam-size against the other options, before any model is loaded"""
+    if args.beam_size == 0:
+        return True
+    if args.beam_size > args.max_batch:
+        print(f"error: --beam-size {args.beam_size} needs --max-batch >= {args.beam_size} (a window takes one decoder row per beam)", file=sys.stderr)
+        return False
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        print("error: --beam-size is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+        return False
+    return True
 
 
 def _align_heads(args):
@@ -213,7 +239,7 @@ def _transcribe_many(args) -> int:
     fields of `transcribe --format json`.  The times are the whole call's: transcription_time_ms and duration_ms are the same in
     every line, real_time_factor is that time over the summed duration of all files."""
     align_heads = _align_heads(args)
-    if align_heads is None:
+    if align_heads is None or not _check_beam(args):
         return 1
     from . import engine as E
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -243,6 +269,8 @@ def _transcribe_many(args) -> int:
     print(f"Model loaded in {1e3 * (time.perf_counter() - t0):.0f}ms", file=sys.stderr)
     if args.prompt:
         eng.set_initial_prompt(args.prompt)
+    if args.beam_size:
+        eng.set_beam_size(args.beam_size)
     if args.packed_encoder:
         eng.set_packed_encoder(True)
     if args.detect_language:
@@ -276,7 +304,7 @@ def _transcribe_many(args) -> int:
 
 def _transcribe_one(args) -> int:
     align_heads = _align_heads(args)
-    if align_heads is None:
+    if align_heads is None or not _check_beam(args):
         return 1
 
     from . import engine as E
@@ -313,6 +341,8 @@ def _transcribe_one(args) -> int:
         eng.set_audio_ctx(audio_ctx)
     if args.prompt:
         eng.set_initial_prompt(args.prompt)
+    if args.beam_size:
+        eng.set_beam_size(args.beam_size)
     if args.packed_encoder:
         eng.set_packed_encoder(True)
     if args.detect_language:

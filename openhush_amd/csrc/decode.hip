@@ -7,6 +7,7 @@
 //     16 output rows as consecutive 1-KiB blocks straight into VGPRs (no LDS round trip: the weights
 //     are used once; cdna_hip_programming.md "GEMV / M <= 16 decode weights"),
 //   * cross K/V are head-major [B][H][1500][64]: one (window, head) = 192 KiB contiguous per tensor.
+#include <algorithm>
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -1896,6 +1897,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(SamplerParams p
   // loads (clamped address, masked below), the bias behind ONE test of its pointer per batch.
   float v[BEAM_PER_THREAD];
   float lmax = -INFINITY;
+  // the first step of a search whose result a policy judges: the log-sum-exp state of the UNFILTERED row too (bias added, no
+  // mask), as sampler_kernel's want_raw branch keeps it; uniform over the workgroup
+  const bool want_raw = first && bp.nosp_prob != nullptr;
+  float rm = -INFINITY, rs = 0.f;
   constexpr int TB = BEAM_PER_THREAD / 2;
 #pragma unroll
   for (int hb = 0; hb < 2; ++hb) {
@@ -1914,6 +1919,16 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(SamplerParams p
       }
 #pragma unroll
       for (int u = 0; u < TB; ++u) vv[u] += bb[u];
+    }
+    if (want_raw) {
+#pragma unroll
+      for (int u = 0; u < TB; ++u) {
+        const int i = lo + tid + (hb * TB + u) * BEAM_THREADS;
+        const float x = vv[u];
+        if (i >= V) continue;
+        if (x > rm) { rs *= rm == -INFINITY ? 0.f : expf(rm - x); rm = x; }
+        rs += expf(x - rm);
+      }
     }
 #pragma unroll
     for (int u = 0; u < TB; ++u) {
@@ -1953,6 +1968,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(SamplerParams p
     }
   }
   const float sum_all = block_sum(s_all), sum_ts = block_sum(s_ts), text_max = block_max(t_max);
+  float raw_max = -INFINITY, raw_sum = 0.f;
+  if (want_raw) {
+    raw_max = block_max(rm);
+    raw_sum = block_sum(rm == -INFINITY ? 0.f : rs * expf(rm - raw_max));
+  }
   // The slice's K + 1 best per kind (0: text, 1: timestamps).  Every LANE first sorts the best six of its own 26 values per kind into
   // registers (one pass, branch-free insertion; equal values keep the lower index in front); a wave's K + 1 best are then K + 1
   // rounds over the lanes' list HEADS - a shuffle tree, the winner pops its list - and wave 0 takes the K + 1 best of the waves'
@@ -2034,6 +2054,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(SamplerParams p
       }
 #pragma unroll
     for (int k = 0; k < 28; ++k) __hip_atomic_store(slot + k, words[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (want_raw) {
+      __hip_atomic_store(slot + 28, __float_as_uint(raw_max), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(slot + 29, __float_as_uint(raw_sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned ticket = __hip_atomic_fetch_add(bp.tickets + row, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     sh_last = ticket == BEAM_SPLIT - 1;
@@ -2047,7 +2071,25 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(SamplerParams p
     const unsigned* all = bp.part + (int64_t)row * BEAM_SPLIT * BEAM_PART_WORDS;
     sh_w[tid / 28][tid % 28] = __hip_atomic_load(all + (tid / 28) * BEAM_PART_WORDS + tid % 28, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  __shared__ unsigned sh_raw[BEAM_SPLIT][2];
+  if (want_raw && tid >= BEAM_SPLIT * 28 && tid < BEAM_SPLIT * 30) {
+    const int k = tid - BEAM_SPLIT * 28;
+    sh_raw[k >> 1][k & 1] = __hip_atomic_load(bp.part + ((int64_t)row * BEAM_SPLIT + (k >> 1)) * BEAM_PART_WORDS + 28 + (k & 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   __syncthreads();
+  if (want_raw && tid == 0) {
+    // the slices' unfiltered states merged in slice order; the no-speech token's own (biased) logit against the row's log-sum-exp
+    float RM = -INFINITY, RS = 0.f;
+#pragma unroll
+    for (int q = 0; q < BEAM_SPLIT; ++q) RM = fmaxf(RM, __uint_as_float(sh_raw[q][0]));
+#pragma unroll
+    for (int q = 0; q < BEAM_SPLIT; ++q) {
+      const float mq = __uint_as_float(sh_raw[q][0]);
+      RS += mq == -INFINITY ? 0.f : __uint_as_float(sh_raw[q][1]) * expf(mq - RM);
+    }
+    const float x = lg[p.nosp] + (p.bias ? p.bias[p.nosp] : 0.f);
+    bp.nosp_prob[w] = expf(x - (RM + logf(RS)));
+  }
   float M = -INFINITY;
 #pragma unroll
   for (int q = 0; q < BEAM_SPLIT; ++q) M = fmaxf(M, __uint_as_float(sh_w[q][0]));
@@ -2096,6 +2138,7 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SamplerParams p, BeamP
   constexpr int MAXK = 5, MAXC = MAXK * (MAXK + 1);
   __shared__ int s_src[MAXK], s_tok[MAXK], s_nfin, s_fin_src[MAXC], s_fin_slot[MAXC];
   __shared__ float s_sum[MAXK], s_fin_sum[MAXC];
+  __shared__ float s_lp[MAXK], s_fin_lp[MAXC], s_clp[MAXC];    // a candidate's OWN log-probability (the plog history)
   __shared__ int s_done;
   const int w = blockIdx.x, tid = threadIdx.x, K = bp.K;
   if (bp.win_done[w]) return;
@@ -2112,7 +2155,9 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SamplerParams p, BeamP
     // at -inf, its end-of-text candidate could fill the finished pool and its continuations count as saved
     const bool dead = !first && !(bp.beam_sum[r] > -INFINITY);
     s_ctok[tid] = dead ? -1 : bp.cand_tok[(int64_t)r * (K + 1) + c];
-    s_csc[tid] = (first ? 0.f : bp.beam_sum[r]) + bp.cand_lp[(int64_t)r * (K + 1) + c];
+    const float own = bp.cand_lp[(int64_t)r * (K + 1) + c];
+    s_csc[tid] = (first ? 0.f : bp.beam_sum[r]) + own;
+    s_clp[tid] = own;
   }
   __syncthreads();
   // rank of a candidate = how many candidates come before it (score descending; ties: the earlier beam, then the more likely token =
@@ -2138,13 +2183,13 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SamplerParams p, BeamP
       const int src_o = o / (K + 1);
       if (s_ctok[o] == p.eot) {
         // newly finished, best first; the pool takes them while it has room (max_candidates = beam size)
-        if (fin_cnt < K) { s_fin_src[nfin] = src_o; s_fin_sum[nfin] = s_csc[o]; s_fin_slot[nfin] = fin_cnt; ++nfin; ++fin_cnt; }
+        if (fin_cnt < K) { s_fin_src[nfin] = src_o; s_fin_sum[nfin] = s_csc[o]; s_fin_lp[nfin] = s_clp[o]; s_fin_slot[nfin] = fin_cnt; ++nfin; ++fin_cnt; }
       } else {
-        s_src[saved] = src_o; s_tok[saved] = s_ctok[o]; s_sum[saved] = s_csc[o]; ++saved;
+        s_src[saved] = src_o; s_tok[saved] = s_ctok[o]; s_sum[saved] = s_csc[o]; s_lp[saved] = s_clp[o]; ++saved;
       }
     }
     // fewer live continuations than beams (everything else was end-of-text or forbidden): repeat the last one
-    for (int j = saved; j < K; ++j) { s_src[j] = saved ? s_src[saved - 1] : 0; s_tok[j] = saved ? s_tok[saved - 1] : p.eot; s_sum[j] = saved ? -INFINITY : -INFINITY; }
+    for (int j = saved; j < K; ++j) { s_src[j] = saved ? s_src[saved - 1] : 0; s_tok[j] = saved ? s_tok[saved - 1] : p.eot; s_sum[j] = saved ? -INFINITY : -INFINITY; s_lp[j] = -INFINITY; }
     s_nfin = nfin;
     bp.fin_cnt[w] = fin_cnt;
     const bool full = fin_cnt >= K;
@@ -2159,6 +2204,20 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SamplerParams p, BeamP
     bp.fin_tok[((int64_t)w * K + s_fin_slot[f]) * p.max_tokens + i] = p.tokens[(int64_t)(w * K + s_fin_src[f]) * p.max_tokens + i];
   }
   if (tid < s_nfin) { bp.fin_len[w * K + s_fin_slot[tid]] = n_cur; bp.fin_sum[w * K + s_fin_slot[tid]] = s_fin_sum[tid]; }
+  if (bp.plog) {
+    // the log-probability histories travel with the tokens: the same flat-index gathers over rows of max_tokens + 1 values
+    const int64_t ls = p.max_tokens + 1;
+    for (int idx = tid; idx < s_nfin * n_cur; idx += 256) {
+      const int f = idx / n_cur, i = idx - f * n_cur;
+      bp.fin_plog[((int64_t)w * K + s_fin_slot[f]) * ls + i] = bp.plog[(int64_t)(w * K + s_fin_src[f]) * ls + i];
+    }
+    if (tid < s_nfin) bp.fin_plog[((int64_t)w * K + s_fin_slot[tid]) * ls + n_cur] = s_fin_lp[tid];      // end-of-text's own
+    for (int idx = tid; idx < K * n_cur; idx += 256) {
+      const int j = idx / n_cur, i = idx - j * n_cur;
+      bp.plog_next[(int64_t)(w * K + j) * ls + i] = bp.plog[(int64_t)(w * K + s_src[j]) * ls + i];
+    }
+    if (tid < K) bp.plog_next[(int64_t)(w * K + tid) * ls + n_cur] = s_lp[tid];     // not the cumulative score; -inf in a dead row
+  }
   // new beams: history and kv_slot rows are gathered from the source beams into the other half of the double buffers
   for (int idx = tid; idx < K * n_cur; idx += 256) {
     const int j = idx / n_cur, i = idx - j * n_cur;
@@ -2200,7 +2259,86 @@ void launch_kv_prefix_move(void* self_kv, int planes, int max_batch, int n_head,
   HIP_CHECK(hipGetLastError());
 }
 
+// The final ranking of window w, shared by the device kernel and its host twin (the loop ohw_beam_search runs on the host):
+// candidates are the pool's entries in pool order, then - while there are fewer than K - the live beams by descending sum
+// (equal sums: the lower beam index; -inf skipped); score = sum / max(1, n) in fp32, correctly rounded; the first strict
+// maximum wins.  -> the winner as (from_pool, row, n, sum), row < 0: no candidate at all.
+struct BeamPick { int from_pool, row, n; float sum; };
+__host__ __device__ inline BeamPick beam_pick(int K, int w, int fin_cnt, const int32_t* fin_len, const float* fin_sum, const float* live_sum, int n_cur) {
+  BeamPick best{0, -1, 0, 0.f};
+  float best_score = -INFINITY;
+  int n_cand = 0;
+  auto offer = [&](int from_pool, int row, int n, float sum) {
+    const float score = sum / (float)(n > 1 ? n : 1);
+    if (best.row < 0 || score > best_score) { best = BeamPick{from_pool, row, n, sum}; best_score = score; }
+    ++n_cand;
+  };
+  for (int f = 0; f < fin_cnt; ++f) offer(1, w * K + f, fin_len[w * K + f], fin_sum[w * K + f]);
+  // the a-th live beam of the stable descending order: the one that exactly a others come before
+  for (int a = 0; a < K && n_cand < K; ++a)
+    for (int j = 0; j < K; ++j) {
+      const float sj = live_sum[w * K + j];
+      int before = 0;
+      for (int o = 0; o < K; ++o) {
+        const float so = live_sum[w * K + o];
+        if (so > sj || (o < j && !(sj > so))) ++before;
+      }
+      if (before != a) continue;
+      if (sj > -INFINITY) offer(0, w * K + j, n_cur, sj);
+      break;
+    }
+  return best;
+}
+
+__global__ __launch_bounds__(64) void beam_finish_kernel(BeamFinishParams f) {
+  __shared__ int s_pool, s_row, s_n, s_len;
+  const int w = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) {
+    const int fin_cnt = f.fin_cnt[w];
+    const BeamPick b = beam_pick(f.K, w, fin_cnt, f.fin_len, f.fin_sum, f.beam_sum, f.n_cur[w]);
+    const int n = b.row < 0 ? 0 : (b.n < f.max_tokens ? b.n : f.max_tokens);
+    s_pool = b.from_pool; s_row = b.row; s_n = n; s_len = b.n;
+    f.out_n[w] = n;
+    f.out_sum[w] = b.row < 0 ? 0.f : b.sum;
+    f.out_eot[w] = b.row < 0 ? 0 : b.from_pool;
+    f.out_nfin[w] = fin_cnt;
+  }
+  __syncthreads();
+  if (s_row < 0) return;
+  const int n = s_n;
+  const int32_t* src_t = (s_pool ? f.fin_tok : f.tokens) + (int64_t)s_row * f.stride;
+  const float* src_l = (s_pool ? f.fin_plog : f.plog) + (int64_t)s_row * (f.stride + 1);
+  for (int i = tid; i < n; i += 64) {
+    f.out_tok[(int64_t)w * f.stride + i] = src_t[i];
+    f.out_lp[(int64_t)w * (f.stride + 1) + i] = src_l[i];
+  }
+  if (tid == 0 && s_pool) f.out_lp[(int64_t)w * (f.stride + 1) + n] = src_l[s_len];      // end-of-text's, after the kept tokens
+}
+void launch_beam_finish(const BeamFinishParams& f, int n_windows, hipStream_t s) {
+  if (f.K < 2 || f.K > 5 || f.stride < 1 || f.max_tokens < 0 || n_windows < 1) throw Error(OHW_E_INVALID_ARG, "beam finish: beam size, stride or clip out of range");
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(n_windows), dim3(64), 0, s, f);
+  HIP_CHECK(hipGetLastError());
+}
+void beam_finish_host(const BeamFinishParams& f, int n_windows) {
+  for (int w = 0; w < n_windows; ++w) {
+    const int fin_cnt = f.fin_cnt[w];
+    const BeamPick b = beam_pick(f.K, w, fin_cnt, f.fin_len, f.fin_sum, f.beam_sum, f.n_cur[w]);
+    const int n = b.row < 0 ? 0 : std::min(b.n, f.max_tokens);
+    f.out_n[w] = n;
+    f.out_sum[w] = b.row < 0 ? 0.f : b.sum;
+    f.out_eot[w] = b.row < 0 ? 0 : b.from_pool;
+    f.out_nfin[w] = fin_cnt;
+    if (b.row < 0) continue;
+    const int32_t* src_t = (b.from_pool ? f.fin_tok : f.tokens) + (int64_t)b.row * f.stride;
+    const float* src_l = (b.from_pool ? f.fin_plog : f.plog) + (int64_t)b.row * (f.stride + 1);
+    std::copy(src_t, src_t + n, f.out_tok + (int64_t)w * f.stride);
+    std::copy(src_l, src_l + n, f.out_lp + (int64_t)w * (f.stride + 1));
+    if (b.from_pool) f.out_lp[(int64_t)w * (f.stride + 1) + n] = src_l[b.n];
+  }
+}
+
 void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_windows, int first, hipStream_t s) {
+  if (bp.plog && (!bp.plog_next || !bp.fin_plog)) throw Error(OHW_E_INVALID_ARG, "beam search: the log-probability history needs both halves and the pool's rows");
   if (bp.K < 2 || bp.K > 5) throw Error(OHW_E_INVALID_ARG, "beam search: beam size must be in 2..5");
   if (p.n_vocab > BEAM_SPLIT * BEAM_THREADS * BEAM_PER_THREAD) throw Error(OHW_E_INVALID_ARG, "beam search: vocabulary too large");
   if (!bp.part || !bp.tickets) throw Error(OHW_E_INVALID_ARG, "beam search: the split top-k needs its slice buffers");

@@ -183,11 +183,14 @@ struct ohw_state {
   DevBuf step_tok, n_past, tokens, n_cur, next_tok, done, n_done, sum_lp;
   // beam search (made on first use): candidates, cumulative scores, the kv_slot / token-history double buffers, finished pool
   DevBuf bm_cand_lp, bm_cand_tok, bm_sum, bm_slot[2], bm_tok2, bm_ncur, bm_npast, bm_done, bm_fin_cnt, bm_fin_tok, bm_fin_len, bm_fin_sum, bm_part, bm_ticket;
+  // ohw_beam_search_ex only (made on its first use): per-token log-probability histories (double buffer, pool), the device-side
+  // ranking's result rows
+  DevBuf bm_plog[2], bm_fin_plog, bm_out_tok, bm_out_lp, bm_out_n, bm_out_sum, bm_out_eot, bm_out_nfin, bm_nosp;
   // one entry = the PAIR of graphs of a (windows, beam size, sampler parameters, CU budget, cross-attention variant) key: the
   // odd and the even iteration (the token-history and kv_slot double buffers alternate); made, looked up and evicted together,
   // so a call never holds an exec of an entry it then evicts
-  struct BeamGraph { hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr}; int windows = 0, K = 0, cus = 0, t_len = 0; bool invariant = false, persist = false, var = false; SamplerParams spar; };
-  std::vector<BeamGraph> beam_graphs;
+  struct BeamGraph { hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr}; int windows = 0, K = 0, cus = 0, t_len = 0; bool invariant = false, persist = false, var = false, lp = false; SamplerParams spar; };
+  std::vector<BeamGraph> beam_graphs;      // lp: the pair of ohw_beam_search_ex (log-probability history on: other pointers baked in)
   // the persistent small-batch decoder step (decode_persist.hip): per-layer pointer table, granule arena, epoch / abort words
   DevBuf ps_layers, ps_gran, ps_words;
   PersistParams ps_layout{};         // region offsets of the arena
@@ -1514,11 +1517,33 @@ static void alloc_beam_buffers(ohw_state* st) {
   st->bm_fin_cnt.alloc(MB * 4, true); st->bm_fin_tok.alloc(MB * MT * 4, true); st->bm_fin_len.alloc(MB * 4, true);
   st->bm_fin_sum.alloc(MB * 4, true);
   st->bm_part.alloc(MB * BEAM_SPLIT * BEAM_PART_WORDS * 4, true); st->bm_ticket.alloc(MB * 4, true);
+  st->bm_plog[0].alloc(MB * (MT + 1) * 4, true); st->bm_plog[1].alloc(MB * (MT + 1) * 4, true); st->bm_fin_plog.alloc(MB * (MT + 1) * 4, true);
+  st->bm_out_tok.alloc(MB * MT * 4, true); st->bm_out_lp.alloc(MB * (MT + 1) * 4, true);
+  for (DevBuf* b : {&st->bm_out_n, &st->bm_out_sum, &st->bm_out_eot, &st->bm_out_nfin, &st->bm_nosp}) b->alloc(MB * 4, true);
 }
 
-int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, int beam_size, int max_tokens, const ohw_beam_result* res) {
-  return guard([&] {
-    if (!st || !sp || !res || !res->tokens || !res->n_tokens) throw Error(OHW_E_INVALID_ARG, "null argument");
+// the device-side ranking on a state's beam buffers; last_q: the half of the double buffers that holds the live beams
+static BeamFinishParams finish_params(ohw_state* st, int K, int max_tokens, int last_q) {
+  BeamFinishParams f{};
+  f.K = K; f.stride = st->max_tokens; f.max_tokens = std::min(max_tokens, st->max_tokens);
+  f.fin_cnt = st->bm_fin_cnt.as<int32_t>(); f.fin_len = st->bm_fin_len.as<int32_t>(); f.fin_tok = st->bm_fin_tok.as<int32_t>();
+  f.n_cur = st->bm_ncur.as<int32_t>(); f.tokens = last_q ? st->bm_tok2.as<int32_t>() : st->tokens.as<int32_t>();
+  f.fin_sum = st->bm_fin_sum.as<float>(); f.fin_plog = st->bm_fin_plog.as<float>(); f.beam_sum = st->bm_sum.as<float>();
+  f.plog = st->bm_plog[last_q].as<float>();
+  f.out_tok = st->bm_out_tok.as<int32_t>(); f.out_n = st->bm_out_n.as<int32_t>(); f.out_eot = st->bm_out_eot.as<int32_t>();
+  f.out_nfin = st->bm_out_nfin.as<int32_t>(); f.out_lp = st->bm_out_lp.as<float>(); f.out_sum = st->bm_out_sum.as<float>();
+  return f;
+}
+
+// ohw_beam_search (ex null: no log-probability history, the final ranking on the host) and ohw_beam_search_ex (ex set: res is
+// unused) are ONE search; what differs is which pointers the step kernels get and where the winner is picked
+static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_windows, int beam_size, int max_tokens, const ohw_beam_result* res,
+                            const ohw_beam_result_ex* ex) {
+  {
+    if (!st || !sp) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (ex ? (!ex->tokens || !ex->n_tokens) : (!res || !res->tokens || !res->n_tokens)) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (max_tokens < 0) throw Error(OHW_E_INVALID_ARG, "beam search: max_tokens < 0");
+    const bool lp = ex != nullptr;
     const int W = n_windows, K = beam_size, R = W * K;
     if (W < 1 || W != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "beam search: n_windows must equal the batch of the last ohw_encode");
     if (K < 2 || K > 5) throw Error(OHW_E_INVALID_ARG, "beam search: beam_size must be in 2..5");
@@ -1569,6 +1594,10 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
       bp->fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp->fin_tok = st->bm_fin_tok.as<int32_t>(); bp->fin_len = st->bm_fin_len.as<int32_t>();
       bp->fin_sum = st->bm_fin_sum.as<float>();
       bp->part = st->bm_part.as<unsigned>(); bp->tickets = st->bm_ticket.as<unsigned>();
+      if (lp) {
+        bp->plog = st->bm_plog[q].as<float>(); bp->plog_next = st->bm_plog[q ^ 1].as<float>(); bp->fin_plog = st->bm_fin_plog.as<float>();
+        bp->nosp_prob = st->bm_nosp.as<float>();      // read by the first step alone
+      }
     };
     int steps = 0, last_q = 1;
     Dispatch::run(c->dtype, [&](auto* tag) {
@@ -1591,7 +1620,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
       hipGraphExec_t exec[2] = {nullptr, nullptr};
       if (use_graph) {
         for (auto& g : st->beam_graphs)
-          if (g.windows == W && g.K == K && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant && g.persist == st->persist && std::memcmp(&g.spar, &base, sizeof base) == 0) {
+          if (g.windows == W && g.K == K && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant && g.persist == st->persist && g.lp == lp && std::memcmp(&g.spar, &base, sizeof base) == 0) {
             exec[0] = g.exec[0]; exec[1] = g.exec[1];
           }
       }
@@ -1644,7 +1673,7 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
           drop();
           throw;
         }
-        ng.windows = W; ng.K = K; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.var = st->enc_var; ng.invariant = st->batch_invariant; ng.persist = st->persist;
+        ng.windows = W; ng.K = K; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.var = st->enc_var; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.lp = lp;
         std::memcpy(&ng.spar, &base, sizeof base);
         st->beam_graphs.push_back(ng);
         ++st->beam_captures;
@@ -1672,6 +1701,24 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
         }
       }
     });
+    if (lp) {
+      // the ranking on the device (beam_finish_kernel restates the host loop below); W rows come back
+      launch_beam_finish(finish_params(st, K, max_tokens, last_q), W, s);
+      HIP_CHECK(hipEventRecord(st->ev[5], s));
+      const int n_copy = std::min(max_tokens, MT);
+      if (n_copy > 0) HIP_CHECK(hipMemcpy2DAsync(ex->tokens, (size_t)max_tokens * 4, st->bm_out_tok.p, (size_t)MT * 4, (size_t)n_copy * 4, (size_t)W, hipMemcpyDeviceToHost, s));
+      if (ex->token_logprobs)
+        HIP_CHECK(hipMemcpy2DAsync(ex->token_logprobs, (size_t)(max_tokens + 1) * 4, st->bm_out_lp.p, (size_t)(MT + 1) * 4, (size_t)(n_copy + 1) * 4, (size_t)W, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(ex->n_tokens, st->bm_out_n.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+      if (ex->sum_logprob) HIP_CHECK(hipMemcpyAsync(ex->sum_logprob, st->bm_out_sum.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+      if (ex->n_finished) HIP_CHECK(hipMemcpyAsync(ex->n_finished, st->bm_out_nfin.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+      if (ex->ended_by_eot) HIP_CHECK(hipMemcpyAsync(ex->ended_by_eot, st->bm_out_eot.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+      if (ex->no_speech_prob) HIP_CHECK(hipMemcpyAsync(ex->no_speech_prob, st->bm_nosp.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      persist_check(st);
+      st->last.decode_steps = steps;
+      return;
+    }
     HIP_CHECK(hipEventRecord(st->ev[5], s));
     // read the finished pools and the live beams back; rank on the host: cumulative log-probability / length
     std::vector<int32_t> fin_cnt((size_t)W), fin_len((size_t)R), fin_tok((size_t)R * MT), live_tok((size_t)R * MT), ncur((size_t)W);
@@ -1713,6 +1760,16 @@ int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, i
       if (res->n_finished) res->n_finished[w] = fin_cnt[(size_t)w];
     }
     st->last.decode_steps = steps;
+  }
+}
+
+int ohw_beam_search(ohw_state* st, const ohw_sample_params* sp, int n_windows, int beam_size, int max_tokens, const ohw_beam_result* res) {
+  return guard([&] { beam_search_run(st, sp, n_windows, beam_size, max_tokens, res, nullptr); });
+}
+int ohw_beam_search_ex(ohw_state* st, const ohw_sample_params* sp, int n_windows, int beam_size, int max_tokens, const ohw_beam_result_ex* out) {
+  return guard([&] {
+    if (!out) throw Error(OHW_E_INVALID_ARG, "null argument");
+    beam_search_run(st, sp, n_windows, beam_size, max_tokens, nullptr, out);
   });
 }
 
@@ -2035,9 +2092,12 @@ int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* sp, const float* lo
 
 // test entry: one beam step on caller-supplied rows and state (include/ohw.h).  Everything is range-checked first: the
 // kernels index with these values.
-int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_beam_io* io) {
-  return guard([&] {
+// x: the log-probability history and the no-speech probability of ohw_dbg_beam_step_ex, or null
+static void dbg_beam_step_run(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_beam_io* io, const ohw_dbg_beam_io_ex* x) {
+  {
     if (!st || !sp || !io) throw Error(OHW_E_INVALID_ARG, "null argument");
+    const bool lp = x && x->plog;
+    if (lp && (!x->plog_next || !x->fin_plog)) throw Error(OHW_E_INVALID_ARG, "dbg_beam_step_ex: plog needs plog_next and fin_plog");
     if (!io->logits || !io->tokens || !io->kv_slot || !io->n_cur || !io->n_past_w || !io->win_done || !io->beam_sum || !io->fin_cnt ||
         !io->fin_tok || !io->fin_len || !io->fin_sum || !io->cand_tok || !io->cand_lp || !io->tokens_next || !io->kv_slot_next ||
         !io->next_tok || !io->n_past || !io->n_done || !io->tickets_out)
@@ -2101,6 +2161,17 @@ int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_
     HIP_CHECK(hipMemcpyAsync(st->bm_fin_len.p, fin_len.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(st->bm_fin_sum.p, fin_sum.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
+    std::vector<float> fin_plog;
+    const std::vector<float> sent_lp(lp ? (size_t)R * (MT + 1) : (size_t)W, OHW_DBG_SENTINEL_F32);
+    if (lp) {
+      fin_plog.assign(x->fin_plog, x->fin_plog + (size_t)R * (MT + 1));
+      for (int w = 0; w < W; ++w)
+        for (int f = io->fin_cnt[w]; f < K; ++f) std::fill_n(&fin_plog[(size_t)(w * K + f) * (MT + 1)], (size_t)MT + 1, OHW_DBG_SENTINEL_F32);
+      HIP_CHECK(hipMemcpyAsync(st->bm_plog[q].p, x->plog, (size_t)R * (MT + 1) * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->bm_plog[q ^ 1].p, sent_lp.data(), (size_t)R * (MT + 1) * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->bm_fin_plog.p, fin_plog.data(), (size_t)R * (MT + 1) * 4, hipMemcpyHostToDevice, s));
+    }
+    if (x && x->nosp_prob) HIP_CHECK(hipMemcpyAsync(st->bm_nosp.p, sent_lp.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
     SamplerParams p;
     fill_sampler(st, sp, R, &p);
     p.tokens = tokbuf[q];
@@ -2111,7 +2182,14 @@ int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_
     bp.fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp.fin_tok = st->bm_fin_tok.as<int32_t>(); bp.fin_len = st->bm_fin_len.as<int32_t>();
     bp.fin_sum = st->bm_fin_sum.as<float>();
     bp.part = st->bm_part.as<unsigned>(); bp.tickets = st->bm_ticket.as<unsigned>();
+    if (lp) { bp.plog = st->bm_plog[q].as<float>(); bp.plog_next = st->bm_plog[q ^ 1].as<float>(); bp.fin_plog = st->bm_fin_plog.as<float>(); }
+    if (x && x->nosp_prob) bp.nosp_prob = st->bm_nosp.as<float>();
     launch_beam_step(p, bp, W, first, s);
+    if (lp) {
+      HIP_CHECK(hipMemcpyAsync(x->plog_next, st->bm_plog[q ^ 1].p, (size_t)R * (MT + 1) * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(x->fin_plog, st->bm_fin_plog.p, (size_t)R * (MT + 1) * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (x && x->nosp_prob) HIP_CHECK(hipMemcpyAsync(x->nosp_prob, st->bm_nosp.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(io->cand_tok, st->bm_cand_tok.p, (size_t)R * K1 * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(io->cand_lp, st->bm_cand_lp.p, (size_t)R * K1 * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(io->tokens_next, tokbuf[q ^ 1], (size_t)R * MT * 4, hipMemcpyDeviceToHost, s));
@@ -2128,6 +2206,97 @@ int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_
     HIP_CHECK(hipMemcpyAsync(io->fin_tok, st->bm_fin_tok.p, (size_t)R * MT * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(io->fin_len, st->bm_fin_len.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(io->fin_sum, st->bm_fin_sum.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+}
+int ohw_dbg_beam_step(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_beam_io* io) {
+  return guard([&] { dbg_beam_step_run(st, sp, io, nullptr); });
+}
+int ohw_dbg_beam_step_ex(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_beam_io_ex* io) {
+  return guard([&] {
+    if (!io) throw Error(OHW_E_INVALID_ARG, "null argument");
+    dbg_beam_step_run(st, sp, &io->base, io);
+  });
+}
+
+// the range checks of the two finish entries: the ranking indexes with these values
+static void check_beam_finish_io(const ohw_beam_finish_io* io) {
+  if (!io) throw Error(OHW_E_INVALID_ARG, "null argument");
+  if (!io->fin_cnt || !io->fin_len || !io->fin_sum || !io->fin_tok || !io->fin_plog || !io->n_cur || !io->tokens || !io->plog || !io->beam_sum ||
+      !io->out_tokens || !io->out_logprobs || !io->n_tokens || !io->sum_logprob || !io->ended_by_eot || !io->n_finished)
+    throw Error(OHW_E_INVALID_ARG, "beam finish: null array");
+  const int K = io->K, W = io->W;
+  if (K < 2 || K > 5 || W < 1) throw Error(OHW_E_INVALID_ARG, "beam finish: K must be in 2..5 and W >= 1");
+  if (io->stride < 1 || io->max_tokens < 0 || io->max_tokens > io->stride) throw Error(OHW_E_INVALID_ARG, "beam finish: need 1 <= stride and 0 <= max_tokens <= stride");
+  for (int w = 0; w < W; ++w) {
+    if (io->fin_cnt[w] < 0 || io->fin_cnt[w] > K) throw Error(OHW_E_INVALID_ARG, "beam finish: fin_cnt out of range");
+    for (int f = 0; f < io->fin_cnt[w]; ++f)
+      if (io->fin_len[w * K + f] < 0 || io->fin_len[w * K + f] > io->stride) throw Error(OHW_E_INVALID_ARG, "beam finish: fin_len out of range");
+    if (io->n_cur[w] < 0 || io->n_cur[w] > io->stride) throw Error(OHW_E_INVALID_ARG, "beam finish: n_cur out of range");
+  }
+}
+static void fill_beam_finish_out(const ohw_beam_finish_io* io) {
+  const size_t W = (size_t)io->W, n = (size_t)io->max_tokens;
+  std::fill_n(io->out_tokens, W * n, OHW_DBG_SENTINEL_I32); std::fill_n(io->out_logprobs, W * (n + 1), OHW_DBG_SENTINEL_F32);
+  std::fill_n(io->n_tokens, W, OHW_DBG_SENTINEL_I32); std::fill_n(io->sum_logprob, W, OHW_DBG_SENTINEL_F32);
+  std::fill_n(io->ended_by_eot, W, OHW_DBG_SENTINEL_I32); std::fill_n(io->n_finished, W, OHW_DBG_SENTINEL_I32);
+}
+
+int ohw_beam_finish_host(const ohw_beam_finish_io* io) {
+  return guard([&] {
+    check_beam_finish_io(io);
+    fill_beam_finish_out(io);
+    // the rule writes rows of the input's stride; the caller's rows are max_tokens (+ 1) long
+    const size_t W = (size_t)io->W, S = (size_t)io->stride, n = (size_t)io->max_tokens;
+    std::vector<int32_t> tok(W * S, OHW_DBG_SENTINEL_I32);
+    std::vector<float> lp(W * (S + 1), OHW_DBG_SENTINEL_F32);
+    BeamFinishParams f{};
+    f.K = io->K; f.stride = io->stride; f.max_tokens = io->max_tokens;
+    f.fin_cnt = io->fin_cnt; f.fin_len = io->fin_len; f.fin_tok = io->fin_tok; f.n_cur = io->n_cur; f.tokens = io->tokens;
+    f.fin_sum = io->fin_sum; f.fin_plog = io->fin_plog; f.beam_sum = io->beam_sum; f.plog = io->plog;
+    f.out_tok = tok.data(); f.out_n = io->n_tokens; f.out_eot = io->ended_by_eot; f.out_nfin = io->n_finished; f.out_lp = lp.data(); f.out_sum = io->sum_logprob;
+    beam_finish_host(f, io->W);
+    for (size_t w = 0; w < W; ++w) {
+      std::copy_n(&tok[w * S], n, io->out_tokens + w * n);
+      std::copy_n(&lp[w * (S + 1)], n + 1, io->out_logprobs + w * (n + 1));
+    }
+  });
+}
+
+int ohw_dbg_beam_finish(ohw_state* st, const ohw_beam_finish_io* io) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    check_beam_finish_io(io);
+    const int K = io->K, W = io->W, R = W * K, MT = st->max_tokens;
+    if ((int64_t)W * K > st->max_batch) throw Error(OHW_E_INVALID_ARG, "dbg_beam_finish: W * K exceeds the state's max_batch");
+    if (io->stride != MT) throw Error(OHW_E_INVALID_ARG, "dbg_beam_finish: stride must be the state's token capacity");
+    fill_beam_finish_out(io);
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    alloc_beam_buffers(st);
+    const std::vector<int32_t> sent_i((size_t)W * MT, OHW_DBG_SENTINEL_I32);
+    const std::vector<float> sent_f((size_t)W * (MT + 1), OHW_DBG_SENTINEL_F32);
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_cnt.p, io->fin_cnt, (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_len.p, io->fin_len, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_sum.p, io->fin_sum, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_tok.p, io->fin_tok, (size_t)R * MT * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_fin_plog.p, io->fin_plog, (size_t)R * (MT + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_ncur.p, io->n_cur, (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->tokens.p, io->tokens, (size_t)R * MT * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_plog[0].p, io->plog, (size_t)R * (MT + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_sum.p, io->beam_sum, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_out_tok.p, sent_i.data(), (size_t)W * MT * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_out_lp.p, sent_f.data(), (size_t)W * (MT + 1) * 4, hipMemcpyHostToDevice, s));
+    for (DevBuf* b : {&st->bm_out_n, &st->bm_out_eot, &st->bm_out_nfin}) HIP_CHECK(hipMemcpyAsync(b->p, sent_i.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->bm_out_sum.p, sent_f.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+    launch_beam_finish(finish_params(st, K, io->max_tokens, 0), W, s);
+    const size_t n = (size_t)io->max_tokens;
+    if (n) HIP_CHECK(hipMemcpy2DAsync(io->out_tokens, n * 4, st->bm_out_tok.p, (size_t)MT * 4, n * 4, (size_t)W, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpy2DAsync(io->out_logprobs, (n + 1) * 4, st->bm_out_lp.p, (size_t)(MT + 1) * 4, (n + 1) * 4, (size_t)W, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_tokens, st->bm_out_n.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->sum_logprob, st->bm_out_sum.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->ended_by_eot, st->bm_out_eot.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_finished, st->bm_out_nfin.p, (size_t)W * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   });
 }

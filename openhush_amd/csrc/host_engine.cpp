@@ -263,6 +263,11 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
     const int n_max = sp.n_max;
     const ohw_decode_policy& pol = e->policy;
     const std::vector<float> temps = ladder(pol);
+    // ohw_engine_set_beam_size: the T = 0 pass is a beam search of K rows per window, so a decode batch holds max_batch / K
+    // windows; everything that cuts batches below takes WB.  Beam calls run one batch after the other on the engine's own state
+    const int beam_K = e->beam_size;
+    const int WB = beam_K > 0 ? e->max_batch / beam_K : e->max_batch;
+    if (WB < 1) throw Error(OHW_E_INVALID_ARG, "transcribe: beam size exceeds max_batch");
     int32_t prompt[8];
     int n_prompt = 0;
     prompt[n_prompt++] = tk.sot;
@@ -316,6 +321,42 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         r.pending = needs_fallback(r.ev, pol, r.nosp, temps.empty());
         trace(sc, w0 + b, 0.f, r.tok);
       }
+    };
+    // T = 0 under ohw_engine_set_beam_size: ohw_beam_search_ex in greedy_t0's place, filling the same WindowRun.  The winner (with
+    // end-of-text when it came from the finished pool) is judged by evaluate_sequence and cut at n_sampled, as device_pass cuts a
+    // sampled pass: beam search is not causal, so whisper.cpp's loop exits are applied to the winner after the search (a
+    // definition), not to every decoder during it.  From there on it is the greedy pass: needs_fallback,
+    // t0_failed, the no-speech rule, n_keep, segments, alignment.
+    // The ladder that may follow is unchanged and safe after a search: it decodes rows 0 .. B-1 from position 0 (prefill,
+    // prompt, steps), reads a row's self K/V only below the position it has itself written in that pass, without a kv_slot
+    // table, and reads cross K/V by WINDOW index, which the search never moves - nothing it relies on is left in beam layout
+    // (row w * K); its entries re-initialise n_past, the token history and the done flags themselves
+    auto beam_t0 = [&](Scratch& sc, ohw_state* st, int B, const int* seek, const int* seek_end, int64_t w0) {
+      apply_prompt(st, B);
+      ohw_beam_result_ex br{};
+      br.tokens = sc.toks.data(); br.n_tokens = sc.ntok.data(); br.token_logprobs = sc.lps.data(); br.ended_by_eot = sc.eot.data();
+      br.no_speech_prob = sc.nsp.data();
+      check(ohw_beam_search_ex(st, &sp, B, beam_K, max_tok, &br));
+      sc.runs.assign((size_t)B, WindowRun());
+      for (int b = 0; b < B; ++b) {
+        WindowRun& r = sc.runs[(size_t)b];
+        const int nt = sc.ntok[(size_t)b] + (sc.eot[(size_t)b] ? 1 : 0);
+        r.tok.assign(&sc.toks[(size_t)b * max_tok], &sc.toks[(size_t)b * max_tok] + sc.ntok[(size_t)b]);
+        if (sc.eot[(size_t)b]) r.tok.push_back(tk.eot);
+        r.plog.assign(&sc.lps[(size_t)b * (max_tok + 1)], &sc.lps[(size_t)b * (max_tok + 1)] + nt);
+        r.nosp = sc.nsp[(size_t)b];
+        const SeqEval ev = evaluate_sequence(tk, r.tok.data(), r.plog.data(), nt, seek[b], seek_end[b], n_max, sp.no_timestamps != 0, e->window_mode);
+        r.tok.resize((size_t)ev.n_sampled);
+        r.plog.resize((size_t)ev.n_sampled);
+        r.ev = evaluate_sequence(tk, r.tok.data(), r.plog.data(), (int)r.tok.size(), seek[b], seek_end[b], n_max, sp.no_timestamps != 0, e->window_mode);
+        r.t0_failed = needs_fallback(r.ev, pol, r.nosp, false);
+        r.pending = needs_fallback(r.ev, pol, r.nosp, temps.empty());
+        trace(sc, w0 + b, 0.f, r.tok);
+      }
+    };
+    auto pass_t0 = [&](Scratch& sc, ohw_state* st, int B, const int* seek, const int* seek_end, int64_t w0) {
+      if (beam_K > 0) beam_t0(sc, st, B, seek, seek_end, w0);
+      else greedy_t0(sc, st, B, seek, seek_end, w0);
     };
     // the temperature ladder for the windows of a batch whose pass failed the acceptance test, drawn from std::mt19937 through
     // std::discrete_distribution as whisper.cpp's decoders do, on the pending windows' resident cross K/V.  By default the
@@ -530,7 +571,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
     auto decode_windows = [&](Scratch& sc, ohw_state* st, int64_t w0, int B, const int32_t* nsb) {
       std::vector<int> zero((size_t)B, 0), ends((size_t)B);
       for (int b = 0; b < B; ++b) ends[(size_t)b] = mel_frames(nsb[b]);
-      greedy_t0(sc, st, B, zero.data(), ends.data(), w0);
+      pass_t0(sc, st, B, zero.data(), ends.data(), w0);
       for (int b = 0; b < B; ++b) if (ends[(size_t)b] <= 100) { sc.runs[(size_t)b] = WindowRun(); sc.runs[(size_t)b].ev.result_len = 0; }
       bool any = false;
       for (int b = 0; b < B; ++b) any = any || sc.runs[(size_t)b].pending;
@@ -548,7 +589,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       // frame count as the end of the audio, the full audio context (what the single loop runs anything longer than a window
       // at).  The caller has set e->window_mode to OHW_WINDOW_SEEK for the call.
       e->batch_records.assign((size_t)n_recs, ohw_engine::BatchRecord());
-      const int MB = e->max_batch;
+      const int MB = WB;
       std::vector<int64_t> lens((size_t)n_recs);
       for (int i = 0; i < n_recs; ++i) lens[(size_t)i] = recs[i].n;
       ohw_seek_sched* sched_raw = nullptr;
@@ -615,7 +656,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
             for (int b = 0; b < B; ++b) rec_lang[(size_t)r_rec[(size_t)b]] = batch_lang[(size_t)b];
           }
         }
-        greedy_t0(sc, e->state, B, seeks.data(), ends.data(), 0);
+        pass_t0(sc, e->state, B, seeks.data(), ends.data(), 0);
         run_ladder(sc, e->state, B, seeks.data(), ends.data(), 0, round_rngs);
         align_runs(sc, e->state, B, frames.data());
         sc.trace.clear();
@@ -652,7 +693,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       e->batch_records.assign((size_t)n_recs, ohw_engine::BatchRecord());
       std::vector<int64_t> lens((size_t)n_recs);
       for (int i = 0; i < n_recs; ++i) lens[(size_t)i] = recs[i].n;
-      const int MB = e->max_batch, n_b = (n_recs + MB - 1) / MB;
+      const int MB = WB, n_b = (n_recs + MB - 1) / MB;
       std::vector<int32_t> order((size_t)n_recs), rctx((size_t)n_recs), env((size_t)n_b);
       const int prc = ohw_batch_plan(lens.data(), n_recs, MB, e->audio_ctx, order.data(), rctx.data(), env.data());
       if (prc != OHW_OK) throw Error(prc, g_last_error);
@@ -740,7 +781,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         check_window_fits(w, std::min<int64_t>(CHUNK_SAMPLES, n - (int64_t)seek * HOP));
         check(ohw_mel_seek(e->state, &seek32, 1, nullptr));      // 3000 frames of the recording-wide spectrogram
         check(ohw_encode(e->state, 1));
-        greedy_t0(sc, e->state, 1, &seek, &seek_end, w);
+        pass_t0(sc, e->state, 1, &seek, &seek_end, w);
         run_ladder(sc, e->state, 1, &seek, &seek_end, w, rngs.v);
         const int win_frames = std::min(CHUNK_FRAMES, seek_end - seek);
         align_runs(sc, e->state, 1, &win_frames);
@@ -760,8 +801,8 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       const int64_t n_win = n_win_rec > win_first ? (n_win_rec - win_first + win_step - 1) / win_step : 0;
       auto rec_win = [&](int64_t k) { return win_first + k * win_step; };
       for (int64_t k = 0; k < n_win; ++k) check_window_fits(rec_win(k), std::min<int64_t>(CHUNK_SAMPLES, n - rec_win(k) * CHUNK_SAMPLES));
-      const int64_t n_batches = (n_win + e->max_batch - 1) / e->max_batch;
-      auto batch_of = [&](int64_t bi) { return (int)std::min<int64_t>(e->max_batch, n_win - bi * e->max_batch); };
+      const int64_t n_batches = (n_win + WB - 1) / WB;
+      auto batch_of = [&](int64_t bi) { return (int)std::min<int64_t>(WB, n_win - bi * WB); };
       // windows w0 .. w0 + B of the recording into st: each cut on its own (its own `full()` call), or cut from the spectrogram
       // of the whole recording (FIXED_RECORDING_MEL: st reads the recording e->state holds)
       const bool rec_mel = e->window_mode == OHW_WINDOW_FIXED_RECORDING_MEL;
@@ -773,17 +814,17 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       };
       if (rec_mel) check(ohw_recording_set(e->state, samples, n, 0, nullptr));
       auto fill_ns = [&](int64_t bi, std::vector<int32_t>& nsv) {
-        const int64_t w0 = bi * e->max_batch;
+        const int64_t w0 = bi * WB;
         const int B = batch_of(bi);
         for (int b = 0; b < B; ++b) nsv[(size_t)b] = (int32_t)std::min<int64_t>(CHUNK_SAMPLES, n - rec_win(w0 + b) * CHUNK_SAMPLES);
       };
       auto front = [&](int64_t bi, ohw_state* st, void* stream, std::vector<int32_t>& nsv) {
         fill_ns(bi, nsv);
         check(ohw_state_set_stream(st, stream));
-        mel_windows(st, bi * e->max_batch, batch_of(bi), nsv.data());
+        mel_windows(st, bi * WB, batch_of(bi), nsv.data());
         check(ohw_encode(st, batch_of(bi)));
       };
-      auto decode_batch = [&](Scratch& sc, ohw_state* st, int64_t bi, const int32_t* nsb) { decode_windows(sc, st, bi * e->max_batch, batch_of(bi), nsb); };
+      auto decode_batch = [&](Scratch& sc, ohw_state* st, int64_t bi, const int32_t* nsb) { decode_windows(sc, st, bi * WB, batch_of(bi), nsb); };
       auto collect = [&](Scratch& sc, int B, int64_t w0) {
         flush_trace(sc);
         for (int b = 0; b < B; ++b) {
@@ -792,6 +833,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         }
       };
       int schedule = n_batches > 1 ? e->schedule : OHW_SCHEDULE_SEQUENTIAL;
+      if (beam_K > 0) schedule = OHW_SCHEDULE_SEQUENTIAL;      // no lanes for beams: the serial path on the engine's own state
       if (schedule == OHW_SCHEDULE_LANES && e->lanes < 2) schedule = OHW_SCHEDULE_SEQUENTIAL;
       if (schedule == OHW_SCHEDULE_PIPELINE && e->enc_cus <= 0) schedule = OHW_SCHEDULE_SEQUENTIAL;
       // ---- resources of the overlapped schedules, made when a long input first needs them: more states, CU-masked streams ----
@@ -907,14 +949,14 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         (void)ohw_state_set_stream(e->state, nullptr);
       };
       if (schedule == OHW_SCHEDULE_SEQUENTIAL) {
-        Scratch sc(e->max_batch, max_tok);
-        std::vector<int32_t> ns((size_t)e->max_batch);
+        Scratch sc(WB, max_tok);
+        std::vector<int32_t> ns((size_t)WB);
         for (int64_t bi = 0; bi < n_batches; ++bi) {
           fill_ns(bi, ns);
-          mel_windows(e->state, bi * e->max_batch, batch_of(bi), ns.data());
+          mel_windows(e->state, bi * WB, batch_of(bi), ns.data());
           check(ohw_encode(e->state, batch_of(bi)));
           decode_batch(sc, e->state, bi, ns.data());
-          collect(sc, batch_of(bi), bi * e->max_batch);
+          collect(sc, batch_of(bi), bi * WB);
         }
       } else if (schedule == OHW_SCHEDULE_PIPELINE) {
         // mel + encoder + cross-K/V of batch i+1 (MFMA-bound) run beside the greedy decode of batch i (HBM- and
@@ -1659,8 +1701,22 @@ int ohw_engine_set_packed_encoder(ohw_engine* e, int on) {
 
 int ohw_engine_set_force_len(ohw_engine* e, int n_tokens) {
   if (!e || n_tokens < 0) return OHW_E_INVALID_ARG;
+  if (n_tokens > 0 && e->beam_size > 0) {       // ohw_beam_search refuses force_len: the setter that comes second fails
+    g_last_error = "set_force_len: a beam size is set, and beam search refuses force_len";
+    return OHW_E_INVALID_ARG;
+  }
   e->force_len = n_tokens;
   return OHW_OK;
+}
+
+int ohw_engine_set_beam_size(ohw_engine* e, int k) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (k != 0 && (k < 2 || k > 5)) throw Error(OHW_E_INVALID_ARG, "set_beam_size: 0 (off) or 2..5, got " + std::to_string(k));
+    if (k > e->max_batch) throw Error(OHW_E_INVALID_ARG, "set_beam_size: " + std::to_string(k) + " beams need max_batch >= " + std::to_string(k) + ", the engine has " + std::to_string(e->max_batch));
+    if (k > 0 && e->force_len > 0) throw Error(OHW_E_INVALID_ARG, "set_beam_size: force_len is set, and beam search refuses it");
+    e->beam_size = k;
+  });
 }
 
 int ohw_engine_set_window_mode(ohw_engine* e, int mode) {

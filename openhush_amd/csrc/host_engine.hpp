@@ -19,6 +19,8 @@ struct ohw_engine {
   // schedule; empty: none.  prompt_used: a prompt has been set at some time, so states may still hold a table to clear
   std::vector<int32_t> prompt;
   bool prompt_used = false;
+  int beam_size = 0;                     // ohw_engine_set_beam_size: 0 = greedy at T = 0, 2..5 = beam search (a decode batch then holds
+                                         //   max_batch / beam_size windows, on the engine's own state)
   int force_len = 0;                     // measurement knob (ohw_engine_set_force_len): every window decodes exactly this many tokens
   std::vector<int32_t> last_tokens;
   std::string last_text;

@@ -213,10 +213,28 @@ struct BeamParams {
   float* fin_sum;         // [windows][K] cumulative log-probability, the end-of-text token's included
   unsigned* part;         // [rows][BEAM_SPLIT][BEAM_PART_WORDS] slice states of the split top-k (beam_topk_kernel)
   unsigned* tickets;      // [rows], zero between launches (re-armed by the kernel)
+  // what a decode policy needs of the result (ohw_beam_search_ex); null: the kernels touch none of it
+  const float* plog;      // [rows][max_tokens + 1] log-probability of every token of a beam's history (this step's view), or null
+  float* plog_next;       // the other half of the double buffer: gathered like tokens_next, the chosen candidate's own cand_lp at n_cur
+  float* fin_plog;        // [windows][K][max_tokens + 1] the same for the pool; end-of-text's at index fin_len
+  float* nosp_prob;       // [windows] first step: soft-max probability of the no-speech token in the unfiltered row, or null
 };
 constexpr int BEAM_SPLIT = 8;         // workgroups per logits row
-constexpr int BEAM_PART_WORDS = 32;   // max, sum, timestamp sum, best text logit, then (K + 1) text and (K + 1) timestamp candidates (value, index)
+constexpr int BEAM_PART_WORDS = 32;   // max, sum, timestamp sum, best text logit, then (K + 1) text and (K + 1) timestamp candidates (value, index);
+                                      //   words 28 / 29: the unfiltered row's max and sum (first step with nosp_prob only)
 void launch_beam_step(const SamplerParams& p, const BeamParams& bp, int n_windows, int first, hipStream_t s);
+// the final ranking of a beam search, one workgroup per window (decode.hip): the pool's sequences, then the live beams by
+// descending cumulative log-probability until there are K; the best cumulative log-probability per token wins (first maximum)
+struct BeamFinishParams {
+  int32_t K, stride, max_tokens;   // beams per window; row length of the token arrays (log-probability rows: stride + 1); clip
+  const int32_t *fin_cnt, *fin_len, *fin_tok, *n_cur, *tokens;
+  const float *fin_sum, *fin_plog, *beam_sum, *plog;
+  int32_t *out_tok, *out_n, *out_eot, *out_nfin;   // [windows][stride], [windows] ...
+  float *out_lp, *out_sum;                         // [windows][stride + 1], [windows]
+};
+void launch_beam_finish(const BeamFinishParams& f, int n_windows, hipStream_t s);
+// the same rule on the host (no GPU): the arrays are host memory
+void beam_finish_host(const BeamFinishParams& f, int n_windows);
 // self K/V cache T [planes][max_batch][n_head][n_ctx][64] (planes = 2 * layers): positions 0 .. n_pos - 1 of cache row src are
 // copied to row dst in every plane and head.  Beam search under a context table: window w's shared past goes from row w to row
 // w * K, a row only w's own beams write - row w is also the own row of a beam of window w / K, which would write into a longer context

@@ -303,6 +303,14 @@ int ohw_pool_set_force_len(ohw_pool* p, int n_tokens) {
   }
   return OHW_OK;
 }
+int ohw_pool_set_beam_size(ohw_pool* p, int k) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_beam_size(e, k);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {

@@ -115,8 +115,55 @@ class DbgBeamIO(C.Structure):
                 [("tickets_out", C.POINTER(C.c_uint32))])
 
 
+class BeamResultEx(C.Structure):
+    """ohw_beam_result_ex"""
+    _fields_ = [("tokens", C.POINTER(C.c_int32)), ("n_tokens", C.POINTER(C.c_int32)), ("sum_logprob", C.POINTER(C.c_float)),
+                ("n_finished", C.POINTER(C.c_int32)), ("token_logprobs", C.POINTER(C.c_float)), ("ended_by_eot", C.POINTER(C.c_int32)),
+                ("no_speech_prob", C.POINTER(C.c_float))]
+
+
+class DbgBeamIOEx(C.Structure):
+    """ohw_dbg_beam_io_ex"""
+    _fields_ = [("base", DbgBeamIO), ("plog", C.POINTER(C.c_float)), ("plog_next", C.POINTER(C.c_float)), ("fin_plog", C.POINTER(C.c_float)),
+                ("nosp_prob", C.POINTER(C.c_float))]
+
+
+class BeamFinishIO(C.Structure):
+    """ohw_beam_finish_io"""
+    _fields_ = ([(n, C.c_int32) for n in ("K", "W", "stride", "max_tokens")] +
+                [(n, C.POINTER(C.c_float) if n in ("fin_sum", "fin_plog", "plog", "beam_sum", "out_logprobs", "sum_logprob") else C.POINTER(C.c_int32))
+                 for n in ("fin_cnt", "fin_len", "fin_sum", "fin_tok", "fin_plog", "n_cur", "tokens", "plog", "beam_sum", "out_tokens",
+                           "out_logprobs", "n_tokens", "sum_logprob", "ended_by_eot", "n_finished")])
+
+
 OHW_DBG_SENTINEL_I32 = -7777777
 OHW_DBG_SENTINEL_F32 = -12345.0
+
+
+def _beam_finish(handle, K: int, state: dict, max_tokens: Optional[int]) -> dict:
+    W = int(np.asarray(state["n_cur"]).size)
+    R = W * K
+    S = int(np.asarray(state["tokens"]).shape[1])
+    n = S if max_tokens is None else int(max_tokens)
+    i32 = lambda k, shape: np.array(state[k], dtype=np.int32, order="C").reshape(shape)
+    f32 = lambda k, shape: np.array(state[k], dtype=np.float32, order="C").reshape(shape)
+    a = dict(fin_cnt=i32("fin_cnt", W), fin_len=i32("fin_len", R), fin_sum=f32("fin_sum", R), fin_tok=i32("fin_tok", (R, S)),
+             fin_plog=f32("fin_plog", (R, S + 1)), n_cur=i32("n_cur", W), tokens=i32("tokens", (R, S)), plog=f32("plog", (R, S + 1)),
+             beam_sum=f32("beam_sum", R), out_tokens=np.zeros((W, max(n, 0)), np.int32), out_logprobs=np.zeros((W, max(n, 0) + 1), np.float32),
+             n_tokens=np.zeros(W, np.int32), sum_logprob=np.zeros(W, np.float32), ended_by_eot=np.zeros(W, np.int32),
+             n_finished=np.zeros(W, np.int32))
+    io = BeamFinishIO(K, W, S, n, *[(_fp(a[k]) if a[k].dtype == np.float32 else _ip(a[k])) for k, _ in BeamFinishIO._fields_[4:]])
+    _check(lib().ohw_beam_finish_host(C.byref(io)) if handle is None else lib().ohw_dbg_beam_finish(handle, C.byref(io)))
+    return {"tokens": a["out_tokens"], "logprobs": a["out_logprobs"], "n_tokens": a["n_tokens"], "sum_logprob": a["sum_logprob"],
+            "ended_by_eot": a["ended_by_eot"], "n_finished": a["n_finished"]}
+
+
+def beam_finish_host(K: int, state: dict, max_tokens: Optional[int] = None) -> dict:
+    """ohw_beam_finish_host: the final ranking of a beam search on the host, no GPU.  state: fin_cnt / n_cur [W], fin_len /
+    fin_sum / beam_sum [R], fin_tok / tokens [R][S], fin_plog / plog [R][S + 1] (R = W * K; S: any row length).
+    -> dict(tokens [W][max_tokens], logprobs [W][max_tokens + 1], n_tokens, sum_logprob, ended_by_eot, n_finished [W]); what the
+    rule did not write holds OHW_DBG_SENTINEL_*"""
+    return _beam_finish(None, K, state, max_tokens)
 
 
 class WindowQuality(C.Structure):
@@ -193,7 +240,8 @@ EXPORTS = [
     "ohw_dbg_dtw", "ohw_engine_set_word_timestamps", "ohw_engine_last_token_times", "ohw_engine_last_words", "ohw_engine_last_segments",
     "ohw_engine_batch_times", "ohw_word_starts_host", "ohw_segments_host",
     "ohw_pool_set_word_timestamps", "ohw_pool_last_token_times", "ohw_pool_last_words", "ohw_pool_last_segments",
-    "ohw_dbg_beam_step",
+    "ohw_dbg_beam_step", "ohw_beam_search_ex", "ohw_dbg_beam_step_ex", "ohw_dbg_beam_finish", "ohw_beam_finish_host",
+    "ohw_engine_set_beam_size", "ohw_pool_set_beam_size",
     "ohw_dbg_cross_attn_chunk",
     "ohw_state_set_window_prompt", "ohw_state_window_prompt_len", "ohw_state_prefill", "ohw_tokenize_host", "ohw_tokenize", "ohw_prompt_clip_host",
     "ohw_engine_set_initial_prompt", "ohw_engine_set_initial_prompt_tokens", "ohw_pool_set_initial_prompt",
@@ -271,6 +319,8 @@ def lib():
         L.ohw_pool_set_force_len.argtypes = [vp, C.c_int]
         L.ohw_pool_set_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.ohw_engine_set_force_len.argtypes = [vp, C.c_int]
+        L.ohw_engine_set_beam_size.argtypes = [vp, C.c_int]
+        L.ohw_pool_set_beam_size.argtypes = [vp, C.c_int]
         L.ohw_pool_broadcast_note.argtypes = [vp]
         L.ohw_pool_broadcast_note.restype = C.c_char_p
         L.ohw_dsp_rms_db.argtypes = [fp, C.c_int64]
@@ -466,6 +516,10 @@ def lib():
         L.ohw_dbg_lang_pick.argtypes = [vp, fp, C.c_int, ip, fp]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
         L.ohw_dbg_beam_step.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIO)]
+        L.ohw_beam_search_ex.argtypes = [vp, C.POINTER(SampleParams), C.c_int, C.c_int, C.c_int, C.POINTER(BeamResultEx)]
+        L.ohw_dbg_beam_step_ex.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIOEx)]
+        L.ohw_dbg_beam_finish.argtypes = [vp, C.POINTER(BeamFinishIO)]
+        L.ohw_beam_finish_host.argtypes = [C.POINTER(BeamFinishIO)]
         L.ohw_state_set_align_heads.argtypes = [vp, C.POINTER(AlignHead), C.c_int]
         L.ohw_state_align.argtypes = [vp, C.POINTER(SampleParams), ip, C.c_int, ip, ip, C.c_int, ip]
         L.ohw_align_reduce_host.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
@@ -1049,6 +1103,24 @@ class State:
         _check(lib().ohw_beam_search(self.h, C.byref(p), n_windows, beam_size, cap, C.byref(r)))
         return [{"tokens": [int(x) for x in toks[w, :nt[w]]], "sum_logprob": float(sm[w]), "n_finished": int(nf[w])} for w in range(n_windows)]
 
+    def beam_search_ex(self, n_windows: int, beam_size: int = 5, p: Optional[SampleParams] = None):
+        """ohw_beam_search_ex: beam_search's result (the same bits) plus what a decode policy judges ->
+        [dict(tokens, sum_logprob, n_finished, logprobs (end-of-text's last when ended_by_eot), ended_by_eot, no_speech_prob)]"""
+        p = p or self.ctx.default_params()
+        cap = self.ctx.hp.n_text_ctx
+        toks = np.zeros((n_windows, cap), dtype=np.int32)
+        nt = np.zeros(n_windows, dtype=np.int32)
+        sm = np.zeros(n_windows, dtype=np.float32)
+        nf = np.zeros(n_windows, dtype=np.int32)
+        lps = np.zeros((n_windows, cap + 1), dtype=np.float32)
+        eot = np.zeros(n_windows, dtype=np.int32)
+        nsp = np.zeros(n_windows, dtype=np.float32)
+        r = BeamResultEx(_ip(toks), _ip(nt), _fp(sm), _ip(nf), _fp(lps), _ip(eot), _fp(nsp))
+        _check(lib().ohw_beam_search_ex(self.h, C.byref(p), n_windows, beam_size, cap, C.byref(r)))
+        return [{"tokens": [int(x) for x in toks[w, :nt[w]]], "sum_logprob": float(sm[w]), "n_finished": int(nf[w]),
+                 "logprobs": lps[w, :nt[w] + (1 if eot[w] else 0)].copy(), "ended_by_eot": bool(eot[w]), "no_speech_prob": float(nsp[w])}
+                for w in range(n_windows)]
+
     def set_logit_bias(self, bias: Optional[np.ndarray]):
         """additive bias [n_vocab] on every logits row before the filter (None clears it)"""
         if bias is None:
@@ -1264,6 +1336,51 @@ class State:
         out["tokens"], out["kv_slot"] = a["tokens_next"], a["kv_slot_next"]
         out["n_done"], out["tickets"] = int(a["n_done"][0]), tickets
         return out
+
+    def dbg_beam_step_ex(self, p: SampleParams, K: int, first: bool, state: dict, logits: np.ndarray, side: int = 0, nosp: bool = True) -> dict:
+        """ohw_dbg_beam_step_ex: dbg_beam_step with the log-probability history.  state may also hold plog and fin_plog
+        [R][n_text_ctx + 1]; without plog the history pointers are NULL (the kernels touch none of it).
+        -> dbg_beam_step's dict, plus plog (the other half) and fin_plog when plog was given, and nosp_prob [W] when nosp"""
+        W = int(np.asarray(state["n_cur"]).size)
+        R, Cx, V = W * K, self.ctx.hp.n_text_ctx, self.ctx.hp.n_vocab
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        assert lg.shape == ((W if first else R), V), lg.shape
+        i32 = lambda k, shape: np.array(state[k], dtype=np.int32, order="C").reshape(shape)
+        f32 = lambda k, shape: np.array(state[k], dtype=np.float32, order="C").reshape(shape)
+        a = dict(tokens=i32("tokens", (R, Cx)), kv_slot=i32("kv_slot", (R, Cx)), n_cur=i32("n_cur", W), n_past_w=i32("n_past_w", W),
+                 win_done=i32("win_done", W), beam_sum=f32("beam_sum", R), fin_cnt=i32("fin_cnt", W), fin_tok=i32("fin_tok", (R, Cx)),
+                 fin_len=i32("fin_len", R), fin_sum=f32("fin_sum", R),
+                 cand_tok=np.zeros((R, K + 1), np.int32), cand_lp=np.zeros((R, K + 1), np.float32),
+                 tokens_next=np.zeros((R, Cx), np.int32), kv_slot_next=np.zeros((R, Cx), np.int32),
+                 next_tok=np.zeros(R, np.int32), n_past=np.zeros(R, np.int32), n_done=np.zeros(1, np.int32))
+        tickets = np.ones(R, np.uint32)
+        base = DbgBeamIO(int(bool(first)), K, W, side, _fp(lg),
+                         *[(_fp(a[n]) if a[n].dtype == np.float32 else _ip(a[n])) for n, _ in DbgBeamIO._fields_[5:-1]],
+                         tickets.ctypes.data_as(C.POINTER(C.c_uint32)))
+        null = C.cast(None, C.POINTER(C.c_float))
+        lp = state.get("plog") is not None
+        if lp:
+            plog, fin_plog = f32("plog", (R, Cx + 1)), f32("fin_plog", (R, Cx + 1))
+            plog_next = np.zeros((R, Cx + 1), np.float32)
+        nsp = np.zeros(W, np.float32)
+        io = DbgBeamIOEx(base, _fp(plog) if lp else null, _fp(plog_next) if lp else null, _fp(fin_plog) if lp else null, _fp(nsp) if nosp else null)
+        _check(lib().ohw_dbg_beam_step_ex(self.h, C.byref(p), C.byref(io)))
+        out = {k: a[k] for k in ("n_cur", "n_past_w", "win_done", "beam_sum", "fin_cnt", "fin_tok", "fin_len", "fin_sum", "cand_tok",
+                                 "cand_lp", "next_tok", "n_past")}
+        out["tokens"], out["kv_slot"] = a["tokens_next"], a["kv_slot_next"]
+        out["n_done"], out["tickets"] = int(a["n_done"][0]), tickets
+        if lp:
+            out["plog"], out["fin_plog"] = plog_next, fin_plog
+        if nosp:
+            out["nosp_prob"] = nsp
+        return out
+
+    beam_finish_host = staticmethod(beam_finish_host)
+
+    def dbg_beam_finish(self, K: int, state: dict, max_tokens: Optional[int] = None) -> dict:
+        """ohw_dbg_beam_finish: the device's final ranking on a host-supplied pool and live state (beam_finish_host's arguments;
+        the rows must be n_text_ctx long)"""
+        return _beam_finish(self.h, K, state, max_tokens)
 
     def sample_pass(self, batch: int, temperature: float, active: Sequence[int], uniforms: np.ndarray, p: Optional[SampleParams] = None):
         """ohw_sample_pass: one temperature pass on the device; uniforms [batch][n_text_ctx] -> greedy_ex's dicts (zeros for
@@ -1840,6 +1957,15 @@ class WhisperEngine:
             i += 3 + k
         return out
 
+    def set_beam_size(self, k: int):
+        """ohw_engine_set_beam_size: 0 (default) = greedy at T = 0, 2..5 = beam search with k beams per window in every
+        transcribe, transcribe_batch and transcribe_long_batch; a decode batch then holds max_batch // k windows"""
+        _check(lib().ohw_engine_set_beam_size(self.h, int(k)))
+
+    def set_force_len(self, n_tokens: int):
+        """ohw_engine_set_force_len (measurement knob); refused while a beam size is set"""
+        _check(lib().ohw_engine_set_force_len(self.h, int(n_tokens)))
+
     def set_window_mode(self, mode: int):
         """OHW_WINDOW_FIXED (0, default), OHW_WINDOW_SEEK (1, whisper.cpp's timestamp-driven loop) or OHW_WINDOW_FIXED_RECORDING_MEL
         (2: fixed cuts taken from the spectrogram of the whole recording)"""
@@ -1911,6 +2037,10 @@ class EnginePool:
 
     def set_force_len(self, n_tokens: int):
         _check(lib().ohw_pool_set_force_len(self.h, n_tokens))
+
+    def set_beam_size(self, k: int):
+        """ohw_pool_set_beam_size: WhisperEngine.set_beam_size(k) on every engine of the pool"""
+        _check(lib().ohw_pool_set_beam_size(self.h, int(k)))
 
     def set_schedule(self, schedule: int, lanes: int = 0, merge: int = 0):
         _check(lib().ohw_pool_set_schedule(self.h, schedule, lanes, merge))
