@@ -1086,6 +1086,70 @@ typedef struct {
 int ohw_dbg_beam_finish(ohw_state* st, const ohw_beam_finish_io* io);
 int ohw_beam_finish_host(const ohw_beam_finish_io* io);
 
+/* ONE decoder GEMM launch (launch_dec_gemm: decode.hip) on caller data (tests/test_gpu_dec_gemm.py); no ohw_state.  Every
+ * pointer but n_past is a DEVICE pointer; the entry checks every range on the host before any device work (OHW_E_INVALID_ARG,
+ * nothing launched), prepares the weights on private copies with the loader's own kernels, launches once on `stream`,
+ * synchronises it and frees its copies.
+ * Weights: w f32 [N][K] row-major, bias f32 [N] or NULL, gamma / beta f32 [K], both or neither: with them the LayerNorm's
+ *   affine part is folded first (launch_fold_ln: bias += W beta, W *= gamma; a NULL bias counts as zeros), then the matrix is
+ *   rounded to `dtype` in fragment-tile order with ceil16(N) rows (launch_repack_tiled), and for form PN its row sums are
+ *   taken (launch_tiled_rowsum).
+ * Activations, by form:
+ *   PLAIN  x: `dtype` activation tiles [ceil(M / 16)][K / 32][64][8] (the order ohw_dbg_cross_attn documents for its output)
+ *   LN     x: f32 [M][K]; (x - mean) * rstd is fused into the prologue; K % 64 == 0, K <= 1280; epilogues QKV, BIAS_T, GELU_T
+ *   PN     x: tiles as PLAIN, stat_in f32 [M][K / 16][2] (mean and sum of squared deviations of 16 columns):
+ *          out = rstd * (x W^T - mean * wsum) + bias; K / 16 <= 128 statistics tiles; epilogues QKV, BIAS_T, GELU_T
+ * Epilogues (M rows, out written for rows < M and columns < N only):
+ *   QKV     N == 3 * d_model, d_model == 64 * n_head, M % n_new == 0.  out: `dtype` [M][d_model] (q, ld_out ignored);
+ *           k_cache / v_cache `dtype` [M / n_new][n_head][n_ctx][64]: row m = b * n_new + i stores position n_past[b] + i, and
+ *           nothing when that is >= n_ctx.  n_past: HOST [M / n_new], 0 <= n_past[b] <= n_ctx
+ *   BIAS_T  out `dtype` [M][ld_out]            GELU_T  out `dtype` activation tiles [ceil(M / 16)][N / 32][64][8], N % 32 == 0
+ *   RESID   out f32 [M][ld_out] += x W^T + bias.  ksplit > 1 (form PLAIN): K cut over ksplit workgroups per tile,
+ *           2 <= ksplit <= K / 32, slab f32 of slab_bytes >= ceil(N / 16) * ceil(M / 32) * ksplit * 2048 bytes, ticket u32
+ *           [ceil(N / 16) * ceil(M / 32)] zero before and after.  x16_out and stat_out (both or neither; form PLAIN, no
+ *           split, N % 32 == 0): also the `dtype` tiled copy [ceil(M / 16)][N / 32][64][8] of the new rows and f32
+ *           [M][N / 16][2] statistics of every 16 columns
+ *   LOGITS  out f32 [M / n_new][ld_out]: only rows m with m % n_new == n_new - 1 are stored, as row m / n_new
+ *   ld_out >= N wherever it is used.  cu_budget: compute units the launch may use (0: the whole device); with M, N and K it
+ *   decides the work shape.  *shape_out (may be NULL): OHW_DG_SHAPE_* of the kernel that ran. */
+enum { OHW_DEPI_QKV = 0, OHW_DEPI_BIAS_T, OHW_DEPI_BIAS_GELU_T, OHW_DEPI_BIAS_RESID, OHW_DEPI_LOGITS };
+enum { OHW_DG_FORM_PLAIN = 0, OHW_DG_FORM_LN, OHW_DG_FORM_PN };
+enum { OHW_DG_SHAPE_1x1 = 0, OHW_DG_SHAPE_2x1, OHW_DG_SHAPE_1x2, OHW_DG_SHAPE_2x2, OHW_DG_SHAPE_4x2, OHW_DG_SHAPE_1x6 };
+typedef struct {
+  int32_t dtype, epilogue, form;
+  int32_t M, N, K, n_new;
+  int64_t ld_out;
+  int32_t cu_budget, ksplit;
+  const float* w;          /* f32 [N][K] */
+  const float* bias;       /* f32 [N] or NULL */
+  const float* gamma;      /* f32 [K] or NULL */
+  const float* beta;       /* f32 [K] or NULL */
+  const void* x;
+  const float* stat_in;    /* form PN */
+  void* out;
+  float* slab;             /* ksplit > 1 */
+  int64_t slab_bytes;
+  uint32_t* ticket;
+  void* x16_out;           /* RESID producer, or NULL */
+  float* stat_out;
+  void* k_cache;           /* QKV */
+  void* v_cache;
+  const int32_t* n_past;   /* QKV: HOST [M / n_new] */
+  int32_t d_model, n_head, n_ctx;
+  int32_t* shape_out;      /* HOST, or NULL */
+} ohw_dbg_dec_gemm_io;
+int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream);
+/* launch_embed on caller data: emb f32 [n_vocab][d] (device; rounded and tiled like a weight matrix, rows padded to a multiple
+ * of 16), pos f32 [n_pos][d] (device), tok and n_past HOST tables [M] and [M / n_new]: 0 <= tok[m] < n_vocab,
+ * 0 <= n_past[b] and n_past[b] + n_new <= n_pos; M % n_new == 0, d % 32 == 0.  x f32 [M][d] = emb[tok[m]] + pos[n_past[m / n_new]
+ * + m % n_new]; x16 (`dtype` tiles [ceil(M / 16)][d / 32][64][8]) and stat (f32 [M][d / 16][2]) may be NULL. */
+int ohw_dbg_embed(int dtype, const float* emb, int n_vocab, const float* pos, int n_pos, const int32_t* tok_host,
+                  const int32_t* n_past_host, float* x, void* x16, float* stat, int M, int n_new, int d, void* stream);
+/* launch_layernorm on caller data (device pointers): x f32 [rows][d], gamma / beta f32 [d]; y `dtype` [rows][d] row-major, or
+ * with tiled != 0 activation tiles [ceil(rows / 16)][d / 32][64][8] (then d % 32 == 0).  d % 4 == 0, 4 <= d <= 2048. */
+int ohw_dbg_layernorm(int dtype, const float* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, int tiled,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

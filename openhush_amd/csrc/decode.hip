@@ -764,6 +764,7 @@ int launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s) {
   if (p.pn && (ln || !p.stat_in || !p.wsum || p.n_stat * 16 != p.K || p.n_stat > 128)) throw Error(OHW_E_INVALID_ARG, "dec_gemm: post-norm needs statistics of K / 16 tiles per row and the weights' row sums");
   if (p.stat_out && (epilogue != DEPI_BIAS_RESID || !p.x16_out || p.N % 32 != 0 || p.ksplit > 1))
     throw Error(OHW_E_INVALID_ARG, "dec_gemm: statistics come from the unsplit RESID epilogue with N % 32 == 0");
+  if (epilogue == DEPI_BIAS_GELU_T && p.N % 32 != 0) throw Error(OHW_E_INVALID_ARG, "dec_gemm: the tiled GELU output needs N % 32 == 0");
   int shape = 0;
   switch (epilogue) {
     case DEPI_QKV: shape = ln ? dec_gemm_pick<T, DEPI_QKV, true>(p, s) : dec_gemm_pick<T, DEPI_QKV, false>(p, s); break;

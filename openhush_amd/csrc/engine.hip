@@ -2873,4 +2873,140 @@ int ohw_dbg_self_attn(int dtype, const void* q, const void* k_cache, const void*
   });
 }
 
+static_assert(OHW_DEPI_QKV == DEPI_QKV && OHW_DEPI_BIAS_T == DEPI_BIAS_T && OHW_DEPI_BIAS_GELU_T == DEPI_BIAS_GELU_T &&
+              OHW_DEPI_BIAS_RESID == DEPI_BIAS_RESID && OHW_DEPI_LOGITS == DEPI_LOGITS, "ohw.h names kernels.hpp's epilogues");
+static_assert(OHW_DG_SHAPE_1x1 == DG_SHAPE_1x1 && OHW_DG_SHAPE_2x1 == DG_SHAPE_2x1 && OHW_DG_SHAPE_1x2 == DG_SHAPE_1x2 &&
+              OHW_DG_SHAPE_2x2 == DG_SHAPE_2x2 && OHW_DG_SHAPE_4x2 == DG_SHAPE_4x2 && OHW_DG_SHAPE_1x6 == DG_SHAPE_1x6, "ohw.h names kernels.hpp's shapes");
+
+int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
+  return guard([&] {
+    if (!io) throw Error(OHW_E_INVALID_ARG, "dbg_dec_gemm: null io");
+    const ohw_dbg_dec_gemm_io& a = *io;
+    auto bad = [](const std::string& why) { throw Error(OHW_E_INVALID_ARG, "dbg_dec_gemm: " + why); };
+    dbg_check_dtype(a.dtype, "dbg_dec_gemm");
+    if (a.epilogue < DEPI_QKV || a.epilogue > DEPI_LOGITS) bad("epilogue must be 0 .. 4");
+    if (a.form < OHW_DG_FORM_PLAIN || a.form > OHW_DG_FORM_PN) bad("form must be 0 (plain), 1 (ln) or 2 (pn)");
+    if (!a.w || !a.x || !a.out) bad("null w, x or out");
+    if (a.M < 1 || a.N < 1 || a.K < 32 || a.M > (1 << 20) || a.N > (1 << 20) || a.K > (1 << 20)) bad("M, N >= 1 and K >= 32 (each at most 2^20)");
+    if (a.K % 32 != 0) bad("K = " + std::to_string(a.K) + " must be a multiple of 32");
+    if (a.cu_budget < 0 || a.ksplit < 0) bad("cu_budget and ksplit must not be negative");
+    if ((a.gamma == nullptr) != (a.beta == nullptr)) bad("gamma and beta come together");
+    const bool ln = a.form == OHW_DG_FORM_LN, pn = a.form == OHW_DG_FORM_PN;
+    const bool t_epi = a.epilogue == DEPI_QKV || a.epilogue == DEPI_BIAS_T || a.epilogue == DEPI_BIAS_GELU_T;
+    if ((ln || pn) && !t_epi) bad("the ln and pn forms exist for the QKV, BIAS_T and BIAS_GELU_T epilogues");
+    if (ln && a.K > 1280) bad("ln: K = " + std::to_string(a.K) + " exceeds the 1280 columns of the fused LayerNorm");
+    if (ln && a.K % 64 != 0) bad("ln: K = " + std::to_string(a.K) + " must be a multiple of 64");
+    if (pn && a.K / 16 > 128) bad("pn: n_stat = K / 16 = " + std::to_string(a.K / 16) + " exceeds 128 statistics tiles per row");
+    if (pn && !a.stat_in) bad("pn: null stat_in");
+    const bool uses_ld = a.epilogue == DEPI_BIAS_T || a.epilogue == DEPI_BIAS_RESID || a.epilogue == DEPI_LOGITS;
+    if (uses_ld && a.ld_out < a.N) bad("ld_out = " + std::to_string(a.ld_out) + " is below N = " + std::to_string(a.N));
+    if (a.epilogue == DEPI_BIAS_GELU_T && a.N % 32 != 0) bad("BIAS_GELU_T writes activation tiles: N = " + std::to_string(a.N) + " must be a multiple of 32");
+    const bool rows_epi = a.epilogue == DEPI_QKV || a.epilogue == DEPI_LOGITS;
+    if (rows_epi && (a.n_new < 1 || a.M % a.n_new != 0)) bad("M = " + std::to_string(a.M) + " must be a multiple of n_new = " + std::to_string(a.n_new) + " >= 1");
+    const int windows = rows_epi ? a.M / a.n_new : 0;
+    if (a.epilogue == DEPI_QKV) {
+      if (!a.k_cache || !a.v_cache || !a.n_past) bad("QKV: null k_cache, v_cache or n_past");
+      if (a.n_head < 1 || a.n_ctx < 1 || a.d_model != 64 * a.n_head || a.N != 3 * a.d_model) bad("QKV: d_model == 64 * n_head, N == 3 * d_model, n_ctx >= 1");
+      for (int b = 0; b < windows; ++b)
+        if (a.n_past[b] < 0 || a.n_past[b] > a.n_ctx)
+          bad("n_past[" + std::to_string(b) + "] = " + std::to_string(a.n_past[b]) + " is outside 0 .. n_ctx = " + std::to_string(a.n_ctx));
+    }
+    const int64_t tiles = (int64_t)((a.N + 15) / 16) * ((a.M + 31) / 32);
+    if (a.ksplit > 1) {
+      if (a.epilogue != DEPI_BIAS_RESID) bad("split-K exists for the RESID epilogue only");
+      if (a.ksplit > a.K / 32) bad("ksplit = " + std::to_string(a.ksplit) + " exceeds the K / 32 = " + std::to_string(a.K / 32) + " k-blocks");
+      if (!a.slab || !a.ticket) bad("split-K: null slab or ticket");
+      if (a.slab_bytes < tiles * a.ksplit * 2048 || a.slab_bytes > INT32_MAX)
+        bad("split-K: slab_bytes = " + std::to_string(a.slab_bytes) + ", needed " + std::to_string(tiles * a.ksplit * 2048) + " (tiles * ksplit * 2 KiB, below 2 GiB)");
+    }
+    if ((a.x16_out == nullptr) != (a.stat_out == nullptr)) bad("x16_out and stat_out come together");
+    if (a.stat_out) {
+      if (a.epilogue != DEPI_BIAS_RESID || a.ksplit > 1) bad("stat_out: statistics come from the unsplit RESID epilogue");
+      if (a.N % 32 != 0) bad("stat_out: N = " + std::to_string(a.N) + " must be a multiple of 32");
+    }
+
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_pad = ((int64_t)a.N + 15) / 16 * 16;
+    DevBuf wf, bf, wt, ws, past;
+    // private copies, prepared as the loader prepares a decoder linear (model.hip): fold, round + tile, row sums
+    wf.alloc((size_t)a.N * a.K * 4);
+    HIP_CHECK(hipMemcpyAsync(wf.p, a.w, (size_t)a.N * a.K * 4, hipMemcpyDeviceToDevice, s));
+    const bool own_bias = a.bias != nullptr || a.gamma != nullptr;
+    if (own_bias) {
+      bf.alloc((size_t)a.N * 4);
+      if (a.bias) HIP_CHECK(hipMemcpyAsync(bf.p, a.bias, (size_t)a.N * 4, hipMemcpyDeviceToDevice, s));
+      else HIP_CHECK(hipMemsetAsync(bf.p, 0, (size_t)a.N * 4, s));
+    }
+    if (a.gamma) launch_fold_ln(wf.as<float>(), bf.as<float>(), a.gamma, a.beta, a.N, a.K, s);
+    wt.alloc((size_t)n_pad * a.K * 2);
+    if (pn) ws.alloc((size_t)a.N * 4);
+    if (a.epilogue == DEPI_QKV) dbg_upload(past, a.n_past, (size_t)windows);
+    int shape = -1;
+    Dispatch::run(a.dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      launch_repack_tiled<TT>(wf.as<float>(), wt.p, a.N, n_pad, a.K, s);
+      if (pn) launch_tiled_rowsum<TT>(wt.p, ws.as<float>(), a.N, a.K, s);
+      DecGemmParams p{};
+      p.x = a.x; p.ln = ln ? 1 : 0; p.w = wt.p; p.bias = own_bias ? bf.as<float>() : nullptr; p.out = a.out;
+      p.M = a.M; p.N = a.N; p.K = a.K; p.n_new = rows_epi ? a.n_new : 1;
+      p.ld_out = a.epilogue == DEPI_QKV ? a.d_model : a.ld_out; p.cu_budget = a.cu_budget;
+      if (a.epilogue == DEPI_QKV) {
+        p.k_cache = a.k_cache; p.v_cache = a.v_cache; p.n_past = past.as<int32_t>();
+        p.d_model = a.d_model; p.n_head = a.n_head; p.n_ctx = a.n_ctx;
+      }
+      if (a.ksplit > 1) { p.ksplit = a.ksplit; p.slab = a.slab; p.slab_bytes = (int32_t)a.slab_bytes; p.ticket = a.ticket; }
+      if (pn) { p.pn = 1; p.n_stat = a.K / 16; p.stat_in = a.stat_in; p.wsum = ws.as<float>(); }
+      if (a.stat_out) { p.x16_out = a.x16_out; p.stat_out = a.stat_out; }
+      shape = launch_dec_gemm<TT>(p, a.epilogue, s);
+    });
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (a.shape_out) *a.shape_out = shape;
+  });
+}
+
+int ohw_dbg_embed(int dtype, const float* emb, int n_vocab, const float* pos, int n_pos, const int32_t* tok_host,
+                  const int32_t* n_past_host, float* x, void* x16, float* stat, int M, int n_new, int d, void* stream) {
+  return guard([&] {
+    dbg_check_dtype(dtype, "dbg_embed");
+    if (!emb || !pos || !tok_host || !n_past_host || !x || n_vocab < 1 || n_pos < 1 || M < 1 || n_new < 1 || d < 32)
+      throw Error(OHW_E_INVALID_ARG, "dbg_embed: null buffer, or n_vocab, n_pos, M or n_new below 1, or d below 32");
+    if (d % 32 != 0 || d > (1 << 16) || n_vocab > (1 << 20)) throw Error(OHW_E_INVALID_ARG, "dbg_embed: d must be a multiple of 32 (at most 2^16), n_vocab at most 2^20");
+    if (M % n_new != 0) throw Error(OHW_E_INVALID_ARG, "dbg_embed: M must be a multiple of n_new");
+    for (int m = 0; m < M; ++m)
+      if (tok_host[m] < 0 || tok_host[m] >= n_vocab)
+        throw Error(OHW_E_INVALID_ARG, "dbg_embed: tok[" + std::to_string(m) + "] = " + std::to_string(tok_host[m]) + " is outside the " + std::to_string(n_vocab) + " rows of the table");
+    for (int b = 0; b < M / n_new; ++b)
+      if (n_past_host[b] < 0 || (int64_t)n_past_host[b] + n_new > n_pos)
+        throw Error(OHW_E_INVALID_ARG, "dbg_embed: n_past[" + std::to_string(b) + "] = " + std::to_string(n_past_host[b]) + " with n_new = " + std::to_string(n_new) +
+                                           " is outside the " + std::to_string(n_pos) + " positions");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t v_pad = ((int64_t)n_vocab + 15) / 16 * 16;
+    DevBuf et, tok, past;
+    et.alloc((size_t)v_pad * d * 2);
+    dbg_upload(tok, tok_host, (size_t)M);
+    dbg_upload(past, n_past_host, (size_t)(M / n_new));
+    Dispatch::run(dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      launch_repack_tiled<TT>(emb, et.p, n_vocab, v_pad, d, s);
+      launch_embed<TT>(et.p, pos, tok.as<int32_t>(), past.as<int32_t>(), x, x16, stat, M, n_new, d, s);
+    });
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+int ohw_dbg_layernorm(int dtype, const float* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, int tiled,
+                      void* stream) {
+  return guard([&] {
+    dbg_check_dtype(dtype, "dbg_layernorm");
+    if (!x || !gamma || !beta || !y || rows < 1 || rows > (1 << 24)) throw Error(OHW_E_INVALID_ARG, "dbg_layernorm: null buffer, or rows outside 1 .. 2^24");
+    if (d < 4 || d % 4 != 0 || d > 2048) throw Error(OHW_E_INVALID_ARG, "dbg_layernorm: d must be a multiple of 4 in 4 .. 2048");
+    if (tiled && d % 32 != 0) throw Error(OHW_E_INVALID_ARG, "dbg_layernorm: the tiled output needs d % 32 == 0");
+    Dispatch::run(dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      launch_layernorm<TT>(x, gamma, beta, y, rows, d, (hipStream_t)stream, tiled != 0);
+    });
+    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
 }  // extern "C"

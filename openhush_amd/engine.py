@@ -136,6 +136,20 @@ class BeamFinishIO(C.Structure):
                            "out_logprobs", "n_tokens", "sum_logprob", "ended_by_eot", "n_finished")])
 
 
+class DbgDecGemmIO(C.Structure):
+    """ohw_dbg_dec_gemm_io: every pointer but n_past and shape_out is a device address"""
+    _fields_ = ([(n, C.c_int32) for n in ("dtype", "epilogue", "form", "M", "N", "K", "n_new")] + [("ld_out", C.c_int64)] +
+                [(n, C.c_int32) for n in ("cu_budget", "ksplit")] +
+                [(n, C.c_void_p) for n in ("w", "bias", "gamma", "beta", "x", "stat_in", "out", "slab")] + [("slab_bytes", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("ticket", "x16_out", "stat_out", "k_cache", "v_cache")] + [("n_past", C.POINTER(C.c_int32))] +
+                [(n, C.c_int32) for n in ("d_model", "n_head", "n_ctx")] + [("shape_out", C.POINTER(C.c_int32))])
+
+
+# ohw_dbg_dec_gemm: epilogues (kernels.hpp's DecEpilogue), operand forms and the work shape that ran (DecGemmShape)
+DEPI_QKV, DEPI_BIAS_T, DEPI_BIAS_GELU_T, DEPI_BIAS_RESID, DEPI_LOGITS = range(5)
+DG_FORM_PLAIN, DG_FORM_LN, DG_FORM_PN = range(3)
+DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_SHAPE_1x6 = range(6)
+
 OHW_DBG_SENTINEL_I32 = -7777777
 OHW_DBG_SENTINEL_F32 = -12345.0
 
@@ -247,6 +261,7 @@ EXPORTS = [
     "ohw_engine_set_initial_prompt", "ohw_engine_set_initial_prompt_tokens", "ohw_pool_set_initial_prompt",
     "ohw_recording_set_slot", "ohw_mel_seek_slots", "ohw_seek_sched_new", "ohw_seek_sched_round", "ohw_seek_sched_advance", "ohw_seek_sched_free",
     "ohw_engine_transcribe_long_batch", "ohw_engine_long_batch_quality",
+    "ohw_dbg_dec_gemm", "ohw_dbg_embed", "ohw_dbg_layernorm",
 ]
 
 
@@ -487,6 +502,9 @@ def lib():
         L.ohw_engine_set_initial_prompt_tokens.argtypes = [vp, ip, C.c_int]
         L.ohw_pool_set_initial_prompt.argtypes = [vp, C.c_char_p]
         L.ohw_dbg_self_attn.argtypes = [C.c_int, vp, vp, vp, ip, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int), vp]
+        L.ohw_dbg_dec_gemm.argtypes = [C.POINTER(DbgDecGemmIO), vp]
+        L.ohw_dbg_embed.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, ip, ip, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+        L.ohw_dbg_layernorm.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp]
         L.ohw_state_set_audio_ctx.argtypes = [vp, C.c_int]
         L.ohw_state_audio_ctx.argtypes = [vp]
         L.ohw_audio_ctx_for.argtypes = [C.c_int64]
