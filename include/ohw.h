@@ -529,6 +529,16 @@ int ohw_state_window_lang(ohw_state* st, int batch, int32_t* ids_out, float* pro
 int ohw_state_set_window_prompt(ohw_state* st, const int32_t* tokens, int stride, const int32_t* n_tokens, int batch);
 int ohw_state_window_prompt_len(const ohw_state* st, int window);
 int ohw_state_prefill(ohw_state* st, int batch, const int32_t* active);
+/* the prefill's chunk size: 8 (default) or 16 positions per pass (anything else: OHW_E_INVALID_ARG).  With 16 a prefill makes half
+ * as many passes, so the decoder weights and every window's cross K/V are streamed half as often, and its cross-attention fills
+ * all 16 columns of its MFMA tile (cross_attn_chunk_kernel<T, 16, VAR>).  Surplus rows of a chunk then reach cache positions up to
+ * len[b] + 15, still inside n_text_ctx and still overwritten by the decode before a query reads them.  A table that is set is laid
+ * out again for the new size; the results agree with chunk 8 within the decoder's rounding (the GEMMs see other row counts), not
+ * bit for bit.  ohw_decode / ohw_decode_active keep their limit of 8 tokens per window, ohw_state_align replays in chunks of 8.
+ * ohw_state_prefill_chunk reads the setting back.  ohw_engine_set_prefill_chunk: the setting on the engine's own, pipeline and
+ * lane states, those made later included.                                                                                    */
+int ohw_state_set_prefill_chunk(ohw_state* st, int positions);
+int ohw_state_prefill_chunk(const ohw_state* st);
 /* text -> token ids, the scheme of whisper.cpp's tokenizer restated (csrc/tokenize.cpp states the rule): the text is split into
  * pieces (contractions; an optional space and a run of letters, of digits, or of other non-space bytes; runs of white space), and
  * inside a piece the longest vocabulary entry that is a prefix of the rest is taken, again and again; a byte no entry starts
@@ -746,6 +756,30 @@ int ohw_engine_set_audio_ctx(ohw_engine* e, int n);
  * T >= 0.5 and set again for the next batch.  Off by default: with no prompt ever set nothing takes a new path.             */
 int ohw_engine_set_initial_prompt(ohw_engine* e, const char* text);
 int ohw_engine_set_initial_prompt_tokens(ohw_engine* e, const int32_t* tokens, int n);
+/* carried context in the seek loops (whisper.cpp's prompt_past / n_max_text_ctx, as recalled): max_tokens 0 (default) = off,
+ * -1 = on with the full cap of ohw_prompt_clip_host, n > 0 = on with at most n tokens (whisper.cpp's --max-context); below -1:
+ * OHW_E_INVALID_ARG.  It applies to OHW_WINDOW_SEEK in ohw_engine_transcribe and to ohw_engine_transcribe_long_batch, one
+ * history per recording and call (in the long batch it follows the recording, not the slot).  The history starts as the initial
+ * prompt (which is then only its seed and scrolls away; it is not put in front of every window in addition); a window's T = 0
+ * pass and the ladder's passes below T = 0.5 decode behind the history's tail, the table is cleared before the first pass with
+ * T >= 0.5; after the window ohw_carry_step_host moves the history on.  In OHW_WINDOW_FIXED, OHW_WINDOW_FIXED_RECORDING_MEL and
+ * ohw_engine_transcribe_batch every cut or recording is its own whisper_full call: the setting has no effect there.
+ * ohw_pool_set_carry_context: the setting on every engine of the pool.
+ * ohw_engine_last_context: the context tokens ([prev] not included; n = 0: none) window `window` of the last
+ * ohw_engine_transcribe was decoded behind at T = 0 - with carry off, the initial prompt; a window out of range:
+ * OHW_E_INVALID_ARG.  ohw_engine_long_batch_context: the same for window `window` of recording `rec` of the last long batch.
+ * ohw_carry_step_host (host only, the function the engine itself calls): history [n_text_ctx / 2] holds *n_history tokens, oldest
+ * first.  First the window's kept pass is applied: kept_temperature >= 0.5 clears the history (that pass ran without [prev]),
+ * then kept[0 .. n_kept) - what the window contributed to the tokens of the result, timestamp tokens included - is appended and
+ * the history keeps its last n_text_ctx / 2 tokens.  Then the next window's context is written to context_out
+ * [n_text_ctx / 2 - 1]: with max_tokens = 0 nothing, else the tail ohw_prompt_clip_host keeps, cut to its last max_tokens when
+ * max_tokens > 0.  n_kept = 0 at temperature 0 only derives the context (the first window of a call).                      */
+int ohw_engine_set_prefill_chunk(ohw_engine* e, int positions);     /* ohw_state_set_prefill_chunk on every state of the engine */
+int ohw_engine_set_carry_context(ohw_engine* e, int max_tokens);
+int ohw_engine_last_context(ohw_engine* e, int window, const int32_t** tokens, int* n);
+int ohw_engine_long_batch_context(ohw_engine* e, int rec, int window, const int32_t** tokens, int* n);
+int ohw_carry_step_host(int32_t* history, int* n_history, int n_text_ctx, const int32_t* kept, int n_kept, float kept_temperature,
+                        int max_tokens, int32_t* context_out, int* n_context_out);
 /* ohw_state_set_packed_encoder on the engine's own, pipeline and lane states, those made later included (default: what
  * OHW_ENC_PACKED gave the engine's own state).  It matters for ohw_engine_transcribe_batch under the auto context (-1): a
  * batch of mixed lengths then encodes the sum of its contexts; tokens, text and quality records do not change.             */
@@ -807,7 +841,8 @@ void ohw_seek_sched_free(ohw_seek_sched* s);
  * end and generator, the alignment when word timestamps are on, then each window's records with its offset seek * 0.01 s.  Each
  * recording is one whisper_full call in whisper.cpp terms: its own std::mt19937(0) across all its windows, its own frame count
  * as the end of the audio, the full audio context (ohw_engine_set_audio_ctx does not apply), the initial prompt in front of every
- * window.  Language: lang_ids as in ohw_engine_transcribe_batch_lang (NULL: the engine's language, or - with
+ * window - or, under ohw_engine_set_carry_context, the recording's own carried history, which follows the recording and not its
+ * slot.  Language: lang_ids as in ohw_engine_transcribe_batch_lang (NULL: the engine's language, or - with
  * ohw_engine_set_detect_language - one detection per recording, on its first window, read back once and kept for its later ones).
  * CONTRACT: recording i's text, tokens, per-window quality records (seek_delta and temperature included), segments, token and
  * word times and language are exactly those of ohw_engine_transcribe on it alone in OHW_WINDOW_SEEK at the full audio context
@@ -878,6 +913,7 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
 int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text);           /* ohw_engine_set_initial_prompt on every engine */
+int ohw_pool_set_carry_context(ohw_pool* p, int max_tokens);              /* ohw_engine_set_carry_context on every engine */
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
 int ohw_pool_set_packed_encoder(ohw_pool* p, int on);
 int ohw_pool_set_detect_language(ohw_pool* p, int on);                     /* ohw_engine_set_detect_language on every engine */                     /* ohw_engine_set_packed_encoder on every engine */
@@ -957,6 +993,10 @@ int ohw_dbg_cross_attn(int dtype, const void* q, const void* xk, const void* xv,
  *   1 .. t_len.                                                                                                             */
 int ohw_dbg_cross_attn_chunk(int dtype, const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
                              const int32_t* win_len_host, const int32_t* done_host, void* stream);
+/* the same with n_q = 8 or 16 query rows per window (q [windows * n_q][d], row b * n_q + i; out ceil(windows * n_q / 16) tiles);
+ * another n_q: OHW_E_INVALID_ARG.  ohw_dbg_cross_attn_chunk is n_q = 8.                                                       */
+int ohw_dbg_cross_attn_chunk_n(int dtype, const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
+                               const int32_t* win_len_host, const int32_t* done_host, void* stream, int n_q);
 int ohw_dbg_self_attn(int dtype, const void* q, const void* k_cache, const void* v_cache, const int32_t* n_past_host, void* out, int M,
                       int n_new, int n_head, int n_ctx, const int32_t* kv_slot_host, int* variant_out, void* stream);
 /* The alignment kernels on caller data (tests/test_gpu_align.py).

@@ -149,6 +149,12 @@ def main(argv=None) -> int:
     many = sub.add_parser("transcribe-many", help="several recordings of any length in one call, each through whisper.cpp's seek loop, one "
                                                   "window of every recording per decode batch; prints one JSON object per line, in argument order")
     many.add_argument("files", nargs="+", metavar="FILE")
+    many.add_argument("--carry-context", action="store_true",
+                      help="decode every window behind the text of the recording's earlier windows (whisper.cpp's default; off by default "
+                           "here); --prompt then only seeds that history.  The contexts are not part of the JSON")
+    many.add_argument("--max-context", type=_max_context_arg, default=-1, metavar="N",
+                      help="with --carry-context: at most N tokens of earlier text (whisper.cpp's --max-context); -1 (default): up to half "
+                           "the model's text context")
     for sp_ in (t, many):
         _add_transcribe_options(sp_)
     args = ap.parse_args(argv)
@@ -204,6 +210,16 @@ def _beam_size_arg(v: str) -> int:
     return k
 
 
+def _max_context_arg(v: str) -> int:
+    try:
+        n = int(v)
+    except ValueError:
+        n = -2
+    if n < -1:
+        raise argparse.ArgumentTypeError(f"takes -1 (the model's cap) or a token count, not '{v}'")
+    return n
+
+
 def _check_beam(args) -> bool:
     """--beam-size against the other options, before any model is loaded"""
     if args.beam_size == 0:
@@ -241,6 +257,9 @@ def _transcribe_many(args) -> int:
     align_heads = _align_heads(args)
     if align_heads is None or not _check_beam(args):
         return 1
+    if args.max_context != -1 and not args.carry_context:
+        print("error: --max-context limits the carried context; it needs --carry-context", file=sys.stderr)
+        return 1
     from . import engine as E
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         print("error: transcribe-many is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
@@ -271,6 +290,8 @@ def _transcribe_many(args) -> int:
         eng.set_initial_prompt(args.prompt)
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
+    if args.carry_context and args.max_context != 0:      # --max-context 0 carries nothing, as in whisper.cpp
+        eng.set_carry_context(args.max_context)
     if args.packed_encoder:
         eng.set_packed_encoder(True)
     if args.detect_language:

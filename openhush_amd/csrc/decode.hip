@@ -1228,19 +1228,25 @@ int launch_cross_attn(const void* q, const void* xk, const void* xv, void* out, 
 // loaded from the last valid row (finite data) and masked to -inf before the maximum; a wave only enters blocks that hold a
 // valid key, so its maximum is finite from its first block on, and a wave without blocks keeps (-inf, 0), which the merge
 // of the 4 waves' states (as in cross_attn_rows_kernel) gives weight 0.
+// NQ = 16 (ohw_state_set_prefill_chunk: 16-position chunks): the window's rows b * 16 + c fill all 16 columns of the B operand, so
+// no MFMA column idles and a prefill streams the weights and every window's K/V half as often.  A query's arithmetic (its
+// column of S^T, its running maximum over its own 4 lanes, its column of O^T) never reads another column, so rows 0..7 see
+// what they see at NQ = 8; the merge state holds 16 rows (16 KB + 0.5 KB next to the 20 KB of V images).  NQ = 8 is the code
+// as it stood.
 // ------------------------------------------------------------------------------------------------
 constexpr int XAC_KB = 32;                 // keys per wave and block
 constexpr int XAC_VROW = 160;              // bytes per V row in LDS (128 of data)
 
-template <typename T, bool VAR>
+template <typename T, int NQ, bool VAR>
 __global__ __launch_bounds__(XA_THREADS) void cross_attn_chunk_kernel(const T* __restrict__ q, const T* __restrict__ xk, const T* __restrict__ xv,
                                                                       T* __restrict__ out, int n_head, int t_len,
                                                                       const int32_t* __restrict__ done, const int32_t* __restrict__ win_len) {
   using Ops = TypeOps<T>;
   using vec8 = typename Ops::vec8;
   __shared__ __attribute__((aligned(16))) unsigned char vimg[4][XAC_KB * XAC_VROW];
-  __shared__ float red_m[4][8], red_l[4][8];
-  __shared__ float red_o[4][8][64];
+  static_assert(NQ == 8 || NQ == 16, "a chunk holds 8 or 16 query rows: the columns of one 16-column MFMA tile");
+  __shared__ float red_m[4][NQ], red_l[4][NQ];
+  __shared__ float red_o[4][NQ][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = blockIdx.x, b = blockIdx.y;
   if (done && done[b]) return;
@@ -1256,7 +1262,7 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_chunk_kernel(const T* _
   for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) qf[ks][e] = (T)0.f;
-    if (c < 8) qf[ks] = *(const vec8*)(q + (int64_t)(b * 8 + c) * d + h * 64 + ks * 32 + g * 8);
+    if (c < NQ) qf[ks] = *(const vec8*)(q + (int64_t)(b * NQ + c) * d + h * 64 + ks * 32 + g * 8);
   }
 
   f32x4 oacc[4];
@@ -1348,10 +1354,10 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_chunk_kernel(const T* _
       oacc[dt] = Ops::mfma16(vt.v, pf.v, oacc[dt]);
     }
   }
-  // the query's sum over its 4 lanes (they share m_run), then this wave's state of the 8 real rows
+  // the query's sum over its 4 lanes (they share m_run), then this wave's state of the NQ real rows
   l_run += __shfl_xor(l_run, 16, 64);
   l_run += __shfl_xor(l_run, 32, 64);
-  if (c < 8) {
+  if (c < NQ) {
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
@@ -1359,8 +1365,8 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_chunk_kernel(const T* _
     if (g == 0) { red_m[wave][c] = m_run; red_l[wave][c] = l_run; }
   }
   __syncthreads();
-  // thread -> rows tid / 64 and tid / 64 + 4, column tid % 64
-  for (int i = wave; i < 8; i += 4) {
+  // thread -> rows tid / 64, tid / 64 + 4, .. below NQ, column tid % 64
+  for (int i = wave; i < NQ; i += 4) {
     const float mn = fmaxf(fmaxf(red_m[0][i], red_m[1][i]), fmaxf(red_m[2][i], red_m[3][i]));
     float l = 0.f, o = 0.f;
 #pragma unroll
@@ -1369,19 +1375,25 @@ __global__ __launch_bounds__(XA_THREADS) void cross_attn_chunk_kernel(const T* _
       l += red_l[w][i] * a;
       o += red_o[w][i][lane] * a;
     }
-    out[act_tiled_offset(b * 8 + i, h * 64 + lane, d)] = (T)(o / l);
+    out[act_tiled_offset(b * NQ + i, h * 64 + lane, d)] = (T)(o / l);
   }
+}
+
+template <typename T, int NQ>
+static void launch_xa_chunk(const dim3 grid, const T* q, const T* xk, const T* xv, T* out, int n_head, int t_len, const int32_t* done, const int32_t* win_len,
+                            hipStream_t s) {
+  if (win_len) hipLaunchKernelGGL((cross_attn_chunk_kernel<T, NQ, true>), grid, dim3(XA_THREADS), 0, s, q, xk, xv, out, n_head, t_len, done, win_len);
+  else hipLaunchKernelGGL((cross_attn_chunk_kernel<T, NQ, false>), grid, dim3(XA_THREADS), 0, s, q, xk, xv, out, n_head, t_len, done, win_len);
 }
 
 template <typename T>
 void launch_cross_attn_chunk(const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len, const int32_t* done,
-                             const int32_t* win_len, hipStream_t s) {
+                             const int32_t* win_len, hipStream_t s, int n_q) {
   if (windows < 1 || n_head < 1 || t_len < 1) throw Error(OHW_E_INVALID_ARG, "cross-attention chunk: windows, n_head or t_len below 1");
+  if (n_q != 8 && n_q != 16) throw Error(OHW_E_INVALID_ARG, "cross-attention chunk: 8 or 16 query rows per window, got " + std::to_string(n_q));
   const dim3 grid(n_head, windows);
-  if (win_len)
-    hipLaunchKernelGGL((cross_attn_chunk_kernel<T, true>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len);
-  else
-    hipLaunchKernelGGL((cross_attn_chunk_kernel<T, false>), grid, dim3(XA_THREADS), 0, s, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len);
+  if (n_q == 16) launch_xa_chunk<T, 16>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s);
+  else launch_xa_chunk<T, 8>(grid, (const T*)q, (const T*)xk, (const T*)xv, (T*)out, n_head, t_len, done, win_len, s);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2411,7 +2423,7 @@ int launch_prompt_fill(const int32_t* lang, int32_t* step_tok, int batch, int so
   template int launch_self_attn<T>(const void*, const void*, const void*, const int32_t*, void*, int, int, int, int, hipStream_t, const int32_t*); \
   template int launch_cross_attn<T>(const void*, const void*, const void*, void*, int, int, int, int, float*, unsigned*, int, const int32_t*, hipStream_t, int, bool, const int32_t*); \
   template void launch_kv_prefix_move<T>(void*, int, int, int, int, int, int, int, hipStream_t); \
-  template void launch_cross_attn_chunk<T>(const void*, const void*, const void*, void*, int, int, int, const int32_t*, const int32_t*, hipStream_t);
+  template void launch_cross_attn_chunk<T>(const void*, const void*, const void*, void*, int, int, int, const int32_t*, const int32_t*, hipStream_t, int);
 INST(bf16_t)
 INST(f16_t)
 #undef INST

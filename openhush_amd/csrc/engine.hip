@@ -138,12 +138,16 @@ struct ohw_state {
   std::vector<int32_t> lang_ids;      // explicit id, else LANG_PENDING: what an encode uploads again
   DevBuf lang_tab, lang_prob;         // i32 [max_batch], f32 [max_batch][n_langs]
   // per-window text context (ohw_state_set_window_prompt).  wp_len: the positions the context of every decode-batch slot occupies
-  // (0, or its tokens + 1 for [prev]); empty: no table.  The table lives on the device, laid out as the prefill feeds it: wp_feed
-  // [chunk][table batch][8] tokens ([eot] in the surplus rows), wp_pos [chunk][max_batch] = 8 * chunk, wp_lens [max_batch]; wp_done
-  // [chunk][max_batch] is the done mask of the prefill under way (it depends on the call's active windows)
+  // (0, or its tokens + 1 for [prev]); empty: no table.  The table lives on the device, laid out as the prefill feeds it in chunks
+  // of Q = wp_chunk positions (ohw_state_set_prefill_chunk: 8 or 16): wp_feed [chunk][table batch][Q] tokens ([eot] in the surplus
+  // rows), wp_pos [chunk][max_batch] = Q * chunk, wp_lens [max_batch]; wp_done [chunk][max_batch] is the done mask of the prefill
+  // under way (it depends on the call's active windows).  A 16-position chunk is not two adjacent 8-position chunks, so the host
+  // keeps the contexts (wp_host: [prev] + tokens per slot) and lays the table out again when the chunk size changes
   std::vector<int32_t> wp_len;
+  std::vector<std::vector<int32_t>> wp_host;
   DevBuf wp_feed, wp_pos, wp_done, wp_lens;
   int wp_chunks = 0;                 // chunks the buffers hold: ceil(n_text_ctx / 2 / 8)
+  int wp_chunk = 8;                  // positions per prefill chunk
   bool prefill_xa = true;            // OHW_PREFILL_XA=0: the prefill's cross-attention through launch_cross_attn's kernels (A/B knob)
   int64_t tally_xchunk = 0;          // cross_attn_chunk_kernel launches (ohw_dbg_counter "xattn.chunk")
   bool gemm_small = false;  // OHW_GEMM_SMALL=1: short windows take the 64x64-tile encoder GEMM (gemm_small.hip; off until measured)
@@ -332,7 +336,7 @@ void state_alloc(ohw_state* st) {
   }
   st->xkv.alloc((size_t)2 * L * B * H * T * 64 * 2);
   st->self_kv.alloc((size_t)L * 2 * B * H * hp.n_text_ctx * 64 * 2, true);
-  st->m_max = (int)B * 8;
+  st->m_max = (int)B * 16;      // a 16-position prefill chunk of every window; the decode entries keep to 8 tokens per window
   st->dx.alloc((size_t)st->m_max * dt * 4);
   // dy / da / df are read as 16-row activation tiles by 32-row workgroups: whole tiles, zeroed once (rows past M are
   // multiplied but never stored)
@@ -362,7 +366,7 @@ void state_alloc(ohw_state* st) {
   st->lang_prob.alloc((size_t)B * std::max(1, c->tok.n_langs) * 4, true);
   st->attn_ticket.alloc((size_t)hp.n_text_head * 4, true);
   st->wp_chunks = (hp.n_text_ctx / 2 + 7) / 8;
-  st->wp_feed.alloc((size_t)st->wp_chunks * B * 8 * 4, true);
+  st->wp_feed.alloc((size_t)((hp.n_text_ctx / 2 + 15) / 16) * 16 * B * 4, true);      // whole chunks of either size
   st->wp_pos.alloc((size_t)st->wp_chunks * B * 4, true);
   st->wp_done.alloc((size_t)st->wp_chunks * B * 4, true);
   st->wp_lens.alloc((size_t)B * 4, true);
@@ -558,7 +562,7 @@ void run_encode(ohw_state* st, int B, int first, int total) {
 // kv_group > 1 (beam search): B rows are kv_group beams per window - cross K/V is per window, self K/V goes through kv_slot,
 // win_done flags whole windows
 // want_logits = false (the prefill's chunks): the pass ends behind the last layer - only the self K/V it leaves in the cache is wanted
-// chunk_xa (the prefill's chunks, n_new = 8): cross-attention through cross_attn_chunk_kernel under the rule of the rows path
+// chunk_xa (the prefill's chunks, n_new = 8 or 16): cross-attention through cross_attn_chunk_kernel under the rule of the rows path
 template <typename T>
 void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = nullptr, int kv_group = 1, const int32_t* kv_slot = nullptr,
                       const int32_t* win_done = nullptr, bool want_logits = true, bool chunk_xa = false) {
@@ -568,7 +572,7 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
   // Tn: keys per cross-attention = the context of the last encode (the entries refuse a call under another one)
   const int d = hp.n_text_state, H = hp.n_text_head, C = hp.n_text_ctx, Tn = st->enc_ctx, L = hp.n_text_layer;
   const int M = B * n_new;
-  if (M > st->m_max) throw Error(OHW_E_INVALID_ARG, "decode: batch * n_new exceeds the state's capacity (8 tokens per window per call)");
+  if (M > st->m_max) throw Error(OHW_E_INVALID_ARG, "decode: batch * n_new exceeds the state's capacity (16 tokens per window per call)");
   const int32_t* n_past = st->n_past.as<int32_t>();
   const bool pn = st->postnorm;
   // ---- at most 16 single-token rows: the 32 layers in ONE persistent launch (decode_persist.hip) instead of 8 launches per
@@ -678,7 +682,7 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     {
       // algorithmic bytes: K and V of every (query row, head); the prompt pass streams them once per (window, head)
       // for all its rows (cross_attn_rows_kernel: same condition as launch_cross_attn)
-      const bool chunk_path = chunk_xa && st->prefill_xa && n_new == 8 && kv_group == 1 && ((int64_t)B * H >= 256 || st->batch_invariant || var);
+      const bool chunk_path = chunk_xa && st->prefill_xa && (n_new == 8 || n_new == 16) && kv_group == 1 && ((int64_t)B * H >= 256 || st->batch_invariant || var);
       const bool rows_path = chunk_path || (n_new >= 2 && n_new <= 4 && ((int64_t)B * H >= 256 || st->batch_invariant || var));
       // (window, head) streams x keys: under per-window contexts the sum of the windows' own lengths
       double xa_keys = (double)(kv_group > 1 ? B / kv_group : rows_path ? B : M) * Tn;
@@ -690,7 +694,7 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
       ProfScope psx(st, OHW_PROF_DEC_XATTN, 2.0 * 2.0 * xa_keys * H * 64.0);
       if (chunk_path) {
         launch_cross_attn_chunk<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab, st->da.p, B, H, Tn,
-                                   st->skip_done ? st->done.as<int32_t>() : nullptr, var ? st->wc_dec.as<int32_t>() : nullptr, s);
+                                   st->skip_done ? st->done.as<int32_t>() : nullptr, var ? st->wc_dec.as<int32_t>() : nullptr, s, n_new);
         ++st->tally_xchunk;
       } else {
         ++st->tally_xattn[launch_cross_attn<T>(st->dq.p, (const T*)st->xkv.p + (int64_t)(2 * l) * xkv_slab, (const T*)st->xkv.p + (int64_t)(2 * l + 1) * xkv_slab,
@@ -709,11 +713,34 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
   gemm(DT_LOGITS, st->dy.p, nullptr, c->emb, none, st->logits.p, hp.n_vocab, d, DEPI_LOGITS, st->logits_ld);
 }
 
-// the text context of the table (ohw_state_set_window_prompt) through the decoder in chunks of 8 positions: chunk j feeds positions
-// 8j .. 8j + 7 of every window at n_past = 8j ([eot] where a window's context has ended: those rows write cache positions at or
-// past the window's length, which the decode overwrites one by one before a query reads them), and names the windows it has
-// nothing for - 8j >= len[b], or not active - in the done mask, so their cross K/V is not streamed.  No logits.  Leaves every
-// layer's self K/V of positions 0 .. len[b] - 1 in cache row b; st->n_past and st->done are the caller's to set afterwards.
+// the context table onto the device in the layout of the state's chunk size; host[b]: [prev] + the tokens of slot b, or empty
+void window_prompt_upload(ohw_state* st, const std::vector<std::vector<int32_t>>& host) {
+  const ohw_ctx* c = st->ctx;
+  const size_t Q = (size_t)st->wp_chunk, batch = host.size(), MB = (size_t)st->max_batch;
+  const size_t NC = ((size_t)c->hp.n_text_ctx / 2 + Q - 1) / Q;
+  std::vector<int32_t> feed(NC * batch * Q, c->tok.eot), pos(NC * MB), lens(MB, 0);
+  if (feed.size() * 4 > st->wp_feed.bytes || pos.size() * 4 > st->wp_pos.bytes) throw Error(OHW_E_INVALID_ARG, "window_prompt: the table exceeds its buffers");
+  for (size_t b = 0; b < batch; ++b) {
+    lens[b] = (int32_t)host[b].size();
+    for (size_t p = 0; p < host[b].size(); ++p) feed[((p / Q) * batch + b) * Q + p % Q] = host[b][p];
+  }
+  for (size_t j = 0; j < NC; ++j)
+    for (size_t b = 0; b < MB; ++b) pos[j * MB + b] = (int32_t)(Q * j);
+  HIP_CHECK(hipSetDevice(c->device));
+  // in stream order behind the kernels that still read the previous table; the sources are vectors of this call, so wait
+  HIP_CHECK(hipMemcpyAsync(st->wp_feed.p, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, st->stream));
+  HIP_CHECK(hipMemcpyAsync(st->wp_pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st->stream));
+  HIP_CHECK(hipMemcpyAsync(st->wp_lens.p, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, st->stream));
+  HIP_CHECK(hipStreamSynchronize(st->stream));
+  st->wp_len.assign(lens.begin(), lens.begin() + (long)batch);
+}
+
+// the text context of the table (ohw_state_set_window_prompt) through the decoder in chunks of Q = 8 or 16 positions
+// (ohw_state_set_prefill_chunk): chunk j feeds positions Qj .. Qj + Q - 1 of every window at n_past = Qj ([eot] where a window's
+// context has ended: those rows write cache positions at or past the window's length - at most len + Q - 1 <= n_text_ctx / 2 + 15,
+// inside n_text_ctx - which the decode overwrites one by one before a query reads them), and names the windows it has nothing
+// for - Qj >= len[b], or not active - in the done mask, so their cross K/V is not streamed.  No logits.  Leaves every layer's
+// self K/V of positions 0 .. len[b] - 1 in cache row b; st->n_past and st->done are the caller's to set afterwards.
 void run_prefill(ohw_state* st, int batch, const int32_t* active, const std::string& what) {
   if (st->wp_len.empty()) return;
   if ((int)st->wp_len.size() != batch)
@@ -722,13 +749,14 @@ void run_prefill(ohw_state* st, int batch, const int32_t* active, const std::str
   int max_len = 0;
   for (int b = 0; b < batch; ++b)
     if (!active || active[b]) max_len = std::max(max_len, st->wp_len[(size_t)b]);
-  const int nc = (max_len + 7) / 8;
+  const int Q = st->wp_chunk;
+  const int nc = (max_len + Q - 1) / Q;
   if (nc == 0) return;
   const size_t MB = (size_t)st->max_batch;
   hipStream_t s = st->stream;
   std::vector<int32_t> done((size_t)nc * MB, 1);
   for (int j = 0; j < nc; ++j)
-    for (int b = 0; b < batch; ++b) done[(size_t)j * MB + b] = ((active && !active[b]) || 8 * j >= st->wp_len[(size_t)b]) ? 1 : 0;
+    for (int b = 0; b < batch; ++b) done[(size_t)j * MB + b] = ((active && !active[b]) || Q * j >= st->wp_len[(size_t)b]) ? 1 : 0;
   HIP_CHECK(hipMemcpyAsync(st->wp_done.p, done.data(), done.size() * 4, hipMemcpyHostToDevice, s));
   struct SkipDone { bool& f; bool keep; explicit SkipDone(bool& r) : f(r), keep(r) { f = true; } ~SkipDone() { f = keep; } } skip_done(st->skip_done);
   Dispatch::run(st->ctx->dtype, [&](auto* tag) {
@@ -736,7 +764,7 @@ void run_prefill(ohw_state* st, int batch, const int32_t* active, const std::str
     for (int j = 0; j < nc; ++j) {
       HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_pos.as<int32_t>() + (size_t)j * MB, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
       HIP_CHECK(hipMemcpyAsync(st->done.p, st->wp_done.as<int32_t>() + (size_t)j * MB, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
-      run_decoder_step<T>(st, batch, 8, st->wp_feed.as<int32_t>() + (size_t)j * batch * 8, 1, nullptr, nullptr, false, true);
+      run_decoder_step<T>(st, batch, Q, st->wp_feed.as<int32_t>() + (size_t)j * batch * Q, 1, nullptr, nullptr, false, true);
     }
   });
   HIP_CHECK(hipStreamSynchronize(s));     // `done` is a stack-lifetime source
@@ -1874,12 +1902,13 @@ int ohw_state_set_window_lang(ohw_state* st, const int32_t* lang_ids, int batch)
 int ohw_state_set_window_prompt(ohw_state* st, const int32_t* tokens, int stride, const int32_t* n_tokens, int batch) {
   return guard([&] {
     if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
-    if (!tokens || batch == 0) { st->wp_len.clear(); return; }
+    if (!tokens || batch == 0) { st->wp_len.clear(); st->wp_host.clear(); return; }
     const ohw_ctx* c = st->ctx;
     const int C = c->hp.n_text_ctx, cap = C / 2 - 1;
     if (!n_tokens) throw Error(OHW_E_INVALID_ARG, "window_prompt: n_tokens is null");
     if (batch < 0 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "window_prompt: batch exceeds the state's max_batch");
-    if (cap < 1 || st->wp_chunks * 8 > C) throw Error(OHW_E_INVALID_ARG, "window_prompt: the model's text context is too short for a prompt");
+    if (cap < 1 || (C / 2 + st->wp_chunk - 1) / st->wp_chunk * st->wp_chunk > C)
+      throw Error(OHW_E_INVALID_ARG, "window_prompt: the model's text context is too short for a prompt");
     for (int b = 0; b < batch; ++b) {
       if (n_tokens[b] < 0 || n_tokens[b] > cap)
         throw Error(OHW_E_INVALID_ARG, "window_prompt: window " + std::to_string(b) + " has " + std::to_string(n_tokens[b]) + " context tokens (0.." +
@@ -1892,25 +1921,38 @@ int ohw_state_set_window_prompt(ohw_state* st, const int32_t* tokens, int stride
                                              " is outside 0.." + std::to_string(c->hp.n_vocab - 1));
       }
     }
-    const size_t NC = (size_t)st->wp_chunks, MB = (size_t)st->max_batch;
-    std::vector<int32_t> feed(NC * batch * 8, c->tok.eot), pos(NC * MB), lens(MB, 0);
+    std::vector<std::vector<int32_t>> host((size_t)batch);
     for (int b = 0; b < batch; ++b) {
-      const int n = n_tokens[b];
-      lens[(size_t)b] = n > 0 ? n + 1 : 0;
-      for (int p = 0; p < lens[(size_t)b]; ++p)
-        feed[((size_t)(p / 8) * batch + b) * 8 + p % 8] = p == 0 ? c->tok.prev : tokens[(size_t)b * stride + p - 1];
+      if (n_tokens[b] == 0) continue;
+      host[(size_t)b].push_back(c->tok.prev);
+      host[(size_t)b].insert(host[(size_t)b].end(), tokens + (size_t)b * stride, tokens + (size_t)b * stride + n_tokens[b]);
     }
-    for (size_t j = 0; j < NC; ++j)
-      for (size_t b = 0; b < MB; ++b) pos[j * MB + b] = (int32_t)(8 * j);
-    HIP_CHECK(hipSetDevice(c->device));
-    // in stream order behind the kernels that still read the previous table; the sources are vectors of this call, so wait
-    HIP_CHECK(hipMemcpyAsync(st->wp_feed.p, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, st->stream));
-    HIP_CHECK(hipMemcpyAsync(st->wp_pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st->stream));
-    HIP_CHECK(hipMemcpyAsync(st->wp_lens.p, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, st->stream));
-    HIP_CHECK(hipStreamSynchronize(st->stream));
-    st->wp_len.assign(lens.begin(), lens.begin() + batch);
+    window_prompt_upload(st, host);
+    st->wp_host = std::move(host);
   });
 }
+
+int ohw_state_set_prefill_chunk(ohw_state* st, int positions) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    if (positions != 8 && positions != 16) throw Error(OHW_E_INVALID_ARG, "set_prefill_chunk: 8 or 16 positions, got " + std::to_string(positions));
+    if (positions == st->wp_chunk) return;
+    const int C = st->ctx->hp.n_text_ctx;
+    if ((C / 2 + positions - 1) / positions * positions > C)
+      throw Error(OHW_E_INVALID_ARG, "set_prefill_chunk: the model's text context is too short for chunks of " + std::to_string(positions));
+    st->wp_chunk = positions;
+    if (!st->wp_len.empty()) {
+      try {
+        window_prompt_upload(st, st->wp_host);
+      } catch (...) {
+        st->wp_chunk = positions == 8 ? 16 : 8;
+        throw;
+      }
+    }
+  });
+}
+
+int ohw_state_prefill_chunk(const ohw_state* st) { return st ? st->wp_chunk : OHW_E_INVALID_ARG; }
 
 int ohw_state_window_prompt_len(const ohw_state* st, int window) {
   if (!st || window < 0 || window >= st->max_batch) return OHW_E_INVALID_ARG;
@@ -2824,8 +2866,14 @@ int ohw_dbg_cross_attn(int dtype, const void* q, const void* xk, const void* xv,
 
 int ohw_dbg_cross_attn_chunk(int dtype, const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
                              const int32_t* win_len_host, const int32_t* done_host, void* stream) {
+  return ohw_dbg_cross_attn_chunk_n(dtype, q, xk, xv, out, windows, n_head, t_len, win_len_host, done_host, stream, 8);
+}
+
+int ohw_dbg_cross_attn_chunk_n(int dtype, const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
+                               const int32_t* win_len_host, const int32_t* done_host, void* stream, int n_q) {
   return guard([&] {
     dbg_check_dtype(dtype, "dbg_cross_attn_chunk");
+    if (n_q != 8 && n_q != 16) throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn_chunk: n_q is 8 or 16, got " + std::to_string(n_q));
     if (!q || !xk || !xv || !out || windows < 1 || n_head < 1 || t_len < 1)
       throw Error(OHW_E_INVALID_ARG, "dbg_cross_attn_chunk: null buffer, or windows, n_head or t_len below 1");
     for (int w = 0; win_len_host && w < windows; ++w)
@@ -2837,7 +2885,7 @@ int ohw_dbg_cross_attn_chunk(int dtype, const void* q, const void* xk, const voi
     Dispatch::run(dtype, [&](auto* tag) {
       using TT = std::remove_pointer_t<decltype(tag)>;
       launch_cross_attn_chunk<TT>(q, xk, xv, out, windows, n_head, t_len, done_host ? done.as<int32_t>() : nullptr,
-                                  win_len_host ? len.as<int32_t>() : nullptr, (hipStream_t)stream);
+                                  win_len_host ? len.as<int32_t>() : nullptr, (hipStream_t)stream, n_q);
     });
     HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   });

@@ -257,7 +257,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
     e->last_tokens.clear();
     e->last_quality.clear();
     e->last_trace.clear();
-    e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
+    e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear(); e->last_contexts.clear();
     const int max_tok = e->ctx->hp.n_text_ctx;
     const int V = e->ctx->hp.n_vocab;
     const int n_max = sp.n_max;
@@ -289,7 +289,44 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
     // the initial prompt (ohw_engine_set_initial_prompt) as the context of every window of the batch; with none set and none
     // ever set, nothing is called.  The ladder clears the table before its first pass with T >= 0.5 (whisper.cpp's rule, as
     // recalled), so every batch sets it again here
+    // carried context (ohw_engine_set_carry_context; the seek loops only): one history per recording of the call, seeded with the
+    // initial prompt and moved on by ohw_carry_step_host after every window; `next` is what the recording's next window decodes
+    // behind at T = 0.  round_ctx[b]: the context of decode-batch entry b of the round being decoded
+    const bool carrying = e->carry_max != 0 && e->window_mode == OHW_WINDOW_SEEK;
+    struct Carry { std::vector<int32_t> hist, next; int n_hist = 0; };
+    std::vector<const std::vector<int32_t>*> round_ctx;
+    const std::vector<int32_t>* emit_ctx = nullptr;         // what emit() records as the window's context (null: the initial prompt)
+    auto carry_step = [&](Carry& c, const int32_t* kept, int n_kept, float temp) {
+      std::vector<int32_t> out((size_t)std::max(1, max_tok / 2));
+      int n_out = 0;
+      const int rc = ohw_carry_step_host(c.hist.data(), &c.n_hist, max_tok, kept, n_kept, temp, e->carry_max, out.data(), &n_out);
+      if (rc != OHW_OK) throw Error(rc, "carry_context: " + g_last_error);
+      c.next.assign(out.begin(), out.begin() + n_out);
+    };
+    auto carry_init = [&](Carry& c) {
+      c.hist.assign((size_t)std::max(1, max_tok / 2), 0);
+      c.n_hist = (int)std::min(e->prompt.size(), c.hist.size());
+      std::copy(e->prompt.end() - c.n_hist, e->prompt.end(), c.hist.begin());
+      carry_step(c, nullptr, 0, 0.f);
+    };
     auto apply_prompt = [&](ohw_state* st, int B) {
+      if (carrying) {
+        // a slot whose history is empty gets count 0; a round in which every history is empty runs with no table at all
+        size_t np = 0;
+        for (int b = 0; b < B; ++b) np = std::max(np, round_ctx[(size_t)b]->size());
+        if (np == 0) {
+          if (e->prompt_used) check(ohw_state_set_window_prompt(st, nullptr, 0, nullptr, 0));
+          return;
+        }
+        std::vector<int32_t> tab((size_t)B * np, 0), cnt((size_t)B, 0);
+        for (int b = 0; b < B; ++b) {
+          cnt[(size_t)b] = (int32_t)round_ctx[(size_t)b]->size();
+          std::copy(round_ctx[(size_t)b]->begin(), round_ctx[(size_t)b]->end(), tab.begin() + (long)((size_t)b * np));
+        }
+        e->prompt_used = true;
+        check(ohw_state_set_window_prompt(st, tab.data(), (int)np, cnt.data(), B));
+        return;
+      }
       if (e->prompt.empty()) {
         if (e->prompt_used) check(ohw_state_set_window_prompt(st, nullptr, 0, nullptr, 0));
         return;
@@ -399,7 +436,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         const bool is_last = ti + 1 == temps.size();
         std::vector<WindowRun> pass((size_t)B);
         // passes with T < 0.5 decode behind the context; from the first pass with T >= 0.5 on the table is gone
-        if (T >= 0.5f && !e->prompt.empty()) check(ohw_state_set_window_prompt(st, nullptr, 0, nullptr, 0));
+        if (T >= 0.5f && (carrying || !e->prompt.empty())) check(ohw_state_set_window_prompt(st, nullptr, 0, nullptr, 0));
         if (e->fallback_device) {
           device_pass(sc, st, B, seek, seek_end, active, T, rngs, pass);
         } else {
@@ -531,6 +568,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       mark.n_words = (int32_t)(e->last_words.size() - wd0);
       mark.n_segments = (int32_t)(e->last_segments.size() - sg0);
       e->last_marks.push_back(mark);
+      e->last_contexts.push_back(emit_ctx ? *emit_ctx : e->prompt);
       ohw_window_quality q{};
       q.n_tokens = keep; q.avg_logprob = r.ev.avg_logprob; q.entropy = r.ev.entropy; q.would_fallback = r.t0_failed ? 1 : 0;
       q.temperature = r.temp; q.no_speech_prob = r.nosp; q.no_speech = no_speech ? 1 : 0; q.seek_delta = r.ev.seek_delta;
@@ -613,16 +651,22 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       struct Acc {
         std::string text; std::vector<int32_t> tokens; std::vector<ohw_window_quality> quality;
         std::vector<ohw_token_time> token_times; std::vector<ohw_span_time> words, segments; std::vector<ohw_engine::WindowMark> marks;
+        std::vector<std::vector<int32_t>> contexts;
       };
       std::vector<Acc> acc((size_t)n_recs);
       auto swap_acc = [&](Acc& a) {
         text.swap(a.text); e->last_tokens.swap(a.tokens); e->last_quality.swap(a.quality); e->last_token_times.swap(a.token_times);
         e->last_words.swap(a.words); e->last_segments.swap(a.segments); e->last_marks.swap(a.marks);
+        e->last_contexts.swap(a.contexts);
       };
       // a recording's language: the caller's id, or OHW_LANG_DETECT until its first window has been detected (with no table: -1)
       std::vector<int32_t> rec_lang((size_t)n_recs, -1);
       if (per_rec) for (int i = 0; i < n_recs; ++i) rec_lang[(size_t)i] = rec_langs ? rec_langs[i] : OHW_LANG_DETECT;
       rngs.reset((size_t)n_recs);
+      // a history follows its recording, not the slot: a refilled slot starts from its new recording's own history
+      std::vector<Carry> carry((size_t)(carrying ? n_recs : 0));
+      for (Carry& c : carry) carry_init(c);
+      round_ctx.assign((size_t)MB, nullptr);
       Scratch sc(MB, max_tok);
       std::vector<int32_t> r_rec((size_t)MB), r_slot((size_t)MB), r_seek((size_t)MB), r_fresh((size_t)MB);
       std::vector<int> seeks((size_t)MB), ends((size_t)MB), frames((size_t)MB);
@@ -638,6 +682,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
           ends[(size_t)b] = mel_frames(recs[i].n);
           frames[(size_t)b] = std::min(CHUNK_FRAMES, ends[(size_t)b] - seeks[(size_t)b]);
           round_rngs[(size_t)b] = rngs.v[(size_t)i];
+          if (carrying) round_ctx[(size_t)b] = &carry[(size_t)i].next;
         }
         check(ohw_mel_seek_slots(e->state, r_slot.data(), r_seek.data(), B, nullptr));
         check(ohw_encode(e->state, B));
@@ -664,11 +709,14 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
           const int i = r_rec[(size_t)b];
           const WindowRun& r = sc.runs[(size_t)b];
           swap_acc(acc[(size_t)i]);
+          emit_ctx = carrying ? round_ctx[(size_t)b] : nullptr;
           emit(r, seeks[(size_t)b] * 0.01, std::min(seeks[(size_t)b] * 0.01 + 30.0, (double)recs[i].n / 16000.0));
           swap_acc(acc[(size_t)i]);
-          check(ohw_seek_sched_advance(sched_raw, b, r.ev.seek_delta));
+          if (carrying) carry_step(carry[(size_t)i], r.tok.data(), kept_tokens(r), r.temp);
+            check(ohw_seek_sched_advance(sched_raw, b, r.ev.seek_delta));
         }
       }
+      if (carrying) check(ohw_state_set_window_prompt(e->state, nullptr, 0, nullptr, 0));
       for (int i = 0; i < n_recs; ++i) {
         Acc& a = acc[(size_t)i];
         ohw_engine::BatchRecord& r = e->batch_records[(size_t)i];
@@ -676,14 +724,14 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         r.text = b0 == std::string::npos ? std::string() : a.text.substr(b0, b1 - b0 + 1);
         trim_spans(a.words, b0 == std::string::npos ? 0 : b0, r.text.size());
         trim_spans(a.segments, b0 == std::string::npos ? 0 : b0, r.text.size());
-        r.tokens = std::move(a.tokens); r.qualities = std::move(a.quality);
+        r.tokens = std::move(a.tokens); r.qualities = std::move(a.quality); r.contexts = std::move(a.contexts);
         r.token_times = std::move(a.token_times); r.words = std::move(a.words); r.segments = std::move(a.segments);
         if (!r.qualities.empty()) r.quality = r.qualities[0];
         // a recording that never ran a window (under 1 s) was never detected: id 0, as the single loop reports it
         r.lang_id = !per_rec ? -1 : rec_lang[(size_t)i] == OHW_LANG_DETECT ? 0 : rec_lang[(size_t)i];
       }
       text.clear(); e->last_tokens.clear(); e->last_quality.clear();
-      e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
+      e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear(); e->last_contexts.clear();
       return;
     }
     if (recs) {
@@ -747,7 +795,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         sc.trace.clear();
         for (int b = 0; b < B; ++b) {
           text.clear(); e->last_tokens.clear(); e->last_quality.clear();
-          e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
+          e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear(); e->last_contexts.clear();
           emit(sc.runs[(size_t)b], 0.0, (double)recs[ord[b]].n / 16000.0);
           ohw_engine::BatchRecord& r = e->batch_records[(size_t)ord[b]];
           const size_t b0 = text.find_first_not_of(" \t\r\n"), b1 = text.find_last_not_of(" \t\r\n");
@@ -761,7 +809,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         }
       }
       text.clear(); e->last_tokens.clear(); e->last_quality.clear();
-      e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear();
+      e->last_token_times.clear(); e->last_words.clear(); e->last_segments.clear(); e->last_marks.clear(); e->last_contexts.clear();
       return;
     }
     if (e->window_mode == OHW_WINDOW_SEEK) {
@@ -769,6 +817,8 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
       // generator for the whole call
       rngs.reset(1);
       Scratch sc(1, max_tok);
+      Carry carry;
+      if (carrying) { carry_init(carry); round_ctx.assign(1, &carry.next); emit_ctx = &carry.next; }
       const int seek_end = mel_frames(n);
       int seek = 0;
       int64_t w = 0;
@@ -787,9 +837,11 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
         align_runs(sc, e->state, 1, &win_frames);
         flush_trace(sc);
         emit(sc.runs[0], seek * 0.01, std::min(seek * 0.01 + 30.0, (double)n / 16000.0));
+        if (carrying) carry_step(carry, sc.runs[0].tok.data(), kept_tokens(sc.runs[0]), sc.runs[0].temp);
         seek += sc.runs[0].ev.seek_delta > 0 ? sc.runs[0].ev.seek_delta : 3000;
         ++w;
       }
+      if (carrying && w > 0) check(ohw_state_set_window_prompt(e->state, nullptr, 0, nullptr, 0));
     } else {
       // host-side windowing: fixed 30 s cuts (BASELINE.json north_star).  Each cut is its own `full` call in
       // whisper.cpp terms: seek 0, its own frame count as the end of the audio, a fresh generator - and, like a call with
@@ -849,7 +901,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
           while (rc == OHW_OK && (int)e->states.size() < 2) {
             ohw_state* st = nullptr;
             rc = ohw_state_create(e->ctx, e->max_batch, &st);
-            if (rc == OHW_OK) { (void)ohw_state_set_packed_encoder(st, e->packed_encoder); e->states.push_back(st); }
+            if (rc == OHW_OK) { (void)ohw_state_set_packed_encoder(st, e->packed_encoder); (void)ohw_state_set_prefill_chunk(st, e->prefill_chunk); e->states.push_back(st); }
           }
         }
         if (rc == OHW_OK && schedule == OHW_SCHEDULE_PIPELINE && !e->s_enc) {
@@ -871,6 +923,7 @@ void engine_transcribe_core(ohw_engine* e, const float* samples, int64_t n, std:
             rc = ohw_state_create(e->ctx, e->lane_capacity, &st);
             if (rc == OHW_OK) {
               (void)ohw_state_set_packed_encoder(st, e->packed_encoder);
+              (void)ohw_state_set_prefill_chunk(st, e->prefill_chunk);
               state_set_graph_max_batch(st, 16);      // see engine.hip: a capture on a lane waits for the other lanes' decodes
               e->lane_states.push_back(st);
             }
@@ -1688,6 +1741,74 @@ int ohw_engine_set_initial_prompt(ohw_engine* e, const char* text) {
   const int n = ohw_tokenize(e->ctx, text, toks.data(), (int)toks.size());
   if (n < 0) return n;
   return ohw_engine_set_initial_prompt_tokens(e, toks.data(), n);
+}
+
+int ohw_engine_set_prefill_chunk(ohw_engine* e, int positions) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    auto set = [&](ohw_state* st) { const int rc = ohw_state_set_prefill_chunk(st, positions); if (rc != OHW_OK) throw Error(rc, g_last_error); };
+    set(e->state);
+    for (ohw_state* st : e->states) set(st);
+    for (ohw_state* st : e->lane_states) set(st);
+    e->prefill_chunk = positions;
+  });
+}
+
+int ohw_engine_set_carry_context(ohw_engine* e, int max_tokens) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (max_tokens < -1) throw Error(OHW_E_INVALID_ARG, "set_carry_context: 0 (off), -1 (the full cap) or a token count, got " + std::to_string(max_tokens));
+    e->carry_max = max_tokens;
+  });
+}
+
+int ohw_engine_last_context(ohw_engine* e, int window, const int32_t** tokens, int* n) {
+  return guard([&] {
+    if (!e || !tokens || !n) throw Error(OHW_E_INVALID_ARG, "last_context: null argument");
+    if (window < 0 || window >= (int)e->last_contexts.size())
+      throw Error(OHW_E_INVALID_ARG, "last_context: no window " + std::to_string(window) + " in the last transcribe");
+    *tokens = e->last_contexts[(size_t)window].data();
+    *n = (int)e->last_contexts[(size_t)window].size();
+  });
+}
+
+int ohw_engine_long_batch_context(ohw_engine* e, int rec, int window, const int32_t** tokens, int* n) {
+  return guard([&] {
+    if (!e || !tokens || !n) throw Error(OHW_E_INVALID_ARG, "long_batch_context: null argument");
+    if (rec < 0 || rec >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "long_batch_context: no recording " + std::to_string(rec) + " in the last batch call");
+    const ohw_engine::BatchRecord& r = e->batch_records[(size_t)rec];
+    if (window < 0 || window >= (int)r.contexts.size())
+      throw Error(OHW_E_INVALID_ARG, "long_batch_context: recording " + std::to_string(rec) + " has no window " + std::to_string(window));
+    *tokens = r.contexts[(size_t)window].data();
+    *n = (int)r.contexts[(size_t)window].size();
+  });
+}
+
+// host only; the seek loops of engine_transcribe_core call it after every window (include/ohw.h states the rule)
+int ohw_carry_step_host(int32_t* history, int* n_history, int n_text_ctx, const int32_t* kept, int n_kept, float kept_temperature,
+                        int max_tokens, int32_t* context_out, int* n_context_out) {
+  return guard([&] {
+    if (!history || !n_history || !n_context_out || n_text_ctx < 2 || n_kept < 0 || (n_kept > 0 && !kept) || max_tokens < -1)
+      throw Error(OHW_E_INVALID_ARG, "carry_step_host: bad argument");
+    const int half = n_text_ctx / 2;
+    if (*n_history < 0 || *n_history > half) throw Error(OHW_E_INVALID_ARG, "carry_step_host: the history holds 0 .. n_text_ctx / 2 tokens");
+    // a pass kept at T >= 0.5 ran without [prev]: the history starts again from this window alone
+    std::vector<int32_t> h;
+    if (kept_temperature < 0.5f) h.assign(history, history + *n_history);
+    if (n_kept > 0) h.insert(h.end(), kept, kept + n_kept);
+    const size_t drop = h.size() > (size_t)half ? h.size() - (size_t)half : 0;
+    std::copy(h.begin() + (long)drop, h.end(), history);
+    *n_history = (int)(h.size() - drop);
+    *n_context_out = 0;
+    if (max_tokens == 0 || *n_history == 0) return;
+    if (!context_out) throw Error(OHW_E_INVALID_ARG, "carry_step_host: context_out is null");
+    std::vector<int32_t> tail((size_t)*n_history);
+    const int k = ohw_prompt_clip_host(history, *n_history, n_text_ctx, tail.data());
+    if (k < 0) throw Error(OHW_E_INVALID_ARG, "carry_step_host: " + g_last_error);
+    const int take = max_tokens > 0 ? std::min(max_tokens, k) : k;
+    std::copy(tail.begin() + (k - take), tail.begin() + k, context_out);
+    *n_context_out = take;
+  });
 }
 
 int ohw_engine_set_packed_encoder(ohw_engine* e, int on) {

@@ -19,6 +19,11 @@ struct ohw_engine {
   // schedule; empty: none.  prompt_used: a prompt has been set at some time, so states may still hold a table to clear
   std::vector<int32_t> prompt;
   bool prompt_used = false;
+  // ohw_engine_set_carry_context: 0 off, -1 the full cap, n > 0 at most n tokens of the recording's earlier windows as context in
+  // the seek loops.  last_contexts: per window record of last_quality, what its T = 0 pass was decoded behind
+  int carry_max = 0;
+  int prefill_chunk = 8;                 // ohw_engine_set_prefill_chunk: every state of the engine, those made later too
+  std::vector<std::vector<int32_t>> last_contexts;
   int beam_size = 0;                     // ohw_engine_set_beam_size: 0 = greedy at T = 0, 2..5 = beam search (a decode batch then holds
                                          //   max_batch / beam_size windows, on the engine's own state)
   int force_len = 0;                     // measurement knob (ohw_engine_set_force_len): every window decodes exactly this many tokens
@@ -45,6 +50,7 @@ struct ohw_engine {
   struct BatchRecord {
     std::string text; std::vector<int32_t> tokens; ohw_window_quality quality{}; int32_t lang_id = -1;
     std::vector<ohw_window_quality> qualities;      // ohw_engine_transcribe_long_batch: one record per window (else empty)
+    std::vector<std::vector<int32_t>> contexts;     //   and the context every window's T = 0 pass was decoded behind
     std::vector<ohw_token_time> token_times; std::vector<ohw_span_time> words, segments;
   };
   std::vector<BatchRecord> batch_records;

@@ -139,10 +139,11 @@ template <typename T> int launch_cross_attn(const void* q, const void* xk, const
                                              bool batch_invariant = false /* pick the variant from n_new alone, never from M */,
                                              const int32_t* win_len = nullptr /* device [windows] or null: window w streams its first
                                                 win_len[w] keys of a slab whose stride stays t_len; implies batch_invariant's variant choice */);
-// the 8 query rows per window of one prefill chunk (ohw_state_prefill): q T [windows * 8][d], row b * 8 + i; one workgroup per
-// (head, window) streams K/V once for the 8 rows, both products on the MFMA units (cross_attn_chunk_kernel).  done / win_len as above
+// the n_q (8 or 16) query rows per window of one prefill chunk (ohw_state_prefill): q T [windows * n_q][d], row b * n_q + i; one
+// workgroup per (head, window) streams K/V once for the rows, both products on the MFMA units (cross_attn_chunk_kernel).  done /
+// win_len as above
 template <typename T> void launch_cross_attn_chunk(const void* q, const void* xk, const void* xv, void* out, int windows, int n_head, int t_len,
-                                                   const int32_t* done, const int32_t* win_len, hipStream_t s);
+                                                   const int32_t* done, const int32_t* win_len, hipStream_t s, int n_q = 8);
 
 // ---- the 32 decoder layers of a single-token step in ONE persistent launch, at most 16 rows (decode_persist.hip) ----------
 struct PersistLayer {

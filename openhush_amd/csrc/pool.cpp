@@ -327,6 +327,14 @@ int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text) {
   }
   return OHW_OK;
 }
+int ohw_pool_set_carry_context(ohw_pool* p, int max_tokens) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_carry_context(e, max_tokens);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
 int ohw_pool_set_packed_encoder(ohw_pool* p, int on) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {

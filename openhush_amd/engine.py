@@ -262,6 +262,8 @@ EXPORTS = [
     "ohw_recording_set_slot", "ohw_mel_seek_slots", "ohw_seek_sched_new", "ohw_seek_sched_round", "ohw_seek_sched_advance", "ohw_seek_sched_free",
     "ohw_engine_transcribe_long_batch", "ohw_engine_long_batch_quality",
     "ohw_dbg_dec_gemm", "ohw_dbg_embed", "ohw_dbg_layernorm",
+    "ohw_state_set_prefill_chunk", "ohw_state_prefill_chunk", "ohw_engine_set_prefill_chunk", "ohw_dbg_cross_attn_chunk_n",
+    "ohw_engine_set_carry_context", "ohw_pool_set_carry_context", "ohw_engine_last_context", "ohw_engine_long_batch_context", "ohw_carry_step_host",
 ]
 
 
@@ -501,6 +503,15 @@ def lib():
         L.ohw_engine_set_initial_prompt.argtypes = [vp, C.c_char_p]
         L.ohw_engine_set_initial_prompt_tokens.argtypes = [vp, ip, C.c_int]
         L.ohw_pool_set_initial_prompt.argtypes = [vp, C.c_char_p]
+        L.ohw_engine_set_carry_context.argtypes = [vp, C.c_int]
+        L.ohw_state_set_prefill_chunk.argtypes = [vp, C.c_int]
+        L.ohw_state_prefill_chunk.argtypes = [vp]
+        L.ohw_engine_set_prefill_chunk.argtypes = [vp, C.c_int]
+        L.ohw_dbg_cross_attn_chunk_n.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_int]
+        L.ohw_pool_set_carry_context.argtypes = [vp, C.c_int]
+        L.ohw_engine_last_context.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int)]
+        L.ohw_engine_long_batch_context.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int)]
+        L.ohw_carry_step_host.argtypes = [ip, C.POINTER(C.c_int), C.c_int, ip, C.c_int, C.c_float, C.c_int, ip, C.POINTER(C.c_int)]
         L.ohw_dbg_self_attn.argtypes = [C.c_int, vp, vp, vp, ip, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int), vp]
         L.ohw_dbg_dec_gemm.argtypes = [C.POINTER(DbgDecGemmIO), vp]
         L.ohw_dbg_embed.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, ip, ip, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
@@ -594,6 +605,23 @@ def prompt_clip(tokens: Sequence[int], n_text_ctx: int) -> List[int]:
     if n < 0:
         _raise(n)
     return [int(t) for t in out[:n]]
+
+
+def carry_step_host(history: Sequence[int], n_text_ctx: int, kept: Sequence[int], kept_temperature: float, max_tokens: int = -1):
+    """ohw_carry_step_host: the seek loops' carried-context rule, on the host.  Applies a window's kept pass to `history` (a pass
+    kept at T >= 0.5 clears it; the kept tokens, timestamps included, are appended; the last n_text_ctx / 2 stay), then derives the
+    next window's context (max_tokens: 0 none, -1 the full cap, n > 0 at most n).  Returns (new history, context)"""
+    half = max(int(n_text_ctx) // 2, 1)
+    if len(history) > half:
+        raise ValueError("carry_step_host: the history holds at most n_text_ctx / 2 tokens")
+    h = np.zeros(half, dtype=np.int32)
+    h[:len(history)] = list(history)
+    nh, nc = C.c_int(len(history)), C.c_int(0)
+    k = np.ascontiguousarray(list(kept) or [0], dtype=np.int32)
+    out = np.zeros(half, dtype=np.int32)
+    _check(lib().ohw_carry_step_host(_ip(h), C.byref(nh), int(n_text_ctx), _ip(k), len(kept), float(kept_temperature), int(max_tokens),
+                                     _ip(out), C.byref(nc)))
+    return [int(t) for t in h[:nh.value]], [int(t) for t in out[:nc.value]]
 
 
 def lang_pick_host(row: np.ndarray, tok: "SpecialTokens"):
@@ -1216,6 +1244,14 @@ class State:
         a = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
         _check(lib().ohw_state_prefill(self.h, int(batch), None if a is None else _ip(a)))
 
+    def set_prefill_chunk(self, positions: int):
+        """ohw_state_set_prefill_chunk: the prefill feeds the context in chunks of 8 (default) or 16 positions; a table that is set
+        is laid out again"""
+        _check(lib().ohw_state_set_prefill_chunk(self.h, int(positions)))
+
+    def prefill_chunk(self) -> int:
+        return int(lib().ohw_state_prefill_chunk(self.h))
+
     def detect_window_lang(self, batch: int):
         """ohw_state_detect_window_lang: resolve the table's pending entries for the windows of the last encode, on the device"""
         _check(lib().ohw_state_detect_window_lang(self.h, int(batch)))
@@ -1270,13 +1306,14 @@ class State:
 
     @staticmethod
     def dbg_cross_attn_chunk(dtype: int, q_ptr: int, xk_ptr: int, xv_ptr: int, out_ptr: int, windows: int, n_head: int, t_len: int,
-                             win_len: Optional[Sequence[int]] = None, done: Optional[Sequence[int]] = None, stream: Optional[int] = None):
-        """ohw_dbg_cross_attn_chunk: the prefill's cross-attention kernel on device buffers of the caller (8 query rows per window;
-        out in activation-tile order, pre-filled by the caller: the rows of a done window keep what they held)"""
+                             win_len: Optional[Sequence[int]] = None, done: Optional[Sequence[int]] = None, stream: Optional[int] = None,
+                             n_q: int = 8):
+        """ohw_dbg_cross_attn_chunk_n: the prefill's cross-attention kernel on device buffers of the caller (n_q = 8 or 16 query rows
+        per window; out in activation-tile order, pre-filled by the caller: the rows of a done window keep what they held)"""
         wl = None if win_len is None else np.ascontiguousarray(win_len, dtype=np.int32)
         dn = None if done is None else np.ascontiguousarray(done, dtype=np.int32)
-        _check(lib().ohw_dbg_cross_attn_chunk(int(dtype), q_ptr, xk_ptr, xv_ptr, out_ptr, int(windows), int(n_head), int(t_len),
-                                              None if wl is None else _ip(wl), None if dn is None else _ip(dn), stream))
+        _check(lib().ohw_dbg_cross_attn_chunk_n(int(dtype), q_ptr, xk_ptr, xv_ptr, out_ptr, int(windows), int(n_head), int(t_len),
+                                                None if wl is None else _ip(wl), None if dn is None else _ip(dn), stream, int(n_q)))
 
     def poison(self, what: str):
         """ohw_dbg_poison (tests): fill the encoder's "qkv" or "att" buffer with NaN"""
@@ -2002,6 +2039,32 @@ class WhisperEngine:
             a = np.ascontiguousarray(list(prompt) or [0], dtype=np.int32)
             _check(lib().ohw_engine_set_initial_prompt_tokens(self.h, _ip(a), len(prompt)))
 
+    def set_prefill_chunk(self, positions: int):
+        """ohw_engine_set_prefill_chunk: State.set_prefill_chunk on every state of the engine, those made later included"""
+        _check(lib().ohw_engine_set_prefill_chunk(self.h, int(positions)))
+
+    def set_carry_context(self, max_tokens: int = -1):
+        """ohw_engine_set_carry_context: in the seek loops (OHW_WINDOW_SEEK transcribe, transcribe_long_batch) every window is
+        decoded behind the tail of what the recording's earlier windows produced (whisper.cpp's default): -1 = up to the cap of
+        n_text_ctx / 2 - 1 tokens, n > 0 = at most n (--max-context), 0 = off (the default here).  The initial prompt then only seeds
+        the history.  No effect on fixed cuts and transcribe_batch, where every cut or recording is a call of its own"""
+        _check(lib().ohw_engine_set_carry_context(self.h, int(max_tokens)))
+
+    def _context(self, call) -> List[int]:
+        p, n = C.POINTER(C.c_int32)(), C.c_int(0)
+        _check(call(C.byref(p), C.byref(n)))
+        return [int(p[k]) for k in range(n.value)]
+
+    def last_contexts(self) -> List[List[int]]:
+        """ohw_engine_last_context per window of the last transcribe: the context tokens ([prev] not included) its T = 0 pass was
+        decoded behind; [] = none"""
+        return [self._context(lambda p, n, w=w: lib().ohw_engine_last_context(self.h, w, p, n)) for w in range(len(self.last_quality_ex()))]
+
+    def long_batch_contexts(self, i: int) -> List[List[int]]:
+        """ohw_engine_long_batch_context per window of recording i of the last transcribe_long_batch"""
+        return [self._context(lambda p, n, w=w: lib().ohw_engine_long_batch_context(self.h, int(i), w, p, n))
+                for w in range(len(self.long_batch_quality(i)))]
+
     def set_audio_ctx(self, n):
         """ohw_engine_set_audio_ctx: 0 (default, off), a fixed context n, or "auto" (audio_ctx_for(len) for a recording of at most
         one window, full context beyond); a fixed context that does not cover a window's audio fails the transcribe"""
@@ -2081,6 +2144,10 @@ class EnginePool:
     def set_initial_prompt(self, text):
         """ohw_pool_set_initial_prompt: WhisperEngine.set_initial_prompt(text) on every engine of the pool"""
         _check(lib().ohw_pool_set_initial_prompt(self.h, _text_bytes(text or "")))
+
+    def set_carry_context(self, max_tokens: int = -1):
+        """ohw_pool_set_carry_context: WhisperEngine.set_carry_context on every engine of the pool"""
+        _check(lib().ohw_pool_set_carry_context(self.h, int(max_tokens)))
 
     def set_audio_ctx(self, n):
         """ohw_pool_set_audio_ctx: WhisperEngine.set_audio_ctx on every engine of the pool"""

@@ -11,9 +11,12 @@ the slot front end and the scheduler - a gap larger than A1's own min-max spread
 
 One warm-up and --repeats timed repeats per leg; median and min-max audio-s/s, the ratio of the medians, the round count and
 the mean live batch size (replayed on ohw_seek_sched from the windows' seek deltas).  temperature_inc = 0 unless --ladder
-(the default policy's fallback ladder, sampled on the device).
+(the default policy's fallback ladder, sampled on the device).  --carry turns the carried context on for every leg
+(ohw_engine_set_carry_context(-1): every window after a recording's first pays a prefill); --chunk 16 runs those prefills in
+16-position chunks.
 
-  python tools/long_batch_probe.py [--recordings 32] [--min-s 45] [--max-s 300] [--max-batch 32] [--repeats 5] [--json out.json]
+  python tools/long_batch_probe.py [--recordings 32] [--min-s 45] [--max-s 300] [--max-batch 32] [--repeats 5] [--carry] [--chunk 8|16]
+                                     [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -37,6 +40,8 @@ def main():
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--ladder", action="store_true", help="whisper.cpp's default policy with the device ladder instead of temperature_inc = 0")
+    ap.add_argument("--carry", action="store_true", help="carried context on (set_carry_context(-1)) in every leg")
+    ap.add_argument("--chunk", type=int, default=8, choices=[8, 16], help="positions per prefill chunk (set_prefill_chunk)")
     ap.add_argument("--skip-single-slot", action="store_true", help="leave out the max_batch = 1 engine (legs A1 / B1)")
     ap.add_argument("--budget-s", type=float, default=0.0,
                     help="give up before the timed legs when one pass of leg A, estimated from the first recording, would take longer "
@@ -71,6 +76,9 @@ def main():
         E._check(L.ohw_state_set_logit_bias(eng.state_h, E._fp(bias), bias.size))
         eng.set_decode_policy(temperature_inc=None if args.ladder else 0.0)
         eng.set_fallback_on_device(True)
+        if args.carry:
+            eng.set_carry_context(-1)
+        eng.set_prefill_chunk(args.chunk)
         bufs = [E.AudioBuffer(p, 16000) for p in pcms]
 
         def leg_a():
@@ -149,7 +157,8 @@ def main():
         return out
 
     out = {"dims": "large-v3", "dtype": "bf16", "recordings": args.recordings, "seconds": [float(s) for s in secs], "audio_s": total_s,
-           "repeats": args.repeats, "policy": "default, device ladder" if args.ladder else "temperature_inc 0", "bias": "ts 6 / eot 27"}
+           "repeats": args.repeats, "policy": "default, device ladder" if args.ladder else "temperature_inc 0", "bias": "ts 6 / eot 27",
+           "carry": bool(args.carry), "prefill_chunk": args.chunk}
     out["batch"] = run_engine(args.max_batch, "batch")
     if not args.skip_single_slot:
         out["single_slot"] = run_engine(1, "single slot")

@@ -1,6 +1,6 @@
 """Time ohw_state_prefill: a 224-position context at large-v3 dimensions, OHW_PREFILL_XA=1 against =0.
 
-    python tools/prefill_probe.py [--windows 1,32,96] [--cus 64] [--preset large-v3] [--runs 5] [--out FILE.json]
+    python tools/prefill_probe.py [--windows 1,32,96] [--cus 64] [--preset large-v3] [--runs 5] [--chunk 8|16] [--out FILE.json]
 
 For every window count and both knob values (each in a child process: the knob is read when a state is created) it reports the
 median of --runs timed prefills after one warm-up, and from ohw_state_profile_begin / _end the time inside the cross-attention
@@ -10,6 +10,8 @@ OHW_PREFILL_XA=0 is the parent commit's kernels on the same chunks.  A prefill e
 timed with the host's clock around the call (tens of milliseconds and more: the call's overhead does not show).
 K/V bytes per chunk = 2 (K, V) * layers * windows * heads * keys * 64 * 2 bytes; the rate is those bytes times the chunks over the
 cross-attention time, to be read against the 5.7 TB/s the single-token kernel reaches.
+--chunk 8|16 times the prefill at that chunk size (ohw_state_set_prefill_chunk) with the knob at its default alone, one process per
+window count: chunk 8 is the unchanged path and the baseline of chunk 16.
 """
 import argparse
 import json
@@ -23,12 +25,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def child(preset, windows, cus, runs):
+def child(preset, windows, cus, runs, chunk):
     import numpy as np
     from openhush_amd import engine as E, synth
     hp = synth.PRESETS[preset]
     ctx = E.Context.synthetic(hp.as_list(), 1234, 0, E.OHW_DTYPE_BF16)
     st = E.State(ctx, windows)
+    st.set_prefill_chunk(chunk)
     stream = None
     if windows > 32 and cus > 0:
         stream = E.Stream(0, 0, cus)
@@ -53,10 +56,10 @@ def child(preset, windows, cus, runs):
         st.prefill(windows)
         n, ms, _ = st.profile_end()
         prof[name] = {"launches": n, "ms": ms}
-    chunks = (cap + 1 + 7) // 8
+    chunks = (cap + 1 + chunk - 1) // chunk
     kv_chunk = 2.0 * hp.n_text_layer * windows * hp.n_text_head * hp.n_audio_ctx * 64 * 2
     xa_ms = prof["xattn"]["ms"]
-    print(json.dumps({"windows": windows, "xa": int(os.environ.get("OHW_PREFILL_XA", "1")), "cus": cus if stream else 0,
+    print(json.dumps({"windows": windows, "chunk": chunk, "xa": int(os.environ.get("OHW_PREFILL_XA", "1")), "cus": cus if stream else 0,
                       "prefill_ms_median": statistics.median(times), "prefill_ms": times, "chunks": chunks,
                       "xattn_launches_chunk_kernel": st.counter("xattn.chunk"), "profile": prof,
                       "gemm_ms_all": sum(prof[k]["ms"] for k in prof if k != "xattn"),
@@ -69,23 +72,25 @@ def main():
     ap.add_argument("--cus", type=int, default=64)
     ap.add_argument("--preset", default="large-v3")
     ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--chunk", type=int, default=0, choices=[0, 8, 16], help="0 (default): chunk 8 under both values of OHW_PREFILL_XA")
     ap.add_argument("--out", default="")
     ap.add_argument("--child", type=int, default=0)
     a = ap.parse_args()
     if a.child:
-        child(a.preset, a.child, a.cus, a.runs)
+        child(a.preset, a.child, a.cus, a.runs, a.chunk or 8)
         return 0
     rows = []
     for w in [int(x) for x in a.windows.split(",")]:
-        for xa in ("1", "0"):
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(w), "--cus", str(a.cus), "--preset", a.preset, "--runs", str(a.runs)],
+        for xa in ("1", "0") if a.chunk == 0 else ("1",):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(w), "--cus", str(a.cus), "--preset", a.preset, "--runs", str(a.runs),
+                                "--chunk", str(a.chunk or 8)],
                                env=dict(os.environ, OHW_PREFILL_XA=xa), capture_output=True, text=True, timeout=900)
             if r.returncode != 0:
                 print(r.stdout[-2000:], r.stderr[-2000:], file=sys.stderr)
                 return 1            # nothing more is started on the device after a failure
             row = json.loads(r.stdout.strip().splitlines()[-1])
             rows.append(row)
-            print(f"windows {w:3d} xa={xa}: prefill {row['prefill_ms_median']:.1f} ms (median of {a.runs}); cross-attention {row['profile']['xattn']['ms']:.1f} ms, "
+            print(f"windows {w:3d} chunk {row['chunk']} xa={xa}: prefill {row['prefill_ms_median']:.1f} ms (median of {a.runs}); cross-attention {row['profile']['xattn']['ms']:.1f} ms, "
                   f"GEMMs {row['gemm_ms_all']:.1f} ms; K/V {row['kv_gb_per_chunk']:.2f} GB per chunk, {row['kv_tb_per_s'] or 0:.2f} TB/s", flush=True)
             if a.out:
                 with open(a.out, "w") as f:
