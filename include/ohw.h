@@ -695,6 +695,15 @@ int ohw_engine_last_text(ohw_engine* e, const char** text, size_t* len);
 typedef struct { float temperature_inc, entropy_thold, logprob_thold, no_speech_thold; } ohw_decode_policy;
 void ohw_default_decode_policy(ohw_decode_policy* q);   /* 0.2, 2.4, -1.0, 0.6 */
 int ohw_engine_set_decode_policy(ohw_engine* e, const ohw_decode_policy* q);
+/* host only: the engine's own copy of the two rules above, for tests.  ohw_seq_eval_host judges one sampled sequence
+ * (tokens[0..n), end-of-text last when it was sampled, plogs its log-probabilities) of the window [seek, seek_end) in 10 ms
+ * frames: where the loop would have stopped (n_sampled), result_len, seek_delta, the tokens that reach the text (n_keep: all
+ * before the exit in the fixed-cut modes, result_len in OHW_WINDOW_SEEK), failed / completed, and the two scores.
+ * ohw_needs_fallback_host: 1 when a pass so judged goes to the next temperature, 0 when it is kept (always at the last). */
+typedef struct { int32_t n_sampled, result_len, n_keep, seek_delta, failed, completed; float avg_logprob, entropy; } ohw_seq_eval;
+int ohw_seq_eval_host(const ohw_special_tokens* tok, const int32_t* tokens, const float* plogs, int n, int seek, int seek_end, int n_max,
+                      int no_timestamps, int window_mode, ohw_seq_eval* out);
+int ohw_needs_fallback_host(const ohw_seq_eval* ev, const ohw_decode_policy* q, float no_speech_prob, int is_last);
 /* on != 0: the temperature fallback samples on the device (ohw_sample_pass, one call per rung) instead of the host; the
  * same passes, generators and decisions.  Default 0. */
 int ohw_engine_set_fallback_device(ohw_engine* e, int on);

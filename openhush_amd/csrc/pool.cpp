@@ -27,9 +27,6 @@
 #include "host_engine.hpp"
 #include "model.hpp"
 
-namespace ohw {
-extern thread_local std::string g_last_error;
-}
 using namespace ohw;
 
 struct ohw_pool {
@@ -39,11 +36,8 @@ struct ohw_pool {
   int32_t last_lang_id = 0;            // what the last transcribe decoded in (detected with ohw_pool_set_detect_language)
   std::string last_text, broadcast;    // broadcast: "none" | "rccl" | "peer"
   std::string broadcast_note;          // why RCCL was given up, if it was
-  std::vector<int32_t> last_tokens;
-  std::vector<ohw_window_quality> last_quality;
-  // times of the last transcribe, gathered in recording order; words / segments index last_text (ohw_pool_set_word_timestamps)
-  std::vector<ohw_token_time> last_token_times;
-  std::vector<ohw_span_time> last_words, last_segments;
+  // the last transcribe, gathered in recording order; words / segments index last_text (ohw_pool_set_word_timestamps)
+  Transcript last;
 };
 
 namespace {
@@ -361,20 +355,20 @@ int ohw_pool_set_word_timestamps(ohw_pool* p, const ohw_align_head* heads, int n
 }
 int ohw_pool_last_token_times(ohw_pool* p, const ohw_token_time** t, int* n) {
   if (!p || !t || !n) return OHW_E_INVALID_ARG;
-  *t = p->last_token_times.data();
-  *n = (int)p->last_token_times.size();
+  *t = p->last.token_times.data();
+  *n = (int)p->last.token_times.size();
   return OHW_OK;
 }
 int ohw_pool_last_words(ohw_pool* p, const ohw_span_time** w, int* n) {
   if (!p || !w || !n) return OHW_E_INVALID_ARG;
-  *w = p->last_words.data();
-  *n = (int)p->last_words.size();
+  *w = p->last.words.data();
+  *n = (int)p->last.words.size();
   return OHW_OK;
 }
 int ohw_pool_last_segments(ohw_pool* p, const ohw_span_time** s, int* n) {
   if (!p || !s || !n) return OHW_E_INVALID_ARG;
-  *s = p->last_segments.data();
-  *n = (int)p->last_segments.size();
+  *s = p->last.segments.data();
+  *n = (int)p->last.segments.size();
   return OHW_OK;
 }
 int ohw_pool_set_schedule(ohw_pool* p, int schedule, int lanes, int merge) {
@@ -402,14 +396,7 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
                         char* language_out, uint64_t* duration_ms, ohw_audio_info* info_out) {
   return guard([&] {
     if (!p) throw Error(OHW_E_INVALID_ARG, "pool is null");
-    ohw_audio_info info;
-    const int vrc = ohw_validate_audio(samples, n, sample_rate, &info);
-    if (info_out) *info_out = info;
-    if (vrc != OHW_OK) {
-      static const char* const names[] = {"ok", "Audio is empty (no samples)", "Unexpected sample rate", "Audio too long", "Audio too short",
-                                          "Audio contains NaN values", "Audio contains infinite values"};
-      throw Error(OHW_E_VALIDATION, std::string("Audio validation failed: ") + names[info.error]);
-    }
+    validate_or_throw(samples, n, sample_rate, info_out);
     const auto t0 = std::chrono::steady_clock::now();
     const int G = (int)p->engines.size();
     const int64_t n_win = (n + CHUNK_SAMPLES - 1) / CHUNK_SAMPLES;
@@ -417,7 +404,7 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
     for (ohw_engine* e : p->engines)
       if (e->window_mode != mode) throw Error(OHW_E_INVALID_ARG, "pool: the engines disagree on the window mode (use ohw_pool_set_window_mode)");
     // window w -> device w % G.  Every engine is handed the WHOLE recording (borrowed, not copied) and the arithmetic
-    // progression of windows it owns (engine_transcribe_core: first g, step G): its windows are cut at the recording's own
+    // progression of windows it owns (engine_transcribe: first g, step G): its windows are cut at the recording's own
     // 30 s marks - and in FIXED_RECORDING_MEL from the spectrogram of the whole recording - exactly as a single engine cuts them
     std::vector<std::string> errs((size_t)G);
     std::vector<std::thread> th;
@@ -437,9 +424,8 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
     for (int g = 0; g < used; ++g) {
       th.emplace_back([&, g] {
         try {
-          std::string text;
-          if (seek) engine_transcribe_core(p->engines[(size_t)g], samples, n, &text);
-          else engine_transcribe_core(p->engines[(size_t)g], samples, n, &text, g, used);
+          if (seek) engine_transcribe(p->engines[(size_t)g], samples, n);
+          else engine_transcribe(p->engines[(size_t)g], samples, n, g, used);
         } catch (const std::exception& ex) {
           errs[(size_t)g] = ex.what()[0] ? ex.what() : "unknown error";
         }
@@ -449,40 +435,39 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
     for (int g = 0; g < used; ++g)
       if (!errs[(size_t)g].empty()) throw Error(OHW_E_TRANSCRIBE, "Transcription failed on device " + std::to_string(p->devices[(size_t)g]) + ": " + errs[(size_t)g]);
     // gather in recording order: device g's k-th window record is window g + k * G
-    p->last_tokens.clear();
-    p->last_quality.clear();
-    p->last_token_times.clear(); p->last_words.clear(); p->last_segments.clear();
-    std::string text;
+    Transcript& out = p->last;
+    out.clear();
+    std::string& text = out.text;
     std::vector<size_t> tok_pos((size_t)G, 0), win_pos((size_t)G, 0), tt_pos((size_t)G, 0), wd_pos((size_t)G, 0), sg_pos((size_t)G, 0);
-    const int64_t n_rec = seek ? (int64_t)p->engines[0]->last_quality.size() : n_win;
+    const int64_t n_rec = seek ? (int64_t)p->engines[0]->last.quality.size() : n_win;
     for (int64_t w = 0; w < n_rec; ++w) {
       const int g = seek ? 0 : (int)(w % used);
-      ohw_engine* e = p->engines[(size_t)g];
-      if (win_pos[(size_t)g] >= e->last_quality.size()) throw Error(OHW_E_TRANSCRIBE, "pool: a device returned fewer windows than it was dealt");
+      const Transcript& got = p->engines[(size_t)g]->last;
+      if (win_pos[(size_t)g] >= got.quality.size()) throw Error(OHW_E_TRANSCRIBE, "pool: a device returned fewer windows than it was dealt");
       // the window's times: its engine indexed them against its own untrimmed text and counted its own windows
-      if (win_pos[(size_t)g] < e->last_marks.size()) {
-        const ohw_engine::WindowMark& mk = e->last_marks[win_pos[(size_t)g]];
+      if (win_pos[(size_t)g] < got.marks.size()) {
+        const WindowMark& mk = got.marks[win_pos[(size_t)g]];
         for (int i = 0; i < mk.n_token_times; ++i) {
-          ohw_token_time t = e->last_token_times[tt_pos[(size_t)g]++];
+          ohw_token_time t = got.token_times[tt_pos[(size_t)g]++];
           t.window = (int32_t)w;
-          p->last_token_times.push_back(t);
+          out.token_times.push_back(t);
         }
         for (int i = 0; i < mk.n_words; ++i) {
-          ohw_span_time s = e->last_words[wd_pos[(size_t)g]++];
+          ohw_span_time s = got.words[wd_pos[(size_t)g]++];
           s.text_off = s.text_off - mk.text0 + text.size();
-          p->last_words.push_back(s);
+          out.words.push_back(s);
         }
         for (int i = 0; i < mk.n_segments; ++i) {
-          ohw_span_time s = e->last_segments[sg_pos[(size_t)g]++];
+          ohw_span_time s = got.segments[sg_pos[(size_t)g]++];
           s.text_off = s.text_off - mk.text0 + text.size();
-          p->last_segments.push_back(s);
+          out.segments.push_back(s);
         }
       }
-      const ohw_window_quality& q = e->last_quality[win_pos[(size_t)g]++];
-      p->last_quality.push_back(q);
+      const ohw_window_quality& q = got.quality[win_pos[(size_t)g]++];
+      out.quality.push_back(q);
       for (int i = 0; i < q.n_tokens; ++i) {
-        const int32_t t = e->last_tokens[tok_pos[(size_t)g]++];
-        p->last_tokens.push_back(t);
+        const int32_t t = got.tokens[tok_pos[(size_t)g]++];
+        out.tokens.push_back(t);
         if (t < p->engines[0]->ctx->tok.eot) {
           const char* sp = nullptr;
           const int len = ohw_token_text(p->engines[0]->ctx, t, &sp);     // device 0 read the file: it has the vocabulary
@@ -490,23 +475,11 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
         }
       }
     }
-    const size_t b0 = text.find_first_not_of(" \t\r\n");
-    const size_t b1 = text.find_last_not_of(" \t\r\n");
-    text = b0 == std::string::npos ? std::string() : text.substr(b0, b1 - b0 + 1);
+    out.trim();
     p->last_text = text;
-    trim_spans(p->last_words, b0 == std::string::npos ? 0 : b0, text.size());
-    trim_spans(p->last_segments, b0 == std::string::npos ? 0 : b0, text.size());
-    if (text_buf && text_cap > 0) {
-      const size_t nc = std::min(text.size(), text_cap - 1);
-      std::memcpy(text_buf, text.data(), nc);
-      text_buf[nc] = 0;
-    }
+    copy_text_out(text_buf, text_cap, text);
     p->last_lang_id = used > 0 ? p->engines[0]->last_lang_id : 0;
-    if (language_out) {
-      const std::string lang = p->language == "auto" ? ohw_lang_id_to_code(p->last_lang_id) : p->language;
-      std::strncpy(language_out, lang.c_str(), 7);
-      language_out[7] = 0;
-    }
+    write_language_out(language_out, p->language, p->last_lang_id);
     if (duration_ms) *duration_ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
   });
 }
@@ -519,14 +492,14 @@ int ohw_pool_last_text(ohw_pool* p, const char** text, size_t* len) {
 }
 int ohw_pool_last_tokens(ohw_pool* p, const int32_t** tokens, int* n) {
   if (!p || !tokens || !n) return OHW_E_INVALID_ARG;
-  *tokens = p->last_tokens.data();
-  *n = (int)p->last_tokens.size();
+  *tokens = p->last.tokens.data();
+  *n = (int)p->last.tokens.size();
   return OHW_OK;
 }
 int ohw_pool_last_quality(ohw_pool* p, const ohw_window_quality** q, int* n_windows) {
   if (!p || !q || !n_windows) return OHW_E_INVALID_ARG;
-  *q = p->last_quality.data();
-  *n_windows = (int)p->last_quality.size();
+  *q = p->last.quality.data();
+  *n_windows = (int)p->last.quality.size();
   return OHW_OK;
 }
 

@@ -191,6 +191,12 @@ class DecodePolicy(C.Structure):
     _fields_ = [("temperature_inc", C.c_float), ("entropy_thold", C.c_float), ("logprob_thold", C.c_float), ("no_speech_thold", C.c_float)]
 
 
+class SeqEval(C.Structure):
+    """ohw_seq_eval: one sampled sequence as whisper.cpp's loop bookkeeping judges it"""
+    _fields_ = [("n_sampled", C.c_int32), ("result_len", C.c_int32), ("n_keep", C.c_int32), ("seek_delta", C.c_int32),
+                ("failed", C.c_int32), ("completed", C.c_int32), ("avg_logprob", C.c_float), ("entropy", C.c_float)]
+
+
 class AudioSpan(C.Structure):
     _fields_ = [("samples", C.POINTER(C.c_float)), ("n", C.c_int64)]
 
@@ -264,6 +270,7 @@ EXPORTS = [
     "ohw_dbg_dec_gemm", "ohw_dbg_embed", "ohw_dbg_layernorm",
     "ohw_state_set_prefill_chunk", "ohw_state_prefill_chunk", "ohw_engine_set_prefill_chunk", "ohw_dbg_cross_attn_chunk_n",
     "ohw_engine_set_carry_context", "ohw_pool_set_carry_context", "ohw_engine_last_context", "ohw_engine_long_batch_context", "ohw_carry_step_host",
+    "ohw_seq_eval_host", "ohw_needs_fallback_host",
 ]
 
 
@@ -568,6 +575,8 @@ def lib():
         L.ohw_pool_last_words.argtypes = [vp, pst, C.POINTER(C.c_int)]
         L.ohw_pool_last_segments.argtypes = [vp, pst, C.POINTER(C.c_int)]
         L.ohw_segments_host.argtypes = [ip, C.c_int, C.POINTER(SpecialTokens), C.c_float, C.c_float, C.POINTER(TokenSpan), C.c_int]
+        L.ohw_seq_eval_host.argtypes = [C.POINTER(SpecialTokens), ip, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SeqEval)]
+        L.ohw_needs_fallback_host.argtypes = [C.POINTER(SeqEval), C.POINTER(DecodePolicy), C.c_float, C.c_int]
         L.ohw_dequantize_host.argtypes = [C.c_int, vp, C.c_int64, fp]
         L.ohw_dbg_dequantize.argtypes = [C.c_int, C.c_int, vp, C.c_int64, fp]
         _lib = L
@@ -692,6 +701,26 @@ def segments_host(tokens: Sequence[int], tok: "SpecialTokens", t_off: float, t_e
     if n < 0:
         _raise(n)
     return [(out[i].first, out[i].end, float(out[i].t0), float(out[i].t1)) for i in range(n)]
+
+
+def seq_eval_host(tok: "SpecialTokens", tokens: Sequence[int], plogs: Sequence[float], seek: int, seek_end: int, n_max: int,
+                  no_timestamps: bool = False, window_mode: int = OHW_WINDOW_FIXED) -> SeqEval:
+    """ohw_seq_eval_host (host only): the engine's judgement of one sampled sequence (end-of-text last when it was sampled) of the
+    window [seek, seek_end) in 10 ms frames"""
+    t = np.ascontiguousarray(list(tokens) or [0], dtype=np.int32)
+    lp = np.ascontiguousarray(list(plogs) or [0.0], dtype=np.float32)
+    ev = SeqEval()
+    _check(lib().ohw_seq_eval_host(C.byref(tok), _ip(t), _fp(lp), len(tokens), int(seek), int(seek_end), int(n_max), int(bool(no_timestamps)),
+                                   int(window_mode), C.byref(ev)))
+    return ev
+
+
+def needs_fallback_host(ev: SeqEval, policy: DecodePolicy, no_speech_prob: float, is_last: bool) -> bool:
+    """ohw_needs_fallback_host (host only): does a pass judged `ev` go to the next temperature?"""
+    rc = int(lib().ohw_needs_fallback_host(C.byref(ev), C.byref(policy), float(no_speech_prob), int(bool(is_last))))
+    if rc < 0:
+        _raise(rc)
+    return rc == 1
 
 
 def _token_times(p, n):

@@ -5,7 +5,7 @@ test, and the whole procedure on a tiny synthetic model."""
 import numpy as np
 import pytest
 
-from openhush_amd import synth
+from openhush_amd import engine as E, synth
 from oracle import oracle
 
 
@@ -115,3 +115,117 @@ def test_whole_window_procedure_on_a_tiny_model(model):
     q1 = oracle.default_policy(); q1.temperature_inc = 0.0; q1.logprob_thold = 0.0
     keptn, resn, _ = s.decode_window(p, q1, bias, 0, 2999, 0, None)
     assert resn.no_speech_prob > 0.9 and resn.no_speech == 1 and keptn == []
+
+
+# ---- the engine's own copy of the rules (ohw_seq_eval_host / ohw_needs_fallback_host) against the oracle's restatement ----
+
+def _special_tokens(m):
+    t = E.SpecialTokens()
+    (t.eot, t.sot, t.translate, t.transcribe, t.solm, t.prev, t.nosp, t.no_timestamps, t.timestamp_begin, t.blank) = (
+        m.tok_eot, m.tok_sot, m.tok_translate, m.tok_transcribe, m.tok_solm, m.tok_prev, m.tok_nosp, m.tok_not, m.tok_beg, m.tok_blank)
+    t.n_langs = 99
+    return t
+
+
+def _crafted(m):
+    """every sequence the tests above judge: (tokens, log-probabilities, seek, seek_end, n_max, no_timestamps, window_mode)"""
+    tb, eot = m.tok_beg, m.tok_eot
+    good = list(range(100, 140)) + [tb + 700, eot]
+    stamped = [tb, 10, 11, tb + 500, tb + 500, 12, 13, tb + 900, 14, eot]
+    cases = [([10, 11, eot], -0.5, 0, 9000, 0), ([10, 11, eot], -0.5, 0, 2999, 0), (stamped, -0.5, 0, 9000, 1), (stamped, -0.5, 0, 9000, 0),
+             ([tb, 10, tb + 1460, 11, 12, eot], -0.5, 0, 2999, 0), ([tb + 100, 5, tb + 300, tb + 300, 6, tb + 200, 7], -0.5, 0, 9000, 0),
+             ([tb + 10] + [42] * 219, -0.5, 0, 9000, 0), ([tb + 10, 1, tb + 800] + [42] * 217, -0.5, 0, 9000, 0),
+             (good, -0.5, 0, 9000, 0), (good, -0.3, 0, 9000, 0), (good, -1.5, 0, 9000, 0), ([tb] + [42] * 40 + [tb + 700, eot], -0.1, 0, 9000, 0)]
+    return [(seq, [lp] * len(seq), seek, end, 220, False, mode) for seq, lp, seek, end, mode in cases]
+
+
+def _random_case(m, rng):
+    """lengths 1 .. 230; text tokens, timestamps (rising, repeated, falling) and end-of-text anywhere; both window modes;
+    no_timestamps on and off; n_max 8 and 220; about a third of the windows within 1 s of the end of the audio, some of them with
+    seek_end <= 100"""
+    tb, eot = m.tok_beg, m.tok_eot
+    n = int(rng.integers(1, 231))
+    n_max = 8 if rng.random() < 0.4 else 220
+    alphabet = rng.integers(0, eot, size=int(rng.choice([1, 3, 40, 400])))
+    p_ts = float(rng.choice([0.0, 0.05, 0.2, 0.5]))
+    p_back = float(rng.choice([0.0, 0.0, 0.15, 0.5]))
+    toks, ts = [], int(rng.integers(0, 200))
+    for _ in range(n):
+        if rng.random() < p_ts:
+            u = rng.random()
+            ts = max(0, ts - int(rng.integers(1, 80))) if u < p_back else ts if u < p_back + 0.2 else min(1500, ts + int(rng.integers(1, 400)))
+            toks.append(tb + ts)
+        else:
+            toks.append(int(rng.choice(alphabet)))
+    if rng.random() < 0.45:
+        toks[int(rng.integers(0, n if rng.random() < 0.5 else min(n, 6)))] = eot          # anywhere; half of them early
+    if rng.random() < 0.2:
+        toks[-1] = eot
+    seek = int(rng.choice([0, 0, 1000, 6000]))
+    u = rng.random()
+    seek_end = int(rng.integers(0, 101)) if u < 0.05 else seek + int(rng.integers(101, 3101)) if u < 0.35 else seek + int(rng.integers(3200, 20000))
+    plogs = rng.uniform(-3.0, 0.0, size=n).astype(np.float32)
+    return toks, plogs, seek, seek_end, n_max, bool(rng.random() < 0.2), int(rng.integers(0, 2))
+
+
+def _exit_of(m, toks, ev):
+    """which exit of whisper.cpp's loop ended the walk, read off the oracle's judgement"""
+    if ev.completed:
+        return "completed"
+    if not ev.failed:
+        return "ran out"
+    last = toks[ev.n_sampled - 1]
+    if last == m.tok_eot:
+        return "end-of-text without timestamp"
+    if last > m.tok_beg and 2 * (last - m.tok_beg) < ev.seek_delta:
+        return "backward timestamp"
+    return "n_max guard"
+
+
+def _same_judgement(tok, m, case, policies):
+    toks, plogs, seek, seek_end, n_max, no_ts, mode = case
+    ref = oracle.evaluate_sequence(m, toks, plogs, seek, seek_end, n_max, no_ts, mode)
+    got = E.seq_eval_host(tok, toks, plogs, seek, seek_end, n_max, no_ts, mode)
+    for f in ("n_sampled", "result_len", "n_keep", "seek_delta", "failed", "completed"):
+        assert getattr(got, f) == getattr(ref, f), (f, case, ref.as_dict())
+    a, b = np.float32(got.avg_logprob), np.float32(ref.avg_logprob)
+    assert a == b or abs(float(a) - float(b)) <= float(np.spacing(max(abs(a), abs(b)))), (case, a, b)     # one float ulp (-inf == -inf)
+    assert abs(got.entropy - ref.entropy) <= 1e-6, (case, got.entropy, ref.entropy)
+    for q, eq, nosp in policies:
+        for is_last in (False, True):
+            assert E.needs_fallback_host(got, eq, nosp, is_last) == oracle.pass_needs_fallback(ref, q, nosp, is_last), (case, nosp, is_last)
+    return ref
+
+
+def _policy_pair(entropy_thold=2.4, logprob_thold=-1.0, no_speech_thold=0.6):
+    q = oracle.default_policy()
+    q.entropy_thold, q.logprob_thold, q.no_speech_thold = entropy_thold, logprob_thold, no_speech_thold
+    return q, E.DecodePolicy(q.temperature_inc, q.entropy_thold, q.logprob_thold, q.no_speech_thold)
+
+
+def test_engine_rules_equal_the_oracle_on_crafted_sequences(model):
+    tok = _special_tokens(model)
+    policies = [_policy_pair() + (nosp,) for nosp in (0.01, 0.9)]
+    for case in _crafted(model):
+        _same_judgement(tok, model, case, policies)
+    assert E.lib().ohw_seq_eval_host(None, None, None, 0, 0, 0, 0, 0, 0, None) == E.OHW_E_INVALID_ARG            # null arguments are refused, not read
+    assert E.lib().ohw_needs_fallback_host(None, None, 0.0, 0) == E.OHW_E_INVALID_ARG
+
+
+def test_engine_rules_equal_the_oracle_on_random_sequences(model):
+    """600 seeded sequences; every integer field and the fallback decision equal, avg_logprob to one float ulp, entropy to 1e-6
+    (both sides sum in double; the slack is a contracted multiply-add on a value of at most ln 32).  The generator must reach
+    every exit of the loop in at least 5 % of the cases."""
+    tok = _special_tokens(model)
+    rng = np.random.default_rng(20240607)
+    exits = {}
+    n_cases = 600
+    for _ in range(n_cases):
+        case = _random_case(model, rng)
+        q, eq = _policy_pair(float(rng.uniform(0.0, 3.5)), float(rng.uniform(-2.5, 0.0)), float(rng.choice([0.3, 0.6])))
+        ref = _same_judgement(tok, model, case, [_policy_pair() + (float(rng.random()),), (q, eq, float(rng.random()))])
+        k = _exit_of(model, case[0], ref)
+        exits[k] = exits.get(k, 0) + 1
+    print(exits)
+    for k in ("completed", "backward timestamp", "end-of-text without timestamp", "n_max guard"):
+        assert exits.get(k, 0) >= 0.05 * n_cases, (k, exits)
