@@ -1199,6 +1199,50 @@ int ohw_dbg_embed(int dtype, const float* emb, int n_vocab, const float* pos, in
 int ohw_dbg_layernorm(int dtype, const float* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, int tiled,
                       void* stream);
 
+/* ONE encoder GEMM launch (gemm.hip 128x128, gemm256.hip 256x256, gemm_small.hip 64x64) on caller data, in any of the forms
+ * run_encode launches (tests/test_gpu_enc_gemm.py); no ohw_state.  a, w, bias, pos and out are DEVICE pointers, c_row_map is a
+ * HOST table.  Every range is checked on the host before any device work (OHW_E_INVALID_ARG, nothing launched); then the
+ * weights are prepared on a private copy with the loader's own kernels, the GEMM is launched once on `stream`, the stream is
+ * synchronised and the copies are freed.
+ * Geometry: gemm.hpp's GemmParams.  Row m of A is at a + (m / rows_per_batch) * a_batch_stride + (m % rows_per_batch) * lda
+ *   and has K elements of `dtype` (rows may overlap: lda < K); with nb = ceil(M / rows_per_batch) windows,
+ *   (nb - 1) * a_batch_stride + (min(M, rows_per_batch) - 1) * lda + K <= a_elems.  K % 64 == 0; lda and a_batch_stride are
+ *   multiples of 8 elements and a is 16-byte aligned.
+ * Weights: w f32 [N][K] row-major, rounded to `dtype` (launch_convert_rows); with conv_cin > 0 w is a convolution's f32
+ *   [N][conv_cin][3] instead and is repacked tap-major with c_pad = K / 3 zero-padded channels (launch_repack_conv: K % 3 == 0,
+ *   conv_cin <= K / 3).  bias f32 [N] or NULL.
+ * Epilogues (gemm.hpp's GemmEpilogue, 0 .. 5):
+ *   0 BIAS_T, 1 BIAS_GELU_T       out `dtype`; 2 BIAS_RESID_F32 (out +=), 3 GELU_POS_F32 (+ pos[m % rows_per_batch][n], pos f32
+ *   [rows_per_batch][N]), 4 F32   out f32.  Row m goes to out + (m / rows_per_batch) * c_batch_stride + (m % rows_per_batch) * ldc,
+ *       N elements; ldc >= N, windows must not overlap (c_batch_stride >= (min(M, rows_per_batch) - 1) * ldc + N when nb > 1),
+ *       (nb - 1) * c_batch_stride + (min(M, rows_per_batch) - 1) * ldc + N <= out_elems; ldc and c_batch_stride are multiples
+ *       of 16 bytes, out is 16-byte aligned.
+ *   5 CROSSKV_T                   out `dtype` head-major [N / d_model][batch][n_head][t_len][64]: column n = slab * d_model + 64 h + dh
+ *       of row m goes to [slab][batch_offset + m / rows_per_batch][h][m % rows_per_batch][dh]; d_model == 64 * n_head,
+ *       N % d_model == 0, min(M, rows_per_batch) <= t_len, 0 <= batch_offset, batch_offset + nb <= batch,
+ *       N / d_model * batch * n_head * t_len * 64 <= out_elems.  c_row_map (HOST [M], epilogue 5 only) or NULL: with it row m
+ *       goes to window batch_offset + c_row_map[m] / t_len, position c_row_map[m] % t_len, whatever rows_per_batch is;
+ *       0 <= c_row_map[m] <= (batch - batch_offset) * t_len - 1.
+ * kernel: AUTO is launch_gemm's own pick; K128 needs N % 128 == 0, SMALL N % 64 == 0, K256 N % 256 == 0. */
+enum { OHW_EG_KERNEL_AUTO = 0, OHW_EG_KERNEL_K128, OHW_EG_KERNEL_SMALL, OHW_EG_KERNEL_K256 };
+typedef struct {
+  int32_t dtype, epilogue, kernel;
+  int32_t conv_cin;            /* > 0: w is [N][conv_cin][3] */
+  int64_t M, N, K;
+  int64_t lda, a_batch_stride, rows_per_batch;
+  int64_t ldc, c_batch_stride;
+  int32_t d_model, n_head, t_len, batch, batch_offset;   /* CROSSKV_T */
+  const int32_t* c_row_map;    /* HOST [M] or NULL */
+  const void* a;
+  int64_t a_elems;
+  const float* w;
+  const float* bias;           /* f32 [N] or NULL */
+  const float* pos;            /* GELU_POS_F32 */
+  void* out;
+  int64_t out_elems;
+} ohw_dbg_enc_gemm_io;
+int ohw_dbg_enc_gemm(const ohw_dbg_enc_gemm_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

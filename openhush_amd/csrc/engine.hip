@@ -3057,4 +3057,90 @@ int ohw_dbg_layernorm(int dtype, const float* x, const float* gamma, const float
   });
 }
 
+static_assert(OHW_EG_KERNEL_AUTO == 0 && OHW_EG_KERNEL_K128 == 1 && OHW_EG_KERNEL_SMALL == 2 && OHW_EG_KERNEL_K256 == 3, "ohw.h names the encoder GEMM kernels");
+
+int ohw_dbg_enc_gemm(const ohw_dbg_enc_gemm_io* io, void* stream) {
+  return guard([&] {
+    if (!io) throw Error(OHW_E_INVALID_ARG, "dbg_enc_gemm: null io");
+    const ohw_dbg_enc_gemm_io& a = *io;
+    auto bad = [](const std::string& why) { throw Error(OHW_E_INVALID_ARG, "dbg_enc_gemm: " + why); };
+    auto str = [](int64_t v) { return std::to_string(v); };
+    auto aligned16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    dbg_check_dtype(a.dtype, "dbg_enc_gemm");
+    if (a.epilogue < EPI_BIAS_T || a.epilogue > EPI_CROSSKV_T) bad("epilogue must be 0 .. 5");
+    if (a.kernel < OHW_EG_KERNEL_AUTO || a.kernel > OHW_EG_KERNEL_K256) bad("kernel must be 0 (auto), 1 (128x128), 2 (64x64) or 3 (256x256)");
+    if (!a.a || !a.w || !a.out) bad("null a, w or out");
+    const int64_t lim = (int64_t)1 << 20;
+    if (a.M < 1 || a.N < 64 || a.K < 64 || a.M > lim || a.N > lim || a.K > lim) bad("M >= 1, N >= 64 and K >= 64 (each at most 2^20)");
+    if (a.K % 64 != 0) bad("K = " + str(a.K) + " must be a multiple of 64");
+    const int64_t n_mult = a.kernel == OHW_EG_KERNEL_K256 ? 256 : a.kernel == OHW_EG_KERNEL_SMALL ? 64 : 128;
+    if (a.N % n_mult != 0) bad("N = " + str(a.N) + " must be a multiple of " + str(n_mult) + " for this kernel");
+    if (a.rows_per_batch < 1 || a.rows_per_batch > lim) bad("rows_per_batch must be 1 .. 2^20");
+    if (a.lda < 0 || a.a_batch_stride < 0 || a.lda > ((int64_t)1 << 30) || a.a_batch_stride > ((int64_t)1 << 30)) bad("lda and a_batch_stride must lie in 0 .. 2^30");
+    if (a.lda % 8 != 0 || a.a_batch_stride % 8 != 0 || !aligned16(a.a)) bad("lda and a_batch_stride must be multiples of 8 elements and a 16-byte aligned");
+    if (a.a_elems < 0 || a.out_elems < 0) bad("negative a_elems or out_elems");
+    // the last element any row reads: window nb - 1, its last row, K columns
+    const int64_t nb = (a.M + a.rows_per_batch - 1) / a.rows_per_batch, rows = std::min(a.M, a.rows_per_batch);
+    const int64_t a_need = (nb - 1) * a.a_batch_stride + (rows - 1) * a.lda + a.K;
+    if (a_need > a.a_elems) bad("the rows of A end at element " + str(a_need) + ", past a_elems = " + str(a.a_elems));
+    if (a.bias && !aligned16(a.bias)) bad("bias must be 16-byte aligned");
+    if (!aligned16(a.out)) bad("out must be 16-byte aligned");
+    if (a.c_row_map && a.epilogue != EPI_CROSSKV_T) bad("a row map goes with the cross-K/V epilogue only");
+    if (a.conv_cin < 0) bad("conv_cin must not be negative");
+    if (a.conv_cin > 0 && (a.K % 3 != 0 || a.conv_cin > a.K / 3)) bad("conv weights: K must be 3 * c_pad with conv_cin <= c_pad");
+    if (a.epilogue == EPI_CROSSKV_T) {
+      if (a.n_head < 1 || a.n_head > 1024 || a.d_model != 64 * a.n_head || a.N % a.d_model != 0) bad("cross-K/V: d_model == 64 * n_head and N a multiple of d_model");
+      if (a.t_len < 1 || a.t_len > lim || a.batch < 1 || a.batch > lim || a.batch_offset < 0 || a.batch_offset >= a.batch)
+        bad("cross-K/V: t_len and batch in 1 .. 2^20, 0 <= batch_offset < batch");
+      const double need = (double)(a.N / a.d_model) * a.batch * a.n_head * a.t_len * 64.0;   // exact below 2^53; out_elems is far below
+      if (need > (double)a.out_elems) bad("cross-K/V: the slabs hold more than out_elems = " + str(a.out_elems) + " elements");
+      if (a.c_row_map) {
+        const int64_t top = (int64_t)(a.batch - a.batch_offset) * a.t_len;
+        for (int64_t m = 0; m < a.M; ++m)
+          if (a.c_row_map[m] < 0 || a.c_row_map[m] >= top)
+            bad("c_row_map[" + str(m) + "] = " + str(a.c_row_map[m]) + " is outside 0 .. " + str(top - 1));
+      } else {
+        if (rows > a.t_len) bad("cross-K/V: " + str(rows) + " rows per window exceed t_len = " + str(a.t_len));
+        if (a.batch_offset + nb > a.batch) bad("cross-K/V: windows " + str(a.batch_offset) + " .. " + str(a.batch_offset + nb - 1) + " exceed batch = " + str(a.batch));
+      }
+    } else {
+      const bool f32_out = a.epilogue == EPI_BIAS_RESID_F32 || a.epilogue == EPI_GELU_POS_F32 || a.epilogue == EPI_F32;
+      const int64_t el16 = f32_out ? 4 : 8;   // elements in 16 bytes
+      if (a.ldc < a.N || a.ldc > ((int64_t)1 << 30) || a.c_batch_stride < 0 || a.c_batch_stride > ((int64_t)1 << 30)) bad("N <= ldc <= 2^30 and 0 <= c_batch_stride <= 2^30");
+      if (a.ldc % el16 != 0 || a.c_batch_stride % el16 != 0) bad("ldc and c_batch_stride must be multiples of 16 bytes");
+      if (nb > 1 && a.c_batch_stride < (rows - 1) * a.ldc + a.N) bad("c_batch_stride = " + str(a.c_batch_stride) + ": the output windows overlap");
+      const int64_t need = (nb - 1) * a.c_batch_stride + (rows - 1) * a.ldc + a.N;
+      if (need > a.out_elems) bad("the output rows end at element " + str(need) + ", past out_elems = " + str(a.out_elems));
+      if (a.epilogue == EPI_GELU_POS_F32 && (!a.pos || !aligned16(a.pos))) bad("GELU_POS_F32 needs pos, 16-byte aligned");
+    }
+
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf wt, map;
+    wt.alloc((size_t)a.N * a.K * 2);
+    if (a.c_row_map) dbg_upload(map, a.c_row_map, (size_t)a.M);
+    Dispatch::run(a.dtype, [&](auto* tag) {
+      using TT = std::remove_pointer_t<decltype(tag)>;
+      // the weights as the loader prepares them (model.hip): a linear's rows rounded, a convolution's taps repacked
+      if (a.conv_cin > 0) launch_repack_conv<TT>(a.w, wt.p, a.N, a.conv_cin, a.K / 3, s);
+      else launch_convert_rows<TT>(a.w, wt.p, a.N, a.K, a.K, s);
+      GemmParams g{};
+      g.A = a.a; g.W = wt.p; g.bias = a.bias; g.out = a.out; g.pos = a.epilogue == EPI_GELU_POS_F32 ? a.pos : nullptr;
+      g.M = a.M; g.N = a.N; g.K = a.K;
+      g.lda = a.lda; g.a_batch_stride = a.a_batch_stride; g.rows_per_batch = a.rows_per_batch;
+      g.ldc = a.ldc; g.c_batch_stride = a.c_batch_stride;
+      if (a.epilogue == EPI_CROSSKV_T) {
+        g.d_model = a.d_model; g.n_head = a.n_head; g.t_len = a.t_len; g.batch = a.batch; g.batch_offset = a.batch_offset;
+        g.c_row_map = a.c_row_map ? map.as<int32_t>() : nullptr;
+      }
+      switch (a.kernel) {
+        case OHW_EG_KERNEL_K128: launch_gemm128<TT>(g, a.epilogue, s); break;
+        case OHW_EG_KERNEL_SMALL: launch_gemm_small<TT>(g, a.epilogue, s); break;
+        case OHW_EG_KERNEL_K256: launch_gemm256<TT>(g, a.epilogue, s); break;
+        default: launch_gemm<TT>(g, a.epilogue, s); break;
+      }
+    });
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
 }  // extern "C"

@@ -169,6 +169,12 @@ void launch_gemm(const GemmParams& p, int epilogue, hipStream_t stream) {
   static const int min_tiles = getenv("OHW_GEMM256_MIN_TILES") ? atoi(getenv("OHW_GEMM256_MIN_TILES")) : 128;
   const int64_t tiles256 = ((p.M + 255) / 256) * (p.N / 256);
   if (p.N % 256 == 0 && p.M >= 1024 && p.K % 64 == 0 && tiles256 >= min_tiles) { launch_gemm256<T>(p, epilogue, stream); return; }
+  launch_gemm128<T>(p, epilogue, stream);
+}
+
+template <typename T>
+void launch_gemm128(const GemmParams& p, int epilogue, hipStream_t stream) {
+  if (p.M <= 0) return;
   if (p.N % BN != 0 || p.K % BK != 0 || p.lda % 8 != 0 || p.a_batch_stride % 8 != 0 || p.rows_per_batch <= 0 || p.M >= ((int64_t)1 << 31) || p.N >= ((int64_t)1 << 31))
     throw Error(OHW_E_INVALID_ARG, "gemm: N must be a multiple of 128, K of 64, row strides of 8 elements");
   switch (epilogue) {
@@ -184,5 +190,7 @@ void launch_gemm(const GemmParams& p, int epilogue, hipStream_t stream) {
 
 template void launch_gemm<bf16_t>(const GemmParams&, int, hipStream_t);
 template void launch_gemm<f16_t>(const GemmParams&, int, hipStream_t);
+template void launch_gemm128<bf16_t>(const GemmParams&, int, hipStream_t);
+template void launch_gemm128<f16_t>(const GemmParams&, int, hipStream_t);
 
 }  // namespace ohw

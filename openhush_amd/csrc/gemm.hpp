@@ -34,6 +34,8 @@ struct GemmParams {
 
 // N % 128 == 0, K % 64 == 0, lda/ldc/strides multiples of 8 elements (16-byte rows)
 template <typename T> void launch_gemm(const GemmParams& p, int epilogue, hipStream_t stream);
+// the 128x128x64 kernel of gemm.hip itself: launch_gemm's last stop, its checks and its epilogue switch (ohw_dbg_enc_gemm names it)
+template <typename T> void launch_gemm128(const GemmParams& p, int epilogue, hipStream_t stream);
 // the 64x64x64 variant for short windows (N % 64 == 0); launch_gemm hands a problem over only when p.small_m is set
 template <typename T> void launch_gemm_small(const GemmParams& p, int epilogue, hipStream_t stream);
 // the 256x256x64 variant (N % 256 == 0); launch_gemm dispatches to it for large problems

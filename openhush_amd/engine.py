@@ -145,6 +145,19 @@ class DbgDecGemmIO(C.Structure):
                 [(n, C.c_int32) for n in ("d_model", "n_head", "n_ctx")] + [("shape_out", C.POINTER(C.c_int32))])
 
 
+class DbgEncGemmIO(C.Structure):
+    """ohw_dbg_enc_gemm_io: a, w, bias, pos and out are device addresses, c_row_map is a host table"""
+    _fields_ = ([(n, C.c_int32) for n in ("dtype", "epilogue", "kernel", "conv_cin")] +
+                [(n, C.c_int64) for n in ("M", "N", "K", "lda", "a_batch_stride", "rows_per_batch", "ldc", "c_batch_stride")] +
+                [(n, C.c_int32) for n in ("d_model", "n_head", "t_len", "batch", "batch_offset")] + [("c_row_map", C.POINTER(C.c_int32))] +
+                [("a", C.c_void_p), ("a_elems", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p), ("pos", C.c_void_p), ("out", C.c_void_p),
+                 ("out_elems", C.c_int64)])
+
+
+# ohw_dbg_enc_gemm: every epilogue of gemm.hpp's GemmEpilogue and the kernel to run (OHW_EG_KERNEL_*)
+EPI_GELU_POS_F32, EPI_CROSSKV_T = 3, 5
+EG_KERNEL_AUTO, EG_KERNEL_K128, EG_KERNEL_SMALL, EG_KERNEL_K256 = range(4)
+
 # ohw_dbg_dec_gemm: epilogues (kernels.hpp's DecEpilogue), operand forms and the work shape that ran (DecGemmShape)
 DEPI_QKV, DEPI_BIAS_T, DEPI_BIAS_GELU_T, DEPI_BIAS_RESID, DEPI_LOGITS = range(5)
 DG_FORM_PLAIN, DG_FORM_LN, DG_FORM_PN = range(3)
@@ -271,6 +284,7 @@ EXPORTS = [
     "ohw_state_set_prefill_chunk", "ohw_state_prefill_chunk", "ohw_engine_set_prefill_chunk", "ohw_dbg_cross_attn_chunk_n",
     "ohw_engine_set_carry_context", "ohw_pool_set_carry_context", "ohw_engine_last_context", "ohw_engine_long_batch_context", "ohw_carry_step_host",
     "ohw_seq_eval_host", "ohw_needs_fallback_host",
+    "ohw_dbg_enc_gemm",
 ]
 
 
@@ -521,6 +535,7 @@ def lib():
         L.ohw_carry_step_host.argtypes = [ip, C.POINTER(C.c_int), C.c_int, ip, C.c_int, C.c_float, C.c_int, ip, C.POINTER(C.c_int)]
         L.ohw_dbg_self_attn.argtypes = [C.c_int, vp, vp, vp, ip, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int), vp]
         L.ohw_dbg_dec_gemm.argtypes = [C.POINTER(DbgDecGemmIO), vp]
+        L.ohw_dbg_enc_gemm.argtypes = [C.POINTER(DbgEncGemmIO), vp]
         L.ohw_dbg_embed.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, ip, ip, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
         L.ohw_dbg_layernorm.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp]
         L.ohw_state_set_audio_ctx.argtypes = [vp, C.c_int]
