@@ -944,7 +944,8 @@ const char* ohw_last_error(void);
 int ohw_abi_version(void);
 /* copy an internal activation to the host as f32: what = "mel" [B][n_mels][3000], "conv1"        */
 /* [B][3000][d], "stem" / "block0" / "enc" [B][1500][d], "xk<l>" / "xv<l>" [B][1500][d]            */
-/* (under a reduced audio context C, "stem" / "block0" / "enc" / "xk<l>" / "xv<l>" are [B][C][d])    */
+/* (under a reduced audio context C, "stem" / "block0" / "enc" / "xk<l>" / "xv<l>" are [B][C][d]),   */
+/* "mel_t" [B][3002][128]: the 16-bit time-major image conv1 reads, pad rows and channels included  */
 int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int64_t out_elems);
 /* 64-bit digest of the index-th resident weight buffer (engine layout); returns OHW_E_INVALID_ARG  */
 /* past the last buffer.  Lets tests prove "synthetic ctx == ctx loaded from the synthetic file".  */

@@ -2570,6 +2570,7 @@ int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int6
       HIP_CHECK(hipStreamSynchronize(s));
     };
     if (w == "mel") { from_f32(st->logmel.p, (int64_t)batch * hp.n_mels * CHUNK_FRAMES); return; }
+    if (w == "mel_t") { from_t(st->mel_t.p, (int64_t)batch * MEL_ROWS * MEL_CPAD); return; }   // the image conv1 reads, pad rows and channels included
     if (w == "align_q" || w == "align_p" || w == "align_m") {
       // window batch - 1 of the last ohw_state_align
       const int b = batch - 1;

@@ -1564,10 +1564,11 @@ class State:
                 return out[:A * n_all * n_keys].reshape(A, n_all, n_keys).copy()
             return out[:(n_text + 1) * n_keys].reshape(n_text + 1, n_keys).copy()
         d, T = hp.n_audio_state, hp.n_audio_ctx
-        shape = {"mel": (batch, hp.n_mels, CHUNK_FRAMES), "conv1": (batch, CHUNK_FRAMES, d)}.get(what, (batch, T, d))
+        shape = {"mel": (batch, hp.n_mels, CHUNK_FRAMES), "conv1": (batch, CHUNK_FRAMES, d),
+                 "mel_t": (batch, CHUNK_FRAMES + 2, 128)}.get(what, (batch, T, d))
         out = np.empty(shape, dtype=np.float32)
         _check(lib().ohw_state_fetch(self.h, what.encode(), batch, _fp(out), out.size))
-        if what not in ("mel", "conv1") and self.audio_ctx < T:
+        if what not in ("mel", "conv1", "mel_t") and self.audio_ctx < T:
             # the last encode ran a reduced context: the library packed [batch][C][d] into the front of the buffer
             Cn = self.audio_ctx
             out = out.reshape(-1)[:batch * Cn * d].reshape(batch, Cn, d).copy()
