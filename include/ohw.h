@@ -376,6 +376,22 @@ int ohw_greedy_ex(ohw_state* st, const ohw_sample_params* p, int batch, int max_
  * caller cuts the pass at whisper.cpp's other loop exits and discards the draws it kept (ohw_rng_discard_draws).    */
 int ohw_sample_pass(ohw_state* st, const ohw_sample_params* p, int batch, int max_tokens, float temperature, const int32_t* active,
                     const double* uniforms /* [batch][max_tokens] */, const ohw_greedy_result* out);
+/* the same pass with best_of (1..5) candidates per window: row w * best_of + j of `out` is candidate j of window w, drawing
+ * with uniforms[w][j][step]; needs max_batch >= n_windows * best_of.  The prefill and the task prompt run once per window; the
+ * best_of rows of a window share that past through a kv_slot table built on the device (positions below the window's shared
+ * length read the window's cache row - row w, or row w * best_of under a context table with more than one window - every
+ * later position the candidate's own row; ohw_state_fetch "sample_slots" returns the table of the last call as
+ * [n_windows * best_of][n_text_ctx]) and its cross K/V, streamed once per step for all of them (cross_attn_rows_kernel).  On
+ * the first step every row of a window reads the window's prompt logits, so the no-speech probability is the window's and
+ * is reported in each of its rows.  Windows with active[w] == 0 are not decoded (their rows' results are 0).  A row stops at
+ * end-of-text or a length limit only; the step is skipped for a window once all its rows have stopped.  Language tables,
+ * per-window audio contexts, context tables, the logit bias, ohw_state_set_batch_invariant and the persistent step (at most
+ * 16 rows) all apply as they do to ohw_beam_search; nothing of the group layout outlives the call.  A row's arithmetic is
+ * ohw_sample_pass's sampler; its decoder step takes the beam rows' kernels, so bit equality with ohw_sample_pass is not
+ * promised.  best_of = 1 is ohw_sample_pass.                                                                            */
+int ohw_sample_pass_n(ohw_state* st, const ohw_sample_params* p, int n_windows, int best_of, int max_tokens, float temperature,
+                      const int32_t* active /* [n_windows] */, const double* uniforms /* [n_windows][best_of][max_tokens] */,
+                      const ohw_greedy_result* out /* rows [n_windows * best_of] */);
 
 /* beam search for the windows of the last ohw_encode (BASELINE.json config #5: beam = 5, hipGraph-captured decoder step).
  * The reference never uses one (Greedy{best_of:1}, src/engine/whisper.rs:243); the rule is the published Whisper
@@ -748,9 +764,37 @@ int ohw_engine_set_force_len(ohw_engine* e, int n_tokens);
  *     cut at the first of its loop exits, like a sampled pass; it is traced at temperature 0 (ohw_engine_last_trace).
  *     DEVIATION: whisper.cpp applies its loop exits to every decoder during the search; beam search is not causal, so here they
  *     are applied to the winner after it
- *   - passes at T > 0 are the unchanged ladder (whisper.cpp as recalled: at t_cur > 0 the beam strategy samples, best_of)
+ *   - passes at T > 0 are the unchanged ladder (whisper.cpp as recalled: at t_cur > 0 the beam strategy samples, best_of:
+ *     ohw_engine_set_best_of gives those passes their candidates)
  *   - the LANES / PIPELINE schedules are not used: a call with beam on runs one batch after the other on the engine's own state */
 int ohw_engine_set_beam_size(ohw_engine* e, int k);
+/* best-of sampling above T = 0 (whisper.cpp's best_of, for the greedy and the beam strategy alike; restated from memory,
+ * unpinned - DESIGN.md section 9 marks the definitions): n = 1 (default) = today's ladder, n = 2..5 = every rung with T > 0
+ * samples n candidates per pending window and keeps one.  OHW_E_INVALID_ARG outside 1..5, for n > max_batch, and together with
+ * ohw_engine_set_force_len (whichever setter comes second fails).  Nothing changes at T = 0 or when temperature_inc <= 0.
+ *   - candidate j draws from its own std::mt19937(j) (ohw_rng_new(j)), which lives where today's one generator lives (per cut;
+ *     per recording and call in the seek loops); candidate 0 is today's decoder.  After a rung candidate j's generator has
+ *     advanced by the draws its own cut pass consumed
+ *   - every candidate is cut at the loop exits and judged like today's one row; ohw_best_of_pick_host picks: a candidate is
+ *     out when it failed or its entropy is below entropy_thold; of the rest the highest avg_logprob wins, the lowest j among
+ *     equals; all out: candidate 0.  The kept candidate is the rung's pass from there on (acceptance test, no-speech rule,
+ *     carry, segments, alignment); ohw_engine_last_trace records it, ohw_engine_last_candidates all of them
+ *   - with n > 1 the rungs are sampled on the device (ohw_sample_pass_n) whatever ohw_engine_set_fallback_device says
+ *   - a decode batch holds floor(max_batch / max(n, beam size, 1)) windows; calls with n > 1 run one batch after the other on
+ *     the engine's own state, like beam calls                                                                             */
+int ohw_engine_set_best_of(ohw_engine* e, int n);
+/* windows per decode batch of an engine with these settings: floor(max_batch / max(best_of, beam_size, 1)), what every
+ * transcribe path cuts its batches by (host only); OHW_E_INVALID_ARG (negative) for max_batch < 1, a beam size other than 0 or
+ * 2..5, best_of outside 1..5, or a result of 0 */
+int ohw_batch_windows_host(int max_batch, int beam_size, int best_of);
+/* the pick of one rung over n judged candidates (host only; the engine calls this function): *kept = the candidate's index */
+int ohw_best_of_pick_host(const ohw_seq_eval* ev, int n, const ohw_decode_policy* q, int* kept);
+/* every best-of rung of the last transcribe, flat: {window index, temperature * 1000, N, kept j}, then per candidate {n, n
+ * tokens (cut; end-of-text included when it was sampled)}; rungs in the order of ohw_engine_last_trace.  Empty when best_of = 1 */
+int ohw_engine_last_candidates(ohw_engine* e, const int32_t** data, int* n);
+/* the log-probabilities of those candidates' tokens, in the record's order and nothing else: what ohw_seq_eval_host needs to
+ * judge a recorded candidate again */
+int ohw_engine_last_candidate_logprobs(ohw_engine* e, const float** data, int* n);
 /* reduced audio context of every window ohw_engine_transcribe runs (ohw_state_set_audio_ctx on the engine's own, pipeline
  * and lane states): 0 (default) = off, the full context; n > 0 = that context for every window of every window mode and
  * schedule - a transcribe in which some window holds samples past n * 320 fails with OHW_E_INVALID_ARG naming the window
@@ -922,6 +966,7 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
 int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text);           /* ohw_engine_set_initial_prompt on every engine */
+int ohw_pool_set_best_of(ohw_pool* p, int n);                             /* ohw_engine_set_best_of on every engine */
 int ohw_pool_set_carry_context(ohw_pool* p, int max_tokens);              /* ohw_engine_set_carry_context on every engine */
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
 int ohw_pool_set_packed_encoder(ohw_pool* p, int on);
@@ -945,7 +990,9 @@ int ohw_abi_version(void);
 /* copy an internal activation to the host as f32: what = "mel" [B][n_mels][3000], "conv1"        */
 /* [B][3000][d], "stem" / "block0" / "enc" [B][1500][d], "xk<l>" / "xv<l>" [B][1500][d]            */
 /* (under a reduced audio context C, "stem" / "block0" / "enc" / "xk<l>" / "xv<l>" are [B][C][d]),   */
-/* "mel_t" [B][3002][128]: the 16-bit time-major image conv1 reads, pad rows and channels included  */
+/* "mel_t" [B][3002][128]: the 16-bit time-major image conv1 reads, pad rows and channels included; */
+/* "sample_slots" [batch][n_text_ctx]: the kv_slot table of the last ohw_sample_pass_n, batch = its   */
+/* n_windows * best_of rows (entries are cache row indices, exact in f32)                            */
 int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int64_t out_elems);
 /* 64-bit digest of the index-th resident weight buffer (engine layout); returns OHW_E_INVALID_ARG  */
 /* past the last buffer.  Lets tests prove "synthetic ctx == ctx loaded from the synthetic file".  */
@@ -1030,11 +1077,21 @@ int ohw_dbg_sample(ohw_state* st, const ohw_sample_params* p, const float* logit
 int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* p, const float* logits, const int32_t* history, int hist_stride,
                      const int32_t* n_hist, int batch, float temperature, const double* uniforms, int32_t* tokens_out,
                      float* logprobs_out, float* no_speech_out);
+/* the group form of that sampler (ohw_sample_pass_n) once on caller data: rows = n_windows * group, row r = candidate r % group
+ * of window r / group.  first != 0 (the step behind the prompt): logits [n_windows][n_vocab], every row of a window reads its
+ * window's row; first == 0: logits [rows][n_vocab].  history / n_hist / uniforms per row as above; done [rows] in and out: a
+ * row with done != 0 is not sampled (token_out 0, nothing written or advanced).  win_done_out [n_windows]: 1 once every row of
+ * the window is done - the windows whose rows all came in done start at 1, the others are set by the row that finishes last.
+ * n_cur_out [rows] (may be NULL): tokens in the row's history afterwards.  The other outputs as above.                     */
+int ohw_dbg_sample_group(ohw_state* st, const ohw_sample_params* p, const float* logits, const int32_t* history, int hist_stride,
+                         const int32_t* n_hist, int n_windows, int group, int first, float temperature, const double* uniforms,
+                         int32_t* done, int32_t* tokens_out, float* logprobs_out, float* no_speech_out, int32_t* win_done_out,
+                         int32_t* n_cur_out);
 /* the DEVICE language pick (ohw_state_detect_window_lang's kernel) on caller-supplied rows: logits [batch][n_vocab] (host);
  * ids_out [batch], probs_out [batch][n_langs] or NULL.  Leaves the state's language table alone.                       */
 int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* ids_out, float* probs_out);
-/* counters of a state's graph caches: "step_captures" / "beam_captures" (graphs / graph pairs captured so far),
- * "step_graphs" / "beam_graphs" (entries held now), "persist_launches" (persistent decoder steps launched or captured),
+/* counters of a state's graph caches: "step_captures" / "beam_captures" (graphs / graph pairs captured so far; a group pass's
+ * graph counts as a step capture), "step_graphs" / "beam_graphs" / "group_graphs" (entries held now; the last: ohw_sample_pass_n's), "persist_launches" (persistent decoder steps launched or captured),
  * "enc_rows" (rows M of the dense encoder GEMMs of the last encode: B * E, or the sum of the lengths when it ran packed);
  * OHW_E_INVALID_ARG for another name.  A second ohw_greedy /
  * ohw_beam_search with the same batch, parameters and stream must add no capture (tests/test_gpu_beam.py).

@@ -192,6 +192,9 @@ def _add_transcribe_options(t):
     t.add_argument("--beam-size", type=_beam_size_arg, default=0, metavar="K",
                    help="beam search with K beams (2..5) as the temperature-0 strategy (whisper.cpp's beam_size); 0 (default): greedy. "
                         "A decode batch then holds max-batch / K windows; the fallback temperatures sample as before")
+    t.add_argument("--best-of", type=_best_of_arg, default=1, metavar="N",
+                   help="candidates per window (1..5) on every fallback temperature above 0 (whisper.cpp's best_of), sampled on the "
+                        "device, the best kept; 1 (default): one sampled sequence. A decode batch then holds max-batch / max(N, K) windows")
     t.add_argument("--word-timestamps", action="store_true",
                    help="align every window's tokens on the device and add \"segments\" and \"words\" arrays (text, t0, t1 in seconds) to "
                         "the JSON; needs --align-heads")
@@ -210,6 +213,16 @@ def _beam_size_arg(v: str) -> int:
     return k
 
 
+def _best_of_arg(v: str) -> int:
+    try:
+        n = int(v)
+    except ValueError:
+        n = -1
+    if not 1 <= n <= 5:
+        raise argparse.ArgumentTypeError(f"takes a number of candidates in 1..5, not '{v}'")
+    return n
+
+
 def _max_context_arg(v: str) -> int:
     try:
         n = int(v)
@@ -221,7 +234,14 @@ def _max_context_arg(v: str) -> int:
 
 
 def _check_beam(args) -> bool:
-    """--beam-size against the other options, before any model is loaded"""
+    """--beam-size and --best-of against the other options, before any model is loaded"""
+    if args.best_of > 1:
+        if args.best_of > args.max_batch:
+            print(f"error: --best-of {args.best_of} needs --max-batch >= {args.best_of} (a window takes one decoder row per candidate)", file=sys.stderr)
+            return False
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            print("error: --best-of is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+            return False
     if args.beam_size == 0:
         return True
     if args.beam_size > args.max_batch:
@@ -290,6 +310,8 @@ def _transcribe_many(args) -> int:
         eng.set_initial_prompt(args.prompt)
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
+    if args.best_of > 1:
+        eng.set_best_of(args.best_of)
     if args.carry_context and args.max_context != 0:      # --max-context 0 carries nothing, as in whisper.cpp
         eng.set_carry_context(args.max_context)
     if args.packed_encoder:
@@ -364,6 +386,8 @@ def _transcribe_one(args) -> int:
         eng.set_initial_prompt(args.prompt)
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
+    if args.best_of > 1:
+        eng.set_best_of(args.best_of)
     if args.packed_encoder:
         eng.set_packed_encoder(True)
     if args.detect_language:

@@ -1639,7 +1639,10 @@ __device__ __forceinline__ double wave_incl_scan(double x, int lane) {
   return x;
 }
 
-__global__ __launch_bounds__(SP_THREADS) void sampler_t_kernel(SamplerParams p, const float* __restrict__ temp, const double* __restrict__ uniforms) {
+// One body for both forms.  GROUP = false is the sampler of ohw_sample_pass (g is unused and compiles away); GROUP = true adds
+// what the group form needs around the same row arithmetic: where the first step's logits row lives, and the window's done flag
+template <bool GROUP>
+__device__ __forceinline__ void sampler_t_row(SamplerParams p, const float* __restrict__ temp, const double* __restrict__ uniforms, SampGroup g) {
   __shared__ SampAcc sh[SPT_WAVES];
   __shared__ int sh_ts[SPT_WAVES];
   __shared__ double sh_wsum[SPT_WAVES];
@@ -1649,7 +1652,7 @@ __global__ __launch_bounds__(SP_THREADS) void sampler_t_kernel(SamplerParams p, 
   if (p.done[b]) return;
   const float T = temp[0];
   const int np_now = p.n_past[b] + p.advance;
-  const float* lg = p.logits + (int64_t)b * p.ld;
+  const float* lg = p.logits + (int64_t)(GROUP && !p.advance ? b / g.group : b) * p.ld;
   int32_t* toks = p.tokens + (int64_t)b * p.max_tokens;
   const int n_cur = p.n_cur[b];
   SampState st;
@@ -1857,11 +1860,52 @@ __global__ __launch_bounds__(SP_THREADS) void sampler_t_kernel(SamplerParams p, 
       const int np = np_now;
       if (n_cur + 1 >= n_max || n_cur + 1 >= p.max_tokens || np + 1 >= p.n_text_ctx) finished = true;
     }
-    if (finished) { p.done[b] = 1; atomicAdd(p.n_done, 1); }
+    if (finished) {
+      p.done[b] = 1; atomicAdd(p.n_done, 1);
+      if (GROUP) {
+        // the window's rows finish on different steps and, within a step, in any order: the one that draws the window's last
+        // ticket flags the window.  The flag is read by the NEXT launches only (the decoder step's cross-attention)
+        const int w = b / g.group;
+        const unsigned ticket = __hip_atomic_fetch_add(g.win_cnt + w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == (unsigned)g.group - 1u) g.win_done[w] = 1;
+      }
+    }
   }
+}
+__global__ __launch_bounds__(SP_THREADS) void sampler_t_kernel(SamplerParams p, const float* __restrict__ temp, const double* __restrict__ uniforms) {
+  sampler_t_row<false>(p, temp, uniforms, SampGroup{});
+}
+__global__ __launch_bounds__(SP_THREADS) void sampler_group_kernel(SamplerParams p, SampGroup g, const float* __restrict__ temp, const double* __restrict__ uniforms) {
+  sampler_t_row<true>(p, temp, uniforms, g);
 }
 void launch_sampler_t(const SamplerParams& p, const float* temperature, const double* uniforms, hipStream_t s) {
   hipLaunchKernelGGL(sampler_t_kernel, dim3(SAMPLER_SPLIT, p.batch), dim3(SP_THREADS), 0, s, p, temperature, uniforms);
+  HIP_CHECK(hipGetLastError());
+}
+void launch_sampler_group(const SamplerParams& p, const SampGroup& g, const float* temperature, const double* uniforms, hipStream_t s) {
+  if (g.group < 1 || g.group > 5 || p.batch < 1 || p.batch % g.group != 0 || !g.win_done || !g.win_cnt)
+    throw Error(OHW_E_INVALID_ARG, "group sampler: 1..5 candidates per window, rows a multiple of that, and the windows' flags");
+  hipLaunchKernelGGL(sampler_group_kernel, dim3(SAMPLER_SPLIT, p.batch), dim3(SP_THREADS), 0, s, p, g, temperature, uniforms);
+  HIP_CHECK(hipGetLastError());
+}
+
+// the layout of a group pass (kernels.hpp): one workgroup per row, 4-byte vector stores
+__global__ __launch_bounds__(256) void sample_group_init_kernel(SampGroupInit q) {
+  const int r = blockIdx.x, w = r / q.group, j = r - w * q.group;
+  const int shared = q.shared[w], off = q.active[w] ? 0 : 1;
+  const int past_row = w * q.prefix_stride;
+  int32_t* row = q.kv_slot + (int64_t)r * q.n_ctx;
+  for (int i = threadIdx.x; i < q.n_ctx; i += 256) row[i] = i < shared ? past_row : r;
+  if (threadIdx.x == 0) {
+    q.n_past[r] = shared;
+    q.done[r] = off;
+    if (j == 0) { q.win_done[w] = off; q.win_cnt[w] = off ? (unsigned)q.group : 0u; }
+  }
+}
+void launch_sample_group_init(const SampGroupInit& q, hipStream_t s) {
+  if (q.group < 1 || q.group > 5 || q.rows < 1 || q.rows % q.group != 0 || q.n_ctx < 1 || q.prefix_stride < 1)
+    throw Error(OHW_E_INVALID_ARG, "group sampler: bad layout");
+  hipLaunchKernelGGL(sample_group_init_kernel, dim3(q.rows), dim3(256), 0, s, q);
   HIP_CHECK(hipGetLastError());
 }
 

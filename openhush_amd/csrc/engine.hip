@@ -227,6 +227,13 @@ struct ohw_state {
   struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; int t_len = 0; bool invariant = false, persist = false, temp = false, var = false; SamplerParams spar{}; };
   bool batch_invariant = false;      // cross-attention variant picked from n_new alone (state_set_batch_invariant)
   std::vector<StepGraph> step_graphs;
+  // best-of sampling (ohw_sample_pass_n; made on first use): the pass's constant kv_slot table [rows][n_text_ctx], then per window
+  // {shared length, active, done flag, finished-row count} [4][max_batch]; sn_rows: rows of the last pass's table ("sample_slots").
+  // Its replayed {decoder step with kv_group = N, group sampler} graphs are kept apart from step_graphs, keyed on N as well
+  DevBuf sn_slot, sn_win;
+  int sn_rows = 0;
+  struct GroupGraph { StepGraph g; int windows = 0, group = 0; };
+  std::vector<GroupGraph> group_graphs;
   bool graphs_enabled = true;
   int graph_max_batch = 32;         // graphs for batches below this (OHW_GRAPH_MAX_BATCH)
   // word timestamps (ohw_state_set_align_heads / ohw_state_align; align.hip).  al_heads: the caller's list; the buffers are made
@@ -907,6 +914,10 @@ void ohw_state_free(ohw_state* st) {
       if (g.exec[q]) (void)hipGraphExecDestroy(g.exec[q]);
       if (g.graph[q]) (void)hipGraphDestroy(g.graph[q]);
     }
+  for (auto& g : st->group_graphs) {
+    if (g.g.exec) (void)hipGraphExecDestroy(g.g.exec);
+    if (g.g.graph) (void)hipGraphDestroy(g.g.graph);
+  }
   if (st->own_stream) (void)hipStreamDestroy(st->own_stream);
   delete st;
 }
@@ -1336,6 +1347,41 @@ void ohw_default_sample_params(const ohw_ctx* ctx, ohw_sample_params* p) {
   p->force_len = 0;
 }
 
+// what a device-resident loop left in the state's sampler buffers, rows 0 .. batch - 1, as an ohw_greedy_result
+static void decode_read_back(ohw_state* st, int batch, int max_tokens, const ohw_greedy_result* res) {
+    const ohw_ctx* c = st->ctx;
+    hipStream_t s = st->stream;
+    int32_t* tokens_out = res->tokens;
+    int32_t* n_tokens_out = res->n_tokens;
+    float* sum_logprob_out = res->sum_logprob;
+    std::vector<int32_t> toks((size_t)batch * st->max_tokens), ncur((size_t)batch);
+    HIP_CHECK(hipMemcpyAsync(toks.data(), st->tokens.p, toks.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(ncur.data(), st->n_cur.p, ncur.size() * 4, hipMemcpyDeviceToHost, s));
+    if (sum_logprob_out) HIP_CHECK(hipMemcpyAsync(sum_logprob_out, st->sum_lp.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+    std::vector<int32_t> last((size_t)batch);
+    std::vector<float> lps;
+    HIP_CHECK(hipMemcpyAsync(last.data(), st->next_tok.p, last.size() * 4, hipMemcpyDeviceToHost, s));
+    if (res->no_speech_prob) HIP_CHECK(hipMemcpyAsync(res->no_speech_prob, st->nosp_prob.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+    if (res->token_logprobs) {
+      lps.resize((size_t)batch * (st->max_tokens + 1));
+      HIP_CHECK(hipMemcpyAsync(lps.data(), st->tok_lp.p, lps.size() * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    persist_check(st);
+    for (int b = 0; b < batch; ++b) {
+      const int n = std::min(ncur[(size_t)b], max_tokens);
+      n_tokens_out[b] = n;
+      std::memcpy(tokens_out + (size_t)b * max_tokens, &toks[(size_t)b * st->max_tokens], (size_t)n * 4);
+      const bool eot = last[(size_t)b] == c->tok.eot && ncur[(size_t)b] <= max_tokens;
+      if (res->ended_by_eot) res->ended_by_eot[b] = eot ? 1 : 0;
+      if (res->token_logprobs) {
+        float* dst = res->token_logprobs + (size_t)b * (max_tokens + 1);
+        const int m = std::min(n + (eot ? 1 : 0), max_tokens + 1);
+        std::memcpy(dst, &lps[(size_t)b * (st->max_tokens + 1)], (size_t)m * 4);
+      }
+    }
+}
+
 // the device-resident decode loop of ohw_greedy_ex (tp == nullptr: arg-max) and of ohw_sample_pass (tp: one temperature pass
 // over the windows tp->active names, drawing with tp->uniforms).  Throws; the entries wrap it in guard().
 struct TempPass {
@@ -1346,9 +1392,6 @@ struct TempPass {
 static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, int max_tokens, const ohw_greedy_result* res, const TempPass* tp) {
     const char* what = tp ? "sample_pass" : "greedy";
     if (!st || !sp || !res || !res->tokens || !res->n_tokens) throw Error(OHW_E_INVALID_ARG, "null argument");
-    int32_t* tokens_out = res->tokens;
-    int32_t* n_tokens_out = res->n_tokens;
-    float* sum_logprob_out = res->sum_logprob;
     if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": batch must equal the batch of the last ohw_encode");
     const ohw_ctx* c = st->ctx;
     check_decode_ctx(st, what);
@@ -1484,32 +1527,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
       }
     });
     if (!tp) HIP_CHECK(hipEventRecord(st->ev[5], s));
-    std::vector<int32_t> toks((size_t)batch * st->max_tokens), ncur((size_t)batch);
-    HIP_CHECK(hipMemcpyAsync(toks.data(), st->tokens.p, toks.size() * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(ncur.data(), st->n_cur.p, ncur.size() * 4, hipMemcpyDeviceToHost, s));
-    if (sum_logprob_out) HIP_CHECK(hipMemcpyAsync(sum_logprob_out, st->sum_lp.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    std::vector<int32_t> last((size_t)batch);
-    std::vector<float> lps;
-    HIP_CHECK(hipMemcpyAsync(last.data(), st->next_tok.p, last.size() * 4, hipMemcpyDeviceToHost, s));
-    if (res->no_speech_prob) HIP_CHECK(hipMemcpyAsync(res->no_speech_prob, st->nosp_prob.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    if (res->token_logprobs) {
-      lps.resize((size_t)batch * (st->max_tokens + 1));
-      HIP_CHECK(hipMemcpyAsync(lps.data(), st->tok_lp.p, lps.size() * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    persist_check(st);
-    for (int b = 0; b < batch; ++b) {
-      const int n = std::min(ncur[(size_t)b], max_tokens);
-      n_tokens_out[b] = n;
-      std::memcpy(tokens_out + (size_t)b * max_tokens, &toks[(size_t)b * st->max_tokens], (size_t)n * 4);
-      const bool eot = last[(size_t)b] == c->tok.eot && ncur[(size_t)b] <= max_tokens;
-      if (res->ended_by_eot) res->ended_by_eot[b] = eot ? 1 : 0;
-      if (res->token_logprobs) {
-        float* dst = res->token_logprobs + (size_t)b * (max_tokens + 1);
-        const int m = std::min(n + (eot ? 1 : 0), max_tokens + 1);
-        std::memcpy(dst, &lps[(size_t)b * (st->max_tokens + 1)], (size_t)m * 4);
-      }
-    }
+    decode_read_back(st, batch, max_tokens, res);
     if (!tp) st->last.decode_steps = steps;     // ohw_state_timings reports the T = 0 loop
 }
 
@@ -1522,6 +1540,155 @@ int ohw_sample_pass(ohw_state* st, const ohw_sample_params* sp, int batch, int m
   return guard([&] {
     const TempPass tp{temperature, active, uniforms};
     decode_loop(st, sp, batch, max_tokens, out, &tp);
+  });
+}
+
+// ohw_sample_pass_n: one temperature pass with N candidates per window (best-of sampling).  The prefill and the prompt run once
+// per window, as in beam_search_run; the N rows of window w then share that past through a kv_slot table that is CONSTANT for
+// the pass (candidates never reorder) and the window's cross K/V (run_decoder_step with kv_group = N).  Nothing of the layout
+// outlives the call: every decode entry sets n_past, the done flags, the histories and its own slot table (or none) itself
+static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W, int N, int max_tokens, const TempPass& tp, const ohw_greedy_result* res) {
+    if (!st || !sp || !res || !res->tokens || !res->n_tokens) throw Error(OHW_E_INVALID_ARG, "null argument");
+    const int R = W * N;
+    if (W < 1 || W != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: n_windows must equal the batch of the last ohw_encode");
+    if (N < 2 || N > 5) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: best_of must be in 1..5");
+    if (R > st->max_batch) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: the state needs max_batch >= n_windows * best_of decoder rows");
+    if (!tp.active || !tp.uniforms || !(tp.temperature > 0.0f) || max_tokens < 1)
+      throw Error(OHW_E_INVALID_ARG, "sample_pass_n: needs temperature > 0, active, uniforms and max_tokens >= 1");
+    if (sp->force_len > 0) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: force_len is a single-candidate knob");
+    const ohw_ctx* c = st->ctx;
+    check_decode_ctx(st, "sample_pass_n");
+    const bool lang_tab = !st->lang_kind.empty();     // then sp->lang_id is ignored: the N rows of a window share its prompt
+    if (lang_tab) check_window_lang(st, W, "sample_pass_n");
+    else if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: lang_id out of range");
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = st->stream;
+    const int C = c->hp.n_text_ctx, MB = st->max_batch;
+    if (!st->sn_slot.p) { st->sn_slot.alloc((size_t)MB * C * 4, true); st->sn_win.alloc((size_t)MB * 4 * 4, true); }
+    int32_t* d_shared = st->sn_win.as<int32_t>();
+    int32_t* d_active = d_shared + MB;
+    int32_t* d_wdone = d_shared + 2 * MB;
+    unsigned* d_wcnt = (unsigned*)(d_shared + 3 * MB);
+    int32_t prompt[8];
+    ohw_sample_params psp = *sp;
+    if (lang_tab) psp.lang_id = 0;
+    const int n_prompt = build_prompt(c, &psp, prompt);
+    const bool wp = !st->wp_len.empty();
+    const int n_max = std::min(std::min(std::min(sp->n_max, st->max_tokens), c->hp.n_text_ctx - n_prompt - window_prompt_max(st)), max_tokens);
+    if (n_max < 1) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: n_max < 1");
+    std::vector<int32_t> ptoks((size_t)W * n_prompt), shared((size_t)W, n_prompt), act((size_t)W), skip((size_t)W);
+    int32_t n_done0[4] = {0, 0, 0, 0};
+    for (int w = 0; w < W; ++w) {
+      std::memcpy(&ptoks[(size_t)w * n_prompt], prompt, (size_t)n_prompt * 4);
+      act[(size_t)w] = tp.active[w] ? 1 : 0;
+      skip[(size_t)w] = act[(size_t)w] ? 0 : 1;
+      n_done0[0] += skip[(size_t)w] * N;             // n_done counts rows
+    }
+    run_prefill(st, W, tp.active, "sample_pass_n");  // checks the context table's batch
+    for (int w = 0; wp && w < W; ++w) shared[(size_t)w] += st->wp_len[(size_t)w];
+    if (lang_tab) fill_prompt_rows(st, &psp, W, n_prompt);
+    else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
+    if (wp) HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_lens.p, (size_t)W * 4, hipMemcpyDeviceToDevice, s));
+    else HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)W * 4, s));
+    HIP_CHECK(hipMemcpyAsync(st->done.p, skip.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));     // the prompt pass skips inactive windows
+    HIP_CHECK(hipMemcpyAsync(st->n_done.p, n_done0, 16, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_shared, shared.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_active, act.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->samp_temp.p, &tp.temperature, 4, hipMemcpyHostToDevice, s));
+    const int nu = std::min(max_tokens, st->max_tokens);
+    HIP_CHECK(hipMemcpy2DAsync(st->samp_u.p, (size_t)st->max_tokens * 8, tp.uniforms, (size_t)max_tokens * 8, (size_t)nu * 8, (size_t)R, hipMemcpyHostToDevice, s));
+    for (DevBuf* b : {&st->n_cur, &st->sum_lp, &st->next_tok, &st->nosp_prob}) HIP_CHECK(hipMemsetAsync(b->p, 0, (size_t)R * 4, s));
+    SamplerParams spar;
+    ohw_sample_params eff = *sp;
+    eff.n_max = n_max;
+    fill_sampler(st, &eff, R, &spar);
+    SampGroup grp{N, d_wdone, d_wcnt};
+    // under a context table the windows' pasts differ in length: window w's goes to row w * N, which only its own candidates
+    // write (beam_search_run gives the reason)
+    const int stride = (wp && W > 1) ? N : 1;
+    SampGroupInit gi{};
+    gi.rows = R; gi.group = N; gi.n_ctx = C; gi.prefix_stride = stride; gi.shared = d_shared; gi.active = d_active;
+    gi.kv_slot = st->sn_slot.as<int32_t>(); gi.n_past = st->n_past.as<int32_t>(); gi.done = st->done.as<int32_t>(); gi.win_done = d_wdone; gi.win_cnt = d_wcnt;
+    const int32_t* slots = st->sn_slot.as<int32_t>();
+    Dispatch::run(c->dtype, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      {
+        struct SkipDone { bool& f; explicit SkipDone(bool& r) : f(r) { f = true; } ~SkipDone() { f = false; } } skip_done(st->skip_done);
+        run_decoder_step<T>(st, W, n_prompt);                     // the prompt once per window; its K/V stays in cache rows 0 .. W-1
+      }
+      if (stride > 1)
+        for (int w = W - 1; w >= 1; --w)                          // from the last window down: row w * N < W is a later window's source
+          launch_kv_prefix_move<T>(st->self_kv.p, 2 * c->hp.n_text_layer, MB, c->hp.n_text_head, C, w, w * N, shared[(size_t)w], s);
+      launch_sample_group_init(gi, s);                            // slot table, n_past and done per row, the windows' flags
+      st->sn_rows = R;
+      HIP_CHECK(hipStreamSynchronize(s));                         // the vectors above are stack-lifetime sources
+      spar.advance = 0;
+      launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);   // first token of every row from its window's prompt logits
+      spar.advance = 1;
+      const bool use_graph = st->graphs_enabled && st->prof_class == 0 && s != nullptr;
+      hipGraphExec_t step_exec = nullptr;
+      if (use_graph) {
+        for (auto& gg : st->group_graphs) {
+          const auto& g = gg.g;
+          if (gg.windows == W && gg.group == N && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant &&
+              g.persist == st->persist && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
+        }
+      }
+      if (use_graph && !step_exec) {
+        if (st->group_graphs.size() >= 4) {     // bounded: drop the oldest capture
+          auto& g = st->group_graphs.front().g;
+          if (g.exec) (void)hipGraphExecDestroy(g.exec);
+          if (g.graph) (void)hipGraphDestroy(g.graph);
+          st->group_graphs.erase(st->group_graphs.begin());
+        }
+        ohw_state::GroupGraph ng;
+        hipStream_t cap = st->own_stream;       // captured as decode_loop captures its step (the reasons are given there)
+        CaptureGate gate;
+        struct StreamSwap { ohw_state* st; hipStream_t keep; ~StreamSwap() { st->stream = keep; } } swap{st, st->stream};
+        st->stream = cap;
+        HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
+        try {
+          run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
+          launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), cap);
+        } catch (...) {
+          hipGraph_t g = nullptr;
+          (void)hipStreamEndCapture(cap, &g);
+          if (g) (void)hipGraphDestroy(g);
+          throw;
+        }
+        HIP_CHECK(hipStreamEndCapture(cap, &ng.g.graph));
+        hipError_t ie = hipGraphInstantiate(&ng.g.exec, ng.g.graph, nullptr, nullptr, 0);
+        if (ie != hipSuccess) { (void)hipGraphDestroy(ng.g.graph); HIP_CHECK(ie); }
+        ng.windows = W; ng.group = N; ng.g.batch = R; ng.g.cus = st->stream_cus; ng.g.t_len = st->enc_ctx; ng.g.var = st->enc_var; ng.g.invariant = st->batch_invariant;
+        ng.g.persist = st->persist; ng.g.temp = true; ng.g.spar = spar;
+        st->group_graphs.push_back(ng);
+        ++st->step_captures;
+        step_exec = ng.g.exec;
+      }
+      int32_t n_done_host = 0;
+      for (int it = 1; it < n_max; ++it) {
+        if (use_graph) {
+          HIP_CHECK(hipGraphLaunch(step_exec, s));
+        } else {
+          run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
+          launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);
+        }
+        if ((it & 7) == 7) {
+          HIP_CHECK(hipMemcpyAsync(&n_done_host, st->n_done.p, 4, hipMemcpyDeviceToHost, s));
+          HIP_CHECK(hipStreamSynchronize(s));
+          if (n_done_host >= R) break;
+        }
+      }
+    });
+    decode_read_back(st, R, max_tokens, res);
+}
+
+int ohw_sample_pass_n(ohw_state* st, const ohw_sample_params* sp, int n_windows, int best_of, int max_tokens, float temperature,
+                      const int32_t* active, const double* uniforms, const ohw_greedy_result* out) {
+  if (best_of == 1) return ohw_sample_pass(st, sp, n_windows, max_tokens, temperature, active, uniforms, out);
+  return guard([&] {
+    const TempPass tp{temperature, active, uniforms};
+    sample_pass_group(st, sp, n_windows, best_of, max_tokens, tp, out);
   });
 }
 
@@ -1808,6 +1975,7 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "beam_graphs") return (int)st->beam_graphs.size();
   if (n == "step_captures") return st->step_captures;
   if (n == "step_graphs") return (int)st->step_graphs.size();
+  if (n == "group_graphs") return (int)st->group_graphs.size();
   if (n == "persist_launches") return st->persist_launches;
   if (n == "xattn.chunk") return (int)std::min<int64_t>(st->tally_xchunk, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
@@ -2129,6 +2297,64 @@ int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* sp, const float* lo
   return guard([&] {
     if (!(temperature > 0.0f)) throw Error(OHW_E_INVALID_ARG, "dbg_sample_t: temperature must be > 0");
     dbg_sample(st, sp, logits, history, hist_stride, n_hist, batch, temperature, uniforms, tokens_out, logprobs_out, no_speech_out);
+  });
+}
+
+// test entry: the group sampler of ohw_sample_pass_n once on caller-supplied rows (include/ohw.h)
+int ohw_dbg_sample_group(ohw_state* st, const ohw_sample_params* sp, const float* logits, const int32_t* history, int hist_stride,
+                         const int32_t* n_hist, int n_windows, int group, int first, float temperature, const double* uniforms,
+                         int32_t* done, int32_t* tokens_out, float* logprobs_out, float* no_speech_out, int32_t* win_done_out,
+                         int32_t* n_cur_out) {
+  return guard([&] {
+    if (!st || !sp || !logits || !n_hist || !uniforms || !done || !tokens_out || !win_done_out) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (!(temperature > 0.0f)) throw Error(OHW_E_INVALID_ARG, "dbg_sample_group: temperature must be > 0");
+    if (group < 1 || group > 5 || n_windows < 1) throw Error(OHW_E_INVALID_ARG, "dbg_sample_group: 1..5 candidates per window, at least one window");
+    const int W = n_windows, R = W * group;
+    if (R > st->max_batch) throw Error(OHW_E_INVALID_ARG, "dbg_sample_group: rows exceed the state's max_batch");
+    const ohw_ctx* c = st->ctx;
+    const int V = c->hp.n_vocab, MT = st->max_tokens, MB = st->max_batch;
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = st->stream;
+    std::vector<int32_t> hist((size_t)R * MT, 0), ncur((size_t)R), wdone((size_t)W), rdone((size_t)R);
+    std::vector<unsigned> wcnt((size_t)W, 0u);
+    std::vector<double> u((size_t)R * MT, 0.0);
+    for (int r = 0; r < R; ++r) {
+      if (n_hist[r] < 0 || n_hist[r] >= MT || n_hist[r] > hist_stride || (n_hist[r] > 0 && !history)) throw Error(OHW_E_INVALID_ARG, "dbg_sample_group: bad history length");
+      ncur[(size_t)r] = n_hist[r];
+      for (int i = 0; i < n_hist[r]; ++i) hist[(size_t)r * MT + i] = history[(size_t)r * hist_stride + i];
+      u[(size_t)r * MT + n_hist[r]] = uniforms[r];
+      rdone[(size_t)r] = done[r] ? 1 : 0;
+      wcnt[(size_t)(r / group)] += (unsigned)rdone[(size_t)r];
+    }
+    for (int w = 0; w < W; ++w) wdone[(size_t)w] = wcnt[(size_t)w] == (unsigned)group ? 1 : 0;
+    if (!st->sn_slot.p) { st->sn_slot.alloc((size_t)MB * c->hp.n_text_ctx * 4, true); st->sn_win.alloc((size_t)MB * 4 * 4, true); }
+    int32_t* d_wdone = st->sn_win.as<int32_t>() + 2 * MB;
+    unsigned* d_wcnt = (unsigned*)(st->sn_win.as<int32_t>() + 3 * MB);
+    HIP_CHECK(hipMemcpy2DAsync(st->logits.p, (size_t)st->logits_ld * 4, logits, (size_t)V * 4, (size_t)V * 4, (size_t)(first ? W : R), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->tokens.p, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->n_cur.p, ncur.data(), ncur.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->done.p, rdone.data(), rdone.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_wdone, wdone.data(), wdone.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_wcnt, wcnt.data(), wcnt.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
+    for (DevBuf* b : {&st->n_past, &st->sum_lp, &st->next_tok, &st->nosp_prob}) HIP_CHECK(hipMemsetAsync(b->p, 0, (size_t)R * 4, s));
+    HIP_CHECK(hipMemsetAsync(st->tok_lp.p, 0, (size_t)R * (MT + 1) * 4, s));
+    SamplerParams spar;
+    fill_sampler(st, sp, R, &spar);
+    spar.advance = first ? 0 : 1;
+    HIP_CHECK(hipMemcpyAsync(st->samp_temp.p, &temperature, 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->samp_u.p, u.data(), u.size() * 8, hipMemcpyHostToDevice, s));
+    launch_sampler_group(spar, SampGroup{group, d_wdone, d_wcnt}, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);
+    std::vector<float> lps((size_t)R * (MT + 1));
+    HIP_CHECK(hipMemcpyAsync(tokens_out, st->next_tok.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(lps.data(), st->tok_lp.p, lps.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(done, st->done.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(win_done_out, d_wdone, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    if (n_cur_out) HIP_CHECK(hipMemcpyAsync(n_cur_out, st->n_cur.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    if (no_speech_out) HIP_CHECK(hipMemcpyAsync(no_speech_out, st->nosp_prob.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (logprobs_out)
+      for (int r = 0; r < R; ++r) logprobs_out[r] = lps[(size_t)r * (MT + 1) + n_hist[r]];
   });
 }
 
@@ -2546,10 +2772,20 @@ int ohw_state_profile_end(ohw_state* st, int64_t* launches, double* total_ms, do
 int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int64_t out_elems) {
   return guard([&] {
     if (!st || !what || !out) throw Error(OHW_E_INVALID_ARG, "null argument");
-    if (batch < 1 || batch > st->enc_batch) throw Error(OHW_E_INVALID_ARG, "fetch: batch exceeds the last encode");
     const ohw_hparams& hp = st->ctx->hp;
     HIP_CHECK(hipSetDevice(st->ctx->device));
     hipStream_t s = st->stream;
+    if (std::string(what) == "sample_slots") {      // rows, not windows: n_windows * best_of of the last ohw_sample_pass_n
+      if (st->sn_rows < 1 || batch != st->sn_rows) throw Error(OHW_E_INVALID_ARG, "fetch: sample_slots holds the " + std::to_string(st->sn_rows) + " rows of the last ohw_sample_pass_n");
+      const int64_t n = (int64_t)batch * hp.n_text_ctx;
+      if (out_elems < n) throw Error(OHW_E_INVALID_ARG, "fetch: output buffer too small");
+      std::vector<int32_t> tab((size_t)n);
+      HIP_CHECK(hipMemcpyAsync(tab.data(), st->sn_slot.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      for (int64_t i = 0; i < n; ++i) out[i] = (float)tab[(size_t)i];
+      return;
+    }
+    if (batch < 1 || batch > st->enc_batch) throw Error(OHW_E_INVALID_ARG, "fetch: batch exceeds the last encode");
     const int64_t d = hp.n_audio_state, Tn = st->enc_ctx;   // rows per window of the last encode
     const std::string w = what;
     DevBuf tmp;

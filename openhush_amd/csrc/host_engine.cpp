@@ -832,7 +832,35 @@ int ohw_engine_set_force_len(ohw_engine* e, int n_tokens) {
     g_last_error = "set_force_len: a beam size is set, and beam search refuses force_len";
     return OHW_E_INVALID_ARG;
   }
+  if (n_tokens > 0 && e->best_of > 1) {
+    g_last_error = "set_force_len: best_of is set, and best-of sampling refuses force_len";
+    return OHW_E_INVALID_ARG;
+  }
   e->force_len = n_tokens;
+  return OHW_OK;
+}
+
+int ohw_engine_set_best_of(ohw_engine* e, int n) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (n < 1 || n > 5) throw Error(OHW_E_INVALID_ARG, "set_best_of: 1 (off) .. 5, got " + std::to_string(n));
+    if (n > e->max_batch) throw Error(OHW_E_INVALID_ARG, "set_best_of: " + std::to_string(n) + " candidates need max_batch >= " + std::to_string(n) + ", the engine has " + std::to_string(e->max_batch));
+    if (n > 1 && e->force_len > 0) throw Error(OHW_E_INVALID_ARG, "set_best_of: force_len is set, and best-of sampling refuses it");
+    e->best_of = n;
+  });
+}
+
+int ohw_engine_last_candidates(ohw_engine* e, const int32_t** data, int* n) {
+  if (!e || !data || !n) return OHW_E_INVALID_ARG;
+  *data = e->last_cands.data();
+  *n = (int)e->last_cands.size();
+  return OHW_OK;
+}
+
+int ohw_engine_last_candidate_logprobs(ohw_engine* e, const float** data, int* n) {
+  if (!e || !data || !n) return OHW_E_INVALID_ARG;
+  *data = e->last_cand_lps.data();
+  *n = (int)e->last_cand_lps.size();
   return OHW_OK;
 }
 

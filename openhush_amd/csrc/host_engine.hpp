@@ -56,6 +56,9 @@ struct ohw_engine {
   int prefill_chunk = 8;                 // ohw_engine_set_prefill_chunk: every state of the engine, those made later too
   int beam_size = 0;                     // ohw_engine_set_beam_size: 0 = greedy at T = 0, 2..5 = beam search (a decode batch then holds
                                          //   max_batch / beam_size windows, on the engine's own state)
+  int best_of = 1;                       // ohw_engine_set_best_of: candidates per pending window on every rung above T = 0 (1: today's ladder)
+  std::vector<int32_t> last_cands;       // ohw_engine_last_candidates: every best-of rung of the last transcribe
+  std::vector<float> last_cand_lps;      //   and the candidates' log-probabilities, in the same order
   int force_len = 0;                     // measurement knob (ohw_engine_set_force_len): every window decodes exactly this many tokens
   // the last ohw_engine_transcribe: its records (words / segments index last_text once the call has trimmed) and the trimmed text
   ohw::Transcript last;

@@ -246,6 +246,27 @@ void launch_sampler(const SamplerParams& p, hipStream_t s);
 // the same filter at a temperature, then one draw (the fallback ladder on the device): temperature [1] and
 // uniforms [batch][p.max_tokens] (the canonical double of step n_cur of row b) are read from device memory
 void launch_sampler_t(const SamplerParams& p, const float* temperature, const double* uniforms, hipStream_t s);
+// the group form (best-of sampling: ohw_sample_pass_n): p.batch rows are `group` candidates per window, row r = candidate
+// r % group of window r / group, each with its own history, draws, done flag and every other per-row entry of p.  A row's
+// arithmetic is launch_sampler_t's (one kernel body, sampler_t_row).  p.advance == 0 is the step behind the prompt: row r reads
+// the WINDOW's logits row r / group.  The row that finishes last in a window (a ticket on win_cnt, agent scope) sets win_done
+struct SampGroup {
+  int32_t group;          // candidates per window, 1..5
+  int32_t* win_done;      // [windows]: what run_decoder_step and the cross-attention get
+  unsigned* win_cnt;      // [windows]: finished rows; the caller zeroes it per pass (`group` for a window that starts done)
+};
+void launch_sampler_group(const SamplerParams& p, const SampGroup& g, const float* temperature, const double* uniforms, hipStream_t s);
+// the layout of a group pass, built where it lives: for row r = w * group + j (one workgroup per row)
+//   kv_slot[r][i] = i < shared[w] ? w * prefix_stride : r  for i < n_ctx;  n_past[r] = shared[w];
+//   done[r] = !active[w];  and by the rows with j == 0:  win_done[w] = !active[w], win_cnt[w] = active[w] ? 0 : group
+struct SampGroupInit {
+  int32_t rows, group, n_ctx, prefix_stride;
+  const int32_t* shared;  // [windows]: positions of the window's shared past (context + prompt)
+  const int32_t* active;  // [windows]
+  int32_t *kv_slot, *n_past, *done, *win_done;
+  unsigned* win_cnt;
+};
+void launch_sample_group_init(const SampGroupInit& q, hipStream_t s);
 
 // ---- per-window language (decode.hip; ohw_state_set_window_lang) -------------------------------------------------------
 constexpr int32_t LANG_PENDING = -1;   // table entry that waits for a detection (OHW_LANG_DETECT)

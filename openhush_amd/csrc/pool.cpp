@@ -305,6 +305,14 @@ int ohw_pool_set_beam_size(ohw_pool* p, int k) {
   }
   return OHW_OK;
 }
+int ohw_pool_set_best_of(ohw_pool* p, int n) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_best_of(e, n);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {

@@ -22,7 +22,12 @@ namespace {
 void check(int rc) { if (rc != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: " + g_last_error); }   // reference :266-268
 
 // per-decode scratch: one per lane when several batches decode side by side
+// one best-of rung of one window (ohw_engine_last_candidates): {window, T * 1000, N, kept}, then {n, tokens} per candidate; the
+// candidates' log-probabilities beside it
+struct CandRec { int32_t window; std::vector<int32_t> rec; std::vector<float> lps; };
+
 struct Scratch {
+  std::vector<CandRec> cands;
   std::vector<int32_t> toks, ntok, eot, trace;
   std::vector<float> lps, nsp, logits;
   std::vector<WindowRun> runs;
@@ -34,9 +39,11 @@ struct Scratch {
   }
 };
 
-struct Rngs {   // whisper.cpp seeds every decoder's generator with 0 once per whisper_full call
+// whisper.cpp seeds decoder j's generator with j once per whisper_full call.  nr decoders' sets of N (best-of sampling: candidate
+// j of entry i is v[i * N + j]); N = 1 is the one generator seeded with 0
+struct Rngs {
   std::vector<ohw_rng*> v;
-  explicit Rngs(size_t nr) { for (size_t i = 0; i < nr; ++i) v.push_back(ohw_rng_new(0)); }
+  explicit Rngs(size_t nr, int N = 1) { for (size_t i = 0; i < nr * (size_t)N; ++i) v.push_back(ohw_rng_new((uint32_t)(i % (size_t)N))); }
   ~Rngs() { for (ohw_rng* r : v) ohw_rng_free(r); }
 };
 
@@ -54,7 +61,7 @@ struct Batch {
   int64_t w0 = 0;                                          // window index of entry 0 in the trace
   const int32_t* langs = nullptr;                          // language ids read back from the state's table (null: the call's for all)
   const std::vector<int32_t>* const* ctx = nullptr;        // carried context per entry (null: the initial prompt for all)
-  ohw_rng* const* rngs = nullptr;                          // the ladder's generator per entry
+  ohw_rng* const* rngs = nullptr;                          // the ladder's generators: best_of per entry, candidate j of entry b at [b * best_of + j]
 };
 
 // The window decoder of one transcribe call: constant for the call, so lane threads share it, each with its own Scratch and Batch
@@ -68,7 +75,9 @@ struct TranscribeCall {
   std::vector<float> temps;            // the ladder's temperatures after T = 0
   // ohw_engine_set_beam_size: the T = 0 pass is a beam search of K rows per window, so a decode batch holds max_batch / K
   // windows (WB); beam calls run one batch after the other on the engine's own state
-  int beam_K = 0, WB = 1;
+  // ohw_engine_set_best_of: every rung above T = 0 samples best_N rows per pending window on the device (rung_best_of), so a
+  // batch holds max_batch / max(best_N, beam_K, 1) windows, and the call runs like a beam call
+  int beam_K = 0, WB = 1, best_N = 1;
   int32_t prompt[8];                   // the task prompt: sot [, language, task] [, no_timestamps]
   int n_prompt = 0;
   const bool carrying;
@@ -98,8 +107,11 @@ struct TranscribeCall {
     n_max = sp.n_max;
     temps = ladder(pol);
     beam_K = e->beam_size;
-    WB = beam_K > 0 ? e->max_batch / beam_K : e->max_batch;
-    if (WB < 1) throw Error(OHW_E_INVALID_ARG, "transcribe: beam size exceeds max_batch");
+    best_N = temps.empty() ? 1 : e->best_of;       // no rung above T = 0: nothing of best-of applies, batch size included
+    WB = ohw_batch_windows_host(e->max_batch, beam_K, best_N);
+    if (WB < 1) throw Error(OHW_E_INVALID_ARG, "transcribe: beam size or best_of exceeds max_batch");
+    e->last_cands.clear();
+    e->last_cand_lps.clear();
     prompt[n_prompt++] = tk.sot;
     if (V >= 51865) { prompt[n_prompt++] = tk.sot + 1 + sp.lang_id; prompt[n_prompt++] = sp.translate ? tk.translate : tk.transcribe; }
     if (sp.no_timestamps) prompt[n_prompt++] = tk.no_timestamps;
@@ -150,17 +162,20 @@ struct TranscribeCall {
   // row b of a greedy, beam or sample result as a WindowRun: tokens (end-of-text last when it ended the row), log-probabilities,
   // no-speech probability, and the row's evaluation.  cut: the row was not decoded under whisper.cpp's loop exits (beam search is
   // not causal, the device sampler runs to the end), so it is cut at the first exit and judged again; a greedy row stays whole
-  void unpack(const Scratch& sc, const Batch& bt, int b, bool cut, WindowRun& r) const {
+  // row: the result row of entry b when it is not b itself (best-of sampling: one of the entry's candidates)
+  void unpack(const Scratch& sc, const Batch& bt, int b, bool cut, WindowRun& r, int row = -1) const {
+    const int eb = b;
+    if (row >= 0) b = row;
     const int nt = sc.ntok[(size_t)b] + (sc.eot[(size_t)b] ? 1 : 0);
     r.tok.assign(&sc.toks[(size_t)b * max_tok], &sc.toks[(size_t)b * max_tok] + sc.ntok[(size_t)b]);
     if (sc.eot[(size_t)b]) r.tok.push_back(tk.eot);
     r.plog.assign(&sc.lps[(size_t)b * (max_tok + 1)], &sc.lps[(size_t)b * (max_tok + 1)] + nt);
     r.nosp = sc.nsp[(size_t)b];
-    r.ev = evaluate(r, bt, b);
+    r.ev = evaluate(r, bt, eb);
     if (!cut) return;
     r.tok.resize((size_t)r.ev.n_sampled);
     r.plog.resize((size_t)r.ev.n_sampled);
-    r.ev = evaluate(r, bt, b);
+    r.ev = evaluate(r, bt, eb);
   }
   // T = 0: the device-resident greedy loop for B windows, or under ohw_engine_set_beam_size ohw_beam_search_ex in its place; then
   // whisper.cpp's bookkeeping per window.  A beam winner (with end-of-text when it came from the finished pool) has whisper.cpp's
@@ -204,6 +219,41 @@ struct TranscribeCall {
       if (!active[(size_t)b]) continue;
       unpack(sc, bt, b, true, pass[(size_t)b]);
       if (ohw_rng_discard_draws(bt.rngs[b], pass[(size_t)b].ev.n_sampled) != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: generator");
+    }
+  }
+  // one rung of best-of sampling (ohw_engine_set_best_of): best_N candidates per pending window in ONE
+  // ohw_sample_pass_n - candidate j draws from the entry's generator j, is cut and judged like rung_device's one row, and moves
+  // its own generator on by the draws its cut pass used; ohw_best_of_pick_host keeps one, which is the rung's pass from here on
+  void rung_best_of(Scratch& sc, const Batch& bt, const std::vector<int32_t>& active, float T, std::vector<WindowRun>& pass) const {
+    const int N = best_N, R = bt.B * N;
+    Scratch cs(R, max_tok);
+    std::vector<double> u((size_t)R * max_tok, 0.0);
+    const int n_draw = std::min(n_max, max_tok);
+    for (int r = 0; r < R; ++r)
+      if (active[(size_t)(r / N)] && ohw_rng_uniforms(bt.rngs[r], n_draw, &u[(size_t)r * max_tok]) != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: generator");
+    ohw_greedy_result gr = cs.greedy_result();
+    check(ohw_sample_pass_n(bt.st, &sp, bt.B, N, max_tok, T, active.data(), u.data(), &gr));
+    for (int b = 0; b < bt.B; ++b) {
+      if (!active[(size_t)b]) continue;
+      std::vector<WindowRun> c((size_t)N);
+      ohw_seq_eval ev[5];
+      for (int j = 0; j < N; ++j) {
+        unpack(cs, bt, b, true, c[(size_t)j], b * N + j);
+        if (ohw_rng_discard_draws(bt.rngs[b * N + j], c[(size_t)j].ev.n_sampled) != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: generator");
+        ev[j] = seq_eval_c(c[(size_t)j].ev);
+      }
+      int kept = 0;
+      if (ohw_best_of_pick_host(ev, N, &pol, &kept) != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: best-of pick");
+      CandRec cr;
+      cr.window = (int32_t)(bt.w0 + b);
+      cr.rec = {cr.window, (int32_t)std::lround(T * 1000.f), N, kept};
+      for (const WindowRun& r : c) {
+        cr.rec.push_back((int32_t)r.tok.size());
+        cr.rec.insert(cr.rec.end(), r.tok.begin(), r.tok.end());
+        cr.lps.insert(cr.lps.end(), r.plog.begin(), r.plog.end());
+      }
+      sc.cands.push_back(std::move(cr));
+      pass[(size_t)b] = std::move(c[(size_t)kept]);
     }
   }
   // one rung sampled on the host: the device runs the decoder steps of the pending windows only and their logits cross PCIe
@@ -258,7 +308,8 @@ struct TranscribeCall {
       std::vector<WindowRun> pass((size_t)bt.B);
       // passes with T < 0.5 decode behind the context; from the first pass with T >= 0.5 on the table is gone
       if (T >= 0.5f && (carrying || !e->prompt.empty())) check(ohw_state_set_window_prompt(bt.st, nullptr, 0, nullptr, 0));
-      if (e->fallback_device) rung_device(sc, bt, active, T, pass);
+      if (best_N > 1) rung_best_of(sc, bt, active, T, pass);
+      else if (e->fallback_device) rung_device(sc, bt, active, T, pass);
       else rung_host(sc, bt, active, T, pass);
       for (int b = 0; b < bt.B; ++b) {
         if (!active[(size_t)b]) continue;
@@ -309,7 +360,7 @@ struct TranscribeCall {
     bool any = false;
     for (int b = 0; b < B; ++b) any = any || sc.runs[(size_t)b].pending;
     if (any) {
-      Rngs lr((size_t)B);
+      Rngs lr((size_t)B, best_N);
       bt.rngs = lr.v.data();
       run_ladder(sc, bt);
     }
@@ -379,6 +430,13 @@ struct TranscribeCall {
     std::stable_sort(recs.begin(), recs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
     for (const auto& r : recs) e->last_trace.insert(e->last_trace.end(), sc.trace.begin() + (long)r.second, sc.trace.begin() + (long)(r.second + 3 + (size_t)sc.trace[r.second + 2]));
     sc.trace.clear();
+    // the best-of rungs alike: window by window, a window's rungs in the order they ran
+    std::stable_sort(sc.cands.begin(), sc.cands.end(), [](const CandRec& a, const CandRec& b) { return a.window < b.window; });
+    for (const CandRec& c : sc.cands) {
+      e->last_cands.insert(e->last_cands.end(), c.rec.begin(), c.rec.end());
+      e->last_cand_lps.insert(e->last_cand_lps.end(), c.lps.begin(), c.lps.end());
+    }
+    sc.cands.clear();
   }
 };
 
@@ -408,7 +466,7 @@ bool apply_window_langs(ohw_state* st, std::vector<int32_t>& langs, bool always_
 // for the whole call ----
 void transcribe_seek(const TranscribeCall& tc, const float* samples, int64_t n) {
   ohw_engine* e = tc.e;
-  Rngs rngs(1);
+  Rngs rngs(1, tc.best_N);
   Scratch sc(1, tc.max_tok);
   Carry carry;
   if (tc.carrying) tc.carry_init(carry);
@@ -705,7 +763,7 @@ void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n,
   for (int64_t k = 0; k < cuts.n_win; ++k) check_window_fits(call_ctx, cuts.rec_win(k), cuts.win_samples(k));
   if (cuts.rec_mel) check(ohw_recording_set(e->state, samples, n, 0, nullptr));
   int schedule = cuts.n_batches > 1 ? e->schedule : OHW_SCHEDULE_SEQUENTIAL;
-  if (tc.beam_K > 0) schedule = OHW_SCHEDULE_SEQUENTIAL;      // no lanes for beams: the serial path on the engine's own state
+  if (tc.beam_K > 0 || tc.best_N > 1) schedule = OHW_SCHEDULE_SEQUENTIAL;      // no lanes for beams or best-of: the serial path on the engine's own state
   if (schedule == OHW_SCHEDULE_LANES && e->lanes < 2) schedule = OHW_SCHEDULE_SEQUENTIAL;
   if (schedule == OHW_SCHEDULE_PIPELINE && e->enc_cus <= 0) schedule = OHW_SCHEDULE_SEQUENTIAL;
   schedule = ensure_schedule_resources(e, schedule, cuts.n_batches);
@@ -774,6 +832,7 @@ void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_re
     }
     tc.decode_windows(sc, e->state, (int64_t)bi * MB, B, ns.data(), per_rec ? batch_lang.data() : nullptr);
     sc.trace.clear();
+    sc.cands.clear();
     for (int b = 0; b < B; ++b) {
       ohw_engine::BatchRecord& r = e->batch_records[(size_t)ord[b]];
       tc.emit(sc.runs[(size_t)b], 0.0, (double)recs[ord[b]].n / 16000.0, r.t, e->prompt);
@@ -806,13 +865,14 @@ void engine_transcribe_long_batch(ohw_engine* e, const ohw_audio_span* recs, int
   // a recording's language: the caller's id, or OHW_LANG_DETECT until its first window has been detected (with no table: -1)
   std::vector<int32_t> rec_lang((size_t)n_recs, -1), batch_lang;
   if (per_rec) for (int i = 0; i < n_recs; ++i) rec_lang[(size_t)i] = rec_langs ? rec_langs[i] : OHW_LANG_DETECT;
-  Rngs rngs((size_t)n_recs);
+  const int N = tc.best_N;
+  Rngs rngs((size_t)n_recs, N);
   std::vector<Carry> carry((size_t)(tc.carrying ? n_recs : 0));
   for (Carry& c : carry) tc.carry_init(c);
   Scratch sc(MB, tc.max_tok);
   std::vector<int32_t> r_rec((size_t)MB), r_slot((size_t)MB), r_seek((size_t)MB), r_fresh((size_t)MB);
   std::vector<int> seeks((size_t)MB), ends((size_t)MB), frames((size_t)MB);
-  std::vector<ohw_rng*> round_rngs((size_t)MB);
+  std::vector<ohw_rng*> round_rngs((size_t)MB * (size_t)N);
   std::vector<const std::vector<int32_t>*> round_ctx((size_t)MB, nullptr);
   for (;;) {
     const int B = ohw_seek_sched_round(sched, r_rec.data(), r_slot.data(), r_seek.data(), r_fresh.data());
@@ -824,7 +884,7 @@ void engine_transcribe_long_batch(ohw_engine* e, const ohw_audio_span* recs, int
       seeks[(size_t)b] = r_seek[(size_t)b];
       ends[(size_t)b] = mel_frames(recs[i].n);
       frames[(size_t)b] = std::min(CHUNK_FRAMES, ends[(size_t)b] - seeks[(size_t)b]);
-      round_rngs[(size_t)b] = rngs.v[(size_t)i];
+      for (int j = 0; j < N; ++j) round_rngs[(size_t)(b * N + j)] = rngs.v[(size_t)(i * N + j)];
       if (tc.carrying) round_ctx[(size_t)b] = &carry[(size_t)i].next;
     }
     check(ohw_mel_seek_slots(e->state, r_slot.data(), r_seek.data(), B, nullptr));
@@ -841,6 +901,7 @@ void engine_transcribe_long_batch(ohw_engine* e, const ohw_audio_span* recs, int
     tc.run_ladder(sc, bt);
     tc.align_runs(sc, e->state, B, frames.data());
     sc.trace.clear();
+    sc.cands.clear();
     for (int b = 0; b < B; ++b) {
       const int i = r_rec[(size_t)b];
       const WindowRun& r = sc.runs[(size_t)b];

@@ -86,4 +86,23 @@ int ohw_needs_fallback_host(const ohw_seq_eval* ev, const ohw_decode_policy* q, 
   return ohw::needs_fallback(r, *q, no_speech_prob, is_last != 0) ? 1 : 0;
 }
 
+int ohw_batch_windows_host(int max_batch, int beam_size, int best_of) {
+  if (max_batch < 1 || (beam_size != 0 && (beam_size < 2 || beam_size > 5)) || best_of < 1 || best_of > 5) return OHW_E_INVALID_ARG;
+  const int wb = max_batch / std::max(std::max(best_of, beam_size), 1);
+  return wb < 1 ? OHW_E_INVALID_ARG : wb;
+}
+
+// best-of sampling: which of a rung's n judged candidates is kept (include/ohw.h).  The engine's rung calls
+// this function itself
+int ohw_best_of_pick_host(const ohw_seq_eval* ev, int n, const ohw_decode_policy* q, int* kept) {
+  if (!ev || !q || !kept || n < 1 || n > 5) return OHW_E_INVALID_ARG;
+  int best = -1;
+  for (int j = 0; j < n; ++j) {
+    if (ev[j].failed != 0 || ev[j].entropy < q->entropy_thold) continue;          // out
+    if (best < 0 || ev[j].avg_logprob > ev[best].avg_logprob) best = j;           // strictly better only: the lowest j among equals
+  }
+  *kept = best < 0 ? 0 : best;
+  return OHW_OK;
+}
+
 }  // extern "C"

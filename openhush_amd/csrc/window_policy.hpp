@@ -50,6 +50,11 @@ bool is_no_speech(const WindowRun& r, const ohw_decode_policy& q);
 // tokens of the window that reach the text: none of a no-speech window
 inline int kept_tokens(const WindowRun& r, const ohw_decode_policy& q) { return is_no_speech(r, q) ? 0 : r.ev.n_keep; }
 
+// a SeqEval as the C ABI carries it (ohw_seq_eval_host, ohw_best_of_pick_host)
+inline ohw_seq_eval seq_eval_c(const SeqEval& r) {
+  return ohw_seq_eval{r.n_sampled, r.result_len, r.n_keep, r.seek_delta, r.failed ? 1 : 0, r.completed ? 1 : 0, r.avg_logprob, r.entropy};
+}
+
 // the temperatures after T = 0: temperature_inc, 2 * temperature_inc, ... up to 1.0
 std::vector<float> ladder(const ohw_decode_policy& q);
 

@@ -284,6 +284,8 @@ EXPORTS = [
     "ohw_state_set_prefill_chunk", "ohw_state_prefill_chunk", "ohw_engine_set_prefill_chunk", "ohw_dbg_cross_attn_chunk_n",
     "ohw_engine_set_carry_context", "ohw_pool_set_carry_context", "ohw_engine_last_context", "ohw_engine_long_batch_context", "ohw_carry_step_host",
     "ohw_seq_eval_host", "ohw_needs_fallback_host",
+    "ohw_sample_pass_n", "ohw_dbg_sample_group", "ohw_best_of_pick_host", "ohw_engine_set_best_of", "ohw_pool_set_best_of",
+    "ohw_engine_last_candidates", "ohw_engine_last_candidate_logprobs", "ohw_batch_windows_host",
     "ohw_dbg_enc_gemm",
 ]
 
@@ -592,6 +594,15 @@ def lib():
         L.ohw_segments_host.argtypes = [ip, C.c_int, C.POINTER(SpecialTokens), C.c_float, C.c_float, C.POINTER(TokenSpan), C.c_int]
         L.ohw_seq_eval_host.argtypes = [C.POINTER(SpecialTokens), ip, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SeqEval)]
         L.ohw_needs_fallback_host.argtypes = [C.POINTER(SeqEval), C.POINTER(DecodePolicy), C.c_float, C.c_int]
+        L.ohw_best_of_pick_host.argtypes = [C.POINTER(SeqEval), C.c_int, C.POINTER(DecodePolicy), ip]
+        L.ohw_sample_pass_n.argtypes = [vp, C.POINTER(SampleParams), C.c_int, C.c_int, C.c_int, C.c_float, ip, C.POINTER(C.c_double), C.POINTER(GreedyResult)]
+        L.ohw_dbg_sample_group.argtypes = [vp, C.POINTER(SampleParams), fp, ip, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.POINTER(C.c_double), ip, ip, fp, fp, ip, ip]
+        L.ohw_batch_windows_host.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.ohw_engine_set_best_of.argtypes = [vp, C.c_int]
+        L.ohw_pool_set_best_of.argtypes = [vp, C.c_int]
+        L.ohw_engine_last_candidates.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_int)]
+        L.ohw_engine_last_candidate_logprobs.argtypes = [vp, C.POINTER(fp), C.POINTER(C.c_int)]
         L.ohw_dequantize_host.argtypes = [C.c_int, vp, C.c_int64, fp]
         L.ohw_dbg_dequantize.argtypes = [C.c_int, C.c_int, vp, C.c_int64, fp]
         _lib = L
@@ -728,6 +739,22 @@ def seq_eval_host(tok: "SpecialTokens", tokens: Sequence[int], plogs: Sequence[f
     _check(lib().ohw_seq_eval_host(C.byref(tok), _ip(t), _fp(lp), len(tokens), int(seek), int(seek_end), int(n_max), int(bool(no_timestamps)),
                                    int(window_mode), C.byref(ev)))
     return ev
+
+
+def batch_windows_host(max_batch: int, beam_size: int = 0, best_of: int = 1) -> int:
+    """ohw_batch_windows_host (host only): windows per decode batch, max_batch // max(best_of, beam_size, 1)"""
+    n = int(lib().ohw_batch_windows_host(int(max_batch), int(beam_size), int(best_of)))
+    if n < 1:
+        raise WhisperError(OHW_E_INVALID_ARG, f"batch_windows_host: no batch for max_batch {max_batch}, beam size {beam_size}, best_of {best_of}")
+    return n
+
+
+def best_of_pick_host(evs: Sequence[SeqEval], policy: DecodePolicy) -> int:
+    """ohw_best_of_pick_host (host only): which of a best-of rung's judged candidates the engine keeps"""
+    arr = (SeqEval * len(evs))(*evs)
+    kept = np.zeros(1, dtype=np.int32)
+    _check(lib().ohw_best_of_pick_host(arr, len(evs), C.byref(policy), _ip(kept)))
+    return int(kept[0])
 
 
 def needs_fallback_host(ev: SeqEval, policy: DecodePolicy, no_speech_prob: float, is_last: bool) -> bool:
@@ -1500,6 +1527,58 @@ class State:
         return [{"tokens": [int(x) for x in toks[b, :nt[b]]], "logprobs": lps[b, :nt[b] + (1 if eot[b] else 0)].copy(),
                  "ended_by_eot": bool(eot[b]), "no_speech_prob": float(nsp[b]), "sum_logprob": float(slp[b])} for b in range(batch)]
 
+    def sample_pass_n(self, n_windows: int, best_of: int, temperature: float, active: Sequence[int], uniforms: np.ndarray,
+                      p: Optional[SampleParams] = None):
+        """ohw_sample_pass_n: one temperature pass with best_of candidates per window; uniforms [n_windows][best_of][n_text_ctx]
+        -> sample_pass's dicts, row w * best_of + j = candidate j of window w (zeros for the rows of inactive windows)"""
+        p = p or self.ctx.default_params()
+        cap = self.ctx.hp.n_text_ctx
+        R = n_windows * best_of
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        assert u.shape == (n_windows, best_of, cap)
+        act = np.ascontiguousarray(active, dtype=np.int32)
+        assert act.shape == (n_windows,)
+        toks = np.zeros((R, cap), dtype=np.int32)
+        nt = np.zeros(R, dtype=np.int32)
+        slp = np.zeros(R, dtype=np.float32)
+        lps = np.zeros((R, cap + 1), dtype=np.float32)
+        eot = np.zeros(R, dtype=np.int32)
+        nsp = np.zeros(R, dtype=np.float32)
+        r = GreedyResult(_ip(toks), _ip(nt), _fp(slp), _fp(lps), _ip(eot), _fp(nsp))
+        _check(lib().ohw_sample_pass_n(self.h, C.byref(p), n_windows, best_of, cap, temperature, _ip(act),
+                                       u.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))
+        return [{"tokens": [int(x) for x in toks[b, :nt[b]]], "logprobs": lps[b, :nt[b] + (1 if eot[b] else 0)].copy(),
+                 "ended_by_eot": bool(eot[b]), "no_speech_prob": float(nsp[b]), "sum_logprob": float(slp[b])} for b in range(R)]
+
+    def dbg_sample_group(self, p: SampleParams, logits: np.ndarray, histories: Sequence[Sequence[int]], group: int, first: bool,
+                         temperature: float, uniforms: Sequence[float], done: Sequence[int]) -> dict:
+        """ohw_dbg_sample_group: the group sampler of sample_pass_n once on host data.  histories / uniforms / done per row
+        (rows = windows * group); logits [windows][V] when first, else [rows][V] -> tokens, logprobs, no_speech_prob, done,
+        n_cur [rows] and win_done [windows]"""
+        R = len(histories)
+        assert R % group == 0
+        W = R // group
+        lg = np.ascontiguousarray(np.atleast_2d(logits), dtype=np.float32)
+        assert lg.shape[0] == (W if first else R)
+        stride = max(1, max(len(h) for h in histories))
+        hist = np.zeros((R, stride), dtype=np.int32)
+        nh = np.zeros(R, dtype=np.int32)
+        for b, h in enumerate(histories):
+            hist[b, :len(h)] = h
+            nh[b] = len(h)
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        assert u.shape == (R,)
+        dn = np.ascontiguousarray(done, dtype=np.int32).copy()
+        assert dn.shape == (R,)
+        tok = np.zeros(R, dtype=np.int32)
+        lp = np.zeros(R, dtype=np.float32)
+        ns = np.zeros(R, dtype=np.float32)
+        wd = np.zeros(W, dtype=np.int32)
+        nc = np.zeros(R, dtype=np.int32)
+        _check(lib().ohw_dbg_sample_group(self.h, C.byref(p), _fp(lg), _ip(hist), stride, _ip(nh), W, group, int(bool(first)), temperature,
+                                          u.ctypes.data_as(C.POINTER(C.c_double)), _ip(dn), _ip(tok), _fp(lp), _fp(ns), _ip(wd), _ip(nc)))
+        return {"tokens": tok, "logprobs": lp, "no_speech_prob": ns, "done": dn, "win_done": wd, "n_cur": nc}
+
     def greedy_host_sampler(self, batch: int, p: Optional[SampleParams] = None):
         """the same loop with the HOST owning the sampler: logits cross PCIe every step"""
         p = p or self.ctx.default_params()
@@ -1563,6 +1642,11 @@ class State:
             if what == "align_p":
                 return out[:A * n_all * n_keys].reshape(A, n_all, n_keys).copy()
             return out[:(n_text + 1) * n_keys].reshape(n_text + 1, n_keys).copy()
+        if what == "sample_slots":
+            # the kv_slot table of the last sample_pass_n: batch = its n_windows * best_of rows -> i32 [batch][n_text_ctx]
+            out = np.empty((batch, hp.n_text_ctx), dtype=np.float32)
+            _check(lib().ohw_state_fetch(self.h, what.encode(), batch, _fp(out), out.size))
+            return out.astype(np.int32)
         d, T = hp.n_audio_state, hp.n_audio_ctx
         shape = {"mel": (batch, hp.n_mels, CHUNK_FRAMES), "conv1": (batch, CHUNK_FRAMES, d),
                  "mel_t": (batch, CHUNK_FRAMES + 2, 128)}.get(what, (batch, T, d))
@@ -2057,6 +2141,33 @@ class WhisperEngine:
             i += 3 + k
         return out
 
+    def set_best_of(self, n: int):
+        """ohw_engine_set_best_of: 1 (default) = one sampled sequence per rung above T = 0, 2..5 = that many candidates per pending
+        window and rung, sampled on the device, the best kept (ohw_best_of_pick_host); a decode batch then holds
+        max_batch // max(n, beam size, 1) windows"""
+        _check(lib().ohw_engine_set_best_of(self.h, int(n)))
+
+    def last_candidates(self):
+        """[(window, temperature, kept j, [(tokens, logprobs) per candidate])] for every best-of rung of the last transcribe
+        (ohw_engine_last_candidates / ohw_engine_last_candidate_logprobs); tokens are cut, end-of-text included when sampled"""
+        p, n = C.POINTER(C.c_int32)(), C.c_int(0)
+        q, m = C.POINTER(C.c_float)(), C.c_int(0)
+        _check(lib().ohw_engine_last_candidates(self.h, C.byref(p), C.byref(n)))
+        _check(lib().ohw_engine_last_candidate_logprobs(self.h, C.byref(q), C.byref(m)))
+        out, i, f = [], 0, 0
+        while i + 4 <= n.value:
+            w, t, N, kept = p[i], p[i + 1], p[i + 2], p[i + 3]
+            i += 4
+            cands = []
+            for _ in range(N):
+                k = p[i]
+                cands.append(([int(p[i + 1 + j]) for j in range(k)], np.array([q[f + j] for j in range(k)], dtype=np.float32)))
+                i += 1 + k
+                f += k
+            out.append((int(w), t / 1000.0, int(kept), cands))
+        assert f == m.value
+        return out
+
     def set_beam_size(self, k: int):
         """ohw_engine_set_beam_size: 0 (default) = greedy at T = 0, 2..5 = beam search with k beams per window in every
         transcribe, transcribe_batch and transcribe_long_batch; a decode batch then holds max_batch // k windows"""
@@ -2163,6 +2274,10 @@ class EnginePool:
 
     def set_force_len(self, n_tokens: int):
         _check(lib().ohw_pool_set_force_len(self.h, n_tokens))
+
+    def set_best_of(self, n: int):
+        """ohw_pool_set_best_of: WhisperEngine.set_best_of(n) on every engine of the pool"""
+        _check(lib().ohw_pool_set_best_of(self.h, int(n)))
 
     def set_beam_size(self, k: int):
         """ohw_pool_set_beam_size: WhisperEngine.set_beam_size(k) on every engine of the pool"""

@@ -11,6 +11,17 @@ the share that fell back is measured, not assumed.  Per leg: audio-s/s, mean pas
 at T > 0 (against the off leg on the same windows).  The host leg runs fewer windows (--host-windows, default 32): it is slow.
 
   python tools/ladder_probe.py [--windows 120] [--host-windows 32] [--json out.json]
+
+--best-of N measures best-of sampling instead (ohw_engine_set_best_of, ohw_sample_pass_n), same dims and dtype, unbiased audio
+(every window runs every rung):
+
+  rung        one rung at T = 0.6 for W = max_batch // N windows on one state, in the same process and alternating, every shape
+              warmed first: ohw_sample_pass_n with N candidates per window, against N ohw_sample_pass rungs (what N candidates cost
+              without the group pass) and against one ohw_sample_pass rung; median, minimum and maximum of --reps repetitions
+  transcribe  ohw_engine_transcribe of --windows windows (default 24 in this mode) under the default policy with the device
+              ladder, best_of 1 against best_of N: audio-s/s, the smaller T = 0 batch of best_of N included
+
+  python tools/ladder_probe.py --best-of 5 [--max-batch 30] [--windows 24] [--reps 5] [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -25,13 +36,89 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def best_of_probe(args):
+    from openhush_amd import engine as E, synth
+    N = args.best_of
+    hp = synth.PRESETS["large-v3"]
+    W = max(1, args.max_batch // N)
+    n_win = args.windows if args.windows != 120 else 24
+    out = {"dims": "large-v3", "dtype": "bf16", "best_of": N, "max_batch": args.max_batch, "rung_windows": W, "temperature": 0.6, "reps": args.reps}
+    ctx = E.Context.synthetic(hp.as_list(), 1234, 0, E.OHW_DTYPE_BF16)
+    st = E.State(ctx, W * N)
+    st.mel(np.stack([synth.synth_audio(1000 + w) for w in range(W)]), None, E.OHW_MEL_ZERO_TAIL, want=False)
+    st.encode(W)
+    p = ctx.default_params()
+    cap = hp.n_text_ctx
+    u = np.stack([np.stack([E.HostRng(j).uniforms(cap) for j in range(N)]) for _ in range(W)])
+    act = [1] * W
+
+    def group():
+        return st.sample_pass_n(W, N, 0.6, act, u, p)
+
+    def single(j):
+        return st.sample_pass(W, 0.6, act, np.ascontiguousarray(u[:, j, :]), p)
+
+    def timed(f):
+        t0 = time.perf_counter()
+        r = f()
+        return time.perf_counter() - t0, r
+
+    legs = {"group_n": group, "n_singles": lambda: [single(j) for j in range(N)], "one_single": lambda: single(0)}
+    steps = {}
+    for k, f in legs.items():                              # warm every shape: graph captures, first-use buffers
+        _, r = timed(f)
+        rows = r if k == "group_n" else (r[0] if k == "n_singles" else r)
+        steps[k] = float(np.mean([len(x["tokens"]) + x["ended_by_eot"] for x in rows]))
+    times = {k: [] for k in legs}
+    for _ in range(args.reps):                             # alternating
+        for k, f in legs.items():
+            times[k].append(timed(f)[0])
+    out["rung"] = {k: {"median_ms": 1e3 * float(np.median(v)), "min_ms": 1e3 * min(v), "max_ms": 1e3 * max(v), "mean_tokens_per_row": steps[k]} for k, v in times.items()}
+    out["rung"]["group_vs_n_singles"] = out["rung"]["group_n"]["median_ms"] / out["rung"]["n_singles"]["median_ms"]
+    out["rung"]["group_vs_one_single"] = out["rung"]["group_n"]["median_ms"] / out["rung"]["one_single"]["median_ms"]
+    for k in legs:
+        r = out["rung"][k]
+        print(f"[rung, {W} windows, N = {N}] {k:>10}: median {r['median_ms']:8.1f} ms  (min {r['min_ms']:.1f}, max {r['max_ms']:.1f}; {r['mean_tokens_per_row']:.0f} tokens per row)", flush=True)
+    print(f"[rung] group / N singles {out['rung']['group_vs_n_singles']:.3f}   group / one single {out['rung']['group_vs_one_single']:.3f}", flush=True)
+    st.close()
+    ctx.close()
+    # through the product path
+    pcm = np.concatenate([synth.synth_audio(1000 + w) for w in range(n_win)]).astype(np.float32)
+    out["transcribe"] = {"windows": n_win}
+    for bo in (1, N):
+        pool = E.EnginePool(None, "en", False, [0], E.OHW_DTYPE_BF16, args.max_batch, synthetic=hp.as_list(), seed=1234)
+        pool.set_fallback_on_device(True)
+        pool.set_best_of(bo)
+        audio = E.AudioBuffer(pcm, 16000)
+        pool.transcribe(E.AudioBuffer(pcm[:min(n_win, max(1, args.max_batch // bo)) * synth.CHUNK_SAMPLES], 16000))      # warm-up: one batch
+        ts = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            pool.transcribe(audio)
+            ts.append(time.perf_counter() - t0)
+        out["transcribe"][f"best_of_{bo}"] = {"wall_s": ts, "audio_s_per_s": n_win * 30.0 / min(ts)}
+        print(f"[transcribe, {n_win} windows, device ladder, all rungs] best_of {bo}: {n_win * 30.0 / min(ts):8.1f} audio-s/s  (walls {[round(t, 2) for t in ts]})", flush=True)
+        pool.close()
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=120, help="windows of the off / device legs (config #4: 120 = 1 h)")
     ap.add_argument("--host-windows", type=int, default=32, help="windows of the host leg (and of its off leg)")
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--json", default="")
+    ap.add_argument("--best-of", type=int, default=0, help="measure best-of sampling with N candidates instead (see above)")
+    ap.add_argument("--reps", type=int, default=5, help="--best-of: repetitions of every rung leg")
     args = ap.parse_args()
+    if args.best_of:
+        if not 2 <= args.best_of <= 5 or args.max_batch < args.best_of:
+            ap.error("--best-of takes 2..5 and a --max-batch of at least that")
+        return best_of_probe(args)
 
     from openhush_amd import engine as E, synth
     hp = synth.PRESETS["large-v3"]
