@@ -1090,8 +1090,10 @@ int ohw_dbg_sample_group(ohw_state* st, const ohw_sample_params* p, const float*
 /* the DEVICE language pick (ohw_state_detect_window_lang's kernel) on caller-supplied rows: logits [batch][n_vocab] (host);
  * ids_out [batch], probs_out [batch][n_langs] or NULL.  Leaves the state's language table alone.                       */
 int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* ids_out, float* probs_out);
-/* counters of a state's graph caches: "step_captures" / "beam_captures" (graphs / graph pairs captured so far; a group pass's
- * graph counts as a step capture), "step_graphs" / "beam_graphs" / "group_graphs" (entries held now; the last: ohw_sample_pass_n's), "persist_launches" (persistent decoder steps launched or captured),
+/* counters of a state's three graph caches, one cache type with capacities 8 (step: ohw_greedy*, ohw_sample_pass), 4 (group:
+ * ohw_sample_pass_n) and 4 pairs (beam: ohw_beam_search*), the oldest entry evicted: "step_captures" / "beam_captures" (entries
+ * captured so far by the step and the group cache together / by the beam cache, a pair counting once), "step_graphs" /
+ * "group_graphs" / "beam_graphs" (entries held now), "persist_launches" (persistent decoder steps launched or captured),
  * "enc_rows" (rows M of the dense encoder GEMMs of the last encode: B * E, or the sum of the lengths when it ran packed);
  * OHW_E_INVALID_ARG for another name.  A second ohw_greedy /
  * ohw_beam_search with the same batch, parameters and stream must add no capture (tests/test_gpu_beam.py).

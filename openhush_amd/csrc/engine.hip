@@ -105,6 +105,56 @@ static const char* const kDecTallyShape[DG_N_SHAPES] = {"1x1", "2x1", "1x2", "2x
 static const char* const kXattnTally[XA_N_VARIANTS] = {"plain", "split", "rows2", "rows3", "rows4", "group2", "group3", "group4", "group5", "group_split"};
 static const char* const kSelfAttnTally[4] = {"plain", "slots", "fused", "fused_slots"};
 
+// OHW_DEBUG_MARKS=1: progress lines on stderr (which HIP call a tool died under)
+#define BMARK(what, i) do { static const bool on_ = env_int("OHW_DEBUG_MARKS", 0, 0, 1) != 0; if (on_) { std::fprintf(stderr, "[ohw beam] %s %d\n", what, (int)(i)); std::fflush(stderr); } } while (0)
+
+// The replayed iterations of the device decode loops, captured as hipGraphs.  Positions, tokens and the done flags live in
+// device memory, so one capture serves every iteration of every call that agrees with it in GraphKey: what is baked into the
+// captured launches.  A state keeps three caches (ohw_state: step_graphs, group_graphs, beam_graphs).
+struct GraphKey {
+  int rows = 0;        // decoder rows (step cache) or windows (group and beam caches)
+  int group = 0;       // candidates (group cache) or beams (beam cache) per window; 0 in the step cache
+  int cus = 0;         // CU budget of the stream
+  int t_len = 0;       // audio context: a captured kernel argument
+  bool var = false, invariant = false, persist = false;     // per-window contexts, the cross-attention variant rule, the persistent step
+  bool flag = false;   // step cache: a temperature pass; beam cache: log-probability history on (other pointers baked in)
+  SamplerParams spar;  // compared byte by byte: fill_sampler zeroes the struct, padding included, before it fills it
+  bool operator==(const GraphKey& o) const {
+    return rows == o.rows && group == o.group && cus == o.cus && t_len == o.t_len && var == o.var && invariant == o.invariant &&
+           persist == o.persist && flag == o.flag && std::memcmp(&spar, &o.spar, sizeof spar) == 0;
+  }
+};
+// one entry = the graph of a key's iteration, or the PAIR of a key whose iterations alternate between two forms (beam search:
+// the token-history and kv_slot double buffers); a pair is made, looked up and evicted together
+struct GraphEntry {
+  GraphKey key;
+  hipGraph_t graph[2] = {nullptr, nullptr};
+  hipGraphExec_t exec[2] = {nullptr, nullptr};
+  void destroy() {
+    for (int q = 0; q < 2; ++q) {
+      if (exec[q]) (void)hipGraphExecDestroy(exec[q]);
+      if (graph[q]) (void)hipGraphDestroy(graph[q]);
+    }
+  }
+};
+struct GraphCache {
+  size_t capacity;
+  bool marks = false;             // OHW_DEBUG_MARKS lines around the capture calls (the beam cache)
+  int captures = 0;               // entries captured so far (ohw_dbg_counter: a second call with the same key adds none)
+  std::vector<GraphEntry> entries;     // oldest first
+  const GraphEntry* find(const GraphKey& key) const {
+    for (const auto& e : entries)
+      if (e.key == key) return &e;
+    return nullptr;
+  }
+  // the entry of `key`, captured now if the cache does not hold it: body(q, capture_stream) enqueues iteration form q
+  template <typename F> const GraphEntry& get_or_capture(ohw_state* st, const GraphKey& key, int n_graphs, F&& body);
+  void clear() {
+    for (auto& e : entries) e.destroy();
+    entries.clear();
+  }
+};
+
 struct ohw_state {
   ohw_ctx* ctx = nullptr;
   int max_batch = 0;
@@ -190,11 +240,11 @@ struct ohw_state {
   // ohw_beam_search_ex only (made on its first use): per-token log-probability histories (double buffer, pool), the device-side
   // ranking's result rows
   DevBuf bm_plog[2], bm_fin_plog, bm_out_tok, bm_out_lp, bm_out_n, bm_out_sum, bm_out_eot, bm_out_nfin, bm_nosp;
-  // one entry = the PAIR of graphs of a (windows, beam size, sampler parameters, CU budget, cross-attention variant) key: the
-  // odd and the even iteration (the token-history and kv_slot double buffers alternate); made, looked up and evicted together,
-  // so a call never holds an exec of an entry it then evicts
-  struct BeamGraph { hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr}; int windows = 0, K = 0, cus = 0, t_len = 0; bool invariant = false, persist = false, var = false, lp = false; SamplerParams spar; };
-  std::vector<BeamGraph> beam_graphs;      // lp: the pair of ohw_beam_search_ex (log-probability history on: other pointers baked in)
+  // the captured iterations (GraphCache), a handful each.  step_graphs: one greedy or temperature iteration {feed the sampled
+  // token, single-token decoder step, sampler} per (batch, ...) seen; group_graphs: best-of sampling's {decoder step with
+  // kv_group = N, group sampler}, keyed on N as well and kept apart from step_graphs; beam_graphs: the odd and the even beam
+  // iteration of a (windows, beam size, ...) key as one entry, so a call never holds an exec of an entry it then evicts
+  GraphCache step_graphs{8}, group_graphs{4}, beam_graphs{4, true};
   // the persistent small-batch decoder step (decode_persist.hip): per-layer pointer table, granule arena, epoch / abort words
   DevBuf ps_layers, ps_gran, ps_words;
   PersistParams ps_layout{};         // region offsets of the arena
@@ -203,8 +253,6 @@ struct ohw_state {
   DevBuf attn_ticket;                // u32 [n_text_head], zero between launches
   int persist_launches = 0;
   int n_cu = 0;
-  int step_captures = 0;
-  int beam_captures = 0;            // graph pairs captured so far (ohw_dbg_counter: a second call with the same key adds none)
   // which decoder kernel instantiations run_decoder_step launched (ohw_dbg_counter "dec_gemm.*", "xattn.*", "self_attn.*"):
   // counted on the host, so a captured step counts once, at its capture
   int64_t tally_gemm[DT_GEMMS][DT_FORMS][DG_N_SHAPES] = {};
@@ -221,19 +269,11 @@ struct ohw_state {
   std::vector<hipEvent_t> prof_ev;
   size_t prof_used = 0;
   double prof_work = 0.0;
-  // hipGraph of one greedy iteration {feed sampled token, single-token decoder step, sampler}
-  // captured greedy iterations, one per (batch, sampler parameters, CU budget of the stream, audio context: t_len is a
-  // captured kernel argument) seen; a handful at most
-  struct StepGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int batch = 0; int cus = 0; int t_len = 0; bool invariant = false, persist = false, temp = false, var = false; SamplerParams spar{}; };
   bool batch_invariant = false;      // cross-attention variant picked from n_new alone (state_set_batch_invariant)
-  std::vector<StepGraph> step_graphs;
   // best-of sampling (ohw_sample_pass_n; made on first use): the pass's constant kv_slot table [rows][n_text_ctx], then per window
-  // {shared length, active, done flag, finished-row count} [4][max_batch]; sn_rows: rows of the last pass's table ("sample_slots").
-  // Its replayed {decoder step with kv_group = N, group sampler} graphs are kept apart from step_graphs, keyed on N as well
+  // {shared length, active, done flag, finished-row count} [4][max_batch]; sn_rows: rows of the last pass's table ("sample_slots")
   DevBuf sn_slot, sn_win;
   int sn_rows = 0;
-  struct GroupGraph { StepGraph g; int windows = 0, group = 0; };
-  std::vector<GroupGraph> group_graphs;
   bool graphs_enabled = true;
   int graph_max_batch = 32;         // graphs for batches below this (OHW_GRAPH_MAX_BATCH)
   // word timestamps (ohw_state_set_align_heads / ohw_state_align; align.hip).  al_heads: the caller's list; the buffers are made
@@ -253,7 +293,73 @@ struct ohw_state {
   int max_tokens = 0;
 };
 
+template <typename F>
+const GraphEntry& GraphCache::get_or_capture(ohw_state* st, const GraphKey& key, int n_graphs, F&& body) {
+  if (const GraphEntry* e = find(key)) return *e;
+  // room first: the oldest entry goes before anything of this call exists (an eviction between the two captures of a pair
+  // once dropped an entry whose exec the call might already hold)
+  if (entries.size() >= capacity) {
+    entries.front().destroy();
+    entries.erase(entries.begin());
+  }
+  GraphEntry ng;
+  ng.key = key;
+  try {
+    for (int q = 0; q < n_graphs; ++q) {
+      // The iteration is captured on the state's OWN stream (non-blocking) and replayed on whatever stream the state
+      // runs on: a CU-masked stream (hipExtStreamCreateWithCUMask) is a blocking stream, and while a blocking stream
+      // captures, any use of the legacy stream by another thread - another engine loading its model, say - fails with
+      // "would make the legacy stream depend on a capturing blocking stream" and kills the capture (two engines driven
+      // by two threads: tests/test_gpu_configs.py).  The own stream is idle whenever the state runs on an external one.
+      // Capture mode RELAXED: in the other modes HIP (ROCm 7.2) rejects every synchronous memory call of EVERY thread
+      // while a capture is open - hipMemset in another engine's state allocation failed that way - and this thread
+      // makes no call during the capture that the stricter modes would have to catch.
+      hipStream_t cap = st->own_stream;
+      CaptureGate gate;   // no other thread is inside the library while this stream captures (common.hpp)
+      struct StreamSwap { ohw_state* st; hipStream_t keep; ~StreamSwap() { st->stream = keep; } } swap{st, st->stream};
+      st->stream = cap;
+      if (marks) BMARK("capture begin", q);
+      HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
+      try {
+        body(q, cap);
+      } catch (...) {
+        hipGraph_t g = nullptr;
+        (void)hipStreamEndCapture(cap, &g);
+        if (g) (void)hipGraphDestroy(g);
+        throw;
+      }
+      HIP_CHECK(hipStreamEndCapture(cap, &ng.graph[q]));
+      if (marks) BMARK("capture ended", q);
+      HIP_CHECK(hipGraphInstantiate(&ng.exec[q], ng.graph[q], nullptr, nullptr, 0));
+      if (marks) BMARK("instantiated", q);
+    }
+  } catch (...) {
+    ng.destroy();     // a partially built entry goes whole; only a complete one is kept
+    throw;
+  }
+  entries.push_back(ng);
+  ++captures;
+  return entries.back();
+}
+
 namespace {
+
+// the key of an iteration captured now: the state's settings that the captured launches bake in, and the caller's own terms
+GraphKey graph_key(const ohw_state* st, int rows, int group, bool flag, const SamplerParams& spar) {
+  GraphKey k;
+  k.rows = rows; k.group = group; k.cus = st->stream_cus; k.t_len = st->enc_ctx; k.var = st->enc_var; k.invariant = st->batch_invariant;
+  k.persist = st->persist; k.flag = flag;
+  std::memcpy(&k.spar, &spar, sizeof spar);
+  return k;
+}
+
+// while one lives (and is on), cross-attention skips the windows whose done flag is set; the earlier setting returns after it
+struct SkipDone {
+  bool& f;
+  bool keep;
+  explicit SkipDone(bool& r, bool on = true) : f(r), keep(r) { if (on) f = true; }
+  ~SkipDone() { f = keep; }
+};
 
 struct ProfScope {
   ohw_state* st;
@@ -765,7 +871,7 @@ void run_prefill(ohw_state* st, int batch, const int32_t* active, const std::str
   for (int j = 0; j < nc; ++j)
     for (int b = 0; b < batch; ++b) done[(size_t)j * MB + b] = ((active && !active[b]) || Q * j >= st->wp_len[(size_t)b]) ? 1 : 0;
   HIP_CHECK(hipMemcpyAsync(st->wp_done.p, done.data(), done.size() * 4, hipMemcpyHostToDevice, s));
-  struct SkipDone { bool& f; bool keep; explicit SkipDone(bool& r) : f(r), keep(r) { f = true; } ~SkipDone() { f = keep; } } skip_done(st->skip_done);
+  SkipDone skip_done(st->skip_done);
   Dispatch::run(st->ctx->dtype, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     for (int j = 0; j < nc; ++j) {
@@ -830,6 +936,98 @@ void fill_prompt_rows(ohw_state* st, const ohw_sample_params* sp, int windows, i
   const int n = launch_prompt_fill(st->lang_tab.as<int32_t>(), st->step_tok.as<int32_t>(), windows, c->tok.sot, c->hp.n_vocab >= 51865 ? 1 : 0,
                                    sp->translate ? c->tok.translate : c->tok.transcribe, sp->no_timestamps ? c->tok.no_timestamps : -1, st->stream);
   if (n != n_prompt) throw Error(OHW_E_TRANSCRIBE, "prompt_fill: the device prompt has another length than build_prompt's");
+}
+
+// The start of a pass of a device decode loop (decode_loop, sample_pass_group, beam_search_run): the checks the three share,
+// the prefill of the text contexts, the prompt rows in step_tok and the windows' start positions in n_past.  The caller has
+// checked its pointers and its own arguments; what follows - its buffers, its first step - is its own.
+struct PassOpts {
+  const char* count = "n_windows";   // the name of the `windows` argument in the entry's messages
+  int group = 1;                     // decoder rows per window, and that argument's name (null: the entry has no such argument)
+  const char* group_name = nullptr;
+  const int32_t* active = nullptr;   // a temperature pass: the windows it decodes (the prefill serves no others)
+  int token_cap = INT32_MAX;         // a temperature pass: a row consumes at most this many draws
+  bool timed = false;                // the pass is the one ohw_state_timings reports: its start is recorded
+  int zero_rows = 0;                 // n_past is zeroed over this many rows first (beam search: the whole table)
+};
+struct PassSetup {
+  int n_prompt = 0, n_max = 0;
+  bool lang_tab = false;             // the rows' language tokens come from the state's table and sp->lang_id is ignored
+  bool wp = false;                   // a text-context table is set (ohw_state_set_window_prompt)
+  std::vector<int32_t> start;        // [windows] where window w's prompt starts: the length of its text context, or 0
+  std::vector<int32_t> prompt_rows;  // the source of the prompt upload: it lives until the caller's next stream synchronisation
+};
+PassSetup begin_pass(ohw_state* st, const ohw_sample_params* sp, int windows, const char* what, const PassOpts& o) {
+  const std::string w = what;
+  if (windows < 1 || windows != st->enc_batch) throw Error(OHW_E_INVALID_ARG, w + ": " + o.count + " must equal the batch of the last ohw_encode");
+  if (o.group_name && windows * o.group > st->max_batch)
+    throw Error(OHW_E_INVALID_ARG, w + ": the state needs max_batch >= n_windows * " + o.group_name + " decoder rows");
+  const ohw_ctx* c = st->ctx;
+  check_decode_ctx(st, what);
+  PassSetup ps;
+  // under a language table the rows' language tokens come from device memory and sp->lang_id is ignored
+  ps.lang_tab = !st->lang_kind.empty();
+  if (ps.lang_tab) check_window_lang(st, windows, w);
+  else if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, w + ": lang_id out of range");
+  HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = st->stream;
+  int32_t prompt[8];
+  ohw_sample_params psp = *sp;
+  if (ps.lang_tab) psp.lang_id = 0;
+  ps.n_prompt = build_prompt(c, &psp, prompt);
+  // under a text-context table window b starts at position wp_len[b]: the prefill puts the context there
+  ps.wp = !st->wp_len.empty();
+  const int n_max_raw = sp->force_len > 0 ? sp->force_len : sp->n_max;
+  ps.n_max = std::min(std::min(std::min(n_max_raw, st->max_tokens), c->hp.n_text_ctx - ps.n_prompt - window_prompt_max(st)), o.token_cap);
+  if (ps.n_max < 1) throw Error(OHW_E_INVALID_ARG, w + ": n_max < 1");
+  if (o.timed) HIP_CHECK(hipEventRecord(st->ev[4], s));
+  run_prefill(st, windows, o.active, w);     // checks the context table's batch
+  ps.start.assign((size_t)windows, 0);
+  if (ps.wp) ps.start = st->wp_len;
+  if (ps.lang_tab) {
+    fill_prompt_rows(st, &psp, windows, ps.n_prompt);
+  } else {
+    ps.prompt_rows.resize((size_t)windows * ps.n_prompt);
+    for (int b = 0; b < windows; ++b) std::memcpy(&ps.prompt_rows[(size_t)b * ps.n_prompt], prompt, (size_t)ps.n_prompt * 4);
+    HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ps.prompt_rows.data(), ps.prompt_rows.size() * 4, hipMemcpyHostToDevice, s));
+  }
+  if (o.zero_rows > 0 || !ps.wp) HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)(o.zero_rows > 0 ? o.zero_rows : windows) * 4, s));
+  if (ps.wp) HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_lens.p, (size_t)windows * 4, hipMemcpyDeviceToDevice, s));
+  return ps;
+}
+
+// iterations 1 .. n_max - 1 of a device decode loop: launch(it) replays the captured graph or enqueues the kernels.  With
+// `poll`, every eighth iteration reads n_done back and the loop leaves once it has reached `target`.  Returns the iterations run.
+template <typename F>
+int replay(ohw_state* st, int n_max, bool poll, int target, F&& launch) {
+  hipStream_t s = st->stream;
+  int32_t n_done_host = 0;
+  int ran = 0;
+  for (int it = 1; it < n_max; ++it) {
+    launch(it);
+    ++ran;
+    if (poll && ((it & 7) == 7)) {
+      HIP_CHECK(hipMemcpyAsync(&n_done_host, st->n_done.p, 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (n_done_host >= target) break;
+    }
+  }
+  return ran;
+}
+
+// a beam step's pointers on a state's beam buffers; q: the side of the token-history, kv_slot and log-probability double buffers
+// the step reads (it writes side q ^ 1).  nosp_prob stays null: the callers have their own rules for it
+BeamParams beam_params(ohw_state* st, int K, int q, bool lp, int prefix_stride) {
+  int32_t* tokbuf[2] = {st->tokens.as<int32_t>(), st->bm_tok2.as<int32_t>()};
+  BeamParams bp{};
+  bp.K = K; bp.prefix_stride = prefix_stride; bp.cand_lp = st->bm_cand_lp.as<float>(); bp.cand_tok = st->bm_cand_tok.as<int32_t>(); bp.beam_sum = st->bm_sum.as<float>();
+  bp.kv_slot = st->bm_slot[q].as<int32_t>(); bp.kv_slot_next = st->bm_slot[q ^ 1].as<int32_t>(); bp.tokens_next = tokbuf[q ^ 1];
+  bp.n_cur = st->bm_ncur.as<int32_t>(); bp.n_past_w = st->bm_npast.as<int32_t>(); bp.win_done = st->bm_done.as<int32_t>();
+  bp.fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp.fin_tok = st->bm_fin_tok.as<int32_t>(); bp.fin_len = st->bm_fin_len.as<int32_t>();
+  bp.fin_sum = st->bm_fin_sum.as<float>();
+  bp.part = st->bm_part.as<unsigned>(); bp.tickets = st->bm_ticket.as<unsigned>();
+  if (lp) { bp.plog = st->bm_plog[q].as<float>(); bp.plog_next = st->bm_plog[q ^ 1].as<float>(); bp.fin_plog = st->bm_fin_plog.as<float>(); }
+  return bp;
 }
 
 }  // namespace
@@ -905,19 +1103,7 @@ void ohw_state_free(ohw_state* st) {
   (void)hipDeviceSynchronize();
   for (auto& e : st->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : st->prof_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& g : st->step_graphs) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (g.graph) (void)hipGraphDestroy(g.graph);
-  }
-  for (auto& g : st->beam_graphs)
-    for (int q = 0; q < 2; ++q) {
-      if (g.exec[q]) (void)hipGraphExecDestroy(g.exec[q]);
-      if (g.graph[q]) (void)hipGraphDestroy(g.graph[q]);
-    }
-  for (auto& g : st->group_graphs) {
-    if (g.g.exec) (void)hipGraphExecDestroy(g.g.exec);
-    if (g.g.graph) (void)hipGraphDestroy(g.g.graph);
-  }
+  for (GraphCache* g : {&st->step_graphs, &st->group_graphs, &st->beam_graphs}) g->clear();
   if (st->own_stream) (void)hipStreamDestroy(st->own_stream);
   delete st;
 }
@@ -1310,7 +1496,7 @@ int ohw_decode_active(ohw_state* st, const int32_t* tokens, int n_new, const int
     // inactive windows ride along (their GEMM rows are free) but their cross K/V is not streamed: the done flags the
     // greedy loop uses for finished windows
     std::vector<int32_t> skip;
-    struct SkipDone { bool& f; bool on; SkipDone(bool& r, bool o) : f(r), on(o) { if (on) f = true; } ~SkipDone() { if (on) f = false; } } skip_done(st->skip_done, active != nullptr);
+    SkipDone skip_done(st->skip_done, active != nullptr);
     if (active) {
       skip.resize((size_t)batch);
       for (int b = 0; b < batch; ++b) skip[(size_t)b] = active[b] ? 0 : 1;
@@ -1392,35 +1578,16 @@ struct TempPass {
 static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, int max_tokens, const ohw_greedy_result* res, const TempPass* tp) {
     const char* what = tp ? "sample_pass" : "greedy";
     if (!st || !sp || !res || !res->tokens || !res->n_tokens) throw Error(OHW_E_INVALID_ARG, "null argument");
-    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": batch must equal the batch of the last ohw_encode");
-    const ohw_ctx* c = st->ctx;
-    check_decode_ctx(st, what);
-    // under a language table the rows' language tokens come from device memory and sp->lang_id is ignored
-    const bool lang_tab = !st->lang_kind.empty();
-    if (lang_tab) check_window_lang(st, batch, what);
-    else if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": lang_id out of range");
     if (tp && (!tp->active || !tp->uniforms || !(tp->temperature > 0.0f) || max_tokens < 1))
       throw Error(OHW_E_INVALID_ARG, "sample_pass: needs temperature > 0, active, uniforms and max_tokens >= 1");
-    HIP_CHECK(hipSetDevice(c->device));
+    PassOpts po;
+    po.count = "batch";
+    po.timed = !tp;                                        // ohw_state_timings reports the T = 0 loop
+    if (tp) { po.active = tp->active; po.token_cap = max_tokens; }
+    const PassSetup ps = begin_pass(st, sp, batch, what, po);
+    const ohw_ctx* c = st->ctx;
     hipStream_t s = st->stream;
-    int32_t prompt[8];
-    ohw_sample_params psp = *sp;
-    if (lang_tab) psp.lang_id = 0;
-    const int n_prompt = build_prompt(c, &psp, prompt);
-    // under a text-context table (ohw_state_set_window_prompt) window b starts at position wp_len[b]: the prefill puts the context there
-    const bool wp = !st->wp_len.empty();
-    const int n_max_raw = sp->force_len > 0 ? sp->force_len : sp->n_max;
-    int n_max = std::min(std::min(n_max_raw, st->max_tokens), c->hp.n_text_ctx - n_prompt - window_prompt_max(st));
-    if (tp) n_max = std::min(n_max, max_tokens);          // a row consumes at most max_tokens draws
-    if (n_max < 1) throw Error(OHW_E_INVALID_ARG, std::string(what) + ": n_max < 1");
-    std::vector<int32_t> ptoks((size_t)batch * n_prompt);
-    for (int b = 0; b < batch; ++b) std::memcpy(&ptoks[(size_t)b * n_prompt], prompt, (size_t)n_prompt * 4);
-    if (!tp) HIP_CHECK(hipEventRecord(st->ev[4], s));
-    run_prefill(st, batch, tp ? tp->active : nullptr, what);
-    if (lang_tab) fill_prompt_rows(st, &psp, batch, n_prompt);
-    else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
-    if (wp) HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_lens.p, (size_t)batch * 4, hipMemcpyDeviceToDevice, s));
-    else HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)batch * 4, s));
+    const int n_prompt = ps.n_prompt, n_max = ps.n_max;
     HIP_CHECK(hipMemsetAsync(st->n_cur.p, 0, (size_t)batch * 4, s));
     // a temperature pass: windows with active[b] == 0 start finished (cross-attention and the sampler skip them)
     std::vector<int32_t> done0;
@@ -1447,14 +1614,14 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
     if (eff.force_len > 0) eff.force_len = n_max;
     fill_sampler(st, &eff, batch, &spar);
     int steps = 0;
-    struct SkipDone { bool& f; explicit SkipDone(bool& r) : f(r) { f = true; } ~SkipDone() { f = false; } } skip_done(st->skip_done);
+    SkipDone skip_done(st->skip_done);
     Dispatch::run(c->dtype, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
       run_decoder_step<T>(st, batch, n_prompt);
       std::vector<int32_t> np((size_t)batch, n_prompt);
-      for (int b = 0; wp && b < batch; ++b) np[(size_t)b] += st->wp_len[(size_t)b];
+      for (int b = 0; b < batch; ++b) np[(size_t)b] += ps.start[(size_t)b];
       HIP_CHECK(hipMemcpyAsync(st->n_past.p, np.data(), np.size() * 4, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipStreamSynchronize(s));  // np (and a temperature pass's done0, n_done0, T, draws) are stack-lifetime sources
+      HIP_CHECK(hipStreamSynchronize(s));  // np, the prompt rows (and a temperature pass's done0, n_done0, T, draws) are stack-lifetime sources
       ++steps;
       auto sample = [&](hipStream_t q) {
         if (tp) launch_sampler_t(spar, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
@@ -1466,65 +1633,19 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
       // One greedy iteration = {feed next_tok, decoder step, sampler}.  It is launch-bound (about 260
       // short kernels), so it is captured once into a hipGraph and replayed; positions, tokens and
       // the done flags live in device memory, so the same graph serves every iteration.
+      auto iteration = [&](int, hipStream_t q) {
+        run_decoder_step<T>(st, batch, 1, st->next_tok.as<int32_t>());   // the token the sampler just wrote
+        sample(q);
+      };
+      // batch < graph_max_batch in this loop alone: the bound keeps a lane's wide greedy batch from capturing, which waits for the other lanes' decodes (state_set_graph_max_batch)
       const bool use_graph = st->graphs_enabled && st->prof_class == 0 && s != nullptr && batch < st->graph_max_batch;
       hipGraphExec_t step_exec = nullptr;
-      if (use_graph) {
-        for (auto& g : st->step_graphs)
-          if (g.batch == batch && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant && g.persist == st->persist && g.temp == (tp != nullptr) && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
-      }
-      if (use_graph && !step_exec) {
-        if (st->step_graphs.size() >= 8) {     // bounded: drop the oldest capture
-          auto& g = st->step_graphs.front();
-          if (g.exec) (void)hipGraphExecDestroy(g.exec);
-          if (g.graph) (void)hipGraphDestroy(g.graph);
-          st->step_graphs.erase(st->step_graphs.begin());
-        }
-        ohw_state::StepGraph ng;
-        // The iteration is captured on the state's OWN stream (non-blocking) and replayed on whatever stream the state
-        // runs on: a CU-masked stream (hipExtStreamCreateWithCUMask) is a blocking stream, and while a blocking stream
-        // captures, any use of the legacy stream by another thread - another engine loading its model, say - fails with
-        // "would make the legacy stream depend on a capturing blocking stream" and kills the capture (two engines driven
-        // by two threads: tests/test_gpu_configs.py).  The own stream is idle whenever the state runs on an external one.
-        // Capture mode RELAXED: in the other modes HIP (ROCm 7.2) rejects every synchronous memory call of EVERY thread
-        // while a capture is open - hipMemset in another engine's state allocation failed that way - and this thread
-        // makes no call during the capture that the stricter modes would have to catch.
-        hipStream_t cap = st->own_stream;
-        CaptureGate gate;   // no other thread is inside the library while this stream captures (common.hpp)
-        struct StreamSwap { ohw_state* st; hipStream_t keep; ~StreamSwap() { st->stream = keep; } } swap{st, st->stream};
-        st->stream = cap;
-        HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
-        try {
-          run_decoder_step<T>(st, batch, 1, st->next_tok.as<int32_t>());   // the token the sampler just wrote
-          sample(cap);
-        } catch (...) {
-          hipGraph_t g = nullptr;
-          (void)hipStreamEndCapture(cap, &g);
-          if (g) (void)hipGraphDestroy(g);
-          throw;
-        }
-        HIP_CHECK(hipStreamEndCapture(cap, &ng.graph));
-        hipError_t ie = hipGraphInstantiate(&ng.exec, ng.graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) { (void)hipGraphDestroy(ng.graph); HIP_CHECK(ie); }
-        ng.batch = batch; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.var = st->enc_var; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.temp = tp != nullptr; ng.spar = spar;
-        st->step_graphs.push_back(ng);
-        ++st->step_captures;
-        step_exec = ng.exec;
-      }
-      int32_t n_done_host = 0;
-      for (int it = 1; it < n_max; ++it) {
-        if (use_graph) {
-          HIP_CHECK(hipGraphLaunch(step_exec, s));
-        } else {
-          run_decoder_step<T>(st, batch, 1, st->next_tok.as<int32_t>());
-          sample(s);
-        }
-        ++steps;
-        if (sp->force_len <= 0 && ((it & 7) == 7)) {
-          HIP_CHECK(hipMemcpyAsync(&n_done_host, st->n_done.p, 4, hipMemcpyDeviceToHost, s));
-          HIP_CHECK(hipStreamSynchronize(s));
-          if (n_done_host >= batch) break;
-        }
-      }
+      if (use_graph) step_exec = st->step_graphs.get_or_capture(st, graph_key(st, batch, 0, tp != nullptr, spar), 1, iteration).exec[0];
+      // a forced length runs every iteration: no polling
+      steps += replay(st, n_max, sp->force_len <= 0, batch, [&](int it) {
+        if (use_graph) HIP_CHECK(hipGraphLaunch(step_exec, s));
+        else iteration(it, s);
+      });
     });
     if (!tp) HIP_CHECK(hipEventRecord(st->ev[5], s));
     decode_read_back(st, batch, max_tokens, res);
@@ -1550,46 +1671,32 @@ int ohw_sample_pass(ohw_state* st, const ohw_sample_params* sp, int batch, int m
 static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W, int N, int max_tokens, const TempPass& tp, const ohw_greedy_result* res) {
     if (!st || !sp || !res || !res->tokens || !res->n_tokens) throw Error(OHW_E_INVALID_ARG, "null argument");
     const int R = W * N;
-    if (W < 1 || W != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: n_windows must equal the batch of the last ohw_encode");
     if (N < 2 || N > 5) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: best_of must be in 1..5");
-    if (R > st->max_batch) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: the state needs max_batch >= n_windows * best_of decoder rows");
     if (!tp.active || !tp.uniforms || !(tp.temperature > 0.0f) || max_tokens < 1)
       throw Error(OHW_E_INVALID_ARG, "sample_pass_n: needs temperature > 0, active, uniforms and max_tokens >= 1");
     if (sp->force_len > 0) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: force_len is a single-candidate knob");
     const ohw_ctx* c = st->ctx;
-    check_decode_ctx(st, "sample_pass_n");
-    const bool lang_tab = !st->lang_kind.empty();     // then sp->lang_id is ignored: the N rows of a window share its prompt
-    if (lang_tab) check_window_lang(st, W, "sample_pass_n");
-    else if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: lang_id out of range");
     HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t s = st->stream;
     const int C = c->hp.n_text_ctx, MB = st->max_batch;
     if (!st->sn_slot.p) { st->sn_slot.alloc((size_t)MB * C * 4, true); st->sn_win.alloc((size_t)MB * 4 * 4, true); }
+    PassOpts po;                                      // the N rows of a window share its prompt; the prompt pass skips inactive windows
+    po.group = N; po.group_name = "best_of";
+    po.active = tp.active; po.token_cap = max_tokens;
+    const PassSetup ps = begin_pass(st, sp, W, "sample_pass_n", po);
+    hipStream_t s = st->stream;
+    const int n_prompt = ps.n_prompt, n_max = ps.n_max;
     int32_t* d_shared = st->sn_win.as<int32_t>();
     int32_t* d_active = d_shared + MB;
     int32_t* d_wdone = d_shared + 2 * MB;
     unsigned* d_wcnt = (unsigned*)(d_shared + 3 * MB);
-    int32_t prompt[8];
-    ohw_sample_params psp = *sp;
-    if (lang_tab) psp.lang_id = 0;
-    const int n_prompt = build_prompt(c, &psp, prompt);
-    const bool wp = !st->wp_len.empty();
-    const int n_max = std::min(std::min(std::min(sp->n_max, st->max_tokens), c->hp.n_text_ctx - n_prompt - window_prompt_max(st)), max_tokens);
-    if (n_max < 1) throw Error(OHW_E_INVALID_ARG, "sample_pass_n: n_max < 1");
-    std::vector<int32_t> ptoks((size_t)W * n_prompt), shared((size_t)W, n_prompt), act((size_t)W), skip((size_t)W);
+    std::vector<int32_t> shared((size_t)W), act((size_t)W), skip((size_t)W);
     int32_t n_done0[4] = {0, 0, 0, 0};
     for (int w = 0; w < W; ++w) {
-      std::memcpy(&ptoks[(size_t)w * n_prompt], prompt, (size_t)n_prompt * 4);
+      shared[(size_t)w] = ps.start[(size_t)w] + n_prompt;
       act[(size_t)w] = tp.active[w] ? 1 : 0;
       skip[(size_t)w] = act[(size_t)w] ? 0 : 1;
       n_done0[0] += skip[(size_t)w] * N;             // n_done counts rows
     }
-    run_prefill(st, W, tp.active, "sample_pass_n");  // checks the context table's batch
-    for (int w = 0; wp && w < W; ++w) shared[(size_t)w] += st->wp_len[(size_t)w];
-    if (lang_tab) fill_prompt_rows(st, &psp, W, n_prompt);
-    else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
-    if (wp) HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_lens.p, (size_t)W * 4, hipMemcpyDeviceToDevice, s));
-    else HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)W * 4, s));
     HIP_CHECK(hipMemcpyAsync(st->done.p, skip.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));     // the prompt pass skips inactive windows
     HIP_CHECK(hipMemcpyAsync(st->n_done.p, n_done0, 16, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_shared, shared.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
@@ -1605,7 +1712,7 @@ static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W,
     SampGroup grp{N, d_wdone, d_wcnt};
     // under a context table the windows' pasts differ in length: window w's goes to row w * N, which only its own candidates
     // write (beam_search_run gives the reason)
-    const int stride = (wp && W > 1) ? N : 1;
+    const int stride = (ps.wp && W > 1) ? N : 1;
     SampGroupInit gi{};
     gi.rows = R; gi.group = N; gi.n_ctx = C; gi.prefix_stride = stride; gi.shared = d_shared; gi.active = d_active;
     gi.kv_slot = st->sn_slot.as<int32_t>(); gi.n_past = st->n_past.as<int32_t>(); gi.done = st->done.as<int32_t>(); gi.win_done = d_wdone; gi.win_cnt = d_wcnt;
@@ -1613,7 +1720,7 @@ static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W,
     Dispatch::run(c->dtype, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
       {
-        struct SkipDone { bool& f; explicit SkipDone(bool& r) : f(r) { f = true; } ~SkipDone() { f = false; } } skip_done(st->skip_done);
+        SkipDone skip_done(st->skip_done);
         run_decoder_step<T>(st, W, n_prompt);                     // the prompt once per window; its K/V stays in cache rows 0 .. W-1
       }
       if (stride > 1)
@@ -1621,64 +1728,21 @@ static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W,
           launch_kv_prefix_move<T>(st->self_kv.p, 2 * c->hp.n_text_layer, MB, c->hp.n_text_head, C, w, w * N, shared[(size_t)w], s);
       launch_sample_group_init(gi, s);                            // slot table, n_past and done per row, the windows' flags
       st->sn_rows = R;
-      HIP_CHECK(hipStreamSynchronize(s));                         // the vectors above are stack-lifetime sources
+      HIP_CHECK(hipStreamSynchronize(s));                         // the vectors above and the prompt rows are stack-lifetime sources
       spar.advance = 0;
       launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);   // first token of every row from its window's prompt logits
       spar.advance = 1;
+      auto iteration = [&](int, hipStream_t q) {
+        run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
+        launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
+      };
       const bool use_graph = st->graphs_enabled && st->prof_class == 0 && s != nullptr;
       hipGraphExec_t step_exec = nullptr;
-      if (use_graph) {
-        for (auto& gg : st->group_graphs) {
-          const auto& g = gg.g;
-          if (gg.windows == W && gg.group == N && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant &&
-              g.persist == st->persist && std::memcmp(&g.spar, &spar, sizeof spar) == 0) step_exec = g.exec;
-        }
-      }
-      if (use_graph && !step_exec) {
-        if (st->group_graphs.size() >= 4) {     // bounded: drop the oldest capture
-          auto& g = st->group_graphs.front().g;
-          if (g.exec) (void)hipGraphExecDestroy(g.exec);
-          if (g.graph) (void)hipGraphDestroy(g.graph);
-          st->group_graphs.erase(st->group_graphs.begin());
-        }
-        ohw_state::GroupGraph ng;
-        hipStream_t cap = st->own_stream;       // captured as decode_loop captures its step (the reasons are given there)
-        CaptureGate gate;
-        struct StreamSwap { ohw_state* st; hipStream_t keep; ~StreamSwap() { st->stream = keep; } } swap{st, st->stream};
-        st->stream = cap;
-        HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
-        try {
-          run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
-          launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), cap);
-        } catch (...) {
-          hipGraph_t g = nullptr;
-          (void)hipStreamEndCapture(cap, &g);
-          if (g) (void)hipGraphDestroy(g);
-          throw;
-        }
-        HIP_CHECK(hipStreamEndCapture(cap, &ng.g.graph));
-        hipError_t ie = hipGraphInstantiate(&ng.g.exec, ng.g.graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) { (void)hipGraphDestroy(ng.g.graph); HIP_CHECK(ie); }
-        ng.windows = W; ng.group = N; ng.g.batch = R; ng.g.cus = st->stream_cus; ng.g.t_len = st->enc_ctx; ng.g.var = st->enc_var; ng.g.invariant = st->batch_invariant;
-        ng.g.persist = st->persist; ng.g.temp = true; ng.g.spar = spar;
-        st->group_graphs.push_back(ng);
-        ++st->step_captures;
-        step_exec = ng.g.exec;
-      }
-      int32_t n_done_host = 0;
-      for (int it = 1; it < n_max; ++it) {
-        if (use_graph) {
-          HIP_CHECK(hipGraphLaunch(step_exec, s));
-        } else {
-          run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
-          launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);
-        }
-        if ((it & 7) == 7) {
-          HIP_CHECK(hipMemcpyAsync(&n_done_host, st->n_done.p, 4, hipMemcpyDeviceToHost, s));
-          HIP_CHECK(hipStreamSynchronize(s));
-          if (n_done_host >= R) break;
-        }
-      }
+      if (use_graph) step_exec = st->group_graphs.get_or_capture(st, graph_key(st, W, N, true, spar), 1, iteration).exec[0];
+      replay(st, n_max, true, R, [&](int it) {
+        if (use_graph) HIP_CHECK(hipGraphLaunch(step_exec, s));
+        else iteration(it, s);
+      });
     });
     decode_read_back(st, R, max_tokens, res);
 }
@@ -1698,9 +1762,6 @@ int ohw_greedy(ohw_state* st, const ohw_sample_params* sp, int batch, int32_t* t
   r.tokens = tokens_out; r.n_tokens = n_tokens_out; r.sum_logprob = sum_logprob_out;
   return ohw_greedy_ex(st, sp, batch, max_tokens, &r);
 }
-
-// OHW_DEBUG_MARKS=1: progress lines on stderr (which HIP call a tool died under)
-#define BMARK(what, i) do { static const bool on_ = env_int("OHW_DEBUG_MARKS", 0, 0, 1) != 0; if (on_) { std::fprintf(stderr, "[ohw beam] %s %d\n", what, (int)(i)); std::fflush(stderr); } } while (0)
 
 // the beam search's buffers of a state, allocated at first use (ohw_beam_search, ohw_dbg_beam_step)
 static void alloc_beam_buffers(ohw_state* st) {
@@ -1740,37 +1801,23 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
     if (max_tokens < 0) throw Error(OHW_E_INVALID_ARG, "beam search: max_tokens < 0");
     const bool lp = ex != nullptr;
     const int W = n_windows, K = beam_size, R = W * K;
-    if (W < 1 || W != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "beam search: n_windows must equal the batch of the last ohw_encode");
     if (K < 2 || K > 5) throw Error(OHW_E_INVALID_ARG, "beam search: beam_size must be in 2..5");
-    if (R > st->max_batch) throw Error(OHW_E_INVALID_ARG, "beam search: the state needs max_batch >= n_windows * beam_size decoder rows");
-    check_decode_ctx(st, "beam search");
-    const ohw_ctx* c = st->ctx;
-    const bool lang_tab = !st->lang_kind.empty();     // then sp->lang_id is ignored: all K rows of a window share its table entry
-    if (lang_tab) check_window_lang(st, W, "beam search");
-    else if (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs) throw Error(OHW_E_INVALID_ARG, "beam search: lang_id out of range");
     if (sp->force_len > 0) throw Error(OHW_E_INVALID_ARG, "beam search: force_len is a greedy-only knob");
+    const ohw_ctx* c = st->ctx;
     HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t s = st->stream;
     const int MT = st->max_tokens, C = c->hp.n_text_ctx, MB = st->max_batch;
     alloc_beam_buffers(st);
-    int32_t prompt[8];
-    ohw_sample_params psp = *sp;
-    if (lang_tab) psp.lang_id = 0;
-    const int n_prompt = build_prompt(c, &psp, prompt);
+    PassOpts po;                                      // all K rows of a window share its prompt and its language table entry
+    po.group = K; po.group_name = "beam_size";
+    po.timed = true;
+    po.zero_rows = MB;
+    const PassSetup ps = begin_pass(st, sp, W, "beam search", po);     // n_max is not clamped to max_tokens: the ranking truncates
+    hipStream_t s = st->stream;
+    const int n_prompt = ps.n_prompt, n_max = ps.n_max;
     // under a text-context table window w's prompt starts at position wp_len[w]; the context's K/V lives in slot w like the prompt's
-    const bool wp = !st->wp_len.empty();
-    const int n_max = std::min(std::min(sp->n_max, MT), C - n_prompt - window_prompt_max(st));
-    if (n_max < 1) throw Error(OHW_E_INVALID_ARG, "beam search: n_max < 1");
-    std::vector<int32_t> ptoks((size_t)W * n_prompt), np0((size_t)W, n_prompt - 1);
-    if (wp && (int)st->wp_len.size() == W)
-      for (int w = 0; w < W; ++w) np0[(size_t)w] += st->wp_len[(size_t)w];
-    for (int w = 0; w < W; ++w) std::memcpy(&ptoks[(size_t)w * n_prompt], prompt, (size_t)n_prompt * 4);
-    HIP_CHECK(hipEventRecord(st->ev[4], s));
-    run_prefill(st, W, nullptr, "beam search");
-    if (lang_tab) fill_prompt_rows(st, &psp, W, n_prompt);
-    else HIP_CHECK(hipMemcpyAsync(st->step_tok.p, ptoks.data(), ptoks.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(st->n_past.p, 0, (size_t)MB * 4, s));
-    if (wp) HIP_CHECK(hipMemcpyAsync(st->n_past.p, st->wp_lens.p, (size_t)W * 4, hipMemcpyDeviceToDevice, s));
+    const bool wp = ps.wp;
+    std::vector<int32_t> np0((size_t)W);
+    for (int w = 0; w < W; ++w) np0[(size_t)w] = ps.start[(size_t)w] + n_prompt - 1;
     HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
     for (DevBuf* b : {&st->bm_sum, &st->bm_ncur, &st->bm_done, &st->bm_fin_cnt, &st->bm_fin_len}) HIP_CHECK(hipMemsetAsync(b->p, 0, (size_t)MB * 4, s));
     HIP_CHECK(hipMemcpyAsync(st->bm_npast.p, np0.data(), np0.size() * 4, hipMemcpyHostToDevice, s));
@@ -1782,17 +1829,8 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
     auto params = [&](int q, SamplerParams* p, BeamParams* bp) {
       std::memcpy(p, &base, sizeof base);
       p->tokens = tokbuf[q];
-      *bp = BeamParams{};
-      bp->K = K; bp->prefix_stride = (wp && W > 1) ? K : 1; bp->cand_lp = st->bm_cand_lp.as<float>(); bp->cand_tok = st->bm_cand_tok.as<int32_t>(); bp->beam_sum = st->bm_sum.as<float>();
-      bp->kv_slot = st->bm_slot[q].as<int32_t>(); bp->kv_slot_next = st->bm_slot[q ^ 1].as<int32_t>(); bp->tokens_next = tokbuf[q ^ 1];
-      bp->n_cur = st->bm_ncur.as<int32_t>(); bp->n_past_w = st->bm_npast.as<int32_t>(); bp->win_done = st->bm_done.as<int32_t>();
-      bp->fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp->fin_tok = st->bm_fin_tok.as<int32_t>(); bp->fin_len = st->bm_fin_len.as<int32_t>();
-      bp->fin_sum = st->bm_fin_sum.as<float>();
-      bp->part = st->bm_part.as<unsigned>(); bp->tickets = st->bm_ticket.as<unsigned>();
-      if (lp) {
-        bp->plog = st->bm_plog[q].as<float>(); bp->plog_next = st->bm_plog[q ^ 1].as<float>(); bp->fin_plog = st->bm_fin_plog.as<float>();
-        bp->nosp_prob = st->bm_nosp.as<float>();      // read by the first step alone
-      }
+      *bp = beam_params(st, K, q, lp, (wp && W > 1) ? K : 1);
+      if (lp) bp->nosp_prob = st->bm_nosp.as<float>();      // read by the first step alone
     };
     int steps = 0, last_q = 1;
     Dispatch::run(c->dtype, [&](auto* tag) {
@@ -1804,7 +1842,7 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
       if (wp && W > 1)
         for (int w = W - 1; w >= 1; --w)
           launch_kv_prefix_move<T>(st->self_kv.p, 2 * c->hp.n_text_layer, st->max_batch, c->hp.n_text_head, C, w, w * K, np0[(size_t)w] + 1, s);
-      HIP_CHECK(hipStreamSynchronize(s));                         // ptoks / np0 are stack-lifetime sources
+      HIP_CHECK(hipStreamSynchronize(s));                         // the prompt rows / np0 are stack-lifetime sources
       ++steps;
       SamplerParams p0; BeamParams b0;
       params(0, &p0, &b0);
@@ -1814,68 +1852,17 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
       const bool use_graph = st->graphs_enabled && st->prof_class == 0 && s != nullptr;
       hipGraphExec_t exec[2] = {nullptr, nullptr};
       if (use_graph) {
-        for (auto& g : st->beam_graphs)
-          if (g.windows == W && g.K == K && g.cus == st->stream_cus && g.t_len == st->enc_ctx && g.var == st->enc_var && g.invariant == st->batch_invariant && g.persist == st->persist && g.lp == lp && std::memcmp(&g.spar, &base, sizeof base) == 0) {
-            exec[0] = g.exec[0]; exec[1] = g.exec[1];
-          }
+        const GraphEntry& g = st->beam_graphs.get_or_capture(st, graph_key(st, W, K, lp, base), 2, [&](int q, hipStream_t cap) {
+          SamplerParams pq; BeamParams bq;
+          params(q, &pq, &bq);
+          run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), K, bq.kv_slot, bq.win_done);
+          BMARK("decoder step captured", q);
+          launch_beam_step(pq, bq, W, 0, cap);
+          BMARK("beam step captured", q);
+        });
+        exec[0] = g.exec[0]; exec[1] = g.exec[1];
       }
-      if (use_graph && !exec[0]) {
-        // room first: the oldest PAIR goes before anything of this call exists (round 2 evicted the front entry between the
-        // two captures of a call - an entry whose exec the call might already hold)
-        if (st->beam_graphs.size() >= 4) {
-          auto& g = st->beam_graphs.front();
-          for (int q = 0; q < 2; ++q) {
-            if (g.exec[q]) (void)hipGraphExecDestroy(g.exec[q]);
-            if (g.graph[q]) (void)hipGraphDestroy(g.graph[q]);
-          }
-          st->beam_graphs.erase(st->beam_graphs.begin());
-        }
-        ohw_state::BeamGraph ng;
-        std::memset(&ng.spar, 0, sizeof ng.spar);
-        auto drop = [&] {
-          for (int q = 0; q < 2; ++q) {
-            if (ng.exec[q]) (void)hipGraphExecDestroy(ng.exec[q]);
-            if (ng.graph[q]) (void)hipGraphDestroy(ng.graph[q]);
-          }
-        };
-        try {
-          for (int q = 0; q < 2; ++q) {
-            SamplerParams pq; BeamParams bq;
-            params(q, &pq, &bq);
-            hipStream_t cap = st->own_stream;
-            CaptureGate gate;
-            struct StreamSwap { ohw_state* st; hipStream_t keep; ~StreamSwap() { st->stream = keep; } } swap{st, st->stream};
-            st->stream = cap;
-            BMARK("capture begin", q);
-            HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
-            try {
-              run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), K, bq.kv_slot, bq.win_done);
-              BMARK("decoder step captured", q);
-              launch_beam_step(pq, bq, W, 0, cap);
-              BMARK("beam step captured", q);
-            } catch (...) {
-              hipGraph_t g = nullptr;
-              (void)hipStreamEndCapture(cap, &g);
-              if (g) (void)hipGraphDestroy(g);
-              throw;
-            }
-            HIP_CHECK(hipStreamEndCapture(cap, &ng.graph[q]));
-            BMARK("capture ended", q);
-            HIP_CHECK(hipGraphInstantiate(&ng.exec[q], ng.graph[q], nullptr, nullptr, 0));
-            BMARK("instantiated", q);
-          }
-        } catch (...) {
-          drop();
-          throw;
-        }
-        ng.windows = W; ng.K = K; ng.cus = st->stream_cus; ng.t_len = st->enc_ctx; ng.var = st->enc_var; ng.invariant = st->batch_invariant; ng.persist = st->persist; ng.lp = lp;
-        std::memcpy(&ng.spar, &base, sizeof base);
-        st->beam_graphs.push_back(ng);
-        ++st->beam_captures;
-        exec[0] = ng.exec[0]; exec[1] = ng.exec[1];
-      }
-      int32_t n_done_host = 0;
-      for (int it = 1; it < n_max; ++it) {
+      const int ran = replay(st, n_max, true, W, [&](int it) {
         const int q = it & 1;
         if (use_graph) {
           BMARK("graph launch", it);
@@ -1887,14 +1874,9 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
           run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), K, bq.kv_slot, bq.win_done);
           launch_beam_step(pq, bq, W, 0, s);
         }
-        ++steps;
-        last_q = q ^ 1;
-        if ((it & 7) == 7) {
-          HIP_CHECK(hipMemcpyAsync(&n_done_host, st->n_done.p, 4, hipMemcpyDeviceToHost, s));
-          HIP_CHECK(hipStreamSynchronize(s));
-          if (n_done_host >= W) break;
-        }
-      }
+      });
+      steps += ran;
+      last_q = (ran & 1) ^ 1;                                     // the side the last iteration wrote (no iteration: the first step's side 1)
     });
     if (lp) {
       // the ranking on the device (beam_finish_kernel restates the host loop below); W rows come back
@@ -1971,11 +1953,11 @@ int ohw_beam_search_ex(ohw_state* st, const ohw_sample_params* sp, int n_windows
 int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (!st || !name) return OHW_E_INVALID_ARG;
   const std::string n = name;
-  if (n == "beam_captures") return st->beam_captures;
-  if (n == "beam_graphs") return (int)st->beam_graphs.size();
-  if (n == "step_captures") return st->step_captures;
-  if (n == "step_graphs") return (int)st->step_graphs.size();
-  if (n == "group_graphs") return (int)st->group_graphs.size();
+  if (n == "beam_captures") return st->beam_graphs.captures;
+  if (n == "beam_graphs") return (int)st->beam_graphs.entries.size();
+  if (n == "step_captures") return st->step_graphs.captures + st->group_graphs.captures;     // a group capture counts here too
+  if (n == "step_graphs") return (int)st->step_graphs.entries.size();
+  if (n == "group_graphs") return (int)st->group_graphs.entries.size();
   if (n == "persist_launches") return st->persist_launches;
   if (n == "xattn.chunk") return (int)std::min<int64_t>(st->tally_xchunk, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
@@ -2443,14 +2425,7 @@ static void dbg_beam_step_run(ohw_state* st, const ohw_sample_params* sp, const 
     SamplerParams p;
     fill_sampler(st, sp, R, &p);
     p.tokens = tokbuf[q];
-    BeamParams bp{};
-    bp.K = K; bp.prefix_stride = 1; bp.cand_lp = st->bm_cand_lp.as<float>(); bp.cand_tok = st->bm_cand_tok.as<int32_t>(); bp.beam_sum = st->bm_sum.as<float>();
-    bp.kv_slot = st->bm_slot[q].as<int32_t>(); bp.kv_slot_next = st->bm_slot[q ^ 1].as<int32_t>(); bp.tokens_next = tokbuf[q ^ 1];
-    bp.n_cur = st->bm_ncur.as<int32_t>(); bp.n_past_w = st->bm_npast.as<int32_t>(); bp.win_done = st->bm_done.as<int32_t>();
-    bp.fin_cnt = st->bm_fin_cnt.as<int32_t>(); bp.fin_tok = st->bm_fin_tok.as<int32_t>(); bp.fin_len = st->bm_fin_len.as<int32_t>();
-    bp.fin_sum = st->bm_fin_sum.as<float>();
-    bp.part = st->bm_part.as<unsigned>(); bp.tickets = st->bm_ticket.as<unsigned>();
-    if (lp) { bp.plog = st->bm_plog[q].as<float>(); bp.plog_next = st->bm_plog[q ^ 1].as<float>(); bp.fin_plog = st->bm_fin_plog.as<float>(); }
+    BeamParams bp = beam_params(st, K, q, lp, 1);
     if (x && x->nosp_prob) bp.nosp_prob = st->bm_nosp.as<float>();
     launch_beam_step(p, bp, W, first, s);
     if (lp) {
