@@ -1101,7 +1101,8 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  * counts once, at its capture; saturates at INT32_MAX):
  *   "dec_gemm.<gemm><form>.<NT>x<MT>"  gemm: qkv, o (self-attention out), xq, xo (cross-attention q / out), fc1, fc2,
  *                                      logits; form: ".ln" (LayerNorm in the prologue), ".pn" (post-norm), ".ks"
- *                                      (split-K), "" (none); NT x MT n-tiles x m-tiles per workgroup: 1x1 2x1 1x2 2x2 4x2 1x6
+ *                                      (split-K), "" (none); NT x MT n-tiles x m-tiles per workgroup: 1x1 2x1 1x2 2x2 4x2 1x6,
+ *                                      4x6 5x6 (qkv.ln, fc1.ln: all rows behind a LayerNorm launch of its own)
  *   "xattn.plain" / "xattn.split"      cross-attention, one workgroup per (row, head) / keys cut over gridDim.z > 1
  *   "xattn.rows2" .. "xattn.rows4"     one workgroup per (window, head) for 2..4 new tokens
  *   "xattn.chunk"                      the prefill's 8 rows per window on the MFMA units (ohw_state_prefill)
@@ -1223,7 +1224,8 @@ int ohw_beam_finish_host(const ohw_beam_finish_io* io);
  *   decides the work shape.  *shape_out (may be NULL): OHW_DG_SHAPE_* of the kernel that ran. */
 enum { OHW_DEPI_QKV = 0, OHW_DEPI_BIAS_T, OHW_DEPI_BIAS_GELU_T, OHW_DEPI_BIAS_RESID, OHW_DEPI_LOGITS };
 enum { OHW_DG_FORM_PLAIN = 0, OHW_DG_FORM_LN, OHW_DG_FORM_PN };
-enum { OHW_DG_SHAPE_1x1 = 0, OHW_DG_SHAPE_2x1, OHW_DG_SHAPE_1x2, OHW_DG_SHAPE_2x2, OHW_DG_SHAPE_4x2, OHW_DG_SHAPE_1x6 };
+enum { OHW_DG_SHAPE_1x1 = 0, OHW_DG_SHAPE_2x1, OHW_DG_SHAPE_1x2, OHW_DG_SHAPE_2x2, OHW_DG_SHAPE_4x2, OHW_DG_SHAPE_1x6,
+       OHW_DG_SHAPE_4x6, OHW_DG_SHAPE_5x6 };
 typedef struct {
   int32_t dtype, epilogue, form;
   int32_t M, N, K, n_new;

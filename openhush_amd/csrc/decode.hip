@@ -97,6 +97,109 @@ constexpr int DG_THREADS = 512;
 constexpr int DG_WAVES = DG_THREADS / 64;
 constexpr int DG_LN_MAXK = 1280;  // fused LayerNorm: 16 threads per row, 20 float4 each
 
+// The LayerNorm of the LN forms, one row: thread `sub` of the row's TPR threads (16 or 32, consecutive lanes of a wave)
+// normalises its float4 groups sub, sub + TPR ... of xr [K] and hands each as four 16-bit values to store(column, words).
+// One function for the fused prologue (dec_gemm_kernel<.., LN, ..>) and the stand-alone launch (dec_ln_rows_kernel): the
+// same expressions with every fused multiply-add spelled out, so all of them give the same words.
+template <typename T, int TPR, typename Store>
+__device__ __forceinline__ void dec_ln_row(const float* __restrict__ xr, int K, int sub, Store&& store) {
+  // Contraction is off in here and the one fused form is written out: left to hipcc, the squared deviations came out as
+  // fma(a, a, b * b) in every float4 group with 16 threads per row, but as a * a + b * b in the first four groups with 32 - a
+  // row in a few thousand then got another rstd, and other 16-bit words, depending on the work shape that normalised it.
+#pragma clang fp contract(off)
+  constexpr int NV = DG_LN_MAXK / (4 * TPR);
+  // every load is unconditional (clamped column, masked value): a per-element "load or zero" branch
+  // makes hipcc wait vmcnt(0) per element and serialises 20 L2 round trips
+  f32x4 v[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * TPR + sub) * 4;
+    const int cc = c < K ? c : 0;
+    v[i] = *(const f32x4*)(xr + cc);
+  }
+  // The row statistics must not depend on MT (which follows the CU budget of the stream: a decode on a CU-masked
+  // stream has to give the tokens of the same decode on the whole chip, bit for bit).  The sum is DEFINED as that of
+  // 32 "virtual" threads per row - virtual thread s adds the float4 groups s, s + 32, s + 64 ... in order - followed
+  // by the xor tree 16, 8, 4, 2, 1.  With 16 threads per row (MT = 2) a thread plays the virtual threads `sub` (its
+  // even groups) and `sub + 16` (its odd groups) and adds the two: the tree's first level.
+  constexpr int VS = 32 / TPR;                 // virtual threads per physical thread: 1 or 2
+  float sv[VS];
+#pragma unroll
+  for (int q = 0; q < VS; ++q) sv[q] = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * TPR + sub) * 4;
+    const float ok = c < K ? 1.f : 0.f;
+    sv[i % VS] += ok * ((v[i].x + v[i].y) + (v[i].z + v[i].w));
+  }
+  float sum = sv[0];
+  if constexpr (VS == 2) sum += sv[1];
+#pragma unroll
+  for (int o = TPR / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  const float mean = sum / (float)K;
+  float vv[VS];
+#pragma unroll
+  for (int q = 0; q < VS; ++q) vv[q] = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * TPR + sub) * 4;
+    const float ok = c < K ? 1.f : 0.f;
+    const float a = v[i].x - mean, b2 = v[i].y - mean, c2 = v[i].z - mean, d2 = v[i].w - mean;
+    vv[i % VS] += ok * (__builtin_fmaf(a, a, b2 * b2) + __builtin_fmaf(c2, c2, d2 * d2));
+  }
+  float var = vv[0];
+  if constexpr (VS == 2) var += vv[1];
+#pragma unroll
+  for (int o = TPR / 2; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
+  const float rstd = rsqrtf(var / (float)K + 1e-5f);
+  // gamma / beta live in the weights and the bias (launch_fold_ln): only the normalisation is left here
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * TPR + sub) * 4;
+    u32x2 w2;
+    w2.x = pack2<T>((v[i].x - mean) * rstd, (v[i].y - mean) * rstd);
+    w2.y = pack2<T>((v[i].z - mean) * rstd, (v[i].w - mean) * rstd);
+    if (c < K) store(c, w2);
+  }
+}
+
+// the 16-bit epilogues (QKV's scatter into q and the caches, BIAS_T's rows, GELU_T's tiles) of output (m, n) with the bias
+// already added: shared by dec_gemm_kernel and dec_gemm_rows_kernel
+template <typename T, int EPI>
+__device__ __forceinline__ void dec_gemm_store16(const DecGemmParams& p, int m, int n, float v) {
+  if constexpr (EPI == DEPI_QKV) {
+    const int d = p.d_model;
+    const T v16 = (T)v;
+    if (n < d) {
+      if (p.attn_ticket) {      // the fused self-attention reads it in this launch: written through (sc1)
+        __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, 0x7ffffffe, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, v16), ro, (int)(((int64_t)m * d + n) * 2), 0, 16);
+      } else {
+        ((T*)p.out)[(int64_t)m * d + n] = v16;
+      }
+    } else {
+      const int b = m / p.n_new, i = m % p.n_new;
+      const int pos = p.n_past[b] + i;
+      const int nn = n < 2 * d ? n - d : n - 2 * d;
+      const int h = nn >> 6, dh = nn & 63;
+      T* cache = (T*)(n < 2 * d ? p.k_cache : p.v_cache);
+      if (pos < p.n_ctx) {
+        const int64_t at = ((((int64_t)b * p.n_head + h) * p.n_ctx + pos) << 6) + dh;
+        if (p.attn_ticket) {
+          __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)cache, 0, (unsigned)p.kv_bytes, 0x00020000);
+          __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, v16), rc, (int)(at * 2), 0, 16);
+        } else {
+          cache[at] = v16;
+        }
+      }
+    }
+  } else if constexpr (EPI == DEPI_BIAS_T) {
+    ((T*)p.out)[(int64_t)m * p.ld_out + n] = (T)v;
+  } else if constexpr (EPI == DEPI_BIAS_GELU_T) {
+    ((T*)p.out)[act_tiled_offset(m, n, p.N)] = (T)gelu_erf(v);
+  }
+}
+
 template <typename T, int EPI, bool LN, int NT, int MT>
 __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_kernel(DecGemmParams p) {
   // MT = m-tiles (16 rows) per workgroup.  MT = 1 (RESID GEMMs): the two row halves of a weight tile go to two
@@ -202,60 +305,7 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_kernel(DecGemmParams p
     int m = m0 + row;
     if (m > p.M - 1) m = p.M - 1;
     const float* xr = xf + (int64_t)m * p.K;
-    constexpr int NV = DG_LN_MAXK / (4 * TPR);
-    // every load is unconditional (clamped column, masked value): a per-element "load or zero" branch
-    // makes hipcc wait vmcnt(0) per element and serialises 20 L2 round trips
-    f32x4 v[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * TPR + sub) * 4;
-      const int cc = c < p.K ? c : 0;
-      v[i] = *(const f32x4*)(xr + cc);
-    }
-    // The row statistics must not depend on MT (which follows the CU budget of the stream: a decode on a CU-masked
-    // stream has to give the tokens of the same decode on the whole chip, bit for bit).  The sum is DEFINED as that of
-    // 32 "virtual" threads per row - virtual thread s adds the float4 groups s, s + 32, s + 64 ... in order - followed
-    // by the xor tree 16, 8, 4, 2, 1.  With 16 threads per row (MT = 2) a thread plays the virtual threads `sub` (its
-    // even groups) and `sub + 16` (its odd groups) and adds the two: the tree's first level.
-    constexpr int VS = 32 / TPR;                 // virtual threads per physical thread: 1 or 2
-    float sv[VS];
-#pragma unroll
-    for (int q = 0; q < VS; ++q) sv[q] = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * TPR + sub) * 4;
-      const float ok = c < p.K ? 1.f : 0.f;
-      sv[i % VS] += ok * ((v[i].x + v[i].y) + (v[i].z + v[i].w));
-    }
-    float sum = sv[0];
-    if constexpr (VS == 2) sum += sv[1];
-#pragma unroll
-    for (int o = TPR / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum / (float)p.K;
-    float vv[VS];
-#pragma unroll
-    for (int q = 0; q < VS; ++q) vv[q] = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * TPR + sub) * 4;
-      const float ok = c < p.K ? 1.f : 0.f;
-      const float a = v[i].x - mean, b2 = v[i].y - mean, c2 = v[i].z - mean, d2 = v[i].w - mean;
-      vv[i % VS] += ok * ((a * a + b2 * b2) + (c2 * c2 + d2 * d2));
-    }
-    float var = vv[0];
-    if constexpr (VS == 2) var += vv[1];
-#pragma unroll
-    for (int o = TPR / 2; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
-    const float rstd = rsqrtf(var / (float)p.K + 1e-5f);
-    // gamma / beta live in the weights and the bias (launch_fold_ln): only the normalisation is left here
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * TPR + sub) * 4;
-      u32x2 w2;
-      w2.x = pack2<T>((v[i].x - mean) * rstd, (v[i].y - mean) * rstd);
-      w2.y = pack2<T>((v[i].z - mean) * rstd, (v[i].w - mean) * rstd);
-      if (c < p.K) *(u32x2*)(ylds + row * ystride + c * 2) = w2;
-    }
+    dec_ln_row<T, TPR>(xr, p.K, sub, [&](int c, u32x2 w2) { *(u32x2*)(ylds + row * ystride + c * 2) = w2; });
     __syncthreads();
     TRACE(16 + EPI * 2 + 1, 1);
   }
@@ -519,36 +569,8 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_kernel(DecGemmParams p
       v = pnst[2 * r + 1] * (v - pnst[2 * r] * p.wsum[n]);
     }
     if (p.bias) v += p.bias[n];
-    if constexpr (EPI == DEPI_QKV) {
-      const int d = p.d_model;
-      const T v16 = (T)v;
-      if (n < d) {
-        if (p.attn_ticket) {      // the fused self-attention reads it in this launch: written through (sc1)
-          __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, 0x7ffffffe, 0x00020000);
-          __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, v16), ro, (int)(((int64_t)m * d + n) * 2), 0, 16);
-        } else {
-          ((T*)p.out)[(int64_t)m * d + n] = v16;
-        }
-      } else {
-        const int b = m / p.n_new, i = m % p.n_new;
-        const int pos = p.n_past[b] + i;
-        const int nn = n < 2 * d ? n - d : n - 2 * d;
-        const int h = nn >> 6, dh = nn & 63;
-        T* cache = (T*)(n < 2 * d ? p.k_cache : p.v_cache);
-        if (pos < p.n_ctx) {
-          const int64_t at = ((((int64_t)b * p.n_head + h) * p.n_ctx + pos) << 6) + dh;
-          if (p.attn_ticket) {
-            __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)cache, 0, (unsigned)p.kv_bytes, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, v16), rc, (int)(at * 2), 0, 16);
-          } else {
-            cache[at] = v16;
-          }
-        }
-      }
-    } else if constexpr (EPI == DEPI_BIAS_T) {
-      ((T*)p.out)[(int64_t)m * p.ld_out + n] = (T)v;
-    } else if constexpr (EPI == DEPI_BIAS_GELU_T) {
-      ((T*)p.out)[act_tiled_offset(m, n, p.N)] = (T)gelu_erf(v);
+    if constexpr (EPI == DEPI_QKV || EPI == DEPI_BIAS_T || EPI == DEPI_BIAS_GELU_T) {
+      dec_gemm_store16<T, EPI>(p, m, n, v);
     } else if constexpr (EPI == DEPI_BIAS_RESID) {
       ((float*)p.out)[(int64_t)m * p.ld_out + n] = resid_old[t] + v;
     } else if constexpr (EPI == DEPI_LOGITS) {
@@ -598,103 +620,215 @@ static int dec_gemm_launch(const DecGemmParams& p, hipStream_t s) {
   return NT == 4 ? DG_SHAPE_4x2 : NT == 2 ? (MT == 1 ? DG_SHAPE_2x1 : DG_SHAPE_2x2) : (MT == 1 ? DG_SHAPE_1x1 : DG_SHAPE_1x2);
 }
 
-// Many rows on few CUs with a long K (mlp.2 on a lane of the LANES schedule: 96 rows, K = 5120, 64 CUs): the RESID GEMM with
-// MTW m-tiles per workgroup.  dec_gemm_kernel<RESID, 1, 2> launches n_tiles x ceil(m-tiles / 2) workgroups there, and every row
-// block streams the n-tile's weights again.  Here a workgroup takes MTW m-tiles of its n-tile: a wave requests the weight
-// blocks of its K share once and applies each to every m-tile's activation fragment (L2 hits, fetched G k-blocks at a time).
+// The LayerNorm of M fp32 rows once per launch, for the all-rows forms below: y = the 16-bit (x - mean) * rstd in the
+// activation-tile order [ceil(M / 16)][K / 32][64][8] - the very words the fused prologue of dec_gemm_kernel<.., LN, .., 2> puts
+// into its LDS image (dec_ln_row; no gamma / beta: they are folded into the weights).  Eight rows per workgroup and 16
+// threads per row, as in the two-m-tile forms this launch stands in for.  The pad rows of the last m-tile are written as zeros.
+template <typename T>
+__global__ __launch_bounds__(128) void dec_ln_rows_kernel(const float* __restrict__ x, T* __restrict__ y, int M, int K) {
+  const int row = threadIdx.x >> 4, sub = threadIdx.x & 15;
+  const int m = blockIdx.x * 8 + row;              // below ceil(M / 16) * 16: the grid is two workgroups per m-tile
+  const int mc = m < M ? m : M - 1;                // a pad row normalises the last row and stores zeros
+  dec_ln_row<T, 16>(x + (int64_t)mc * K, K, sub, [&](int c, u32x2 w2) {
+    if (m >= M) w2 = (u32x2){0u, 0u};
+    *(u32x2*)(y + act_tiled_offset(m, c, K)) = w2;   // c % 4 == 0: the four columns lie in one 8-element group
+  });
+}
+
+// Many rows on few CUs (a lane of the LANES schedule: 96 rows on 64 CUs): a workgroup takes NTW n-tiles and up to
+// MTP * PASSES m-tiles of them, requests its K share of the weights ONCE and applies each block to every m-tile's
+// activation fragment (plain tiles: L2 hits).  dec_gemm_kernel launches one workgroup per two m-tiles there, and every row
+// block requests the n-tiles' weights again (and, in the LN forms, normalises its rows again).  Two bodies:
+//   RESID, long K (mlp.2, K = 5120; NTW = 1, one pass of six m-tiles): the weights stream through in runs of 20 / 4 / 1
+//     k-blocks per wave, the fragments are fetched G k-blocks at a time;
+//   QKV / GELU_T, K <= 1280 (LN1 + QKV and LN2 + mlp.0 behind dec_ln_rows_kernel): a wave's whole share, at most five
+//     k-blocks of each n-tile, stays in registers over PASSES passes of MTP m-tiles, each with its own reduction and epilogue
+//     (the accumulators and the 1 KiB per wave, n-tile and m-tile of reduction buffer are what bounds a pass).
 // Per (m-tile, n-tile) everything is dec_gemm_kernel's: the 8 waves' interleaved K split, a wave's k-blocks in ascending
-// order through one accumulator, the LDS reduction over the waves in wave order from 0.f, bias, then residual + v.  The
-// bits of the output therefore do not depend on which of the two kernels ran.  No split-K, no statistics, no post-norm.
-template <typename T, int MTW, int G>
+// order through one accumulator (blocks past K multiply a zero fragment, as there), the LDS reduction over the waves in wave
+// order from 0.f, bias, then the epilogue (dec_gemm_store16, or residual + v).  The bits of the output therefore do not
+// depend on which of the kernels ran.  No split-K, no statistics, no post-norm, no fused self-attention.
+template <typename T, int EPI, int NTW, int MTP, int PASSES, int G>
 __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_rows_kernel(DecGemmParams p) {
+  constexpr bool HOLD = EPI != DEPI_BIAS_RESID;
+  static_assert(HOLD ? (EPI == DEPI_QKV || EPI == DEPI_BIAS_GELU_T) : (NTW == 1 && PASSES == 1), "rows form");
   using Ops = TypeOps<T>;
   using vec8 = typename Ops::vec8;
   extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
-  f32x4* part = (f32x4*)dg_smem;                                      // [8 waves][MTW][64]
+  f32x4* part = (f32x4*)dg_smem;                                      // [8 waves][NTW][MTP][64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nt = blockIdx.x;
-  const int mt0 = blockIdx.y * MTW;
+  const int nt0 = blockIdx.x * NTW;
+  const int n_tiles = (p.N + 15) / 16;
   const int kblocks = p.K / 32;
-  TRACE(16 + DEPI_BIAS_RESID * 2, 0);
-  // epilogue coordinates: MTW x 256 outputs over 512 threads; the residual is read now, under the weight stream
-  constexpr int NE = (MTW * 256 + DG_THREADS - 1) / DG_THREADS;
-  float resid_old[NE];
+  TRACE(16 + EPI * 2, 0);
+  // epilogue coordinates: NTW x MTP x 256 outputs of a pass over 512 threads
+  constexpr int NE = (NTW * MTP * 256 + DG_THREADS - 1) / DG_THREADS;
+  [[maybe_unused]] float resid_old[NE];
+  if constexpr (!HOLD) {
+    // the residual is read now, under the weight stream
 #pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    const int idx = tid + DG_THREADS * i, ll = (idx >> 2) & 63;
-    const int m = (mt0 + (idx >> 8)) * 16 + (ll & 15), n = nt * 16 + 4 * (ll >> 4) + (idx & 3);
-    resid_old[i] = (idx < MTW * 256 && m < p.M && n < p.N) ? ((const float*)p.out)[(int64_t)m * p.ld_out + n] : 0.f;
+    for (int i = 0; i < NE; ++i) {
+      const int idx = tid + DG_THREADS * i, ll = (idx >> 2) & 63;
+      const int m = (blockIdx.y * MTP + (idx >> 8)) * 16 + (ll & 15), n = nt0 * 16 + 4 * (ll >> 4) + (idx & 3);
+      resid_old[i] = (idx < MTP * 256 && m < p.M && n < p.N) ? ((const float*)p.out)[(int64_t)m * p.ld_out + n] : 0.f;
+    }
   }
-  const vec8* wt = (const vec8*)p.w + (int64_t)nt * kblocks * 64 + lane;
-  // activation tiles: k-block kk of the 16-row tile mt is the 1 KiB at ((mt * kblocks + kk) * 64 + lane) * 8 elements
-  const T* x0 = (const T*)p.x + ((int64_t)mt0 * kblocks * 64 + lane) * 8;
-  bool ok[MTW];
+  // fragment-tile pointers of this workgroup's n-tiles
+  const vec8* wt[NTW];
 #pragma unroll
-  for (int q = 0; q < MTW; ++q) ok[q] = (mt0 + q) * 16 + (lane & 15) < p.M;
-  f32x4 acc[MTW];
+  for (int t = 0; t < NTW; ++t) {
+    int nt = nt0 + t;
+    if (nt > n_tiles - 1) nt = n_tiles - 1;   // ragged last workgroup: recompute the last tile, never stored
+    wt[t] = (const vec8*)p.w + (int64_t)nt * kblocks * 64 + lane;
+  }
+  constexpr int UL = DG_LN_MAXK / 32 / DG_WAVES;   // 5
+  [[maybe_unused]] vec8 whold[HOLD ? NTW : 1][UL];
+  if constexpr (HOLD) {
 #pragma unroll
-  for (int q = 0; q < MTW; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < UL; ++u) {
+      int kk = wave + DG_WAVES * u;
+      if (kk > kblocks - 1) kk = kblocks - 1;
+#pragma unroll
+      for (int t = 0; t < NTW; ++t) whold[t][u] = __builtin_nontemporal_load(&wt[t][(int64_t)kk * 64]);
+    }
+  }
 
-  auto run = [&](auto ucount, int kb) {
-    constexpr int U = decltype(ucount)::value;
-    constexpr int GG = U < G ? U : G;
-    static_assert(U % GG == 0, "U");
-    vec8 w[U];
+#pragma unroll 1
+  for (int pass = 0; pass < PASSES; ++pass) {
+    const int mt0 = (blockIdx.y * PASSES + pass) * MTP;
+    if (mt0 * 16 >= p.M) break;                  // (the whole workgroup: a pass without a row)
+    // activation tiles: k-block kk of the 16-row tile mt is the 1 KiB at ((mt * kblocks + kk) * 64 + lane) * 8 elements
+    [[maybe_unused]] const T* x0 = (const T*)p.x + ((int64_t)mt0 * kblocks * 64 + lane) * 8;
+    bool ok[MTP];
 #pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = __builtin_nontemporal_load(&wt[(int64_t)(kb + DG_WAVES * u) * 64]);
+    for (int q = 0; q < MTP; ++q) ok[q] = (mt0 + q) * 16 + (lane & 15) < p.M;
+    f32x4 acc[NTW][MTP];
 #pragma unroll
-    for (int g = 0; g < U; g += GG) {
-      // lanes whose row lies past M stay zero and load nothing (one exec-masked batch of loads per m-tile)
-      vec8 a[MTW][GG];
+    for (int t = 0; t < NTW; ++t)
 #pragma unroll
-      for (int q = 0; q < MTW; ++q) {
+      for (int q = 0; q < MTP; ++q) acc[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    if constexpr (HOLD) {
+      // every fragment load is unconditional (the m-tile and the k-block clamped into the image) and all are in flight at
+      // once; lanes whose row lies past M and k-blocks past K are then zeroed in place (and-masks: dec_gemm_kernel's LN
+      // body zeroes the same fragments by register selects)
+      typedef __attribute__((ext_vector_type(4))) unsigned u32v4;
+      const int mt_last = (p.M - 1) >> 4;
+      u32v4 a32[MTP][UL];
 #pragma unroll
-        for (int u = 0; u < GG; ++u)
+      for (int q = 0; q < MTP; ++q) {
+        const int mq = mt0 + q < mt_last ? mt0 + q : mt_last;
+        const T* xq = (const T*)p.x + ((int64_t)mq * kblocks * 64 + lane) * 8;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) a[q][u][e] = 0;
-        if (ok[q]) {
-#pragma unroll
-          for (int u = 0; u < GG; ++u) a[q][u] = *(const vec8*)(x0 + ((int64_t)q * kblocks + kb + DG_WAVES * (g + u)) * 512);
+        for (int u = 0; u < UL; ++u) {
+          const int kk = wave + DG_WAVES * u;
+          a32[q][u] = *(const u32v4*)(xq + (int64_t)(kk < kblocks ? kk : 0) * 512);
         }
       }
+      vec8 a[MTP][UL];
+#pragma unroll
+      for (int q = 0; q < MTP; ++q)
+#pragma unroll
+        for (int u = 0; u < UL; ++u) {
+          const unsigned keep = (ok[q] && wave + DG_WAVES * u < kblocks) ? 0xffffffffu : 0u;
+          a[q][u] = __builtin_bit_cast(vec8, a32[q][u] & keep);
+        }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int u = 0; u < GG; ++u)
+      for (int u = 0; u < UL; ++u)
 #pragma unroll
-        for (int q = 0; q < MTW; ++q) acc[q] = Ops::mfma16(w[g + u], a[q][u], acc[q]);
+        for (int t = 0; t < NTW; ++t)
+#pragma unroll
+          for (int q = 0; q < MTP; ++q) acc[t][q] = Ops::mfma16(whold[t][u], a[q][u], acc[t][q]);
+    } else {
+      auto run = [&](auto ucount, int kb) {
+        constexpr int U = decltype(ucount)::value;
+        constexpr int GG = U < G ? U : G;
+        static_assert(U % GG == 0, "U");
+        vec8 w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) w[u] = __builtin_nontemporal_load(&wt[0][(int64_t)(kb + DG_WAVES * u) * 64]);
+#pragma unroll
+        for (int g = 0; g < U; g += GG) {
+          // lanes whose row lies past M stay zero and load nothing (one exec-masked batch of loads per m-tile)
+          vec8 a[MTP][GG];
+#pragma unroll
+          for (int q = 0; q < MTP; ++q) {
+#pragma unroll
+            for (int u = 0; u < GG; ++u)
+#pragma unroll
+              for (int e = 0; e < 8; ++e) a[q][u][e] = 0;
+            if (ok[q]) {
+#pragma unroll
+              for (int u = 0; u < GG; ++u) a[q][u] = *(const vec8*)(x0 + ((int64_t)q * kblocks + kb + DG_WAVES * (g + u)) * 512);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int u = 0; u < GG; ++u)
+#pragma unroll
+            for (int q = 0; q < MTP; ++q) acc[0][q] = Ops::mfma16(w[g + u], a[q][u], acc[0][q]);
+        }
+      };
+      int kb = wave;
+      for (; kb + DG_WAVES * 19 < kblocks; kb += DG_WAVES * 20) run(std::integral_constant<int, 20>{}, kb);
+      for (; kb + DG_WAVES * 3 < kblocks; kb += DG_WAVES * 4) run(std::integral_constant<int, 4>{}, kb);
+      for (; kb < kblocks; kb += DG_WAVES) run(std::integral_constant<int, 1>{}, kb);
     }
-  };
-  int kb = wave;
-  for (; kb + DG_WAVES * 19 < kblocks; kb += DG_WAVES * 20) run(std::integral_constant<int, 20>{}, kb);
-  for (; kb + DG_WAVES * 3 < kblocks; kb += DG_WAVES * 4) run(std::integral_constant<int, 4>{}, kb);
-  for (; kb < kblocks; kb += DG_WAVES) run(std::integral_constant<int, 1>{}, kb);
 
-  TRACE(16 + DEPI_BIAS_RESID * 2, 2);
+    TRACE(16 + EPI * 2, 2);
+    // the epilogue's coordinates derive from etid, opaque and behind the MFMAs: computed once in front of the pass loop they
+    // would stay in registers next to the held weights and the fragments, and the kernel would spill
+    int etid = tid;
+    if constexpr (HOLD) {
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(etid));
+    }
+    if (pass > 0) __syncthreads();               // the previous pass's partial sums are consumed
 #pragma unroll
-  for (int q = 0; q < MTW; ++q) part[(wave * MTW + q) * 64 + lane] = acc[q];
-  __syncthreads();
-  // D layout: n = 4*(lane'>>4) + reg, m = mt*16 + (lane' & 15)
-  const float* pp = (const float*)part;
+    for (int t = 0; t < NTW; ++t)
 #pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    const int idx = tid + DG_THREADS * i, q = idx >> 8, ll = (idx >> 2) & 63, reg = idx & 3;
-    if (idx >= MTW * 256) continue;
-    float v = 0.f;
+      for (int q = 0; q < MTP; ++q) part[((wave * NTW + t) * MTP + q) * 64 + lane] = acc[t][q];
+    __syncthreads();
+    // D layout: n = 4*(lane'>>4) + reg, m = mt*16 + (lane' & 15)
+    const float* pp = (const float*)part;
 #pragma unroll
-    for (int w = 0; w < DG_WAVES; ++w) v += pp[((w * MTW + q) * 64 + ll) * 4 + reg];
-    const int m = (mt0 + q) * 16 + (ll & 15), n = nt * 16 + 4 * (ll >> 4) + reg;
-    if (m >= p.M || n >= p.N) continue;
-    if (p.bias) v += p.bias[n];
-    ((float*)p.out)[(int64_t)m * p.ld_out + n] = resid_old[i] + v;
+    for (int i = 0; i < NE; ++i) {
+      const int idx = etid + DG_THREADS * i;
+      if (idx >= NTW * MTP * 256) continue;
+      const int t = idx / (MTP * 256), q = (idx % (MTP * 256)) >> 8, ll = (idx >> 2) & 63, reg = idx & 3;
+      float v = 0.f;
+#pragma unroll
+      for (int w = 0; w < DG_WAVES; ++w) v += pp[(((w * NTW + t) * MTP + q) * 64 + ll) * 4 + reg];
+      const int m = (mt0 + q) * 16 + (ll & 15), n = (nt0 + t) * 16 + 4 * (ll >> 4) + reg;
+      if (m >= p.M || n >= p.N || nt0 + t >= n_tiles) continue;
+      if (p.bias) v += p.bias[n];
+      if constexpr (HOLD) dec_gemm_store16<T, EPI>(p, m, n, v);
+      else ((float*)p.out)[(int64_t)m * p.ld_out + n] = resid_old[i] + v;
+    }
   }
-  TRACE(16 + DEPI_BIAS_RESID * 2, 3);
+  TRACE(16 + EPI * 2, 3);
 }
 
-template <typename T, int MTW, int G>
-static int dec_gemm_rows_launch(const DecGemmParams& p, hipStream_t s) {
+template <typename T, int EPI, int NTW, int MTP, int PASSES, int G>
+static void dec_gemm_rows_launch(const DecGemmParams& p, hipStream_t s) {
   const int n_tiles = (p.N + 15) / 16, mt = (p.M + 15) / 16;
-  hipLaunchKernelGGL((dec_gemm_rows_kernel<T, MTW, G>), dim3(n_tiles, (mt + MTW - 1) / MTW), dim3(DG_THREADS), (size_t)DG_WAVES * MTW * 64 * 16, s, p);
-  return DG_SHAPE_1x6;
+  const size_t smem = (size_t)DG_WAVES * NTW * MTP * 64 * 16;
+  if (smem > 64 * 1024) ensure_dynamic_lds((const void*)dec_gemm_rows_kernel<T, EPI, NTW, MTP, PASSES, G>, 160 * 1024);
+  hipLaunchKernelGGL((dec_gemm_rows_kernel<T, EPI, NTW, MTP, PASSES, G>), dim3((n_tiles + NTW - 1) / NTW, (mt + MTP * PASSES - 1) / (MTP * PASSES)),
+                     dim3(DG_THREADS), smem, s, p);
+}
+
+// LN1 + QKV / LN2 + mlp.0 for many rows on few CUs: the LayerNorm once (dec_ln_rows_kernel into p.ln_rows), then the all-rows
+// form on the same stream
+template <typename T, int EPI, int NTW>
+static int dec_gemm_lnrows_launch(const DecGemmParams& p, hipStream_t s) {
+  const int mt = (p.M + 15) / 16;
+  hipLaunchKernelGGL((dec_ln_rows_kernel<T>), dim3(2 * mt), dim3(128), 0, s, (const float*)p.x, (T*)p.ln_rows, p.M, p.K);
+  DecGemmParams q = p;
+  q.x = p.ln_rows; q.ln = 0;
+  dec_gemm_rows_launch<T, EPI, NTW, 3, 2, 5>(q, s);
+  return NTW == 4 ? DG_SHAPE_4x6 : DG_SHAPE_5x6;
 }
 
 template <typename T, int EPI, bool LN>
@@ -734,6 +868,22 @@ static int dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
   // many rows on few CUs (a lane of the LANES schedule: 96 rows on 64 CUs): when the largest grid above would still take
   // more than two rounds of the CUs, a workgroup takes four n-tiles (QKV at 96 rows: 360 workgroups -> 180; the
   // out-projections: 240 -> 60, one round).  A tile's arithmetic does not depend on which workgroup computes it.
+  // LN1 + QKV and LN2 + mlp.0 there: when even the four-tile grid would take more than two rounds (at 96 rows on 64 CUs 60 x 3
+  // and 80 x 3 workgroups, each normalising its 32 rows again and requesting weights that two other row blocks request too), the
+  // LayerNorm runs once as a launch of its own and a workgroup takes four n-tiles (mlp.0: five, when four do not fit one
+  // round) for all rows: 60 and 64 workgroups, one round.  Only while that grid still has 32 workgroups.  The cross query
+  // (20 x 3 workgroups at 96 rows) is within two rounds and keeps the fused form.  OHW_DEC_LNROWS=0: off
+  if constexpr (LN && (EPI == DEPI_QKV || EPI == DEPI_BIAS_GELU_T)) {
+    static const int lnrows = getenv("OHW_DEC_LNROWS") ? atoi(getenv("OHW_DEC_LNROWS")) : 1;
+    if (lnrows && p.ln_rows && mt > 2 && p.K <= DG_LN_MAXK && !p.pn && p.ksplit <= 1 && !p.stat_out && !p.attn_ticket &&
+        (int64_t)((n_tiles + 3) / 4) * ((mt + 1) / 2) > 2 * cus) {
+      if (EPI == DEPI_BIAS_GELU_T && (n_tiles + 3) / 4 > cus) {
+        if ((n_tiles + 4) / 5 >= 32) return dec_gemm_lnrows_launch<T, EPI, 5>(p, s);
+      } else if ((n_tiles + 3) / 4 >= 32) {
+        return dec_gemm_lnrows_launch<T, EPI, 4>(p, s);
+      }
+    }
+  }
   static const int nt4 = getenv("OHW_DEC_NT4") ? atoi(getenv("OHW_DEC_NT4")) : 1;
   if constexpr ((LN && (EPI == DEPI_QKV || EPI == DEPI_BIAS_T || EPI == DEPI_BIAS_GELU_T)) || (!LN && (EPI == DEPI_BIAS_RESID || EPI == DEPI_LOGITS))) {
     const int64_t wgs = LN ? (int64_t)((n_tiles + 1) / 2) * ((mt + 1) / 2) : (int64_t)n_tiles * ((mt + 1) / 2);
@@ -745,7 +895,10 @@ static int dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
   if constexpr (EPI == DEPI_BIAS_RESID && !LN) {
     static const int rows = getenv("OHW_DEC_ROWS") ? atoi(getenv("OHW_DEC_ROWS")) : 1;
     if (rows && mt > 2 && p.ksplit <= 1 && !p.pn && !p.stat_out && p.K > DG_LN_MAXK && (int64_t)n_tiles * ((mt + 1) / 2) > 2 * cus)
-      return dec_gemm_rows_launch<T, 6, 4>(p, s);
+    {
+      dec_gemm_rows_launch<T, DEPI_BIAS_RESID, 1, 6, 1, 4>(p, s);
+      return DG_SHAPE_1x6;
+    }
   }
   if ((LN && n_tiles > cus) || (EPI == DEPI_LOGITS && logits_nt == 2)) return dec_gemm_launch<T, EPI, LN, 2, 2>(p, s);
   return dec_gemm_launch<T, EPI, LN, 1, 2>(p, s);

@@ -101,7 +101,7 @@ enum DecTallyGemm { DT_QKV, DT_O, DT_XQ, DT_XO, DT_FC1, DT_FC2, DT_LOGITS, DT_GE
 enum DecTallyForm { DT_PLAIN, DT_LN, DT_PN, DT_KSPLIT, DT_FORMS };
 static const char* const kDecTallyGemm[DT_GEMMS] = {"qkv", "o", "xq", "xo", "fc1", "fc2", "logits"};
 static const char* const kDecTallyForm[DT_FORMS] = {"", ".ln", ".pn", ".ks"};
-static const char* const kDecTallyShape[DG_N_SHAPES] = {"1x1", "2x1", "1x2", "2x2", "4x2", "1x6"};
+static const char* const kDecTallyShape[DG_N_SHAPES] = {"1x1", "2x1", "1x2", "2x2", "4x2", "1x6", "4x6", "5x6"};
 static const char* const kXattnTally[XA_N_VARIANTS] = {"plain", "split", "rows2", "rows3", "rows4", "group2", "group3", "group4", "group5", "group_split"};
 static const char* const kSelfAttnTally[4] = {"plain", "slots", "fused", "fused_slots"};
 
@@ -224,6 +224,7 @@ struct ohw_state {
   DevBuf xkv;      // T [2L][B][H][1500][64]
   DevBuf self_kv;  // T [L][2][B][H][n_text_ctx][64]
   DevBuf dx, dy, dq, da, df, logits;
+  DevBuf dln;                   // the LayerNorm of a step's rows, 16-bit tiles: scratch of the all-rows LN1 + QKV / LN2 + mlp.0 forms (decode.hip)
   DevBuf dx16, xstat;            // post-norm path: 16-bit tiled copy of the residual stream, per-16-column statistics
   bool postnorm = true;
   DevBuf ks_slab, ks_ticket;   // split-K partial tiles and arrival tickets of the decoder's RESID GEMMs
@@ -455,6 +456,7 @@ void state_alloc(ohw_state* st) {
   // multiplied but never stored)
   const size_t m_tiles = ((size_t)st->m_max + 31) / 32 * 32;
   st->dy.alloc(m_tiles * dt * 2, true);
+  st->dln.alloc(m_tiles * dt * 2, true);
   // post-norm decoder GEMMs (decode.hip): OHW_DEC_POSTNORM=1 (off by default: measured, no gain - the LayerNorm prologue
   // already hides under the weights' first-byte latency); never with a split-K knob (the split path
   // publishes no statistics); dt must be a multiple of 32
@@ -732,7 +734,7 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
                   const DevBuf* wsum = nullptr) {
     DecGemmParams p{};
     p.x = x; p.w = w.p; p.bias = bias.p ? bias.as<float>() : nullptr; p.out = out;
-    p.ln = ln ? 1 : 0;
+    p.ln = ln ? 1 : 0; p.ln_rows = st->dln.p;
     if (ln && pn && wsum) {       // post-norm: the 16-bit tiled residual copy in, LayerNorm applied in the epilogue
       p.x = st->dx16.p; p.ln = 0; p.pn = 1; p.n_stat = K / 16; p.stat_in = st->xstat.as<float>(); p.wsum = wsum->as<float>();
     }
@@ -764,7 +766,7 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     T* vc = kc + kv_layer;
     {  // LN1 + fused QKV projection; K/V go straight into the cache at each window's position
       DecGemmParams p{};
-      p.x = st->dx.p; p.ln = 1; p.cu_budget = st->stream_cus;
+      p.x = st->dx.p; p.ln = 1; p.ln_rows = st->dln.p; p.cu_budget = st->stream_cus;
       if (pn) { p.x = st->dx16.p; p.ln = 0; p.pn = 1; p.n_stat = d / 16; p.stat_in = st->xstat.as<float>(); p.wsum = w.sqkv.as<float>(); }
       p.w = w.wqkv.p; p.bias = w.bqkv.as<float>(); p.out = st->dq.p;
       p.M = M; p.N = 3 * d; p.K = d; p.n_new = n_new; p.ld_out = d;
@@ -3136,7 +3138,8 @@ int ohw_dbg_self_attn(int dtype, const void* q, const void* k_cache, const void*
 static_assert(OHW_DEPI_QKV == DEPI_QKV && OHW_DEPI_BIAS_T == DEPI_BIAS_T && OHW_DEPI_BIAS_GELU_T == DEPI_BIAS_GELU_T &&
               OHW_DEPI_BIAS_RESID == DEPI_BIAS_RESID && OHW_DEPI_LOGITS == DEPI_LOGITS, "ohw.h names kernels.hpp's epilogues");
 static_assert(OHW_DG_SHAPE_1x1 == DG_SHAPE_1x1 && OHW_DG_SHAPE_2x1 == DG_SHAPE_2x1 && OHW_DG_SHAPE_1x2 == DG_SHAPE_1x2 &&
-              OHW_DG_SHAPE_2x2 == DG_SHAPE_2x2 && OHW_DG_SHAPE_4x2 == DG_SHAPE_4x2 && OHW_DG_SHAPE_1x6 == DG_SHAPE_1x6, "ohw.h names kernels.hpp's shapes");
+              OHW_DG_SHAPE_2x2 == DG_SHAPE_2x2 && OHW_DG_SHAPE_4x2 == DG_SHAPE_4x2 && OHW_DG_SHAPE_1x6 == DG_SHAPE_1x6 &&
+              OHW_DG_SHAPE_4x6 == DG_SHAPE_4x6 && OHW_DG_SHAPE_5x6 == DG_SHAPE_5x6, "ohw.h names kernels.hpp's shapes");
 
 int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
   return guard([&] {
@@ -3187,7 +3190,7 @@ int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
 
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_pad = ((int64_t)a.N + 15) / 16 * 16;
-    DevBuf wf, bf, wt, ws, past;
+    DevBuf wf, bf, wt, ws, past, lnr;
     // private copies, prepared as the loader prepares a decoder linear (model.hip): fold, round + tile, row sums
     wf.alloc((size_t)a.N * a.K * 4);
     HIP_CHECK(hipMemcpyAsync(wf.p, a.w, (size_t)a.N * a.K * 4, hipMemcpyDeviceToDevice, s));
@@ -3200,6 +3203,7 @@ int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
     if (a.gamma) launch_fold_ln(wf.as<float>(), bf.as<float>(), a.gamma, a.beta, a.N, a.K, s);
     wt.alloc((size_t)n_pad * a.K * 2);
     if (pn) ws.alloc((size_t)a.N * 4);
+    if (ln) lnr.alloc(((size_t)a.M + 15) / 16 * 16 * a.K * 2);      // the LayerNorm launch of the all-rows forms
     if (a.epilogue == DEPI_QKV) dbg_upload(past, a.n_past, (size_t)windows);
     int shape = -1;
     Dispatch::run(a.dtype, [&](auto* tag) {
@@ -3207,7 +3211,7 @@ int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
       launch_repack_tiled<TT>(wf.as<float>(), wt.p, a.N, n_pad, a.K, s);
       if (pn) launch_tiled_rowsum<TT>(wt.p, ws.as<float>(), a.N, a.K, s);
       DecGemmParams p{};
-      p.x = a.x; p.ln = ln ? 1 : 0; p.w = wt.p; p.bias = own_bias ? bf.as<float>() : nullptr; p.out = a.out;
+      p.x = a.x; p.ln = ln ? 1 : 0; p.ln_rows = lnr.p; p.w = wt.p; p.bias = own_bias ? bf.as<float>() : nullptr; p.out = a.out;
       p.M = a.M; p.N = a.N; p.K = a.K; p.n_new = rows_epi ? a.n_new : 1;
       p.ld_out = a.epilogue == DEPI_QKV ? a.d_model : a.ld_out; p.cu_budget = a.cu_budget;
       if (a.epilogue == DEPI_QKV) {

@@ -109,10 +109,14 @@ struct DecGemmParams {
   void* attn_out;                   // T activation tiles [1][d_model/32][64][8]: what launch_self_attn would have written
   const int32_t* attn_slots;        // beam search: i32 [rows][n_ctx] (launch_self_attn's kv_slot), else null
   int64_t kv_bytes;                 // bytes of one layer's K (or V) cache: bound of the kernel's buffer descriptors
+  // ln != 0, QKV and BIAS_GELU_T: scratch of the all-rows forms, T tiles [ceil(M/16)][K/32][64][8] - the LayerNorm of the rows,
+  // written by a launch of its own in front of the GEMM (decode.hip, dec_ln_rows_kernel); null: those forms are not picked
+  void* ln_rows;
 };
 // the launchers below return which instantiation they launched (the state tallies them: ohw_dbg_counter); the pick itself
 // does not depend on the tally
-enum DecGemmShape { DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_SHAPE_1x6, DG_N_SHAPES };   // n-tiles x m-tiles per workgroup
+// n-tiles x m-tiles per workgroup; 4x6 / 5x6: the all-rows forms behind a LayerNorm launch (two passes of three m-tiles)
+enum DecGemmShape { DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_SHAPE_1x6, DG_SHAPE_4x6, DG_SHAPE_5x6, DG_N_SHAPES };
 template <typename T> int launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s);
 
 // x f32 [M][d] = token_embedding[tok[m]] + pos_emb[n_past[m / n_new] + m % n_new]

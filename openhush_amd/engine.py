@@ -161,7 +161,7 @@ EG_KERNEL_AUTO, EG_KERNEL_K128, EG_KERNEL_SMALL, EG_KERNEL_K256 = range(4)
 # ohw_dbg_dec_gemm: epilogues (kernels.hpp's DecEpilogue), operand forms and the work shape that ran (DecGemmShape)
 DEPI_QKV, DEPI_BIAS_T, DEPI_BIAS_GELU_T, DEPI_BIAS_RESID, DEPI_LOGITS = range(5)
 DG_FORM_PLAIN, DG_FORM_LN, DG_FORM_PN = range(3)
-DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_SHAPE_1x6 = range(6)
+DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_SHAPE_1x6, DG_SHAPE_4x6, DG_SHAPE_5x6 = range(8)
 
 OHW_DBG_SENTINEL_I32 = -7777777
 OHW_DBG_SENTINEL_F32 = -12345.0

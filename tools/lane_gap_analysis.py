@@ -13,13 +13,17 @@ from collections import defaultdict
 
 
 def short(name):
-    m = re.search(r"(cross_attn_rows_kernel|cross_attn_kernel|self_attn_lane_kernel|self_attn_kernel|dec_gemm_rows_kernel|dec_gemm_kernel|sampler_kernel|embed_kernel|gemm256_kernel|"
+    m = re.search(r"(cross_attn_rows_kernel|cross_attn_kernel|self_attn_lane_kernel|self_attn_kernel|dec_gemm_rows_kernel|dec_ln_rows_kernel|dec_gemm_kernel|sampler_kernel|embed_kernel|gemm256_kernel|"
                   r"encoder_attention_kernel|layernorm_kernel|mel_\w+_kernel|beam_\w+_kernel)", name)
     base = m.group(1) if m else name[:40]
     if base == "dec_gemm_kernel":
         m2 = re.search(r"Li(\d)ELb([01])ELi(\d)ELi(\d)", name) or re.search(r"int, E(L?), (bool|true|false), (?:E, )?(\d), (\d)", name)
         if m2:
             base += "<" + ",".join(str(g) for g in m2.groups()) + ">"
+    if base == "dec_gemm_rows_kernel":      # <EPI, NTW, MTP, PASSES, G>
+        m2 = re.search(r"Li(\d)ELi(\d)ELi(\d)ELi(\d)ELi(\d)E", name) or re.search(r", (\d), (\d), (\d), (\d), (\d)>", name)
+        if m2:
+            base += "<" + ",".join(m2.groups()) + ">"
     return base
 
 
@@ -38,7 +42,7 @@ def main():
     t_first = min(r[1] for r in rows)
     for q, lst in sorted(byq.items(), key=lambda kv: -len(kv[1])):
         lst.sort()
-        dec = [x for x in lst if x[2].startswith(("cross_attn", "self_attn", "dec_gemm", "sampler", "embed"))]
+        dec = [x for x in lst if x[2].startswith(("cross_attn", "self_attn", "dec_gemm", "dec_ln", "sampler", "embed"))]
         if len(dec) < 1000:
             print(f"queue {q}: {len(lst)} dispatches, {len(dec)} of the decoder - skipped")
             continue
