@@ -435,6 +435,71 @@ int ohw_beam_search_ex(ohw_state* st, const ohw_sample_params* p, int n_windows,
  * Set on ohw_engine_state(e) it holds for every state ohw_engine_transcribe decodes on (the schedules' lane states too). */
 int ohw_state_set_logit_bias(ohw_state* st, const float* bias, int n);
 
+/* hot phrases: a history-dependent logit boost (shallow-fusion biasing), applied on the device ahead of every sampler of every
+ * decoder.  whisper.cpp has no such option and the reference replaces strings in the finished transcript; the rule below is
+ * this project's definition.  Off by default: with no table set, every token, log-probability, counter
+ * and captured graph is what it is without the feature.
+ *   A phrase is 1..OHW_PHRASE_MAX_LEN text token ids (each in [0, eot)) with a finite fp32 boost in logit units; a table holds at
+ *   most OHW_PHRASE_MAX_PHRASES phrases: phrase i is tokens[offsets[i] .. offsets[i + 1]) with boosts[i] (offsets [n_phrases + 1]).
+ *   The table is compiled into a trie.  Only prefixes that have a continuation are nodes.  A node has a depth d in 0..15, a path
+ *   of d tokens and children (token, boost), sorted by token and unique within the node; an edge's boost is the maximum over the
+ *   phrases that pass through it.  Nodes are ordered by depth, then by path, lexicographically.  The root (depth 0) holds the
+ *   first tokens of all phrases.
+ *   Per live row and step, before the sampler sees the row: h = the row's own sampled tokens so far, tokens[0 .. n_cur) - no
+ *   prefilled context, no sot prompt; for a beam row, that beam's history in this step's view.  A node matches when d <= n_cur
+ *   and the last d entries of h equal its path (at most one node per depth).  For the matching nodes in table order and for each
+ *   child in token order, logit[token] = fl32(logit[token] + boost): nested matches add, and the result is reproducible to the bit.
+ *   A timestamp token in the history breaks a match (no path holds one); the root always matches, so first tokens are raised at
+ *   every step; there is no back-off: a boost spent on a prefix that is then abandoned is not taken back.  The row is changed in
+ *   place ahead of the filter, so the boost behaves like ohw_state_set_logit_bias's: it is applied before the division by T and is
+ *   inside sum_logprob, token_logprobs, the acceptance thresholds, beam scores and the first step's no-speech probability;
+ *   ohw_state_fetch("logits") returns the boosted row while a table is set.  Language detection reads raw rows.  The ohw_dbg_sample*
+ *   and ohw_dbg_beam_step* entries run a sampler alone, not a step: they apply no table.
+ * ohw_phrase_table: the flat trie.  The caller owns the four arrays, sized for the limits (OHW_PHRASE_MAX_NODES + 1 offsets,
+ *   OHW_PHRASE_MAX_PATH path tokens, OHW_PHRASE_MAX_EDGES children).  Nodes of depth d are depth_start[d] .. depth_start[d + 1] - 1;
+ *   the path of node n of depth d is path[path_base[d] + (n - depth_start[d]) * d ..+ d); its children are entries child_off[n] ..
+ *   child_off[n + 1] - 1 of child_tok / child_boost.
+ * ohw_phrase_table_build_host: compiles the table on the host, no device needed.  OHW_E_INVALID_ARG, the phrase named, for a
+ *   length of 0 or above 16, an id outside [0, eot), a non-finite boost; and for more than 1024 phrases.  n_phrases = 0 gives
+ *   the empty table (no nodes).
+ * ohw_phrase_boost_host: the rule on one row on the host: history [>= n_cur], row [n_vocab] changed in place.
+ * ohw_state_set_phrase_table: compiles the table (eot = the model's) and sets it on the state for every later ohw_greedy*,
+ *   ohw_sample_pass, ohw_sample_pass_n and ohw_beam_search* call; n_phrases = 0 clears it.  The device copy is a fixed set of
+ *   buffers sized for the limits (about 0.7 MB), allocated on the first set: swapping tables captures no graph again, while "a
+ *   table is set" is part of the step-graph keys.  ohw_state_phrase_count: phrases of the table in effect (0: none).
+ * ohw_dbg_phrase_boost: test entry, the kernel once on caller data: logits [rows][ld] (host; read and written back whole, so a
+ *   test sees every word the kernel may have touched, guard columns and guard rows included), histories [rows][max_tokens],
+ *   n_cur [rows] in 0..max_tokens, done [rows], a table; n_vocab <= ld and every child token below n_vocab are checked first.
+ *   The state's own table, if any, is in effect again afterwards.
+ * ohw_engine_set_hot_phrases: texts[i] is tokenised with ohw_tokenize in two variants, with a leading space (the mid-sentence
+ *   form) and as given (the window-start form), duplicates and forms without a token dropped (a text with no token at all:
+ *   OHW_E_INVALID_ARG, the text named); boosts NULL = 1.0 each; n = 0 clears.  ohw_tokenize is a
+ *   greedy longest-match and not BPE merging, so it may split a word otherwise than the model's own tokenizer would:
+ *   ohw_engine_set_hot_phrases_tokens (phrase i = tokens[offsets[i] .. offsets[i + 1])) is the exact form.  The engine sets the
+ *   table on its own, pipeline and lane states, states made later included, and its host-sampled ladder applies the same rule.
+ *   ohw_pool_set_hot_phrases: the text form on every engine of the pool.                                                      */
+#define OHW_PHRASE_MAX_LEN 16
+#define OHW_PHRASE_MAX_PHRASES 1024
+#define OHW_PHRASE_MAX_NODES (1 + OHW_PHRASE_MAX_PHRASES * (OHW_PHRASE_MAX_LEN - 1))
+#define OHW_PHRASE_MAX_EDGES (OHW_PHRASE_MAX_PHRASES * OHW_PHRASE_MAX_LEN)
+#define OHW_PHRASE_MAX_PATH (OHW_PHRASE_MAX_PHRASES * (OHW_PHRASE_MAX_LEN - 1) * OHW_PHRASE_MAX_LEN / 2)
+typedef struct {
+  int32_t n_phrases, n_nodes, n_edges, n_path;
+  int32_t depth_start[OHW_PHRASE_MAX_LEN + 1];
+  int32_t path_base[OHW_PHRASE_MAX_LEN];
+  int32_t* child_off;   /* [OHW_PHRASE_MAX_NODES + 1] */
+  int32_t* path;        /* [OHW_PHRASE_MAX_PATH] */
+  int32_t* child_tok;   /* [OHW_PHRASE_MAX_EDGES] */
+  float* child_boost;   /* [OHW_PHRASE_MAX_EDGES] */
+} ohw_phrase_table;
+int ohw_phrase_table_build_host(const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases, int eot,
+                                ohw_phrase_table* out);
+int ohw_phrase_boost_host(const ohw_phrase_table* table, const int32_t* history, int n_cur, float* row, int n_vocab);
+int ohw_state_set_phrase_table(ohw_state* st, const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases);
+int ohw_state_phrase_count(const ohw_state* st);
+int ohw_dbg_phrase_boost(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                         const int32_t* n_cur, const int32_t* done, const ohw_phrase_table* table);
+
 /* the persistent small-batch decoder step (default OFF; OHW_DEC_PERSIST=1 turns it on for new states): single-token steps
  * of at most 16 rows - one utterance, the K rows of a beam search - run their 32 layers as ONE launch whose workgroups hand
  * activations to each other (openhush_amd/csrc/decode_persist.hip) instead of 8 launches per layer.  Correct (tests/
@@ -809,6 +874,9 @@ int ohw_engine_set_audio_ctx(ohw_engine* e, int n);
  * T >= 0.5 and set again for the next batch.  Off by default: with no prompt ever set nothing takes a new path.             */
 int ohw_engine_set_initial_prompt(ohw_engine* e, const char* text);
 int ohw_engine_set_initial_prompt_tokens(ohw_engine* e, const int32_t* tokens, int n);
+/* hot phrases on every state the engine decodes on (ohw_state_set_phrase_table states the rule and both forms) */
+int ohw_engine_set_hot_phrases(ohw_engine* e, const char* const* texts, const float* boosts, int n);
+int ohw_engine_set_hot_phrases_tokens(ohw_engine* e, const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases);
 /* carried context in the seek loops (whisper.cpp's prompt_past / n_max_text_ctx, as recalled): max_tokens 0 (default) = off,
  * -1 = on with the full cap of ohw_prompt_clip_host, n > 0 = on with at most n tokens (whisper.cpp's --max-context); below -1:
  * OHW_E_INVALID_ARG.  It applies to OHW_WINDOW_SEEK in ohw_engine_transcribe and to ohw_engine_transcribe_long_batch, one
@@ -966,6 +1034,7 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
  * windows w, w + n, ... from it (in FIXED_RECORDING_MEL from the recording-wide spectrogram).                              */
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
 int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text);           /* ohw_engine_set_initial_prompt on every engine */
+int ohw_pool_set_hot_phrases(ohw_pool* p, const char* const* texts, const float* boosts, int n);   /* ohw_engine_set_hot_phrases on every engine */
 int ohw_pool_set_best_of(ohw_pool* p, int n);                             /* ohw_engine_set_best_of on every engine */
 int ohw_pool_set_carry_context(ohw_pool* p, int max_tokens);              /* ohw_engine_set_carry_context on every engine */
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
@@ -993,6 +1062,8 @@ int ohw_abi_version(void);
 /* "mel_t" [B][3002][128]: the 16-bit time-major image conv1 reads, pad rows and channels included; */
 /* "sample_slots" [batch][n_text_ctx]: the kv_slot table of the last ohw_sample_pass_n, batch = its   */
 /* n_windows * best_of rows (entries are cache row indices, exact in f32)                            */
+/* "logits" [batch][n_vocab]: the first batch decoder rows (at most max_batch) of the last decoder   */
+/* step's logits as its sampler saw them: the hot-phrase boost included while a table is set         */
 int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int64_t out_elems);
 /* 64-bit digest of the index-th resident weight buffer (engine layout); returns OHW_E_INVALID_ARG  */
 /* past the last buffer.  Lets tests prove "synthetic ctx == ctx loaded from the synthetic file".  */
@@ -1109,6 +1180,7 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  *   "xattn.group2" .. "xattn.group5"   the same for 2..5 beams of a window; "xattn.group_split": beams, keys cut
  *   "self_attn.plain" / ".slots"       masked self-attention, without / with the beam kv_slot table; ".fused" /
  *                                      ".fused_slots": the same inside the QKV launch (OHW_DEC_FUSE_ATTN=1)
+ *   "phrase_boost"                     launches of the hot-phrase kernel (ohw_state_set_phrase_table); 0 with no table
  * The persistent step (ohw_state_set_persistent) counts only its logits GEMM.                                    */
 int ohw_dbg_counter(const ohw_state* st, const char* name);
 

@@ -163,6 +163,19 @@ def main(argv=None) -> int:
     return _transcribe_one(args)
 
 
+def _read_hot_phrases(args):
+    """--hot-phrases FILE with --hot-phrase-boost X -> (phrases, boosts), () without the option, None after an error message"""
+    if not args.hot_phrases:
+        return ()
+    from . import engine as E
+    try:
+        with open(args.hot_phrases, encoding="utf-8") as f:
+            return E.parse_hot_phrases(f.read(), args.hot_phrase_boost)
+    except (OSError, ValueError) as ex:
+        print(f"error: --hot-phrases: {ex}", file=sys.stderr)
+        return None
+
+
 def _add_transcribe_options(t):
     t.add_argument("--model-path", required=True, help="ggml-*.bin model file")
     t.add_argument("--model", default=None, help="name printed in the JSON (default: derived from the file name)")
@@ -183,6 +196,11 @@ def _add_transcribe_options(t):
                         "(320 samples each; audio past them is an error, never dropped); auto: sized to a recording of at most 30 s")
     t.add_argument("--prompt", default="", metavar="TEXT",
                    help="initial prompt (whisper.cpp's initial_prompt): names, jargon and spelling hints every window is decoded behind")
+    t.add_argument("--hot-phrases", default=None, metavar="FILE",
+                   help="hot phrases (names, product terms): one phrase per line, optionally a tab and its boost in logit units. While a "
+                        "window's own tokens end in the front part of a phrase, its next token is raised by the boost")
+    t.add_argument("--hot-phrase-boost", type=float, default=2.0, metavar="X",
+                   help="the boost of every --hot-phrases line that carries none (default 2.0)")
     t.add_argument("--packed-encoder", action="store_true",
                    help="run the encoder on the sum of the windows' contexts when a batch carries per-window contexts (the engine's "
                         "transcribe_batch under --audio-ctx auto); same output, default off")
@@ -290,6 +308,9 @@ def _transcribe_many(args) -> int:
     except ValueError:
         print("error: transcribe-many runs every window at the full audio context; --audio-ctx does not apply", file=sys.stderr)
         return 1
+    hot = _read_hot_phrases(args)
+    if hot is None:
+        return 1
     audios = []
     for f in args.files:
         if not os.path.isfile(f):
@@ -308,6 +329,8 @@ def _transcribe_many(args) -> int:
     print(f"Model loaded in {1e3 * (time.perf_counter() - t0):.0f}ms", file=sys.stderr)
     if args.prompt:
         eng.set_initial_prompt(args.prompt)
+    if hot:
+        eng.set_hot_phrases(*hot)
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
     if args.best_of > 1:
@@ -356,6 +379,9 @@ def _transcribe_one(args) -> int:
     except ValueError:
         print(f"error: --audio-ctx takes 0, a positive number or 'auto', not '{args.audio_ctx}'", file=sys.stderr)
         return 1
+    hot = _read_hot_phrases(args)
+    if hot is None:
+        return 1
     if not os.path.isfile(args.file):            # reference src/main.rs:985-987 and tests/cli_integration.rs:262-269
         print(f"error: File not found: {args.file}", file=sys.stderr)
         return 1
@@ -371,6 +397,9 @@ def _transcribe_one(args) -> int:
         if args.prompt:
             print("error: --prompt is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
             return 1
+        if hot:
+            print("error: --hot-phrases is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+            return 1
         return _transcribe_ranks(args, audio)
     use_gpu = args.device.lower() != "cpu"                    # reference src/main.rs:1037
     dev = int(args.device.split(":")[1]) if ":" in args.device else 0
@@ -384,6 +413,8 @@ def _transcribe_one(args) -> int:
         eng.set_audio_ctx(audio_ctx)
     if args.prompt:
         eng.set_initial_prompt(args.prompt)
+    if hot:
+        eng.set_hot_phrases(*hot)
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
     if args.best_of > 1:

@@ -118,10 +118,11 @@ struct GraphKey {
   int t_len = 0;       // audio context: a captured kernel argument
   bool var = false, invariant = false, persist = false;     // per-window contexts, the cross-attention variant rule, the persistent step
   bool flag = false;   // step cache: a temperature pass; beam cache: log-probability history on (other pointers baked in)
+  bool phrases = false;   // a hot-phrase table is set: the iteration holds the boost kernel (which table is device data)
   SamplerParams spar;  // compared byte by byte: fill_sampler zeroes the struct, padding included, before it fills it
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && group == o.group && cus == o.cus && t_len == o.t_len && var == o.var && invariant == o.invariant &&
-           persist == o.persist && flag == o.flag && std::memcmp(&spar, &o.spar, sizeof spar) == 0;
+           persist == o.persist && flag == o.flag && phrases == o.phrases && std::memcmp(&spar, &o.spar, sizeof spar) == 0;
   }
 };
 // one entry = the graph of a key's iteration, or the PAIR of a key whose iterations alternate between two forms (beam search:
@@ -263,6 +264,15 @@ struct ohw_state {
   DevBuf logit_bias;               // optional f32 [n_vocab] (ohw_state_set_logit_bias)
   std::vector<float> bias_host;    // the same on the host: the temperature ladder samples there (host_engine.cpp)
   bool bias_on = false;
+  // hot phrases (ohw_state_set_phrase_table): the flat trie in one fixed-size device buffer (kernels.hpp, PH_WORDS), made at the
+  // first set; ph_host: the same table on the host (the engine's host-sampled ladder applies it there) with the arrays it
+  // points into; ph_src_*: the phrases as they were given (the engine hands them on to its other states)
+  DevBuf ph_table;
+  bool ph_on = false;
+  ohw_phrase_table ph_host{};
+  std::vector<int32_t> ph_child_off, ph_path, ph_child_tok, ph_src_tok, ph_src_off;
+  std::vector<float> ph_child_boost, ph_src_boost;
+  int64_t tally_phrase = 0;        // phrase_boost_kernel launches (ohw_dbg_counter "phrase_boost"), counted like the tallies above
   int m_max = 0;
   int64_t logits_ld = 0;
   // per-kernel-class profiling (bench): event pairs around every launch of one class
@@ -349,7 +359,7 @@ namespace {
 GraphKey graph_key(const ohw_state* st, int rows, int group, bool flag, const SamplerParams& spar) {
   GraphKey k;
   k.rows = rows; k.group = group; k.cus = st->stream_cus; k.t_len = st->enc_ctx; k.var = st->enc_var; k.invariant = st->batch_invariant;
-  k.persist = st->persist; k.flag = flag;
+  k.persist = st->persist; k.flag = flag; k.phrases = st->ph_on;
   std::memcpy(&k.spar, &spar, sizeof spar);
   return k;
 }
@@ -922,6 +932,16 @@ void fill_sampler(const ohw_state* st, const ohw_sample_params* sp, int B, Sampl
   p->n_max = sp->n_max; p->force_len = sp->force_len; p->n_text_ctx = c->hp.n_text_ctx;
 }
 
+// the hot-phrase boost ahead of a sampler launch (kernels.hpp states the row mapping); nothing without a table
+void boost_rows(ohw_state* st, const SamplerParams& p, int rows, int row_mul, int group, const int32_t* n_cur, const int32_t* done, hipStream_t s) {
+  if (!st->ph_on) return;
+  PhraseBoostParams b{};
+  b.logits = st->logits.as<float>(); b.ld = p.ld; b.n_vocab = p.n_vocab; b.max_tokens = p.max_tokens; b.row_mul = row_mul; b.group = group;
+  b.tokens = p.tokens; b.n_cur = n_cur; b.done = done; b.table = st->ph_table.as<int32_t>();
+  launch_phrase_boost(b, rows, s);
+  ++st->tally_phrase;
+}
+
 int build_prompt(const ohw_ctx* c, const ohw_sample_params* sp, int32_t* out) {
   int n = 0;
   out[n++] = c->tok.sot;
@@ -1201,6 +1221,13 @@ void state_drop_recording(ohw_state* st) {
   st->rec_n = 0;
 }
 const float* state_bias_host(const ohw_state* st) { return st && st->bias_on && !st->bias_host.empty() ? st->bias_host.data() : nullptr; }
+// the host's view of a state's hot phrases: the table in effect (null: none) and the phrases as they were given
+const ohw_phrase_table* state_phrase_table_host(const ohw_state* st) { return st && st->ph_on ? &st->ph_host : nullptr; }
+int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts) {
+  if (!st || !st->ph_on) return 0;
+  *tokens = st->ph_src_tok.data(); *offsets = st->ph_src_off.data(); *boosts = st->ph_src_boost.data();
+  return st->ph_host.n_phrases;
+}
 }
 extern "C" {
 const ohw_ctx* ohw_state_ctx(const ohw_state* st) { return st ? st->ctx : nullptr; }
@@ -1626,6 +1653,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
       HIP_CHECK(hipStreamSynchronize(s));  // np, the prompt rows (and a temperature pass's done0, n_done0, T, draws) are stack-lifetime sources
       ++steps;
       auto sample = [&](hipStream_t q) {
+        boost_rows(st, spar, batch, 1, 1, spar.n_cur, spar.done, q);
         if (tp) launch_sampler_t(spar, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
         else launch_sampler(spar, q);
       };
@@ -1732,10 +1760,12 @@ static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W,
       st->sn_rows = R;
       HIP_CHECK(hipStreamSynchronize(s));                         // the vectors above and the prompt rows are stack-lifetime sources
       spar.advance = 0;
+      boost_rows(st, spar, W, 1, 1, nullptr, d_wdone, s);         // the candidates share the window's prompt row and their histories are empty: once per window
       launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);   // first token of every row from its window's prompt logits
       spar.advance = 1;
       auto iteration = [&](int, hipStream_t q) {
         run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
+        boost_rows(st, spar, R, 1, 1, spar.n_cur, spar.done, q);
         launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
       };
       const bool use_graph = st->graphs_enabled && st->prof_class == 0 && s != nullptr;
@@ -1848,6 +1878,7 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
       ++steps;
       SamplerParams p0; BeamParams b0;
       params(0, &p0, &b0);
+      boost_rows(st, p0, W, K, K, b0.n_cur, b0.win_done, s);
       launch_beam_step(p0, b0, W, 1, s);                          // first candidates from the prompt's logits; writes side 1
       // one beam iteration = {decoder step of the W * K rows, top-k per row, update per window}; the token-history and
       // kv_slot double buffers alternate, so TWO graphs are captured (odd and even steps) and replayed in turn
@@ -1859,6 +1890,7 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
           params(q, &pq, &bq);
           run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), K, bq.kv_slot, bq.win_done);
           BMARK("decoder step captured", q);
+          boost_rows(st, pq, R, 1, K, bq.n_cur, bq.win_done, cap);     // each beam's history in this step's half of the double buffer
           launch_beam_step(pq, bq, W, 0, cap);
           BMARK("beam step captured", q);
         });
@@ -1874,6 +1906,7 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
           SamplerParams pq; BeamParams bq;
           params(q, &pq, &bq);
           run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), K, bq.kv_slot, bq.win_done);
+          boost_rows(st, pq, R, 1, K, bq.n_cur, bq.win_done, s);
           launch_beam_step(pq, bq, W, 0, s);
         }
       });
@@ -1962,6 +1995,7 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "group_graphs") return (int)st->group_graphs.entries.size();
   if (n == "persist_launches") return st->persist_launches;
   if (n == "xattn.chunk") return (int)std::min<int64_t>(st->tally_xchunk, INT32_MAX);
+  if (n == "phrase_boost") return (int)std::min<int64_t>(st->tally_phrase, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
   auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
   for (int g = 0; g < DT_GEMMS; ++g)
@@ -2215,6 +2249,72 @@ int ohw_state_set_logit_bias(ohw_state* st, const float* bias, int n) {
     HIP_CHECK(hipMemcpy(st->logit_bias.p, bias, (size_t)n * 4, hipMemcpyHostToDevice));
     st->bias_host.assign(bias, bias + n);
     st->bias_on = true;
+  });
+}
+
+static void phrase_upload(ohw_state* st, const ohw_phrase_table* t, int n_vocab) {
+  std::vector<int32_t> words;
+  phrase_table_pack(t, n_vocab, &words);
+  if (!st->ph_table.p) st->ph_table.alloc((size_t)PH_WORDS * 4, true);
+  HIP_CHECK(hipMemcpy(st->ph_table.p, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+}
+
+int ohw_state_set_phrase_table(ohw_state* st, const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    if (n_phrases == 0) { st->ph_on = false; return; }
+    // built aside first: a refused table leaves the one in effect as it was
+    std::vector<int32_t> child_off((size_t)OHW_PHRASE_MAX_NODES + 1), path((size_t)OHW_PHRASE_MAX_PATH), child_tok((size_t)OHW_PHRASE_MAX_EDGES);
+    std::vector<float> child_boost((size_t)OHW_PHRASE_MAX_EDGES);
+    ohw_phrase_table t{};
+    t.child_off = child_off.data(); t.path = path.data(); t.child_tok = child_tok.data(); t.child_boost = child_boost.data();
+    phrase_table_build_host(tokens, offsets, boosts, n_phrases, st->ctx->tok.eot, &t);
+    phrase_upload(st, &t, st->ctx->hp.n_vocab);
+    st->ph_child_off.swap(child_off); st->ph_path.swap(path); st->ph_child_tok.swap(child_tok); st->ph_child_boost.swap(child_boost);
+    st->ph_host = t;
+    st->ph_src_tok.assign(tokens, tokens + offsets[n_phrases]);
+    st->ph_src_off.assign(offsets, offsets + n_phrases + 1);
+    st->ph_src_boost.assign(boosts, boosts + n_phrases);
+    st->ph_on = true;
+  });
+}
+
+int ohw_state_phrase_count(const ohw_state* st) { return st && st->ph_on ? st->ph_host.n_phrases : 0; }
+
+// test entry: phrase_boost_kernel once on caller data (include/ohw.h).  Everything is range-checked first: the kernel indexes
+// with these values
+int ohw_dbg_phrase_boost(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                         const int32_t* n_cur, const int32_t* done, const ohw_phrase_table* table) {
+  return guard([&] {
+    if (!st || !logits || !histories || !n_cur || !done || !table) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (rows < 1 || rows > 4096 || n_vocab < 1 || ld < n_vocab || max_tokens < 1 || max_tokens > 65536) throw Error(OHW_E_INVALID_ARG, "dbg_phrase_boost: bad shape");
+    for (int r = 0; r < rows; ++r)
+      if (n_cur[r] < 0 || n_cur[r] > max_tokens) throw Error(OHW_E_INVALID_ARG, "dbg_phrase_boost: n_cur out of range");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    HIP_CHECK(hipStreamSynchronize(s));
+    struct Restore {       // the state's own table is in effect again afterwards, also when a step below throws
+      ohw_state* st;
+      ~Restore() {
+        if (!st->ph_on) return;
+        try { phrase_upload(st, &st->ph_host, st->ctx->hp.n_vocab); } catch (...) { st->ph_on = false; }
+      }
+    } restore{st};
+    phrase_upload(st, table, n_vocab);
+    DevBuf d_logits, d_hist, d_ncur, d_done;
+    d_logits.alloc((size_t)rows * ld * 4); d_hist.alloc((size_t)rows * max_tokens * 4); d_ncur.alloc((size_t)rows * 4); d_done.alloc((size_t)rows * 4);
+    HIP_CHECK(hipMemcpyAsync(d_logits.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_hist.p, histories, (size_t)rows * max_tokens * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_ncur.p, n_cur, (size_t)rows * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_done.p, done, (size_t)rows * 4, hipMemcpyHostToDevice, s));
+    PhraseBoostParams b{};
+    b.logits = d_logits.as<float>(); b.ld = ld; b.n_vocab = n_vocab; b.max_tokens = max_tokens; b.row_mul = 1; b.group = 1;
+    b.tokens = d_hist.as<int32_t>(); b.n_cur = d_ncur.as<int32_t>(); b.done = d_done.as<int32_t>(); b.table = st->ph_table.as<int32_t>();
+    launch_phrase_boost(b, rows, s);
+    HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
   });
 }
 
@@ -2760,6 +2860,13 @@ int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int6
       HIP_CHECK(hipMemcpyAsync(tab.data(), st->sn_slot.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       for (int64_t i = 0; i < n; ++i) out[i] = (float)tab[(size_t)i];
+      return;
+    }
+    if (std::string(what) == "logits") {            // decoder rows, not windows: the first `batch` rows as the last step and its sampler left them
+      if (batch < 1 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "fetch: logits holds at most max_batch rows");
+      if (out_elems < (int64_t)batch * hp.n_vocab) throw Error(OHW_E_INVALID_ARG, "fetch: output buffer too small");
+      HIP_CHECK(hipMemcpy2DAsync(out, (size_t)hp.n_vocab * 4, st->logits.p, (size_t)st->logits_ld * 4, (size_t)hp.n_vocab * 4, (size_t)batch, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
       return;
     }
     if (batch < 1 || batch > st->enc_batch) throw Error(OHW_E_INVALID_ARG, "fetch: batch exceeds the last encode");

@@ -753,6 +753,52 @@ int ohw_engine_set_initial_prompt(ohw_engine* e, const char* text) {
   return ohw_engine_set_initial_prompt_tokens(e, toks.data(), n);
 }
 
+int ohw_engine_set_hot_phrases_tokens(ohw_engine* e, const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases) {
+  return guard([&] {
+    if (!e || n_phrases < 0 || (n_phrases > 0 && (!tokens || !offsets))) throw Error(OHW_E_INVALID_ARG, "hot phrases: bad argument");
+    const std::vector<float> ones((size_t)n_phrases, 1.0f);
+    if (!boosts) boosts = ones.data();
+    // the engine's own state first: a table it refuses reaches no other state
+    const int rc = ohw_state_set_phrase_table(e->state, tokens, offsets, boosts, n_phrases);
+    if (rc != OHW_OK) throw Error(rc, g_last_error);
+    each_state(e, [&](ohw_state* st) {
+      if (st == e->state) return;
+      const int rc2 = ohw_state_set_phrase_table(st, tokens, offsets, boosts, n_phrases);
+      if (rc2 != OHW_OK) throw Error(rc2, g_last_error);
+    });
+  });
+}
+int ohw_engine_set_hot_phrases(ohw_engine* e, const char* const* texts, const float* boosts, int n) {
+  if (!e || n < 0 || (n > 0 && !texts)) return OHW_E_INVALID_ARG;
+  // every phrase in two variants, duplicates dropped: " text" (mid-sentence) and "text" (window start)
+  std::vector<int32_t> toks, offs{0};
+  std::vector<float> bs;
+  std::vector<std::vector<int32_t>> seen;
+  for (int i = 0; i < n; ++i) {
+    if (!texts[i]) return OHW_E_INVALID_ARG;
+    const std::string given = texts[i];
+    bool any = false;
+    for (const std::string& form : {" " + given, given}) {
+      std::vector<int32_t> t(form.size() + 1);       // at most one token per byte
+      const int k = ohw_tokenize(e->ctx, form.c_str(), t.data(), (int)t.size());
+      if (k < 0) return k;
+      if (k == 0) continue;                          // nothing of this form is in the vocabulary
+      any = true;
+      t.resize((size_t)k);
+      if (std::find(seen.begin(), seen.end(), t) != seen.end()) continue;
+      seen.push_back(t);
+      toks.insert(toks.end(), t.begin(), t.end());
+      offs.push_back((int32_t)toks.size());
+      bs.push_back(boosts ? boosts[i] : 1.0f);
+    }
+    if (!any) {
+      g_last_error = "hot phrases: text " + std::to_string(i) + " has no token in this vocabulary";
+      return OHW_E_INVALID_ARG;
+    }
+  }
+  return ohw_engine_set_hot_phrases_tokens(e, toks.data(), offs.data(), bs.data(), (int)bs.size());
+}
+
 int ohw_engine_set_prefill_chunk(ohw_engine* e, int positions) {
   return guard([&] {
     if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");

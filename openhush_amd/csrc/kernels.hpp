@@ -1,5 +1,7 @@
 // kernels.hpp — launchers of the non-GEMM kernels of the hot path (gfx950).
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 namespace ohw {
@@ -271,6 +273,39 @@ struct SampGroupInit {
   unsigned* win_cnt;
 };
 void launch_sample_group_init(const SampGroupInit& q, hipStream_t s);
+
+// ---- hot phrases (phrase.hip; ohw_state_set_phrase_table) ---------------------------------------------------------------
+// The trie of include/ohw.h's ohw_phrase_table in ONE device buffer of fixed size (the limits' worth), so the pointers a
+// captured step bakes in hold for every table set later.  Offsets in 4-byte words:
+constexpr int PH_MAX_NODES = 1 + OHW_PHRASE_MAX_PHRASES * (OHW_PHRASE_MAX_LEN - 1);
+constexpr int PH_MAX_EDGES = OHW_PHRASE_MAX_PHRASES * OHW_PHRASE_MAX_LEN;
+constexpr int PH_MAX_PATH = OHW_PHRASE_MAX_PHRASES * (OHW_PHRASE_MAX_LEN - 1) * OHW_PHRASE_MAX_LEN / 2;
+constexpr int PH_OFF_DEPTH = 0;                                  // i32 [17] depth_start
+constexpr int PH_OFF_BASE = 32;                                  // i32 [16] path_base
+constexpr int PH_OFF_CHILD = 64;                                 // i32 [PH_MAX_NODES + 1] child_off
+constexpr int PH_OFF_PATH = PH_OFF_CHILD + PH_MAX_NODES + 1;     // i32 [PH_MAX_PATH]
+constexpr int PH_OFF_TOK = PH_OFF_PATH + PH_MAX_PATH;            // i32 [PH_MAX_EDGES] child_tok
+constexpr int PH_OFF_BOOST = PH_OFF_TOK + PH_MAX_EDGES;          // f32 [PH_MAX_EDGES] child_boost
+constexpr int PH_WORDS = PH_OFF_BOOST + PH_MAX_EDGES;
+// launch row r (one workgroup each) boosts logits row r with the history of decoder row h = r * row_mul, whose length and
+// done flag are those of entry h / group: n_cur[h / group] (null: every history is empty) and done[h / group].
+//   greedy, temperature and group passes: row_mul = group = 1;  the group pass's first step: the windows' rows, n_cur null
+//   beam search: group = K with the windows' n_cur and done flags; its first step: the windows' rows, row_mul = K
+struct PhraseBoostParams {
+  float* logits;            // [rows][ld], changed in place over columns [0, n_vocab)
+  int64_t ld;
+  int32_t n_vocab, max_tokens, row_mul, group;
+  const int32_t* tokens;    // [decoder rows][max_tokens]; entries at and behind n_cur are never read
+  const int32_t* n_cur;
+  const int32_t* done;
+  const int32_t* table;     // the PH_WORDS buffer
+};
+void launch_phrase_boost(const PhraseBoostParams& p, int rows, hipStream_t s);
+// the two host twins (no device): the builder and the rule that include/ohw.h defines
+void phrase_table_build_host(const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases, int eot, ohw_phrase_table* out);
+void phrase_boost_host(const ohw_phrase_table* t, const int32_t* history, int n_cur, float* row, int n_vocab);
+// the table's arrays laid out as the device buffer above (PH_WORDS words); checks every count and child token against n_vocab
+void phrase_table_pack(const ohw_phrase_table* t, int n_vocab, std::vector<int32_t>* words);
 
 // ---- per-window language (decode.hip; ohw_state_set_window_lang) -------------------------------------------------------
 constexpr int32_t LANG_PENDING = -1;   // table entry that waits for a detection (OHW_LANG_DETECT)

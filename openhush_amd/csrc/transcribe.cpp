@@ -12,6 +12,8 @@
 
 namespace ohw {
 const float* state_bias_host(const ohw_state* st);
+const ohw_phrase_table* state_phrase_table_host(const ohw_state* st);
+int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts);
 void state_share_recording(ohw_state* dst, ohw_state* src);
 void state_drop_recording(ohw_state* st);
 void state_set_graph_max_batch(ohw_state* st, int max_batch);
@@ -280,6 +282,8 @@ struct TranscribeCall {
         if (!live[(size_t)b]) continue;
         WindowRun& r = pass[(size_t)b];
         float lp = 0.f;
+        if (const ohw_phrase_table* pt = state_phrase_table_host(bt.st))     // the state's hot phrases, ahead of the bias as on the device
+          check(ohw_phrase_boost_host(pt, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V));
         if (const float* bias = state_bias_host(bt.st))          // the state's logit bias: the device sampler adds it itself
           for (int i2 = 0; i2 < V; ++i2) logits[(size_t)b * V + i2] += bias[i2];
         const int32_t t = ohw_sample_host(e->ctx, &sp, &logits[(size_t)b * V], r.tok.data(), (int)r.tok.size(), T, bt.rngs[b], &lp, &r.nosp);
@@ -756,6 +760,26 @@ void propagate_logit_bias(ohw_engine* e) {
   for (ohw_state* st : e->lane_states) same(st);
 }
 
+// the hot phrases of the engine's own state (ohw_engine_set_hot_phrases), on the states a schedule made since they were set
+void propagate_hot_phrases(ohw_engine* e) {
+  const int32_t *tok = nullptr, *off = nullptr;
+  const float* boost = nullptr;
+  const int n = state_phrases_src(e->state, &tok, &off, &boost);
+  auto same = [&](ohw_state* st) {
+    if (st == e->state) return;
+    const int32_t *tok2 = nullptr, *off2 = nullptr;
+    const float* boost2 = nullptr;
+    const int n2 = state_phrases_src(st, &tok2, &off2, &boost2);
+    if (n == 0 && n2 == 0) return;
+    if (n == n2 && std::memcmp(off, off2, (size_t)(n + 1) * 4) == 0 && std::memcmp(tok, tok2, (size_t)off[n] * 4) == 0 &&
+        std::memcmp(boost, boost2, (size_t)n * 4) == 0)
+      return;
+    check(ohw_state_set_phrase_table(st, tok, off, boost, n));
+  };
+  for (ohw_state* st : e->states) same(st);
+  for (ohw_state* st : e->lane_states) same(st);
+}
+
 void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n, int64_t win_first, int64_t win_step) {
   ohw_engine* e = tc.e;
   const FixedCuts cuts(tc, samples, n, win_first, win_step);
@@ -772,6 +796,7 @@ void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n,
   Invariant invariant(e, cuts.n_batches > 1 || (!e->wt_heads.empty() && win_step > 1));
   SharedRecording shared_recording(e, cuts.rec_mel);
   propagate_logit_bias(e);
+  propagate_hot_phrases(e);
   apply_ctx(e, call_ctx);
   if (schedule == OHW_SCHEDULE_SEQUENTIAL) cuts.sequential();
   else if (schedule == OHW_SCHEDULE_PIPELINE) cuts.pipeline();

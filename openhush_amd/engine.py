@@ -16,7 +16,7 @@ import ctypes as C
 import dataclasses
 import os
 import time
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -193,6 +193,122 @@ def beam_finish_host(K: int, state: dict, max_tokens: Optional[int] = None) -> d
     return _beam_finish(None, K, state, max_tokens)
 
 
+PHRASE_MAX_LEN, PHRASE_MAX_PHRASES = 16, 1024
+PHRASE_MAX_NODES = 1 + PHRASE_MAX_PHRASES * (PHRASE_MAX_LEN - 1)
+PHRASE_MAX_EDGES = PHRASE_MAX_PHRASES * PHRASE_MAX_LEN
+PHRASE_MAX_PATH = PHRASE_MAX_PHRASES * (PHRASE_MAX_LEN - 1) * PHRASE_MAX_LEN // 2
+
+
+class PhraseTableC(C.Structure):
+    _fields_ = [("n_phrases", C.c_int32), ("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("n_path", C.c_int32),
+                ("depth_start", C.c_int32 * (PHRASE_MAX_LEN + 1)), ("path_base", C.c_int32 * PHRASE_MAX_LEN),
+                ("child_off", C.POINTER(C.c_int32)), ("path", C.POINTER(C.c_int32)), ("child_tok", C.POINTER(C.c_int32)),
+                ("child_boost", C.POINTER(C.c_float))]
+
+
+class PhraseTable:
+    """ohw_phrase_table with the arrays it points into: the flat trie of a hot-phrase table (include/ohw.h states the layout)"""
+
+    def __init__(self):
+        self.child_off = np.zeros(PHRASE_MAX_NODES + 1, dtype=np.int32)
+        self.path = np.zeros(PHRASE_MAX_PATH, dtype=np.int32)
+        self.child_tok = np.zeros(PHRASE_MAX_EDGES, dtype=np.int32)
+        self.child_boost = np.zeros(PHRASE_MAX_EDGES, dtype=np.float32)
+        self.c = PhraseTableC()
+        self.c.child_off, self.c.path, self.c.child_tok, self.c.child_boost = _ip(self.child_off), _ip(self.path), _ip(self.child_tok), _fp(self.child_boost)
+
+    def arrays(self) -> dict:
+        """the table's used parts, copied: depth_start [17], path_base [16], child_off [n_nodes + 1], path, child_tok, child_boost"""
+        c = self.c
+        return {"n_phrases": int(c.n_phrases), "depth_start": np.array(c.depth_start[:], dtype=np.int32), "path_base": np.array(c.path_base[:], dtype=np.int32),
+                "child_off": self.child_off[:c.n_nodes + 1].copy(), "path": self.path[:c.n_path].copy(),
+                "child_tok": self.child_tok[:c.n_edges].copy(), "child_boost": self.child_boost[:c.n_edges].copy()}
+
+    def boost_host(self, history: Sequence[int], n_cur: int, row: np.ndarray) -> np.ndarray:
+        """ohw_phrase_boost_host: the rule on a copy of one row [n_vocab], history = the row's own sampled tokens"""
+        out = np.ascontiguousarray(row, dtype=np.float32).copy()
+        h = np.ascontiguousarray(list(history) or [0], dtype=np.int32)
+        _check(lib().ohw_phrase_boost_host(C.byref(self.c), _ip(h), int(n_cur), _fp(out), int(out.size)))
+        return out
+
+
+def _flat_phrases(phrases, boosts):
+    """token lists -> (tokens, offsets, boosts) as the C ABI takes them"""
+    lens = [len(p) for p in phrases]
+    off = np.zeros(len(lens) + 1, dtype=np.int32)
+    off[1:] = np.cumsum(lens, dtype=np.int64)
+    toks = np.ascontiguousarray([t for p in phrases for t in p] or [0], dtype=np.int32)
+    b = np.ascontiguousarray(list(boosts) or [0.0], dtype=np.float32)
+    if len(boosts) != len(lens):
+        raise ValueError("one boost per phrase")
+    return toks, off, b
+
+
+def phrase_table_build_host(phrases: Sequence[Sequence[int]], boosts: Sequence[float], eot: int) -> PhraseTable:
+    """ohw_phrase_table_build_host: token-id phrases with a boost each -> the flat trie; needs no device"""
+    toks, off, b = _flat_phrases(phrases, boosts)
+    t = PhraseTable()
+    _check(lib().ohw_phrase_table_build_host(_ip(toks), _ip(off), _fp(b), len(phrases), int(eot), C.byref(t.c)))
+    return t
+
+
+def parse_hot_phrases(text: str, default_boost: float) -> Tuple[List[str], List[float]]:
+    """a hot-phrase file: one phrase per line, optionally a tab and its boost; empty lines and lines starting with # are skipped"""
+    phrases, boosts = [], []
+    for ln, line in enumerate(text.splitlines(), 1):
+        line = line.strip("\r\n")
+        if not line.strip() or line.lstrip().startswith("#"):
+            continue
+        phrase, tab, boost = line.partition("\t")
+        try:
+            b = float(boost) if tab and boost.strip() else float(default_boost)
+        except ValueError:
+            raise ValueError(f"hot phrases, line {ln}: the boost {boost!r} is not a number") from None
+        if not phrase.strip():
+            raise ValueError(f"hot phrases, line {ln}: no phrase in front of the tab")
+        phrases.append(phrase.strip())
+        boosts.append(b)
+    return phrases, boosts
+
+
+def _hot_phrase_args(phrases, boost):
+    """(strings or token lists, a boost or one per phrase) -> (is_text, phrases, boosts)"""
+    phrases = list(phrases or [])
+    boosts = [float(boost)] * len(phrases) if np.isscalar(boost) else [float(b) for b in boost]
+    if len(boosts) != len(phrases):
+        raise ValueError("hot phrases: one boost per phrase, or one for all")
+    is_text = [isinstance(p, (str, bytes)) for p in phrases]
+    if any(is_text) and not all(is_text):
+        raise ValueError("hot phrases: strings or token lists, not both in one call")
+    return bool(phrases) and is_text[0], phrases, boosts
+
+
+def hot_phrase_tokens(ctx, phrases, boost=1.0) -> Tuple[List[List[int]], List[float]]:
+    """what ohw_engine_set_hot_phrases does with its texts, for a caller that owns a State: every string in two variants, with a
+    leading space and as given, duplicates dropped; token lists pass through -> (token lists, boosts)"""
+    is_text, phrases, boosts = _hot_phrase_args(phrases, boost)
+    if not is_text:
+        return [list(p) for p in phrases], boosts
+    out, bs = [], []
+    for i, (p, b) in enumerate(zip(phrases, boosts)):
+        raw = _text_bytes(p)
+        forms = [t for t in (ctx.tokenize(b" " + raw), ctx.tokenize(raw)) if t]      # a form with no token in the vocabulary is dropped
+        if not forms:
+            raise ValueError(f"hot phrases: text {i} has no token in this vocabulary")
+        for t in forms:
+            if t not in out:
+                out.append(t)
+                bs.append(b)
+    return out, bs
+
+
+def _hot_phrase_text_call(fn, handle, phrases, boosts):
+    raw = [_text_bytes(p) for p in phrases]
+    arr = (C.c_char_p * max(len(raw), 1))(*raw)
+    b = np.ascontiguousarray(boosts or [0.0], dtype=np.float32)
+    _check(fn(handle, arr, _fp(b), len(raw)))
+
+
 class WindowQuality(C.Structure):
     _fields_ = [("n_tokens", C.c_int32), ("avg_logprob", C.c_float), ("entropy", C.c_float), ("would_fallback", C.c_int32),
                 ("temperature", C.c_float), ("no_speech_prob", C.c_float), ("no_speech", C.c_int32), ("seek_delta", C.c_int32),
@@ -287,6 +403,8 @@ EXPORTS = [
     "ohw_sample_pass_n", "ohw_dbg_sample_group", "ohw_best_of_pick_host", "ohw_engine_set_best_of", "ohw_pool_set_best_of",
     "ohw_engine_last_candidates", "ohw_engine_last_candidate_logprobs", "ohw_batch_windows_host",
     "ohw_dbg_enc_gemm",
+    "ohw_phrase_table_build_host", "ohw_phrase_boost_host", "ohw_state_set_phrase_table", "ohw_state_phrase_count", "ohw_dbg_phrase_boost",
+    "ohw_engine_set_hot_phrases", "ohw_engine_set_hot_phrases_tokens", "ohw_pool_set_hot_phrases",
 ]
 
 
@@ -568,6 +686,14 @@ def lib():
         L.ohw_lang_pick_host.argtypes = [fp, C.POINTER(SpecialTokens), ip, fp]
         L.ohw_dbg_lang_pick.argtypes = [vp, fp, C.c_int, ip, fp]
         L.ohw_dbg_counter.argtypes = [vp, C.c_char_p]
+        L.ohw_phrase_table_build_host.argtypes = [ip, ip, fp, C.c_int, C.c_int, vp]
+        L.ohw_phrase_boost_host.argtypes = [vp, ip, C.c_int, fp, C.c_int]
+        L.ohw_state_set_phrase_table.argtypes = [vp, ip, ip, fp, C.c_int]
+        L.ohw_state_phrase_count.argtypes = [vp]
+        L.ohw_dbg_phrase_boost.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, ip, C.c_int, ip, ip, vp]
+        L.ohw_engine_set_hot_phrases.argtypes = [vp, C.POINTER(C.c_char_p), fp, C.c_int]
+        L.ohw_engine_set_hot_phrases_tokens.argtypes = [vp, ip, ip, fp, C.c_int]
+        L.ohw_pool_set_hot_phrases.argtypes = [vp, C.POINTER(C.c_char_p), fp, C.c_int]
         L.ohw_dbg_beam_step.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIO)]
         L.ohw_beam_search_ex.argtypes = [vp, C.POINTER(SampleParams), C.c_int, C.c_int, C.c_int, C.POINTER(BeamResultEx)]
         L.ohw_dbg_beam_step_ex.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIOEx)]
@@ -957,6 +1083,10 @@ class Context:
             _raise(n)
         return [int(t) for t in out[:n]]
 
+    def phrase_table_build(self, phrases: Sequence[Sequence[int]], boosts: Sequence[float]) -> PhraseTable:
+        """ohw_phrase_table_build_host with the model's end-of-text id: the trie State.set_phrase_table would put on the device"""
+        return phrase_table_build_host(phrases, boosts, int(self.tok.eot))
+
     def sample_greedy_host(self, p: SampleParams, logits: np.ndarray, cur: List[int]) -> Tuple[int, float]:
         lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
         c = np.asarray(cur if len(cur) else [0], dtype=np.int32)
@@ -1245,6 +1375,25 @@ class State:
         else:
             b = np.ascontiguousarray(bias, dtype=np.float32)
             _check(lib().ohw_state_set_logit_bias(self.h, _fp(b), b.size))
+
+    def set_phrase_table(self, phrases: Optional[Sequence[Sequence[int]]], boosts: Union[float, Sequence[float]] = 1.0):
+        """ohw_state_set_phrase_table: hot phrases as token-id lists with a boost each (or one for all); None or [] clears"""
+        phrases = [list(p) for p in (phrases or [])]
+        bs = [float(boosts)] * len(phrases) if np.isscalar(boosts) else list(boosts)
+        toks, off, b = _flat_phrases(phrases, bs)
+        _check(lib().ohw_state_set_phrase_table(self.h, _ip(toks), _ip(off), _fp(b), len(phrases)))
+
+    def phrase_count(self) -> int:
+        return int(lib().ohw_state_phrase_count(self.h))
+
+    def dbg_phrase_boost(self, logits: np.ndarray, n_vocab: int, histories: np.ndarray, n_cur, done, table: PhraseTable) -> np.ndarray:
+        """ohw_dbg_phrase_boost: the kernel once on logits [rows][ld] (a copy comes back whole), histories [rows][max_tokens]"""
+        lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
+        h = np.ascontiguousarray(histories, dtype=np.int32)
+        nc, dn = np.ascontiguousarray(n_cur, dtype=np.int32), np.ascontiguousarray(done, dtype=np.int32)
+        assert lg.ndim == 2 and h.ndim == 2 and h.shape[0] == lg.shape[0] == nc.size == dn.size
+        _check(lib().ohw_dbg_phrase_boost(self.h, _fp(lg), lg.shape[0], lg.shape[1], int(n_vocab), _ip(h), h.shape[1], _ip(nc), _ip(dn), C.byref(table.c)))
+        return lg
 
     def set_audio_ctx(self, n_ctx: int):
         """ohw_state_set_audio_ctx: encoder positions per window for later mel / encode / decode calls (whisper.cpp's audio_ctx);
@@ -1628,6 +1777,11 @@ class State:
 
     def fetch(self, what: str, batch: int) -> np.ndarray:
         hp = self.ctx.hp
+        if what == "logits":
+            # the first `batch` decoder rows of the last step, as its sampler saw them (the hot-phrase boost included)
+            out = np.empty((batch, hp.n_vocab), dtype=np.float32)
+            _check(lib().ohw_state_fetch(self.h, b"logits", batch, _fp(out), out.size))
+            return out
         if what in ("align_q", "align_p", "align_m"):
             # window batch - 1 of the last align(): "align_q" [N_all][A][64], "align_p" [A][N_all][n_keys], "align_m" [N][n_keys]
             A = self._align_heads
@@ -2195,6 +2349,17 @@ class WhisperEngine:
             a = np.ascontiguousarray(list(prompt) or [0], dtype=np.int32)
             _check(lib().ohw_engine_set_initial_prompt_tokens(self.h, _ip(a), len(prompt)))
 
+    def set_hot_phrases(self, phrases, boost=1.0):
+        """ohw_engine_set_hot_phrases / _tokens: strings (each tokenised with and without a leading space) or token-id lists (the
+        exact form) whose continuation is raised by `boost` logit units - one value, or one per phrase - while a row's own history
+        ends in the front part of a phrase; None or [] clears.  Holds for every state the engine decodes on"""
+        is_text, phrases, boosts = _hot_phrase_args(phrases, boost)
+        if is_text or not phrases:
+            _hot_phrase_text_call(lib().ohw_engine_set_hot_phrases, self.h, phrases, boosts)
+        else:
+            toks, off, b = _flat_phrases([list(p) for p in phrases], boosts)
+            _check(lib().ohw_engine_set_hot_phrases_tokens(self.h, _ip(toks), _ip(off), _fp(b), len(phrases)))
+
     def set_prefill_chunk(self, positions: int):
         """ohw_engine_set_prefill_chunk: State.set_prefill_chunk on every state of the engine, those made later included"""
         _check(lib().ohw_engine_set_prefill_chunk(self.h, int(positions)))
@@ -2300,6 +2465,13 @@ class EnginePool:
 
     def set_window_mode(self, mode: int):
         _check(lib().ohw_pool_set_window_mode(self.h, mode))
+
+    def set_hot_phrases(self, phrases, boost=1.0):
+        """ohw_pool_set_hot_phrases: WhisperEngine.set_hot_phrases (the text form) on every engine of the pool; None or [] clears"""
+        is_text, phrases, boosts = _hot_phrase_args(phrases, boost)
+        if phrases and not is_text:
+            raise ValueError("EnginePool.set_hot_phrases takes strings")
+        _hot_phrase_text_call(lib().ohw_pool_set_hot_phrases, self.h, phrases, boosts)
 
     def set_initial_prompt(self, text):
         """ohw_pool_set_initial_prompt: WhisperEngine.set_initial_prompt(text) on every engine of the pool"""

@@ -134,12 +134,13 @@ class StreamingSession:
     job through mel -> encoder -> beam search or greedy -> text.  beam_size 0 = greedy; vad: callable samples -> probability
     (the VadEngine hook) with `vad_threshold`, or None.  audio_ctx: 0 (default) the full 30 s context, n a fixed reduced
     context (a window with samples past n * 320 is refused), "auto" engine.audio_ctx_for(len) for a job of at most one window -
-    a 1.1 s chunk then pays for 128 encoder positions instead of 1500 (WhisperEngine.set_audio_ctx's rule)."""
+    a 1.1 s chunk then pays for 128 encoder positions instead of 1500 (WhisperEngine.set_audio_ctx's rule).  hot_phrases: terms
+    whose continuation is raised while a window's own tokens end in their front part (WhisperEngine.set_hot_phrases)."""
 
     def __init__(self, ctx: E.Context, beam_size: int = 5, vad: Optional[Callable[[np.ndarray], float]] = None, vad_threshold: float = 0.5,
                  sequence_id: int = 1, tracker: Optional[TranscriptionTracker] = None, params: Optional[E.SampleParams] = None,
                  audio_config: Optional[E.PreprocessConfig] = None, noise_reduction: bool = False, noise_reduction_strength: float = 1.0,
-                 denoiser: Optional["E.Denoiser"] = None, audio_ctx=0, carry_context: bool = False):
+                 denoiser: Optional["E.Denoiser"] = None, audio_ctx=0, carry_context: bool = False, hot_phrases=None, hot_phrase_boost=1.0):
         self.ctx = ctx
         self.audio_ctx = E._audio_ctx_arg(audio_ctx)
         if self.audio_ctx > ctx.hp.n_audio_ctx:
@@ -160,6 +161,10 @@ class StreamingSession:
         # clipped to the last n_text_ctx / 2 - 1; carried across the jobs of the session, reset by a job the VAD skips
         self.carry_context = carry_context
         self.context: List[int] = []
+        # hot_phrases: strings (each in its two tokenisations) or token-id lists, raised by hot_phrase_boost - one value, or one
+        # per phrase - on the session's state (WhisperEngine.set_hot_phrases's rule, State.set_phrase_table)
+        if hot_phrases:
+            self.state.set_phrase_table(*E.hot_phrase_tokens(ctx, hot_phrases, hot_phrase_boost))
 
     def _text(self, tokens: List[int]) -> str:
         return b"".join(self.ctx.token_text(t) for t in tokens if t < self.ctx.tok.eot).decode("utf-8", "replace").strip()
