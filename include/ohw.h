@@ -500,6 +500,57 @@ int ohw_state_phrase_count(const ohw_state* st);
 int ohw_dbg_phrase_boost(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
                          const int32_t* n_cur, const int32_t* done, const ohw_phrase_table* table);
 
+/* repetition penalty and no-repeat n-grams: the two decode-time controls of faster-whisper / CTranslate2 (repetition_penalty,
+ * no_repeat_ngram_size) that keep a repetition loop from forming, applied on the device ahead of every sampler of every
+ * decoder.  whisper.cpp has neither.  The rule is that of transformers' RepetitionPenaltyLogitsProcessor and
+ * NoRepeatNGramLogitsProcessor, restricted to text tokens.
+ *   Two parameters per state: penalty theta (fp32) and ngram n (int).  Off is theta = 1.0 and n = 0, the default: nothing is
+ *   launched then, and every token, log-probability, counter and captured graph is what it is without the feature.  The
+ *   setter accepts OHW_REPEAT_PENALTY_MIN <= theta <= OHW_REPEAT_PENALTY_MAX and 0 <= n <= OHW_REPEAT_MAX_NGRAM, so no product
+ *   leaves fp32's range; anything else, NaN included, is OHW_E_INVALID_ARG.
+ *   Per live row and step, before the sampler sees the row - after the hot-phrase boost, ahead of the static bias and the filter,
+ *   both of which the samplers apply themselves.  h = the row's own sampled tokens so far, tokens[0 .. n_cur), exactly the history
+ *   hot phrases use: no prefilled context, no sot prompt; for a beam row, that beam's history in this step's view.
+ *   1. Penalty, if theta != 1.0: for every distinct text token t (t < eot) that occurs in h, once however often it occurs,
+ *      logit[t] = x < 0 ? fl32(x * theta) : fl32(x / theta), x the value after the phrase boost.  Timestamp tokens in h are not
+ *      penalised: a segment legitimately ends and the next begins on the same timestamp.  With theta = 1.0 the step is skipped
+ *      and no word is rewritten.
+ *   2. Ban, if n >= 1 and n_cur >= n - 1: the tail is the last n - 1 entries of h (empty for n = 1).  For every start i with
+ *      0 <= i <= n_cur - n and h[i .. i + n - 2] == tail (raw ids; timestamps take part like any token): if the follower
+ *      f = h[i + n - 1] is a text token, logit[f] = OHW_REPEAT_BAN.  The ban comes after the penalty, so a banned token stays
+ *      banned.  The constant is finite on purpose: the samplers' online log-sum-exp computes expf(v - m) with m = -inf for a
+ *      thread's first element, and -inf - -inf would poison the row; -1e30 survives the bias add and the division by T >= 0.2 and
+ *      underflows to probability 0.  Only text tokens are ever banned - end-of-text and timestamps never - so a row can always
+ *      finish.
+ *   Consequences: the modified value is inside sum_logprob, token_logprobs, the acceptance thresholds, best-of ranking and beam
+ *   scores; ohw_state_fetch("logits") returns the modified rows while the rule is on.  The first step is never touched (its
+ *   history is empty), so the no-speech probability is unchanged.  Language detection, ohw_state_align and the ohw_dbg_sample* /
+ *   ohw_dbg_beam_step* entries are untouched; the persistent step ends at the logits and needs nothing.
+ * ohw_repeat_rule_host: the rule on one row on the host, no device: history [>= n_cur], row [n_vocab] changed in place; history
+ *   entries outside [0, n_vocab) are compared like any id and never written.
+ * ohw_state_set_repeat_rule / ohw_state_repeat_rule: set and read a state's values, for every later ohw_greedy*, ohw_sample_pass,
+ *   ohw_sample_pass_n and ohw_beam_search* call.  The values live in a two-word device buffer made at the first set: "the rule
+ *   is on" is part of the step-graph keys, and a change between two settings that are both on captures nothing again.
+ * ohw_dbg_repeat_rule: test entry, the kernel once on caller data: logits [rows][ld] (host; read and written back whole, guard
+ *   columns and guard rows included), histories [n_entries * group][max_tokens], n_cur (or null: every history is empty) and done
+ *   [n_entries].  Launch row r changes logits row r with the history of row h = r * row_mul under n_cur / done [h / group]
+ *   (greedy, temperature and group passes: row_mul = group = 1; beam search: group = K, its first step row_mul = K).  Checked
+ *   before the launch: shapes, n_vocab <= ld, 0 <= eot, every n_cur in 0..max_tokens, (rows - 1) * row_mul / group < n_entries,
+ *   penalty and ngram as the setter checks them.  The state's own setting is in effect again afterwards.
+ * ohw_engine_set_repetition: the values on the engine's own state and its pipeline and lane states, states made later included;
+ *   its host-sampled ladder applies ohw_repeat_rule_host right behind ohw_phrase_boost_host.  ohw_pool_set_repetition: the same
+ *   on every engine of the pool.                                                                                              */
+#define OHW_REPEAT_BAN (-1.0e30f)
+#define OHW_REPEAT_PENALTY_MIN 0.01f
+#define OHW_REPEAT_PENALTY_MAX 100.0f
+#define OHW_REPEAT_MAX_NGRAM 32
+int ohw_repeat_rule_host(float penalty, int ngram, const int32_t* history, int n_cur, float* row, int n_vocab, int eot);
+int ohw_state_set_repeat_rule(ohw_state* st, float penalty, int ngram);
+int ohw_state_repeat_rule(const ohw_state* st, float* penalty, int* ngram);
+int ohw_dbg_repeat_rule(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                        const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int ngram,
+                        int eot);
+
 /* the persistent small-batch decoder step (default OFF; OHW_DEC_PERSIST=1 turns it on for new states): single-token steps
  * of at most 16 rows - one utterance, the K rows of a beam search - run their 32 layers as ONE launch whose workgroups hand
  * activations to each other (openhush_amd/csrc/decode_persist.hip) instead of 8 launches per layer.  Correct (tests/
@@ -877,6 +928,9 @@ int ohw_engine_set_initial_prompt_tokens(ohw_engine* e, const int32_t* tokens, i
 /* hot phrases on every state the engine decodes on (ohw_state_set_phrase_table states the rule and both forms) */
 int ohw_engine_set_hot_phrases(ohw_engine* e, const char* const* texts, const float* boosts, int n);
 int ohw_engine_set_hot_phrases_tokens(ohw_engine* e, const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases);
+/* repetition penalty and no-repeat n-gram size on every state the engine decodes on (ohw_state_set_repeat_rule states the rule);
+ * (1.0, 0), the default, is off */
+int ohw_engine_set_repetition(ohw_engine* e, float penalty, int ngram);
 /* carried context in the seek loops (whisper.cpp's prompt_past / n_max_text_ctx, as recalled): max_tokens 0 (default) = off,
  * -1 = on with the full cap of ohw_prompt_clip_host, n > 0 = on with at most n tokens (whisper.cpp's --max-context); below -1:
  * OHW_E_INVALID_ARG.  It applies to OHW_WINDOW_SEEK in ohw_engine_transcribe and to ohw_engine_transcribe_long_batch, one
@@ -1035,6 +1089,7 @@ int ohw_pool_set_fallback_device(ohw_pool* p, int on);                    /* ohw
 int ohw_pool_set_window_mode(ohw_pool* p, int mode);
 int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text);           /* ohw_engine_set_initial_prompt on every engine */
 int ohw_pool_set_hot_phrases(ohw_pool* p, const char* const* texts, const float* boosts, int n);   /* ohw_engine_set_hot_phrases on every engine */
+int ohw_pool_set_repetition(ohw_pool* p, float penalty, int ngram);       /* ohw_engine_set_repetition on every engine */
 int ohw_pool_set_best_of(ohw_pool* p, int n);                             /* ohw_engine_set_best_of on every engine */
 int ohw_pool_set_carry_context(ohw_pool* p, int max_tokens);              /* ohw_engine_set_carry_context on every engine */
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
@@ -1064,6 +1119,7 @@ int ohw_abi_version(void);
 /* n_windows * best_of rows (entries are cache row indices, exact in f32)                            */
 /* "logits" [batch][n_vocab]: the first batch decoder rows (at most max_batch) of the last decoder   */
 /* step's logits as its sampler saw them: the hot-phrase boost included while a table is set         */
+/* and the repetition rule's changes while it is on (ohw_state_set_repeat_rule)                      */
 int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int64_t out_elems);
 /* 64-bit digest of the index-th resident weight buffer (engine layout); returns OHW_E_INVALID_ARG  */
 /* past the last buffer.  Lets tests prove "synthetic ctx == ctx loaded from the synthetic file".  */
@@ -1181,6 +1237,7 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  *   "self_attn.plain" / ".slots"       masked self-attention, without / with the beam kv_slot table; ".fused" /
  *                                      ".fused_slots": the same inside the QKV launch (OHW_DEC_FUSE_ATTN=1)
  *   "phrase_boost"                     launches of the hot-phrase kernel (ohw_state_set_phrase_table); 0 with no table
+ *   "repeat_rule"                      launches of the repetition kernel (ohw_state_set_repeat_rule); 0 while the rule is off
  * The persistent step (ohw_state_set_persistent) counts only its logits GEMM.                                    */
 int ohw_dbg_counter(const ohw_state* st, const char* name);
 

@@ -120,7 +120,9 @@ def _transcribe_ranks(args, audio) -> int:
     n_win = (len(audio.samples) + E.CHUNK_SAMPLES - 1) // E.CHUNK_SAMPLES
     t1 = time.perf_counter()
     by_index = args.mel == "recording"
-    runner = shard.recording_window_runner(ctx, args.max_batch, audio.samples, p) if by_index else shard.engine_window_runner(ctx, args.max_batch, p)
+    rep = _repetition(args)             # every rank decodes its windows under the same rule
+    runner = (shard.recording_window_runner(ctx, args.max_batch, audio.samples, p, repetition=rep) if by_index
+              else shard.engine_window_runner(ctx, args.max_batch, p, repetition=rep))
     wins = shard.transcribe_sharded(runner, audio.samples, n_win, ctx.hp.n_text_ctx, dist, world, rank, torch.device("cuda", local),
                                     by_index=by_index)
     dt = time.perf_counter() - t1
@@ -201,6 +203,12 @@ def _add_transcribe_options(t):
                         "window's own tokens end in the front part of a phrase, its next token is raised by the boost")
     t.add_argument("--hot-phrase-boost", type=float, default=2.0, metavar="X",
                    help="the boost of every --hot-phrases line that carries none (default 2.0)")
+    t.add_argument("--repetition-penalty", type=_repetition_penalty_arg, default=1.0, metavar="X",
+                   help="scale the logit of every text token a window has already emitted away from the sampler (x / X above 0, "
+                        "x * X below; faster-whisper's repetition_penalty), 0.01..100; 1.0 (default): off")
+    t.add_argument("--no-repeat-ngram-size", type=_no_repeat_ngram_arg, default=0, metavar="N",
+                   help="never emit a text token that would complete an N-gram the window already holds (faster-whisper's "
+                        "no_repeat_ngram_size), 0..32; 0 (default): off")
     t.add_argument("--packed-encoder", action="store_true",
                    help="run the encoder on the sum of the windows' contexts when a batch carries per-window contexts (the engine's "
                         "transcribe_batch under --audio-ctx auto); same output, default off")
@@ -229,6 +237,31 @@ def _beam_size_arg(v: str) -> int:
     if k != 0 and not 2 <= k <= 5:
         raise argparse.ArgumentTypeError(f"takes 0 (greedy) or a beam size in 2..5, not '{v}'")
     return k
+
+
+def _repetition_penalty_arg(v: str) -> float:
+    try:
+        x = float(v)
+    except ValueError:
+        x = float("nan")
+    if not 0.01 <= x <= 100.0:                      # false for NaN
+        raise argparse.ArgumentTypeError(f"takes a penalty in 0.01..100 (1.0: off), not '{v}'")
+    return x
+
+
+def _no_repeat_ngram_arg(v: str) -> int:
+    try:
+        n = int(v)
+    except ValueError:
+        n = -1
+    if not 0 <= n <= 32:
+        raise argparse.ArgumentTypeError(f"takes an n-gram size in 0..32 (0: off), not '{v}'")
+    return n
+
+
+def _repetition(args):
+    """(--repetition-penalty, --no-repeat-ngram-size) when either is on, None when both are off"""
+    return (args.repetition_penalty, args.no_repeat_ngram_size) if args.repetition_penalty != 1.0 or args.no_repeat_ngram_size != 0 else None
 
 
 def _best_of_arg(v: str) -> int:
@@ -331,6 +364,8 @@ def _transcribe_many(args) -> int:
         eng.set_initial_prompt(args.prompt)
     if hot:
         eng.set_hot_phrases(*hot)
+    if _repetition(args):
+        eng.set_repetition(*_repetition(args))
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
     if args.best_of > 1:
@@ -415,6 +450,8 @@ def _transcribe_one(args) -> int:
         eng.set_initial_prompt(args.prompt)
     if hot:
         eng.set_hot_phrases(*hot)
+    if _repetition(args):
+        eng.set_repetition(*_repetition(args))
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
     if args.best_of > 1:

@@ -119,10 +119,11 @@ struct GraphKey {
   bool var = false, invariant = false, persist = false;     // per-window contexts, the cross-attention variant rule, the persistent step
   bool flag = false;   // step cache: a temperature pass; beam cache: log-probability history on (other pointers baked in)
   bool phrases = false;   // a hot-phrase table is set: the iteration holds the boost kernel (which table is device data)
+  bool repeat = false;    // the repetition rule is on: the iteration holds its kernel (the values are device data)
   SamplerParams spar;  // compared byte by byte: fill_sampler zeroes the struct, padding included, before it fills it
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && group == o.group && cus == o.cus && t_len == o.t_len && var == o.var && invariant == o.invariant &&
-           persist == o.persist && flag == o.flag && phrases == o.phrases && std::memcmp(&spar, &o.spar, sizeof spar) == 0;
+           persist == o.persist && flag == o.flag && phrases == o.phrases && repeat == o.repeat && std::memcmp(&spar, &o.spar, sizeof spar) == 0;
   }
 };
 // one entry = the graph of a key's iteration, or the PAIR of a key whose iterations alternate between two forms (beam search:
@@ -273,6 +274,13 @@ struct ohw_state {
   std::vector<int32_t> ph_child_off, ph_path, ph_child_tok, ph_src_tok, ph_src_off;
   std::vector<float> ph_child_boost, ph_src_boost;
   int64_t tally_phrase = 0;        // phrase_boost_kernel launches (ohw_dbg_counter "phrase_boost"), counted like the tallies above
+  // repetition penalty and no-repeat n-grams (ohw_state_set_repeat_rule): the two values on the host and in a two-word device
+  // buffer {fp32 bits of the penalty, n-gram size}, made at the first set; rp_on: they are not (1.0, 0)
+  DevBuf rp_rule;
+  float rp_penalty = 1.0f;
+  int rp_ngram = 0;
+  bool rp_on = false;
+  int64_t tally_repeat = 0;        // repeat_rule_kernel launches (ohw_dbg_counter "repeat_rule")
   int m_max = 0;
   int64_t logits_ld = 0;
   // per-kernel-class profiling (bench): event pairs around every launch of one class
@@ -359,7 +367,7 @@ namespace {
 GraphKey graph_key(const ohw_state* st, int rows, int group, bool flag, const SamplerParams& spar) {
   GraphKey k;
   k.rows = rows; k.group = group; k.cus = st->stream_cus; k.t_len = st->enc_ctx; k.var = st->enc_var; k.invariant = st->batch_invariant;
-  k.persist = st->persist; k.flag = flag; k.phrases = st->ph_on;
+  k.persist = st->persist; k.flag = flag; k.phrases = st->ph_on; k.repeat = st->rp_on;
   std::memcpy(&k.spar, &spar, sizeof spar);
   return k;
 }
@@ -932,14 +940,25 @@ void fill_sampler(const ohw_state* st, const ohw_sample_params* sp, int B, Sampl
   p->n_max = sp->n_max; p->force_len = sp->force_len; p->n_text_ctx = c->hp.n_text_ctx;
 }
 
-// the hot-phrase boost ahead of a sampler launch (kernels.hpp states the row mapping); nothing without a table
+// the history-dependent logit rules ahead of a sampler launch (kernels.hpp states the row mapping): the hot-phrase boost, then
+// the repetition rule; nothing without a table and with the rule off
 void boost_rows(ohw_state* st, const SamplerParams& p, int rows, int row_mul, int group, const int32_t* n_cur, const int32_t* done, hipStream_t s) {
-  if (!st->ph_on) return;
-  PhraseBoostParams b{};
-  b.logits = st->logits.as<float>(); b.ld = p.ld; b.n_vocab = p.n_vocab; b.max_tokens = p.max_tokens; b.row_mul = row_mul; b.group = group;
-  b.tokens = p.tokens; b.n_cur = n_cur; b.done = done; b.table = st->ph_table.as<int32_t>();
-  launch_phrase_boost(b, rows, s);
-  ++st->tally_phrase;
+  if (st->ph_on) {
+    PhraseBoostParams b{};
+    b.logits = st->logits.as<float>(); b.ld = p.ld; b.n_vocab = p.n_vocab; b.max_tokens = p.max_tokens; b.row_mul = row_mul; b.group = group;
+    b.tokens = p.tokens; b.n_cur = n_cur; b.done = done; b.table = st->ph_table.as<int32_t>();
+    launch_phrase_boost(b, rows, s);
+    ++st->tally_phrase;
+  }
+  // null n_cur is the group pass's first step, where every history is empty by definition: the launch is skipped.  The beam's
+  // first step passes the windows' n_cur, which the device holds as zeros: there the kernel runs and returns at once
+  if (st->rp_on && n_cur) {
+    RepeatRuleParams q{};
+    q.logits = st->logits.as<float>(); q.ld = p.ld; q.n_vocab = p.n_vocab; q.max_tokens = p.max_tokens; q.row_mul = row_mul; q.group = group;
+    q.eot = p.eot; q.tokens = p.tokens; q.n_cur = n_cur; q.done = done; q.rule = st->rp_rule.as<int32_t>();
+    launch_repeat_rule(q, rows, s);
+    ++st->tally_repeat;
+  }
 }
 
 int build_prompt(const ohw_ctx* c, const ohw_sample_params* sp, int32_t* out) {
@@ -1223,6 +1242,12 @@ void state_drop_recording(ohw_state* st) {
 const float* state_bias_host(const ohw_state* st) { return st && st->bias_on && !st->bias_host.empty() ? st->bias_host.data() : nullptr; }
 // the host's view of a state's hot phrases: the table in effect (null: none) and the phrases as they were given
 const ohw_phrase_table* state_phrase_table_host(const ohw_state* st) { return st && st->ph_on ? &st->ph_host : nullptr; }
+// a state's repetition rule as the host-sampled ladder needs it: false while it is off
+bool state_repeat_rule_host(const ohw_state* st, float* penalty, int* ngram) {
+  if (!st || !st->rp_on) return false;
+  *penalty = st->rp_penalty; *ngram = st->rp_ngram;
+  return true;
+}
 int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts) {
   if (!st || !st->ph_on) return 0;
   *tokens = st->ph_src_tok.data(); *offsets = st->ph_src_off.data(); *boosts = st->ph_src_boost.data();
@@ -1996,6 +2021,7 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "persist_launches") return st->persist_launches;
   if (n == "xattn.chunk") return (int)std::min<int64_t>(st->tally_xchunk, INT32_MAX);
   if (n == "phrase_boost") return (int)std::min<int64_t>(st->tally_phrase, INT32_MAX);
+  if (n == "repeat_rule") return (int)std::min<int64_t>(st->tally_repeat, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
   auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
   for (int g = 0; g < DT_GEMMS; ++g)
@@ -2313,6 +2339,73 @@ int ohw_dbg_phrase_boost(ohw_state* st, float* logits, int rows, int64_t ld, int
     b.logits = d_logits.as<float>(); b.ld = ld; b.n_vocab = n_vocab; b.max_tokens = max_tokens; b.row_mul = 1; b.group = 1;
     b.tokens = d_hist.as<int32_t>(); b.n_cur = d_ncur.as<int32_t>(); b.done = d_done.as<int32_t>(); b.table = st->ph_table.as<int32_t>();
     launch_phrase_boost(b, rows, s);
+    HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+static void repeat_upload(ohw_state* st, float penalty, int ngram) {
+  int32_t words[2];
+  std::memcpy(&words[0], &penalty, 4);
+  words[1] = ngram;
+  if (!st->rp_rule.p) st->rp_rule.alloc(sizeof words, true);
+  HIP_CHECK(hipMemcpy(st->rp_rule.p, words, sizeof words, hipMemcpyHostToDevice));
+}
+
+int ohw_state_set_repeat_rule(ohw_state* st, float penalty, int ngram) {
+  return guard([&] {
+    repeat_rule_check(penalty, ngram);                 // the values first: a refusal needs no state and no device
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    const bool on = penalty != 1.0f || ngram != 0;
+    if (on || st->rp_rule.p) {                         // a state that never had the rule on owns no buffer and needs none
+      HIP_CHECK(hipSetDevice(st->ctx->device));
+      HIP_CHECK(hipStreamSynchronize(st->stream));
+      repeat_upload(st, penalty, ngram);
+    }
+    st->rp_penalty = penalty; st->rp_ngram = ngram; st->rp_on = on;
+  });
+}
+
+int ohw_state_repeat_rule(const ohw_state* st, float* penalty, int* ngram) {
+  if (!st || !penalty || !ngram) return OHW_E_INVALID_ARG;
+  *penalty = st->rp_penalty; *ngram = st->rp_ngram;
+  return OHW_OK;
+}
+
+// test entry: repeat_rule_kernel once on caller data (include/ohw.h).  Everything is range-checked first: the kernel indexes
+// with these values
+int ohw_dbg_repeat_rule(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                        const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int ngram, int eot) {
+  return guard([&] {
+    repeat_rule_check(penalty, ngram);
+    if (!st || !logits || !histories || !done) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (rows < 1 || rows > 4096 || n_vocab < 1 || ld < n_vocab || max_tokens < 1 || max_tokens > 4096 || eot < 0 || n_entries < 1 || n_entries > 4096 ||
+        row_mul < 1 || row_mul > 64 || group < 1 || group > 64)
+      throw Error(OHW_E_INVALID_ARG, "dbg_repeat_rule: bad shape");
+    if ((int64_t)(rows - 1) * row_mul / group >= n_entries) throw Error(OHW_E_INVALID_ARG, "dbg_repeat_rule: a launch row maps behind the last entry");
+    for (int i = 0; n_cur && i < n_entries; ++i)
+      if (n_cur[i] < 0 || n_cur[i] > max_tokens) throw Error(OHW_E_INVALID_ARG, "dbg_repeat_rule: n_cur out of range");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    HIP_CHECK(hipStreamSynchronize(s));
+    struct Restore {       // the state's own setting is in effect again afterwards, also when a step below throws
+      ohw_state* st;
+      ~Restore() {
+        try { repeat_upload(st, st->rp_penalty, st->rp_ngram); } catch (...) { st->rp_on = false; st->rp_penalty = 1.0f; st->rp_ngram = 0; }
+      }
+    } restore{st};
+    repeat_upload(st, penalty, ngram);
+    const size_t hist_rows = (size_t)n_entries * group;
+    DevBuf d_logits, d_hist, d_ncur, d_done;
+    d_logits.alloc((size_t)rows * ld * 4); d_hist.alloc(hist_rows * max_tokens * 4); d_ncur.alloc((size_t)n_entries * 4); d_done.alloc((size_t)n_entries * 4);
+    HIP_CHECK(hipMemcpyAsync(d_logits.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_hist.p, histories, hist_rows * max_tokens * 4, hipMemcpyHostToDevice, s));
+    if (n_cur) HIP_CHECK(hipMemcpyAsync(d_ncur.p, n_cur, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_done.p, done, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+    RepeatRuleParams q{};
+    q.logits = d_logits.as<float>(); q.ld = ld; q.n_vocab = n_vocab; q.max_tokens = max_tokens; q.row_mul = row_mul; q.group = group; q.eot = eot;
+    q.tokens = d_hist.as<int32_t>(); q.n_cur = n_cur ? d_ncur.as<int32_t>() : nullptr; q.done = d_done.as<int32_t>(); q.rule = st->rp_rule.as<int32_t>();
+    launch_repeat_rule(q, rows, s);
     HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   });

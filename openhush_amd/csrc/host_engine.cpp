@@ -799,6 +799,19 @@ int ohw_engine_set_hot_phrases(ohw_engine* e, const char* const* texts, const fl
   return ohw_engine_set_hot_phrases_tokens(e, toks.data(), offs.data(), bs.data(), (int)bs.size());
 }
 
+int ohw_engine_set_repetition(ohw_engine* e, float penalty, int ngram) {
+  return guard([&] {
+    // the engine's own state first (the state setter checks the values ahead of the state): refused values reach no state
+    const int rc = ohw_state_set_repeat_rule(e ? e->state : nullptr, penalty, ngram);
+    if (rc != OHW_OK) throw Error(rc, g_last_error);
+    each_state(e, [&](ohw_state* st) {
+      if (st == e->state) return;
+      const int rc2 = ohw_state_set_repeat_rule(st, penalty, ngram);
+      if (rc2 != OHW_OK) throw Error(rc2, g_last_error);
+    });
+  });
+}
+
 int ohw_engine_set_prefill_chunk(ohw_engine* e, int positions) {
   return guard([&] {
     if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");

@@ -307,8 +307,26 @@ void phrase_boost_host(const ohw_phrase_table* t, const int32_t* history, int n_
 // the table's arrays laid out as the device buffer above (PH_WORDS words); checks every count and child token against n_vocab
 void phrase_table_pack(const ohw_phrase_table* t, int n_vocab, std::vector<int32_t>* words);
 
+// ---- repetition penalty and no-repeat n-grams (repeat.hip; ohw_state_set_repeat_rule) ------------------------------------
+// PhraseBoostParams' twin: the same row mapping (launch row r changes logits row r with the history of decoder row
+// h = r * row_mul, length n_cur[h / group] - null: every history is empty - and flag done[h / group]).  rule: two words the
+// state owns, {the fp32 bits of the penalty, the n-gram size}; a captured step holds the pointer, so new values capture nothing.
+struct RepeatRuleParams {
+  float* logits;            // [rows][ld], changed in place over the columns of text tokens, [0, min(eot, n_vocab))
+  int64_t ld;
+  int32_t n_vocab, max_tokens, row_mul, group, eot;
+  const int32_t* tokens;    // [decoder rows][max_tokens]; entries at and behind n_cur are never read
+  const int32_t* n_cur;
+  const int32_t* done;
+  const int32_t* rule;
+};
+void launch_repeat_rule(const RepeatRuleParams& p, int rows, hipStream_t s);
+// the values ohw_state_set_repeat_rule accepts (throws Error otherwise), and the rule on one row on the host (no device)
+void repeat_rule_check(float penalty, int ngram);
+void repeat_rule_host(float penalty, int ngram, const int32_t* history, int n_cur, float* row, int n_vocab, int eot);
+
 // ---- per-window language (decode.hip; ohw_state_set_window_lang) -------------------------------------------------------
-constexpr int32_t LANG_PENDING = -1;   // table entry that waits for a detection (OHW_LANG_DETECT)
+constexpr int32_t LANG_PENDING = -1;  // table entry that waits for a detection (OHW_LANG_DETECT)
 // one workgroup per window whose table entry lang[b] is LANG_PENDING (the others are left alone): over the raw columns
 // logits[b * ld + sot + 1 + i], i < n_langs (no bias, no filter), lang[b] = the arg-max, the lowest index on ties, and
 // lang_prob[b][0 .. n_langs) = the fp32 soft-max over those columns only (n_langs <= 128: two columns per lane).  ohw_lang_pick_host (host_engine.cpp) defines the result

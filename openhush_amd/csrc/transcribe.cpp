@@ -13,6 +13,7 @@
 namespace ohw {
 const float* state_bias_host(const ohw_state* st);
 const ohw_phrase_table* state_phrase_table_host(const ohw_state* st);
+bool state_repeat_rule_host(const ohw_state* st, float* penalty, int* ngram);
 int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts);
 void state_share_recording(ohw_state* dst, ohw_state* src);
 void state_drop_recording(ohw_state* st);
@@ -284,6 +285,10 @@ struct TranscribeCall {
         float lp = 0.f;
         if (const ohw_phrase_table* pt = state_phrase_table_host(bt.st))     // the state's hot phrases, ahead of the bias as on the device
           check(ohw_phrase_boost_host(pt, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V));
+        float rp_theta = 1.f;
+        int rp_n = 0;
+        if (state_repeat_rule_host(bt.st, &rp_theta, &rp_n))                 // the state's repetition rule, behind the boost as on the device
+          check(ohw_repeat_rule_host(rp_theta, rp_n, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V, tk.eot));
         if (const float* bias = state_bias_host(bt.st))          // the state's logit bias: the device sampler adds it itself
           for (int i2 = 0; i2 < V; ++i2) logits[(size_t)b * V + i2] += bias[i2];
         const int32_t t = ohw_sample_host(e->ctx, &sp, &logits[(size_t)b * V], r.tok.data(), (int)r.tok.size(), T, bt.rngs[b], &lp, &r.nosp);
@@ -780,6 +785,20 @@ void propagate_hot_phrases(ohw_engine* e) {
   for (ohw_state* st : e->lane_states) same(st);
 }
 
+// the repetition rule of the engine's own state (ohw_engine_set_repetition), on the states a schedule made since it was set
+void propagate_repetition(ohw_engine* e) {
+  float theta = 1.f, theta2 = 1.f;
+  int n = 0, n2 = 0;
+  check(ohw_state_repeat_rule(e->state, &theta, &n));
+  auto same = [&](ohw_state* st) {
+    if (st == e->state) return;
+    check(ohw_state_repeat_rule(st, &theta2, &n2));
+    if (theta2 != theta || n2 != n) check(ohw_state_set_repeat_rule(st, theta, n));
+  };
+  for (ohw_state* st : e->states) same(st);
+  for (ohw_state* st : e->lane_states) same(st);
+}
+
 void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n, int64_t win_first, int64_t win_step) {
   ohw_engine* e = tc.e;
   const FixedCuts cuts(tc, samples, n, win_first, win_step);
@@ -797,6 +816,7 @@ void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n,
   SharedRecording shared_recording(e, cuts.rec_mel);
   propagate_logit_bias(e);
   propagate_hot_phrases(e);
+  propagate_repetition(e);
   apply_ctx(e, call_ctx);
   if (schedule == OHW_SCHEDULE_SEQUENTIAL) cuts.sequential();
   else if (schedule == OHW_SCHEDULE_PIPELINE) cuts.pipeline();

@@ -302,6 +302,19 @@ def hot_phrase_tokens(ctx, phrases, boost=1.0) -> Tuple[List[List[int]], List[fl
     return out, bs
 
 
+REPEAT_BAN = np.float32(-1.0e30)         # OHW_REPEAT_BAN
+REPEAT_PENALTY_MIN, REPEAT_PENALTY_MAX, REPEAT_MAX_NGRAM = 0.01, 100.0, 32
+
+
+def repeat_rule_host(penalty: float, ngram: int, history: Sequence[int], n_cur: int, row: np.ndarray, eot: int) -> np.ndarray:
+    """ohw_repeat_rule_host: repetition penalty and no-repeat n-grams on a copy of one row [n_vocab]; history = the row's own
+    sampled tokens (include/ohw.h states the rule); needs no device"""
+    out = np.ascontiguousarray(row, dtype=np.float32).copy()
+    h = np.ascontiguousarray(list(history) or [0], dtype=np.int32)
+    _check(lib().ohw_repeat_rule_host(float(penalty), int(ngram), _ip(h), int(n_cur), _fp(out), int(out.size), int(eot)))
+    return out
+
+
 def _hot_phrase_text_call(fn, handle, phrases, boosts):
     raw = [_text_bytes(p) for p in phrases]
     arr = (C.c_char_p * max(len(raw), 1))(*raw)
@@ -405,6 +418,8 @@ EXPORTS = [
     "ohw_dbg_enc_gemm",
     "ohw_phrase_table_build_host", "ohw_phrase_boost_host", "ohw_state_set_phrase_table", "ohw_state_phrase_count", "ohw_dbg_phrase_boost",
     "ohw_engine_set_hot_phrases", "ohw_engine_set_hot_phrases_tokens", "ohw_pool_set_hot_phrases",
+    "ohw_repeat_rule_host", "ohw_state_set_repeat_rule", "ohw_state_repeat_rule", "ohw_dbg_repeat_rule", "ohw_engine_set_repetition",
+    "ohw_pool_set_repetition",
 ]
 
 
@@ -694,6 +709,12 @@ def lib():
         L.ohw_engine_set_hot_phrases.argtypes = [vp, C.POINTER(C.c_char_p), fp, C.c_int]
         L.ohw_engine_set_hot_phrases_tokens.argtypes = [vp, ip, ip, fp, C.c_int]
         L.ohw_pool_set_hot_phrases.argtypes = [vp, C.POINTER(C.c_char_p), fp, C.c_int]
+        L.ohw_repeat_rule_host.argtypes = [C.c_float, C.c_int, ip, C.c_int, fp, C.c_int, C.c_int]
+        L.ohw_state_set_repeat_rule.argtypes = [vp, C.c_float, C.c_int]
+        L.ohw_state_repeat_rule.argtypes = [vp, fp, C.POINTER(C.c_int)]
+        L.ohw_dbg_repeat_rule.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, ip, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]
+        L.ohw_engine_set_repetition.argtypes = [vp, C.c_float, C.c_int]
+        L.ohw_pool_set_repetition.argtypes = [vp, C.c_float, C.c_int]
         L.ohw_dbg_beam_step.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIO)]
         L.ohw_beam_search_ex.argtypes = [vp, C.POINTER(SampleParams), C.c_int, C.c_int, C.c_int, C.POINTER(BeamResultEx)]
         L.ohw_dbg_beam_step_ex.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIOEx)]
@@ -1385,6 +1406,30 @@ class State:
 
     def phrase_count(self) -> int:
         return int(lib().ohw_state_phrase_count(self.h))
+
+    def set_repeat_rule(self, penalty: float = 1.0, ngram: int = 0):
+        """ohw_state_set_repeat_rule: repetition penalty (0.01 .. 100; 1.0 = none) and no-repeat n-gram size (0 .. 32; 0 = none)
+        on the row's own sampled tokens, in every decoder of this state; the defaults turn the rule off"""
+        _check(lib().ohw_state_set_repeat_rule(self.h, float(penalty), int(ngram)))
+
+    def repeat_rule(self) -> Tuple[float, int]:
+        """ohw_state_repeat_rule: (penalty, ngram) in effect; (1.0, 0) is off"""
+        theta, n = C.c_float(), C.c_int()
+        _check(lib().ohw_state_repeat_rule(self.h, C.byref(theta), C.byref(n)))
+        return float(theta.value), int(n.value)
+
+    def dbg_repeat_rule(self, logits: np.ndarray, n_vocab: int, histories: np.ndarray, n_cur, done, penalty: float, ngram: int, eot: int,
+                        row_mul: int = 1, group: int = 1) -> np.ndarray:
+        """ohw_dbg_repeat_rule: the kernel once on logits [rows][ld] (a copy comes back whole), histories [entries * group][max_tokens],
+        n_cur (None: every history is empty) and done [entries]; launch row r reads history row r * row_mul under entry r * row_mul // group"""
+        lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
+        h = np.ascontiguousarray(histories, dtype=np.int32)
+        dn = np.ascontiguousarray(done, dtype=np.int32)
+        nc = None if n_cur is None else np.ascontiguousarray(n_cur, dtype=np.int32)
+        assert lg.ndim == 2 and h.ndim == 2 and h.shape[0] == dn.size * group and (nc is None or nc.size == dn.size)
+        _check(lib().ohw_dbg_repeat_rule(self.h, _fp(lg), lg.shape[0], lg.shape[1], int(n_vocab), _ip(h), h.shape[1], None if nc is None else _ip(nc),
+                                         _ip(dn), dn.size, int(row_mul), int(group), float(penalty), int(ngram), int(eot)))
+        return lg
 
     def dbg_phrase_boost(self, logits: np.ndarray, n_vocab: int, histories: np.ndarray, n_cur, done, table: PhraseTable) -> np.ndarray:
         """ohw_dbg_phrase_boost: the kernel once on logits [rows][ld] (a copy comes back whole), histories [rows][max_tokens]"""
@@ -2349,6 +2394,11 @@ class WhisperEngine:
             a = np.ascontiguousarray(list(prompt) or [0], dtype=np.int32)
             _check(lib().ohw_engine_set_initial_prompt_tokens(self.h, _ip(a), len(prompt)))
 
+    def set_repetition(self, penalty: float = 1.0, no_repeat_ngram_size: int = 0):
+        """ohw_engine_set_repetition: faster-whisper's repetition_penalty and no_repeat_ngram_size on every state the engine decodes
+        on (State.set_repeat_rule states the rule); the defaults turn both off"""
+        _check(lib().ohw_engine_set_repetition(self.h, float(penalty), int(no_repeat_ngram_size)))
+
     def set_hot_phrases(self, phrases, boost=1.0):
         """ohw_engine_set_hot_phrases / _tokens: strings (each tokenised with and without a leading space) or token-id lists (the
         exact form) whose continuation is raised by `boost` logit units - one value, or one per phrase - while a row's own history
@@ -2465,6 +2515,10 @@ class EnginePool:
 
     def set_window_mode(self, mode: int):
         _check(lib().ohw_pool_set_window_mode(self.h, mode))
+
+    def set_repetition(self, penalty: float = 1.0, no_repeat_ngram_size: int = 0):
+        """ohw_pool_set_repetition: WhisperEngine.set_repetition on every engine of the pool"""
+        _check(lib().ohw_pool_set_repetition(self.h, float(penalty), int(no_repeat_ngram_size)))
 
     def set_hot_phrases(self, phrases, boost=1.0):
         """ohw_pool_set_hot_phrases: WhisperEngine.set_hot_phrases (the text form) on every engine of the pool; None or [] clears"""

@@ -135,12 +135,15 @@ class StreamingSession:
     (the VadEngine hook) with `vad_threshold`, or None.  audio_ctx: 0 (default) the full 30 s context, n a fixed reduced
     context (a window with samples past n * 320 is refused), "auto" engine.audio_ctx_for(len) for a job of at most one window -
     a 1.1 s chunk then pays for 128 encoder positions instead of 1500 (WhisperEngine.set_audio_ctx's rule).  hot_phrases: terms
-    whose continuation is raised while a window's own tokens end in their front part (WhisperEngine.set_hot_phrases)."""
+    whose continuation is raised while a window's own tokens end in their front part (WhisperEngine.set_hot_phrases).
+    repetition_penalty / no_repeat_ngram_size: the two controls of WhisperEngine.set_repetition on the session's state; the
+    defaults (1.0, 0) are off."""
 
     def __init__(self, ctx: E.Context, beam_size: int = 5, vad: Optional[Callable[[np.ndarray], float]] = None, vad_threshold: float = 0.5,
                  sequence_id: int = 1, tracker: Optional[TranscriptionTracker] = None, params: Optional[E.SampleParams] = None,
                  audio_config: Optional[E.PreprocessConfig] = None, noise_reduction: bool = False, noise_reduction_strength: float = 1.0,
-                 denoiser: Optional["E.Denoiser"] = None, audio_ctx=0, carry_context: bool = False, hot_phrases=None, hot_phrase_boost=1.0):
+                 denoiser: Optional["E.Denoiser"] = None, audio_ctx=0, carry_context: bool = False, hot_phrases=None, hot_phrase_boost=1.0,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         self.ctx = ctx
         self.audio_ctx = E._audio_ctx_arg(audio_ctx)
         if self.audio_ctx > ctx.hp.n_audio_ctx:
@@ -165,6 +168,8 @@ class StreamingSession:
         # per phrase - on the session's state (WhisperEngine.set_hot_phrases's rule, State.set_phrase_table)
         if hot_phrases:
             self.state.set_phrase_table(*E.hot_phrase_tokens(ctx, hot_phrases, hot_phrase_boost))
+        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
+            self.state.set_repeat_rule(repetition_penalty, no_repeat_ngram_size)
 
     def _text(self, tokens: List[int]) -> str:
         return b"".join(self.ctx.token_text(t) for t in tokens if t < self.ctx.tok.eot).decode("utf-8", "replace").strip()
