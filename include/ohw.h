@@ -432,7 +432,10 @@ int ohw_beam_search_ex(ohw_state* st, const ohw_sample_params* p, int n_windows,
 /* additive bias on every logits row before the filter, bias[n_vocab] (host; copied), NULL clears it.  This is the
  * engine's form of whisper.cpp's logits_filter_callback (whisper_full_params; the reference sets none,
  * src/engine/whisper.rs:243-263, so the default is no bias); tests use it to make end-of-text and timestamps win.
- * Set on ohw_engine_state(e) it holds for every state ohw_engine_transcribe decodes on (the schedules' lane states too). */
+ * Set on ohw_engine_state(e) it holds for every state ohw_engine_transcribe decodes on (the schedules' lane states too).
+ * An entry of -INFINITY is allowed and means "never": the token has probability 0 in every sampler (arg-max, draw, beam
+ * candidates), counts in no log-sum-exp, the no-speech probability's included, and is never returned while another token is
+ * allowed.  +INFINITY and NaN are refused (OHW_E_INVALID_ARG; the bias in effect stays).                                  */
 int ohw_state_set_logit_bias(ohw_state* st, const float* bias, int n);
 
 /* hot phrases: a history-dependent logit boost (shallow-fusion biasing), applied on the device ahead of every sampler of every
@@ -1292,6 +1295,34 @@ typedef struct {
   float* nosp_prob;        /* out [W] or NULL */
 } ohw_dbg_beam_io_ex;
 int ohw_dbg_beam_step_ex(ohw_state* st, const ohw_sample_params* p, const ohw_dbg_beam_io_ex* io);
+
+/* ONE sampler launch (temperature == 0: sampler_kernel as ohw_greedy launches it; > 0: sampler_t_kernel as ohw_sample_pass
+ * does) on caller-supplied host rows, and the sampler's WHOLE output: what ohw_dbg_sample / ohw_dbg_sample_t leave out (the
+ * history rows, the counters, the finishing flags, the log-probability rows, the ticket words).  No decoder runs; the state's
+ * logit bias applies; p->n_max and p->force_len are used as given.  M = the state's token capacity (n_text_ctx).
+ * Every range is checked on the host before any device work (OHW_E_INVALID_ARG): batch in 1..max_batch, advance 0 or 1,
+ * temperature >= 0 (uniforms not NULL and in [0, 1) when > 0), 0 <= n_cur[b] < M, 0 <= n_past[b] and
+ * n_past[b] + advance < n_text_ctx, the first n_cur[b] tokens of a row in 0..n_vocab - 1.
+ * Before the launch next_tok, tok_lp, nosp_prob and the history slot at n_cur[b] of every row are filled with
+ * OHW_DBG_SENTINEL_I32 / OHW_DBG_SENTINEL_F32; afterwards everything is copied back whole: what holds the sentinel was not
+ * written.  tickets_out: the sampler's ticket words, zero after every launch.                                             */
+typedef struct {
+  int32_t batch, advance;
+  float temperature;
+  const float* logits;     /* in  [batch][n_vocab] */
+  const double* uniforms;  /* in  [batch] the draw of each row's step, or NULL when temperature == 0 */
+  int32_t* tokens;         /* in / out [batch][M] token histories, n_cur[b] of them used */
+  int32_t* n_cur;          /* in / out [batch] */
+  int32_t* n_past;         /* in / out [batch] */
+  int32_t* done;           /* in / out [batch]: a row that comes in done is not touched */
+  float* sum_logprob;      /* in / out [batch] */
+  int32_t* next_tok;       /* out [batch] */
+  float* tok_lp;           /* out [batch][M + 1] */
+  float* nosp_prob;        /* out [batch]: written for rows with n_cur == 0 */
+  int32_t* n_done;         /* out [1] rows that finished in this launch */
+  uint32_t* tickets_out;   /* out [batch] */
+} ohw_dbg_sample_io;
+int ohw_dbg_sample_ex(ohw_state* st, const ohw_sample_params* p, const ohw_dbg_sample_io* io);
 
 /* the final ranking of a beam search on caller-supplied pool and live state (host arrays), R = W * K rows:
  * candidates are window w's pool entries 0 .. fin_cnt[w] - 1 in pool order; if fewer than K, its live beams join by

@@ -1672,7 +1672,7 @@ __global__ __launch_bounds__(SP_THREADS) void sampler_kernel(SamplerParams p) {
         const float v = vv[u];
         if (i >= V) continue;
         if (v > a.rm) { a.rs *= a.rm == -INFINITY ? 0.f : expf(a.rm - v); a.rm = v; }
-        a.rs += expf(v - a.rm);
+        a.rs += v == -INFINITY ? 0.f : expf(v - a.rm);       // -inf weighs nothing (a.rm may still be -inf: expf(NaN))
       }
     }
 #pragma unroll
@@ -1684,7 +1684,7 @@ __global__ __launch_bounds__(SP_THREADS) void sampler_kernel(SamplerParams p) {
         const float f = a.m == -INFINITY ? 0.f : expf(a.m - v);
         a.s_all *= f; a.s_ts *= f; a.m = v;
       }
-      const float e = expf(v - a.m);
+      const float e = v == -INFINITY ? 0.f : expf(v - a.m);      // a -inf logit (a "never" bias) weighs nothing and is no candidate
       a.s_all += e;
       if (i >= p.ts_begin) { a.s_ts += e; if (v > a.zv) { a.zv = v; a.zi = i; } }
       else if (v > a.tv) { a.tv = v; a.ti = i; }
@@ -1847,7 +1847,7 @@ __device__ __forceinline__ void sampler_t_row(SamplerParams p, const float* __re
         const float v = vv[u];
         if (i >= V) continue;
         if (v > a.rm) { a.rs *= a.rm == -INFINITY ? 0.f : expf(a.rm - v); a.rm = v; }
-        a.rs += expf(v - a.rm);
+        a.rs += v == -INFINITY ? 0.f : expf(v - a.rm);       // -inf weighs nothing (a.rm may still be -inf: expf(NaN))
       }
     }
 #pragma unroll
@@ -1859,7 +1859,7 @@ __device__ __forceinline__ void sampler_t_row(SamplerParams p, const float* __re
         const float f = a.m == -INFINITY ? 0.f : expf(a.m - v);
         a.s_all *= f; a.s_ts *= f; a.m = v;
       }
-      const float e = expf(v - a.m);
+      const float e = v == -INFINITY ? 0.f : expf(v - a.m);      // a -inf logit (a "never" bias) weighs nothing and is no candidate
       a.s_all += e;
       if (i >= p.ts_begin) { a.s_ts += e; if (v > a.zv) { a.zv = v; a.zi = i; } }
       else if (v > a.tv) { a.tv = v; a.ti = i; }
@@ -2137,7 +2137,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(SamplerParams p
         const float x = vv[u];
         if (i >= V) continue;
         if (x > rm) { rs *= rm == -INFINITY ? 0.f : expf(rm - x); rm = x; }
-        rs += expf(x - rm);
+        rs += x == -INFINITY ? 0.f : expf(x - rm);           // as the samplers: -inf weighs nothing
       }
     }
 #pragma unroll

@@ -2271,6 +2271,9 @@ int ohw_state_set_logit_bias(ohw_state* st, const float* bias, int n) {
     HIP_CHECK(hipStreamSynchronize(st->stream));
     if (!bias) { st->bias_on = false; st->bias_host.clear(); return; }
     if (n != st->ctx->hp.n_vocab) throw Error(OHW_E_INVALID_ARG, "logit bias: n must equal n_vocab");
+    // -inf means "never" (the samplers give such an entry probability 0); +inf and NaN would poison a row's log-sum-exp
+    for (int i = 0; i < n; ++i)
+      if (std::isnan(bias[i]) || bias[i] == INFINITY) throw Error(OHW_E_INVALID_ARG, "logit bias: entry " + std::to_string(i) + " is +inf or NaN");
     if (!st->logit_bias.p) st->logit_bias.alloc((size_t)n * 4);
     HIP_CHECK(hipMemcpy(st->logit_bias.p, bias, (size_t)n * 4, hipMemcpyHostToDevice));
     st->bias_host.assign(bias, bias + n);
@@ -2474,6 +2477,74 @@ int ohw_dbg_sample_t(ohw_state* st, const ohw_sample_params* sp, const float* lo
   return guard([&] {
     if (!(temperature > 0.0f)) throw Error(OHW_E_INVALID_ARG, "dbg_sample_t: temperature must be > 0");
     dbg_sample(st, sp, logits, history, hist_stride, n_hist, batch, temperature, uniforms, tokens_out, logprobs_out, no_speech_out);
+  });
+}
+
+// test entry: one sampler launch on caller-supplied rows and state, the whole output back (include/ohw.h).  Everything is
+// range-checked first: the kernels index with these values
+int ohw_dbg_sample_ex(ohw_state* st, const ohw_sample_params* sp, const ohw_dbg_sample_io* io) {
+  return guard([&] {
+    if (!st || !sp || !io) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (!io->logits || !io->tokens || !io->n_cur || !io->n_past || !io->done || !io->sum_logprob || !io->next_tok || !io->tok_lp ||
+        !io->nosp_prob || !io->n_done || !io->tickets_out)
+      throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: null array");
+    const ohw_ctx* c = st->ctx;
+    const int B = io->batch, V = c->hp.n_vocab, MT = st->max_tokens, C = c->hp.n_text_ctx;
+    const float T = io->temperature;
+    if (B < 1 || B > st->max_batch) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: batch must be in 1..max_batch");
+    if (io->advance != 0 && io->advance != 1) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: advance must be 0 or 1");
+    if (!(T >= 0.0f) || T == INFINITY) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: temperature must be finite and >= 0");
+    if (T > 0.0f && !io->uniforms) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: uniforms is null");
+    for (int b = 0; b < B; ++b) {
+      if (io->n_cur[b] < 0 || io->n_cur[b] >= MT) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: n_cur out of range");
+      if (io->n_past[b] < 0 || (int64_t)io->n_past[b] + io->advance >= C) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: n_past out of range");
+      for (int i = 0; i < io->n_cur[b]; ++i)
+        if (io->tokens[(size_t)b * MT + i] < 0 || io->tokens[(size_t)b * MT + i] >= V) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: history token out of range");
+      if (T > 0.0f && !(io->uniforms[b] >= 0.0 && io->uniforms[b] < 1.0)) throw Error(OHW_E_INVALID_ARG, "dbg_sample_ex: a uniform outside [0, 1)");
+    }
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = st->stream;
+    std::vector<int32_t> hist(io->tokens, io->tokens + (size_t)B * MT), rdone((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      hist[(size_t)b * MT + io->n_cur[b]] = OHW_DBG_SENTINEL_I32;
+      rdone[(size_t)b] = io->done[b] ? 1 : 0;
+    }
+    const std::vector<int32_t> sent_i((size_t)B, OHW_DBG_SENTINEL_I32);
+    const std::vector<float> sent_f((size_t)B * (MT + 1), OHW_DBG_SENTINEL_F32);
+    HIP_CHECK(hipMemcpy2DAsync(st->logits.p, (size_t)st->logits_ld * 4, io->logits, (size_t)V * 4, (size_t)V * 4, (size_t)B, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->tokens.p, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->n_cur.p, io->n_cur, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->n_past.p, io->n_past, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->done.p, rdone.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->sum_lp.p, io->sum_logprob, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->next_tok.p, sent_i.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->tok_lp.p, sent_f.data(), (size_t)B * (MT + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st->nosp_prob.p, sent_f.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(st->n_done.p, 0, 16, s));
+    SamplerParams spar;
+    fill_sampler(st, sp, B, &spar);
+    spar.advance = io->advance;
+    std::vector<double> u;
+    if (T > 0.0f) {
+      u.assign((size_t)B * MT, 0.0);
+      for (int b = 0; b < B; ++b) u[(size_t)b * MT + io->n_cur[b]] = io->uniforms[b];
+      HIP_CHECK(hipMemcpyAsync(st->samp_temp.p, &T, 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->samp_u.p, u.data(), u.size() * 8, hipMemcpyHostToDevice, s));
+      launch_sampler_t(spar, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);
+    } else {
+      launch_sampler(spar, s);
+    }
+    HIP_CHECK(hipMemcpyAsync(io->tokens, st->tokens.p, (size_t)B * MT * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_cur, st->n_cur.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_past, st->n_past.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->done, st->done.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->sum_logprob, st->sum_lp.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->next_tok, st->next_tok.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->tok_lp, st->tok_lp.p, (size_t)B * (MT + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->nosp_prob, st->nosp_prob.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->n_done, st->n_done.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(io->tickets_out, st->samp_ticket.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
   });
 }
 

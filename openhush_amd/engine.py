@@ -115,6 +115,15 @@ class DbgBeamIO(C.Structure):
                 [("tickets_out", C.POINTER(C.c_uint32))])
 
 
+class DbgSampleIO(C.Structure):
+    """ohw_dbg_sample_io"""
+    _fields_ = ([("batch", C.c_int32), ("advance", C.c_int32), ("temperature", C.c_float), ("logits", C.POINTER(C.c_float)),
+                 ("uniforms", C.POINTER(C.c_double))] +
+                [(n, C.POINTER(C.c_float) if n in ("sum_logprob", "tok_lp", "nosp_prob") else C.POINTER(C.c_int32))
+                 for n in ("tokens", "n_cur", "n_past", "done", "sum_logprob", "next_tok", "tok_lp", "nosp_prob", "n_done")] +
+                [("tickets_out", C.POINTER(C.c_uint32))])
+
+
 class BeamResultEx(C.Structure):
     """ohw_beam_result_ex"""
     _fields_ = [("tokens", C.POINTER(C.c_int32)), ("n_tokens", C.POINTER(C.c_int32)), ("sum_logprob", C.POINTER(C.c_float)),
@@ -420,6 +429,7 @@ EXPORTS = [
     "ohw_engine_set_hot_phrases", "ohw_engine_set_hot_phrases_tokens", "ohw_pool_set_hot_phrases",
     "ohw_repeat_rule_host", "ohw_state_set_repeat_rule", "ohw_state_repeat_rule", "ohw_dbg_repeat_rule", "ohw_engine_set_repetition",
     "ohw_pool_set_repetition",
+    "ohw_dbg_sample_ex",
 ]
 
 
@@ -718,6 +728,7 @@ def lib():
         L.ohw_dbg_beam_step.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIO)]
         L.ohw_beam_search_ex.argtypes = [vp, C.POINTER(SampleParams), C.c_int, C.c_int, C.c_int, C.POINTER(BeamResultEx)]
         L.ohw_dbg_beam_step_ex.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIOEx)]
+        L.ohw_dbg_sample_ex.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgSampleIO)]
         L.ohw_dbg_beam_finish.argtypes = [vp, C.POINTER(BeamFinishIO)]
         L.ohw_beam_finish_host.argtypes = [C.POINTER(BeamFinishIO)]
         L.ohw_state_set_align_heads.argtypes = [vp, C.POINTER(AlignHead), C.c_int]
@@ -1627,6 +1638,31 @@ class State:
         _check(lib().ohw_dbg_sample_t(self.h, C.byref(p), _fp(lg), _ip(hist), stride, _ip(nh), B, temperature,
                                       u.ctypes.data_as(C.POINTER(C.c_double)), _ip(tok), _fp(lp), _fp(ns)))
         return tok, lp, ns
+
+    def dbg_sample_ex(self, p: SampleParams, logits: np.ndarray, histories: Sequence[Sequence[int]], n_past=None, done=None,
+                      advance: int = 0, temperature: float = 0.0, uniforms=None, sum_logprob=None) -> dict:
+        """ohw_dbg_sample_ex: ONE sampler launch (temperature 0: the greedy kernel, > 0: the draw) on host rows, the sampler's whole
+        output back.  n_past / done / sum_logprob per row (default 0).  -> dict(tokens [B][max_tokens], n_cur, n_past, done,
+        sum_logprob, next_tok [B], tok_lp [B][max_tokens + 1], nosp_prob [B], n_done, tickets [B]); what the launch did not write
+        holds OHW_DBG_SENTINEL_* (next_tok, tok_lp, nosp_prob, the history slot at n_cur) or its input"""
+        lg = np.ascontiguousarray(np.atleast_2d(logits), dtype=np.float32)
+        B, MT = lg.shape[0], self.ctx.hp.n_text_ctx
+        assert lg.shape == (B, self.ctx.hp.n_vocab) and len(histories) == B, lg.shape
+        vec = lambda x, dt: (np.zeros(B, dt) if x is None else np.array(x, dtype=dt, order="C").reshape(B))
+        a = dict(tokens=np.zeros((B, MT), np.int32), n_cur=np.array([len(h) for h in histories], np.int32), n_past=vec(n_past, np.int32),
+                 done=vec(done, np.int32), sum_logprob=vec(sum_logprob, np.float32), next_tok=np.zeros(B, np.int32),
+                 tok_lp=np.zeros((B, MT + 1), np.float32), nosp_prob=np.zeros(B, np.float32), n_done=np.zeros(1, np.int32))
+        for b, h in enumerate(histories):
+            a["tokens"][b, :min(len(h), MT)] = h[:MT]           # a history too long keeps its length: the entry refuses it
+        tickets = np.ones(B, np.uint32)
+        u = None if uniforms is None else np.array(uniforms, dtype=np.float64, order="C").reshape(B)
+        io = DbgSampleIO(B, int(advance), float(temperature), _fp(lg),
+                         C.cast(None, C.POINTER(C.c_double)) if u is None else u.ctypes.data_as(C.POINTER(C.c_double)),
+                         *[(_fp(a[n]) if a[n].dtype == np.float32 else _ip(a[n])) for n, _ in DbgSampleIO._fields_[5:-1]],
+                         tickets.ctypes.data_as(C.POINTER(C.c_uint32)))
+        _check(lib().ohw_dbg_sample_ex(self.h, C.byref(p), C.byref(io)))
+        a["n_done"], a["tickets"] = int(a["n_done"][0]), tickets
+        return a
 
     def dbg_beam_step(self, p: SampleParams, K: int, first: bool, state: dict, logits: np.ndarray, side: int = 0) -> dict:
         """ohw_dbg_beam_step: ONE beam step of the device on host data.  state: tokens [R][n_text_ctx], kv_slot [R][n_text_ctx],
