@@ -86,6 +86,9 @@ int ohw_validate_audio(const float* samples, int64_t n, uint32_t sample_rate, oh
 /* quantised blocks are uploaded as stored and expanded on the device at load, so the resident weights, their footprint   */
 /* and the throughput are those of an f16 file.  The header's ftype word is ftype + 1000 * quantisation version;          */
 /* ohw_hparams.ftype holds the reduced ftype.  k-quants and quantisation versions other than 2: OHW_E_LOAD_FAILED.        */
+/* Accepted dimensions (every ohw_ctx_create* entry; anything else: OHW_E_LOAD_FAILED "unsupported model dimensions: ..."): */
+/* n_text_state == n_audio_state, a multiple of 128 from 128 to 1280 (the decoder's fused LayerNorm holds 1280 columns),   */
+/* d_head 64 (n_*_head * 64 == n_*_state), n_audio_ctx 1500, n_text_ctx <= 448, n_mels <= 128, 1 .. 64 layers each side.   */
 int ohw_ctx_create(const char* model_path, int device, int dtype, ohw_ctx** out);
 /* procedural weights generated on the device (tests / bench; openhush_amd/synth.py is the spec)  */
 int ohw_ctx_create_synthetic(const ohw_hparams* hp, uint32_t seed, int device, int dtype, ohw_ctx** out);

@@ -95,7 +95,7 @@ __device__ __forceinline__ void self_attn_row(const T* __restrict__ q, const T* 
 
 constexpr int DG_THREADS = 512;
 constexpr int DG_WAVES = DG_THREADS / 64;
-constexpr int DG_LN_MAXK = 1280;  // fused LayerNorm: 16 threads per row, 20 float4 each
+// DG_LN_MAXK (kernels.hpp): the fused LayerNorm's widest K
 
 // The LayerNorm of the LN forms, one row: thread `sub` of the row's TPR threads (16 or 32, consecutive lanes of a wave)
 // normalises its float4 groups sub, sub + TPR ... of xr [K] and hands each as four 16-bit values to store(column, words).

@@ -118,6 +118,10 @@ struct DecGemmParams {
 // the launchers below return which instantiation they launched (the state tallies them: ohw_dbg_counter); the pick itself
 // does not depend on the tally
 // n-tiles x m-tiles per workgroup; 4x6 / 5x6: the all-rows forms behind a LayerNorm launch (two passes of three m-tiles)
+// widest K of the LN forms (fused LayerNorm: 16 threads per row, 20 float4 each).  The engine runs LN1 + QKV, the cross query
+// and LN2 + mlp.0 through them at K = n_text_state on every decode, so this is also the widest model check_hparams (model.hip)
+// lets load: one constant for both
+constexpr int DG_LN_MAXK = 1280;
 enum DecGemmShape { DG_SHAPE_1x1, DG_SHAPE_2x1, DG_SHAPE_1x2, DG_SHAPE_2x2, DG_SHAPE_4x2, DG_SHAPE_1x6, DG_SHAPE_4x6, DG_SHAPE_5x6, DG_N_SHAPES };
 template <typename T> int launch_dec_gemm(const DecGemmParams& p, int epilogue, hipStream_t s);
 

@@ -60,6 +60,8 @@ static void check_hparams(const ohw_hparams& hp) {
   auto bad = [](const char* what) { throw Error(OHW_E_LOAD_FAILED, std::string("unsupported model dimensions: ") + what); };
   if (hp.n_audio_state <= 0 || hp.n_audio_state % 128 != 0) bad("n_audio_state must be a multiple of 128");
   if (hp.n_text_state != hp.n_audio_state) bad("n_text_state != n_audio_state");
+  static_assert(DG_LN_MAXK == 1280, "the message below states the limit");
+  if (hp.n_text_state > DG_LN_MAXK) bad("n_text_state must be <= 1280 (the decoder's fused LayerNorm)");
   if (hp.n_audio_head * 64 != hp.n_audio_state || hp.n_text_head * 64 != hp.n_text_state) bad("d_head must be 64");
   if (hp.n_audio_ctx != 1500) bad("n_audio_ctx must be 1500");
   if (hp.n_text_ctx <= 0 || hp.n_text_ctx > 448) bad("n_text_ctx must be <= 448");

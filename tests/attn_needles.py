@@ -259,7 +259,7 @@ def encoder_qkv(c, packed=False, guard=0):
     return img.reshape(n_rows, 3 * d), where
 
 
-def cross_case(seed, pattern, M, n_new, t_len, kv_group=1, lens=None, ks=1):
+def cross_case(seed, pattern, M, n_new, t_len, kv_group=1, lens=None, ks=1, H=2):
     """cross-attention: row m reads window m / n_new (m / kv_group for beams); ks: the key slices the launch is expected to use"""
     per = kv_group if kv_group > 1 else n_new
     W = M // per
@@ -269,7 +269,7 @@ def cross_case(seed, pattern, M, n_new, t_len, kv_group=1, lens=None, ks=1):
     def units_of(n):
         pos = np.arange(n)
         return [xattn_slice_of(n, ks), pos // 8 % 4, pos % 8]
-    c = windows_case(seed, pattern, lens, t_len, rows_of, units_of)
+    c = windows_case(seed, pattern, lens, t_len, rows_of, units_of, H=H)
     c.ks = ks
     return c
 
