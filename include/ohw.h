@@ -201,6 +201,56 @@ void ohw_vad_energy_engine_free(ohw_vad_engine* e);
 int64_t ohw_vad_run(const ohw_vad_engine* engine, const ohw_vad_config* cfg, const float* samples, int64_t n, int64_t poll_samples,
                     ohw_speech_segment* out, int64_t cap);
 
+/* ---- speech-aware windows: a device detector, a host plan, and (further down) ohw_engine_transcribe_speech -------------
+ * The three rules below are THIS PROJECT'S OWN definitions.  None of them is the reference's (its VadState and daemon loop are
+ * the entries above) and the detector is not Silero: it is a model-free spectral rule and makes no claim to Silero's accuracy on
+ * real speech, which is unmeasured.  A host that has Silero hands its own probabilities to the plan instead (frame_samples 512).
+ *
+ * DETECTOR  ohw_state_vad_frames: one speech probability per 10 ms frame of a recording that ohw_validate_audio accepts, 16 kHz
+ * mono.  pcm: host or device samples (pcm_on_device, as ohw_mel); prob_out: HOST array of n_frames = (n + 159) / 160 floats;
+ * floor_db_out (or NULL): the noise floor.  The call uses scratch buffers of its own and leaves the state's recording, slots,
+ * mel and graphs alone.  Three launches on the state's stream (vad.hip):
+ *   band   frame t = 400 samples centred at t * 160 under the periodic Hann window of the mel front end; samples are reflected at
+ *          the recording's start only and are zero from n on;  e[t] = 10 * log10(max(sum_{k = 8..85} |X_t[k]|^2, 1e-10)), fp32:
+ *          the 320 .. 3400 Hz band of the 400-point DFT
+ *   floor  a histogram of e in 320 bins of 0.5 dB from -100 dB, bin = clamp((int)floorf((e + 100) * 2), 0, 319); the noise floor is
+ *          the lower edge of the first bin whose cumulative count reaches ceilf(floor_quantile * n_frames) (fp32; at least 1)
+ *   prob   es[t] = the mean of e over the frames of [t - 2, t + 2] that exist, summed in ascending order;
+ *          p[t] = 1 / (1 + exp(-(es[t] - floor - margin_db) / slope_db))
+ * ohw_default_vad_detector: 0.10, 9, 3.  floor_quantile in (0, 1], slope_db > 0, all three finite, else OHW_E_INVALID_ARG.     */
+typedef struct { float floor_quantile, margin_db, slope_db; } ohw_vad_detector;
+void ohw_default_vad_detector(ohw_vad_detector* d);
+int ohw_state_vad_frames(ohw_state* st, const float* pcm, int64_t n, int pcm_on_device, const ohw_vad_detector* d, float* prob_out,
+                         float* floor_db_out);
+/* SEGMENTS  ohw_speech_segments_host (host only, no device): per-frame probabilities -> speech segments, modelled on Silero's
+ * get_speech_timestamps with ohw_vad_config's fields, `enabled` ignored.  Frame f covers samples [f * frame_samples,
+ * (f + 1) * frame_samples); frame_samples is 160 for the detector above, 512 for Silero.  neg = max(threshold - 0.15, 0.01);
+ * min_silence / min_speech / pad in samples = ms * 16.  Frames in order: p >= threshold opens a segment if none is open and
+ * clears a pending end; in an open segment p < neg sets a pending end at that frame if none is set; once the frames from the
+ * pending end through the current one cover min_silence ((f + 1 - pending) * frame_samples >= min_silence) the segment closes
+ * at the pending end and is kept if (end - start) * frame_samples >= min_speech; at the end an open segment closes at n_probs under the same
+ * test.  Then every kept segment grows by the pad on both sides, neighbours whose pads would meet (gap < 2 * pad) share the gap
+ * at its midpoint (gap / 2 to the earlier one), and everything is clipped to [0, n_samples].  avg_probability: the mean of p
+ * over the unpadded frames.  Returns the number of segments (all of them; at most cap are written), or a negative error code.  */
+int64_t ohw_speech_segments_host(const float* probs, int64_t n_probs, int frame_samples, int64_t n_samples, const ohw_vad_config* cfg,
+                                 ohw_speech_segment* out, int64_t cap);
+/* CHUNKS  ohw_speech_chunks_host (host only): segments -> contiguous spans of the recording of at most max_chunk_s, each one
+ * recording of a batch.  Segments in order; a new chunk starts when the gap to the previous segment exceeds max_gap_ms or when
+ * the span from the chunk's start to this segment's end would exceed max_chunk_s.  A single segment longer than max_chunk_s is
+ * cut at the frame of lowest p in [start + max_chunk_s / 2, start + max_chunk_s) (frames that start in that range; the first
+ * minimum; no pad at the cut; the cut is at that frame's first sample) and the rule repeats on the rest; a piece in front of
+ * a cut is a chunk of its own, the rest starts a new chunk that later segments may join; with no frame in that range the cut is
+ * at start + max_chunk_s.  A chunk shorter than min_chunk_ms grows evenly on both sides into the surrounding audio,
+ * bounded by its neighbours and by the recording.  first_segment / n_segments: the segments a chunk holds (a cut segment counts
+ * in each of its pieces).  ohw_default_chunk_plan: 30, 2000, 1100.  min_chunk_ms stays above 1000: the batch path drops a cut of
+ * at most 100 frames of 10 ms (like a call with less than 1 s of audio), which would lose a short chunk's text.
+ * max_chunk_s in (0, 30].  Returns the number of chunks (at most cap are written), or a negative error code.                    */
+typedef struct { float max_chunk_s; uint32_t max_gap_ms, min_chunk_ms; } ohw_chunk_plan;
+typedef struct { int64_t start, end; int32_t first_segment, n_segments; } ohw_speech_chunk;   /* positions in samples */
+void ohw_default_chunk_plan(ohw_chunk_plan* p);
+int64_t ohw_speech_chunks_host(const ohw_speech_segment* segments, int64_t n_seg, const float* probs, int64_t n_probs, int frame_samples,
+                               int64_t n_samples, const ohw_chunk_plan* plan, ohw_speech_chunk* out, int64_t cap);
+
 /* ---- streaming glue right after the path, host code -----------------------------------------------
  *      ohw_tracker_*: TranscriptionTracker (reference src/queue/mod.rs:59-297) - chunks are registered as pending under
  *      back-pressure, results come back in any order, take_ready releases them (streaming mode: all completed chunks sorted
@@ -1033,6 +1083,33 @@ void ohw_seek_sched_free(ohw_seek_sched* s);
  * n_windows records; 0 windows for a recording under 1 s).  ohw_engine_last_* are empty after this call.                 */
 int ohw_engine_transcribe_long_batch(ohw_engine* e, const ohw_audio_span* recs, const int32_t* lang_ids, int n_recs, uint32_t sample_rate);
 int ohw_engine_long_batch_quality(ohw_engine* e, int i, const ohw_window_quality** q, int* n_windows);
+/* Speech-aware windows: recordings of ANY length that validation accepts; the speech is found, cut at its pauses into chunks of
+ * at most 30 s and the chunks of all recordings run as ONE ohw_engine_transcribe_batch: longest first, contexts per
+ * ohw_engine_set_audio_ctx, the packed encoder when set, batch-invariant kernels, on the engine's own state (no pool, lanes or
+ * pipeline).  It needs OHW_WINDOW_FIXED, as ohw_engine_transcribe_batch does.  Every recording passes ohw_validate_audio before
+ * any device work (OHW_E_VALIDATION, ohw_last_error() names the index).  Per recording: ohw_state_vad_frames - or the caller's
+ * probabilities: probs NULL = the device detector for all; else probs[i] = {p, n, frame_samples} with p NULL / n 0 = the device
+ * detector for recording i - then ohw_speech_segments_host and ohw_speech_chunks_host under ohw_engine_set_vad's settings.
+ * lang_ids: as ohw_engine_transcribe_batch_lang, per recording (every chunk of a recording gets its entry; OHW_LANG_DETECT
+ * detects per chunk); NULL: the engine's language or, with ohw_engine_set_detect_language, a detection per chunk.
+ * CONTRACT: chunk c's tokens, log-probabilities, quality record, segments, token times and word times are exactly those of
+ * ohw_engine_transcribe_batch given samples[start .. end) as a recording, the times shifted by the offset start / 16000.0 (they
+ * go through the same code with that offset).  A recording's text is its chunks' untrimmed texts joined and then trimmed, the
+ * way the fixed-cut path joins its windows.  A recording with no speech gives empty text, zero chunks and OHW_OK, and with no
+ * chunk at all no encode or decode is launched.  Beam size, best-of, hot phrases, repetition rules, the initial prompt, word
+ * timestamps and per-recording languages work as in ohw_engine_transcribe_batch.  ohw_engine_set_carry_context has NO effect:
+ * chunks decode in parallel, so none can be decoded behind another's text.
+ * Results: ohw_engine_batch_result / ohw_engine_batch_times per recording in submission order (token times' window = the chunk's
+ * index in the recording); ohw_engine_long_batch_quality lists one record per chunk; ohw_engine_speech_chunks the chunks, their
+ * count and the same quality records (any out pointer may be NULL); ohw_engine_speech_segments the segments the chunks index.
+ * ohw_engine_set_vad: NULL = the defaults of ohw_default_vad_config / _vad_detector / _chunk_plan; cfg's enabled is ignored.      */
+typedef struct { const float* p; int64_t n; int32_t frame_samples; } ohw_frame_probs;
+int ohw_engine_set_vad(ohw_engine* e, const ohw_vad_config* cfg, const ohw_vad_detector* det, const ohw_chunk_plan* plan);
+int ohw_engine_transcribe_speech(ohw_engine* e, const ohw_audio_span* recs, const ohw_frame_probs* probs, int n_recs, uint32_t sample_rate);
+int ohw_engine_transcribe_speech_lang(ohw_engine* e, const ohw_audio_span* recs, const ohw_frame_probs* probs, const int32_t* lang_ids,
+                                      int n_recs, uint32_t sample_rate);
+int ohw_engine_speech_chunks(ohw_engine* e, int i, const ohw_speech_chunk** chunks, int* n, const ohw_window_quality** quality);
+int ohw_engine_speech_segments(ohw_engine* e, int i, const ohw_speech_segment** segments, int* n);
 /* host only: how ohw_engine_transcribe_batch batches n_recs recordings of n_samples[i] samples.  order_out [n_recs]: the
  * recordings' indices, longest first (equal lengths keep submission order); batch j holds order_out[j * max_batch ..];
  * ctx_out [n_recs]: the context of recording i under audio_ctx_setting (0 -> 1500, n -> n, -1 -> ohw_audio_ctx_for);
@@ -1201,6 +1278,13 @@ int ohw_dbg_dtw(int device, const float* m_host, int n, int n_keys, int32_t* sta
 /* fill an encoder activation buffer of the state with NaN (every byte 0xff: a NaN in bf16 and in f16): what = "qkv" or "att".
  * An encode overwrites every row it owns, so a test can tell a row that was never written, or written by a neighbour. */
 int ohw_dbg_poison(ohw_state* st, const char* what);
+/* the detector's kernels alone (vad.hip).  ohw_dbg_vad_energy: vad_band_kernel on pcm (as ohw_state_vad_frames takes it; a
+ * device pointer may have samples behind n: they must not count); e_out: HOST array of (n + 159) / 160 + guard floats.
+ * ohw_dbg_vad_floor: the floor and probability kernels on a caller's HOST e array of n_frames values (any finite value);
+ * prob_out: HOST array of n_frames + guard floats, floor_db_out: one float.  The device output of n_frames + guard floats is
+ * filled with OHW_DBG_SENTINEL_F32 (defined below) first and copied back whole: the guard must still hold it.  0 <= guard <= 4096.  */
+int ohw_dbg_vad_energy(ohw_state* st, const float* pcm, int64_t n, int pcm_on_device, float* e_out, int guard);
+int ohw_dbg_vad_floor(ohw_state* st, const float* e, int64_t n_frames, const ohw_vad_detector* d, float* prob_out, int guard, float* floor_db_out);
 /* the DEVICE sampler on caller-supplied rows: logits [batch][n_vocab] (host), history [batch][hist_stride] with
  * n_hist[b] tokens sampled so far in the window.  tokens_out [batch]: the pick (end-of-text included);
  * logprobs_out [batch] / no_speech_out [batch] may be NULL (no-speech is defined for rows with n_hist == 0). */

@@ -22,7 +22,7 @@ CSRC = os.path.join(HERE, "csrc")
 VARIANT = os.environ.get("OHW_BUILD_VARIANT", "")
 OUT = os.path.join(HERE, f"libohw_{VARIANT}.so" if VARIANT else "libohw.so")
 BUILD = os.path.join(CSRC, f"_build_{VARIANT}" if VARIANT else "_build")
-SOURCES = ["gemm.hip", "gemm256.hip", "gemm_small.hip", "attention.hip", "weights.hip", "dequant.hip", "dequant_host.cpp", "mel.hip", "misc.hip", "decode.hip", "decode_persist.hip", "align.hip", "phrase.hip", "repeat.hip", "model.hip", "engine.hip", "host_engine.cpp", "transcribe.cpp", "window_policy.cpp", "pool.cpp", "dsp.cpp", "vad.cpp", "resample.hip", "tracker.cpp", "tokenize.cpp"]
+SOURCES = ["gemm.hip", "gemm256.hip", "gemm_small.hip", "attention.hip", "weights.hip", "dequant.hip", "dequant_host.cpp", "mel.hip", "vad.hip", "misc.hip", "decode.hip", "decode_persist.hip", "align.hip", "phrase.hip", "repeat.hip", "model.hip", "engine.hip", "host_engine.cpp", "transcribe.cpp", "window_policy.cpp", "pool.cpp", "dsp.cpp", "vad.cpp", "resample.hip", "tracker.cpp", "tokenize.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-ffp-contract=fast-honor-pragmas",
          "-fno-gpu-rdc"] + (["-DOHW_TRACE"] + os.environ.get("OHW_EXP_FLAGS", "").split() if VARIANT == "trace" else []) + (
              ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
@@ -52,10 +52,11 @@ def _compile(src: str, hdr: str, force: bool) -> str:
     path = os.path.join(CSRC, src)
     with open(path, "rb") as f:
         key = hashlib.sha256(f.read() + hdr.encode()).hexdigest()[:16]
-    obj = os.path.join(BUILD, f"{os.path.splitext(src)[0]}.{key}.o")
+    stem = src.replace(".", "_")           # vad.cpp and vad.hip are two objects
+    obj = os.path.join(BUILD, f"{stem}.{key}.o")
     if force or not os.path.exists(obj):
         for old in os.listdir(BUILD):
-            if old.startswith(os.path.splitext(src)[0] + ".") and old.endswith(".o"):
+            if old.startswith(stem + ".") and old.endswith(".o"):
                 os.remove(os.path.join(BUILD, old))
         cmd = [_hipcc()] + FLAGS + ["-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -224,9 +224,50 @@ def _add_transcribe_options(t):
     t.add_argument("--word-timestamps", action="store_true",
                    help="align every window's tokens on the device and add \"segments\" and \"words\" arrays (text, t0, t1 in seconds) to "
                         "the JSON; needs --align-heads")
+    _add_vad_options(t)
     t.add_argument("--align-heads", default="", metavar="L.H,L.H,...",
                    help="the (decoder layer, head) pairs whose cross-attention carries the alignment, at most 32; no preset ships "
                         "(INTEGRATION.md says where upstream lists them per checkpoint)")
+
+
+def _add_vad_options(t):
+    t.add_argument("--vad", action="store_true",
+                   help="speech-aware windows: find the speech on the device (a model-free spectral detector, not Silero), cut at the "
+                        "pauses into chunks of at most 30 s and run the chunks as one batch (WhisperEngine.transcribe_speech); "
+                        "JSON output gains \"chunks\"")
+    t.add_argument("--vad-threshold", type=float, default=None, metavar="X", help="speech probability that opens a segment (default 0.5)")
+    t.add_argument("--vad-min-silence-ms", type=int, default=None, metavar="N", help="pause that ends a segment (default 700)")
+    t.add_argument("--vad-max-gap-ms", type=int, default=None, metavar="N", help="largest pause inside one chunk (default 2000)")
+
+
+def _vad_settings(args, E):
+    """-> (VadConfig, ChunkPlan) for --vad, or None after printing an error"""
+    if not args.vad:
+        if args.vad_threshold is not None or args.vad_min_silence_ms is not None or args.vad_max_gap_ms is not None:
+            print("error: --vad-threshold, --vad-min-silence-ms and --vad-max-gap-ms need --vad", file=sys.stderr)
+            return None
+        return ()
+    cfg, plan = E.default_vad_config(), E.default_chunk_plan()
+    if args.vad_threshold is not None:
+        if not 0.0 < args.vad_threshold < 1.0:
+            print("error: --vad-threshold must be between 0 and 1", file=sys.stderr)
+            return None
+        cfg.threshold = args.vad_threshold
+    if args.vad_min_silence_ms is not None:
+        if args.vad_min_silence_ms < 0:
+            print("error: --vad-min-silence-ms must not be negative", file=sys.stderr)
+            return None
+        cfg.min_silence_ms = args.vad_min_silence_ms
+    if args.vad_max_gap_ms is not None:
+        if args.vad_max_gap_ms < 0:
+            print("error: --vad-max-gap-ms must not be negative", file=sys.stderr)
+            return None
+        plan.max_gap_ms = args.vad_max_gap_ms
+    return cfg, plan
+
+
+def _chunks_json(eng, i):
+    return [{"start": c["start"] / SAMPLE_RATE, "end": c["end"] / SAMPLE_RATE} for c in eng.speech_chunks(i)]
 
 
 def _beam_size_arg(v: str) -> int:
@@ -335,11 +376,18 @@ def _transcribe_many(args) -> int:
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         print("error: transcribe-many is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
         return 1
+    vad = _vad_settings(args, E)
+    if vad is None:
+        return 1
+    if vad and args.carry_context:
+        print("error: --vad decodes the chunks in parallel; --carry-context has no effect there", file=sys.stderr)
+        return 1
     try:
-        if E._audio_ctx_arg(args.audio_ctx) != 0:
+        audio_ctx = E._audio_ctx_arg(args.audio_ctx)
+        if audio_ctx != 0 and not vad:
             raise ValueError
     except ValueError:
-        print("error: transcribe-many runs every window at the full audio context; --audio-ctx does not apply", file=sys.stderr)
+        print("error: transcribe-many runs every window at the full audio context; --audio-ctx applies only with --vad", file=sys.stderr)
         return 1
     hot = _read_hot_phrases(args)
     if hot is None:
@@ -384,17 +432,25 @@ def _transcribe_many(args) -> int:
             return 1
     t1 = time.perf_counter()
     try:
-        results = eng.transcribe_long_batch(audios)
+        if vad:
+            eng.set_vad(vad[0], None, vad[1])
+            if audio_ctx != 0:
+                eng.set_audio_ctx(audio_ctx)
+            results = eng.transcribe_speech(audios)
+        else:
+            results = eng.transcribe_long_batch(audios)
     except E.WhisperError as ex:
         print(f"error: {ex}", file=sys.stderr)
         return 1
     dt = time.perf_counter() - t1
     total = sum(a.duration_secs() for a in audios)
     name = args.model or args.model_path.rsplit("/", 1)[-1].replace("ggml-", "").rsplit(".", 1)[0]
-    for a, res in zip(audios, results):
+    for i, (a, res) in enumerate(zip(audios, results)):
         doc = {"text": res.text, "language": res.language, "duration_ms": res.duration_ms,
                "audio_duration_secs": a.duration_secs(), "transcription_time_ms": int(dt * 1e3),
                "real_time_factor": dt / total, "model": name.lower()}
+        if vad:
+            doc["chunks"] = _chunks_json(eng, i)
         if align_heads:
             doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in res.segments]
             doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in res.words]
@@ -425,7 +481,16 @@ def _transcribe_one(args) -> int:
     except (ValueError, struct.error, EOFError) as ex:
         print(f"error: {ex}", file=sys.stderr)
         return 1
+    vad = _vad_settings(args, E)
+    if vad is None:
+        return 1
+    if vad and args.mel == "recording":
+        print("error: --vad cuts chunks as fixed windows of their own; --mel recording does not apply", file=sys.stderr)
+        return 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        if vad:
+            print("error: --vad is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+            return 1
         if audio_ctx != 0:
             print("error: --audio-ctx is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
             return 1
@@ -467,7 +532,15 @@ def _transcribe_one(args) -> int:
             print(f"error: {ex}", file=sys.stderr)
             return 1
     t1 = time.perf_counter()
-    res = eng.transcribe(audio)
+    if vad:
+        try:
+            eng.set_vad(vad[0], None, vad[1])
+            res = eng.transcribe_speech([audio])[0]
+        except E.WhisperError as ex:
+            print(f"error: {ex}", file=sys.stderr)
+            return 1
+    else:
+        res = eng.transcribe(audio)
     dt = time.perf_counter() - t1
     rtf = dt / audio.duration_secs()
     name = args.model or args.model_path.rsplit("/", 1)[-1].replace("ggml-", "").rsplit(".", 1)[0]
@@ -475,9 +548,11 @@ def _transcribe_one(args) -> int:
         doc = {"text": res.text, "language": res.language, "duration_ms": res.duration_ms,
                "audio_duration_secs": audio.duration_secs(), "transcription_time_ms": int(dt * 1e3),
                "real_time_factor": rtf, "model": name.lower()}
+        if vad:
+            doc["chunks"] = _chunks_json(eng, 0)
         if align_heads:
-            doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in eng.last_segments()]
-            doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in eng.last_words()]
+            doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in (res.segments if vad else eng.last_segments())]
+            doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in (res.words if vad else eng.last_words())]
         print(json.dumps(doc, indent=2))
     else:
         print("\n--- Transcription ---")

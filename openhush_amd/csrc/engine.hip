@@ -209,6 +209,8 @@ struct ohw_state {
   DevBuf pcm, n_samples, logmel, max_bits, mel_t;
   DevBuf rec_pcm, rec_max, rec_off;   // a whole recording, the maximum of its log-mel spectrogram, window offsets (ohw_recording_set)
   int64_t rec_n = 0;
+  // ohw_state_vad_frames: scratch of its own (staged host samples, band energies, probabilities, histogram + floor), grown on demand
+  DevBuf vad_pcm, vad_e, vad_p, vad_aux;
   // recording slots (ohw_recording_set_slot / ohw_mel_seek_slots), nothing until a slot is first set: one recording per slot,
   // each buffer sized by the largest recording the state has seen when it was (re)allocated; slot_n: samples held (0: empty);
   // slot_max: i32 [max_batch] ordered-int maxima; slot_tab: the call's tables, [entries] each of offsets i64, pointers,
@@ -1291,6 +1293,104 @@ int ohw_mel(ohw_state* st, const float* pcm, int64_t pcm_stride, const int32_t* 
       HIP_CHECK(hipMemcpyAsync(mel_out, st->logmel.p, (size_t)batch * st->ctx->hp.n_mels * CHUNK_FRAMES * 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
     }
+  });
+}
+
+// ---- the spectral speech detector (vad.hip; include/ohw.h).  Scratch of its own: the state's recording, slots, mel and graphs
+// are not touched ----
+namespace {
+VadParams vad_params(ohw_state* st, const float* pcm_dev, int64_t n, int64_t n_frames, int guard) {
+  const size_t need = (size_t)(n_frames + guard) * 4;
+  if (st->vad_e.bytes < need) st->vad_e.alloc(need);
+  if (st->vad_p.bytes < need) st->vad_p.alloc(need);
+  if (!st->vad_aux.p) st->vad_aux.alloc((VAD_BINS + 4) * 4);
+  VadParams p{};
+  p.pcm = pcm_dev; p.n = n; p.n_frames = n_frames;
+  p.twiddle = st->ctx->twiddle.as<float>(); p.window = st->ctx->window.as<float>();
+  p.energy = st->vad_e.as<float>(); p.prob = st->vad_p.as<float>();
+  p.hist = st->vad_aux.as<int32_t>(); p.floor_db = st->vad_aux.as<float>() + VAD_BINS;
+  return p;
+}
+// host samples go through the detector's own staging buffer; device samples are read where they are
+const float* vad_stage_pcm(ohw_state* st, const float* pcm, int64_t n, int pcm_on_device, hipStream_t s) {
+  if (pcm_on_device) return pcm;
+  if (st->vad_pcm.bytes < (size_t)n * 4) st->vad_pcm.alloc((size_t)n * 4);
+  HIP_CHECK(hipMemcpyAsync(st->vad_pcm.p, pcm, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  return st->vad_pcm.as<float>();
+}
+void vad_check_len(const float* pcm, int64_t n) {
+  if (!pcm || n < 1) throw Error(OHW_E_INVALID_ARG, "vad: null or empty recording");
+  if (n > (int64_t)7201 * 16000) throw Error(OHW_E_INVALID_ARG, "vad: more than two hours");
+}
+}  // namespace
+
+void ohw_default_vad_detector(ohw_vad_detector* d) {
+  if (!d) return;
+  d->floor_quantile = 0.10f; d->margin_db = 9.0f; d->slope_db = 3.0f;
+}
+
+int ohw_state_vad_frames(ohw_state* st, const float* pcm, int64_t n, int pcm_on_device, const ohw_vad_detector* d, float* prob_out,
+                         float* floor_db_out) {
+  return guard([&] {
+    if (!st || !prob_out) throw Error(OHW_E_INVALID_ARG, "vad_frames: null argument");
+    vad_check_len(pcm, n);
+    ohw_vad_detector det;
+    if (d) det = *d; else ohw_default_vad_detector(&det);
+    vad_detector_check(det);
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    const int64_t n_frames = (n + HOP - 1) / HOP;
+    const float* pcm_dev = vad_stage_pcm(st, pcm, n, pcm_on_device, s);
+    VadParams p = vad_params(st, pcm_dev, n, n_frames, 0);
+    p.target = vad_floor_target(det.floor_quantile, n_frames); p.margin_db = det.margin_db; p.slope_db = det.slope_db;
+    launch_vad_band(p, s);
+    launch_vad_floor_prob(p, s);
+    HIP_CHECK(hipMemcpyAsync(prob_out, p.prob, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s));
+    if (floor_db_out) HIP_CHECK(hipMemcpyAsync(floor_db_out, p.floor_db, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+// test entries: the detector's kernels alone, outputs sentinel-filled with guard space behind them (include/ohw.h)
+int ohw_dbg_vad_energy(ohw_state* st, const float* pcm, int64_t n, int pcm_on_device, float* e_out, int guard_n) {
+  return guard([&] {
+    if (!st || !e_out) throw Error(OHW_E_INVALID_ARG, "dbg_vad_energy: null argument");
+    if (guard_n < 0 || guard_n > 4096) throw Error(OHW_E_INVALID_ARG, "dbg_vad_energy: guard must be in 0..4096");
+    vad_check_len(pcm, n);
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    const int64_t n_frames = (n + HOP - 1) / HOP;
+    const float* pcm_dev = vad_stage_pcm(st, pcm, n, pcm_on_device, s);
+    const VadParams p = vad_params(st, pcm_dev, n, n_frames, guard_n);
+    const std::vector<float> sent((size_t)(n_frames + guard_n), OHW_DBG_SENTINEL_F32);
+    HIP_CHECK(hipMemcpyAsync(p.energy, sent.data(), sent.size() * 4, hipMemcpyHostToDevice, s));
+    launch_vad_band(p, s);
+    HIP_CHECK(hipMemcpyAsync(e_out, p.energy, sent.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+int ohw_dbg_vad_floor(ohw_state* st, const float* e, int64_t n_frames, const ohw_vad_detector* d, float* prob_out, int guard_n, float* floor_db_out) {
+  return guard([&] {
+    if (!st || !e || !prob_out || !floor_db_out) throw Error(OHW_E_INVALID_ARG, "dbg_vad_floor: null argument");
+    if (guard_n < 0 || guard_n > 4096) throw Error(OHW_E_INVALID_ARG, "dbg_vad_floor: guard must be in 0..4096");
+    if (n_frames < 1 || n_frames > (int64_t)7201 * 100) throw Error(OHW_E_INVALID_ARG, "dbg_vad_floor: n_frames out of range");
+    ohw_vad_detector det;
+    if (d) det = *d; else ohw_default_vad_detector(&det);
+    vad_detector_check(det);
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    VadParams p = vad_params(st, nullptr, 0, n_frames, guard_n);
+    p.target = vad_floor_target(det.floor_quantile, n_frames); p.margin_db = det.margin_db; p.slope_db = det.slope_db;
+    const std::vector<float> sent((size_t)(n_frames + guard_n), OHW_DBG_SENTINEL_F32);
+    HIP_CHECK(hipMemcpyAsync(p.energy, e, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(p.prob, sent.data(), sent.size() * 4, hipMemcpyHostToDevice, s));
+    const float sent_f = OHW_DBG_SENTINEL_F32;
+    HIP_CHECK(hipMemcpyAsync(p.floor_db, &sent_f, 4, hipMemcpyHostToDevice, s));
+    launch_vad_floor_prob(p, s);
+    HIP_CHECK(hipMemcpyAsync(prob_out, p.prob, sent.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(floor_db_out, p.floor_db, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
   });
 }
 

@@ -663,6 +663,60 @@ int ohw_engine_long_batch_quality(ohw_engine* e, int i, const ohw_window_quality
   });
 }
 
+// ---- speech-aware windows (include/ohw.h) ------------------------------------------------------------------------------------
+int ohw_engine_set_vad(ohw_engine* e, const ohw_vad_config* cfg, const ohw_vad_detector* det, const ohw_chunk_plan* plan) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    ohw_vad_config c; ohw_vad_detector d; ohw_chunk_plan p;
+    if (cfg) c = *cfg; else ohw_default_vad_config(&c);
+    if (det) d = *det; else ohw_default_vad_detector(&d);
+    if (plan) p = *plan; else ohw_default_chunk_plan(&p);
+    if (!std::isfinite(c.threshold)) throw Error(OHW_E_INVALID_ARG, "set_vad: the threshold is not finite");
+    if (!std::isfinite(d.floor_quantile) || !std::isfinite(d.margin_db) || !std::isfinite(d.slope_db) || !(d.floor_quantile > 0.0f) ||
+        !(d.floor_quantile <= 1.0f) || !(d.slope_db > 0.0f))
+      throw Error(OHW_E_INVALID_ARG, "set_vad: floor_quantile must be in (0, 1], slope_db above 0, and all three finite");
+    if (!std::isfinite(p.max_chunk_s) || !(p.max_chunk_s > 0.0f) || p.max_chunk_s > 30.0f || (double)p.min_chunk_ms * 16.0 > (double)p.max_chunk_s * 16000.0)
+      throw Error(OHW_E_INVALID_ARG, "set_vad: max_chunk_s must be in (0, 30] and cover min_chunk_ms");
+    e->vad_cfg = c; e->vad_det = d; e->chunk_plan = p;
+  });
+}
+
+int ohw_engine_transcribe_speech(ohw_engine* e, const ohw_audio_span* recs, const ohw_frame_probs* probs, int n_recs, uint32_t sample_rate) {
+  return ohw_engine_transcribe_speech_lang(e, recs, probs, nullptr, n_recs, sample_rate);
+}
+
+int ohw_engine_transcribe_speech_lang(ohw_engine* e, const ohw_audio_span* recs, const ohw_frame_probs* probs, const int32_t* lang_ids,
+                                      int n_recs, uint32_t sample_rate) {
+  return guard([&] {
+    if (!e || !recs || n_recs < 1) throw Error(OHW_E_INVALID_ARG, "transcribe_speech: null engine or no recordings");
+    if (e->window_mode != OHW_WINDOW_FIXED) throw Error(OHW_E_INVALID_ARG, "transcribe_speech: chunks are cut as OHW_WINDOW_FIXED cuts; set that window mode");
+    e->batch_records.clear();
+    for (int i = 0; i < n_recs; ++i) validate_or_throw(recs[i].samples, recs[i].n, sample_rate, nullptr, i);
+    engine_transcribe_speech(e, recs, probs, n_recs, lang_ids);
+  });
+}
+
+int ohw_engine_speech_chunks(ohw_engine* e, int i, const ohw_speech_chunk** chunks, int* n, const ohw_window_quality** quality) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (i < 0 || i >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "speech_chunks: no recording " + std::to_string(i) + " in the last batch call");
+    const ohw_engine::BatchRecord& r = e->batch_records[(size_t)i];
+    if (chunks) *chunks = r.chunks.data();
+    if (n) *n = (int)r.chunks.size();
+    if (quality) *quality = r.t.quality.data();
+  });
+}
+
+int ohw_engine_speech_segments(ohw_engine* e, int i, const ohw_speech_segment** segments, int* n) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (i < 0 || i >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "speech_segments: no recording " + std::to_string(i) + " in the last batch call");
+    const ohw_engine::BatchRecord& r = e->batch_records[(size_t)i];
+    if (segments) *segments = r.speech.data();
+    if (n) *n = (int)r.speech.size();
+  });
+}
+
 int ohw_engine_batch_result(ohw_engine* e, int i, const char** text, size_t* text_len, const int32_t** tokens, int* n_tokens,
                             const ohw_window_quality** quality, char* language_out) {
   return guard([&] {

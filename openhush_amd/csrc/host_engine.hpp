@@ -85,8 +85,15 @@ struct ohw_engine {
     ohw::Transcript t; int32_t lang_id = -1; bool per_window = false;
     ohw_window_quality none{};          // what ohw_engine_batch_result points at for a recording that never ran a window
     size_t n_windows() const { return per_window ? t.quality.size() : 0; }
+    // ohw_engine_transcribe_speech: the recording's speech segments and its chunks (one quality record per chunk)
+    std::vector<ohw_speech_segment> speech;
+    std::vector<ohw_speech_chunk> chunks;
   };
   std::vector<BatchRecord> batch_records;
+  // ohw_engine_set_vad: what ohw_engine_transcribe_speech detects, segments and chunks with
+  ohw_vad_config vad_cfg{0, 0.5f, 700, 250, 30};
+  ohw_vad_detector vad_det{0.10f, 9.0f, 3.0f};
+  ohw_chunk_plan chunk_plan{30.0f, 2000, 1100};
   // word timestamps (ohw_engine_set_word_timestamps): the heads every state of the engine aligns with (empty: off)
   std::vector<ohw_align_head> wt_heads;
   // language detection (ohw_engine_set_detect_language; only with language "auto" on a multilingual model).  given_lang: the pool
@@ -110,7 +117,13 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
 void engine_transcribe(ohw_engine* e, const float* samples, int64_t n, int64_t win_first = 0, int64_t win_step = 1);
 // n_recs validated recordings of at most one window each, batched longest first on the engine's own state and decoded by the
 // same per-window code; fills e->batch_records.  langs (may be null): one language id or OHW_LANG_DETECT per recording
-void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* langs);
+// t_offs (may be null: all 0): the offset of recording i on some longer recording's clock, in seconds, which its times are emitted
+// with; trim = false leaves each record's text untrimmed (the speech call joins chunks first)
+void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* langs, const double* t_offs = nullptr,
+                             bool trim = true);
+// speech-aware windows: detect (or take probs[i]), segment and chunk every validated recording, run all chunks as one
+// engine_transcribe_batch, gather per recording; fills e->batch_records
+void engine_transcribe_speech(ohw_engine* e, const ohw_audio_span* recs, const ohw_frame_probs* probs, int n_recs, const int32_t* langs);
 // recordings of any length, each through the seek loop, one window of every live recording per round (ohw_seek_sched_*); the
 // caller sets e->window_mode to OHW_WINDOW_SEEK for the call
 void engine_transcribe_long_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* langs);

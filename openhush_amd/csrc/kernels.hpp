@@ -329,6 +329,27 @@ void launch_repeat_rule(const RepeatRuleParams& p, int rows, hipStream_t s);
 void repeat_rule_check(float penalty, int ngram);
 void repeat_rule_host(float penalty, int ngram, const int32_t* history, int n_cur, float* row, int n_vocab, int eot);
 
+// ---- vad.hip: the spectral speech detector (include/ohw.h, ohw_state_vad_frames).  All pointers are device pointers ----
+constexpr int VAD_BINS = 320;          // histogram bins of 0.5 dB from -100 dB
+struct VadParams {
+  const float* pcm;         // n samples
+  int64_t n;
+  int64_t n_frames;         // (n + 159) / 160
+  const float* twiddle;     // the mel front end's [2][400] cos / sin
+  const float* window;      //   and its periodic Hann window [400]
+  float* energy;            // [n_frames] band energies in dB
+  int32_t* hist;            // [VAD_BINS], zeroed by launch_vad_floor_prob
+  float* floor_db;          // [1]
+  float* prob;              // [n_frames]
+  int32_t target;           // the cumulative count that defines the floor: ceilf(q * n_frames), 1 .. n_frames
+  float margin_db, slope_db;
+};
+void launch_vad_band(const VadParams& p, hipStream_t s);
+void launch_vad_floor_prob(const VadParams& p, hipStream_t s);
+// the detector's parameters as ohw.h states them (throws Error), and the target count of the floor's quantile
+void vad_detector_check(const ohw_vad_detector& d);
+int32_t vad_floor_target(float q, int64_t n_frames);
+
 // ---- per-window language (decode.hip; ohw_state_set_window_lang) -------------------------------------------------------
 constexpr int32_t LANG_PENDING = -1;  // table entry that waits for a detection (OHW_LANG_DETECT)
 // one workgroup per window whose table entry lang[b] is LANG_PENDING (the others are left alone): over the raw columns

@@ -836,7 +836,7 @@ void engine_transcribe(ohw_engine* e, const float* samples, int64_t n, int64_t w
 // ohw_engine_transcribe_batch: every recording one window of its own; longest first, max_batch at a time, one batch after the
 // other on the engine's own state.  Under the auto setting a batch's envelope is its largest context and every window runs at
 // its own (ohw_state_set_window_ctx) - unless all of them equal the envelope, which is the uniform path
-void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs) {
+void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs, const double* t_offs, bool trim) {
   const TranscribeCall tc(e, nullptr, 0);
   e->batch_records.assign((size_t)n_recs, ohw_engine::BatchRecord());
   std::vector<int64_t> lens((size_t)n_recs);
@@ -880,11 +880,78 @@ void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_re
     sc.cands.clear();
     for (int b = 0; b < B; ++b) {
       ohw_engine::BatchRecord& r = e->batch_records[(size_t)ord[b]];
-      tc.emit(sc.runs[(size_t)b], 0.0, (double)recs[ord[b]].n / 16000.0, r.t, e->prompt);
-      r.t.trim();
+      const double t_off = t_offs ? t_offs[ord[b]] : 0.0;
+      tc.emit(sc.runs[(size_t)b], t_off, t_off + (double)recs[ord[b]].n / 16000.0, r.t, e->prompt);
+      if (trim) r.t.trim();
       r.lang_id = per_rec ? batch_lang[(size_t)b] : -1;
     }
   }
+}
+
+// ohw_engine_transcribe_speech: the front half (detector, segments, chunks) per recording, then every chunk of every recording as
+// one recording of ONE engine_transcribe_batch - emitted with its offset on its recording's clock - and the chunk records
+// appended to their recording's, the way the fixed-cut path appends its windows
+void engine_transcribe_speech(ohw_engine* e, const ohw_audio_span* recs, const ohw_frame_probs* probs, int n_recs, const int32_t* rec_langs) {
+  std::vector<ohw_engine::BatchRecord> out((size_t)n_recs);
+  std::vector<ohw_audio_span> pool;
+  std::vector<double> offs;
+  std::vector<int32_t> pool_lang, owner;
+  std::vector<float> own;
+  for (int i = 0; i < n_recs; ++i) {
+    const int64_t n = recs[i].n;
+    const float* p = probs ? probs[i].p : nullptr;
+    int64_t n_p = probs ? probs[i].n : 0;
+    int fs = probs ? probs[i].frame_samples : 0;
+    if (!p || n_p <= 0) {                               // the device detector, 10 ms frames
+      n_p = (n + HOP - 1) / HOP; fs = HOP;
+      own.assign((size_t)n_p, 0.0f);
+      check(ohw_state_vad_frames(e->state, recs[i].samples, n, 0, &e->vad_det, own.data(), nullptr));
+      p = own.data();
+    } else if (fs < 1) {
+      throw Error(OHW_E_INVALID_ARG, "transcribe_speech: recording " + std::to_string(i) + " has probabilities with frame_samples < 1");
+    }
+    ohw_engine::BatchRecord& r = out[(size_t)i];
+    r.per_window = true;
+    r.speech.resize((size_t)n_p / 2 + 1);               // a segment needs a frame at or above the threshold and one below behind it
+    const int64_t n_seg = ohw_speech_segments_host(p, n_p, fs, n, &e->vad_cfg, r.speech.data(), (int64_t)r.speech.size());
+    if (n_seg < 0 || n_seg > (int64_t)r.speech.size()) throw Error(OHW_E_INVALID_ARG, "transcribe_speech: bad probabilities or vad settings for recording " + std::to_string(i));
+    r.speech.resize((size_t)n_seg);
+    const int64_t n_ch = ohw_speech_chunks_host(r.speech.data(), n_seg, p, n_p, fs, n, &e->chunk_plan, nullptr, 0);
+    if (n_ch < 0) throw Error(OHW_E_INVALID_ARG, "transcribe_speech: bad chunk plan for recording " + std::to_string(i));
+    r.chunks.resize((size_t)n_ch);
+    (void)ohw_speech_chunks_host(r.speech.data(), n_seg, p, n_p, fs, n, &e->chunk_plan, r.chunks.data(), n_ch);
+    for (const ohw_speech_chunk& c : r.chunks) {
+      pool.push_back(ohw_audio_span{recs[i].samples + c.start, c.end - c.start});
+      offs.push_back((double)c.start / 16000.0);
+      owner.push_back(i);
+      if (rec_langs) pool_lang.push_back(rec_langs[i]);
+    }
+  }
+  if (!pool.empty()) {
+    if (pool.size() > (size_t)0x7fffffff) throw Error(OHW_E_INVALID_ARG, "transcribe_speech: too many chunks");
+    engine_transcribe_batch(e, pool.data(), (int)pool.size(), rec_langs ? pool_lang.data() : nullptr, offs.data(), false);
+    for (size_t k = 0; k < pool.size(); ++k) {
+      ohw_engine::BatchRecord& r = out[(size_t)owner[k]];
+      const Transcript& c = e->batch_records[k].t;
+      Transcript& t = r.t;
+      const size_t text0 = t.text.size();
+      const int32_t win0 = (int32_t)t.quality.size();
+      if (win0 == 0) r.lang_id = e->batch_records[k].lang_id;          // a recording reports its first chunk's language
+      t.text += c.text;
+      t.tokens.insert(t.tokens.end(), c.tokens.begin(), c.tokens.end());
+      t.quality.insert(t.quality.end(), c.quality.begin(), c.quality.end());
+      for (ohw_token_time tt : c.token_times) { tt.window += win0; t.token_times.push_back(tt); }
+      for (ohw_span_time w : c.words) { w.text_off += text0; t.words.push_back(w); }
+      for (ohw_span_time sg : c.segments) { sg.text_off += text0; t.segments.push_back(sg); }
+      for (WindowMark m : c.marks) { m.text0 += text0; t.marks.push_back(m); }
+      t.contexts.insert(t.contexts.end(), c.contexts.begin(), c.contexts.end());
+    }
+  } else {
+    const TranscribeCall tc(e, nullptr, 0);             // what every call starts with: the last call's records are gone
+    check_recording_langs("transcribe_speech", rec_langs, n_recs, tc.tk.n_langs);
+  }
+  for (ohw_engine::BatchRecord& r : out) r.t.trim();
+  e->batch_records = std::move(out);
 }
 
 // ohw_engine_transcribe_long_batch: the seek loop of every recording, one window of each live recording per round, on the

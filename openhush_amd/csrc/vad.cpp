@@ -11,6 +11,7 @@
 //                         segment is cut from the first speech poll to the current position
 //   ohw_vad_energy_engine  a built-in detector for tests and for hosts without a model: short-time RMS against a threshold.
 //                         It is NOT Silero and makes no claim to its accuracy.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -158,6 +159,123 @@ int64_t ohw_vad_run(const ohw_vad_engine* engine, const ohw_vad_config* cfg, con
   }
   ohw_vad_state_free(st);
   return n_seg;
+}
+
+// ---- speech-aware windows: the plan (include/ohw.h).  This project's own rules, host only; tests/vad_ref.py restates them ------
+void ohw_default_chunk_plan(ohw_chunk_plan* p) {
+  if (!p) return;
+  p->max_chunk_s = 30.0f; p->max_gap_ms = 2000; p->min_chunk_ms = 1100;
+}
+
+int64_t ohw_speech_segments_host(const float* probs, int64_t n_probs, int frame_samples, int64_t n_samples, const ohw_vad_config* cfg,
+                                 ohw_speech_segment* out, int64_t cap) {
+  if (n_probs < 0 || (!probs && n_probs > 0) || frame_samples < 1 || n_samples < 0 || cap < 0 || (!out && cap > 0)) return OHW_E_INVALID_ARG;
+  ohw_vad_config c;
+  if (cfg) c = *cfg; else ohw_default_vad_config(&c);
+  if (!std::isfinite(c.threshold)) return OHW_E_INVALID_ARG;
+  const float thr = c.threshold, neg = std::max(thr - 0.15f, 0.01f);
+  const int64_t fs = frame_samples, min_silence = (int64_t)c.min_silence_ms * 16, min_speech = (int64_t)c.min_speech_ms * 16, pad = (int64_t)c.speech_pad_ms * 16;
+  struct Raw { int64_t f0, f1; };
+  std::vector<Raw> raw;
+  bool open = false;
+  int64_t start = 0, pending = -1;
+  for (int64_t f = 0; f < n_probs; ++f) {
+    const float p = probs[f];
+    if (p >= thr) {
+      if (!open) { open = true; start = f; }
+      pending = -1;
+    } else if (open) {
+      if (p < neg && pending < 0) pending = f;
+      if (pending >= 0 && (f + 1 - pending) * fs >= min_silence) {
+        if ((pending - start) * fs >= min_speech) raw.push_back(Raw{start, pending});
+        open = false; pending = -1;
+      }
+    }
+  }
+  if (open && (n_probs - start) * fs >= min_speech) raw.push_back(Raw{start, n_probs});
+  const int64_t n_seg = (int64_t)raw.size();
+  // pads: both sides; neighbours whose pads would meet share the gap at its midpoint; clipped to the recording
+  std::vector<int64_t> s((size_t)n_seg), e((size_t)n_seg);
+  for (int64_t i = 0; i < n_seg; ++i) { s[(size_t)i] = raw[(size_t)i].f0 * fs; e[(size_t)i] = raw[(size_t)i].f1 * fs; }
+  for (int64_t i = 0; i < n_seg; ++i) {
+    int64_t a = s[(size_t)i] - pad, b = e[(size_t)i] + pad;
+    if (i > 0) {
+      const int64_t gap = s[(size_t)i] - e[(size_t)i - 1];
+      if (gap < 2 * pad) a = e[(size_t)i - 1] + gap / 2;
+    }
+    if (i + 1 < n_seg) {
+      const int64_t gap = s[(size_t)i + 1] - e[(size_t)i];
+      if (gap < 2 * pad) b = e[(size_t)i] + gap / 2;
+    }
+    a = std::min(std::max<int64_t>(a, 0), n_samples);
+    b = std::min(std::max<int64_t>(b, 0), n_samples);
+    if (i < cap) {
+      double sum = 0.0;
+      for (int64_t f = raw[(size_t)i].f0; f < raw[(size_t)i].f1; ++f) sum += (double)probs[f];
+      out[i].start = a; out[i].end = b;
+      out[i].avg_probability = (float)(sum / (double)(raw[(size_t)i].f1 - raw[(size_t)i].f0));
+    }
+  }
+  return n_seg;
+}
+
+int64_t ohw_speech_chunks_host(const ohw_speech_segment* segments, int64_t n_seg, const float* probs, int64_t n_probs, int frame_samples,
+                               int64_t n_samples, const ohw_chunk_plan* plan, ohw_speech_chunk* out, int64_t cap) {
+  if (n_seg < 0 || (!segments && n_seg > 0) || n_probs < 0 || (!probs && n_probs > 0) || frame_samples < 1 || n_samples < 0 || cap < 0 ||
+      (!out && cap > 0))
+    return OHW_E_INVALID_ARG;
+  ohw_chunk_plan pl;
+  if (plan) pl = *plan; else ohw_default_chunk_plan(&pl);
+  if (!std::isfinite(pl.max_chunk_s) || !(pl.max_chunk_s > 0.0f) || pl.max_chunk_s > 30.0f) return OHW_E_INVALID_ARG;
+  const int64_t fs = frame_samples, max_len = (int64_t)((double)pl.max_chunk_s * 16000.0), max_gap = (int64_t)pl.max_gap_ms * 16,
+                min_chunk = (int64_t)pl.min_chunk_ms * 16;
+  if (max_len < 2 || min_chunk > max_len) return OHW_E_INVALID_ARG;
+  for (int64_t i = 0; i < n_seg; ++i)
+    if (segments[i].start < 0 || segments[i].end < segments[i].start || segments[i].end > n_samples || (i > 0 && segments[i].start < segments[i - 1].end))
+      return OHW_E_INVALID_ARG;
+  std::vector<ohw_speech_chunk> ch;
+  bool have = false;
+  ohw_speech_chunk cur{};
+  int64_t prev_end = 0;
+  for (int64_t i = 0; i < n_seg; ++i) {
+    int64_t s = segments[i].start;
+    const int64_t e = segments[i].end;
+    if (have && (s - prev_end > max_gap || e - cur.start > max_len)) { ch.push_back(cur); have = false; }
+    if (!have) {
+      // a segment longer than a chunk: cut at the frame of lowest p among those that start in [s + max_len / 2, s + max_len)
+      while (e - s > max_len) {
+        const int64_t lo = s + max_len / 2, hi = s + max_len;
+        int64_t cut = hi;
+        float best = 0.0f;
+        bool found = false;
+        for (int64_t f = (lo + fs - 1) / fs; f < n_probs && f * fs < hi; ++f)
+          if (!found || probs[f] < best) { best = probs[f]; cut = f * fs; found = true; }
+        ch.push_back(ohw_speech_chunk{s, cut, (int32_t)i, 1});
+        s = cut;
+      }
+      cur = ohw_speech_chunk{s, e, (int32_t)i, 1};
+      have = true;
+    } else {
+      cur.end = e;
+      ++cur.n_segments;
+    }
+    prev_end = e;
+  }
+  if (have) ch.push_back(cur);
+  // a short chunk grows evenly on both sides, bounded by its neighbours (the earlier one as already grown) and the recording
+  const int64_t n_ch = (int64_t)ch.size();
+  for (int64_t c = 0; c < n_ch; ++c) {
+    ohw_speech_chunk& k = ch[(size_t)c];
+    const int64_t need = min_chunk - (k.end - k.start);
+    if (need <= 0) continue;
+    const int64_t avail_l = k.start - (c > 0 ? ch[(size_t)c - 1].end : 0), avail_r = (c + 1 < n_ch ? ch[(size_t)c + 1].start : n_samples) - k.end;
+    int64_t a = std::min(need / 2, avail_l);
+    const int64_t b = std::min(need - a, avail_r);
+    a = std::min(need - b, avail_l);
+    k.start -= a; k.end += b;
+  }
+  for (int64_t c = 0; c < n_ch && c < cap; ++c) out[c] = ch[(size_t)c];
+  return n_ch;
 }
 
 }  // extern "C"

@@ -84,6 +84,24 @@ class SpeechSegment(C.Structure):
     _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("avg_probability", C.c_float)]
 
 
+class VadDetector(C.Structure):
+    """ohw_vad_detector: the device detector's noise-floor quantile, margin and slope (defaults 0.10, 9 dB, 3 dB)"""
+    _fields_ = [("floor_quantile", C.c_float), ("margin_db", C.c_float), ("slope_db", C.c_float)]
+
+
+class ChunkPlan(C.Structure):
+    """ohw_chunk_plan (defaults 30 s, 2000 ms, 1100 ms)"""
+    _fields_ = [("max_chunk_s", C.c_float), ("max_gap_ms", C.c_uint32), ("min_chunk_ms", C.c_uint32)]
+
+
+class SpeechChunk(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("first_segment", C.c_int32), ("n_segments", C.c_int32)]
+
+
+class FrameProbs(C.Structure):
+    _fields_ = [("p", C.POINTER(C.c_float)), ("n", C.c_int64), ("frame_samples", C.c_int32)]
+
+
 DENOISE_FRAME_FN = C.CFUNCTYPE(C.c_float, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float))
 DENOISE_RESET_FN = C.CFUNCTYPE(None, C.c_void_p)
 
@@ -430,6 +448,9 @@ EXPORTS = [
     "ohw_repeat_rule_host", "ohw_state_set_repeat_rule", "ohw_state_repeat_rule", "ohw_dbg_repeat_rule", "ohw_engine_set_repetition",
     "ohw_pool_set_repetition",
     "ohw_dbg_sample_ex",
+    "ohw_default_vad_detector", "ohw_state_vad_frames", "ohw_speech_segments_host", "ohw_default_chunk_plan", "ohw_speech_chunks_host",
+    "ohw_engine_set_vad", "ohw_engine_transcribe_speech", "ohw_engine_transcribe_speech_lang", "ohw_engine_speech_chunks",
+    "ohw_engine_speech_segments", "ohw_dbg_vad_energy", "ohw_dbg_vad_floor",
 ]
 
 
@@ -588,6 +609,23 @@ def lib():
         L.ohw_seek_sched_free.restype = None
         L.ohw_engine_transcribe_long_batch.argtypes = [vp, C.POINTER(AudioSpan), ip, C.c_int, C.c_uint32]
         L.ohw_engine_long_batch_quality.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(WindowQuality)), C.POINTER(C.c_int)]
+        L.ohw_default_vad_detector.argtypes = [C.POINTER(VadDetector)]
+        L.ohw_default_vad_detector.restype = None
+        L.ohw_default_chunk_plan.argtypes = [C.POINTER(ChunkPlan)]
+        L.ohw_default_chunk_plan.restype = None
+        L.ohw_state_vad_frames.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(VadDetector), fp, fp]
+        L.ohw_dbg_vad_energy.argtypes = [vp, vp, C.c_int64, C.c_int, fp, C.c_int]
+        L.ohw_dbg_vad_floor.argtypes = [vp, fp, C.c_int64, C.POINTER(VadDetector), fp, C.c_int, fp]
+        L.ohw_speech_segments_host.argtypes = [fp, C.c_int64, C.c_int, C.c_int64, C.POINTER(VadConfig), C.POINTER(SpeechSegment), C.c_int64]
+        L.ohw_speech_segments_host.restype = C.c_int64
+        L.ohw_speech_chunks_host.argtypes = [C.POINTER(SpeechSegment), C.c_int64, fp, C.c_int64, C.c_int, C.c_int64, C.POINTER(ChunkPlan),
+                                             C.POINTER(SpeechChunk), C.c_int64]
+        L.ohw_speech_chunks_host.restype = C.c_int64
+        L.ohw_engine_set_vad.argtypes = [vp, C.POINTER(VadConfig), C.POINTER(VadDetector), C.POINTER(ChunkPlan)]
+        L.ohw_engine_transcribe_speech.argtypes = [vp, C.POINTER(AudioSpan), C.POINTER(FrameProbs), C.c_int, C.c_uint32]
+        L.ohw_engine_transcribe_speech_lang.argtypes = [vp, C.POINTER(AudioSpan), C.POINTER(FrameProbs), ip, C.c_int, C.c_uint32]
+        L.ohw_engine_speech_chunks.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(SpeechChunk)), C.POINTER(C.c_int), C.POINTER(C.POINTER(WindowQuality))]
+        L.ohw_engine_speech_segments.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(SpeechSegment)), C.POINTER(C.c_int)]
         L.ohw_encode.argtypes = [vp, C.c_int]
         L.ohw_encode_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.ohw_detect_language.argtypes = [vp, C.c_int, ip, fp]
@@ -1274,6 +1312,44 @@ class State:
         _check(lib().ohw_mel(self.h, pcm.ctypes.data_as(C.c_void_p), stride, _ip(ns), B, 0, mode,
                              _fp(out) if want else C.cast(None, C.POINTER(C.c_float))))
         return out
+
+    def vad_frames(self, pcm, n: Optional[int] = None, detector: Optional[VadDetector] = None):
+        """ohw_state_vad_frames: (probabilities [ceil(n / 160)] float32, noise floor in dB) of a recording, one value per 10 ms
+        frame, by the device detector (this project's own spectral rule, not Silero).  pcm: a host float32 array, or - with n -
+        the address of n samples resident in HBM"""
+        on_device = isinstance(pcm, int)
+        if on_device:
+            ptr, n = C.c_void_p(pcm), int(n)
+        else:
+            x = np.ascontiguousarray(pcm, dtype=np.float32)
+            ptr, n = x.ctypes.data_as(C.c_void_p), x.size if n is None else int(n)
+        out = np.empty(max((n + 159) // 160, 0), dtype=np.float32)
+        fl = C.c_float(0.0)
+        _check(lib().ohw_state_vad_frames(self.h, ptr, n, int(on_device), C.byref(detector) if detector is not None else None,
+                                          _fp(out) if out.size else C.cast(None, C.POINTER(C.c_float)), C.byref(fl)))
+        return out, float(fl.value)
+
+    def dbg_vad_energy(self, pcm, n: Optional[int] = None, guard: int = 16):
+        """ohw_dbg_vad_energy: the band energies e [ceil(n / 160) + guard] of vad_band_kernel (the guard holds
+        OHW_DBG_SENTINEL_F32); pcm as in vad_frames"""
+        on_device = isinstance(pcm, int)
+        if on_device:
+            ptr, n = C.c_void_p(pcm), int(n)
+        else:
+            x = np.ascontiguousarray(pcm, dtype=np.float32)
+            ptr, n = x.ctypes.data_as(C.c_void_p), x.size if n is None else int(n)
+        out = np.zeros(max((n + 159) // 160, 0) + guard, dtype=np.float32)
+        _check(lib().ohw_dbg_vad_energy(self.h, ptr, n, int(on_device), _fp(out), guard))
+        return out
+
+    def dbg_vad_floor(self, e: np.ndarray, detector: Optional[VadDetector] = None, guard: int = 16):
+        """ohw_dbg_vad_floor: the floor and probability kernels on a caller's e -> (p [len(e) + guard], floor in dB)"""
+        x = np.ascontiguousarray(e, dtype=np.float32)
+        out = np.zeros(x.size + guard, dtype=np.float32)
+        fl = C.c_float(0.0)
+        _check(lib().ohw_dbg_vad_floor(self.h, _fp(x) if x.size else C.cast(None, C.POINTER(C.c_float)), x.size,
+                                       C.byref(detector) if detector is not None else None, _fp(out), guard, C.byref(fl)))
+        return out, float(fl.value)
 
     def mel_device(self, pcm_ptr: int, stride: int, n_samples: Sequence[int], mode: int = OHW_MEL_REFLECT):
         """pcm already resident in HBM (e.g. a torch tensor's data_ptr())"""
@@ -2106,6 +2182,54 @@ def vad_segments(samples: np.ndarray, config: VadConfig, poll_samples: int = 800
     return [(int(segs[i].start), int(segs[i].end), float(segs[i].avg_probability)) for i in range(min(n, cap))]
 
 
+def default_vad_config() -> VadConfig:
+    c = VadConfig()
+    lib().ohw_default_vad_config(C.byref(c))
+    return c
+
+
+def default_vad_detector() -> VadDetector:
+    d = VadDetector()
+    lib().ohw_default_vad_detector(C.byref(d))
+    return d
+
+
+def default_chunk_plan() -> ChunkPlan:
+    p = ChunkPlan()
+    lib().ohw_default_chunk_plan(C.byref(p))
+    return p
+
+
+def speech_segments_host(probs, frame_samples: int, n_samples: int, config: Optional[VadConfig] = None):
+    """ohw_speech_segments_host (no GPU): per-frame probabilities -> [(start, end, avg_probability)] in samples, padded and
+    clipped.  This project's own rule, modelled on Silero's get_speech_timestamps"""
+    p = np.ascontiguousarray(probs, dtype=np.float32)
+    cap = p.size // 2 + 1
+    segs = (SpeechSegment * cap)()
+    n = int(lib().ohw_speech_segments_host(_fp(p) if p.size else C.cast(None, C.POINTER(C.c_float)), p.size, int(frame_samples), int(n_samples),
+                                           C.byref(config) if config is not None else None, segs, cap))
+    if n < 0:
+        raise ValueError("speech_segments_host: bad probabilities or config")
+    return [(int(segs[i].start), int(segs[i].end), float(segs[i].avg_probability)) for i in range(min(n, cap))]
+
+
+def speech_chunks_host(segments, probs, frame_samples: int, n_samples: int, plan: Optional[ChunkPlan] = None):
+    """ohw_speech_chunks_host (no GPU): segments [(start, end[, avg])] -> [(start, end, first_segment, n_segments)]"""
+    p = np.ascontiguousarray(probs, dtype=np.float32)
+    segs = (SpeechSegment * max(len(segments), 1))()
+    for i, sg in enumerate(segments):
+        segs[i].start, segs[i].end = int(sg[0]), int(sg[1])
+        segs[i].avg_probability = float(sg[2]) if len(sg) > 2 else 0.0
+    args = (segs, len(segments), _fp(p) if p.size else C.cast(None, C.POINTER(C.c_float)), p.size, int(frame_samples), int(n_samples),
+            C.byref(plan) if plan is not None else None)
+    n = int(lib().ohw_speech_chunks_host(*args, None, 0))
+    if n < 0:
+        raise ValueError("speech_chunks_host: bad segments or plan")
+    out = (SpeechChunk * max(n, 1))()
+    lib().ohw_speech_chunks_host(*args, out, n)
+    return [(int(out[i].start), int(out[i].end), int(out[i].first_segment), int(out[i].n_segments)) for i in range(n)]
+
+
 class EnergyVad:
     """the built-in energy detector as a VadEngine (process(samples) -> probability): ohw_vad_energy_engine.  Not Silero."""
     def __init__(self, threshold_db: float = -40.0):
@@ -2309,6 +2433,55 @@ class WhisperEngine:
         def call(spans, langs, n, rate):
             return lib().ohw_engine_transcribe_long_batch(self.h, spans, _ip(langs) if langs is not None else None, n, rate)
         return self._batch_call("transcribe_long_batch", audios, languages, call)
+
+    def set_vad(self, config: Optional[VadConfig] = None, detector: Optional[VadDetector] = None, plan: Optional[ChunkPlan] = None):
+        """ohw_engine_set_vad: what transcribe_speech segments (config; its `enabled` is ignored), detects (detector) and chunks
+        (plan) with; None = the defaults"""
+        _check(lib().ohw_engine_set_vad(self.h, C.byref(config) if config is not None else None, C.byref(detector) if detector is not None else None,
+                                        C.byref(plan) if plan is not None else None))
+
+    def transcribe_speech(self, audios: Sequence[AudioBuffer], probs: Optional[Sequence] = None, languages: Optional[Sequence] = None) -> List[TranscriptionResult]:
+        """ohw_engine_transcribe_speech: recordings of any length; the speech of each is found (the device detector, or
+        probs[i] = (array, frame_samples) / None), cut at its pauses into chunks of at most 30 s, and the chunks of all recordings
+        run as one transcribe_batch; times are on each recording's own clock.  Chunk c of recording i is transcribe_batch of its
+        slice, bit for bit.  speech_chunks(i): the chunks and their quality records; languages as in transcribe_batch"""
+        if not audios:
+            return []
+        fpr, keep = None, []
+        if probs is not None:
+            if len(probs) != len(audios):
+                raise ValueError("transcribe_speech: one probs entry (or None) per recording")
+            fpr = (FrameProbs * len(audios))()
+            for i, pr in enumerate(probs):
+                if pr is None:
+                    fpr[i].p, fpr[i].n, fpr[i].frame_samples = C.cast(None, C.POINTER(C.c_float)), 0, 0
+                else:
+                    a = np.ascontiguousarray(pr[0], dtype=np.float32)
+                    keep.append(a)
+                    fpr[i].p, fpr[i].n, fpr[i].frame_samples = _fp(a) if a.size else C.cast(None, C.POINTER(C.c_float)), a.size, int(pr[1])
+
+        def call(spans, langs, n, rate):
+            return lib().ohw_engine_transcribe_speech_lang(self.h, spans, fpr, _ip(langs) if langs is not None else None, n, rate)
+        return self._batch_call("transcribe_speech", audios, languages, call)
+
+    def speech_chunks(self, i: int):
+        """ohw_engine_speech_chunks: [{"start", "end" (samples), "first_segment", "n_segments", "quality": dict}] of recording i
+        of the last transcribe_speech"""
+        ch, n, q = C.POINTER(SpeechChunk)(), C.c_int(0), C.POINTER(WindowQuality)()
+        _check(lib().ohw_engine_speech_chunks(self.h, int(i), C.byref(ch), C.byref(n), C.byref(q)))
+        out = []
+        for k in range(n.value):
+            d = {name: getattr(q[k], name) for name, _ in WindowQuality._fields_}
+            d["would_fallback"], d["no_speech"], d["failed"] = bool(d["would_fallback"]), bool(d["no_speech"]), bool(d["failed"])
+            out.append({"start": int(ch[k].start), "end": int(ch[k].end), "first_segment": int(ch[k].first_segment),
+                        "n_segments": int(ch[k].n_segments), "quality": d})
+        return out
+
+    def speech_segments(self, i: int):
+        """ohw_engine_speech_segments: [(start, end, avg_probability)] of recording i of the last transcribe_speech"""
+        sg, n = C.POINTER(SpeechSegment)(), C.c_int(0)
+        _check(lib().ohw_engine_speech_segments(self.h, int(i), C.byref(sg), C.byref(n)))
+        return [(int(sg[k].start), int(sg[k].end), float(sg[k].avg_probability)) for k in range(n.value)]
 
     def long_batch_quality(self, i: int):
         """one dict per window of recording i of the last transcribe_long_batch with every ohw_window_quality field"""
