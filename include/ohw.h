@@ -607,6 +607,95 @@ int ohw_dbg_repeat_rule(ohw_state* st, float* logits, int rows, int64_t ld, int 
                         const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int ngram,
                         int eot);
 
+/* command lists: constrain a window to a closed list of phrases, on the device ahead of every sampler of every decoder.
+ * whisper.cpp does this with grammar / grammar_penalty in whisper_full_params and its `command` example: rejected text tokens
+ * are lowered by grammar_penalty (default 100), and end-of-text too while the grammar cannot accept - recalled from upstream,
+ * unpinned.  A phrase list is the finite special case of that grammar; the rule below is this project's definition of it
+ * (DESIGN.md section 9).  Off by default: with no list set nothing is launched, and every token, log-probability, counter and
+ * captured graph is what it is without the feature.
+ *   A list is 1..OHW_PHRASE_MAX_PHRASES phrases of 1..OHW_PHRASE_MAX_LEN text token ids (each in [0, eot)); phrase i is
+ *   tokens[offsets[i] .. offsets[i + 1]); duplicates are allowed.  It compiles into an ANCHORED trie, ohw_command_table: every
+ *   prefix of every phrase is a node, the empty prefix (the root, depth 0) and the full phrases (up to depth 16) included.  Nodes
+ *   are ordered by depth, then by path, lexicographically, as in ohw_phrase_table; the path of node n of depth d is
+ *   path[path_base[d] + (n - depth_start[d]) * d ..+ d), its children are child_tok[child_off[n] .. child_off[n + 1]), sorted and
+ *   unique; terminal[n] = 1 when some phrase ends at n, and phrase_id[n] = the lowest index of such a phrase, else -1.
+ *   Per live row and step, behind the hot-phrase boost and the repetition rule and ahead of the sampler (which adds the static
+ *   bias and runs its own filter afterwards): h = the row's own sampled tokens tokens[0 .. n_cur), the history the other two rules
+ *   use (no prompt, no prefilled context; a beam row: that beam's view); nothing at or behind tokens[n_cur] is read.  t = the
+ *   entries of h in [0, eot), in order: timestamps and other specials are skipped, so a leading <|0.00|> breaks no match.
+ *   d = len(t).  The row's node is the depth-d node whose path equals t; with d > 16 or no such node the row is OFF THE LIST.
+ *   With penalty p:
+ *     text tokens   every column < eot that is not a child of the row's node becomes fl32(x - p), with p = +inf OHW_REPEAT_BAN
+ *                   (finite, for the reason given there); children are not touched; off the list every text column is lowered
+ *     end-of-text   lowered the same way, unless the node is terminal or the row is off the list: then it is not touched
+ *     >= eot + 1    timestamps and every other id: never touched
+ *   Each word is read once and written at most once; words the rule leaves alone are not rewritten.  The host twin does the same
+ *   single fp32 subtraction, so the two agree to the bit.  0 < p <= OHW_COMMAND_PENALTY_MAX or p = +inf; NaN, zero and negatives
+ *   are OHW_E_INVALID_ARG.
+ *   List probability: at a step with d == 0 the first decoder row of each window also writes list_logprob[window] =
+ *   LSE(x over the root's children) - LSE(x over all columns < eot), in fp32 on the row as the kernel finds it, before lowering:
+ *   given that text comes next, the probability that the unconstrained model starts a listed phrase - the handle for rejecting
+ *   off-list speech, like the first step's no-speech probability.  The latest such step wins (with timestamps, usually the step
+ *   behind the opening timestamp).  -inf logits mean "never" and enter neither sum; all children at -inf give -inf, not NaN.
+ *   Rows with d == 0 of a window's first decoder row are read a second time for this (the maxima first, then the sums).
+ *   Consequences: the lowered row is inside sum_logprob, token_logprobs, the acceptance thresholds, best-of ranking, beam scores
+ *   and the first step's no-speech probability, as the boost is: under a hard list a silent window can pass the no-speech rule;
+ *   list_logprob and the speech detector are the remedies.  ohw_state_fetch("logits") returns lowered rows while a list is set.
+ *   Language detection, ohw_state_align, prefill, the persistent step and the ohw_dbg_sample* / ohw_dbg_beam_step* entries are
+ *   untouched.  A row can always finish: a node that is not terminal has a child, terminal and off-list rows keep end-of-text,
+ *   timestamps are never touched.  The sampler's own filter (suppress_blank, timestamp pairing) still applies afterwards: a
+ *   phrase whose first token is the model's blank token cannot start a window.
+ * ohw_command_table: the caller owns the five arrays, sized for the limits.  ohw_command_table_build_host: compiles a list on the
+ *   host, no device; the refusals of ohw_phrase_table_build_host, the phrase named; n_phrases = 0 gives the empty table.
+ * ohw_command_rule_host: the rule on one row on the host: history [>= n_cur], row [n_vocab] changed in place; *list_logprob_out
+ *   (may be null) is written only when d == 0, summed in double.  ohw_command_match_host: phrase_id of the node whose path equals
+ *   the entries of tokens[0 .. n) below the table's eot, when it is terminal; else -1.
+ * ohw_state_set_command_table: compiles the list (eot = the model's) and sets it with the penalty for every later ohw_greedy*,
+ *   ohw_sample_pass, ohw_sample_pass_n and ohw_beam_search* call; n_phrases = 0 clears it.  The device copy is one buffer sized
+ *   for the limits (about 0.8 MB) holding the penalty too, made at the first set: "a list is set" is part of the step-graph keys,
+ *   and swapping lists or penalties captures nothing again.  ohw_state_command_count: phrases of the list in effect (0: none).
+ * ohw_state_command_list_logprob: out[0 .. batch) = list_logprob of the windows of the last decoding call on this state.  An entry
+ *   is written by its window's d == 0 steps only: a window that was done when the call began keeps its earlier value, and before
+ *   any such step an entry is NaN.  OHW_E_INVALID_ARG with no list set or batch outside 1..max_batch.
+ * ohw_dbg_command_rule: test entry, the kernel once on caller data, the arguments and checks of ohw_dbg_repeat_rule: logits
+ *   [rows][ld] come back whole (guard rows and columns included), list_logprob [n_entries] is read and written back whole (fill
+ *   it with a sentinel), row h writes it when h % group == 0.  The state's own list is in effect again afterwards.
+ * ohw_engine_set_commands: the text form.  texts[i] is tokenised with ohw_tokenize as given and with a leading space; both forms
+ *   belong to index i (a form without a token, or equal to the other, is dropped; a text with no token at all:
+ *   OHW_E_INVALID_ARG, the text named).  ohw_tokenize is a greedy longest-match and not BPE merging, so it may split a word
+ *   otherwise than the model's tokenizer would: ohw_engine_set_commands_tokens is the exact form.  n = 0 clears.  The engine sets
+ *   the list on its own, pipeline and lane states, states made later included; its host-sampled ladder applies
+ *   ohw_command_rule_host right behind ohw_repeat_rule_host.  ohw_pool_set_commands: the text form on every engine of the pool.
+ * ohw_engine_last_commands: one ohw_command_hit per kept window of the last transcribe call (of recording i of a batch call, in
+ *   window order, `window` counted within the recording): phrase = the caller's index when the kept tokens' text tokens equal a
+ *   listed phrase exactly, else -1; list_logprob belongs to the kept pass, device and host ladders alike.  Empty with no list.  */
+#define OHW_COMMAND_PENALTY_MAX 1000.0f
+#define OHW_COMMAND_PENALTY_DEFAULT 100.0f
+#define OHW_COMMAND_MAX_NODES (1 + OHW_PHRASE_MAX_PHRASES * OHW_PHRASE_MAX_LEN)
+#define OHW_COMMAND_MAX_EDGES (OHW_PHRASE_MAX_PHRASES * OHW_PHRASE_MAX_LEN)
+#define OHW_COMMAND_MAX_PATH (OHW_PHRASE_MAX_PHRASES * OHW_PHRASE_MAX_LEN * (OHW_PHRASE_MAX_LEN + 1) / 2)
+typedef struct {
+  int32_t n_phrases, n_nodes, n_edges, n_path, eot;
+  int32_t depth_start[OHW_PHRASE_MAX_LEN + 2];
+  int32_t path_base[OHW_PHRASE_MAX_LEN + 1];
+  int32_t* child_off;   /* [OHW_COMMAND_MAX_NODES + 1] */
+  int32_t* path;        /* [OHW_COMMAND_MAX_PATH] */
+  int32_t* child_tok;   /* [OHW_COMMAND_MAX_EDGES] */
+  int32_t* terminal;    /* [OHW_COMMAND_MAX_NODES] */
+  int32_t* phrase_id;   /* [OHW_COMMAND_MAX_NODES] */
+} ohw_command_table;
+typedef struct { int32_t window, phrase; float list_logprob; } ohw_command_hit;
+int ohw_command_table_build_host(const int32_t* tokens, const int32_t* offsets, int n_phrases, int eot, ohw_command_table* out);
+int ohw_command_rule_host(const ohw_command_table* table, float penalty, const int32_t* history, int n_cur, float* row, int n_vocab,
+                          int eot, float* list_logprob_out);
+int ohw_command_match_host(const ohw_command_table* table, const int32_t* tokens, int n);
+int ohw_state_set_command_table(ohw_state* st, const int32_t* tokens, const int32_t* offsets, int n_phrases, float penalty);
+int ohw_state_command_count(const ohw_state* st);
+int ohw_state_command_list_logprob(ohw_state* st, int batch, float* out);
+int ohw_dbg_command_rule(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                         const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int eot,
+                         const ohw_command_table* table, float* list_logprob);
+
 /* the persistent small-batch decoder step (default OFF; OHW_DEC_PERSIST=1 turns it on for new states): single-token steps
  * of at most 16 rows - one utterance, the K rows of a beam search - run their 32 layers as ONE launch whose workgroups hand
  * activations to each other (openhush_amd/csrc/decode_persist.hip) instead of 8 launches per layer.  Correct (tests/
@@ -987,6 +1076,12 @@ int ohw_engine_set_hot_phrases_tokens(ohw_engine* e, const int32_t* tokens, cons
 /* repetition penalty and no-repeat n-gram size on every state the engine decodes on (ohw_state_set_repeat_rule states the rule);
  * (1.0, 0), the default, is off */
 int ohw_engine_set_repetition(ohw_engine* e, float penalty, int ngram);
+/* a command list on every state the engine decodes on (ohw_state_set_command_table states the rule, both forms and the hits);
+ * ohw_engine_batch_commands: the hits of recording i of the last ohw_engine_transcribe_batch / _long_batch / _speech call */
+int ohw_engine_set_commands(ohw_engine* e, const char* const* texts, int n, float penalty);
+int ohw_engine_set_commands_tokens(ohw_engine* e, const int32_t* tokens, const int32_t* offsets, int n_phrases, float penalty);
+int ohw_engine_last_commands(ohw_engine* e, const ohw_command_hit** hits, int* n);
+int ohw_engine_batch_commands(ohw_engine* e, int i, const ohw_command_hit** hits, int* n);
 /* carried context in the seek loops (whisper.cpp's prompt_past / n_max_text_ctx, as recalled): max_tokens 0 (default) = off,
  * -1 = on with the full cap of ohw_prompt_clip_host, n > 0 = on with at most n tokens (whisper.cpp's --max-context); below -1:
  * OHW_E_INVALID_ARG.  It applies to OHW_WINDOW_SEEK in ohw_engine_transcribe and to ohw_engine_transcribe_long_batch, one
@@ -1173,6 +1268,7 @@ int ohw_pool_set_window_mode(ohw_pool* p, int mode);
 int ohw_pool_set_initial_prompt(ohw_pool* p, const char* text);           /* ohw_engine_set_initial_prompt on every engine */
 int ohw_pool_set_hot_phrases(ohw_pool* p, const char* const* texts, const float* boosts, int n);   /* ohw_engine_set_hot_phrases on every engine */
 int ohw_pool_set_repetition(ohw_pool* p, float penalty, int ngram);       /* ohw_engine_set_repetition on every engine */
+int ohw_pool_set_commands(ohw_pool* p, const char* const* texts, int n, float penalty);   /* ohw_engine_set_commands on every engine */
 int ohw_pool_set_best_of(ohw_pool* p, int n);                             /* ohw_engine_set_best_of on every engine */
 int ohw_pool_set_carry_context(ohw_pool* p, int max_tokens);              /* ohw_engine_set_carry_context on every engine */
 int ohw_pool_set_audio_ctx(ohw_pool* p, int n);                           /* ohw_engine_set_audio_ctx on every engine */
@@ -1203,6 +1299,7 @@ int ohw_abi_version(void);
 /* "logits" [batch][n_vocab]: the first batch decoder rows (at most max_batch) of the last decoder   */
 /* step's logits as its sampler saw them: the hot-phrase boost included while a table is set         */
 /* and the repetition rule's changes while it is on (ohw_state_set_repeat_rule)                      */
+/* and the command list's while one is set (ohw_state_set_command_table)                            */
 int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int64_t out_elems);
 /* 64-bit digest of the index-th resident weight buffer (engine layout); returns OHW_E_INVALID_ARG  */
 /* past the last buffer.  Lets tests prove "synthetic ctx == ctx loaded from the synthetic file".  */
@@ -1328,6 +1425,7 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  *                                      ".fused_slots": the same inside the QKV launch (OHW_DEC_FUSE_ATTN=1)
  *   "phrase_boost"                     launches of the hot-phrase kernel (ohw_state_set_phrase_table); 0 with no table
  *   "repeat_rule"                      launches of the repetition kernel (ohw_state_set_repeat_rule); 0 while the rule is off
+ *   "command_rule"                     launches of the command-list kernel (ohw_state_set_command_table); 0 with no list
  * The persistent step (ohw_state_set_persistent) counts only its logits GEMM.                                    */
 int ohw_dbg_counter(const ohw_state* st, const char* name);
 

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import struct
 import sys
@@ -89,7 +90,7 @@ def load_wav_file(path: str, quality: str = "high") -> np.ndarray:
     return np.ascontiguousarray(s, dtype=np.float32)
 
 
-def _transcribe_ranks(args, audio) -> int:
+def _transcribe_ranks(args, audio, commands=()) -> int:
     """one process per GPU under torch.distributed.run: shard the windows, gather the tokens, rank 0 prints"""
     import torch
     import torch.distributed as dist
@@ -121,8 +122,9 @@ def _transcribe_ranks(args, audio) -> int:
     t1 = time.perf_counter()
     by_index = args.mel == "recording"
     rep = _repetition(args)             # every rank decodes its windows under the same rule
-    runner = (shard.recording_window_runner(ctx, args.max_batch, audio.samples, p, repetition=rep) if by_index
-              else shard.engine_window_runner(ctx, args.max_batch, p, repetition=rep))
+    cmds = (commands, args.command_penalty) if commands else None        # and under the same list; the JSON carries no "commands" here
+    runner = (shard.recording_window_runner(ctx, args.max_batch, audio.samples, p, repetition=rep, commands=cmds) if by_index
+              else shard.engine_window_runner(ctx, args.max_batch, p, repetition=rep, commands=cmds))
     wins = shard.transcribe_sharded(runner, audio.samples, n_win, ctx.hp.n_text_ctx, dist, world, rank, torch.device("cuda", local),
                                     by_index=by_index)
     dt = time.perf_counter() - t1
@@ -165,6 +167,30 @@ def main(argv=None) -> int:
     return _transcribe_one(args)
 
 
+def _read_commands(args):
+    """--commands FILE -> the phrases, () without the option, None after an error message"""
+    if not args.commands:
+        return ()
+    from . import engine as E
+    try:
+        with open(args.commands, encoding="utf-8") as f:
+            phrases = E.parse_commands(f.read())
+        if not phrases:
+            raise ValueError("the file holds no phrase")
+        if len(phrases) > E.PHRASE_MAX_PHRASES // 2:
+            raise ValueError(f"{len(phrases)} phrases, at most {E.PHRASE_MAX_PHRASES // 2} fit (each in two forms)")
+        return phrases
+    except (OSError, ValueError) as ex:
+        print(f"error: --commands: {ex}", file=sys.stderr)
+        return None
+
+
+def _commands_json(hits, phrases):
+    """WhisperEngine.last_commands() as the JSON carries it: the phrase's text beside its index, null for a list_logprob that is not finite"""
+    return [{"window": h["window"], "index": h["index"], "phrase": phrases[h["index"]] if h["index"] >= 0 else None,
+             "list_logprob": h["list_logprob"] if math.isfinite(h["list_logprob"]) else None} for h in hits]
+
+
 def _read_hot_phrases(args):
     """--hot-phrases FILE with --hot-phrase-boost X -> (phrases, boosts), () without the option, None after an error message"""
     if not args.hot_phrases:
@@ -203,6 +229,13 @@ def _add_transcribe_options(t):
                         "window's own tokens end in the front part of a phrase, its next token is raised by the boost")
     t.add_argument("--hot-phrase-boost", type=float, default=2.0, metavar="X",
                    help="the boost of every --hot-phrases line that carries none (default 2.0)")
+    t.add_argument("--commands", default=None, metavar="FILE",
+                   help="a closed list of phrases, one per line: every window is held to the list (whisper.cpp's grammar for a fixed "
+                        "vocabulary) and the JSON gains \"commands\": per window the index and text of the phrase it was, or -1, and "
+                        "list_logprob, the log-probability that the unconstrained model starts a listed phrase")
+    t.add_argument("--command-penalty", type=_command_penalty_arg, default=100.0, metavar="X|inf",
+                   help="how far a text token that leaves the list, and end-of-text inside a phrase, is lowered, in logit units: "
+                        "0 < X <= 1000, or inf for a hard list (default 100, whisper.cpp's grammar_penalty)")
     t.add_argument("--repetition-penalty", type=_repetition_penalty_arg, default=1.0, metavar="X",
                    help="scale the logit of every text token a window has already emitted away from the sampler (x / X above 0, "
                         "x * X below; faster-whisper's repetition_penalty), 0.01..100; 1.0 (default): off")
@@ -287,6 +320,17 @@ def _repetition_penalty_arg(v: str) -> float:
         x = float("nan")
     if not 0.01 <= x <= 100.0:                      # false for NaN
         raise argparse.ArgumentTypeError(f"takes a penalty in 0.01..100 (1.0: off), not '{v}'")
+    return x
+
+
+def _command_penalty_arg(v: str) -> float:
+    x = float("nan")
+    try:
+        x = float(v)
+    except ValueError:
+        pass
+    if not (0.0 < x <= 1000.0 or x == float("inf")):          # false for NaN
+        raise argparse.ArgumentTypeError(f"takes a penalty in (0, 1000] or inf, not '{v}'")
     return x
 
 
@@ -392,6 +436,9 @@ def _transcribe_many(args) -> int:
     hot = _read_hot_phrases(args)
     if hot is None:
         return 1
+    commands = _read_commands(args)
+    if commands is None:
+        return 1
     audios = []
     for f in args.files:
         if not os.path.isfile(f):
@@ -414,6 +461,12 @@ def _transcribe_many(args) -> int:
         eng.set_hot_phrases(*hot)
     if _repetition(args):
         eng.set_repetition(*_repetition(args))
+    if commands:
+        try:
+            eng.set_commands(commands, args.command_penalty)
+        except E.WhisperError as ex:
+            print(f"error: --commands: {ex}", file=sys.stderr)
+            return 1
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
     if args.best_of > 1:
@@ -451,6 +504,8 @@ def _transcribe_many(args) -> int:
                "real_time_factor": dt / total, "model": name.lower()}
         if vad:
             doc["chunks"] = _chunks_json(eng, i)
+        if commands:
+            doc["commands"] = _commands_json(eng.last_commands(i), commands)
         if align_heads:
             doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in res.segments]
             doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in res.words]
@@ -472,6 +527,9 @@ def _transcribe_one(args) -> int:
         return 1
     hot = _read_hot_phrases(args)
     if hot is None:
+        return 1
+    commands = _read_commands(args)
+    if commands is None:
         return 1
     if not os.path.isfile(args.file):            # reference src/main.rs:985-987 and tests/cli_integration.rs:262-269
         print(f"error: File not found: {args.file}", file=sys.stderr)
@@ -500,7 +558,7 @@ def _transcribe_one(args) -> int:
         if hot:
             print("error: --hot-phrases is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
             return 1
-        return _transcribe_ranks(args, audio)
+        return _transcribe_ranks(args, audio, commands)
     use_gpu = args.device.lower() != "cpu"                    # reference src/main.rs:1037
     dev = int(args.device.split(":")[1]) if ":" in args.device else 0
     t0 = time.perf_counter()
@@ -517,6 +575,12 @@ def _transcribe_one(args) -> int:
         eng.set_hot_phrases(*hot)
     if _repetition(args):
         eng.set_repetition(*_repetition(args))
+    if commands:
+        try:
+            eng.set_commands(commands, args.command_penalty)
+        except E.WhisperError as ex:
+            print(f"error: --commands: {ex}", file=sys.stderr)
+            return 1
     if args.beam_size:
         eng.set_beam_size(args.beam_size)
     if args.best_of > 1:
@@ -550,6 +614,8 @@ def _transcribe_one(args) -> int:
                "real_time_factor": rtf, "model": name.lower()}
         if vad:
             doc["chunks"] = _chunks_json(eng, 0)
+        if commands:
+            doc["commands"] = _commands_json(eng.last_commands(0 if vad else None), commands)
         if align_heads:
             doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in (res.segments if vad else eng.last_segments())]
             doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in (res.words if vad else eng.last_words())]

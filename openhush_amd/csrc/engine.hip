@@ -120,10 +120,11 @@ struct GraphKey {
   bool flag = false;   // step cache: a temperature pass; beam cache: log-probability history on (other pointers baked in)
   bool phrases = false;   // a hot-phrase table is set: the iteration holds the boost kernel (which table is device data)
   bool repeat = false;    // the repetition rule is on: the iteration holds its kernel (the values are device data)
+  bool commands = false;  // a command list is set: the iteration holds its kernel (list and penalty are device data)
   SamplerParams spar;  // compared byte by byte: fill_sampler zeroes the struct, padding included, before it fills it
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && group == o.group && cus == o.cus && t_len == o.t_len && var == o.var && invariant == o.invariant &&
-           persist == o.persist && flag == o.flag && phrases == o.phrases && repeat == o.repeat && std::memcmp(&spar, &o.spar, sizeof spar) == 0;
+           persist == o.persist && flag == o.flag && phrases == o.phrases && repeat == o.repeat && commands == o.commands && std::memcmp(&spar, &o.spar, sizeof spar) == 0;
   }
 };
 // one entry = the graph of a key's iteration, or the PAIR of a key whose iterations alternate between two forms (beam search:
@@ -283,6 +284,15 @@ struct ohw_state {
   int rp_ngram = 0;
   bool rp_on = false;
   int64_t tally_repeat = 0;        // repeat_rule_kernel launches (ohw_dbg_counter "repeat_rule")
+  // command list (ohw_state_set_command_table): the anchored trie and the penalty in one fixed-size device buffer (kernels.hpp,
+  // CM_WORDS) and list_logprob [max_batch], both made at the first set; cm_host: the same table on the host (the engine's
+  // host-sampled ladder applies it there) with the arrays it points into; cm_src_*: the phrases as they were given
+  DevBuf cm_table, cm_lp;
+  bool cm_on = false;
+  float cm_penalty = OHW_COMMAND_PENALTY_DEFAULT;
+  ohw_command_table cm_host{};
+  std::vector<int32_t> cm_child_off, cm_path, cm_child_tok, cm_terminal, cm_phrase_id, cm_src_tok, cm_src_off;
+  int64_t tally_command = 0;       // command_rule_kernel launches (ohw_dbg_counter "command_rule")
   int m_max = 0;
   int64_t logits_ld = 0;
   // per-kernel-class profiling (bench): event pairs around every launch of one class
@@ -369,7 +379,7 @@ namespace {
 GraphKey graph_key(const ohw_state* st, int rows, int group, bool flag, const SamplerParams& spar) {
   GraphKey k;
   k.rows = rows; k.group = group; k.cus = st->stream_cus; k.t_len = st->enc_ctx; k.var = st->enc_var; k.invariant = st->batch_invariant;
-  k.persist = st->persist; k.flag = flag; k.phrases = st->ph_on; k.repeat = st->rp_on;
+  k.persist = st->persist; k.flag = flag; k.phrases = st->ph_on; k.repeat = st->rp_on; k.commands = st->cm_on;
   std::memcpy(&k.spar, &spar, sizeof spar);
   return k;
 }
@@ -943,8 +953,10 @@ void fill_sampler(const ohw_state* st, const ohw_sample_params* sp, int B, Sampl
 }
 
 // the history-dependent logit rules ahead of a sampler launch (kernels.hpp states the row mapping): the hot-phrase boost, then
-// the repetition rule; nothing without a table and with the rule off
-void boost_rows(ohw_state* st, const SamplerParams& p, int rows, int row_mul, int group, const int32_t* n_cur, const int32_t* done, hipStream_t s) {
+// the repetition rule, then the command list; nothing without a table or a list and with the rule off.  lp_group: the decoder
+// rows per window among the launch rows (0: group), which only the command list's list_logprob needs
+void boost_rows(ohw_state* st, const SamplerParams& p, int rows, int row_mul, int group, const int32_t* n_cur, const int32_t* done, hipStream_t s,
+                int lp_group = 0) {
   if (st->ph_on) {
     PhraseBoostParams b{};
     b.logits = st->logits.as<float>(); b.ld = p.ld; b.n_vocab = p.n_vocab; b.max_tokens = p.max_tokens; b.row_mul = row_mul; b.group = group;
@@ -960,6 +972,15 @@ void boost_rows(ohw_state* st, const SamplerParams& p, int rows, int row_mul, in
     q.eot = p.eot; q.tokens = p.tokens; q.n_cur = n_cur; q.done = done; q.rule = st->rp_rule.as<int32_t>();
     launch_repeat_rule(q, rows, s);
     ++st->tally_repeat;
+  }
+  // null n_cur launches here: the first step is where the root applies
+  if (st->cm_on) {
+    CommandRuleParams q{};
+    q.logits = st->logits.as<float>(); q.ld = p.ld; q.n_vocab = p.n_vocab; q.max_tokens = p.max_tokens; q.row_mul = row_mul; q.group = group;
+    q.lp_group = lp_group > 0 ? lp_group : group;
+    q.eot = p.eot; q.tokens = p.tokens; q.n_cur = n_cur; q.done = done; q.table = st->cm_table.as<int32_t>(); q.list_logprob = st->cm_lp.as<float>();
+    launch_command_rule(q, rows, s);
+    ++st->tally_command;
   }
 }
 
@@ -1249,6 +1270,17 @@ bool state_repeat_rule_host(const ohw_state* st, float* penalty, int* ngram) {
   if (!st || !st->rp_on) return false;
   *penalty = st->rp_penalty; *ngram = st->rp_ngram;
   return true;
+}
+// a state's command list as the host-sampled ladder and the engine's fan-out need it: null while none is set
+const ohw_command_table* state_command_table_host(const ohw_state* st, float* penalty) {
+  if (!st || !st->cm_on) return nullptr;
+  if (penalty) *penalty = st->cm_penalty;
+  return &st->cm_host;
+}
+int state_commands_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets) {
+  if (!st || !st->cm_on) return 0;
+  *tokens = st->cm_src_tok.data(); *offsets = st->cm_src_off.data();
+  return st->cm_host.n_phrases;
 }
 int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts) {
   if (!st || !st->ph_on) return 0;
@@ -1890,7 +1922,7 @@ static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W,
       spar.advance = 1;
       auto iteration = [&](int, hipStream_t q) {
         run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
-        boost_rows(st, spar, R, 1, 1, spar.n_cur, spar.done, q);
+        boost_rows(st, spar, R, 1, 1, spar.n_cur, spar.done, q, N);     // a window's N candidates are neighbours
         launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
       };
       const bool use_graph = st->graphs_enabled && st->prof_class == 0 && s != nullptr;
@@ -2122,6 +2154,7 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "xattn.chunk") return (int)std::min<int64_t>(st->tally_xchunk, INT32_MAX);
   if (n == "phrase_boost") return (int)std::min<int64_t>(st->tally_phrase, INT32_MAX);
   if (n == "repeat_rule") return (int)std::min<int64_t>(st->tally_repeat, INT32_MAX);
+  if (n == "command_rule") return (int)std::min<int64_t>(st->tally_command, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
   auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
   for (int g = 0; g < DT_GEMMS; ++g)
@@ -2510,6 +2543,108 @@ int ohw_dbg_repeat_rule(ohw_state* st, float* logits, int rows, int64_t ld, int 
     q.tokens = d_hist.as<int32_t>(); q.n_cur = n_cur ? d_ncur.as<int32_t>() : nullptr; q.done = d_done.as<int32_t>(); q.rule = st->rp_rule.as<int32_t>();
     launch_repeat_rule(q, rows, s);
     HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+static void command_upload(ohw_state* st, const ohw_command_table* t, float penalty) {
+  std::vector<int32_t> words;
+  command_table_pack(t, penalty, &words);
+  if (!st->cm_table.p) st->cm_table.alloc((size_t)CM_WORDS * 4, true);
+  if (!st->cm_lp.p) {
+    const std::vector<float> nan((size_t)st->max_batch, std::numeric_limits<float>::quiet_NaN());
+    st->cm_lp.alloc(nan.size() * 4, true);
+    HIP_CHECK(hipMemcpy(st->cm_lp.p, nan.data(), nan.size() * 4, hipMemcpyHostToDevice));
+  }
+  HIP_CHECK(hipMemcpy(st->cm_table.p, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+}
+
+// the five arrays of a command table, sized for the limits, and the table that points into them
+struct CommandArrays {
+  std::vector<int32_t> child_off, path, child_tok, terminal, phrase_id;
+  ohw_command_table t{};
+  CommandArrays()
+      : child_off((size_t)OHW_COMMAND_MAX_NODES + 1), path((size_t)OHW_COMMAND_MAX_PATH), child_tok((size_t)OHW_COMMAND_MAX_EDGES),
+        terminal((size_t)OHW_COMMAND_MAX_NODES), phrase_id((size_t)OHW_COMMAND_MAX_NODES) {
+    t.child_off = child_off.data(); t.path = path.data(); t.child_tok = child_tok.data(); t.terminal = terminal.data(); t.phrase_id = phrase_id.data();
+  }
+};
+
+int ohw_state_set_command_table(ohw_state* st, const int32_t* tokens, const int32_t* offsets, int n_phrases, float penalty) {
+  return guard([&] {
+    if (n_phrases != 0) command_penalty_check(penalty);  // the value first: a refusal needs no state and no device
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    if (n_phrases == 0) { st->cm_on = false; return; }
+    // built aside first: a refused list leaves the one in effect as it was
+    CommandArrays a;
+    command_table_build_host(tokens, offsets, n_phrases, st->ctx->tok.eot, &a.t);
+    command_upload(st, &a.t, penalty);
+    st->cm_child_off.swap(a.child_off); st->cm_path.swap(a.path); st->cm_child_tok.swap(a.child_tok); st->cm_terminal.swap(a.terminal);
+    st->cm_phrase_id.swap(a.phrase_id);
+    st->cm_host = a.t;                                   // the vectors' storage moved with the swap: the pointers hold
+    st->cm_src_tok.assign(tokens, tokens + offsets[n_phrases]);
+    st->cm_src_off.assign(offsets, offsets + n_phrases + 1);
+    st->cm_penalty = penalty;
+    st->cm_on = true;
+  });
+}
+
+int ohw_state_command_count(const ohw_state* st) { return st && st->cm_on ? st->cm_host.n_phrases : 0; }
+
+int ohw_state_command_list_logprob(ohw_state* st, int batch, float* out) {
+  return guard([&] {
+    if (!st || !out) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (!st->cm_on) throw Error(OHW_E_INVALID_ARG, "command list: none is set on this state");
+    if (batch < 1 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "command list: batch must lie in 1..max_batch");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    HIP_CHECK(hipMemcpy(out, st->cm_lp.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+// test entry: command_rule_kernel once on caller data (include/ohw.h).  Everything is range-checked first: the kernel indexes
+// with these values
+int ohw_dbg_command_rule(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                         const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int eot,
+                         const ohw_command_table* table, float* list_logprob) {
+  return guard([&] {
+    command_penalty_check(penalty);
+    if (!st || !logits || !histories || !done || !table || !list_logprob) throw Error(OHW_E_INVALID_ARG, "null argument");
+    if (rows < 1 || rows > 4096 || n_vocab < 1 || n_vocab > CM_MAX_VOCAB || ld < n_vocab || max_tokens < 1 || max_tokens > 4096 || eot < 0 || n_entries < 1 ||
+        n_entries > 4096 || row_mul < 1 || row_mul > 64 || group < 1 || group > 64)
+      throw Error(OHW_E_INVALID_ARG, "dbg_command_rule: bad shape");
+    if ((int64_t)(rows - 1) * row_mul / group >= n_entries) throw Error(OHW_E_INVALID_ARG, "dbg_command_rule: a launch row maps behind the last entry");
+    for (int i = 0; n_cur && i < n_entries; ++i)
+      if (n_cur[i] < 0 || n_cur[i] > max_tokens) throw Error(OHW_E_INVALID_ARG, "dbg_command_rule: n_cur out of range");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    HIP_CHECK(hipStreamSynchronize(s));
+    struct Restore {       // the state's own list is in effect again afterwards, also when a step below throws
+      ohw_state* st;
+      ~Restore() {
+        if (!st->cm_on) return;
+        try { command_upload(st, &st->cm_host, st->cm_penalty); } catch (...) { st->cm_on = false; }
+      }
+    } restore{st};
+    command_upload(st, table, penalty);                  // checks the table's every count and index
+    const size_t hist_rows = (size_t)n_entries * group;
+    DevBuf d_logits, d_hist, d_ncur, d_done, d_lp;
+    d_logits.alloc((size_t)rows * ld * 4); d_hist.alloc(hist_rows * max_tokens * 4); d_ncur.alloc((size_t)n_entries * 4); d_done.alloc((size_t)n_entries * 4);
+    d_lp.alloc((size_t)n_entries * 4);
+    HIP_CHECK(hipMemcpyAsync(d_logits.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_hist.p, histories, hist_rows * max_tokens * 4, hipMemcpyHostToDevice, s));
+    if (n_cur) HIP_CHECK(hipMemcpyAsync(d_ncur.p, n_cur, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_done.p, done, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_lp.p, list_logprob, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+    CommandRuleParams q{};
+    q.logits = d_logits.as<float>(); q.ld = ld; q.n_vocab = n_vocab; q.max_tokens = max_tokens; q.row_mul = row_mul; q.group = group; q.lp_group = group;
+    q.eot = eot; q.tokens = d_hist.as<int32_t>(); q.n_cur = n_cur ? d_ncur.as<int32_t>() : nullptr; q.done = d_done.as<int32_t>();
+    q.table = st->cm_table.as<int32_t>(); q.list_logprob = d_lp.as<float>();
+    launch_command_rule(q, rows, s);
+    HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(list_logprob, d_lp.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   });
 }

@@ -866,6 +866,71 @@ int ohw_engine_set_repetition(ohw_engine* e, float penalty, int ngram) {
   });
 }
 
+static void engine_set_commands_tokens(ohw_engine* e, const int32_t* tokens, const int32_t* offsets, int n_phrases, float penalty, std::vector<int32_t> index) {
+  if (!e || n_phrases < 0 || (n_phrases > 0 && (!tokens || !offsets))) throw Error(OHW_E_INVALID_ARG, "commands: bad argument");
+  // the engine's own state first: a list or a penalty it refuses reaches no other state
+  const int rc = ohw_state_set_command_table(e->state, tokens, offsets, n_phrases, penalty);
+  if (rc != OHW_OK) throw Error(rc, g_last_error);
+  each_state(e, [&](ohw_state* st) {
+    if (st == e->state) return;
+    const int rc2 = ohw_state_set_command_table(st, tokens, offsets, n_phrases, penalty);
+    if (rc2 != OHW_OK) throw Error(rc2, g_last_error);
+  });
+  e->cmd_index.swap(index);
+}
+
+int ohw_engine_set_commands_tokens(ohw_engine* e, const int32_t* tokens, const int32_t* offsets, int n_phrases, float penalty) {
+  return guard([&] {
+    std::vector<int32_t> index((size_t)std::max(0, n_phrases));
+    for (size_t i = 0; i < index.size(); ++i) index[i] = (int32_t)i;
+    engine_set_commands_tokens(e, tokens, offsets, n_phrases, penalty, std::move(index));
+  });
+}
+
+int ohw_engine_set_commands(ohw_engine* e, const char* const* texts, int n, float penalty) {
+  return guard([&] {
+    if (!e || n < 0 || (n > 0 && !texts)) throw Error(OHW_E_INVALID_ARG, "commands: bad argument");
+    // every text in up to two forms under the text's index: "text" (window start) and " text"; a form equal to the other is dropped
+    std::vector<int32_t> toks, offs{0}, index;
+    for (int i = 0; i < n; ++i) {
+      if (!texts[i]) throw Error(OHW_E_INVALID_ARG, "commands: text " + std::to_string(i) + " is null");
+      const std::string given = texts[i];
+      std::vector<int32_t> first;
+      for (const std::string& form : {given, " " + given}) {
+        std::vector<int32_t> t(form.size() + 1);       // at most one token per byte
+        const int k = ohw_tokenize(e->ctx, form.c_str(), t.data(), (int)t.size());
+        if (k < 0) throw Error(k, g_last_error);
+        if (k == 0) continue;                          // nothing of this form is in the vocabulary
+        t.resize((size_t)k);
+        if (t == first) continue;
+        if (first.empty()) first = t;
+        toks.insert(toks.end(), t.begin(), t.end());
+        offs.push_back((int32_t)toks.size());
+        index.push_back(i);
+      }
+      if (first.empty()) throw Error(OHW_E_INVALID_ARG, "commands: text " + std::to_string(i) + " ('" + given + "') has no token in this vocabulary");
+    }
+    const int n_forms = (int)index.size();
+    engine_set_commands_tokens(e, toks.data(), offs.data(), n_forms, penalty, std::move(index));
+  });
+}
+
+int ohw_engine_last_commands(ohw_engine* e, const ohw_command_hit** hits, int* n) {
+  if (!e || !hits || !n) return OHW_E_INVALID_ARG;
+  *hits = e->last.commands.data();
+  *n = (int)e->last.commands.size();
+  return OHW_OK;
+}
+
+int ohw_engine_batch_commands(ohw_engine* e, int i, const ohw_command_hit** hits, int* n) {
+  return guard([&] {
+    if (!e || !hits || !n) throw Error(OHW_E_INVALID_ARG, "batch_commands: null argument");
+    if (i < 0 || i >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "batch_commands: no recording " + std::to_string(i) + " in the last batch call");
+    *hits = e->batch_records[(size_t)i].t.commands.data();
+    *n = (int)e->batch_records[(size_t)i].t.commands.size();
+  });
+}
+
 int ohw_engine_set_prefill_chunk(ohw_engine* e, int positions) {
   return guard([&] {
     if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");

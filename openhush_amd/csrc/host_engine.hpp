@@ -26,6 +26,7 @@ struct Transcript {
   std::vector<ohw_span_time> words, segments;     // index text
   std::vector<WindowMark> marks;                  // one per window record
   std::vector<std::vector<int32_t>> contexts;     // per window record: what its T = 0 pass was decoded behind
+  std::vector<ohw_command_hit> commands;          // per window record while a command list is set (ohw_engine_last_commands)
   void clear() { *this = Transcript(); }
   // reference :282-283: the text loses its leading and trailing white space; the spans then index the trimmed text
   void trim() {
@@ -59,6 +60,9 @@ struct ohw_engine {
   int best_of = 1;                       // ohw_engine_set_best_of: candidates per pending window on every rung above T = 0 (1: today's ladder)
   std::vector<int32_t> last_cands;       // ohw_engine_last_candidates: every best-of rung of the last transcribe
   std::vector<float> last_cand_lps;      //   and the candidates' log-probabilities, in the same order
+  // ohw_engine_set_commands: the caller's index of every phrase of the list on the engine's state (the text form lists a text
+  // in up to two forms)
+  std::vector<int32_t> cmd_index;
   int force_len = 0;                     // measurement knob (ohw_engine_set_force_len): every window decodes exactly this many tokens
   // the last ohw_engine_transcribe: its records (words / segments index last_text once the call has trimmed) and the trimmed text
   ohw::Transcript last;

@@ -329,6 +329,47 @@ void launch_repeat_rule(const RepeatRuleParams& p, int rows, hipStream_t s);
 void repeat_rule_check(float penalty, int ngram);
 void repeat_rule_host(float penalty, int ngram, const int32_t* history, int n_cur, float* row, int n_vocab, int eot);
 
+// ---- command lists (command.hip; ohw_state_set_command_table) ------------------------------------------------------------
+// The anchored trie of include/ohw.h's ohw_command_table in ONE device buffer of fixed size, the penalty's fp32 bits with it, so
+// the pointer a captured step bakes in holds for every list and penalty set later.  Offsets in 4-byte words:
+constexpr int CM_DEPTHS = OHW_PHRASE_MAX_LEN + 1;                // depths 0 .. 16: the full phrases are nodes too
+constexpr int CM_MAX_NODES = OHW_COMMAND_MAX_NODES;
+constexpr int CM_MAX_EDGES = OHW_COMMAND_MAX_EDGES;
+constexpr int CM_MAX_PATH = OHW_COMMAND_MAX_PATH;
+constexpr int CM_OFF_DEPTH = 0;                                  // i32 [18] depth_start
+constexpr int CM_OFF_BASE = 32;                                  // i32 [17] path_base
+constexpr int CM_OFF_PENALTY = 60;                               // f32 the penalty (+inf: OHW_REPEAT_BAN)
+constexpr int CM_OFF_CHILD = 64;                                 // i32 [CM_MAX_NODES + 1] child_off
+constexpr int CM_OFF_TERM = CM_OFF_CHILD + CM_MAX_NODES + 1;     // i32 [CM_MAX_NODES] terminal
+constexpr int CM_OFF_PATH = CM_OFF_TERM + CM_MAX_NODES;          // i32 [CM_MAX_PATH]
+constexpr int CM_OFF_TOK = CM_OFF_PATH + CM_MAX_PATH;            // i32 [CM_MAX_EDGES] child_tok
+constexpr int CM_WORDS = CM_OFF_TOK + CM_MAX_EDGES;
+constexpr int CM_MAX_VOCAB = 1 << 18;                            // the children's bit map lives in LDS: 32 KiB at most
+// PhraseBoostParams' row mapping (launch row r changes logits row r with the history of decoder row h = r * row_mul, length
+// n_cur[h / group] - null: every history is empty - and flag done[h / group]).  list_logprob: the row h with
+// h % lp_group == 0 writes list_logprob[h / lp_group] at a step where its history holds no text token; lp_group is the
+// decoder rows per window (the beams, or a group pass's candidates; 1 where the launch rows are the windows).
+struct CommandRuleParams {
+  float* logits;            // [rows][ld], changed in place over columns [0, min(eot + 1, n_vocab))
+  int64_t ld;
+  int32_t n_vocab, max_tokens, row_mul, group, lp_group, eot;
+  const int32_t* tokens;    // [decoder rows][max_tokens]; entries at and behind n_cur are never read
+  const int32_t* n_cur;
+  const int32_t* done;
+  const int32_t* table;     // the CM_WORDS buffer
+  float* list_logprob;
+};
+void launch_command_rule(const CommandRuleParams& p, int rows, hipStream_t s);
+// the host twins (no device): the penalty the setter accepts (throws Error otherwise), the builder, the rule on one row
+// (list_logprob_out, if given, is written only when the history holds no text token), the exact match of a result
+void command_penalty_check(float penalty);
+void command_table_build_host(const int32_t* tokens, const int32_t* offsets, int n_phrases, int eot, ohw_command_table* out);
+void command_rule_host(const ohw_command_table* t, float penalty, const int32_t* history, int n_cur, float* row, int n_vocab, int eot,
+                       float* list_logprob_out);
+int command_match_host(const ohw_command_table* t, const int32_t* tokens, int n);
+// the table's arrays and the penalty laid out as the device buffer above (CM_WORDS words); checks every count and index
+void command_table_pack(const ohw_command_table* t, float penalty, std::vector<int32_t>* words);
+
 // ---- vad.hip: the spectral speech detector (include/ohw.h, ohw_state_vad_frames).  All pointers are device pointers ----
 constexpr int VAD_BINS = 320;          // histogram bins of 0.5 dB from -100 dB
 struct VadParams {

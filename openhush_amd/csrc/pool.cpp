@@ -337,6 +337,14 @@ int ohw_pool_set_hot_phrases(ohw_pool* p, const char* const* texts, const float*
   }
   return OHW_OK;
 }
+int ohw_pool_set_commands(ohw_pool* p, const char* const* texts, int n, float penalty) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_commands(e, texts, n, penalty);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
 int ohw_pool_set_repetition(ohw_pool* p, float penalty, int ngram) {
   if (!p) return OHW_E_INVALID_ARG;
   for (ohw_engine* e : p->engines) {

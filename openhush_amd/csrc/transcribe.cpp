@@ -14,6 +14,8 @@ namespace ohw {
 const float* state_bias_host(const ohw_state* st);
 const ohw_phrase_table* state_phrase_table_host(const ohw_state* st);
 bool state_repeat_rule_host(const ohw_state* st, float* penalty, int* ngram);
+const ohw_command_table* state_command_table_host(const ohw_state* st, float* penalty);
+int state_commands_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets);
 int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts);
 void state_share_recording(ohw_state* dst, ohw_state* src);
 void state_drop_recording(ohw_state* st);
@@ -180,6 +182,15 @@ struct TranscribeCall {
     r.plog.resize((size_t)r.ev.n_sampled);
     r.ev = evaluate(r, bt, eb);
   }
+  // command lists: list_logprob of the device pass that just ran on the batch's state, into the runs of its active windows (every
+  // device pass writes entry b for window b); nothing with no list set
+  void read_list_logprob(const Batch& bt, const int32_t* active, std::vector<WindowRun>& runs) const {
+    if (!state_command_table_host(bt.st, nullptr)) return;
+    std::vector<float> lp((size_t)bt.B);
+    check(ohw_state_command_list_logprob(bt.st, bt.B, lp.data()));
+    for (int b = 0; b < bt.B; ++b)
+      if (!active || active[b]) runs[(size_t)b].list_lp = lp[(size_t)b];
+  }
   // T = 0: the device-resident greedy loop for B windows, or under ohw_engine_set_beam_size ohw_beam_search_ex in its place; then
   // whisper.cpp's bookkeeping per window.  A beam winner (with end-of-text when it came from the finished pool) has whisper.cpp's
   // loop exits applied after the search (a definition), not to every decoder during it; from there on it is
@@ -207,6 +218,7 @@ struct TranscribeCall {
       r.pending = needs_fallback(r.ev, pol, r.nosp, temps.empty());
       trace(sc, bt.w0 + b, 0.f, r.tok);
     }
+    read_list_logprob(bt, nullptr, sc.runs);
   }
   // one rung sampled on the device (ohw_sample_pass: the greedy loop's replayed {step, sampler} with the temperature sampler)
   // from the host generators' pre-drawn doubles; the host then cuts each pass at whisper.cpp's loop exits and advances each
@@ -223,6 +235,7 @@ struct TranscribeCall {
       unpack(sc, bt, b, true, pass[(size_t)b]);
       if (ohw_rng_discard_draws(bt.rngs[b], pass[(size_t)b].ev.n_sampled) != OHW_OK) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: generator");
     }
+    read_list_logprob(bt, active.data(), pass);
   }
   // one rung of best-of sampling (ohw_engine_set_best_of): best_N candidates per pending window in ONE
   // ohw_sample_pass_n - candidate j draws from the entry's generator j, is cut and judged like rung_device's one row, and moves
@@ -258,6 +271,7 @@ struct TranscribeCall {
       sc.cands.push_back(std::move(cr));
       pass[(size_t)b] = std::move(c[(size_t)kept]);
     }
+    read_list_logprob(bt, active.data(), pass);      // the window's first candidate's: the candidates part ways behind the first token
   }
   // one rung sampled on the host: the device runs the decoder steps of the pending windows only and their logits cross PCIe
   // every step; a window stops inside the loop, at whisper.cpp's exits
@@ -289,6 +303,9 @@ struct TranscribeCall {
         int rp_n = 0;
         if (state_repeat_rule_host(bt.st, &rp_theta, &rp_n))                 // the state's repetition rule, behind the boost as on the device
           check(ohw_repeat_rule_host(rp_theta, rp_n, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V, tk.eot));
+        float cm_p = 0.f;
+        if (const ohw_command_table* ct = state_command_table_host(bt.st, &cm_p))     // the state's command list, behind the repetition rule as on the device
+          check(ohw_command_rule_host(ct, cm_p, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V, tk.eot, &r.list_lp));
         if (const float* bias = state_bias_host(bt.st))          // the state's logit bias: the device sampler adds it itself
           for (int i2 = 0; i2 < V; ++i2) logits[(size_t)b * V + i2] += bias[i2];
         const int32_t t = ohw_sample_host(e->ctx, &sp, &logits[(size_t)b * V], r.tok.data(), (int)r.tok.size(), T, bt.rngs[b], &lp, &r.nosp);
@@ -425,6 +442,11 @@ struct TranscribeCall {
     }
     out.marks.push_back(WindowMark{win_text0, (int32_t)(out.token_times.size() - tt0), (int32_t)(out.words.size() - wd0), (int32_t)(out.segments.size() - sg0)});
     out.contexts.push_back(ctx);
+    if (const ohw_command_table* ct = state_command_table_host(e->state, nullptr)) {
+      const int id = ohw_command_match_host(ct, r.tok.data(), keep);
+      const int32_t phrase = id < 0 ? -1 : (size_t)id < e->cmd_index.size() ? e->cmd_index[(size_t)id] : id;
+      out.commands.push_back(ohw_command_hit{(int32_t)out.quality.size(), phrase, r.list_lp});
+    }
     ohw_window_quality q{};
     q.n_tokens = keep; q.avg_logprob = r.ev.avg_logprob; q.entropy = r.ev.entropy; q.would_fallback = r.t0_failed ? 1 : 0;
     q.temperature = r.temp; q.no_speech_prob = r.nosp; q.no_speech = no_speech ? 1 : 0; q.seek_delta = r.ev.seek_delta;
@@ -799,6 +821,26 @@ void propagate_repetition(ohw_engine* e) {
   for (ohw_state* st : e->lane_states) same(st);
 }
 
+// the command list of the engine's own state (ohw_engine_set_commands), on the states a schedule made since it was set
+void propagate_commands(ohw_engine* e) {
+  const int32_t *tok = nullptr, *off = nullptr;
+  float p = 0.f;
+  const int n = state_commands_src(e->state, &tok, &off);
+  (void)state_command_table_host(e->state, &p);
+  auto same = [&](ohw_state* st) {
+    if (st == e->state) return;
+    const int32_t *tok2 = nullptr, *off2 = nullptr;
+    float p2 = 0.f;
+    const int n2 = state_commands_src(st, &tok2, &off2);
+    (void)state_command_table_host(st, &p2);
+    if (n == 0 && n2 == 0) return;
+    if (n == n2 && p == p2 && std::memcmp(off, off2, (size_t)(n + 1) * 4) == 0 && std::memcmp(tok, tok2, (size_t)off[n] * 4) == 0) return;
+    check(ohw_state_set_command_table(st, tok, off, n, p));
+  };
+  for (ohw_state* st : e->states) same(st);
+  for (ohw_state* st : e->lane_states) same(st);
+}
+
 void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n, int64_t win_first, int64_t win_step) {
   ohw_engine* e = tc.e;
   const FixedCuts cuts(tc, samples, n, win_first, win_step);
@@ -817,6 +859,7 @@ void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n,
   propagate_logit_bias(e);
   propagate_hot_phrases(e);
   propagate_repetition(e);
+  propagate_commands(e);
   apply_ctx(e, call_ctx);
   if (schedule == OHW_SCHEDULE_SEQUENTIAL) cuts.sequential();
   else if (schedule == OHW_SCHEDULE_PIPELINE) cuts.pipeline();
@@ -945,6 +988,7 @@ void engine_transcribe_speech(ohw_engine* e, const ohw_audio_span* recs, const o
       for (ohw_span_time sg : c.segments) { sg.text_off += text0; t.segments.push_back(sg); }
       for (WindowMark m : c.marks) { m.text0 += text0; t.marks.push_back(m); }
       t.contexts.insert(t.contexts.end(), c.contexts.begin(), c.contexts.end());
+      for (ohw_command_hit hit : c.commands) { hit.window += win0; t.commands.push_back(hit); }
     }
   } else {
     const TranscribeCall tc(e, nullptr, 0);             // what every call starts with: the last call's records are gone

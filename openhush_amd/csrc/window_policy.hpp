@@ -25,6 +25,7 @@ struct WindowRun {
   float nosp = 0.f, temp = 0.f;
   SeqEval ev;
   bool pending = false, t0_failed = false;
+  float list_lp = __builtin_nanf("");   // command lists: the pass's list_logprob (NaN: no list, or no step wrote one)
   std::vector<int32_t> al_idx;   // word timestamps: start index of every kept text token, then the end of the last (empty: not aligned)
 };
 

@@ -342,6 +342,120 @@ def repeat_rule_host(penalty: float, ngram: int, history: Sequence[int], n_cur: 
     return out
 
 
+COMMAND_PENALTY_MAX, COMMAND_PENALTY_DEFAULT = 1000.0, 100.0
+COMMAND_MAX_NODES = 1 + PHRASE_MAX_PHRASES * PHRASE_MAX_LEN
+COMMAND_MAX_EDGES = PHRASE_MAX_PHRASES * PHRASE_MAX_LEN
+COMMAND_MAX_PATH = PHRASE_MAX_PHRASES * PHRASE_MAX_LEN * (PHRASE_MAX_LEN + 1) // 2
+
+
+class CommandTableC(C.Structure):
+    _fields_ = [("n_phrases", C.c_int32), ("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("n_path", C.c_int32), ("eot", C.c_int32),
+                ("depth_start", C.c_int32 * (PHRASE_MAX_LEN + 2)), ("path_base", C.c_int32 * (PHRASE_MAX_LEN + 1)),
+                ("child_off", C.POINTER(C.c_int32)), ("path", C.POINTER(C.c_int32)), ("child_tok", C.POINTER(C.c_int32)),
+                ("terminal", C.POINTER(C.c_int32)), ("phrase_id", C.POINTER(C.c_int32))]
+
+
+class CommandHit(C.Structure):
+    _fields_ = [("window", C.c_int32), ("phrase", C.c_int32), ("list_logprob", C.c_float)]
+
+
+class CommandTable:
+    """ohw_command_table with the arrays it points into: the anchored flat trie of a command list (include/ohw.h states the layout)"""
+
+    def __init__(self):
+        self.child_off = np.zeros(COMMAND_MAX_NODES + 1, dtype=np.int32)
+        self.path = np.zeros(COMMAND_MAX_PATH, dtype=np.int32)
+        self.child_tok = np.zeros(COMMAND_MAX_EDGES, dtype=np.int32)
+        self.terminal = np.zeros(COMMAND_MAX_NODES, dtype=np.int32)
+        self.phrase_id = np.zeros(COMMAND_MAX_NODES, dtype=np.int32)
+        self.c = CommandTableC()
+        self.c.child_off, self.c.path, self.c.child_tok = _ip(self.child_off), _ip(self.path), _ip(self.child_tok)
+        self.c.terminal, self.c.phrase_id = _ip(self.terminal), _ip(self.phrase_id)
+
+    def arrays(self) -> dict:
+        """the table's used parts, copied: depth_start [18], path_base [17], child_off [n_nodes + 1], path, child_tok, terminal, phrase_id"""
+        c = self.c
+        return {"n_phrases": int(c.n_phrases), "eot": int(c.eot), "depth_start": np.array(c.depth_start[:], dtype=np.int32),
+                "path_base": np.array(c.path_base[:], dtype=np.int32), "child_off": self.child_off[:c.n_nodes + 1].copy(),
+                "path": self.path[:c.n_path].copy(), "child_tok": self.child_tok[:c.n_edges].copy(),
+                "terminal": self.terminal[:c.n_nodes].copy(), "phrase_id": self.phrase_id[:c.n_nodes].copy()}
+
+
+def command_table_build_host(phrases: Sequence[Sequence[int]], eot: int) -> CommandTable:
+    """ohw_command_table_build_host: token-id phrases -> the anchored trie; needs no device"""
+    toks, off, _ = _flat_phrases(phrases, [0.0] * len(phrases))
+    t = CommandTable()
+    _check(lib().ohw_command_table_build_host(_ip(toks), _ip(off), len(phrases), int(eot), C.byref(t.c)))
+    return t
+
+
+def command_rule_host(table: CommandTable, penalty: float, history: Sequence[int], n_cur: int, row: np.ndarray, eot: int) -> Tuple[np.ndarray, Optional[float]]:
+    """ohw_command_rule_host: the command-list rule on a copy of one row [n_vocab]; history = the row's own sampled tokens
+    (include/ohw.h states the rule); needs no device -> (the row, list_logprob or None when the history holds a text token)"""
+    out = np.ascontiguousarray(row, dtype=np.float32).copy()
+    h = np.ascontiguousarray(list(history) or [0], dtype=np.int32)
+    lp = C.c_float(float("nan"))
+    has_text = any(0 <= int(t) < int(eot) for t in list(history)[:int(n_cur)])
+    _check(lib().ohw_command_rule_host(C.byref(table.c), float(penalty), _ip(h), int(n_cur), _fp(out), int(out.size), int(eot), C.byref(lp)))
+    return out, (None if has_text else float(lp.value))
+
+
+def command_match_host(table: CommandTable, tokens: Sequence[int]) -> int:
+    """ohw_command_match_host: the index of the listed phrase that the text tokens of `tokens` equal exactly (the lowest, among
+    duplicates), else -1"""
+    toks = list(tokens)
+    t = np.ascontiguousarray(toks or [0], dtype=np.int32)
+    return int(lib().ohw_command_match_host(C.byref(table.c), _ip(t), len(toks)))
+
+
+def parse_commands(text: str) -> List[str]:
+    """a command file: one phrase per line; empty lines and lines starting with # are skipped"""
+    return [line.strip() for line in text.splitlines() if line.strip() and not line.lstrip().startswith("#")]
+
+
+def command_penalty_arg(v) -> float:
+    """a command penalty as the C ABI accepts it: 0 < p <= 1000, or inf; ValueError otherwise"""
+    try:
+        x = float(v)
+    except (TypeError, ValueError):
+        x = float("nan")
+    if not (0.0 < x <= COMMAND_PENALTY_MAX or x == float("inf")):      # false for NaN
+        raise ValueError(f"the command penalty must lie in (0, 1000] or be inf, not {v!r}")
+    return x
+
+
+def _commands_are_text(phrases) -> bool:
+    is_text = [isinstance(p, (str, bytes)) for p in phrases]
+    if any(is_text) and not all(is_text):
+        raise ValueError("commands: strings or token lists, not both in one call")
+    return bool(phrases) and is_text[0]
+
+
+def command_tokens(ctx, phrases) -> Tuple[List[List[int]], List[int]]:
+    """what ohw_engine_set_commands does with its texts, for a caller that owns a State: every string as given and with a leading
+    space, a form without a token or equal to the other dropped; token lists pass through -> (token lists, the caller's index of each)"""
+    phrases = list(phrases or [])
+    if not _commands_are_text(phrases):
+        return [list(p) for p in phrases], list(range(len(phrases)))
+    out, index = [], []
+    for i, p in enumerate(phrases):
+        raw = _text_bytes(p)
+        forms = [t for t in (ctx.tokenize(raw), ctx.tokenize(b" " + raw)) if t]
+        if not forms:
+            raise ValueError(f"commands: text {i} has no token in this vocabulary")
+        for k, t in enumerate(forms):
+            if k == 0 or t != forms[0]:
+                out.append(t)
+                index.append(i)
+    return out, index
+
+
+def _commands_text_call(fn, handle, phrases, penalty):
+    raw = [_text_bytes(p) for p in phrases]
+    arr = (C.c_char_p * max(len(raw), 1))(*raw)
+    _check(fn(handle, arr, len(raw), float(penalty)))
+
+
 def _hot_phrase_text_call(fn, handle, phrases, boosts):
     raw = [_text_bytes(p) for p in phrases]
     arr = (C.c_char_p * max(len(raw), 1))(*raw)
@@ -447,6 +561,9 @@ EXPORTS = [
     "ohw_engine_set_hot_phrases", "ohw_engine_set_hot_phrases_tokens", "ohw_pool_set_hot_phrases",
     "ohw_repeat_rule_host", "ohw_state_set_repeat_rule", "ohw_state_repeat_rule", "ohw_dbg_repeat_rule", "ohw_engine_set_repetition",
     "ohw_pool_set_repetition",
+    "ohw_command_table_build_host", "ohw_command_rule_host", "ohw_command_match_host", "ohw_state_set_command_table", "ohw_state_command_count",
+    "ohw_state_command_list_logprob", "ohw_dbg_command_rule", "ohw_engine_set_commands", "ohw_engine_set_commands_tokens", "ohw_pool_set_commands",
+    "ohw_engine_last_commands", "ohw_engine_batch_commands",
     "ohw_dbg_sample_ex",
     "ohw_default_vad_detector", "ohw_state_vad_frames", "ohw_speech_segments_host", "ohw_default_chunk_plan", "ohw_speech_chunks_host",
     "ohw_engine_set_vad", "ohw_engine_transcribe_speech", "ohw_engine_transcribe_speech_lang", "ohw_engine_speech_chunks",
@@ -763,6 +880,18 @@ def lib():
         L.ohw_dbg_repeat_rule.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, ip, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]
         L.ohw_engine_set_repetition.argtypes = [vp, C.c_float, C.c_int]
         L.ohw_pool_set_repetition.argtypes = [vp, C.c_float, C.c_int]
+        L.ohw_command_table_build_host.argtypes = [ip, ip, C.c_int, C.c_int, vp]
+        L.ohw_command_rule_host.argtypes = [vp, C.c_float, ip, C.c_int, fp, C.c_int, C.c_int, fp]
+        L.ohw_command_match_host.argtypes = [vp, ip, C.c_int]
+        L.ohw_state_set_command_table.argtypes = [vp, ip, ip, C.c_int, C.c_float]
+        L.ohw_state_command_count.argtypes = [vp]
+        L.ohw_state_command_list_logprob.argtypes = [vp, C.c_int, fp]
+        L.ohw_dbg_command_rule.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, ip, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, fp]
+        L.ohw_engine_set_commands.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.c_float]
+        L.ohw_engine_set_commands_tokens.argtypes = [vp, ip, ip, C.c_int, C.c_float]
+        L.ohw_pool_set_commands.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.c_float]
+        L.ohw_engine_last_commands.argtypes = [vp, C.POINTER(C.POINTER(CommandHit)), C.POINTER(C.c_int)]
+        L.ohw_engine_batch_commands.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(CommandHit)), C.POINTER(C.c_int)]
         L.ohw_dbg_beam_step.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIO)]
         L.ohw_beam_search_ex.argtypes = [vp, C.POINTER(SampleParams), C.c_int, C.c_int, C.c_int, C.POINTER(BeamResultEx)]
         L.ohw_dbg_beam_step_ex.argtypes = [vp, C.POINTER(SampleParams), C.POINTER(DbgBeamIOEx)]
@@ -1493,6 +1622,39 @@ class State:
 
     def phrase_count(self) -> int:
         return int(lib().ohw_state_phrase_count(self.h))
+
+    def set_command_table(self, phrases: Optional[Sequence[Sequence[int]]], penalty: float = COMMAND_PENALTY_DEFAULT):
+        """ohw_state_set_command_table: a closed list of phrases as token-id lists; every text token that does not continue a listed
+        phrase from the window's start is lowered by `penalty` (float("inf"): banned), end-of-text too until a phrase is complete;
+        None or [] clears"""
+        phrases = [list(p) for p in (phrases or [])]
+        toks, off, _ = _flat_phrases(phrases, [0.0] * len(phrases))
+        _check(lib().ohw_state_set_command_table(self.h, _ip(toks), _ip(off), len(phrases), float(penalty)))
+
+    def command_count(self) -> int:
+        return int(lib().ohw_state_command_count(self.h))
+
+    def command_list_logprob(self, batch: int) -> np.ndarray:
+        """ohw_state_command_list_logprob: per window of the last decoding call, log P(a listed phrase starts | text comes next)
+        under the unconstrained model, from the window's latest step without a text token"""
+        out = np.empty(int(batch), dtype=np.float32)
+        _check(lib().ohw_state_command_list_logprob(self.h, int(batch), _fp(out)))
+        return out
+
+    def dbg_command_rule(self, logits: np.ndarray, n_vocab: int, histories: np.ndarray, n_cur, done, table: CommandTable, penalty: float, eot: int,
+                         row_mul: int = 1, group: int = 1, sentinel: float = -12345.0) -> Tuple[np.ndarray, np.ndarray]:
+        """ohw_dbg_command_rule: the kernel once on logits [rows][ld] (a copy comes back whole), histories [entries * group][max_tokens],
+        n_cur (None: every history is empty) and done [entries]; launch row r reads history row r * row_mul under entry
+        r * row_mul // group -> (logits, list_logprob [entries], `sentinel` where the kernel wrote nothing)"""
+        lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
+        h = np.ascontiguousarray(histories, dtype=np.int32)
+        dn = np.ascontiguousarray(done, dtype=np.int32)
+        nc = None if n_cur is None else np.ascontiguousarray(n_cur, dtype=np.int32)
+        lp = np.full(dn.size, sentinel, dtype=np.float32)
+        assert lg.ndim == 2 and h.ndim == 2 and h.shape[0] == dn.size * group and (nc is None or nc.size == dn.size)
+        _check(lib().ohw_dbg_command_rule(self.h, _fp(lg), lg.shape[0], lg.shape[1], int(n_vocab), _ip(h), h.shape[1], None if nc is None else _ip(nc),
+                                          _ip(dn), dn.size, int(row_mul), int(group), float(penalty), int(eot), C.byref(table.c), _fp(lp)))
+        return lg, lp
 
     def set_repeat_rule(self, penalty: float = 1.0, ngram: int = 0):
         """ohw_state_set_repeat_rule: repetition penalty (0.01 .. 100; 1.0 = none) and no-repeat n-gram size (0 .. 32; 0 = none)
@@ -2603,6 +2765,29 @@ class WhisperEngine:
             a = np.ascontiguousarray(list(prompt) or [0], dtype=np.int32)
             _check(lib().ohw_engine_set_initial_prompt_tokens(self.h, _ip(a), len(prompt)))
 
+    def set_commands(self, phrases, penalty: float = COMMAND_PENALTY_DEFAULT):
+        """ohw_engine_set_commands / _tokens: a closed list of phrases, strings (each tokenised as given and with a leading space,
+        both forms under the string's index) or token-id lists (the exact form): every window is held to the list by `penalty`
+        (State.set_command_table states the rule; float("inf") is the hard form); None or [] clears.  Holds for every state the
+        engine decodes on; last_commands() tells which phrase each window was"""
+        phrases = list(phrases or [])
+        if _commands_are_text(phrases) or not phrases:
+            _commands_text_call(lib().ohw_engine_set_commands, self.h, phrases, penalty)
+        else:
+            t, off, _ = _flat_phrases([list(p) for p in phrases], [0.0] * len(phrases))
+            _check(lib().ohw_engine_set_commands_tokens(self.h, _ip(t), _ip(off), len(phrases), float(penalty)))
+
+    def last_commands(self, recording: Optional[int] = None) -> List[dict]:
+        """ohw_engine_last_commands (recording i of the last batch call: ohw_engine_batch_commands): per kept window
+        {"window", "index", "list_logprob"}: index = the position in set_commands' list of the phrase the window's text tokens
+        equal exactly, or -1; list_logprob = State.command_list_logprob's value of the kept pass; [] with no list set"""
+        hits, n = C.POINTER(CommandHit)(), C.c_int()
+        if recording is None:
+            _check(lib().ohw_engine_last_commands(self.h, C.byref(hits), C.byref(n)))
+        else:
+            _check(lib().ohw_engine_batch_commands(self.h, int(recording), C.byref(hits), C.byref(n)))
+        return [{"window": int(hits[i].window), "index": int(hits[i].phrase), "list_logprob": float(hits[i].list_logprob)} for i in range(n.value)]
+
     def set_repetition(self, penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         """ohw_engine_set_repetition: faster-whisper's repetition_penalty and no_repeat_ngram_size on every state the engine decodes
         on (State.set_repeat_rule states the rule); the defaults turn both off"""
@@ -2724,6 +2909,13 @@ class EnginePool:
 
     def set_window_mode(self, mode: int):
         _check(lib().ohw_pool_set_window_mode(self.h, mode))
+
+    def set_commands(self, phrases, penalty: float = COMMAND_PENALTY_DEFAULT):
+        """ohw_pool_set_commands: WhisperEngine.set_commands (the text form) on every engine of the pool; None or [] clears"""
+        phrases = list(phrases or [])
+        if phrases and not _commands_are_text(phrases):
+            raise ValueError("EnginePool.set_commands takes strings")
+        _commands_text_call(lib().ohw_pool_set_commands, self.h, phrases, penalty)
 
     def set_repetition(self, penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         """ohw_pool_set_repetition: WhisperEngine.set_repetition on every engine of the pool"""

@@ -76,15 +76,18 @@ def transcribe_sharded(transcribe_windows, pcm, n_windows: int, width: int, dist
     return interleave([unpack_tokens(g) for g in got], n_windows, world)
 
 
-def engine_window_runner(ctx, max_batch: int, params=None, mel_mode: Optional[int] = None, repetition=None):
+def engine_window_runner(ctx, max_batch: int, params=None, mel_mode: Optional[int] = None, repetition=None, commands=None):
     """transcribe_windows for transcribe_sharded on top of the staged C ABI: batches of up to max_batch windows through
     mel -> encode -> greedy on this rank's device (the fixed-window path of ohw_engine_transcribe).
-    repetition: (penalty, no-repeat n-gram size) for State.set_repeat_rule, or None."""
+    repetition: (penalty, no-repeat n-gram size) for State.set_repeat_rule, or None.
+    commands: (phrases as strings or token lists, penalty) for State.set_command_table, or None."""
     import numpy as np
     from . import engine as E
     st = E.State(ctx, max_batch)
     if repetition:
         st.set_repeat_rule(*repetition)
+    if commands:
+        st.set_command_table(E.command_tokens(ctx, commands[0])[0], commands[1])
     p = params or ctx.default_params()
     mode = E.OHW_MEL_ZERO_TAIL if mel_mode is None else mel_mode
 
@@ -106,16 +109,18 @@ def engine_window_runner(ctx, max_batch: int, params=None, mel_mode: Optional[in
     return run
 
 
-def recording_window_runner(ctx, max_batch: int, pcm, params=None, repetition=None):
+def recording_window_runner(ctx, max_batch: int, pcm, params=None, repetition=None, commands=None):
     """transcribe_windows for transcribe_sharded(.., by_index=True): this rank's windows are cut from the spectrogram of the
     WHOLE recording (ohw_recording_set / ohw_mel_seek: one clamp maximum for all windows, real samples across the 30 s
     marks - what whisper.cpp computes for a recording handed over in one call; the engine's OHW_WINDOW_FIXED_RECORDING_MEL).
     Every rank holds the recording and finds the same maximum (a pass of the mel kernel over all frames).
-    repetition: as engine_window_runner's."""
+    repetition, commands: as engine_window_runner's."""
     from . import engine as E
     st = E.State(ctx, max_batch)
     if repetition:
         st.set_repeat_rule(*repetition)
+    if commands:
+        st.set_command_table(E.command_tokens(ctx, commands[0])[0], commands[1])
     p = params or ctx.default_params()
     st.recording_set(pcm)
 

@@ -137,13 +137,15 @@ class StreamingSession:
     a 1.1 s chunk then pays for 128 encoder positions instead of 1500 (WhisperEngine.set_audio_ctx's rule).  hot_phrases: terms
     whose continuation is raised while a window's own tokens end in their front part (WhisperEngine.set_hot_phrases).
     repetition_penalty / no_repeat_ngram_size: the two controls of WhisperEngine.set_repetition on the session's state; the
-    defaults (1.0, 0) are off."""
+    defaults (1.0, 0) are off.  commands / command_penalty: a closed list of phrases every chunk is held to
+    (WhisperEngine.set_commands's rule on the session's state); after a chunk, last_command is the index of the phrase its tokens
+    were, or -1, and last_list_logprob the log-probability that the unconstrained model starts a listed phrase."""
 
     def __init__(self, ctx: E.Context, beam_size: int = 5, vad: Optional[Callable[[np.ndarray], float]] = None, vad_threshold: float = 0.5,
                  sequence_id: int = 1, tracker: Optional[TranscriptionTracker] = None, params: Optional[E.SampleParams] = None,
                  audio_config: Optional[E.PreprocessConfig] = None, noise_reduction: bool = False, noise_reduction_strength: float = 1.0,
                  denoiser: Optional["E.Denoiser"] = None, audio_ctx=0, carry_context: bool = False, hot_phrases=None, hot_phrase_boost=1.0,
-                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, commands=None, command_penalty: float = E.COMMAND_PENALTY_DEFAULT):
         self.ctx = ctx
         self.audio_ctx = E._audio_ctx_arg(audio_ctx)
         if self.audio_ctx > ctx.hp.n_audio_ctx:
@@ -170,6 +172,12 @@ class StreamingSession:
             self.state.set_phrase_table(*E.hot_phrase_tokens(ctx, hot_phrases, hot_phrase_boost))
         if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
             self.state.set_repeat_rule(repetition_penalty, no_repeat_ngram_size)
+        self.last_command, self.last_list_logprob = -1, float("nan")
+        self._command_table, self._command_index = None, []
+        if commands:
+            toks, self._command_index = E.command_tokens(ctx, commands)
+            self.state.set_command_table(toks, E.command_penalty_arg(command_penalty))
+            self._command_table = E.command_table_build_host(toks, int(ctx.tok.eot))
 
     def _text(self, tokens: List[int]) -> str:
         return b"".join(self.ctx.token_text(t) for t in tokens if t < self.ctx.tok.eot).decode("utf-8", "replace").strip()
@@ -208,6 +216,10 @@ class StreamingSession:
                 else:
                     toks = self.state.greedy(1, self.params)[0][0]
                 parts.append(b"".join(self.ctx.token_text(t) for t in toks if t < self.ctx.tok.eot))
+                if self._command_table is not None:                      # of the job's last window
+                    k = E.command_match_host(self._command_table, toks)
+                    self.last_command = self._command_index[k] if k >= 0 else -1
+                    self.last_list_logprob = float(self.state.command_list_logprob(1)[0])
                 if self.carry_context:
                     self.context = E.prompt_clip([t for t in toks if t < self.ctx.tok.eot], self.ctx.hp.n_text_ctx)
                 self.windows_decoded += 1

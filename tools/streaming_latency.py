@@ -19,6 +19,8 @@ hot-phrase table of N random phrases of --phrase-len text tokens at boost 2 (Sta
 last line with the medians of the two settings and their difference per decoder step: what the boost kernel costs.
 --repetition THETA,N (with --batch B, not --mixed, not with --hot-phrases): the same four legs without / with the repetition
 rule (State.set_repeat_rule(THETA, N)): what the repetition kernel costs per decoder step.
+--commands N (with --batch B, not --mixed, one at a time with the other two): the same four legs without / with a command list of
+N random phrases of --phrase-len text tokens at penalty 100 (State.set_command_table): what the command-list kernel costs.
 --out FILE appends the JSON line to FILE as well (profiles/).
 """
 import argparse
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--hot-phrases", type=int, default=0, help="N > 0: A/B legs without and with a table of N random phrases (needs --batch)")
     ap.add_argument("--phrase-len", type=int, default=4, help="tokens per phrase of the --hot-phrases table")
     ap.add_argument("--repetition", default=None, metavar="THETA,N", help="A/B legs without and with the repetition rule (needs --batch)")
+    ap.add_argument("--commands", type=int, default=0, help="N > 0: A/B legs without and with a command list of N random phrases (needs --batch)")
     ap.add_argument("--out", default=None, help="append the JSON result line to this file")
     a = ap.parse_args()
 
@@ -124,9 +127,14 @@ def main():
                 ap.error("--repetition and --hot-phrases are measured one at a time")
             theta, ngram = a.repetition.split(",")
             rule = (float(theta), int(ngram))
+        if a.commands and (a.hot_phrases or rule):
+            ap.error("--commands, --repetition and --hot-phrases are measured one at a time")
+        commands = [[int(t) for t in rng.integers(0, ctx.tok.eot, a.phrase_len)] for _ in range(a.commands)]
         per_step = {0: [], 1: []}
-        for leg in ([0, 1, 0, 1] if table or rule else [0]):
-            if rule:
+        for leg in ([0, 1, 0, 1] if table or rule or commands else [0]):
+            if commands:
+                st.set_command_table(commands if leg else None, 100.0)
+            elif rule:
                 st.set_repeat_rule(*(rule if leg else (1.0, 0)))
             else:
                 st.set_phrase_table(table if leg else None, 2.0)
@@ -144,13 +152,15 @@ def main():
                   "audio_ctx": st.audio_ctx, "gemm_small": os.environ.get("OHW_GEMM_SMALL", "default"), "reps": a.reps,
                   "hot_phrases": st.phrase_count(), "phrase_boost_launches": st.counter("phrase_boost"),
                   "repeat_rule": list(st.repeat_rule()), "repeat_rule_launches": st.counter("repeat_rule"),
+                  "commands": st.command_count(), "command_rule_launches": st.counter("command_rule"),
                   "encode_ms": {"median": round(float(np.median(enc)), 3), "min": round(min(enc), 3), "max": round(max(enc), 3)},
                   "decode_ms_per_step": {"median": round(float(np.median(dec)) / max(1, steps), 4), "min": round(min(dec) / max(1, steps), 4),
                                          "max": round(max(dec) / max(1, steps), 4)},
                   "batch_latency_ms": {"median": round(1e3 * float(np.median(wall)), 2), "min": round(1e3 * min(wall), 2), "max": round(1e3 * max(wall), 2)}})
-        if table or rule:
+        if table or rule or commands:
             off, on = float(np.median(per_step[0])), float(np.median(per_step[1]))
-            what = f"repetition rule ({rule[0]:g}, {rule[1]})" if rule else f"hot-phrase table of {a.hot_phrases} x {a.phrase_len} tokens"
+            what = (f"command list of {a.commands} x {a.phrase_len} tokens, penalty 100" if commands else
+                    f"repetition rule ({rule[0]:g}, {rule[1]})" if rule else f"hot-phrase table of {a.hot_phrases} x {a.phrase_len} tokens")
             emit({"workload": f"{a.model} batch of {a.batch}, greedy, {a.tokens} decoder steps, {a.dtype}: {what}",
                   "decode_ms_per_step_without": round(off, 4), "decode_ms_per_step_with": round(on, 4), "difference_us_per_step": round(1e3 * (on - off), 2),
                   "spread_us_without": round(1e3 * (max(per_step[0]) - min(per_step[0])), 2),
