@@ -1416,7 +1416,8 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  *   "dec_gemm.<gemm><form>.<NT>x<MT>"  gemm: qkv, o (self-attention out), xq, xo (cross-attention q / out), fc1, fc2,
  *                                      logits; form: ".ln" (LayerNorm in the prologue), ".pn" (post-norm), ".ks"
  *                                      (split-K), "" (none); NT x MT n-tiles x m-tiles per workgroup: 1x1 2x1 1x2 2x2 4x2 1x6,
- *                                      4x6 5x6 (qkv.ln, fc1.ln: all rows behind a LayerNorm launch of its own)
+ *                                      4x6 5x6 (qkv.ln, fc1.ln: all rows behind a LayerNorm launch of its own; logits: 4x6,
+ *                                      all rows, on a CU-masked stream)
  *   "xattn.plain" / "xattn.split"      cross-attention, one workgroup per (row, head) / keys cut over gridDim.z > 1
  *   "xattn.rows2" .. "xattn.rows4"     one workgroup per (window, head) for 2..4 new tokens
  *   "xattn.chunk"                      the prefill's 8 rows per window on the MFMA units (ohw_state_prefill)

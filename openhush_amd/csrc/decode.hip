@@ -641,7 +641,7 @@ __global__ __launch_bounds__(128) void dec_ln_rows_kernel(const float* __restric
 // block requests the n-tiles' weights again (and, in the LN forms, normalises its rows again).  Two bodies:
 //   RESID, long K (mlp.2, K = 5120; NTW = 1, one pass of six m-tiles): the weights stream through in runs of 20 / 4 / 1
 //     k-blocks per wave, the fragments are fetched G k-blocks at a time;
-//   QKV / GELU_T, K <= 1280 (LN1 + QKV and LN2 + mlp.0 behind dec_ln_rows_kernel): a wave's whole share, at most five
+//   QKV / GELU_T / LOGITS, K <= 1280 (LN1 + QKV and LN2 + mlp.0 behind dec_ln_rows_kernel; the logits): a wave's whole share, at most five
 //     k-blocks of each n-tile, stays in registers over PASSES passes of MTP m-tiles, each with its own reduction and epilogue
 //     (the accumulators and the 1 KiB per wave, n-tile and m-tile of reduction buffer are what bounds a pass).
 // Per (m-tile, n-tile) everything is dec_gemm_kernel's: the 8 waves' interleaved K split, a wave's k-blocks in ascending
@@ -651,7 +651,7 @@ __global__ __launch_bounds__(128) void dec_ln_rows_kernel(const float* __restric
 template <typename T, int EPI, int NTW, int MTP, int PASSES, int G>
 __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_rows_kernel(DecGemmParams p) {
   constexpr bool HOLD = EPI != DEPI_BIAS_RESID;
-  static_assert(HOLD ? (EPI == DEPI_QKV || EPI == DEPI_BIAS_GELU_T) : (NTW == 1 && PASSES == 1), "rows form");
+  static_assert(HOLD ? (EPI == DEPI_QKV || EPI == DEPI_BIAS_GELU_T || EPI == DEPI_LOGITS) : (NTW == 1 && PASSES == 1), "rows form");
   using Ops = TypeOps<T>;
   using vec8 = typename Ops::vec8;
   extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
@@ -803,8 +803,13 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_rows_kernel(DecGemmPar
       const int m = (mt0 + q) * 16 + (ll & 15), n = (nt0 + t) * 16 + 4 * (ll >> 4) + reg;
       if (m >= p.M || n >= p.N || nt0 + t >= n_tiles) continue;
       if (p.bias) v += p.bias[n];
-      if constexpr (HOLD) dec_gemm_store16<T, EPI>(p, m, n, v);
-      else ((float*)p.out)[(int64_t)m * p.ld_out + n] = resid_old[i] + v;
+      if constexpr (EPI == DEPI_LOGITS) {          // dec_gemm_kernel's row selection: the last row of each window, fp32
+        if (m % p.n_new == p.n_new - 1) ((float*)p.out)[(int64_t)(m / p.n_new) * p.ld_out + n] = v;
+      } else if constexpr (HOLD) {
+        dec_gemm_store16<T, EPI>(p, m, n, v);
+      } else {
+        ((float*)p.out)[(int64_t)m * p.ld_out + n] = resid_old[i] + v;
+      }
     }
   }
   TRACE(16 + EPI * 2, 3);
@@ -884,6 +889,22 @@ static int dec_gemm_pick(const DecGemmParams& p, hipStream_t s) {
       }
     }
   }
+  // The logits there (at 96 rows 811 x 3 four-tile workgroups, the 133 MB embedding requested once per 32-row block, 339 us):
+  // the held-weights body for all rows, 811 workgroups that request their four n-tiles once (176 us).  On a CU-masked stream
+  // only, while that grid has 32 workgroups and at most 16 rounds of the stream's CUs: measured on a 64-CU lane (13 rounds)
+  // and nowhere narrower.  OHW_DEC_LOGITS_ROWS=0: off
+  if constexpr (EPI == DEPI_LOGITS) {
+    static const int lrows = getenv("OHW_DEC_LOGITS_ROWS") ? atoi(getenv("OHW_DEC_LOGITS_ROWS")) : 1;
+    const int64_t g4 = (n_tiles + 3) / 4;
+    if (lrows && p.cu_budget > 0 && mt > 2 && p.ksplit <= 1 && !p.pn && !p.stat_out && p.K <= DG_LN_MAXK &&
+        (int64_t)n_tiles * ((mt + 1) / 2) > 2 * cus && g4 >= 32 && g4 <= 16 * (int64_t)cus) {
+      dec_gemm_rows_launch<T, DEPI_LOGITS, 4, 3, 2, 5>(p, s);
+      return DG_SHAPE_4x6;
+    }
+  }
+  // (The cross query, 40 x 3 two-tile workgroups at 96 rows, stays below: as 20 x 3 four-tile workgroups it measured 12.5 us
+  // against 15.1; mlp.2 keeps one n-tile per workgroup: with two it measured 28.5 us against 35.8.  Both are short of what
+  // a per-layer launch was asked to save - DESIGN.md Appendix A.)
   static const int nt4 = getenv("OHW_DEC_NT4") ? atoi(getenv("OHW_DEC_NT4")) : 1;
   if constexpr ((LN && (EPI == DEPI_QKV || EPI == DEPI_BIAS_T || EPI == DEPI_BIAS_GELU_T)) || (!LN && (EPI == DEPI_BIAS_RESID || EPI == DEPI_LOGITS))) {
     const int64_t wgs = LN ? (int64_t)((n_tiles + 1) / 2) * ((mt + 1) / 2) : (int64_t)n_tiles * ((mt + 1) / 2);
