@@ -19,6 +19,7 @@
 #include "dequant.hpp"
 #include "gemm.hpp"
 #include "kernels.hpp"
+#include "logit_rules.hpp"
 #include "model.hpp"
 
 namespace ohw {
@@ -265,34 +266,7 @@ struct ohw_state {
   int64_t tally_xattn[XA_N_VARIANTS] = {};
   int64_t tally_self[4] = {};      // SA_PLAIN, SA_SLOTS, then the same two run inside the QKV launch (OHW_DEC_FUSE_ATTN)
   DevBuf tok_lp, nosp_prob;        // per-token log-probabilities [B][max_tokens + 1], no-speech probability [B]
-  DevBuf logit_bias;               // optional f32 [n_vocab] (ohw_state_set_logit_bias)
-  std::vector<float> bias_host;    // the same on the host: the temperature ladder samples there (host_engine.cpp)
-  bool bias_on = false;
-  // hot phrases (ohw_state_set_phrase_table): the flat trie in one fixed-size device buffer (kernels.hpp, PH_WORDS), made at the
-  // first set; ph_host: the same table on the host (the engine's host-sampled ladder applies it there) with the arrays it
-  // points into; ph_src_*: the phrases as they were given (the engine hands them on to its other states)
-  DevBuf ph_table;
-  bool ph_on = false;
-  ohw_phrase_table ph_host{};
-  std::vector<int32_t> ph_child_off, ph_path, ph_child_tok, ph_src_tok, ph_src_off;
-  std::vector<float> ph_child_boost, ph_src_boost;
-  int64_t tally_phrase = 0;        // phrase_boost_kernel launches (ohw_dbg_counter "phrase_boost"), counted like the tallies above
-  // repetition penalty and no-repeat n-grams (ohw_state_set_repeat_rule): the two values on the host and in a two-word device
-  // buffer {fp32 bits of the penalty, n-gram size}, made at the first set; rp_on: they are not (1.0, 0)
-  DevBuf rp_rule;
-  float rp_penalty = 1.0f;
-  int rp_ngram = 0;
-  bool rp_on = false;
-  int64_t tally_repeat = 0;        // repeat_rule_kernel launches (ohw_dbg_counter "repeat_rule")
-  // command list (ohw_state_set_command_table): the anchored trie and the penalty in one fixed-size device buffer (kernels.hpp,
-  // CM_WORDS) and list_logprob [max_batch], both made at the first set; cm_host: the same table on the host (the engine's
-  // host-sampled ladder applies it there) with the arrays it points into; cm_src_*: the phrases as they were given
-  DevBuf cm_table, cm_lp;
-  bool cm_on = false;
-  float cm_penalty = OHW_COMMAND_PENALTY_DEFAULT;
-  ohw_command_table cm_host{};
-  std::vector<int32_t> cm_child_off, cm_path, cm_child_tok, cm_terminal, cm_phrase_id, cm_src_tok, cm_src_off;
-  int64_t tally_command = 0;       // command_rule_kernel launches (ohw_dbg_counter "command_rule")
+  LogitRules rules;                // logit bias, hot phrases, repetition rule, command list: logit_rules.hpp owns them and their order
   int m_max = 0;
   int64_t logits_ld = 0;
   // per-kernel-class profiling (bench): event pairs around every launch of one class
@@ -379,7 +353,7 @@ namespace {
 GraphKey graph_key(const ohw_state* st, int rows, int group, bool flag, const SamplerParams& spar) {
   GraphKey k;
   k.rows = rows; k.group = group; k.cus = st->stream_cus; k.t_len = st->enc_ctx; k.var = st->enc_var; k.invariant = st->batch_invariant;
-  k.persist = st->persist; k.flag = flag; k.phrases = st->ph_on; k.repeat = st->rp_on; k.commands = st->cm_on;
+  k.persist = st->persist; k.flag = flag; k.phrases = st->rules.ph.on; k.repeat = st->rules.rp.on; k.commands = st->rules.cm.on;
   std::memcpy(&k.spar, &spar, sizeof spar);
   return k;
 }
@@ -942,7 +916,7 @@ void fill_sampler(const ohw_state* st, const ohw_sample_params* sp, int B, Sampl
   p->next_tok = st->next_tok.as<int32_t>(); p->done = st->done.as<int32_t>(); p->n_done = st->n_done.as<int32_t>();
   p->sum_logprob = st->sum_lp.as<float>();
   p->partials = st->samp_part.as<float>(); p->tickets = st->samp_ticket.as<unsigned>();
-  p->bias = st->bias_on ? st->logit_bias.as<float>() : nullptr;
+  p->bias = st->rules.bias_device();
   p->tok_lp = st->tok_lp.as<float>(); p->nosp_prob = st->nosp_prob.as<float>();
   p->batch = B; p->max_tokens = st->max_tokens; p->n_vocab = c->hp.n_vocab;
   p->eot = c->tok.eot; p->sot = c->tok.sot; p->translate = c->tok.translate; p->transcribe = c->tok.transcribe;
@@ -950,38 +924,6 @@ void fill_sampler(const ohw_state* st, const ohw_sample_params* sp, int B, Sampl
   p->ts_begin = c->tok.timestamp_begin; p->blank = c->tok.blank; p->n_langs = c->tok.n_langs;
   p->suppress_blank = sp->suppress_blank; p->no_timestamps = sp->no_timestamps; p->max_initial_ts = sp->max_initial_ts;
   p->n_max = sp->n_max; p->force_len = sp->force_len; p->n_text_ctx = c->hp.n_text_ctx;
-}
-
-// the history-dependent logit rules ahead of a sampler launch (kernels.hpp states the row mapping): the hot-phrase boost, then
-// the repetition rule, then the command list; nothing without a table or a list and with the rule off.  lp_group: the decoder
-// rows per window among the launch rows (0: group), which only the command list's list_logprob needs
-void boost_rows(ohw_state* st, const SamplerParams& p, int rows, int row_mul, int group, const int32_t* n_cur, const int32_t* done, hipStream_t s,
-                int lp_group = 0) {
-  if (st->ph_on) {
-    PhraseBoostParams b{};
-    b.logits = st->logits.as<float>(); b.ld = p.ld; b.n_vocab = p.n_vocab; b.max_tokens = p.max_tokens; b.row_mul = row_mul; b.group = group;
-    b.tokens = p.tokens; b.n_cur = n_cur; b.done = done; b.table = st->ph_table.as<int32_t>();
-    launch_phrase_boost(b, rows, s);
-    ++st->tally_phrase;
-  }
-  // null n_cur is the group pass's first step, where every history is empty by definition: the launch is skipped.  The beam's
-  // first step passes the windows' n_cur, which the device holds as zeros: there the kernel runs and returns at once
-  if (st->rp_on && n_cur) {
-    RepeatRuleParams q{};
-    q.logits = st->logits.as<float>(); q.ld = p.ld; q.n_vocab = p.n_vocab; q.max_tokens = p.max_tokens; q.row_mul = row_mul; q.group = group;
-    q.eot = p.eot; q.tokens = p.tokens; q.n_cur = n_cur; q.done = done; q.rule = st->rp_rule.as<int32_t>();
-    launch_repeat_rule(q, rows, s);
-    ++st->tally_repeat;
-  }
-  // null n_cur launches here: the first step is where the root applies
-  if (st->cm_on) {
-    CommandRuleParams q{};
-    q.logits = st->logits.as<float>(); q.ld = p.ld; q.n_vocab = p.n_vocab; q.max_tokens = p.max_tokens; q.row_mul = row_mul; q.group = group;
-    q.lp_group = lp_group > 0 ? lp_group : group;
-    q.eot = p.eot; q.tokens = p.tokens; q.n_cur = n_cur; q.done = done; q.table = st->cm_table.as<int32_t>(); q.list_logprob = st->cm_lp.as<float>();
-    launch_command_rule(q, rows, s);
-    ++st->tally_command;
-  }
 }
 
 int build_prompt(const ohw_ctx* c, const ohw_sample_params* sp, int32_t* out) {
@@ -1152,6 +1094,7 @@ int ohw_state_create(ohw_ctx* ctx, int max_batch, ohw_state** out) {
     std::unique_ptr<ohw_state> st(new ohw_state());
     st->ctx = ctx;
     st->max_batch = max_batch;
+    st->rules.init(ctx->device, ctx->hp.n_vocab, ctx->tok.eot, max_batch, &st->stream);
     HIP_CHECK(hipStreamCreateWithFlags(&st->own_stream, hipStreamNonBlocking));
     st->stream = st->own_stream;
     state_alloc(st.get());
@@ -1262,30 +1205,39 @@ void state_drop_recording(ohw_state* st) {
   st->rec_pcm.release();          // a view: nothing is freed
   st->rec_n = 0;
 }
-const float* state_bias_host(const ohw_state* st) { return st && st->bias_on && !st->bias_host.empty() ? st->bias_host.data() : nullptr; }
-// the host's view of a state's hot phrases: the table in effect (null: none) and the phrases as they were given
-const ohw_phrase_table* state_phrase_table_host(const ohw_state* st) { return st && st->ph_on ? &st->ph_host : nullptr; }
-// a state's repetition rule as the host-sampled ladder needs it: false while it is off
-bool state_repeat_rule_host(const ohw_state* st, float* penalty, int* ngram) {
-  if (!st || !st->rp_on) return false;
-  *penalty = st->rp_penalty; *ngram = st->rp_ngram;
-  return true;
-}
-// a state's command list as the host-sampled ladder and the engine's fan-out need it: null while none is set
-const ohw_command_table* state_command_table_host(const ohw_state* st, float* penalty) {
-  if (!st || !st->cm_on) return nullptr;
-  if (penalty) *penalty = st->cm_penalty;
-  return &st->cm_host;
-}
-int state_commands_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets) {
-  if (!st || !st->cm_on) return 0;
-  *tokens = st->cm_src_tok.data(); *offsets = st->cm_src_off.data();
-  return st->cm_host.n_phrases;
-}
-int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts) {
-  if (!st || !st->ph_on) return 0;
-  *tokens = st->ph_src_tok.data(); *offsets = st->ph_src_off.data(); *boosts = st->ph_src_boost.data();
-  return st->ph_host.n_phrases;
+// a state's logit rules, for the engine: the host-sampled rung applies them and a transcribe syncs them across its states
+LogitRules& state_rules(ohw_state* st) { return st->rules; }
+
+// What the three rule test entries share (ohw_dbg_phrase_boost, ohw_dbg_repeat_rule, ohw_dbg_command_rule; include/ohw.h has
+// their arguments).  Everything is range-checked first: the kernels index with these values.  Then, on the state's device and
+// stream: upload() fills the entry's OWN LogitRules - a test entry never touches the state's -, logits, histories, n_cur and
+// done are staged, launch() runs the kernel on them, and the logits come back whole
+struct RuleRows {
+  float* logits; int rows; int64_t ld; int n_vocab; const int32_t* histories; int max_tokens; const int32_t* n_cur; const int32_t* done;
+  int n_entries, row_mul, group, eot;
+};
+template <typename U, typename L>
+void dbg_rule_rows(ohw_state* st, const std::string& name, const RuleRows& a, int max_tokens_limit, int n_vocab_limit, U&& upload, L&& launch) {
+  if (a.rows < 1 || a.rows > 4096 || a.n_vocab < 1 || a.n_vocab > n_vocab_limit || a.ld < a.n_vocab || a.max_tokens < 1 || a.max_tokens > max_tokens_limit ||
+      a.eot < 0 || a.n_entries < 1 || a.n_entries > 4096 || a.row_mul < 1 || a.row_mul > 64 || a.group < 1 || a.group > 64)
+    throw Error(OHW_E_INVALID_ARG, name + ": bad shape");
+  if ((int64_t)(a.rows - 1) * a.row_mul / a.group >= a.n_entries) throw Error(OHW_E_INVALID_ARG, name + ": a launch row maps behind the last entry");
+  for (int i = 0; a.n_cur && i < a.n_entries; ++i)
+    if (a.n_cur[i] < 0 || a.n_cur[i] > a.max_tokens) throw Error(OHW_E_INVALID_ARG, name + ": n_cur out of range");
+  HIP_CHECK(hipSetDevice(st->ctx->device));
+  hipStream_t s = st->stream;
+  HIP_CHECK(hipStreamSynchronize(s));
+  upload();
+  const size_t hist_rows = (size_t)a.n_entries * a.group, logit_bytes = (size_t)a.rows * a.ld * 4;
+  DevBuf d_logits, d_hist, d_ncur, d_done;
+  d_logits.alloc(logit_bytes); d_hist.alloc(hist_rows * a.max_tokens * 4); d_ncur.alloc((size_t)a.n_entries * 4); d_done.alloc((size_t)a.n_entries * 4);
+  HIP_CHECK(hipMemcpyAsync(d_logits.p, a.logits, logit_bytes, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_hist.p, a.histories, hist_rows * a.max_tokens * 4, hipMemcpyHostToDevice, s));
+  if (a.n_cur) HIP_CHECK(hipMemcpyAsync(d_ncur.p, a.n_cur, (size_t)a.n_entries * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_done.p, a.done, (size_t)a.n_entries * 4, hipMemcpyHostToDevice, s));
+  launch(d_logits.as<float>(), d_hist.as<int32_t>(), a.n_cur ? d_ncur.as<int32_t>() : nullptr, d_done.as<int32_t>(), s);
+  HIP_CHECK(hipMemcpyAsync(a.logits, d_logits.p, logit_bytes, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
 }
 }
 extern "C" {
@@ -1810,7 +1762,7 @@ static void decode_loop(ohw_state* st, const ohw_sample_params* sp, int batch, i
       HIP_CHECK(hipStreamSynchronize(s));  // np, the prompt rows (and a temperature pass's done0, n_done0, T, draws) are stack-lifetime sources
       ++steps;
       auto sample = [&](hipStream_t q) {
-        boost_rows(st, spar, batch, 1, 1, spar.n_cur, spar.done, q);
+        st->rules.apply(st->logits.as<float>(), spar.ld, spar, batch, 1, 1, spar.n_cur, spar.done, q);
         if (tp) launch_sampler_t(spar, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
         else launch_sampler(spar, q);
       };
@@ -1917,12 +1869,13 @@ static void sample_pass_group(ohw_state* st, const ohw_sample_params* sp, int W,
       st->sn_rows = R;
       HIP_CHECK(hipStreamSynchronize(s));                         // the vectors above and the prompt rows are stack-lifetime sources
       spar.advance = 0;
-      boost_rows(st, spar, W, 1, 1, nullptr, d_wdone, s);         // the candidates share the window's prompt row and their histories are empty: once per window
+      // the candidates share the window's prompt row and their histories are empty: once per window
+      st->rules.apply(st->logits.as<float>(), spar.ld, spar, W, 1, 1, nullptr, d_wdone, s);
       launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), s);   // first token of every row from its window's prompt logits
       spar.advance = 1;
       auto iteration = [&](int, hipStream_t q) {
         run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), N, slots, d_wdone);
-        boost_rows(st, spar, R, 1, 1, spar.n_cur, spar.done, q, N);     // a window's N candidates are neighbours
+        st->rules.apply(st->logits.as<float>(), spar.ld, spar, R, 1, 1, spar.n_cur, spar.done, q, N);     // a window's N candidates are neighbours
         launch_sampler_group(spar, grp, st->samp_temp.as<float>(), st->samp_u.as<double>(), q);
       };
       const bool use_graph = st->graphs_enabled && st->prof_class == 0 && s != nullptr;
@@ -2035,7 +1988,7 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
       ++steps;
       SamplerParams p0; BeamParams b0;
       params(0, &p0, &b0);
-      boost_rows(st, p0, W, K, K, b0.n_cur, b0.win_done, s);
+      st->rules.apply(st->logits.as<float>(), p0.ld, p0, W, K, K, b0.n_cur, b0.win_done, s);
       launch_beam_step(p0, b0, W, 1, s);                          // first candidates from the prompt's logits; writes side 1
       // one beam iteration = {decoder step of the W * K rows, top-k per row, update per window}; the token-history and
       // kv_slot double buffers alternate, so TWO graphs are captured (odd and even steps) and replayed in turn
@@ -2047,7 +2000,7 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
           params(q, &pq, &bq);
           run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), K, bq.kv_slot, bq.win_done);
           BMARK("decoder step captured", q);
-          boost_rows(st, pq, R, 1, K, bq.n_cur, bq.win_done, cap);     // each beam's history in this step's half of the double buffer
+          st->rules.apply(st->logits.as<float>(), pq.ld, pq, R, 1, K, bq.n_cur, bq.win_done, cap);   // each beam's history in this step's half of the buffer
           launch_beam_step(pq, bq, W, 0, cap);
           BMARK("beam step captured", q);
         });
@@ -2063,7 +2016,7 @@ static void beam_search_run(ohw_state* st, const ohw_sample_params* sp, int n_wi
           SamplerParams pq; BeamParams bq;
           params(q, &pq, &bq);
           run_decoder_step<T>(st, R, 1, st->next_tok.as<int32_t>(), K, bq.kv_slot, bq.win_done);
-          boost_rows(st, pq, R, 1, K, bq.n_cur, bq.win_done, s);
+          st->rules.apply(st->logits.as<float>(), pq.ld, pq, R, 1, K, bq.n_cur, bq.win_done, s);
           launch_beam_step(pq, bq, W, 0, s);
         }
       });
@@ -2152,9 +2105,9 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "group_graphs") return (int)st->group_graphs.entries.size();
   if (n == "persist_launches") return st->persist_launches;
   if (n == "xattn.chunk") return (int)std::min<int64_t>(st->tally_xchunk, INT32_MAX);
-  if (n == "phrase_boost") return (int)std::min<int64_t>(st->tally_phrase, INT32_MAX);
-  if (n == "repeat_rule") return (int)std::min<int64_t>(st->tally_repeat, INT32_MAX);
-  if (n == "command_rule") return (int)std::min<int64_t>(st->tally_command, INT32_MAX);
+  if (n == "phrase_boost") return (int)std::min<int64_t>(st->rules.tally_phrase, INT32_MAX);
+  if (n == "repeat_rule") return (int)std::min<int64_t>(st->rules.tally_repeat, INT32_MAX);
+  if (n == "command_rule") return (int)std::min<int64_t>(st->rules.tally_command, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
   auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
   for (int g = 0; g < DT_GEMMS; ++g)
@@ -2397,255 +2350,109 @@ int32_t ohw_audio_ctx_for(int64_t n_samples) {
   return (int32_t)std::min<int64_t>(1500, (pos + 63) / 64 * 64);
 }
 
+// the four logit rules of a state: LogitRules (logit_rules.hpp) checks, builds and uploads; a setter waits for the state's stream
 int ohw_state_set_logit_bias(ohw_state* st, const float* bias, int n) {
   return guard([&] {
     if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
-    HIP_CHECK(hipSetDevice(st->ctx->device));
-    HIP_CHECK(hipStreamSynchronize(st->stream));
-    if (!bias) { st->bias_on = false; st->bias_host.clear(); return; }
-    if (n != st->ctx->hp.n_vocab) throw Error(OHW_E_INVALID_ARG, "logit bias: n must equal n_vocab");
-    // -inf means "never" (the samplers give such an entry probability 0); +inf and NaN would poison a row's log-sum-exp
-    for (int i = 0; i < n; ++i)
-      if (std::isnan(bias[i]) || bias[i] == INFINITY) throw Error(OHW_E_INVALID_ARG, "logit bias: entry " + std::to_string(i) + " is +inf or NaN");
-    if (!st->logit_bias.p) st->logit_bias.alloc((size_t)n * 4);
-    HIP_CHECK(hipMemcpy(st->logit_bias.p, bias, (size_t)n * 4, hipMemcpyHostToDevice));
-    st->bias_host.assign(bias, bias + n);
-    st->bias_on = true;
+    st->rules.set_bias(bias, n);
   });
-}
-
-static void phrase_upload(ohw_state* st, const ohw_phrase_table* t, int n_vocab) {
-  std::vector<int32_t> words;
-  phrase_table_pack(t, n_vocab, &words);
-  if (!st->ph_table.p) st->ph_table.alloc((size_t)PH_WORDS * 4, true);
-  HIP_CHECK(hipMemcpy(st->ph_table.p, words.data(), words.size() * 4, hipMemcpyHostToDevice));
 }
 
 int ohw_state_set_phrase_table(ohw_state* st, const int32_t* tokens, const int32_t* offsets, const float* boosts, int n_phrases) {
   return guard([&] {
     if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
-    HIP_CHECK(hipSetDevice(st->ctx->device));
-    HIP_CHECK(hipStreamSynchronize(st->stream));
-    if (n_phrases == 0) { st->ph_on = false; return; }
-    // built aside first: a refused table leaves the one in effect as it was
-    std::vector<int32_t> child_off((size_t)OHW_PHRASE_MAX_NODES + 1), path((size_t)OHW_PHRASE_MAX_PATH), child_tok((size_t)OHW_PHRASE_MAX_EDGES);
-    std::vector<float> child_boost((size_t)OHW_PHRASE_MAX_EDGES);
-    ohw_phrase_table t{};
-    t.child_off = child_off.data(); t.path = path.data(); t.child_tok = child_tok.data(); t.child_boost = child_boost.data();
-    phrase_table_build_host(tokens, offsets, boosts, n_phrases, st->ctx->tok.eot, &t);
-    phrase_upload(st, &t, st->ctx->hp.n_vocab);
-    st->ph_child_off.swap(child_off); st->ph_path.swap(path); st->ph_child_tok.swap(child_tok); st->ph_child_boost.swap(child_boost);
-    st->ph_host = t;
-    st->ph_src_tok.assign(tokens, tokens + offsets[n_phrases]);
-    st->ph_src_off.assign(offsets, offsets + n_phrases + 1);
-    st->ph_src_boost.assign(boosts, boosts + n_phrases);
-    st->ph_on = true;
+    st->rules.set_phrases(tokens, offsets, boosts, n_phrases);
   });
 }
 
-int ohw_state_phrase_count(const ohw_state* st) { return st && st->ph_on ? st->ph_host.n_phrases : 0; }
-
-// test entry: phrase_boost_kernel once on caller data (include/ohw.h).  Everything is range-checked first: the kernel indexes
-// with these values
-int ohw_dbg_phrase_boost(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
-                         const int32_t* n_cur, const int32_t* done, const ohw_phrase_table* table) {
-  return guard([&] {
-    if (!st || !logits || !histories || !n_cur || !done || !table) throw Error(OHW_E_INVALID_ARG, "null argument");
-    if (rows < 1 || rows > 4096 || n_vocab < 1 || ld < n_vocab || max_tokens < 1 || max_tokens > 65536) throw Error(OHW_E_INVALID_ARG, "dbg_phrase_boost: bad shape");
-    for (int r = 0; r < rows; ++r)
-      if (n_cur[r] < 0 || n_cur[r] > max_tokens) throw Error(OHW_E_INVALID_ARG, "dbg_phrase_boost: n_cur out of range");
-    HIP_CHECK(hipSetDevice(st->ctx->device));
-    hipStream_t s = st->stream;
-    HIP_CHECK(hipStreamSynchronize(s));
-    struct Restore {       // the state's own table is in effect again afterwards, also when a step below throws
-      ohw_state* st;
-      ~Restore() {
-        if (!st->ph_on) return;
-        try { phrase_upload(st, &st->ph_host, st->ctx->hp.n_vocab); } catch (...) { st->ph_on = false; }
-      }
-    } restore{st};
-    phrase_upload(st, table, n_vocab);
-    DevBuf d_logits, d_hist, d_ncur, d_done;
-    d_logits.alloc((size_t)rows * ld * 4); d_hist.alloc((size_t)rows * max_tokens * 4); d_ncur.alloc((size_t)rows * 4); d_done.alloc((size_t)rows * 4);
-    HIP_CHECK(hipMemcpyAsync(d_logits.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_hist.p, histories, (size_t)rows * max_tokens * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_ncur.p, n_cur, (size_t)rows * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_done.p, done, (size_t)rows * 4, hipMemcpyHostToDevice, s));
-    PhraseBoostParams b{};
-    b.logits = d_logits.as<float>(); b.ld = ld; b.n_vocab = n_vocab; b.max_tokens = max_tokens; b.row_mul = 1; b.group = 1;
-    b.tokens = d_hist.as<int32_t>(); b.n_cur = d_ncur.as<int32_t>(); b.done = d_done.as<int32_t>(); b.table = st->ph_table.as<int32_t>();
-    launch_phrase_boost(b, rows, s);
-    HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  });
-}
-
-static void repeat_upload(ohw_state* st, float penalty, int ngram) {
-  int32_t words[2];
-  std::memcpy(&words[0], &penalty, 4);
-  words[1] = ngram;
-  if (!st->rp_rule.p) st->rp_rule.alloc(sizeof words, true);
-  HIP_CHECK(hipMemcpy(st->rp_rule.p, words, sizeof words, hipMemcpyHostToDevice));
-}
+int ohw_state_phrase_count(const ohw_state* st) { return st ? st->rules.phrase_count() : 0; }
 
 int ohw_state_set_repeat_rule(ohw_state* st, float penalty, int ngram) {
   return guard([&] {
     repeat_rule_check(penalty, ngram);                 // the values first: a refusal needs no state and no device
     if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
-    const bool on = penalty != 1.0f || ngram != 0;
-    if (on || st->rp_rule.p) {                         // a state that never had the rule on owns no buffer and needs none
-      HIP_CHECK(hipSetDevice(st->ctx->device));
-      HIP_CHECK(hipStreamSynchronize(st->stream));
-      repeat_upload(st, penalty, ngram);
-    }
-    st->rp_penalty = penalty; st->rp_ngram = ngram; st->rp_on = on;
+    st->rules.set_repeat(penalty, ngram);
   });
 }
 
 int ohw_state_repeat_rule(const ohw_state* st, float* penalty, int* ngram) {
   if (!st || !penalty || !ngram) return OHW_E_INVALID_ARG;
-  *penalty = st->rp_penalty; *ngram = st->rp_ngram;
+  *penalty = st->rules.rp.penalty; *ngram = st->rules.rp.ngram;
   return OHW_OK;
 }
-
-// test entry: repeat_rule_kernel once on caller data (include/ohw.h).  Everything is range-checked first: the kernel indexes
-// with these values
-int ohw_dbg_repeat_rule(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
-                        const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int ngram, int eot) {
-  return guard([&] {
-    repeat_rule_check(penalty, ngram);
-    if (!st || !logits || !histories || !done) throw Error(OHW_E_INVALID_ARG, "null argument");
-    if (rows < 1 || rows > 4096 || n_vocab < 1 || ld < n_vocab || max_tokens < 1 || max_tokens > 4096 || eot < 0 || n_entries < 1 || n_entries > 4096 ||
-        row_mul < 1 || row_mul > 64 || group < 1 || group > 64)
-      throw Error(OHW_E_INVALID_ARG, "dbg_repeat_rule: bad shape");
-    if ((int64_t)(rows - 1) * row_mul / group >= n_entries) throw Error(OHW_E_INVALID_ARG, "dbg_repeat_rule: a launch row maps behind the last entry");
-    for (int i = 0; n_cur && i < n_entries; ++i)
-      if (n_cur[i] < 0 || n_cur[i] > max_tokens) throw Error(OHW_E_INVALID_ARG, "dbg_repeat_rule: n_cur out of range");
-    HIP_CHECK(hipSetDevice(st->ctx->device));
-    hipStream_t s = st->stream;
-    HIP_CHECK(hipStreamSynchronize(s));
-    struct Restore {       // the state's own setting is in effect again afterwards, also when a step below throws
-      ohw_state* st;
-      ~Restore() {
-        try { repeat_upload(st, st->rp_penalty, st->rp_ngram); } catch (...) { st->rp_on = false; st->rp_penalty = 1.0f; st->rp_ngram = 0; }
-      }
-    } restore{st};
-    repeat_upload(st, penalty, ngram);
-    const size_t hist_rows = (size_t)n_entries * group;
-    DevBuf d_logits, d_hist, d_ncur, d_done;
-    d_logits.alloc((size_t)rows * ld * 4); d_hist.alloc(hist_rows * max_tokens * 4); d_ncur.alloc((size_t)n_entries * 4); d_done.alloc((size_t)n_entries * 4);
-    HIP_CHECK(hipMemcpyAsync(d_logits.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_hist.p, histories, hist_rows * max_tokens * 4, hipMemcpyHostToDevice, s));
-    if (n_cur) HIP_CHECK(hipMemcpyAsync(d_ncur.p, n_cur, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_done.p, done, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
-    RepeatRuleParams q{};
-    q.logits = d_logits.as<float>(); q.ld = ld; q.n_vocab = n_vocab; q.max_tokens = max_tokens; q.row_mul = row_mul; q.group = group; q.eot = eot;
-    q.tokens = d_hist.as<int32_t>(); q.n_cur = n_cur ? d_ncur.as<int32_t>() : nullptr; q.done = d_done.as<int32_t>(); q.rule = st->rp_rule.as<int32_t>();
-    launch_repeat_rule(q, rows, s);
-    HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  });
-}
-
-static void command_upload(ohw_state* st, const ohw_command_table* t, float penalty) {
-  std::vector<int32_t> words;
-  command_table_pack(t, penalty, &words);
-  if (!st->cm_table.p) st->cm_table.alloc((size_t)CM_WORDS * 4, true);
-  if (!st->cm_lp.p) {
-    const std::vector<float> nan((size_t)st->max_batch, std::numeric_limits<float>::quiet_NaN());
-    st->cm_lp.alloc(nan.size() * 4, true);
-    HIP_CHECK(hipMemcpy(st->cm_lp.p, nan.data(), nan.size() * 4, hipMemcpyHostToDevice));
-  }
-  HIP_CHECK(hipMemcpy(st->cm_table.p, words.data(), words.size() * 4, hipMemcpyHostToDevice));
-}
-
-// the five arrays of a command table, sized for the limits, and the table that points into them
-struct CommandArrays {
-  std::vector<int32_t> child_off, path, child_tok, terminal, phrase_id;
-  ohw_command_table t{};
-  CommandArrays()
-      : child_off((size_t)OHW_COMMAND_MAX_NODES + 1), path((size_t)OHW_COMMAND_MAX_PATH), child_tok((size_t)OHW_COMMAND_MAX_EDGES),
-        terminal((size_t)OHW_COMMAND_MAX_NODES), phrase_id((size_t)OHW_COMMAND_MAX_NODES) {
-    t.child_off = child_off.data(); t.path = path.data(); t.child_tok = child_tok.data(); t.terminal = terminal.data(); t.phrase_id = phrase_id.data();
-  }
-};
 
 int ohw_state_set_command_table(ohw_state* st, const int32_t* tokens, const int32_t* offsets, int n_phrases, float penalty) {
   return guard([&] {
     if (n_phrases != 0) command_penalty_check(penalty);  // the value first: a refusal needs no state and no device
     if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
-    HIP_CHECK(hipSetDevice(st->ctx->device));
-    HIP_CHECK(hipStreamSynchronize(st->stream));
-    if (n_phrases == 0) { st->cm_on = false; return; }
-    // built aside first: a refused list leaves the one in effect as it was
-    CommandArrays a;
-    command_table_build_host(tokens, offsets, n_phrases, st->ctx->tok.eot, &a.t);
-    command_upload(st, &a.t, penalty);
-    st->cm_child_off.swap(a.child_off); st->cm_path.swap(a.path); st->cm_child_tok.swap(a.child_tok); st->cm_terminal.swap(a.terminal);
-    st->cm_phrase_id.swap(a.phrase_id);
-    st->cm_host = a.t;                                   // the vectors' storage moved with the swap: the pointers hold
-    st->cm_src_tok.assign(tokens, tokens + offsets[n_phrases]);
-    st->cm_src_off.assign(offsets, offsets + n_phrases + 1);
-    st->cm_penalty = penalty;
-    st->cm_on = true;
+    st->rules.set_commands(tokens, offsets, n_phrases, penalty);
   });
 }
 
-int ohw_state_command_count(const ohw_state* st) { return st && st->cm_on ? st->cm_host.n_phrases : 0; }
+int ohw_state_command_count(const ohw_state* st) { return st ? st->rules.command_count() : 0; }
 
 int ohw_state_command_list_logprob(ohw_state* st, int batch, float* out) {
   return guard([&] {
     if (!st || !out) throw Error(OHW_E_INVALID_ARG, "null argument");
-    if (!st->cm_on) throw Error(OHW_E_INVALID_ARG, "command list: none is set on this state");
-    if (batch < 1 || batch > st->max_batch) throw Error(OHW_E_INVALID_ARG, "command list: batch must lie in 1..max_batch");
-    HIP_CHECK(hipSetDevice(st->ctx->device));
-    HIP_CHECK(hipStreamSynchronize(st->stream));
-    HIP_CHECK(hipMemcpy(out, st->cm_lp.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    st->rules.list_logprob(batch, out);
   });
 }
 
-// test entry: command_rule_kernel once on caller data (include/ohw.h).  Everything is range-checked first: the kernel indexes
-// with these values
+// test entry: phrase_boost_kernel once on caller data: one history, length and flag per launch row
+int ohw_dbg_phrase_boost(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                         const int32_t* n_cur, const int32_t* done, const ohw_phrase_table* table) {
+  return guard([&] {
+    if (!st || !logits || !histories || !n_cur || !done || !table) throw Error(OHW_E_INVALID_ARG, "null argument");
+    LogitRules own;
+    dbg_rule_rows(st, "dbg_phrase_boost", {logits, rows, ld, n_vocab, histories, max_tokens, n_cur, done, rows, 1, 1, 0}, 65536, INT32_MAX,
+                  [&] { own.upload_phrases(table, n_vocab); },         // checks the table's every count and child token
+                  [&](float* d_logits, const int32_t* d_hist, const int32_t* d_ncur, const int32_t* d_done, hipStream_t s) {
+                    PhraseBoostParams b{};
+                    b.logits = d_logits; b.ld = ld; b.n_vocab = n_vocab; b.max_tokens = max_tokens; b.row_mul = 1; b.group = 1;
+                    b.tokens = d_hist; b.n_cur = d_ncur; b.done = d_done; b.table = own.ph.table.as<int32_t>();
+                    launch_phrase_boost(b, rows, s);
+                  });
+  });
+}
+
+// test entry: repeat_rule_kernel once on caller data
+int ohw_dbg_repeat_rule(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
+                        const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int ngram, int eot) {
+  return guard([&] {
+    repeat_rule_check(penalty, ngram);
+    if (!st || !logits || !histories || !done) throw Error(OHW_E_INVALID_ARG, "null argument");
+    LogitRules own;
+    dbg_rule_rows(st, "dbg_repeat_rule", {logits, rows, ld, n_vocab, histories, max_tokens, n_cur, done, n_entries, row_mul, group, eot}, 4096, INT32_MAX,
+                  [&] { own.upload_repeat(penalty, ngram); },
+                  [&](float* d_logits, const int32_t* d_hist, const int32_t* d_ncur, const int32_t* d_done, hipStream_t s) {
+                    RepeatRuleParams q{};
+                    q.logits = d_logits; q.ld = ld; q.n_vocab = n_vocab; q.max_tokens = max_tokens; q.row_mul = row_mul; q.group = group; q.eot = eot;
+                    q.tokens = d_hist; q.n_cur = d_ncur; q.done = d_done; q.rule = own.rp.rule.as<int32_t>();
+                    launch_repeat_rule(q, rows, s);
+                  });
+  });
+}
+
+// test entry: command_rule_kernel once on caller data; list_logprob [n_entries] goes in and comes back like the logits
 int ohw_dbg_command_rule(ohw_state* st, float* logits, int rows, int64_t ld, int n_vocab, const int32_t* histories, int max_tokens,
                          const int32_t* n_cur, const int32_t* done, int n_entries, int row_mul, int group, float penalty, int eot,
                          const ohw_command_table* table, float* list_logprob) {
   return guard([&] {
     command_penalty_check(penalty);
     if (!st || !logits || !histories || !done || !table || !list_logprob) throw Error(OHW_E_INVALID_ARG, "null argument");
-    if (rows < 1 || rows > 4096 || n_vocab < 1 || n_vocab > CM_MAX_VOCAB || ld < n_vocab || max_tokens < 1 || max_tokens > 4096 || eot < 0 || n_entries < 1 ||
-        n_entries > 4096 || row_mul < 1 || row_mul > 64 || group < 1 || group > 64)
-      throw Error(OHW_E_INVALID_ARG, "dbg_command_rule: bad shape");
-    if ((int64_t)(rows - 1) * row_mul / group >= n_entries) throw Error(OHW_E_INVALID_ARG, "dbg_command_rule: a launch row maps behind the last entry");
-    for (int i = 0; n_cur && i < n_entries; ++i)
-      if (n_cur[i] < 0 || n_cur[i] > max_tokens) throw Error(OHW_E_INVALID_ARG, "dbg_command_rule: n_cur out of range");
-    HIP_CHECK(hipSetDevice(st->ctx->device));
-    hipStream_t s = st->stream;
-    HIP_CHECK(hipStreamSynchronize(s));
-    struct Restore {       // the state's own list is in effect again afterwards, also when a step below throws
-      ohw_state* st;
-      ~Restore() {
-        if (!st->cm_on) return;
-        try { command_upload(st, &st->cm_host, st->cm_penalty); } catch (...) { st->cm_on = false; }
-      }
-    } restore{st};
-    command_upload(st, table, penalty);                  // checks the table's every count and index
-    const size_t hist_rows = (size_t)n_entries * group;
-    DevBuf d_logits, d_hist, d_ncur, d_done, d_lp;
-    d_logits.alloc((size_t)rows * ld * 4); d_hist.alloc(hist_rows * max_tokens * 4); d_ncur.alloc((size_t)n_entries * 4); d_done.alloc((size_t)n_entries * 4);
-    d_lp.alloc((size_t)n_entries * 4);
-    HIP_CHECK(hipMemcpyAsync(d_logits.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_hist.p, histories, hist_rows * max_tokens * 4, hipMemcpyHostToDevice, s));
-    if (n_cur) HIP_CHECK(hipMemcpyAsync(d_ncur.p, n_cur, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_done.p, done, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_lp.p, list_logprob, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
-    CommandRuleParams q{};
-    q.logits = d_logits.as<float>(); q.ld = ld; q.n_vocab = n_vocab; q.max_tokens = max_tokens; q.row_mul = row_mul; q.group = group; q.lp_group = group;
-    q.eot = eot; q.tokens = d_hist.as<int32_t>(); q.n_cur = n_cur ? d_ncur.as<int32_t>() : nullptr; q.done = d_done.as<int32_t>();
-    q.table = st->cm_table.as<int32_t>(); q.list_logprob = d_lp.as<float>();
-    launch_command_rule(q, rows, s);
-    HIP_CHECK(hipMemcpyAsync(logits, d_logits.p, (size_t)rows * ld * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(list_logprob, d_lp.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    LogitRules own;
+    own.max_batch = std::max(n_entries, 0);              // its list_logprob buffer holds the caller's entries
+    dbg_rule_rows(st, "dbg_command_rule", {logits, rows, ld, n_vocab, histories, max_tokens, n_cur, done, n_entries, row_mul, group, eot}, 4096, CM_MAX_VOCAB,
+                  [&] { own.upload_commands(table, penalty); },        // checks the table's every count and index
+                  [&](float* d_logits, const int32_t* d_hist, const int32_t* d_ncur, const int32_t* d_done, hipStream_t s) {
+                    float* d_lp = own.cm.lp.as<float>();
+                    HIP_CHECK(hipMemcpyAsync(d_lp, list_logprob, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+                    CommandRuleParams q{};
+                    q.logits = d_logits; q.ld = ld; q.n_vocab = n_vocab; q.max_tokens = max_tokens; q.row_mul = row_mul; q.group = group; q.lp_group = group;
+                    q.eot = eot; q.tokens = d_hist; q.n_cur = d_ncur; q.done = d_done; q.table = own.cm.table.as<int32_t>(); q.list_logprob = d_lp;
+                    launch_command_rule(q, rows, s);
+                    HIP_CHECK(hipMemcpyAsync(list_logprob, d_lp, (size_t)n_entries * 4, hipMemcpyDeviceToHost, s));
+                  });
   });
 }
 

@@ -812,14 +812,9 @@ int ohw_engine_set_hot_phrases_tokens(ohw_engine* e, const int32_t* tokens, cons
     if (!e || n_phrases < 0 || (n_phrases > 0 && (!tokens || !offsets))) throw Error(OHW_E_INVALID_ARG, "hot phrases: bad argument");
     const std::vector<float> ones((size_t)n_phrases, 1.0f);
     if (!boosts) boosts = ones.data();
-    // the engine's own state first: a table it refuses reaches no other state
+    // on the engine's own state: the next transcribe hands its rules to the other states it decodes on (transcribe.cpp)
     const int rc = ohw_state_set_phrase_table(e->state, tokens, offsets, boosts, n_phrases);
     if (rc != OHW_OK) throw Error(rc, g_last_error);
-    each_state(e, [&](ohw_state* st) {
-      if (st == e->state) return;
-      const int rc2 = ohw_state_set_phrase_table(st, tokens, offsets, boosts, n_phrases);
-      if (rc2 != OHW_OK) throw Error(rc2, g_last_error);
-    });
   });
 }
 int ohw_engine_set_hot_phrases(ohw_engine* e, const char* const* texts, const float* boosts, int n) {
@@ -855,27 +850,17 @@ int ohw_engine_set_hot_phrases(ohw_engine* e, const char* const* texts, const fl
 
 int ohw_engine_set_repetition(ohw_engine* e, float penalty, int ngram) {
   return guard([&] {
-    // the engine's own state first (the state setter checks the values ahead of the state): refused values reach no state
+    // on the engine's own state, as above (the state setter checks the values ahead of the state)
     const int rc = ohw_state_set_repeat_rule(e ? e->state : nullptr, penalty, ngram);
     if (rc != OHW_OK) throw Error(rc, g_last_error);
-    each_state(e, [&](ohw_state* st) {
-      if (st == e->state) return;
-      const int rc2 = ohw_state_set_repeat_rule(st, penalty, ngram);
-      if (rc2 != OHW_OK) throw Error(rc2, g_last_error);
-    });
   });
 }
 
 static void engine_set_commands_tokens(ohw_engine* e, const int32_t* tokens, const int32_t* offsets, int n_phrases, float penalty, std::vector<int32_t> index) {
   if (!e || n_phrases < 0 || (n_phrases > 0 && (!tokens || !offsets))) throw Error(OHW_E_INVALID_ARG, "commands: bad argument");
-  // the engine's own state first: a list or a penalty it refuses reaches no other state
+  // on the engine's own state, as the hot phrases
   const int rc = ohw_state_set_command_table(e->state, tokens, offsets, n_phrases, penalty);
   if (rc != OHW_OK) throw Error(rc, g_last_error);
-  each_state(e, [&](ohw_state* st) {
-    if (st == e->state) return;
-    const int rc2 = ohw_state_set_command_table(st, tokens, offsets, n_phrases, penalty);
-    if (rc2 != OHW_OK) throw Error(rc2, g_last_error);
-  });
   e->cmd_index.swap(index);
 }
 

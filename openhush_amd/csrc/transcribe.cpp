@@ -7,16 +7,12 @@
 #include <memory>
 
 #include "host_engine.hpp"
+#include "logit_rules.hpp"
 #include "model.hpp"
 #include "window_policy.hpp"
 
 namespace ohw {
-const float* state_bias_host(const ohw_state* st);
-const ohw_phrase_table* state_phrase_table_host(const ohw_state* st);
-bool state_repeat_rule_host(const ohw_state* st, float* penalty, int* ngram);
-const ohw_command_table* state_command_table_host(const ohw_state* st, float* penalty);
-int state_commands_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets);
-int state_phrases_src(const ohw_state* st, const int32_t** tokens, const int32_t** offsets, const float** boosts);
+LogitRules& state_rules(ohw_state* st);
 void state_share_recording(ohw_state* dst, ohw_state* src);
 void state_drop_recording(ohw_state* st);
 void state_set_graph_max_batch(ohw_state* st, int max_batch);
@@ -185,7 +181,7 @@ struct TranscribeCall {
   // command lists: list_logprob of the device pass that just ran on the batch's state, into the runs of its active windows (every
   // device pass writes entry b for window b); nothing with no list set
   void read_list_logprob(const Batch& bt, const int32_t* active, std::vector<WindowRun>& runs) const {
-    if (!state_command_table_host(bt.st, nullptr)) return;
+    if (!state_rules(bt.st).cm.on) return;
     std::vector<float> lp((size_t)bt.B);
     check(ohw_state_command_list_logprob(bt.st, bt.B, lp.data()));
     for (int b = 0; b < bt.B; ++b)
@@ -297,17 +293,8 @@ struct TranscribeCall {
         if (!live[(size_t)b]) continue;
         WindowRun& r = pass[(size_t)b];
         float lp = 0.f;
-        if (const ohw_phrase_table* pt = state_phrase_table_host(bt.st))     // the state's hot phrases, ahead of the bias as on the device
-          check(ohw_phrase_boost_host(pt, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V));
-        float rp_theta = 1.f;
-        int rp_n = 0;
-        if (state_repeat_rule_host(bt.st, &rp_theta, &rp_n))                 // the state's repetition rule, behind the boost as on the device
-          check(ohw_repeat_rule_host(rp_theta, rp_n, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V, tk.eot));
-        float cm_p = 0.f;
-        if (const ohw_command_table* ct = state_command_table_host(bt.st, &cm_p))     // the state's command list, behind the repetition rule as on the device
-          check(ohw_command_rule_host(ct, cm_p, r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V, tk.eot, &r.list_lp));
-        if (const float* bias = state_bias_host(bt.st))          // the state's logit bias: the device sampler adds it itself
-          for (int i2 = 0; i2 < V; ++i2) logits[(size_t)b * V + i2] += bias[i2];
+        // the state's rules and its bias, in the device's order (LogitRules::apply and the samplers)
+        check(state_rules(bt.st).apply_host(r.tok.data(), (int)r.tok.size(), &logits[(size_t)b * V], V, tk.eot, &r.list_lp));
         const int32_t t = ohw_sample_host(e->ctx, &sp, &logits[(size_t)b * V], r.tok.data(), (int)r.tok.size(), T, bt.rngs[b], &lp, &r.nosp);
         if (t < 0) throw Error(OHW_E_TRANSCRIBE, "Transcription failed: host sampler");
         r.tok.push_back(t); r.plog.push_back(lp);
@@ -442,8 +429,8 @@ struct TranscribeCall {
     }
     out.marks.push_back(WindowMark{win_text0, (int32_t)(out.token_times.size() - tt0), (int32_t)(out.words.size() - wd0), (int32_t)(out.segments.size() - sg0)});
     out.contexts.push_back(ctx);
-    if (const ohw_command_table* ct = state_command_table_host(e->state, nullptr)) {
-      const int id = ohw_command_match_host(ct, r.tok.data(), keep);
+    if (const LogitRules& rules = state_rules(e->state); rules.cm.on) {
+      const int id = ohw_command_match_host(&rules.cm.host, r.tok.data(), keep);
       const int32_t phrase = id < 0 ? -1 : (size_t)id < e->cmd_index.size() ? e->cmd_index[(size_t)id] : id;
       out.commands.push_back(ohw_command_hit{(int32_t)out.quality.size(), phrase, r.list_lp});
     }
@@ -771,74 +758,15 @@ struct SharedRecording {      // every state of this transcribe reads the record
     for (ohw_state* st : e->lane_states) state_drop_recording(st);
   }
 };
-// the logit bias of the engine's own state (ohw_state_set_logit_bias on ohw_engine_state(e): the engine's form of
-// whisper.cpp's logits_filter_callback) applies to every state a schedule decodes on, or to none
-void propagate_logit_bias(ohw_engine* e) {
-  const float* bias = state_bias_host(e->state);
-  const int V = e->ctx->hp.n_vocab;
-  auto same = [&](ohw_state* st) {
-    if (st == e->state) return;
-    const float* b2 = state_bias_host(st);
-    if (!bias && !b2) return;
-    if (bias && b2 && std::memcmp(bias, b2, (size_t)V * sizeof(float)) == 0) return;
-    check(ohw_state_set_logit_bias(st, bias, bias ? V : 0));
-  };
-  for (ohw_state* st : e->states) same(st);
-  for (ohw_state* st : e->lane_states) same(st);
-}
-
-// the hot phrases of the engine's own state (ohw_engine_set_hot_phrases), on the states a schedule made since they were set
-void propagate_hot_phrases(ohw_engine* e) {
-  const int32_t *tok = nullptr, *off = nullptr;
-  const float* boost = nullptr;
-  const int n = state_phrases_src(e->state, &tok, &off, &boost);
-  auto same = [&](ohw_state* st) {
-    if (st == e->state) return;
-    const int32_t *tok2 = nullptr, *off2 = nullptr;
-    const float* boost2 = nullptr;
-    const int n2 = state_phrases_src(st, &tok2, &off2, &boost2);
-    if (n == 0 && n2 == 0) return;
-    if (n == n2 && std::memcmp(off, off2, (size_t)(n + 1) * 4) == 0 && std::memcmp(tok, tok2, (size_t)off[n] * 4) == 0 &&
-        std::memcmp(boost, boost2, (size_t)n * 4) == 0)
-      return;
-    check(ohw_state_set_phrase_table(st, tok, off, boost, n));
-  };
-  for (ohw_state* st : e->states) same(st);
-  for (ohw_state* st : e->lane_states) same(st);
-}
-
-// the repetition rule of the engine's own state (ohw_engine_set_repetition), on the states a schedule made since it was set
-void propagate_repetition(ohw_engine* e) {
-  float theta = 1.f, theta2 = 1.f;
-  int n = 0, n2 = 0;
-  check(ohw_state_repeat_rule(e->state, &theta, &n));
-  auto same = [&](ohw_state* st) {
-    if (st == e->state) return;
-    check(ohw_state_repeat_rule(st, &theta2, &n2));
-    if (theta2 != theta || n2 != n) check(ohw_state_set_repeat_rule(st, theta, n));
-  };
-  for (ohw_state* st : e->states) same(st);
-  for (ohw_state* st : e->lane_states) same(st);
-}
-
-// the command list of the engine's own state (ohw_engine_set_commands), on the states a schedule made since it was set
-void propagate_commands(ohw_engine* e) {
-  const int32_t *tok = nullptr, *off = nullptr;
-  float p = 0.f;
-  const int n = state_commands_src(e->state, &tok, &off);
-  (void)state_command_table_host(e->state, &p);
-  auto same = [&](ohw_state* st) {
-    if (st == e->state) return;
-    const int32_t *tok2 = nullptr, *off2 = nullptr;
-    float p2 = 0.f;
-    const int n2 = state_commands_src(st, &tok2, &off2);
-    (void)state_command_table_host(st, &p2);
-    if (n == 0 && n2 == 0) return;
-    if (n == n2 && p == p2 && std::memcmp(off, off2, (size_t)(n + 1) * 4) == 0 && std::memcmp(tok, tok2, (size_t)off[n] * 4) == 0) return;
-    check(ohw_state_set_command_table(st, tok, off, n, p));
-  };
-  for (ohw_state* st : e->states) same(st);
-  for (ohw_state* st : e->lane_states) same(st);
+// the logit rules of the engine's own state (the engine's setters, or the ohw_state_set_* entries on ohw_engine_state(e): a logit
+// bias is the engine's form of whisper.cpp's logits_filter_callback) apply to every state a schedule decodes on, or to none.
+// This is the one delivery: the other states exist from ensure_schedule_resources on and decode only in this transcribe
+void sync_logit_rules(ohw_engine* e) {
+  try {
+    each_state(e, [&](ohw_state* st) { state_rules(st).sync_from(state_rules(e->state)); });
+  } catch (const Error& err) {
+    throw Error(OHW_E_TRANSCRIBE, std::string("Transcription failed: ") + err.what());
+  }
 }
 
 void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n, int64_t win_first, int64_t win_step) {
@@ -856,10 +784,7 @@ void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n,
   // sensitive to last bits, so the times must not depend on how the windows were dealt
   Invariant invariant(e, cuts.n_batches > 1 || (!e->wt_heads.empty() && win_step > 1));
   SharedRecording shared_recording(e, cuts.rec_mel);
-  propagate_logit_bias(e);
-  propagate_hot_phrases(e);
-  propagate_repetition(e);
-  propagate_commands(e);
+  sync_logit_rules(e);
   apply_ctx(e, call_ctx);
   if (schedule == OHW_SCHEDULE_SEQUENTIAL) cuts.sequential();
   else if (schedule == OHW_SCHEDULE_PIPELINE) cuts.pipeline();

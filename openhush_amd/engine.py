@@ -259,6 +259,17 @@ class PhraseTable:
         return out
 
 
+def _dbg_rule_rows(logits, histories, n_cur, done, group):
+    """what the three rule test entries take: a copy of logits [rows][ld] (it comes back changed), histories [entries * group][max_tokens],
+    n_cur (None stays None) and done [entries]"""
+    lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
+    h = np.ascontiguousarray(histories, dtype=np.int32)
+    dn = np.ascontiguousarray(done, dtype=np.int32)
+    nc = None if n_cur is None else np.ascontiguousarray(n_cur, dtype=np.int32)
+    assert lg.ndim == 2 and h.ndim == 2 and h.shape[0] == dn.size * group and (nc is None or nc.size == dn.size)
+    return lg, h, nc, dn
+
+
 def _flat_phrases(phrases, boosts):
     """token lists -> (tokens, offsets, boosts) as the C ABI takes them"""
     lens = [len(p) for p in phrases]
@@ -1646,12 +1657,8 @@ class State:
         """ohw_dbg_command_rule: the kernel once on logits [rows][ld] (a copy comes back whole), histories [entries * group][max_tokens],
         n_cur (None: every history is empty) and done [entries]; launch row r reads history row r * row_mul under entry
         r * row_mul // group -> (logits, list_logprob [entries], `sentinel` where the kernel wrote nothing)"""
-        lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
-        h = np.ascontiguousarray(histories, dtype=np.int32)
-        dn = np.ascontiguousarray(done, dtype=np.int32)
-        nc = None if n_cur is None else np.ascontiguousarray(n_cur, dtype=np.int32)
+        lg, h, nc, dn = _dbg_rule_rows(logits, histories, n_cur, done, group)
         lp = np.full(dn.size, sentinel, dtype=np.float32)
-        assert lg.ndim == 2 and h.ndim == 2 and h.shape[0] == dn.size * group and (nc is None or nc.size == dn.size)
         _check(lib().ohw_dbg_command_rule(self.h, _fp(lg), lg.shape[0], lg.shape[1], int(n_vocab), _ip(h), h.shape[1], None if nc is None else _ip(nc),
                                           _ip(dn), dn.size, int(row_mul), int(group), float(penalty), int(eot), C.byref(table.c), _fp(lp)))
         return lg, lp
@@ -1671,21 +1678,15 @@ class State:
                         row_mul: int = 1, group: int = 1) -> np.ndarray:
         """ohw_dbg_repeat_rule: the kernel once on logits [rows][ld] (a copy comes back whole), histories [entries * group][max_tokens],
         n_cur (None: every history is empty) and done [entries]; launch row r reads history row r * row_mul under entry r * row_mul // group"""
-        lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
-        h = np.ascontiguousarray(histories, dtype=np.int32)
-        dn = np.ascontiguousarray(done, dtype=np.int32)
-        nc = None if n_cur is None else np.ascontiguousarray(n_cur, dtype=np.int32)
-        assert lg.ndim == 2 and h.ndim == 2 and h.shape[0] == dn.size * group and (nc is None or nc.size == dn.size)
+        lg, h, nc, dn = _dbg_rule_rows(logits, histories, n_cur, done, group)
         _check(lib().ohw_dbg_repeat_rule(self.h, _fp(lg), lg.shape[0], lg.shape[1], int(n_vocab), _ip(h), h.shape[1], None if nc is None else _ip(nc),
                                          _ip(dn), dn.size, int(row_mul), int(group), float(penalty), int(ngram), int(eot)))
         return lg
 
     def dbg_phrase_boost(self, logits: np.ndarray, n_vocab: int, histories: np.ndarray, n_cur, done, table: PhraseTable) -> np.ndarray:
         """ohw_dbg_phrase_boost: the kernel once on logits [rows][ld] (a copy comes back whole), histories [rows][max_tokens]"""
-        lg = np.ascontiguousarray(logits, dtype=np.float32).copy()
-        h = np.ascontiguousarray(histories, dtype=np.int32)
-        nc, dn = np.ascontiguousarray(n_cur, dtype=np.int32), np.ascontiguousarray(done, dtype=np.int32)
-        assert lg.ndim == 2 and h.ndim == 2 and h.shape[0] == lg.shape[0] == nc.size == dn.size
+        lg, h, nc, dn = _dbg_rule_rows(logits, histories, n_cur, done, 1)
+        assert nc is not None and dn.size == lg.shape[0]
         _check(lib().ohw_dbg_phrase_boost(self.h, _fp(lg), lg.shape[0], lg.shape[1], int(n_vocab), _ip(h), h.shape[1], _ip(nc), _ip(dn), C.byref(table.c)))
         return lg
 
