@@ -51,10 +51,12 @@ def test_single_token_steps_match_the_launch_path_and_the_oracle(E, oracle, tmp_
         feed = l0l.argmax(axis=1).astype(np.int32)[:, None]
         n_past = [3] * rows
         worst = 0.0
+        path0, row0 = [int(t) for t in prompt[0]], []                   # row 0: the tokens it was fed, its persistent logits per step
         for step in range(6):
             lp, ll = sp.decode(feed, n_past), sl.decode(feed, n_past)
             worst = max(worst, float(np.abs(lp - ll).max()))
             assert np.abs(lp - ll).max() < tol, (preset, rows, step, float(np.abs(lp - ll).max()))
+            path0.append(int(feed[0, 0])); row0.append(lp[0])
             feed = ll.argmax(axis=1).astype(np.int32)[:, None]
             n_past = [x + 1 for x in n_past]
         assert sp.counter("persist_launches") == launches0 + 6 and sl.counter("persist_launches") == 0
@@ -63,9 +65,13 @@ def test_single_token_steps_match_the_launch_path_and_the_oracle(E, oracle, tmp_
             n2 = [n_past[0], 3, n_past[2]]
             lp, ll = sp.decode(feed, n2), sl.decode(feed, n2)
             assert np.abs(lp - ll).max() < tol
-            # and the oracle on row 0's own token path
+            # and the oracle on row 0's own token path: the persistent step's logits at every position it produced
             mel = om.log_mel(pcm[0], 1)
             s = oracle.State(om); s.set_encoder_output(om.encode(mel))
+            ref = s.decode(path0, 0, all_pos=True)
+            worst_o = max(float(np.abs(row0[i] - ref[3 + i]).max()) for i in range(6))
+            print(f"{preset} dtype {dt} rows {rows}: worst |persistent - oracle| on row 0 = {worst_o:.4f} (tolerance {tol})")
+            assert worst_o < tol, (preset, worst_o)
         print(f"{preset} dtype {dt} rows {rows}: worst |persistent - launches| = {worst:.4f}")
         sp.close(); sl.close()
 
@@ -102,6 +108,7 @@ def test_a_row_does_not_depend_on_its_batch_and_runs_are_repeatable(E, tmp_model
     res = {}
     for rows in ((0, 1, 2, 3, 4), (2,), (4, 2)):
         st = E.State(ctx, len(rows))
+        st.set_persistent(True)
         st.mel(pcm[list(rows)], None, E.OHW_MEL_ZERO_TAIL, want=False); st.encode(len(rows))
         l0 = st.decode(np.tile(prompt, (len(rows), 1)), [0] * len(rows))
         feed = np.full((len(rows), 1), 1000, np.int32)
@@ -109,6 +116,7 @@ def test_a_row_does_not_depend_on_its_batch_and_runs_are_repeatable(E, tmp_model
         l1b = st.decode(feed, [3] * len(rows))                          # the same step again: identical bits
         assert np.array_equal(l1, l1b)
         l2 = st.decode(feed, [4] * len(rows))
+        assert st.counter("persist_launches") == 3                      # the three single-token steps took the persistent path
         res[rows] = {r: (l1[i], l2[i]) for i, r in enumerate(rows)}
         st.close()
     for other in ((2,), (4, 2)):
