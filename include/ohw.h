@@ -926,6 +926,100 @@ int ohw_pool_last_segments(struct ohw_pool* p, const ohw_span_time** s, int* n);
 int ohw_word_starts_host(const char* bytes, const int32_t* lens, int n, int32_t* starts_out);
 int ohw_segments_host(const int32_t* tokens, int n, const ohw_special_tokens* tok, float t_off, float t_end, ohw_token_span* out, int cap);
 
+/* ---- confidence: how sure the UNCONSTRAINED model was of each token of a transcript (openai-whisper's word `probability`,
+ *      whisper.cpp's per-token `p`), on the device, for windows whose cross K/V is still resident.
+ * Why not the decode's own token_logprobs: those are taken behind the logit bias, the hot-phrase boost, the repetition rule, the
+ *   command list and the temperature - under a hard command list every kept token has a decode log-probability near 0 whatever
+ *   the audio was.  A confidence is a teacher-forced pass over the kept tokens with a soft-max over the RAW logits.
+ * The sequence: for window b with n text tokens t_0 .. t_{n-1} (ids 0 .. eot - 1, timestamps already removed) it is
+ *   ohw_state_align's: [sot, (lang, task), no_timestamps, t_0 .. t_{n-1}].  P = the prompt length (4 multilingual, 2 not); there
+ *   is no previous-text context.  Position P - 1 + i predicts t_i for i < n, position P - 1 + n predicts end-of-text.
+ * The score of a row: x = that position's raw fp32 logits (no logit bias, no rule, no temperature, no filter):
+ *     logit     = x[target]                     target = t_i, or eot for row n
+ *     lse_text  = log sum_{j < eot}     exp(x[j])
+ *     lse_all   = log sum_{j < n_vocab} exp(x[j])
+ *     top_id    = the first j < eot with x[j] == max_{j < eot} x[j];   top_logit = x[top_id]
+ *   logit, top_id and top_logit are selections: the very 32-bit words the logits buffer holds.  The two lse values are fp32
+ *   reductions whose shape is a function of n_vocab and eot only (score.hip states the order): a row's five words never depend on
+ *   the batch, the row's place in it or the CU budget.  ohw_token_score_host is the rule on one row, no device needed.
+ *   ohw_token_prob_host (any output may be NULL): openai's text-token log-probability logit - lse_text, the full-vocabulary
+ *   log-probability logit - lse_all (summed over rows 0 .. n: the sequence log-likelihood, for rescoring), top_logit - lse_text.
+ * Word probability: words are cut by ohw_word_starts_host on the window's text tokens; a word's probability is the arithmetic
+ *   mean of exp(logit - lse_text) of its tokens (openai-whisper's timing.py), accumulated in double and rounded once to float.
+ *   ohw_word_probs_host is the rule: logprob_text [n] and starts [n] of ONE window (token 0 opens a word whatever starts[0]
+ *   says) -> probs_out, one per word, at most n; returns the number of words, or an error code (< 0).
+ * ohw_state_score: for the windows of the last encode (batch = its batch), the arguments of ohw_state_align.  tokens
+ *   [batch][stride], n_tokens[b] = 0 skips the window (its rows of the outputs are left alone).  scores_out [batch][stride + 1]:
+ *   entry i < n_tokens[b] scores t_i, entry n_tokens[b] scores end-of-text.  The caller may score any text, not only what a decode
+ *   kept: external hypotheses, an expected utterance, corrected text.
+ *   start_idx_out == NULL: score only - no alignment heads are needed, no tap runs, n_frames is not read (may be NULL).
+ *   start_idx_out != NULL: the alignment of ohw_state_align too, from the SAME replay (one run_decoder_step per chunk serves the
+ *   tap and the score): start_idx_out and the "align_*" fetches are those of ohw_state_align on the same arguments, bit for bit.
+ *   After each chunk's step token_score_kernel reads the chunk's logits, which the logits GEMM stores for all 8 rows per window.
+ *   That buffer, f32 [max_batch * 8][ld] (159 MB at 96 windows and 51 866 columns), is made by the first scoring call and
+ *   released by ohw_state_set_score_buffers(st, 0).  on = 1 makes it ahead of time; on = 2 also keeps, from then on, the rows
+ *   of every call's LAST window for the "score_logits" fetch below (f32 [n_text_ctx / 2 + 16][ld], one device copy per chunk).
+ *   It honours ohw_state_set_audio_ctx, ohw_state_set_window_ctx, the packed encoder, the language table and
+ *   ohw_state_set_batch_invariant.  Refused with OHW_E_INVALID_ARG before any launch: a null argument; batch other than the last
+ *   encode's; a token id < 0 or >= eot (window and position named); n_tokens[b] < 0, > stride or > n_text_ctx / 2 (window named);
+ *   with start_idx_out: no head list, n_frames NULL or n_frames[b] < 0; a call under another audio context or other per-window
+ *   contexts than the last encode; a language table with a pending entry (window named).
+ *   Side effects: ohw_state_align's - AFTER THE CALL THE STATE'S SELF K/V IS STALE (every decode entry starts at position 0 and
+ *   rewrites it), the logits rows of the windows hold the last chunk's last position, the tallies count the steps.
+ * ohw_state_fetch gains "score_logits" (under ohw_state_set_score_buffers(st, 2); batch = the last ohw_state_score's): the
+ *   all-rows logits [n_chunks * 8][n_vocab] of window batch - 1 of that call, n_chunks = ceil((P + max n_tokens + 1) / 8); row r =
+ *   position r of the sequence, rows behind the window's own positions are those of the eot padding. */
+typedef struct { float logit, lse_text, lse_all; int32_t top_id; float top_logit; } ohw_token_score;
+int ohw_state_score(ohw_state* st, const ohw_sample_params* p, const int32_t* tokens, int stride, const int32_t* n_tokens,
+                    int batch, ohw_token_score* scores_out /* [batch][stride + 1] */,
+                    const int32_t* n_frames /* NULL unless aligning */, int32_t* start_idx_out /* NULL: score only */);
+int ohw_state_set_score_buffers(ohw_state* st, int on);
+int ohw_token_score_host(const float* x, int n_vocab, int eot, int target, ohw_token_score* out);
+int ohw_token_prob_host(const ohw_token_score* s, float* logprob_text, float* logprob_all, float* top_logprob_text);
+int ohw_word_probs_host(const float* logprob_text, const int32_t* starts, int n, float* probs_out);
+/* ---- confidence in the engine.  ohw_engine_set_confidence(e, on): off (0) is the default and launches and allocates nothing;
+ *      turning it off frees the score buffers of every state of the engine.  When on, every schedule, the seek loop,
+ *      ohw_engine_transcribe_batch, _long_batch and _speech score the kept pass of each window on the state that decoded it, before
+ *      that state's next encode (ohw_state_score) - in the SAME replay as the alignment when word timestamps are on too, alone when
+ *      they are not.  Windows dropped by the no-speech rule or without a text token get none.  Tokens, text, times, quality records
+ *      and candidates do not change.  Results of the last ohw_engine_transcribe, valid until the next call:
+ *   token probs   one entry per kept text token (no alignment needed): its id, the index of its window, logprob_text
+ *                 (logit - lse_text, openai's), logprob_all (logit - lse_all), logprob_decode = the kept pass's OWN token_logprobs
+ *                 entry of that token (whisper.cpp's plog: taken behind every logit rule and the temperature; copied, not
+ *                 recomputed), the unconstrained model's best text token and its logprob_text;
+ *   word probs    one entry per word (ohw_word_starts_host on the window's text tokens; no alignment heads needed): the span of
+ *                 the word in the text and ohw_word_probs_host's probability.  With word timestamps on, entry i covers the span
+ *                 of ohw_engine_last_words entry i;
+ *   segment info  one entry per ohw_engine_last_segments entry: the mean of its text tokens' logprob_text (NaN for a segment
+ *                 whose window was not scored), its window's no_speech_prob and temperature.
+ *   ohw_engine_batch_confidence: the same three arrays for recording i of the last batch call (any pointer may be NULL).
+ *   ohw_pool_set_confidence: the setting on every engine of the pool; ohw_pool_transcribe gathers the three arrays in recording
+ *   order like the times: ohw_pool_last_token_probs / _last_word_probs / _last_segment_info.                              */
+typedef struct { int32_t id, window; float logprob_text, logprob_all, logprob_decode; int32_t top_id; float top_logprob_text; } ohw_token_prob;
+typedef struct { size_t text_off, text_len; float probability; } ohw_word_prob;
+typedef struct { float avg_logprob_text, no_speech_prob, temperature; } ohw_segment_info;
+int ohw_engine_set_confidence(struct ohw_engine* e, int on);
+int ohw_engine_last_token_probs(struct ohw_engine* e, const ohw_token_prob** t, int* n);
+int ohw_engine_last_word_probs(struct ohw_engine* e, const ohw_word_prob** w, int* n);
+int ohw_engine_last_segment_info(struct ohw_engine* e, const ohw_segment_info** s, int* n);
+int ohw_engine_batch_confidence(struct ohw_engine* e, int i, const ohw_token_prob** token_probs, int* n_token_probs,
+                                const ohw_word_prob** word_probs, int* n_word_probs, const ohw_segment_info** segment_info, int* n_segments);
+/* ohw_engine_score_batch: scores text the CALLER supplies - external hypotheses to rescore, an expected utterance to verify,
+ * corrected text - against n recordings of 16 kHz audio, each at most 30 s (one window) and at most n_text_ctx / 2 text tokens
+ * (ids 0 .. eot - 1; recording i's are tokens[offsets[i] .. offsets[i + 1]), offsets [n + 1]).  The recordings go through
+ * ohw_engine_transcribe_batch's front end (validation, longest first, max_batch at a time, audio_ctx "auto" if set, language
+ * detection if set) and each is then scored with ohw_state_score; the confidence setting need not be on.  results [n]: the
+ * ohw_token_prob list (window 0, logprob_decode NaN: nothing was decoded; the pointer is the engine's, valid until its next
+ * call), the end-of-text row, and the sum of logprob_all over the tokens and end-of-text - the sequence log-likelihood.  A
+ * recording with no token gets no scores (n_tokens 0, NaN).  N candidates for one recording: pass it N times (N encodes).
+ * Texts: ohw_tokenize first, with the caveat of command lists - it is not BPE merging; token ids are the exact form.
+ * (The entry itself is declared below, behind ohw_audio_span.)                                                            */
+typedef struct { const ohw_token_prob* tokens; int32_t n_tokens; ohw_token_prob eot; float sum_logprob_all; } ohw_score_result;
+int ohw_pool_set_confidence(struct ohw_pool* p, int on);
+int ohw_pool_last_token_probs(struct ohw_pool* p, const ohw_token_prob** t, int* n);
+int ohw_pool_last_word_probs(struct ohw_pool* p, const ohw_word_prob** w, int* n);
+int ohw_pool_last_segment_info(struct ohw_pool* p, const ohw_segment_info** s, int* n);
+
 /* per-stage device time of the last calls on this state, in milliseconds (reference logs the     */
 /* same split per job: src/queue/worker.rs:170-180)                                               */
 typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t decode_steps; } ohw_timings;
@@ -1123,6 +1217,8 @@ int ohw_engine_set_packed_encoder(ohw_engine* e, int on);
  * valid until the next ohw_engine_transcribe_batch; ohw_engine_last_* are empty after this call.                        */
 typedef struct { const float* samples; int64_t n; } ohw_audio_span;
 int ohw_engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, uint32_t sample_rate);
+int ohw_engine_score_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* tokens, const int32_t* offsets,
+                           ohw_score_result* results);     /* "confidence in the engine" above */
 /* result of recording i of the last ohw_engine_transcribe_batch; every out pointer may be NULL; language_out: >= 8 bytes */
 /* language detection in the engine (default 0: language "auto" stays "en", as in the reference).  It applies only when the
  * engine's language is "auto"; an explicit language is unaffected, and an English-only model stays "en" without a detection.
@@ -1427,6 +1523,9 @@ int ohw_dbg_lang_pick(ohw_state* st, const float* logits, int batch, int32_t* id
  *   "phrase_boost"                     launches of the hot-phrase kernel (ohw_state_set_phrase_table); 0 with no table
  *   "repeat_rule"                      launches of the repetition kernel (ohw_state_set_repeat_rule); 0 while the rule is off
  *   "command_rule"                     launches of the command-list kernel (ohw_state_set_command_table); 0 with no list
+ *   "dec_gemm.total" / "xattn.total"   the sum over every "dec_gemm.*" / "xattn.*" name above ("xattn.chunk" is not in it)
+ *   "token_score"                      launches of token_score_kernel (ohw_state_score): one per replay chunk
+ *   "score_buffers"                    1 while the state holds ohw_state_score's buffers, else 0
  * The persistent step (ohw_state_set_persistent) counts only its logits GEMM.                                    */
 int ohw_dbg_counter(const ohw_state* st, const char* name);
 
@@ -1596,6 +1695,22 @@ typedef struct {
   int32_t* shape_out;      /* HOST, or NULL */
 } ohw_dbg_dec_gemm_io;
 int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream);
+/* ohw_dbg_dec_gemm with epilogue LOGITS (anything else: OHW_E_INVALID_ARG) plus the all-rows output ohw_state_score's replay
+ * uses: out_all DEVICE f32 [M][ld_all], ld_all >= N - every row m < M, column n < N is stored at out_all[m * ld_all + n],
+ * nothing else; g.out is written as ever.  out_all == NULL: the launch ohw_dbg_dec_gemm makes (the work shape never depends on
+ * out_all). */
+typedef struct { ohw_dbg_dec_gemm_io g; float* out_all; int64_t ld_all; } ohw_dbg_logits_rows_io;
+int ohw_dbg_logits_rows(const ohw_dbg_logits_rows_io* io, void* stream);
+/* token_score_kernel once on caller data (tests/test_gpu_token_score.py), on the state's device and stream; the state's own
+ * buffers are not touched.  logits HOST f32 [batch * 8][ld] (ld % 4 == 0, ld >= n_vocab; the caller poisons the padding columns):
+ * staged on the device between two guard rows of NaN, which the kernel must never read into a result.  targets HOST [batch * 8]
+ * (0 .. n_vocab - 1), n_all HOST [batch], row0 >= 0, n_prompt >= 1, cap >= 1: TokenScoreParams of kernels.hpp, that is row
+ * m = b * 8 + j writes entry row0 + j - (n_prompt - 1) of window b iff n_prompt - 1 <= row0 + j < n_all[b] and the entry is
+ * below cap.  out HOST [guard + batch * cap + guard] entries: the device copy is filled with OHW_DBG_SENTINEL_F32 (top_id:
+ * OHW_DBG_SENTINEL_I32) first and copied back whole, the guards in front and behind included: what holds the sentinel afterwards
+ * was not written.  0 <= guard <= 4096, batch <= 4096, n_vocab <= 2^20. */
+int ohw_dbg_token_score(ohw_state* st, const float* logits, int batch, int64_t ld, int n_vocab, int eot, const int32_t* targets,
+                        const int32_t* n_all, int row0, int n_prompt, int cap, int guard, ohw_token_score* out);
 /* launch_embed on caller data: emb f32 [n_vocab][d] (device; rounded and tiled like a weight matrix, rows padded to a multiple
  * of 16), pos f32 [n_pos][d] (device), tok and n_past HOST tables [M] and [M / n_new]: 0 <= tok[m] < n_vocab,
  * 0 <= n_past[b] and n_past[b] + n_new <= n_pos; M % n_new == 0, d % 32 == 0.  x f32 [M][d] = emb[tok[m]] + pos[n_past[m / n_new]

@@ -257,10 +257,28 @@ def _add_transcribe_options(t):
     t.add_argument("--word-timestamps", action="store_true",
                    help="align every window's tokens on the device and add \"segments\" and \"words\" arrays (text, t0, t1 in seconds) to "
                         "the JSON; needs --align-heads")
+    t.add_argument("--confidence", action="store_true",
+                   help="score every window's kept tokens with the unconstrained model on the device (a teacher-forced pass, openai-"
+                        "whisper's word probability) and add to the JSON: \"probability\" on each word (a top-level \"word_probs\" "
+                        "without --word-timestamps), \"avg_logprob\" and \"no_speech_prob\" on segments, and \"tokens_conf\" per text token")
     _add_vad_options(t)
     t.add_argument("--align-heads", default="", metavar="L.H,L.H,...",
                    help="the (decoder layer, head) pairs whose cross-attention carries the alignment, at most 32; no preset ships "
                         "(INTEGRATION.md says where upstream lists them per checkpoint)")
+
+
+def _confidence_json(doc: dict, with_times: bool, segments, token_probs, word_probs, segment_info):
+    """--confidence: the fields the option adds to one recording's JSON document"""
+    if not with_times:
+        doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in segments]
+        doc["word_probs"] = [{"text": w["text"], "probability": w["probability"]} for w in word_probs]
+    else:
+        for w, p in zip(doc["words"], word_probs):
+            w["probability"] = p["probability"]
+    for s, info in zip(doc["segments"], segment_info):
+        s["avg_logprob"] = None if info["avg_logprob"] != info["avg_logprob"] else info["avg_logprob"]      # NaN: the window was not scored
+        s["no_speech_prob"] = info["no_speech_prob"]
+    doc["tokens_conf"] = token_probs
 
 
 def _add_vad_options(t):
@@ -483,6 +501,8 @@ def _transcribe_many(args) -> int:
         except E.WhisperError as ex:
             print(f"error: {ex}", file=sys.stderr)
             return 1
+    if args.confidence:
+        eng.set_confidence(True)
     t1 = time.perf_counter()
     try:
         if vad:
@@ -509,6 +529,8 @@ def _transcribe_many(args) -> int:
         if align_heads:
             doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in res.segments]
             doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in res.words]
+        if args.confidence:
+            _confidence_json(doc, bool(align_heads), res.segments, res.token_probs, res.word_probs, res.segment_info)
         print(json.dumps(doc))
     eng.close()
     return 0
@@ -558,6 +580,9 @@ def _transcribe_one(args) -> int:
         if hot:
             print("error: --hot-phrases is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
             return 1
+        if args.confidence:
+            print("error: --confidence is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
+            return 1
         return _transcribe_ranks(args, audio, commands)
     use_gpu = args.device.lower() != "cpu"                    # reference src/main.rs:1037
     dev = int(args.device.split(":")[1]) if ":" in args.device else 0
@@ -595,6 +620,8 @@ def _transcribe_one(args) -> int:
         except E.WhisperError as ex:
             print(f"error: {ex}", file=sys.stderr)
             return 1
+    if args.confidence:
+        eng.set_confidence(True)
     t1 = time.perf_counter()
     if vad:
         try:
@@ -619,6 +646,11 @@ def _transcribe_one(args) -> int:
         if align_heads:
             doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in (res.segments if vad else eng.last_segments())]
             doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in (res.words if vad else eng.last_words())]
+        if args.confidence:
+            if vad:
+                _confidence_json(doc, bool(align_heads), res.segments, res.token_probs, res.word_probs, res.segment_info)
+            else:
+                _confidence_json(doc, bool(align_heads), eng.last_segments(), eng.last_token_probs(), eng.last_word_probs(), eng.last_segment_info())
         print(json.dumps(doc, indent=2))
     else:
         print("\n--- Transcription ---")

@@ -200,7 +200,9 @@ __device__ __forceinline__ void dec_gemm_store16(const DecGemmParams& p, int m, 
   }
 }
 
-template <typename T, int EPI, bool LN, int NT, int MT>
+// ALLROWS (LOGITS only; DecGemmParams::out_all): an instantiation of its own, so that a launch without out_all runs the very
+// code it ran before the all-rows output existed
+template <typename T, int EPI, bool LN, int NT, int MT, bool ALLROWS = false>
 __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_kernel(DecGemmParams p) {
   // MT = m-tiles (16 rows) per workgroup.  MT = 1 (RESID GEMMs): the two row halves of a weight tile go to two
   // workgroups on the same XCD (the second reads the weights from L2), each pulling half the activation bytes - per-CU
@@ -575,6 +577,7 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_kernel(DecGemmParams p
       ((float*)p.out)[(int64_t)m * p.ld_out + n] = resid_old[t] + v;
     } else if constexpr (EPI == DEPI_LOGITS) {
       if (m % p.n_new == p.n_new - 1) ((float*)p.out)[(int64_t)(m / p.n_new) * p.ld_out + n] = v;
+      if constexpr (ALLROWS) p.out_all[(int64_t)m * p.ld_all + n] = v;      // every row too (ohw_state_score)
     }
   }
   if constexpr (EPI == DEPI_QKV && (NT == 1 || NT == 2 || NT == 4)) {
@@ -616,7 +619,12 @@ static int dec_gemm_launch(const DecGemmParams& p, hipStream_t s) {
   dim3 grid((n_tiles + NT - 1) / NT, (p.M + 16 * MT - 1) / (16 * MT), p.ksplit > 1 ? p.ksplit : 1);
   const size_t smem = (size_t)DG_WAVES * NT * 2 * 64 * 16 + (LN ? (size_t)16 * MT * (p.K * 2 + 16) : 256);
   if (LN) ensure_dynamic_lds((const void*)dec_gemm_kernel<T, EPI, LN, NT, MT>, 160 * 1024);
-  hipLaunchKernelGGL((dec_gemm_kernel<T, EPI, LN, NT, MT>), grid, dim3(DG_THREADS), smem, s, p);
+  if constexpr (EPI == DEPI_LOGITS && !LN) {
+    if (p.out_all) hipLaunchKernelGGL((dec_gemm_kernel<T, EPI, LN, NT, MT, true>), grid, dim3(DG_THREADS), smem, s, p);
+    else hipLaunchKernelGGL((dec_gemm_kernel<T, EPI, LN, NT, MT>), grid, dim3(DG_THREADS), smem, s, p);
+  } else {
+    hipLaunchKernelGGL((dec_gemm_kernel<T, EPI, LN, NT, MT>), grid, dim3(DG_THREADS), smem, s, p);
+  }
   return NT == 4 ? DG_SHAPE_4x2 : NT == 2 ? (MT == 1 ? DG_SHAPE_2x1 : DG_SHAPE_2x2) : (MT == 1 ? DG_SHAPE_1x1 : DG_SHAPE_1x2);
 }
 
@@ -648,7 +656,7 @@ __global__ __launch_bounds__(128) void dec_ln_rows_kernel(const float* __restric
 // order through one accumulator (blocks past K multiply a zero fragment, as there), the LDS reduction over the waves in wave
 // order from 0.f, bias, then the epilogue (dec_gemm_store16, or residual + v).  The bits of the output therefore do not
 // depend on which of the kernels ran.  No split-K, no statistics, no post-norm, no fused self-attention.
-template <typename T, int EPI, int NTW, int MTP, int PASSES, int G>
+template <typename T, int EPI, int NTW, int MTP, int PASSES, int G, bool ALLROWS = false>
 __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_rows_kernel(DecGemmParams p) {
   constexpr bool HOLD = EPI != DEPI_BIAS_RESID;
   static_assert(HOLD ? (EPI == DEPI_QKV || EPI == DEPI_BIAS_GELU_T || EPI == DEPI_LOGITS) : (NTW == 1 && PASSES == 1), "rows form");
@@ -805,6 +813,7 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dec_gemm_rows_kernel(DecGemmPar
       if (p.bias) v += p.bias[n];
       if constexpr (EPI == DEPI_LOGITS) {          // dec_gemm_kernel's row selection: the last row of each window, fp32
         if (m % p.n_new == p.n_new - 1) ((float*)p.out)[(int64_t)(m / p.n_new) * p.ld_out + n] = v;
+        if constexpr (ALLROWS) p.out_all[(int64_t)m * p.ld_all + n] = v;
       } else if constexpr (HOLD) {
         dec_gemm_store16<T, EPI>(p, m, n, v);
       } else {
@@ -819,9 +828,16 @@ template <typename T, int EPI, int NTW, int MTP, int PASSES, int G>
 static void dec_gemm_rows_launch(const DecGemmParams& p, hipStream_t s) {
   const int n_tiles = (p.N + 15) / 16, mt = (p.M + 15) / 16;
   const size_t smem = (size_t)DG_WAVES * NTW * MTP * 64 * 16;
+  const dim3 grid((n_tiles + NTW - 1) / NTW, (mt + MTP * PASSES - 1) / (MTP * PASSES));
+  if constexpr (EPI == DEPI_LOGITS) {
+    if (p.out_all) {
+      if (smem > 64 * 1024) ensure_dynamic_lds((const void*)dec_gemm_rows_kernel<T, EPI, NTW, MTP, PASSES, G, true>, 160 * 1024);
+      hipLaunchKernelGGL((dec_gemm_rows_kernel<T, EPI, NTW, MTP, PASSES, G, true>), grid, dim3(DG_THREADS), smem, s, p);
+      return;
+    }
+  }
   if (smem > 64 * 1024) ensure_dynamic_lds((const void*)dec_gemm_rows_kernel<T, EPI, NTW, MTP, PASSES, G>, 160 * 1024);
-  hipLaunchKernelGGL((dec_gemm_rows_kernel<T, EPI, NTW, MTP, PASSES, G>), dim3((n_tiles + NTW - 1) / NTW, (mt + MTP * PASSES - 1) / (MTP * PASSES)),
-                     dim3(DG_THREADS), smem, s, p);
+  hipLaunchKernelGGL((dec_gemm_rows_kernel<T, EPI, NTW, MTP, PASSES, G>), grid, dim3(DG_THREADS), smem, s, p);
 }
 
 // LN1 + QKV / LN2 + mlp.0 for many rows on few CUs: the LayerNorm once (dec_ln_rows_kernel into p.ln_rows), then the all-rows

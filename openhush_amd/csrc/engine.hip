@@ -292,6 +292,16 @@ struct ohw_state {
   int al_row0 = 0, al_lds = 0;
   std::vector<int32_t> al_nall, al_nk;
   int al_prompt = 0, al_batch = 0;
+  // confidence (ohw_state_score; score.hip), nothing until the first scoring call or ohw_state_set_score_buffers.  sc_logits: the
+  // all-rows logits of ONE replay chunk, f32 [max_batch * 8][logits_ld]; sc_tok / sc_tgt: the chunks' tokens and targets,
+  // [chunk][batch][8]; sc_cnt i32 [max_batch]: positions with a score; sc_out: ohw_token_score [max_batch][n_text_ctx / 2 + 1].
+  // sc_on is set only while ohw_state_score replays: run_decoder_step's logits GEMM then stores every row to sc_logits.
+  // sc_keep (ohw_state_set_score_buffers(st, 2)): the rows of the call's last window, every chunk, for the "score_logits" fetch;
+  // sc_batch / sc_chunks / sc_kept describe them
+  DevBuf sc_logits, sc_tok, sc_tgt, sc_cnt, sc_out, sc_keep;
+  bool sc_on = false, sc_keep_rows = false;
+  int sc_batch = 0, sc_chunks = 0;
+  int64_t tally_score = 0;           // token_score_kernel launches (ohw_dbg_counter "token_score")
   // timing
   hipEvent_t ev[6]{};
   ohw_timings last{};
@@ -752,6 +762,7 @@ void run_decoder_step(ohw_state* st, int B, int n_new, const int32_t* tok_src = 
     }
     p.M = M; p.N = N; p.K = K; p.n_new = n_new; p.ld_out = ld; p.n_past = n_past;
     p.d_model = d; p.n_head = H; p.n_ctx = C;
+    if (epi == DEPI_LOGITS && st->sc_on) { p.out_all = st->sc_logits.as<float>(); p.ld_all = st->logits_ld; }   // ohw_state_score's replay
     const int cls = epi == DEPI_BIAS_T ? OHW_PROF_DEC_GEMM_XQ : epi == DEPI_BIAS_GELU_T ? OHW_PROF_DEC_GEMM_FC1
                   : epi == DEPI_LOGITS ? OHW_PROF_DEC_GEMM_LOGITS : OHW_PROF_DEC_GEMM;
     // algorithmic bytes: the weights once per launch (the m-blocks of a prompt pass share them through L2)
@@ -1605,6 +1616,7 @@ int ohw_encode_slice(ohw_state* st, int batch, int first, int total) {
     HIP_CHECK(hipEventRecord(st->ev[3], st->stream));
     st->enc_batch = total;
     st->al_batch = 0;                  // the aligned windows are no longer resident: "align_*" fetches end here
+    st->sc_batch = 0;                  //   and so does "score_logits"
     st->enc_ctx = audio_ctx_of(st);
     st->enc_set = st->win_ctx;
     st->enc_var = var;
@@ -2110,6 +2122,14 @@ int ohw_dbg_counter(const ohw_state* st, const char* name) {
   if (n == "command_rule") return (int)std::min<int64_t>(st->rules.tally_command, INT32_MAX);
   if (n == "enc_rows") return (int)std::min<int64_t>(st->enc_rows, INT32_MAX);
   auto clamp = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
+  if (n == "token_score") return clamp(st->tally_score);
+  if (n == "score_buffers") return st->sc_logits.p ? 1 : 0;
+  if (n == "dec_gemm.total" || n == "xattn.total") {        // every launch of the family, whatever its variant
+    int64_t t = 0;
+    if (n[0] == 'd') for (int g = 0; g < DT_GEMMS; ++g) for (int f = 0; f < DT_FORMS; ++f) for (int k = 0; k < DG_N_SHAPES; ++k) t += st->tally_gemm[g][f][k];
+    else for (int v = 0; v < XA_N_VARIANTS; ++v) t += st->tally_xattn[v];
+    return clamp(t);
+  }
   for (int g = 0; g < DT_GEMMS; ++g)
     for (int f = 0; f < DT_FORMS; ++f)
       for (int k = 0; k < DG_N_SHAPES; ++k)
@@ -2890,30 +2910,55 @@ int ohw_state_set_align_heads(ohw_state* st, const ohw_align_head* heads, int n)
   });
 }
 
-int ohw_state_align(ohw_state* st, const ohw_sample_params* sp, const int32_t* tokens, int stride, const int32_t* n_tokens, const int32_t* n_frames,
-                    int batch, int32_t* start_idx_out) {
-  return guard([&] {
-    if (!st || !sp || !tokens || !n_tokens || !n_frames || !start_idx_out) throw Error(OHW_E_INVALID_ARG, "align: null argument");
-    if (st->al_heads.empty()) throw Error(OHW_E_INVALID_ARG, "align: no alignment heads are set (ohw_state_set_align_heads)");
-    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, "align: batch must equal the batch of the last ohw_encode");
-    check_decode_ctx(st, "align");
+// the buffers of ohw_state_score; rows: 0 frees them, 1 makes them, 2 also the kept rows of "score_logits"
+static void score_buffers(ohw_state* st, int mode) {
+  if (mode == 0) {
+    for (DevBuf* b : {&st->sc_logits, &st->sc_tok, &st->sc_tgt, &st->sc_cnt, &st->sc_out, &st->sc_keep}) b->release();
+    st->sc_keep_rows = false;
+    st->sc_batch = 0;
+    return;
+  }
+  const size_t B = (size_t)st->max_batch, half = (size_t)st->ctx->hp.n_text_ctx / 2, chunks = (half + 8) / 8 + 1;
+  if (!st->sc_logits.p) {
+    st->sc_logits.alloc(B * 8 * (size_t)st->logits_ld * 4);
+    st->sc_tok.alloc(chunks * B * 8 * 4);
+    st->sc_tgt.alloc(chunks * B * 8 * 4);
+    st->sc_cnt.alloc(B * 4, true);
+    st->sc_out.alloc(B * (half + 1) * sizeof(ohw_token_score));
+  }
+  if (mode == 2 && !st->sc_keep.p) st->sc_keep.alloc(chunks * 8 * (size_t)st->logits_ld * 4);
+  if (mode == 2) st->sc_keep_rows = true;
+}
+
+// The teacher-forced replay ohw_state_align and ohw_state_score share: the windows' sequences through the decoder in chunks of 8
+// positions on the resident cross K/V.  start_idx_out: the tap runs behind the listed heads' cross-query GEMMs and the reduction
+// and the DTW follow; scores_out: the logits GEMM keeps every row of a chunk and token_score_kernel reduces them behind each
+// step.  what: "align" or "score", the name the refusals carry
+static void replay_tokens(ohw_state* st, const ohw_sample_params* sp, const int32_t* tokens, int stride, const int32_t* n_tokens, const int32_t* n_frames,
+                          int batch, int32_t* start_idx_out, ohw_token_score* scores_out, const std::string& what) {
+  {
+    const bool do_align = start_idx_out != nullptr, do_score = scores_out != nullptr;
+    if (!st || !sp || !tokens || !n_tokens || (do_align && !n_frames) || (!do_align && !do_score)) throw Error(OHW_E_INVALID_ARG, what + ": null argument");
+    if (do_align && st->al_heads.empty()) throw Error(OHW_E_INVALID_ARG, what + ": no alignment heads are set (ohw_state_set_align_heads)");
+    if (batch < 1 || batch != st->enc_batch) throw Error(OHW_E_INVALID_ARG, what + ": batch must equal the batch of the last ohw_encode");
+    check_decode_ctx(st, what.c_str());
     const ohw_ctx* c = st->ctx;
     const ohw_hparams& hp = c->hp;
     const bool multilingual = hp.n_vocab >= 51865, lang_tab = !st->lang_kind.empty();
-    if (lang_tab) check_window_lang(st, batch, "align");
-    else if (multilingual && (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs)) throw Error(OHW_E_INVALID_ARG, "align: lang_id out of range");
+    if (lang_tab) check_window_lang(st, batch, what);
+    else if (multilingual && (sp->lang_id < 0 || sp->lang_id >= c->tok.n_langs)) throw Error(OHW_E_INVALID_ARG, what + ": lang_id out of range");
     const int half = hp.n_text_ctx / 2, eot = c->tok.eot;
-    if (stride < 0) throw Error(OHW_E_INVALID_ARG, "align: stride < 0");
+    if (stride < 0) throw Error(OHW_E_INVALID_ARG, what + ": stride < 0");
     for (int b = 0; b < batch; ++b) {
       const int nt = n_tokens[b];
       if (nt < 0 || nt > stride || nt > half)
-        throw Error(OHW_E_INVALID_ARG, "align: window " + std::to_string(b) + " has n_tokens " + std::to_string(nt) + ", outside 0 .. min(stride " +
+        throw Error(OHW_E_INVALID_ARG, what + ": window " + std::to_string(b) + " has n_tokens " + std::to_string(nt) + ", outside 0 .. min(stride " +
                                            std::to_string(stride) + ", n_text_ctx / 2 = " + std::to_string(half) + ")");
-      if (n_frames[b] < 0) throw Error(OHW_E_INVALID_ARG, "align: window " + std::to_string(b) + " has n_frames < 0");
+      if (do_align && n_frames[b] < 0) throw Error(OHW_E_INVALID_ARG, what + ": window " + std::to_string(b) + " has n_frames < 0");
       for (int k = 0; k < nt; ++k) {
         const int32_t id = tokens[(size_t)b * stride + k];
         if (id < 0 || id >= eot)
-          throw Error(OHW_E_INVALID_ARG, "align: window " + std::to_string(b) + ", token " + std::to_string(k) + ": id " + std::to_string(id) +
+          throw Error(OHW_E_INVALID_ARG, what + ": window " + std::to_string(b) + ", token " + std::to_string(k) + ": id " + std::to_string(id) +
                                              " is not a text token (0 .. " + std::to_string(eot - 1) + ")");
       }
     }
@@ -2932,7 +2977,7 @@ int ohw_state_align(ohw_state* st, const ohw_sample_params* sp, const int32_t* t
     for (int b = 0; b < batch; ++b) {
       const int nt = n_tokens[b];
       const int ctx_b = st->enc_var ? st->enc_win[(size_t)b] : Tn;
-      const int nk = std::max(1, std::min(ctx_b, n_frames[b] / 2));
+      const int nk = std::max(1, std::min(ctx_b, do_align ? n_frames[b] / 2 : ctx_b));
       cnt[(size_t)b] = nt > 0 ? P + nt + 1 : 0;
       cnt[(size_t)MB + b] = nk;
       cnt[(size_t)2 * MB + b] = nt > 0 ? nt + 1 : 0;
@@ -2940,14 +2985,27 @@ int ohw_state_align(ohw_state* st, const ohw_sample_params* sp, const int32_t* t
       if (nt > 0) max_nk = std::max(max_nk, nk);
     }
     const int chunks = (max_all + 7) / 8;
-    if (chunks * 8 > hp.n_text_ctx || chunks * 8 > st->al_rows + 7 || (size_t)chunks * batch * 8 * 4 > st->al_tok.bytes)
-      throw Error(OHW_E_INVALID_ARG, "align: the sequence does not fit n_text_ctx");
+    if (chunks * 8 > hp.n_text_ctx || (do_align && (chunks * 8 > st->al_rows + 7 || (size_t)chunks * batch * 8 * 4 > st->al_tok.bytes)) ||
+        (do_score && chunks > (half + 8) / 8 + 1))
+      throw Error(OHW_E_INVALID_ARG, what + ": the sequence does not fit n_text_ctx");
     // nothing below refuses: from here on the "align_*" fetches describe this call (a failed launch ends their validity)
-    st->al_batch = 0;
-    st->al_nall.assign(cnt.begin(), cnt.begin() + batch);
-    st->al_nk.assign(cnt.begin() + MB, cnt.begin() + MB + batch);
-    st->al_prompt = P;
-    if (max_all == 0) { st->al_batch = batch; return; }     // every window skipped
+    if (do_align) {
+      st->al_batch = 0;
+      st->al_nall.assign(cnt.begin(), cnt.begin() + batch);
+      st->al_nk.assign(cnt.begin() + MB, cnt.begin() + MB + batch);
+      st->al_prompt = P;
+    }
+    if (do_score) {
+      st->sc_batch = 0;
+      score_buffers(st, st->sc_keep_rows ? 2 : 1);
+    }
+    if (max_all == 0) {     // every window skipped
+      if (do_align) st->al_batch = batch;
+      return;
+    }
+    // the score's own tables: positions with a score (the end-of-text INPUT position of the alignment has none), and per
+    // row the token its position predicts
+    std::vector<int32_t> sc_cnt((size_t)(do_score ? batch : 0)), tgt((size_t)(do_score ? chunks * batch * 8 : 0), eot);
     std::vector<int32_t> toks((size_t)chunks * batch * 8, eot), npast((size_t)chunks * batch);
     for (int b = 0; b < batch; ++b) {
       const int nt = n_tokens[b];
@@ -2958,29 +3016,60 @@ int ohw_state_align(ohw_state* st, const ohw_sample_params* sp, const int32_t* t
       seq.push_back(c->tok.no_timestamps);
       seq.insert(seq.end(), tokens + (size_t)b * stride, tokens + (size_t)b * stride + nt);
       for (size_t i = 0; i < seq.size(); ++i) toks[((i / 8) * batch + b) * 8 + i % 8] = seq[i];       // the tail stays eot
+      if (do_score) {
+        sc_cnt[(size_t)b] = P + nt;
+        for (size_t i = 0; i + 1 < seq.size(); ++i) tgt[((i / 8) * batch + b) * 8 + i % 8] = seq[i + 1];   // the last position's stays eot
+      }
     }
     for (int ch = 0; ch < chunks; ++ch)
       for (int b = 0; b < batch; ++b) npast[(size_t)ch * batch + b] = ch * 8;
-    HIP_CHECK(hipMemcpyAsync(st->al_tok.p, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(st->al_cnt.p, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, s));
+    DevBuf& tok_buf = do_score ? st->sc_tok : st->al_tok;
+    HIP_CHECK(hipMemcpyAsync(tok_buf.p, toks.data(), toks.size() * 4, hipMemcpyHostToDevice, s));
+    if (do_align) HIP_CHECK(hipMemcpyAsync(st->al_cnt.p, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, s));
+    if (do_score) {
+      HIP_CHECK(hipMemcpyAsync(st->sc_tgt.p, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(st->sc_cnt.p, sc_cnt.data(), sc_cnt.size() * 4, hipMemcpyHostToDevice, s));
+    }
     {
       // the replay: launch-per-kernel steps only, every window's cross-attention runs, nothing is captured
       struct Replay {
         ohw_state* st; bool persist, fuse, skip;
-        explicit Replay(ohw_state* s_) : st(s_), persist(s_->persist), fuse(s_->fuse_attn), skip(s_->skip_done) {
-          st->persist = false; st->fuse_attn = false; st->skip_done = false; st->al_tap = true;
+        Replay(ohw_state* s_, bool tap, bool score) : st(s_), persist(s_->persist), fuse(s_->fuse_attn), skip(s_->skip_done) {
+          st->persist = false; st->fuse_attn = false; st->skip_done = false; st->al_tap = tap; st->sc_on = score;
         }
-        ~Replay() { st->persist = persist; st->fuse_attn = fuse; st->skip_done = skip; st->al_tap = false; }
-      } replay(st);
+        ~Replay() { st->persist = persist; st->fuse_attn = fuse; st->skip_done = skip; st->al_tap = false; st->sc_on = false; }
+      } replay(st, do_align, do_score);
       st->al_lds = max_nk;
+      TokenScoreParams tp{};
+      tp.logits = st->sc_logits.as<float>(); tp.ld = st->logits_ld; tp.n_all = st->sc_cnt.as<int32_t>(); tp.n_prompt = P;
+      tp.n_vocab = hp.n_vocab; tp.eot = eot; tp.batch = batch; tp.cap = half + 1; tp.out = st->sc_out.as<ohw_token_score>();
       Dispatch::run(c->dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         for (int ch = 0; ch < chunks; ++ch) {
           HIP_CHECK(hipMemcpyAsync(st->n_past.p, &npast[(size_t)ch * batch], (size_t)batch * 4, hipMemcpyHostToDevice, s));
           st->al_row0 = ch * 8;
-          run_decoder_step<T>(st, batch, 8, st->al_tok.as<int32_t>() + (size_t)ch * batch * 8);
+          run_decoder_step<T>(st, batch, 8, tok_buf.as<int32_t>() + (size_t)ch * batch * 8);
+          if (!do_score) continue;
+          tp.row0 = ch * 8; tp.targets = st->sc_tgt.as<int32_t>() + (size_t)ch * batch * 8;
+          launch_token_score(tp, s);
+          ++st->tally_score;
+          if (st->sc_keep_rows)
+            HIP_CHECK(hipMemcpyAsync(st->sc_keep.as<float>() + (size_t)ch * 8 * st->logits_ld, st->sc_logits.as<float>() + (size_t)(batch - 1) * 8 * st->logits_ld,
+                                     (size_t)8 * st->logits_ld * 4, hipMemcpyDeviceToDevice, s));
         }
       });
+    }
+    std::vector<ohw_token_score> sc_host((size_t)(do_score ? batch * (half + 1) : 0));
+    if (do_score) HIP_CHECK(hipMemcpyAsync(sc_host.data(), st->sc_out.p, sc_host.size() * sizeof(ohw_token_score), hipMemcpyDeviceToHost, s));
+    auto scores_back = [&] {
+      for (int b = 0; do_score && b < batch; ++b)
+        if (n_tokens[b] > 0) std::memcpy(scores_out + (size_t)b * (stride + 1), &sc_host[(size_t)b * (half + 1)], (size_t)(n_tokens[b] + 1) * sizeof(ohw_token_score));
+      if (do_score) { st->sc_batch = batch; st->sc_chunks = chunks; }
+    };
+    if (!do_align) {
+      HIP_CHECK(hipStreamSynchronize(s));     // also keeps toks / tgt / npast alive until their copies have run
+      scores_back();
+      return;
     }
     const int A = (int)st->al_heads.size();
     const int64_t T = hp.n_audio_ctx;
@@ -3001,6 +3090,35 @@ int ohw_state_align(ohw_state* st, const ohw_sample_params* sp, const int32_t* t
     st->al_batch = batch;
     for (int b = 0; b < batch; ++b)
       if (n_tokens[b] > 0) std::memcpy(start_idx_out + (size_t)b * (stride + 1), &idx[(size_t)b * (half + 1)], (size_t)(n_tokens[b] + 1) * 4);
+    scores_back();
+  }
+}
+
+int ohw_state_align(ohw_state* st, const ohw_sample_params* sp, const int32_t* tokens, int stride, const int32_t* n_tokens, const int32_t* n_frames,
+                    int batch, int32_t* start_idx_out) {
+  return guard([&] {
+    if (!n_frames || !start_idx_out) throw Error(OHW_E_INVALID_ARG, "align: null argument");
+    replay_tokens(st, sp, tokens, stride, n_tokens, n_frames, batch, start_idx_out, nullptr, "align");
+  });
+}
+
+int ohw_state_score(ohw_state* st, const ohw_sample_params* sp, const int32_t* tokens, int stride, const int32_t* n_tokens, int batch,
+                    ohw_token_score* scores_out, const int32_t* n_frames, int32_t* start_idx_out) {
+  return guard([&] {
+    if (!scores_out) throw Error(OHW_E_INVALID_ARG, "score: null argument");
+    replay_tokens(st, sp, tokens, stride, n_tokens, n_frames, batch, start_idx_out, scores_out, "score");
+  });
+}
+
+int ohw_state_set_score_buffers(ohw_state* st, int on) {
+  return guard([&] {
+    if (!st) throw Error(OHW_E_INVALID_ARG, "state is null");
+    if (on < 0 || on > 2) throw Error(OHW_E_INVALID_ARG, "set_score_buffers: on must be 0 (free), 1 (make) or 2 (make, and keep the rows of \"score_logits\")");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    HIP_CHECK(hipStreamSynchronize(st->stream));
+    if (on != 2) st->sc_keep_rows = false;
+    if (on != 2) st->sc_keep.release();
+    score_buffers(st, on);
   });
 }
 
@@ -3097,6 +3215,16 @@ int ohw_state_fetch(ohw_state* st, const char* what, int batch, float* out, int6
     };
     if (w == "mel") { from_f32(st->logmel.p, (int64_t)batch * hp.n_mels * CHUNK_FRAMES); return; }
     if (w == "mel_t") { from_t(st->mel_t.p, (int64_t)batch * MEL_ROWS * MEL_CPAD); return; }   // the image conv1 reads, pad rows and channels included
+    if (w == "score_logits") {
+      // window batch - 1 of the last ohw_state_score: the call's last window, whose rows ohw_state_set_score_buffers(st, 2) keeps
+      if (!st->sc_keep_rows || !st->sc_keep.p || st->sc_batch < 1 || batch != st->sc_batch)
+        throw Error(OHW_E_INVALID_ARG, "fetch: score_logits holds window batch - 1 of the last ohw_state_score, under ohw_state_set_score_buffers(st, 2)");
+      const int64_t rows = (int64_t)st->sc_chunks * 8;
+      need(rows * hp.n_vocab);
+      HIP_CHECK(hipMemcpy2DAsync(out, (size_t)hp.n_vocab * 4, st->sc_keep.p, (size_t)st->logits_ld * 4, (size_t)hp.n_vocab * 4, (size_t)rows, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      return;
+    }
     if (w == "align_q" || w == "align_p" || w == "align_m") {
       // window batch - 1 of the last ohw_state_align
       const int b = batch - 1;
@@ -3454,8 +3582,10 @@ static_assert(OHW_DG_SHAPE_1x1 == DG_SHAPE_1x1 && OHW_DG_SHAPE_2x1 == DG_SHAPE_2
               OHW_DG_SHAPE_2x2 == DG_SHAPE_2x2 && OHW_DG_SHAPE_4x2 == DG_SHAPE_4x2 && OHW_DG_SHAPE_1x6 == DG_SHAPE_1x6 &&
               OHW_DG_SHAPE_4x6 == DG_SHAPE_4x6 && OHW_DG_SHAPE_5x6 == DG_SHAPE_5x6, "ohw.h names kernels.hpp's shapes");
 
-int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
-  return guard([&] {
+}  // extern "C"
+// ohw_dbg_dec_gemm and ohw_dbg_logits_rows: one launch_dec_gemm on caller data; out_all (LOGITS only) may be null
+static void dbg_dec_gemm_run(const ohw_dbg_dec_gemm_io* io, float* out_all, int64_t ld_all, void* stream) {
+  {
     if (!io) throw Error(OHW_E_INVALID_ARG, "dbg_dec_gemm: null io");
     const ohw_dbg_dec_gemm_io& a = *io;
     auto bad = [](const std::string& why) { throw Error(OHW_E_INVALID_ARG, "dbg_dec_gemm: " + why); };
@@ -3534,10 +3664,62 @@ int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
       if (a.ksplit > 1) { p.ksplit = a.ksplit; p.slab = a.slab; p.slab_bytes = (int32_t)a.slab_bytes; p.ticket = a.ticket; }
       if (pn) { p.pn = 1; p.n_stat = a.K / 16; p.stat_in = a.stat_in; p.wsum = ws.as<float>(); }
       if (a.stat_out) { p.x16_out = a.x16_out; p.stat_out = a.stat_out; }
+      if (a.epilogue == DEPI_LOGITS && out_all) { p.out_all = out_all; p.ld_all = ld_all; }
       shape = launch_dec_gemm<TT>(p, a.epilogue, s);
     });
     HIP_CHECK(hipStreamSynchronize(s));
     if (a.shape_out) *a.shape_out = shape;
+  }
+}
+extern "C" {
+int ohw_dbg_dec_gemm(const ohw_dbg_dec_gemm_io* io, void* stream) {
+  return guard([&] { dbg_dec_gemm_run(io, nullptr, 0, stream); });
+}
+
+int ohw_dbg_logits_rows(const ohw_dbg_logits_rows_io* io, void* stream) {
+  return guard([&] {
+    if (!io) throw Error(OHW_E_INVALID_ARG, "dbg_logits_rows: null io");
+    if (io->g.epilogue != DEPI_LOGITS) throw Error(OHW_E_INVALID_ARG, "dbg_logits_rows: the epilogue must be LOGITS");
+    if (io->out_all && io->ld_all < io->g.N)
+      throw Error(OHW_E_INVALID_ARG, "dbg_logits_rows: ld_all = " + std::to_string(io->ld_all) + " is below N = " + std::to_string(io->g.N));
+    dbg_dec_gemm_run(&io->g, io->out_all, io->ld_all, stream);
+  });
+}
+
+int ohw_dbg_token_score(ohw_state* st, const float* logits, int batch, int64_t ld, int n_vocab, int eot, const int32_t* targets,
+                        const int32_t* n_all, int row0, int n_prompt, int cap, int guard_n, ohw_token_score* out) {
+  return guard([&] {
+    if (!st || !logits || !targets || !n_all || !out) throw Error(OHW_E_INVALID_ARG, "dbg_token_score: null argument");
+    if (batch < 1 || batch > 4096 || n_vocab < 1 || n_vocab > (1 << 20) || ld < n_vocab || ld > (1 << 21) || ld % 4 != 0 || eot < 0 || row0 < 0 ||
+        row0 > (1 << 20) || n_prompt < 1 || n_prompt > (1 << 20) || cap < 1 || cap > (1 << 16) || guard_n < 0 || guard_n > 4096)
+      throw Error(OHW_E_INVALID_ARG, "dbg_token_score: bad shape");
+    const int rows = batch * 8;
+    for (int m = 0; m < rows; ++m)
+      if (targets[m] < 0 || targets[m] >= n_vocab) throw Error(OHW_E_INVALID_ARG, "dbg_token_score: row " + std::to_string(m) + " has a target outside 0 .. n_vocab - 1");
+    HIP_CHECK(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->stream;
+    HIP_CHECK(hipStreamSynchronize(s));
+    const size_t n_out = (size_t)batch * cap + 2 * (size_t)guard_n;
+    DevBuf d_logits, d_tgt, d_cnt, d_out;
+    d_logits.alloc(((size_t)rows + 2) * ld * 4);
+    d_tgt.alloc((size_t)rows * 4); d_cnt.alloc((size_t)batch * 4); d_out.alloc(n_out * sizeof(ohw_token_score));
+    const std::vector<float> nan_row((size_t)ld, std::numeric_limits<float>::quiet_NaN());
+    ohw_token_score sent;
+    sent.logit = sent.lse_text = sent.lse_all = sent.top_logit = OHW_DBG_SENTINEL_F32; sent.top_id = OHW_DBG_SENTINEL_I32;
+    const std::vector<ohw_token_score> sent_out(n_out, sent);
+    HIP_CHECK(hipMemcpyAsync(d_logits.p, nan_row.data(), (size_t)ld * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_logits.as<float>() + ld, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_logits.as<float>() + ((size_t)rows + 1) * ld, nan_row.data(), (size_t)ld * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_tgt.p, targets, (size_t)rows * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_cnt.p, n_all, (size_t)batch * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_out.p, sent_out.data(), n_out * sizeof(ohw_token_score), hipMemcpyHostToDevice, s));
+    TokenScoreParams tp{};
+    tp.logits = d_logits.as<float>() + ld; tp.ld = ld; tp.targets = d_tgt.as<int32_t>(); tp.n_all = d_cnt.as<int32_t>();
+    tp.row0 = row0; tp.n_prompt = n_prompt; tp.n_vocab = n_vocab; tp.eot = eot; tp.batch = batch; tp.cap = cap;
+    tp.out = d_out.as<ohw_token_score>() + guard_n;
+    launch_token_score(tp, s);
+    HIP_CHECK(hipMemcpyAsync(out, d_out.p, n_out * sizeof(ohw_token_score), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
   });
 }
 

@@ -92,13 +92,16 @@ ohw_engine* engine_wrap_ctx(ohw_ctx* ctx, const std::string& language, bool tran
   return e.release();
 }
 
-void trim_spans(std::vector<ohw_span_time>& v, size_t lead, size_t new_len) {
-  for (ohw_span_time& s : v) {
+template <typename S>
+static void trim_spans_of(std::vector<S>& v, size_t lead, size_t new_len) {
+  for (S& s : v) {
     size_t o0 = std::max(s.text_off, lead) - lead, o1 = std::max(s.text_off + s.text_len, lead) - lead;
     o0 = std::min(o0, new_len); o1 = std::min(o1, new_len);
     s.text_off = o0; s.text_len = o1 - o0;
   }
 }
+void trim_spans(std::vector<ohw_span_time>& v, size_t lead, size_t new_len) { trim_spans_of(v, lead, new_len); }
+void trim_spans(std::vector<ohw_word_prob>& v, size_t lead, size_t new_len) { trim_spans_of(v, lead, new_len); }
 
 void validate_or_throw(const float* samples, int64_t n, uint32_t sample_rate, ohw_audio_info* info_out, int rec) {
   static const char* const names[] = {"ok", "Audio is empty (no samples)", "Unexpected sample rate", "Audio too long", "Audio too short",
@@ -514,6 +517,48 @@ int ohw_engine_batch_times(ohw_engine* e, int i, const ohw_token_time** token_ti
   });
 }
 
+int ohw_engine_set_confidence(ohw_engine* e, int on) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    e->confidence = on != 0;
+    // off: every state of the engine that may have scored gives its buffers back; on: a state allocates when it first scores
+    if (!e->confidence) {
+      (void)ohw_state_set_score_buffers(e->state, 0);
+      for (ohw_state* st : e->states) if (st != e->state) (void)ohw_state_set_score_buffers(st, 0);
+      for (ohw_state* st : e->lane_states) (void)ohw_state_set_score_buffers(st, 0);
+    }
+  });
+}
+int ohw_engine_last_token_probs(ohw_engine* e, const ohw_token_prob** t, int* n) {
+  if (!e || !t || !n) return OHW_E_INVALID_ARG;
+  *t = e->last.token_probs.data(); *n = (int)e->last.token_probs.size();
+  return OHW_OK;
+}
+int ohw_engine_last_word_probs(ohw_engine* e, const ohw_word_prob** w, int* n) {
+  if (!e || !w || !n) return OHW_E_INVALID_ARG;
+  *w = e->last.word_probs.data(); *n = (int)e->last.word_probs.size();
+  return OHW_OK;
+}
+int ohw_engine_last_segment_info(ohw_engine* e, const ohw_segment_info** s, int* n) {
+  if (!e || !s || !n) return OHW_E_INVALID_ARG;
+  *s = e->last.segment_info.data(); *n = (int)e->last.segment_info.size();
+  return OHW_OK;
+}
+int ohw_engine_batch_confidence(ohw_engine* e, int i, const ohw_token_prob** token_probs, int* n_token_probs, const ohw_word_prob** word_probs,
+                                int* n_word_probs, const ohw_segment_info** segment_info, int* n_segments) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    if (i < 0 || i >= (int)e->batch_records.size()) throw Error(OHW_E_INVALID_ARG, "batch_confidence: no recording " + std::to_string(i) + " in the last batch call");
+    const Transcript& t = e->batch_records[(size_t)i].t;
+    if (token_probs) *token_probs = t.token_probs.data();
+    if (word_probs) *word_probs = t.word_probs.data();
+    if (segment_info) *segment_info = t.segment_info.data();
+    if (n_token_probs) *n_token_probs = (int)t.token_probs.size();
+    if (n_word_probs) *n_word_probs = (int)t.word_probs.size();
+    if (n_segments) *n_segments = (int)t.segment_info.size();
+  });
+}
+
 int ohw_word_starts_host(const char* bytes, const int32_t* lens, int n, int32_t* starts_out) {
   return guard([&] {
     if (n < 0 || (n > 0 && (!bytes || !lens || !starts_out))) throw Error(OHW_E_INVALID_ARG, "word_starts: bad argument");
@@ -579,6 +624,15 @@ int ohw_engine_transcribe_batch_lang(ohw_engine* e, const ohw_audio_span* recs, 
     e->batch_records.clear();
     for (int i = 0; i < n_recs; ++i) validate_or_throw(recs[i].samples, recs[i].n, sample_rate, nullptr, i);
     engine_transcribe_batch(e, recs, n_recs, lang_ids);
+  });
+}
+
+int ohw_engine_score_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* tokens, const int32_t* offsets, ohw_score_result* results) {
+  return guard([&] {
+    if (!e || !recs || n_recs < 1 || !tokens || !offsets || !results) throw Error(OHW_E_INVALID_ARG, "score_batch: null argument or no recordings");
+    if (e->window_mode != OHW_WINDOW_FIXED) throw Error(OHW_E_INVALID_ARG, "score_batch: recordings are cut as OHW_WINDOW_FIXED cuts; set that window mode");
+    for (int i = 0; i < n_recs; ++i) validate_or_throw(recs[i].samples, recs[i].n, 16000, nullptr, i);
+    engine_score_batch(e, recs, n_recs, tokens, offsets, results);
   });
 }
 

@@ -11,10 +11,12 @@ namespace ohw {
 extern thread_local std::string g_last_error;
 // a text lost `lead` bytes at its front and now holds new_len bytes: move and cut the spans that index it
 void trim_spans(std::vector<ohw_span_time>& v, size_t lead, size_t new_len);
+void trim_spans(std::vector<ohw_word_prob>& v, size_t lead, size_t new_len);
 
 // one mark per window record: where the window's text starts in the UNTRIMMED text the spans index while a transcribe runs,
 // and how many token times / words / segments it added (the pool re-indexes with these)
-struct WindowMark { size_t text0 = 0; int32_t n_token_times = 0, n_words = 0, n_segments = 0; };
+// n_token_probs / n_word_probs: the confidence entries it added (segment info: one per segment when confidence is on)
+struct WindowMark { size_t text0 = 0; int32_t n_token_times = 0, n_words = 0, n_segments = 0, n_token_probs = 0, n_word_probs = 0; };
 
 // what a transcribe accumulates window by window (TranscribeCall::emit appends to one): of the engine's last call, of one
 // recording of a batch call, of the pool's gathered result
@@ -24,6 +26,9 @@ struct Transcript {
   std::vector<ohw_window_quality> quality;        // one record per window
   std::vector<ohw_token_time> token_times;
   std::vector<ohw_span_time> words, segments;     // index text
+  std::vector<ohw_token_prob> token_probs;        // confidence (ohw_engine_set_confidence): per kept text token of a scored window
+  std::vector<ohw_word_prob> word_probs;          //   per word (indexes text)
+  std::vector<ohw_segment_info> segment_info;     //   parallel to segments while confidence is on, else empty
   std::vector<WindowMark> marks;                  // one per window record
   std::vector<std::vector<int32_t>> contexts;     // per window record: what its T = 0 pass was decoded behind
   std::vector<ohw_command_hit> commands;          // per window record while a command list is set (ohw_engine_last_commands)
@@ -34,6 +39,7 @@ struct Transcript {
     text = b0 == std::string::npos ? std::string() : text.substr(b0, b1 - b0 + 1);
     trim_spans(words, b0 == std::string::npos ? 0 : b0, text.size());
     trim_spans(segments, b0 == std::string::npos ? 0 : b0, text.size());
+    trim_spans(word_probs, b0 == std::string::npos ? 0 : b0, text.size());
   }
 };
 }  // namespace ohw
@@ -94,12 +100,14 @@ struct ohw_engine {
     std::vector<ohw_speech_chunk> chunks;
   };
   std::vector<BatchRecord> batch_records;
+  std::vector<std::vector<ohw_token_prob>> score_records;   // ohw_engine_score_batch: what its results point into, until the next call
   // ohw_engine_set_vad: what ohw_engine_transcribe_speech detects, segments and chunks with
   ohw_vad_config vad_cfg{0, 0.5f, 700, 250, 30};
   ohw_vad_detector vad_det{0.10f, 9.0f, 3.0f};
   ohw_chunk_plan chunk_plan{30.0f, 2000, 1100};
   // word timestamps (ohw_engine_set_word_timestamps): the heads every state of the engine aligns with (empty: off)
   std::vector<ohw_align_head> wt_heads;
+  bool confidence = false;               // ohw_engine_set_confidence: every kept pass is scored by the unconstrained model (ohw_state_score)
   // language detection (ohw_engine_set_detect_language; only with language "auto" on a multilingual model).  given_lang: the pool
   // detected on its first engine and hands the id to this one (-1: detect yourself).  last_lang_id / last_lang_prob: what the
   // last transcribe decoded in and the detection's probability of it (1 when nothing was detected)
@@ -125,6 +133,9 @@ void engine_transcribe(ohw_engine* e, const float* samples, int64_t n, int64_t w
 // with; trim = false leaves each record's text untrimmed (the speech call joins chunks first)
 void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* langs, const double* t_offs = nullptr,
                              bool trim = true);
+// ohw_engine_score_batch after validation: engine_transcribe_batch's front end, then ohw_state_score on the caller's tokens
+// (recording i: tokens[offsets[i] .. offsets[i + 1])); fills results and e->score_records
+void engine_score_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* tokens, const int32_t* offsets, ohw_score_result* results);
 // speech-aware windows: detect (or take probs[i]), segment and chunk every validated recording, run all chunks as one
 // engine_transcribe_batch, gather per recording; fills e->batch_records
 void engine_transcribe_speech(ohw_engine* e, const ohw_audio_span* recs, const ohw_frame_probs* probs, int n_recs, const int32_t* langs);

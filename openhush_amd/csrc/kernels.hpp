@@ -75,7 +75,7 @@ enum DecEpilogue {
   DEPI_BIAS_T = 1,     // out T [M][N]
   DEPI_BIAS_GELU_T = 2, // out T in activation-tile order (it feeds mlp.2)
   DEPI_BIAS_RESID = 3, // x f32 [M][N] += v + bias
-  DEPI_LOGITS = 4      // logits f32 [batch][ld_logits], only rows m with (m % n_new) == n_new - 1
+  DEPI_LOGITS = 4      // logits f32 [batch][ld_logits], only rows m with (m % n_new) == n_new - 1 (and all rows to out_all, if set)
 };
 struct DecGemmParams {
   const void* x;       // T activation tiles [ceil(M/16)][K/32][64][8] (act_tiled_offset); with ln != 0: f32 [M][K] residual stream, (x - mean) * rstd fused into the prologue
@@ -114,6 +114,10 @@ struct DecGemmParams {
   // ln != 0, QKV and BIAS_GELU_T: scratch of the all-rows forms, T tiles [ceil(M/16)][K/32][64][8] - the LayerNorm of the rows,
   // written by a launch of its own in front of the GEMM (decode.hip, dec_ln_rows_kernel); null: those forms are not picked
   void* ln_rows;
+  // DEPI_LOGITS: besides out, every row m < M and column n < N also goes to out_all[m * ld_all + n] (ohw_state_score reads a
+  // chunk's 8 rows per window).  null: off - the launch is what it is without this field; the shape choice never looks at it
+  float* out_all;
+  int64_t ld_all;
 };
 // the launchers below return which instantiation they launched (the state tallies them: ohw_dbg_counter); the pick itself
 // does not depend on the tally
@@ -448,5 +452,21 @@ void launch_align_dtw(const AlignDtwParams& p, int windows, hipStream_t s);
 // the host twins (no device): what the two launches above compute, bit for bit
 void align_reduce_host(const float* p, int n_heads, int n_all, int n_prompt, int n_keys, float* m_out);
 void dtw_host(const float* m, int n, int n_keys, int32_t* start_idx_out);
+
+// ---- confidence (score.hip; ohw_state_score) ------------------------------------------------------------------------------
+// One workgroup per logits row of a replay chunk: row m = b * 8 + j is position row0 + j of window b.  It writes entry
+// row0 + j - (n_prompt - 1) of window b iff n_prompt - 1 <= row0 + j < n_all[b] (and the entry is below cap); every other row
+// is neither read nor written.  The work shape is fixed by n_vocab alone (score.hip states the reduction order)
+struct TokenScoreParams {
+  const float* logits;      // f32 [batch * 8][ld], raw; columns n_vocab .. ld - 1 are padding and reach no result
+  int64_t ld;               // ld % 4 == 0, 16-byte aligned rows
+  const int32_t* targets;   // i32 [batch * 8]: the column whose logit row m reports
+  const int32_t* n_all;     // i32 [batch]: positions of window b that have a score (0: the window is skipped)
+  int32_t row0, n_prompt, n_vocab, eot, batch, cap;
+  ohw_token_score* out;     // [batch][cap]
+};
+void launch_token_score(const TokenScoreParams& p, hipStream_t s);
+// the rule on one row on the host (no device): the same fp32 operations in the kernel's order
+void token_score_host(const float* x, int n_vocab, int eot, int target, ohw_token_score* out);
 
 }  // namespace ohw

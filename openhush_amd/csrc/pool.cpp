@@ -385,6 +385,32 @@ int ohw_pool_set_word_timestamps(ohw_pool* p, const ohw_align_head* heads, int n
   }
   return OHW_OK;
 }
+int ohw_pool_set_confidence(ohw_pool* p, int on) {
+  if (!p) return OHW_E_INVALID_ARG;
+  for (ohw_engine* e : p->engines) {
+    const int rc = ohw_engine_set_confidence(e, on);
+    if (rc != OHW_OK) return rc;
+  }
+  return OHW_OK;
+}
+int ohw_pool_last_token_probs(ohw_pool* p, const ohw_token_prob** t, int* n) {
+  if (!p || !t || !n) return OHW_E_INVALID_ARG;
+  *t = p->last.token_probs.data();
+  *n = (int)p->last.token_probs.size();
+  return OHW_OK;
+}
+int ohw_pool_last_word_probs(ohw_pool* p, const ohw_word_prob** w, int* n) {
+  if (!p || !w || !n) return OHW_E_INVALID_ARG;
+  *w = p->last.word_probs.data();
+  *n = (int)p->last.word_probs.size();
+  return OHW_OK;
+}
+int ohw_pool_last_segment_info(ohw_pool* p, const ohw_segment_info** s, int* n) {
+  if (!p || !s || !n) return OHW_E_INVALID_ARG;
+  *s = p->last.segment_info.data();
+  *n = (int)p->last.segment_info.size();
+  return OHW_OK;
+}
 int ohw_pool_last_token_times(ohw_pool* p, const ohw_token_time** t, int* n) {
   if (!p || !t || !n) return OHW_E_INVALID_ARG;
   *t = p->last.token_times.data();
@@ -471,6 +497,7 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
     out.clear();
     std::string& text = out.text;
     std::vector<size_t> tok_pos((size_t)G, 0), win_pos((size_t)G, 0), tt_pos((size_t)G, 0), wd_pos((size_t)G, 0), sg_pos((size_t)G, 0);
+    std::vector<size_t> tp_pos((size_t)G, 0), wp_pos((size_t)G, 0);
     const int64_t n_rec = seek ? (int64_t)p->engines[0]->last.quality.size() : n_win;
     for (int64_t w = 0; w < n_rec; ++w) {
       const int g = seek ? 0 : (int)(w % used);
@@ -489,7 +516,18 @@ int ohw_pool_transcribe(ohw_pool* p, const float* samples, int64_t n, uint32_t s
           s.text_off = s.text_off - mk.text0 + text.size();
           out.words.push_back(s);
         }
+        for (int i = 0; i < mk.n_token_probs; ++i) {
+          ohw_token_prob t = got.token_probs[tp_pos[(size_t)g]++];
+          t.window = (int32_t)w;
+          out.token_probs.push_back(t);
+        }
+        for (int i = 0; i < mk.n_word_probs; ++i) {
+          ohw_word_prob s = got.word_probs[wp_pos[(size_t)g]++];
+          s.text_off = s.text_off - mk.text0 + text.size();
+          out.word_probs.push_back(s);
+        }
         for (int i = 0; i < mk.n_segments; ++i) {
+          if (got.segment_info.size() == got.segments.size()) out.segment_info.push_back(got.segment_info[sg_pos[(size_t)g]]);
           ohw_span_time s = got.segments[sg_pos[(size_t)g]++];
           s.text_off = s.text_off - mk.text0 + text.size();
           out.segments.push_back(s);

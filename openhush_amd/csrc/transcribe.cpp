@@ -338,14 +338,18 @@ struct TranscribeCall {
   }
   // word timestamps: the kept pass of every window of a batch is aligned on the state that decoded it, while its cross K/V
   // is resident (before that state's next encode); windows with no kept text token are skipped.  frames: 10 ms frames of audio
+  // confidence (ohw_engine_set_confidence): the same tokens are scored by the unconstrained model, in the alignment's own
+  // replay when both are on (ohw_state_score with a start index output), alone when word timestamps are off
   void align_runs(Scratch& sc, ohw_state* st, int B, const int* frames) const {
-    if (e->wt_heads.empty()) return;
+    const bool al = !e->wt_heads.empty(), conf = e->confidence;
+    if (!al && !conf) return;
     const int half = max_tok / 2;
     std::vector<int32_t> atok((size_t)B * half, 0), nt((size_t)B, 0), nf((size_t)B, 0), out((size_t)B * (half + 1), 0);
     bool any = false;
     for (int b = 0; b < B; ++b) {
       WindowRun& r = sc.runs[(size_t)b];
       r.al_idx.clear();
+      r.sc.clear();
       const int keep = kept_tokens(r, pol);
       int k = 0;
       for (int i = 0; i < keep && k < half; ++i)
@@ -355,10 +359,15 @@ struct TranscribeCall {
       any = any || k > 0;
     }
     if (!any) return;
-    check(ohw_state_set_align_heads(st, e->wt_heads.data(), (int)e->wt_heads.size()));
-    check(ohw_state_align(st, &sp, atok.data(), half, nt.data(), nf.data(), B, out.data()));
-    for (int b = 0; b < B; ++b)
-      if (nt[(size_t)b] > 0) sc.runs[(size_t)b].al_idx.assign(&out[(size_t)b * (half + 1)], &out[(size_t)b * (half + 1)] + nt[(size_t)b] + 1);
+    if (al) check(ohw_state_set_align_heads(st, e->wt_heads.data(), (int)e->wt_heads.size()));
+    std::vector<ohw_token_score> scores((size_t)(conf ? B * (half + 1) : 0));
+    if (conf) check(ohw_state_score(st, &sp, atok.data(), half, nt.data(), B, scores.data(), al ? nf.data() : nullptr, al ? out.data() : nullptr));
+    else check(ohw_state_align(st, &sp, atok.data(), half, nt.data(), nf.data(), B, out.data()));
+    for (int b = 0; b < B; ++b) {
+      if (nt[(size_t)b] == 0) continue;
+      if (al) sc.runs[(size_t)b].al_idx.assign(&out[(size_t)b * (half + 1)], &out[(size_t)b * (half + 1)] + nt[(size_t)b] + 1);
+      if (conf) sc.runs[(size_t)b].sc.assign(&scores[(size_t)b * (half + 1)], &scores[(size_t)b * (half + 1)] + nt[(size_t)b] + 1);
+    }
   }
   // the decode of one batch of fixed cuts (each its own `full` call in whisper.cpp terms: seek 0, its own frame count as the end
   // of the audio, fresh generators) on whatever stream the state is set to; fills sc.runs and sc.trace; re-entrant per Scratch.
@@ -386,6 +395,7 @@ struct TranscribeCall {
     const bool no_speech = is_no_speech(r, pol);
     const int keep = kept_tokens(r, pol);
     const size_t win_text0 = text.size(), tt0 = out.token_times.size(), wd0 = out.words.size(), sg0 = out.segments.size();
+    const size_t tp0 = out.token_probs.size(), wp0 = out.word_probs.size();
     std::vector<size_t> byte_off((size_t)keep + 1, text.size());       // text offset in front of every kept token
     std::vector<int32_t> tlen;                                         // byte length of every kept TEXT token
     std::vector<int> tpos;                                             //   and its position among the kept tokens
@@ -427,7 +437,43 @@ struct TranscribeCall {
         w.t1 = tt.t1;
       }
     }
-    out.marks.push_back(WindowMark{win_text0, (int32_t)(out.token_times.size() - tt0), (int32_t)(out.words.size() - wd0), (int32_t)(out.segments.size() - sg0)});
+    if (e->confidence) {
+      // token probabilities, word probabilities by the host rules (include/ohw.h), one info entry per segment of the window
+      const bool scored = !r.sc.empty() && r.sc.size() == tlen.size() + 1;
+      std::vector<float> lpt(scored ? tlen.size() : 0);
+      if (scored) {
+        const int32_t window = (int32_t)out.quality.size();
+        for (size_t k = 0; k < tlen.size(); ++k) {
+          ohw_token_prob tp{r.tok[(size_t)tpos[k]], window, 0.f, 0.f, r.plog[(size_t)tpos[k]], r.sc[k].top_id, 0.f};
+          (void)ohw_token_prob_host(&r.sc[k], &tp.logprob_text, &tp.logprob_all, &tp.top_logprob_text);
+          lpt[k] = tp.logprob_text;
+          out.token_probs.push_back(tp);
+        }
+        std::vector<int32_t> starts(tlen.size(), 0);
+        std::vector<float> wp(tlen.size(), 0.f);
+        (void)ohw_word_starts_host(text.data() + win_text0, tlen.data(), (int)tlen.size(), starts.data());
+        const int n_wp = ohw_word_probs_host(lpt.data(), starts.data(), (int)tlen.size(), wp.data());
+        for (size_t k = 0; k < tlen.size(); ++k) {
+          const size_t o0 = byte_off[(size_t)tpos[k]];
+          if (starts[k] || out.word_probs.size() == wp0) out.word_probs.push_back(ohw_word_prob{o0, 0, 0.f});
+          ohw_word_prob& w = out.word_probs.back();
+          w.text_len = o0 + (size_t)tlen[k] - w.text_off;
+        }
+        for (size_t i = 0; i < out.word_probs.size() - wp0 && (int)i < n_wp; ++i) out.word_probs[wp0 + i].probability = wp[i];
+      }
+      for (size_t s = sg0; s < out.segments.size(); ++s) {
+        // the segment's text tokens: those whose bytes lie inside its span (a segment is a run of kept tokens)
+        double sum = 0.0;
+        int cnt = 0;
+        for (size_t k = 0; scored && k < tlen.size(); ++k) {
+          const size_t o = byte_off[(size_t)tpos[k]];
+          if (o >= out.segments[s].text_off && o + (size_t)tlen[k] <= out.segments[s].text_off + out.segments[s].text_len) { sum += lpt[k]; ++cnt; }
+        }
+        out.segment_info.push_back(ohw_segment_info{cnt > 0 ? (float)(sum / cnt) : __builtin_nanf(""), r.nosp, r.temp});
+      }
+    }
+    out.marks.push_back(WindowMark{win_text0, (int32_t)(out.token_times.size() - tt0), (int32_t)(out.words.size() - wd0), (int32_t)(out.segments.size() - sg0),
+                                   (int32_t)(out.token_probs.size() - tp0), (int32_t)(out.word_probs.size() - wp0)});
     out.contexts.push_back(ctx);
     if (const LogitRules& rules = state_rules(e->state); rules.cm.on) {
       const int id = ohw_command_match_host(&rules.cm.host, r.tok.data(), keep);
@@ -782,7 +828,8 @@ void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n,
   schedule = ensure_schedule_resources(e, schedule, cuts.n_batches);
   // an engine of a pool that aligns: its share may be one batch while the recording is several, and the alignment's path is
   // sensitive to last bits, so the times must not depend on how the windows were dealt
-  Invariant invariant(e, cuts.n_batches > 1 || (!e->wt_heads.empty() && win_step > 1));
+  // (confidence alike: a score is a function of the last bits of a row)
+  Invariant invariant(e, cuts.n_batches > 1 || ((!e->wt_heads.empty() || e->confidence) && win_step > 1));
   SharedRecording shared_recording(e, cuts.rec_mel);
   sync_logit_rules(e);
   apply_ctx(e, call_ctx);
@@ -804,9 +851,11 @@ void engine_transcribe(ohw_engine* e, const float* samples, int64_t n, int64_t w
 // ohw_engine_transcribe_batch: every recording one window of its own; longest first, max_batch at a time, one batch after the
 // other on the engine's own state.  Under the auto setting a batch's envelope is its largest context and every window runs at
 // its own (ohw_state_set_window_ctx) - unless all of them equal the envelope, which is the uniform path
-void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs, const double* t_offs, bool trim) {
-  const TranscribeCall tc(e, nullptr, 0);
-  e->batch_records.assign((size_t)n_recs, ohw_engine::BatchRecord());
+// the front end of the short batch, shared with ohw_engine_score_batch: plan, stage, context, mel, encode and languages of one
+// batch after the other; then run(bi, B, ord, ns, langs or null) on the engine's own state, whose cross K/V holds the batch
+template <typename F>
+static void short_batch_front(ohw_engine* e, const TranscribeCall& tc, const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs, const char* what,
+                              F&& run) {
   std::vector<int64_t> lens((size_t)n_recs);
   for (int i = 0; i < n_recs; ++i) lens[(size_t)i] = recs[i].n;
   const int MB = tc.WB, n_b = (n_recs + MB - 1) / MB, full_ctx = e->ctx->hp.n_audio_ctx;
@@ -814,13 +863,12 @@ void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_re
   const int prc = ohw_batch_plan(lens.data(), n_recs, MB, e->audio_ctx, order.data(), rctx.data(), env.data());
   if (prc != OHW_OK) throw Error(prc, g_last_error);
   BatchStateGuard restore_state(e, true);
-  Scratch sc(MB, tc.max_tok);
   std::vector<float> stage;
   std::vector<int32_t> ns((size_t)MB), wl((size_t)MB), batch_lang;
   // a language per recording: the caller's ids, or a detection per recording when the engine detects; an English-only model
   // has no language token and stays as it is
   const bool per_rec = tc.V >= 51865 && (rec_langs != nullptr || engine_detects(e));
-  check_recording_langs("transcribe_batch", rec_langs, n_recs, tc.tk.n_langs);
+  check_recording_langs(what, rec_langs, n_recs, tc.tk.n_langs);
   for (int bi = 0; bi < n_b; ++bi) {
     const int B = std::min(MB, n_recs - bi * MB);
     const int32_t* ord = &order[(size_t)bi * MB];
@@ -843,7 +891,17 @@ void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_re
       for (int b = 0; rec_langs && b < B; ++b) batch_lang[(size_t)b] = rec_langs[ord[b]];
       apply_window_langs(e->state, batch_lang, true);
     }
-    tc.decode_windows(sc, e->state, (int64_t)bi * MB, B, ns.data(), per_rec ? batch_lang.data() : nullptr);
+    run(bi, B, ord, ns.data(), per_rec ? batch_lang.data() : nullptr);
+  }
+}
+
+void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* rec_langs, const double* t_offs, bool trim) {
+  const TranscribeCall tc(e, nullptr, 0);
+  e->batch_records.assign((size_t)n_recs, ohw_engine::BatchRecord());
+  const int MB = tc.WB;
+  Scratch sc(MB, tc.max_tok);
+  short_batch_front(e, tc, recs, n_recs, rec_langs, "transcribe_batch", [&](int bi, int B, const int32_t* ord, const int32_t* ns, const int32_t* batch_lang) {
+    tc.decode_windows(sc, e->state, (int64_t)bi * MB, B, ns, batch_lang);
     sc.trace.clear();
     sc.cands.clear();
     for (int b = 0; b < B; ++b) {
@@ -851,9 +909,54 @@ void engine_transcribe_batch(ohw_engine* e, const ohw_audio_span* recs, int n_re
       const double t_off = t_offs ? t_offs[ord[b]] : 0.0;
       tc.emit(sc.runs[(size_t)b], t_off, t_off + (double)recs[ord[b]].n / 16000.0, r.t, e->prompt);
       if (trim) r.t.trim();
-      r.lang_id = per_rec ? batch_lang[(size_t)b] : -1;
+      r.lang_id = batch_lang ? batch_lang[b] : -1;
     }
+  });
+}
+
+// ohw_engine_score_batch: the short batch's front end, then ohw_state_score on the caller's tokens instead of a decode
+void engine_score_batch(ohw_engine* e, const ohw_audio_span* recs, int n_recs, const int32_t* tokens, const int32_t* offsets, ohw_score_result* results) {
+  const TranscribeCall tc(e, nullptr, 0);
+  const int half = tc.max_tok / 2, MB = tc.WB;
+  for (int i = 0; i < n_recs; ++i) {
+    const int64_t nt = (int64_t)offsets[i + 1] - offsets[i];
+    if (offsets[i] < 0 || nt < 0 || nt > half)
+      throw Error(OHW_E_INVALID_ARG, "score_batch: recording " + std::to_string(i) + " has " + std::to_string(nt) + " tokens, outside 0 .. n_text_ctx / 2 = " + std::to_string(half));
+    for (int64_t k = 0; k < nt; ++k)
+      if (tokens[offsets[i] + k] < 0 || tokens[offsets[i] + k] >= tc.tk.eot)
+        throw Error(OHW_E_INVALID_ARG, "score_batch: recording " + std::to_string(i) + ", token " + std::to_string(k) + ": id " + std::to_string(tokens[offsets[i] + k]) +
+                                           " is not a text token (0 .. " + std::to_string(tc.tk.eot - 1) + ")");
   }
+  e->score_records.assign((size_t)n_recs, std::vector<ohw_token_prob>());
+  const float nan = __builtin_nanf("");
+  std::vector<int32_t> atok((size_t)MB * half), nt((size_t)MB);
+  std::vector<ohw_token_score> scores((size_t)MB * (half + 1));
+  short_batch_front(e, tc, recs, n_recs, nullptr, "score_batch", [&](int, int B, const int32_t* ord, const int32_t*, const int32_t*) {
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+      nt[(size_t)b] = offsets[ord[b] + 1] - offsets[ord[b]];
+      std::copy(tokens + offsets[ord[b]], tokens + offsets[ord[b] + 1], atok.begin() + (long)((size_t)b * half));
+      any = any || nt[(size_t)b] > 0;
+    }
+    if (any) check(ohw_state_score(e->state, &tc.sp, atok.data(), half, nt.data(), B, scores.data(), nullptr, nullptr));
+    for (int b = 0; b < B; ++b) {
+      const int i = ord[b], n = nt[(size_t)b];
+      std::vector<ohw_token_prob>& rec = e->score_records[(size_t)i];
+      ohw_score_result& r = results[i];
+      r.eot = ohw_token_prob{tc.tk.eot, 0, nan, nan, nan, -1, nan};
+      r.sum_logprob_all = nan;
+      double sum = 0.0;
+      for (int k = 0; n > 0 && k <= n; ++k) {
+        const ohw_token_score& s = scores[(size_t)b * (half + 1) + k];
+        ohw_token_prob tp{k < n ? atok[(size_t)b * half + k] : tc.tk.eot, 0, 0.f, 0.f, nan, s.top_id, 0.f};
+        (void)ohw_token_prob_host(&s, &tp.logprob_text, &tp.logprob_all, &tp.top_logprob_text);
+        sum += tp.logprob_all;
+        if (k < n) rec.push_back(tp); else r.eot = tp;
+      }
+      if (n > 0) r.sum_logprob_all = (float)sum;
+    }
+  });
+  for (int i = 0; i < n_recs; ++i) { results[i].tokens = e->score_records[(size_t)i].data(); results[i].n_tokens = (int32_t)e->score_records[(size_t)i].size(); }
 }
 
 // ohw_engine_transcribe_speech: the front half (detector, segments, chunks) per recording, then every chunk of every recording as
@@ -911,6 +1014,9 @@ void engine_transcribe_speech(ohw_engine* e, const ohw_audio_span* recs, const o
       for (ohw_token_time tt : c.token_times) { tt.window += win0; t.token_times.push_back(tt); }
       for (ohw_span_time w : c.words) { w.text_off += text0; t.words.push_back(w); }
       for (ohw_span_time sg : c.segments) { sg.text_off += text0; t.segments.push_back(sg); }
+      for (ohw_token_prob tp : c.token_probs) { tp.window += win0; t.token_probs.push_back(tp); }
+      for (ohw_word_prob wp : c.word_probs) { wp.text_off += text0; t.word_probs.push_back(wp); }
+      t.segment_info.insert(t.segment_info.end(), c.segment_info.begin(), c.segment_info.end());
       for (WindowMark m : c.marks) { m.text0 += text0; t.marks.push_back(m); }
       t.contexts.insert(t.contexts.end(), c.contexts.begin(), c.contexts.end());
       for (ohw_command_hit hit : c.commands) { hit.window += win0; t.commands.push_back(hit); }

@@ -27,6 +27,7 @@ struct WindowRun {
   bool pending = false, t0_failed = false;
   float list_lp = __builtin_nanf("");   // command lists: the pass's list_logprob (NaN: no list, or no step wrote one)
   std::vector<int32_t> al_idx;   // word timestamps: start index of every kept text token, then the end of the last (empty: not aligned)
+  std::vector<ohw_token_score> sc;   // confidence: the score of every kept text token, then end-of-text's (empty: not scored)
 };
 
 // frames of 10 ms whisper.cpp attributes to n samples: mel.n_len_org = 1 + (n + 200 - 400) / 160

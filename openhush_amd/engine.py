@@ -172,6 +172,21 @@ class DbgDecGemmIO(C.Structure):
                 [(n, C.c_int32) for n in ("d_model", "n_head", "n_ctx")] + [("shape_out", C.POINTER(C.c_int32))])
 
 
+class DbgLogitsRowsIO(C.Structure):
+    """ohw_dbg_logits_rows_io: ohw_dbg_dec_gemm_io with epilogue LOGITS, plus the all-rows output (a device address, or None)"""
+    _fields_ = [("g", DbgDecGemmIO), ("out_all", C.c_void_p), ("ld_all", C.c_int64)]
+
+
+class TokenScore(C.Structure):
+    """ohw_token_score: the five words of one raw logits row (include/ohw.h, "confidence")"""
+    _fields_ = [("logit", C.c_float), ("lse_text", C.c_float), ("lse_all", C.c_float), ("top_id", C.c_int32), ("top_logit", C.c_float)]
+
+
+# numpy's view of ohw_token_score (20 bytes, no padding)
+TOKEN_SCORE_DTYPE = np.dtype([("logit", np.float32), ("lse_text", np.float32), ("lse_all", np.float32), ("top_id", np.int32), ("top_logit", np.float32)])
+assert TOKEN_SCORE_DTYPE.itemsize == C.sizeof(TokenScore) == 20
+
+
 class DbgEncGemmIO(C.Structure):
     """ohw_dbg_enc_gemm_io: a, w, bias, pos and out are device addresses, c_row_map is a host table"""
     _fields_ = ([(n, C.c_int32) for n in ("dtype", "epilogue", "kernel", "conv_cin")] +
@@ -503,6 +518,27 @@ class TokenTime(C.Structure):
     _fields_ = [("id", C.c_int32), ("window", C.c_int32), ("t0", C.c_float), ("t1", C.c_float)]
 
 
+class TokenProb(C.Structure):
+    """ohw_token_prob"""
+    _fields_ = [("id", C.c_int32), ("window", C.c_int32), ("logprob_text", C.c_float), ("logprob_all", C.c_float), ("logprob_decode", C.c_float),
+                ("top_id", C.c_int32), ("top_logprob_text", C.c_float)]
+
+
+class WordProb(C.Structure):
+    """ohw_word_prob"""
+    _fields_ = [("text_off", C.c_size_t), ("text_len", C.c_size_t), ("probability", C.c_float)]
+
+
+class SegmentInfo(C.Structure):
+    """ohw_segment_info"""
+    _fields_ = [("avg_logprob_text", C.c_float), ("no_speech_prob", C.c_float), ("temperature", C.c_float)]
+
+
+class ScoreResultC(C.Structure):
+    """ohw_score_result"""
+    _fields_ = [("tokens", C.POINTER(TokenProb)), ("n_tokens", C.c_int32), ("eot", TokenProb), ("sum_logprob_all", C.c_float)]
+
+
 class SpanTime(C.Structure):
     _fields_ = [("text_off", C.c_size_t), ("text_len", C.c_size_t), ("t0", C.c_float), ("t1", C.c_float)]
 
@@ -579,6 +615,11 @@ EXPORTS = [
     "ohw_default_vad_detector", "ohw_state_vad_frames", "ohw_speech_segments_host", "ohw_default_chunk_plan", "ohw_speech_chunks_host",
     "ohw_engine_set_vad", "ohw_engine_transcribe_speech", "ohw_engine_transcribe_speech_lang", "ohw_engine_speech_chunks",
     "ohw_engine_speech_segments", "ohw_dbg_vad_energy", "ohw_dbg_vad_floor",
+    "ohw_state_score", "ohw_state_set_score_buffers", "ohw_token_score_host", "ohw_token_prob_host", "ohw_word_probs_host",
+    "ohw_dbg_token_score", "ohw_dbg_logits_rows",
+    "ohw_engine_set_confidence", "ohw_engine_last_token_probs", "ohw_engine_last_word_probs", "ohw_engine_last_segment_info",
+    "ohw_engine_batch_confidence", "ohw_pool_set_confidence", "ohw_pool_last_token_probs", "ohw_pool_last_word_probs",
+    "ohw_pool_last_segment_info", "ohw_engine_score_batch",
 ]
 
 
@@ -849,6 +890,13 @@ def lib():
         L.ohw_dbg_enc_gemm.argtypes = [C.POINTER(DbgEncGemmIO), vp]
         L.ohw_dbg_embed.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, ip, ip, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
         L.ohw_dbg_layernorm.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp]
+        L.ohw_dbg_logits_rows.argtypes = [C.POINTER(DbgLogitsRowsIO), vp]
+        L.ohw_state_score.argtypes = [vp, C.POINTER(SampleParams), ip, C.c_int, ip, C.c_int, vp, ip, ip]
+        L.ohw_state_set_score_buffers.argtypes = [vp, C.c_int]
+        L.ohw_token_score_host.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.POINTER(TokenScore)]
+        L.ohw_token_prob_host.argtypes = [C.POINTER(TokenScore), fp, fp, fp]
+        L.ohw_word_probs_host.argtypes = [fp, ip, C.c_int, fp]
+        L.ohw_dbg_token_score.argtypes = [vp, fp, C.c_int, C.c_int64, C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.ohw_state_set_audio_ctx.argtypes = [vp, C.c_int]
         L.ohw_state_audio_ctx.argtypes = [vp]
         L.ohw_audio_ctx_for.argtypes = [C.c_int64]
@@ -924,6 +972,14 @@ def lib():
         L.ohw_engine_batch_times.argtypes = [vp, C.c_int, ptt, C.POINTER(C.c_int), pst, C.POINTER(C.c_int), pst, C.POINTER(C.c_int)]
         L.ohw_word_starts_host.argtypes = [C.c_char_p, ip, C.c_int, ip]
         L.ohw_pool_set_word_timestamps.argtypes = [vp, C.POINTER(AlignHead), C.c_int]
+        ptp, pwp, psi, pci = C.POINTER(C.POINTER(TokenProb)), C.POINTER(C.POINTER(WordProb)), C.POINTER(C.POINTER(SegmentInfo)), C.POINTER(C.c_int)
+        for who in ("engine", "pool"):
+            getattr(L, f"ohw_{who}_set_confidence").argtypes = [vp, C.c_int]
+            getattr(L, f"ohw_{who}_last_token_probs").argtypes = [vp, ptp, pci]
+            getattr(L, f"ohw_{who}_last_word_probs").argtypes = [vp, pwp, pci]
+            getattr(L, f"ohw_{who}_last_segment_info").argtypes = [vp, psi, pci]
+        L.ohw_engine_batch_confidence.argtypes = [vp, C.c_int, ptp, pci, pwp, pci, psi, pci]
+        L.ohw_engine_score_batch.argtypes = [vp, C.POINTER(AudioSpan), C.c_int, ip, ip, C.POINTER(ScoreResultC)]
         L.ohw_pool_last_token_times.argtypes = [vp, ptt, C.POINTER(C.c_int)]
         L.ohw_pool_last_words.argtypes = [vp, pst, C.POINTER(C.c_int)]
         L.ohw_pool_last_segments.argtypes = [vp, pst, C.POINTER(C.c_int)]
@@ -1046,6 +1102,36 @@ def dbg_align_probs(dtype: int, q_ptr: int, xk_ptr: int, rows: int, n_head: int,
     return out
 
 
+def token_score_host(row: np.ndarray, eot: int, target: int, n_vocab: Optional[int] = None) -> np.ndarray:
+    """ohw_token_score_host (host only): one raw logits row -> a TOKEN_SCORE_DTYPE scalar; n_vocab < len(row) leaves the
+    columns behind it as padding"""
+    r = np.ascontiguousarray(row, dtype=np.float32)
+    out = np.zeros(1, dtype=TOKEN_SCORE_DTYPE)
+    _check(lib().ohw_token_score_host(_fp(r), int(r.size if n_vocab is None else n_vocab), int(eot), int(target),
+                                      C.cast(out.ctypes.data, C.POINTER(TokenScore))))
+    return out[0]
+
+
+def token_prob_host(score) -> Tuple[float, float, float]:
+    """ohw_token_prob_host: one score -> (logprob_text, logprob_all, top_logprob_text) as fp32"""
+    s = TokenScore(float(score["logit"]), float(score["lse_text"]), float(score["lse_all"]), int(score["top_id"]), float(score["top_logit"]))
+    a, b, c = C.c_float(), C.c_float(), C.c_float()
+    _check(lib().ohw_token_prob_host(C.byref(s), C.byref(a), C.byref(b), C.byref(c)))
+    return np.float32(a.value), np.float32(b.value), np.float32(c.value)
+
+
+def word_probs_host(logprob_text, starts) -> np.ndarray:
+    """ohw_word_probs_host (host only): one window's text-token log-probabilities and word starts -> one probability per word"""
+    lp = np.ascontiguousarray(logprob_text, dtype=np.float32)
+    st = np.ascontiguousarray(starts, dtype=np.int32)
+    assert lp.size == st.size
+    out = np.zeros(max(lp.size, 1), dtype=np.float32)
+    n = lib().ohw_word_probs_host(_fp(lp) if lp.size else None, _ip(st) if st.size else None, int(lp.size), _fp(out))
+    if n < 0:
+        _check(n)
+    return out[:n].copy()
+
+
 def word_starts(token_bytes: Sequence[bytes]) -> List[bool]:
     """ohw_word_starts_host (host only): the bytes of one window's text tokens -> which tokens start a word"""
     lens = np.asarray([len(b) for b in token_bytes], dtype=np.int32)
@@ -1103,6 +1189,51 @@ def needs_fallback_host(ev: SeqEval, policy: DecodePolicy, no_speech_prob: float
 
 def _token_times(p, n):
     return [{"id": int(p[i].id), "window": int(p[i].window), "t0": float(p[i].t0), "t1": float(p[i].t1)} for i in range(n)]
+
+
+def _token_probs(p, n):
+    return [{"id": int(p[i].id), "window": int(p[i].window), "logprob_text": float(p[i].logprob_text), "logprob_all": float(p[i].logprob_all),
+             "logprob_decode": float(p[i].logprob_decode), "top_id": int(p[i].top_id), "top_logprob_text": float(p[i].top_logprob_text)}
+            for i in range(n)]
+
+
+def _word_probs(p, n, text_bytes: bytes):
+    return [{"text": text_bytes[p[i].text_off:p[i].text_off + p[i].text_len].decode("utf-8", "replace"), "text_off": int(p[i].text_off),
+             "text_len": int(p[i].text_len), "probability": float(p[i].probability)} for i in range(n)]
+
+
+def _segment_info(p, n):
+    return [{"avg_logprob": float(p[i].avg_logprob_text), "no_speech_prob": float(p[i].no_speech_prob), "temperature": float(p[i].temperature)}
+            for i in range(n)]
+
+
+class _ConfidenceMirror:
+    """the confidence accessors WhisperEngine and EnginePool share (ohw_engine_* / ohw_pool_*; include/ohw.h, "confidence in the
+    engine"); _WHO names the C prefix"""
+    _WHO = "engine"
+
+    def set_confidence(self, on: bool = True):
+        """ohw_*_set_confidence: score every kept pass with the unconstrained model (off, the default, frees the buffers)"""
+        _check(getattr(lib(), f"ohw_{self._WHO}_set_confidence")(self.h, int(bool(on))))
+
+    def last_token_probs(self):
+        """[{id, window, logprob_text, logprob_all, logprob_decode, top_id, top_logprob_text}] per kept text token of the last
+        transcribe (empty unless confidence is on)"""
+        p, n = C.POINTER(TokenProb)(), C.c_int(0)
+        _check(getattr(lib(), f"ohw_{self._WHO}_last_token_probs")(self.h, C.byref(p), C.byref(n)))
+        return _token_probs(p, n.value)
+
+    def last_word_probs(self):
+        """[{text, text_off, text_len, probability}] per word of the last transcribe; no alignment heads needed"""
+        p, n = C.POINTER(WordProb)(), C.c_int(0)
+        _check(getattr(lib(), f"ohw_{self._WHO}_last_word_probs")(self.h, C.byref(p), C.byref(n)))
+        return _word_probs(p, n.value, self._last_text_bytes())
+
+    def last_segment_info(self):
+        """[{avg_logprob, no_speech_prob, temperature}], one per entry of last_segments() while confidence is on"""
+        p, n = C.POINTER(SegmentInfo)(), C.c_int(0)
+        _check(getattr(lib(), f"ohw_{self._WHO}_last_segment_info")(self.h, C.byref(p), C.byref(n)))
+        return _segment_info(p, n.value)
 
 
 def _spans(p, n, text_bytes: bytes):
@@ -1809,6 +1940,55 @@ class State:
         self._align_shape = [(n_prompt, int(nt[b]), max(1, min(self.window_ctx(b), int(nf[b]) // 2))) for b in range(B)]
         return [out[b, :nt[b] + 1].copy() if nt[b] else np.zeros(0, np.int32) for b in range(B)]
 
+    def set_score_buffers(self, on: int):
+        """ohw_state_set_score_buffers: 0 frees the buffers of score(), 1 makes them, 2 also keeps every call's last window's rows
+        for fetch("score_logits", batch)"""
+        _check(lib().ohw_state_set_score_buffers(self.h, int(on)))
+
+    def score(self, tokens: Sequence[Sequence[int]], n_frames: Optional[Sequence[int]] = None, p: Optional[SampleParams] = None):
+        """ohw_state_score for the windows of the last encode: tokens[b] = window b's text tokens (empty: skip the window) -> per
+        window a TOKEN_SCORE_DTYPE array of len(tokens[b]) + 1 entries (the last one scores end-of-text; [] for a skipped window).
+        With n_frames the alignment runs in the same replay (alignment heads needed) and the result is (scores, start_idx) with
+        start_idx as align() returns it.  The state's self K/V is stale afterwards; every decode rewrites it."""
+        p = p or self.ctx.default_params()
+        B = len(tokens)
+        stride = max([len(t) for t in tokens] + [1])
+        tk = np.zeros((B, stride), dtype=np.int32)
+        nt = np.zeros(B, dtype=np.int32)
+        for b, t in enumerate(tokens):
+            nt[b] = len(t)
+            tk[b, :len(t)] = np.asarray(t, dtype=np.int32)
+        sc = np.zeros((B, stride + 1), dtype=TOKEN_SCORE_DTYPE)
+        nf = idx = None
+        if n_frames is not None:
+            nf = np.asarray(list(n_frames), dtype=np.int32)
+            assert nf.size == B
+            idx = np.full((B, stride + 1), -1, dtype=np.int32)
+        _check(lib().ohw_state_score(self.h, C.byref(p), _ip(tk), stride, _ip(nt), B, sc.ctypes.data, None if nf is None else _ip(nf),
+                                     None if idx is None else _ip(idx)))
+        n_prompt = 4 if self.ctx.hp.n_vocab >= 51865 else 2
+        self._score_chunks = (n_prompt + int(nt.max()) + 1 + 7) // 8 if nt.max() > 0 else 0
+        scores = [sc[b, :nt[b] + 1].copy() if nt[b] else np.zeros(0, TOKEN_SCORE_DTYPE) for b in range(B)]
+        if idx is None:
+            return scores
+        self._align_shape = [(n_prompt, int(nt[b]), max(1, min(self.window_ctx(b), int(nf[b]) // 2))) for b in range(B)]
+        return scores, [idx[b, :nt[b] + 1].copy() if nt[b] else np.zeros(0, np.int32) for b in range(B)]
+
+    def dbg_token_score(self, logits: np.ndarray, n_vocab: int, eot: int, targets, n_all, row0: int, n_prompt: int, cap: int, guard: int = 4):
+        """ohw_dbg_token_score: token_score_kernel once on logits [batch * 8][ld] (padding columns as the caller poisoned them),
+        targets [batch * 8], n_all [batch] -> TOKEN_SCORE_DTYPE [guard + batch * cap + guard]; what the kernel did not write
+        holds OHW_DBG_SENTINEL_*"""
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        assert lg.ndim == 2 and lg.shape[0] % 8 == 0
+        batch = lg.shape[0] // 8
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        na = np.ascontiguousarray(n_all, dtype=np.int32)
+        assert tg.size == batch * 8 and na.size == batch
+        out = np.zeros(batch * cap + 2 * guard, dtype=TOKEN_SCORE_DTYPE)
+        _check(lib().ohw_dbg_token_score(self.h, _fp(lg), batch, lg.shape[1], int(n_vocab), int(eot), _ip(tg), _ip(na), int(row0), int(n_prompt),
+                                         int(cap), int(guard), out.ctypes.data))
+        return out
+
     def dbg_lang_pick(self, logits: np.ndarray):
         """the DEVICE language pick on caller-supplied rows [B][n_vocab] -> (ids [B], probs [B][n_langs])"""
         lg = np.ascontiguousarray(np.atleast_2d(logits), dtype=np.float32)
@@ -2116,6 +2296,14 @@ class State:
             if what == "align_p":
                 return out[:A * n_all * n_keys].reshape(A, n_all, n_keys).copy()
             return out[:(n_text + 1) * n_keys].reshape(n_text + 1, n_keys).copy()
+        if what == "score_logits":
+            # window batch - 1 of the last score() under set_score_buffers(2): [n_chunks * 8][n_vocab], row r = position r
+            rows = 8 * getattr(self, "_score_chunks", 0)
+            if rows == 0:
+                raise WhisperError(OHW_E_INVALID_ARG, "fetch: no window was scored by the last score() of this State")
+            out = np.empty((rows, hp.n_vocab), dtype=np.float32)
+            _check(lib().ohw_state_fetch(self.h, what.encode(), batch, _fp(out), out.size))
+            return out
         if what == "sample_slots":
             # the kv_slot table of the last sample_pass_n: batch = its n_windows * best_of rows -> i32 [batch][n_text_ctx]
             out = np.empty((batch, hp.n_text_ctx), dtype=np.float32)
@@ -2429,6 +2617,10 @@ class TranscriptionResult:
     token_times: list = dataclasses.field(default_factory=list)
     words: list = dataclasses.field(default_factory=list)
     segments: list = dataclasses.field(default_factory=list)
+    # the recording's confidence (WhisperEngine.batch_confidence); empty unless set_confidence is on
+    token_probs: list = dataclasses.field(default_factory=list)
+    word_probs: list = dataclasses.field(default_factory=list)
+    segment_info: list = dataclasses.field(default_factory=list)
 
 
 @dataclasses.dataclass
@@ -2439,7 +2631,7 @@ class BenchmarkResult:
     test_audio_secs: float
 
 
-class WhisperEngine:
+class WhisperEngine(_ConfidenceMirror):
     """Drop-in mirror of the reference's WhisperEngine over libohw.so."""
 
     def __init__(self, handle):
@@ -2481,6 +2673,18 @@ class WhisperEngine:
         text = C.string_at(full, n.value).decode("utf-8", "replace") if n.value else ""
         return TranscriptionResult(text, lang.value.decode(), int(ms.value))
 
+    def state_view(self) -> "State":
+        """the engine's own state as a State that does not own it (close() and garbage collection leave the handle alone): what a
+        caller scores or inspects with between two transcribes (State.score, counter, fetch)"""
+        ctx = Context.__new__(Context)
+        ctx.h, ctx.hp, ctx.tok = self.ctx_h, HParams(), SpecialTokens()
+        _check(lib().ohw_ctx_info(ctx.h, C.byref(ctx.hp), C.byref(ctx.tok)))
+        ctx.close = lambda: None
+        st = State.__new__(State)
+        st.ctx, st.h, st.max_batch, st._align_heads, st._align_shape = ctx, self.state_h, int(lib().ohw_state_max_batch(self.state_h)), 0, []
+        st.close = lambda: None
+        return st
+
     def set_word_timestamps(self, heads: Optional[Sequence[Tuple[int, int]]]):
         """ohw_engine_set_word_timestamps: the (decoder layer, head) pairs to align with; None / empty = off (the default)"""
         hs = list(heads) if heads is not None else []
@@ -2521,6 +2725,51 @@ class WhisperEngine:
         _check(lib().ohw_engine_batch_times(self.h, int(i), C.byref(tp), C.byref(tn), C.byref(wp), C.byref(wn), C.byref(sp), C.byref(sn)))
         tb = self.batch_result(i)[0].encode("utf-8")
         return _token_times(tp, tn.value), _spans(wp, wn.value, tb), _spans(sp, sn.value, tb)
+
+    def batch_confidence(self, i: int):
+        """(token_probs, word_probs, segment_info) of recording i of the last batch call"""
+        tp, tn = C.POINTER(TokenProb)(), C.c_int(0)
+        wp, wn = C.POINTER(WordProb)(), C.c_int(0)
+        sp, sn = C.POINTER(SegmentInfo)(), C.c_int(0)
+        _check(lib().ohw_engine_batch_confidence(self.h, int(i), C.byref(tp), C.byref(tn), C.byref(wp), C.byref(wn), C.byref(sp), C.byref(sn)))
+        tb = self.batch_result(i)[0].encode("utf-8")
+        return _token_probs(tp, tn.value), _word_probs(wp, wn.value, tb), _segment_info(sp, sn.value)
+
+    def score(self, audios: Sequence[AudioBuffer], texts_or_token_lists: Sequence) -> List[dict]:
+        """ohw_engine_score_batch: how likely the unconstrained model finds the text the caller supplies for each recording (16 kHz,
+        at most 30 s and n_text_ctx / 2 text tokens each).  An entry is a token-id list (the exact form) or a str / bytes, which
+        goes through ohw_tokenize (not BPE merging: the caveat of set_commands).  -> per recording {"tokens": the last_token_probs
+        dicts (logprob_decode NaN), "eot": the end-of-text row, "sum_logprob": the sum of logprob_all over both}.  N candidates
+        for one recording: pass it N times"""
+        if len(audios) != len(texts_or_token_lists):
+            raise ValueError("score: one text or token list per recording")
+        if not audios:
+            return []
+        if any(int(a.sample_rate) != 16000 for a in audios):
+            raise ValueError("score: the recordings must be 16 kHz")
+        lists = []
+        for t in texts_or_token_lists:
+            if isinstance(t, (str, bytes)):
+                b = _text_bytes(t)
+                out = np.zeros(max(len(b), 1), dtype=np.int32)
+                n = lib().ohw_tokenize(self.ctx_h, b, _ip(out), int(out.size))
+                if n < 0:
+                    _raise(n)
+                lists.append([int(x) for x in out[:n]])
+            else:
+                lists.append([int(x) for x in t])
+        offs = np.zeros(len(lists) + 1, dtype=np.int32)
+        offs[1:] = np.cumsum([len(t) for t in lists])
+        toks = np.asarray([x for t in lists for x in t] or [0], dtype=np.int32)
+        bufs = [np.ascontiguousarray(a.samples, dtype=np.float32) for a in audios]
+        spans = (AudioSpan * len(bufs))()
+        for i, b in enumerate(bufs):
+            spans[i].samples = _fp(b) if b.size else C.cast(None, C.POINTER(C.c_float))
+            spans[i].n = b.size
+        res = (ScoreResultC * len(bufs))()
+        _check(lib().ohw_engine_score_batch(self.h, spans, len(bufs), _ip(toks), _ip(offs), res))
+        return [{"tokens": _token_probs(r.tokens, r.n_tokens), "eot": _token_probs(C.pointer(r.eot), 1)[0], "sum_logprob": float(r.sum_logprob_all)}
+                for r in res]
 
     def set_detect_language(self, on: bool = True):
         """ohw_engine_set_detect_language: with language "auto" on a multilingual model, transcribe detects the language on its
@@ -2567,7 +2816,7 @@ class WhisperEngine:
         for i in range(len(bufs)):
             r = self.batch_result(i)
             tt, words, segs = self.batch_times(i)
-            out.append(TranscriptionResult(r[0], r[3], ms, tt, words, segs))
+            out.append(TranscriptionResult(r[0], r[3], ms, tt, words, segs, *self.batch_confidence(i)))
         return out
 
     def transcribe_batch(self, audios: Sequence[AudioBuffer], languages: Optional[Sequence] = None) -> List[TranscriptionResult]:
@@ -2864,9 +3113,10 @@ class WhisperEngine:
             pass
 
 
-class EnginePool:
+class EnginePool(_ConfidenceMirror):
     """ohw_pool: one engine per device of one node behind the C ABI (the reference's `[gpu] devices` intent,
     src/config.rs:921-929).  transcribe() has WhisperEngine.transcribe's contract."""
+    _WHO = "pool"
 
     def __init__(self, model_path: Optional[str], language: str = "auto", translate: bool = False, devices: Sequence[int] = (0,),
                  dtype: int = OHW_DTYPE_BF16, max_batch: int = 1, synthetic: Optional[Sequence[int]] = None, seed: int = 1234):

@@ -139,14 +139,19 @@ class StreamingSession:
     repetition_penalty / no_repeat_ngram_size: the two controls of WhisperEngine.set_repetition on the session's state; the
     defaults (1.0, 0) are off.  commands / command_penalty: a closed list of phrases every chunk is held to
     (WhisperEngine.set_commands's rule on the session's state); after a chunk, last_command is the index of the phrase its tokens
-    were, or -1, and last_list_logprob the log-probability that the unconstrained model starts a listed phrase."""
+    were, or -1, and last_list_logprob the log-probability that the unconstrained model starts a listed phrase.  confidence:
+    every window's text tokens are scored by the unconstrained model on the session's state (State.score) and the chunk's
+    ChunkResult carries token_probs and word_probs (WhisperEngine.set_confidence's definitions; logprob_decode is NaN here: the
+    session's decodes do not return per-token log-probabilities)."""
 
     def __init__(self, ctx: E.Context, beam_size: int = 5, vad: Optional[Callable[[np.ndarray], float]] = None, vad_threshold: float = 0.5,
                  sequence_id: int = 1, tracker: Optional[TranscriptionTracker] = None, params: Optional[E.SampleParams] = None,
                  audio_config: Optional[E.PreprocessConfig] = None, noise_reduction: bool = False, noise_reduction_strength: float = 1.0,
                  denoiser: Optional["E.Denoiser"] = None, audio_ctx=0, carry_context: bool = False, hot_phrases=None, hot_phrase_boost=1.0,
-                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, commands=None, command_penalty: float = E.COMMAND_PENALTY_DEFAULT):
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, commands=None, command_penalty: float = E.COMMAND_PENALTY_DEFAULT,
+                 confidence: bool = False):
         self.ctx = ctx
+        self.confidence = bool(confidence)
         self.audio_ctx = E._audio_ctx_arg(audio_ctx)
         if self.audio_ctx > ctx.hp.n_audio_ctx:
             raise E.WhisperError(E.OHW_E_INVALID_ARG, f"audio_ctx {self.audio_ctx} exceeds the model's {ctx.hp.n_audio_ctx}")
@@ -182,6 +187,33 @@ class StreamingSession:
     def _text(self, tokens: List[int]) -> str:
         return b"".join(self.ctx.token_text(t) for t in tokens if t < self.ctx.tok.eot).decode("utf-8", "replace").strip()
 
+    def _score_window(self, toks, window: int, text0: int, token_probs: list, word_probs: list):
+        """State.score on the window just decoded (its cross K/V is resident): the engine's token and word records"""
+        text_toks = [int(t) for t in toks if t < self.ctx.tok.eot][:self.ctx.hp.n_text_ctx // 2]
+        if not text_toks:
+            return
+        sc = self.state.score([text_toks], p=self.params)[0]
+        tb = [self.ctx.token_text(t) for t in text_toks]
+        lpt = []
+        for t, s in zip(text_toks, sc[:-1]):
+            lt, la, tt = E.token_prob_host(s)
+            lpt.append(lt)
+            token_probs.append({"id": t, "window": window, "logprob_text": float(lt), "logprob_all": float(la), "logprob_decode": float("nan"),
+                                "top_id": int(s["top_id"]), "top_logprob_text": float(tt)})
+        starts = E.word_starts(tb)
+        probs = E.word_probs_host(lpt, [int(x) for x in starts])
+        off, k = text0, -1
+        for i, b in enumerate(tb):
+            if i == 0 or starts[i]:
+                k += 1
+                word_probs.append({"text": "", "text_off": off, "text_len": 0, "probability": float(probs[k])})
+            w = word_probs[-1]
+            w["text_len"] = off + len(b) - w["text_off"]
+            off += len(b)
+        for w in word_probs:
+            if not w["text"]:
+                w["text"] = b"".join(tb)[w["text_off"] - text0:w["text_off"] - text0 + w["text_len"]].decode("utf-8", "replace")
+
     def preprocess(self, samples: np.ndarray) -> np.ndarray:
         """TranscriptionWorker::preprocess_audio on a copy of the job's buffer"""
         if not self.noise_reduction and (self.audio_config is None or not self.audio_config.preprocessing):
@@ -200,6 +232,7 @@ class StreamingSession:
             # the worker hands the WHOLE buffer to engine.transcribe (worker.rs:152): a job longer than 30 s (a late timer
             # tick, a long VAD segment in continuous mode) is cut at the 30 s marks like any other input, window after window
             parts = []
+            token_probs, word_probs = [], []
             n_ctx = self.audio_ctx if self.audio_ctx > 0 else (
                 min(E.audio_ctx_for(len(s_all)), self.ctx.hp.n_audio_ctx) if self.audio_ctx < 0 and len(s_all) <= E.CHUNK_SAMPLES else 0)
             self.state.set_audio_ctx(n_ctx)
@@ -215,6 +248,8 @@ class StreamingSession:
                     toks = self.state.beam_search(1, self.beam_size, self.params)[0]["tokens"]
                 else:
                     toks = self.state.greedy(1, self.params)[0][0]
+                if self.confidence:
+                    self._score_window(toks, off // E.CHUNK_SAMPLES, sum(len(p) for p in parts), token_probs, word_probs)
                 parts.append(b"".join(self.ctx.token_text(t) for t in toks if t < self.ctx.tok.eot))
                 if self._command_table is not None:                      # of the job's last window
                     k = E.command_match_host(self._command_table, toks)
@@ -224,6 +259,8 @@ class StreamingSession:
                     self.context = E.prompt_clip([t for t in toks if t < self.ctx.tok.eot], self.ctx.hp.n_text_ctx)
                 self.windows_decoded += 1
             text = b"".join(parts).decode("utf-8", "replace").strip()
+            if self.confidence:
+                return ChunkResult(text, job.sequence_id, job.chunk_id, job.is_final, len(job.samples) / SAMPLE_RATE, token_probs, word_probs)
         return ChunkResult(text, job.sequence_id, job.chunk_id, job.is_final, len(job.samples) / SAMPLE_RATE)
 
     def tick(self, recording: np.ndarray, current_pos: int, is_final: bool = False) -> List[ChunkResult]:

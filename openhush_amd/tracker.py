@@ -26,6 +26,10 @@ class ChunkResult:
     chunk_id: int
     is_final: bool = False
     duration_secs: float = 1.0
+    # StreamingSession(confidence=True): the chunk's token and word probabilities (engine.WhisperEngine.last_token_probs /
+    # last_word_probs' dicts; word offsets index the UTF-8 bytes of the chunk's untrimmed text); the tracker does not read them
+    token_probs: list = dataclasses.field(default_factory=list)
+    word_probs: list = dataclasses.field(default_factory=list)
 
 
 @dataclasses.dataclass
