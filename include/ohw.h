@@ -1200,6 +1200,49 @@ int ohw_engine_last_context(ohw_engine* e, int window, const int32_t** tokens, i
 int ohw_engine_long_batch_context(ohw_engine* e, int rec, int window, const int32_t** tokens, int* n);
 int ohw_carry_step_host(int32_t* history, int* n_history, int n_text_ctx, const int32_t* kept, int n_kept, float kept_temperature,
                         int max_tokens, int32_t* context_out, int* n_context_out);
+/* Stitched windows: the fixed cuts overlap and neighbouring windows' tokens are merged where they agree (DESIGN.md sections 6
+ * and 9).  ohw_engine_set_stitch(e, overlap_ms): 0 (default) = off, every path gives the bits it gave before; else a multiple
+ * of 20 in [1000, 15000] (anything else: OHW_E_INVALID_ARG).  It applies to ohw_engine_transcribe in OHW_WINDOW_FIXED and
+ * OHW_WINDOW_FIXED_RECORDING_MEL, all three schedules; it has NO effect on OHW_WINDOW_SEEK, ohw_engine_transcribe_batch,
+ * _long_batch, _speech or on an engine of a pool that takes a share of a recording.
+ *   The plan (ohw_stitch_plan_host): the hop is H = 480000 - overlap_ms * 16 samples; a recording of n <= 480000 samples is one
+ * window (none for n = 0), otherwise W = ceil((n - 480000) / H) + 1; window k covers samples [k * H, min(n, k * H + 480000)), so
+ * the last window always reaches past the end of the one before it.  Off: H = 480000 and W = ceil(n / 480000).
+ *   The seam rule (ohw_stitch_seams_host; ohw_stitch_seams is its device twin on host arrays): a seam joins window w (left) and
+ * w + 1 (right); its inputs are the two windows' kept TEXT tokens (ids below end-of-text), L and R of them.  For every shift
+ * i = 1 .. L + R - 1: ls = max(0, L - i), le = min(L, L + R - i), rs = max(0, i - L), re = min(R, i), m = the number of j with
+ * left[ls + j] == right[rs + j], score = (double)m / (double)i + (double)i / 10000.0.  The seam takes the first i in ascending
+ * order with m > 1 and a score strictly above the best so far (from 0.0): left_cut = (ls + le) / 2, right_cut = (rs + re) / 2.
+ * With no such shift the seam is unmatched: shift = matches = 0, left_cut = L, right_cut = 0 - both windows stay whole.  For two
+ * windows this is transformers' _find_longest_common_sequence; seams are independent of each other (a definition).
+ * text_tokens [n_windows][stride], n_text [n_windows] (0 .. stride, stride <= 4096); seams_out [n_windows - 1]; n_windows <= 1
+ * does nothing.  ohw_dbg_stitch: the device twin with n_guard more seams behind the output, which it fills with `sentinel` words
+ * before the launch (seams_out [n_windows - 1 + n_guard]).
+ *   The ranges (ohw_stitch_ranges_host): window w keeps text tokens [rc, max(rc, lc)) - rc the right_cut of the seam on its left
+ * (0 for the first window), lc the left_cut of the seam on its right (its text count for the last).  In a window's kept tokens
+ * the range runs from the position of text token rc (index 0 when rc = 0) to the position of text token lc (all kept tokens
+ * when lc is the text count): timestamp tokens of an uncut end stay, and so do those in between.
+ *   Segments are formed by ohw_segments_host on the window's whole kept tokens and clipped to the range
+ * (ohw_stitch_clip_segment_host: returns 0 for a segment wholly outside [first, end), else 1 with *out the retained part; an end
+ * the range cut takes the seam time of that side, clamped into the segment's own [t0, t1]).  The seam time is the middle of the
+ * shared audio on the recording's clock: (start of the right window + end of the left window) / 2.
+ *   ohw_engine_last_seams: the seams of the last stitched ohw_engine_transcribe (none with stitch off or one window).
+ * ohw_engine_last_window_tokens: every window's kept tokens before the cut, window w at tokens[offsets[w] .. offsets[w + 1]);
+ * n_windows = 0 when the last transcribe was not stitched.  token_times / token_probs list the retained text tokens only; words
+ * and word probabilities are formed over a window's retained tokens; quality records, contexts, command hits and the trace stay
+ * one per window.                                                                                                            */
+typedef struct { int32_t left_window, shift, matches, left_cut, right_cut, n_left, n_right, reserved; } ohw_seam;
+int ohw_stitch_plan_host(int64_t n_samples, int overlap_ms, int64_t* hop_samples, int64_t* n_windows);
+int ohw_stitch_seams_host(const int32_t* text_tokens, int stride, const int32_t* n_text, int n_windows, ohw_seam* seams_out);
+int ohw_stitch_ranges_host(const ohw_seam* seams, const int32_t* n_text, int n_windows, int32_t* first_out, int32_t* end_out);
+int ohw_stitch_clip_segment_host(const ohw_token_span* seg, int first, int end, float t_seam_left, float t_seam_right, ohw_token_span* out);
+int ohw_stitch_seams(int device, const int32_t* text_tokens_host, int stride, const int32_t* n_text, int n_windows, ohw_seam* seams_out);
+int ohw_dbg_stitch(int device, const int32_t* text_tokens_host, int stride, const int32_t* n_text, int n_windows, int n_guard, int32_t sentinel,
+                   ohw_seam* seams_out);
+int ohw_engine_set_stitch(ohw_engine* e, int overlap_ms);
+int ohw_engine_stitch(ohw_engine* e);      /* the setting, ms */
+int ohw_engine_last_seams(ohw_engine* e, const ohw_seam** seams, int* n);
+int ohw_engine_last_window_tokens(ohw_engine* e, const int32_t** tokens, const int32_t** offsets, int* n_windows);
 /* ohw_state_set_packed_encoder on the engine's own, pipeline and lane states, those made later included (default: what
  * OHW_ENC_PACKED gave the engine's own state).  It matters for ohw_engine_transcribe_batch under the auto context (-1): a
  * batch of mixed lengths then encodes the sum of its contexts; tokens, text and quality records do not change.             */

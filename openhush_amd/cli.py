@@ -261,6 +261,12 @@ def _add_transcribe_options(t):
                    help="score every window's kept tokens with the unconstrained model on the device (a teacher-forced pass, openai-"
                         "whisper's word probability) and add to the JSON: \"probability\" on each word (a top-level \"word_probs\" "
                         "without --word-timestamps), \"avg_logprob\" and \"no_speech_prob\" on segments, and \"tokens_conf\" per text token")
+    t.add_argument("--stitch", action="store_true",
+                   help="overlap the 30 s cuts of a long recording and merge neighbouring windows where their tokens agree, so that a "
+                        "word on a cut is heard whole by one of them; the JSON gains \"seams\": per seam its left window, its time on "
+                        "the recording's clock, and the shift and matches of the merge (0 and 0: no agreement, both windows kept whole)")
+    t.add_argument("--stitch-overlap", type=float, default=None, metavar="S",
+                   help="with --stitch: seconds of audio neighbouring windows share, 1..15 in steps of 0.02 (default 5)")
     _add_vad_options(t)
     t.add_argument("--align-heads", default="", metavar="L.H,L.H,...",
                    help="the (decoder layer, head) pairs whose cross-attention carries the alignment, at most 32; no preset ships "
@@ -279,6 +285,32 @@ def _confidence_json(doc: dict, with_times: bool, segments, token_probs, word_pr
         s["avg_logprob"] = None if info["avg_logprob"] != info["avg_logprob"] else info["avg_logprob"]      # NaN: the window was not scored
         s["no_speech_prob"] = info["no_speech_prob"]
     doc["tokens_conf"] = token_probs
+
+
+def _stitch_ms(args, E):
+    """--stitch [--stitch-overlap S] -> the overlap in ms, 0 without --stitch, None after an error message"""
+    if not args.stitch:
+        if args.stitch_overlap is not None:
+            print("error: --stitch-overlap sets the overlap of --stitch; it needs --stitch", file=sys.stderr)
+            return None
+        return 0
+    s = 5.0 if args.stitch_overlap is None else args.stitch_overlap
+    ms = int(round(s * 1000.0)) if math.isfinite(s) else -1
+    try:
+        if ms == 0 or abs(ms - s * 1000.0) > 1e-6:
+            raise ValueError
+        E.stitch_plan_host(0, ms)
+    except (ValueError, E.WhisperError):
+        print(f"error: --stitch-overlap takes 1..15 seconds in steps of 0.02, not '{args.stitch_overlap}'", file=sys.stderr)
+        return None
+    return ms
+
+
+def _seams_json(seams, stitch_ms: int, duration: float):
+    """--stitch: per seam its left window, the seam time (the middle of the audio the two windows share) and the merge's words"""
+    hop = 30.0 - stitch_ms / 1000.0
+    return [{"window": s["left_window"], "time": ((s["left_window"] + 1) * hop + min(duration, s["left_window"] * hop + 30.0)) / 2.0,
+             "shift": s["shift"], "matches": s["matches"]} for s in seams]
 
 
 def _add_vad_options(t):
@@ -434,6 +466,9 @@ def _transcribe_many(args) -> int:
     if args.max_context != -1 and not args.carry_context:
         print("error: --max-context limits the carried context; it needs --carry-context", file=sys.stderr)
         return 1
+    if args.stitch or args.stitch_overlap is not None:
+        print("error: --stitch merges the fixed cuts of `transcribe`; transcribe-many runs the seek loop, which has no cuts", file=sys.stderr)
+        return 1
     from . import engine as E
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         print("error: transcribe-many is not supported under torch.distributed.run (one process per GPU)", file=sys.stderr)
@@ -547,6 +582,9 @@ def _transcribe_one(args) -> int:
     except ValueError:
         print(f"error: --audio-ctx takes 0, a positive number or 'auto', not '{args.audio_ctx}'", file=sys.stderr)
         return 1
+    stitch_ms = _stitch_ms(args, E)
+    if stitch_ms is None:
+        return 1
     hot = _read_hot_phrases(args)
     if hot is None:
         return 1
@@ -566,6 +604,9 @@ def _transcribe_one(args) -> int:
         return 1
     if vad and args.mel == "recording":
         print("error: --vad cuts chunks as fixed windows of their own; --mel recording does not apply", file=sys.stderr)
+        return 1
+    if stitch_ms and (vad or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        print("error: --stitch merges the fixed cuts of one engine; it does not apply to --vad or under torch.distributed.run", file=sys.stderr)
         return 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         if vad:
@@ -622,6 +663,8 @@ def _transcribe_one(args) -> int:
             return 1
     if args.confidence:
         eng.set_confidence(True)
+    if stitch_ms:
+        eng.set_stitch(stitch_ms / 1000.0)
     t1 = time.perf_counter()
     if vad:
         try:
@@ -646,6 +689,8 @@ def _transcribe_one(args) -> int:
         if align_heads:
             doc["segments"] = [{"text": s["text"], "t0": s["t0"], "t1": s["t1"]} for s in (res.segments if vad else eng.last_segments())]
             doc["words"] = [{"text": w["text"], "t0": w["t0"], "t1": w["t1"]} for w in (res.words if vad else eng.last_words())]
+        if stitch_ms:
+            doc["seams"] = _seams_json(eng.last_seams(), stitch_ms, audio.duration_secs())
         if args.confidence:
             if vad:
                 _confidence_json(doc, bool(align_heads), res.segments, res.token_probs, res.word_probs, res.segment_info)

@@ -987,6 +987,32 @@ int ohw_engine_set_carry_context(ohw_engine* e, int max_tokens) {
   });
 }
 
+int ohw_engine_set_stitch(ohw_engine* e, int overlap_ms) {
+  return guard([&] {
+    if (!e) throw Error(OHW_E_INVALID_ARG, "engine is null");
+    const int rc = ohw_stitch_plan_host(0, overlap_ms, nullptr, nullptr);      // the one place that judges an overlap
+    if (rc != OHW_OK) throw Error(rc, g_last_error);
+    e->stitch_ms = overlap_ms;
+  });
+}
+
+int ohw_engine_stitch(ohw_engine* e) { return e ? e->stitch_ms : OHW_E_INVALID_ARG; }
+
+int ohw_engine_last_seams(ohw_engine* e, const ohw_seam** seams, int* n) {
+  if (!e || !seams || !n) return OHW_E_INVALID_ARG;
+  *seams = e->last_seams.data();
+  *n = (int)e->last_seams.size();
+  return OHW_OK;
+}
+
+int ohw_engine_last_window_tokens(ohw_engine* e, const int32_t** tokens, const int32_t** offsets, int* n_windows) {
+  if (!e || !tokens || !offsets || !n_windows) return OHW_E_INVALID_ARG;
+  *tokens = e->last_win_tokens.data();
+  *offsets = e->last_win_offsets.data();
+  *n_windows = e->last_win_offsets.empty() ? 0 : (int)e->last_win_offsets.size() - 1;
+  return OHW_OK;
+}
+
 int ohw_engine_last_context(ohw_engine* e, int window, const int32_t** tokens, int* n) {
   return guard([&] {
     if (!e || !tokens || !n) throw Error(OHW_E_INVALID_ARG, "last_context: null argument");

@@ -60,7 +60,12 @@ struct ohw_engine {
   // ohw_engine_set_carry_context: 0 off, -1 the full cap, n > 0 at most n tokens of the recording's earlier windows as context in
   // the seek loops
   int carry_max = 0;
-  int prefill_chunk = 8;                 // ohw_engine_set_prefill_chunk: every state of the engine, those made later too
+  // ohw_engine_set_stitch: 0 off, else the overlap of neighbouring fixed cuts in ms; the seams and every window's kept tokens
+  // (offsets: n_windows + 1 entries) of the last stitched transcribe
+  int stitch_ms = 0;
+  std::vector<ohw_seam> last_seams;
+  std::vector<int32_t> last_win_tokens, last_win_offsets;
+  int prefill_chunk = 8;                // ohw_engine_set_prefill_chunk: every state of the engine, those made later too
   int beam_size = 0;                     // ohw_engine_set_beam_size: 0 = greedy at T = 0, 2..5 = beam search (a decode batch then holds
                                          //   max_batch / beam_size windows, on the engine's own state)
   int best_of = 1;                       // ohw_engine_set_best_of: candidates per pending window on every rung above T = 0 (1: today's ladder)

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <memory>
 
 #include "host_engine.hpp"
@@ -113,6 +114,9 @@ struct TranscribeCall {
     if (WB < 1) throw Error(OHW_E_INVALID_ARG, "transcribe: beam size or best_of exceeds max_batch");
     e->last_cands.clear();
     e->last_cand_lps.clear();
+    e->last_seams.clear();
+    e->last_win_tokens.clear();
+    e->last_win_offsets.clear();
     prompt[n_prompt++] = tk.sot;
     if (V >= 51865) { prompt[n_prompt++] = tk.sot + 1 + sp.lang_id; prompt[n_prompt++] = sp.translate ? tk.translate : tk.transcribe; }
     if (sp.no_timestamps) prompt[n_prompt++] = tk.no_timestamps;
@@ -390,16 +394,23 @@ struct TranscribeCall {
   }
   // one window's kept pass onto the end of a transcript.  t_off: the window's offset in the recording, t_end: the earlier of the
   // window's end and the recording's end (seconds); ctx: what the window's T = 0 pass was decoded behind
-  void emit(const WindowRun& r, double t_off, double t_end, Transcript& out, const std::vector<int32_t>& ctx) const {
+  // cut (stitched windows): the kept-token range [first, end) that reaches the transcript and the seam times of its two sides;
+  // null: the whole window
+  struct Cut { int first, end; float t_left, t_right; };
+  void emit(const WindowRun& r, double t_off, double t_end, Transcript& out, const std::vector<int32_t>& ctx, const Cut* cut = nullptr) const {
     std::string& text = out.text;
     const bool no_speech = is_no_speech(r, pol);
     const int keep = kept_tokens(r, pol);
+    const int first = cut ? std::min(std::max(cut->first, 0), keep) : 0, end = cut ? std::min(std::max(cut->end, first), keep) : keep;
+    size_t k0 = 0, nt_all = 0;                                         // text tokens in front of the range, and of the whole window
+    for (int i = 0; i < keep; ++i)
+      if (r.tok[(size_t)i] < tk.eot) { ++nt_all; if (i < first) ++k0; }
     const size_t win_text0 = text.size(), tt0 = out.token_times.size(), wd0 = out.words.size(), sg0 = out.segments.size();
     const size_t tp0 = out.token_probs.size(), wp0 = out.word_probs.size();
     std::vector<size_t> byte_off((size_t)keep + 1, text.size());       // text offset in front of every kept token
     std::vector<int32_t> tlen;                                         // byte length of every kept TEXT token
     std::vector<int> tpos;                                             //   and its position among the kept tokens
-    for (int i = 0; i < keep; ++i) {
+    for (int i = first; i < end; ++i) {
       byte_off[(size_t)i] = text.size();
       out.tokens.push_back(r.tok[(size_t)i]);
       if (r.tok[(size_t)i] < tk.eot) {                                    // segment text = text tokens only (:271-279)
@@ -409,23 +420,25 @@ struct TranscribeCall {
         tlen.push_back(len); tpos.push_back(i);
       }
     }
-    byte_off[(size_t)keep] = text.size();
+    for (int i = end; i <= keep; ++i) byte_off[(size_t)i] = text.size();
     if (keep > 0) {
       // segments (always): the text between consecutive timestamp tokens
       std::vector<ohw_token_span> spans((size_t)keep);
       const int ns_ = ohw_segments_host(r.tok.data(), keep, &tk, (float)t_off, (float)t_end, spans.data(), keep);
       for (int s = 0; s < ns_; ++s) {
-        const size_t o0 = byte_off[(size_t)spans[(size_t)s].first], o1 = byte_off[(size_t)spans[(size_t)s].end];
-        out.segments.push_back(ohw_span_time{o0, o1 - o0, spans[(size_t)s].t0, spans[(size_t)s].t1});
+        ohw_token_span sp_ = spans[(size_t)s];
+        if (cut && ohw_stitch_clip_segment_host(&spans[(size_t)s], first, end, cut->t_left, cut->t_right, &sp_) != 1) continue;
+        const size_t o0 = byte_off[(size_t)sp_.first], o1 = byte_off[(size_t)sp_.end];
+        out.segments.push_back(ohw_span_time{o0, o1 - o0, sp_.t0, sp_.t1});
       }
     }
-    if (!r.al_idx.empty() && r.al_idx.size() == tlen.size() + 1) {
+    if (!r.al_idx.empty() && r.al_idx.size() == nt_all + 1) {
       // token times, and words by the host rule (include/ohw.h)
       const int32_t window = (int32_t)out.quality.size();
       const size_t first_tt = out.token_times.size();
       for (size_t k = 0; k < tlen.size(); ++k)
-        out.token_times.push_back(ohw_token_time{r.tok[(size_t)tpos[k]], window, (float)t_off + (float)r.al_idx[k] * 0.02f,
-                                                 (float)t_off + (float)r.al_idx[k + 1] * 0.02f});
+        out.token_times.push_back(ohw_token_time{r.tok[(size_t)tpos[k]], window, (float)t_off + (float)r.al_idx[k0 + k] * 0.02f,
+                                                 (float)t_off + (float)r.al_idx[k0 + k + 1] * 0.02f});
       std::vector<int32_t> starts(tlen.size(), 0);
       (void)ohw_word_starts_host(text.data() + win_text0, tlen.data(), (int)tlen.size(), starts.data());
       for (size_t k = 0; k < tlen.size(); ++k) {
@@ -439,13 +452,13 @@ struct TranscribeCall {
     }
     if (e->confidence) {
       // token probabilities, word probabilities by the host rules (include/ohw.h), one info entry per segment of the window
-      const bool scored = !r.sc.empty() && r.sc.size() == tlen.size() + 1;
+      const bool scored = !r.sc.empty() && r.sc.size() == nt_all + 1;
       std::vector<float> lpt(scored ? tlen.size() : 0);
       if (scored) {
         const int32_t window = (int32_t)out.quality.size();
         for (size_t k = 0; k < tlen.size(); ++k) {
-          ohw_token_prob tp{r.tok[(size_t)tpos[k]], window, 0.f, 0.f, r.plog[(size_t)tpos[k]], r.sc[k].top_id, 0.f};
-          (void)ohw_token_prob_host(&r.sc[k], &tp.logprob_text, &tp.logprob_all, &tp.top_logprob_text);
+          ohw_token_prob tp{r.tok[(size_t)tpos[k]], window, 0.f, 0.f, r.plog[(size_t)tpos[k]], r.sc[k0 + k].top_id, 0.f};
+          (void)ohw_token_prob_host(&r.sc[k0 + k], &tp.logprob_text, &tp.logprob_all, &tp.top_logprob_text);
           lpt[k] = tp.logprob_text;
           out.token_probs.push_back(tp);
         }
@@ -570,22 +583,46 @@ struct FixedCuts {
   const TranscribeCall& tc;
   ohw_engine* const e;
   const float* const samples;
-  const int64_t n, win_first, win_step, n_win, n_batches;
+  const int64_t n, win_first, win_step;
+  // stitched windows (ohw_engine_set_stitch; an engine that takes the whole recording): neighbouring windows start `hop` samples
+  // apart and share the rest, every window's kept pass waits in `held` until finish() has cut them at the seams.  Off: the hop
+  // is the window, and nothing below differs from cuts every 30 s
+  const bool stitch;
+  const int64_t hop, n_win, n_batches;
   const int WB;
   const bool rec_mel;        // cut from the spectrogram of the whole recording, which e->state holds, instead of each cut on its own
+  mutable std::vector<WindowRun> held;
+  mutable std::map<ohw_state*, std::vector<float>> staged;      // front ends are enqueued by the calling thread only
   FixedCuts(const TranscribeCall& tc_, const float* samples_, int64_t n_, int64_t first, int64_t step)
-      : tc(tc_), e(tc_.e), samples(samples_), n(n_), win_first(first), win_step(step),
-        n_win(share_of(n_, first, step)), n_batches((n_win + tc_.WB - 1) / tc_.WB), WB(tc_.WB), rec_mel(tc_.e->window_mode == OHW_WINDOW_FIXED_RECORDING_MEL) {}
-  static int64_t share_of(int64_t n, int64_t first, int64_t step) { const int64_t all = (n + CHUNK_SAMPLES - 1) / CHUNK_SAMPLES; return all > first ? (all - first + step - 1) / step : 0; }
+      : tc(tc_), e(tc_.e), samples(samples_), n(n_), win_first(first), win_step(step), stitch(tc_.e->stitch_ms > 0 && step == 1),
+        hop(stitch ? CHUNK_SAMPLES - (int64_t)tc_.e->stitch_ms * 16 : CHUNK_SAMPLES),
+        n_win(share_of(n_, first, step, hop)), n_batches((n_win + tc_.WB - 1) / tc_.WB), WB(tc_.WB), rec_mel(tc_.e->window_mode == OHW_WINDOW_FIXED_RECORDING_MEL) {
+    if (stitch) held.resize((size_t)n_win);
+  }
+  // ohw_stitch_plan_host's count: with the hop at 480 000 it is ceil(n / 480 000)
+  static int64_t share_of(int64_t n, int64_t first, int64_t step, int64_t hop) {
+    const int64_t all = n <= 0 ? 0 : n <= CHUNK_SAMPLES ? 1 : (n - CHUNK_SAMPLES + hop - 1) / hop + 1;
+    return all > first ? (all - first + step - 1) / step : 0;
+  }
   int64_t rec_win(int64_t k) const { return win_first + k * win_step; }
-  int32_t win_samples(int64_t k) const { return (int32_t)std::min<int64_t>(CHUNK_SAMPLES, n - rec_win(k) * CHUNK_SAMPLES); }
+  int32_t win_samples(int64_t k) const { return (int32_t)std::min<int64_t>(CHUNK_SAMPLES, n - rec_win(k) * hop); }
+  double win_t_off(int64_t k) const { return (double)rec_win(k) * ((double)hop / 16000.0); }
   int batch_of(int64_t bi) const { return (int)std::min<int64_t>(WB, n_win - bi * WB); }
   void fill_ns(int64_t w0, int B, std::vector<int32_t>& nsv) const { for (int b = 0; b < B; ++b) nsv[(size_t)b] = win_samples(w0 + b); }
   // windows w0 .. w0 + B of the engine's share into st
   void mel_windows(ohw_state* st, int64_t w0, int B, const int32_t* nsv) const {
-    if (!rec_mel) { check(ohw_mel(st, samples + rec_win(w0) * CHUNK_SAMPLES, win_step * CHUNK_SAMPLES, nsv, B, 0, OHW_MEL_ZERO_TAIL, nullptr)); return; }
+    if (!rec_mel && hop < CHUNK_SAMPLES) {
+      // overlapped windows share samples and ohw_mel takes rows that do not: the batch's windows side by side in a staging
+      // buffer of the state's own, which stands until the state's next front end (its decode has been read back by then)
+      std::vector<float>& rows = staged[st];
+      rows.resize(std::max(rows.size(), (size_t)B * CHUNK_SAMPLES));
+      for (int b = 0; b < B; ++b) std::memcpy(&rows[(size_t)b * CHUNK_SAMPLES], samples + rec_win(w0 + b) * hop, (size_t)nsv[b] * 4);
+      check(ohw_mel(st, rows.data(), CHUNK_SAMPLES, nsv, B, 0, OHW_MEL_ZERO_TAIL, nullptr));
+      return;
+    }
+    if (!rec_mel) { check(ohw_mel(st, samples + rec_win(w0) * hop, win_step * hop, nsv, B, 0, OHW_MEL_ZERO_TAIL, nullptr)); return; }
     std::vector<int32_t> seeks((size_t)B);
-    for (int b = 0; b < B; ++b) seeks[(size_t)b] = (int32_t)(rec_win(w0 + b) * CHUNK_FRAMES);
+    for (int b = 0; b < B; ++b) seeks[(size_t)b] = (int32_t)(rec_win(w0 + b) * (hop / HOP));
     check(ohw_mel_seek(st, seeks.data(), B, nullptr));
   }
   void front(int64_t bi, ohw_state* st, void* stream, std::vector<int32_t>& nsv) const {
@@ -597,9 +634,45 @@ struct FixedCuts {
   void collect(Scratch& sc, int B, int64_t w0) const {
     tc.flush_trace(sc);
     for (int b = 0; b < B; ++b) {
-      const double t_off = (double)rec_win(w0 + b) * 30.0;
+      if (stitch) { held[(size_t)(w0 + b)] = std::move(sc.runs[(size_t)b]); continue; }
+      const double t_off = win_t_off(w0 + b);
       tc.emit(sc.runs[(size_t)b], t_off, std::min(t_off + 30.0, (double)n / 16000.0), e->last, e->prompt);
     }
+  }
+  // stitched windows, after the last batch: the windows' text tokens, the seams in one launch, the ranges, then every window's
+  // records in window order, cut to its range
+  void finish() const {
+    if (!stitch) return;
+    const int W = (int)n_win, stride = tc.max_tok;
+    std::vector<int32_t> text((size_t)std::max(W, 1) * stride, 0), nt((size_t)W, 0), t_first((size_t)W, 0), t_end((size_t)W, 0);
+    std::vector<std::vector<int>> tpos((size_t)W);         // kept-token position of every text token
+    e->last_win_offsets.assign(1, 0);
+    for (int w = 0; w < W; ++w) {
+      const WindowRun& r = held[(size_t)w];
+      const int keep = kept_tokens(r, tc.pol);
+      for (int i = 0; i < keep; ++i)
+        if (r.tok[(size_t)i] < tc.tk.eot && nt[(size_t)w] < stride) { text[(size_t)w * stride + nt[(size_t)w]++] = r.tok[(size_t)i]; tpos[(size_t)w].push_back(i); }
+      e->last_win_tokens.insert(e->last_win_tokens.end(), r.tok.begin(), r.tok.begin() + keep);
+      e->last_win_offsets.push_back((int32_t)e->last_win_tokens.size());
+    }
+    e->last_seams.assign((size_t)std::max(0, W - 1), ohw_seam{});
+    check(ohw_stitch_seams(e->device, text.data(), stride, nt.data(), W, e->last_seams.data()));
+    check(ohw_stitch_ranges_host(e->last_seams.data(), nt.data(), W, t_first.data(), t_end.data()));
+    const double rec_end = (double)n / 16000.0;
+    for (int w = 0; w < W; ++w) {
+      const WindowRun& r = held[(size_t)w];
+      const int keep = kept_tokens(r, tc.pol), rc = t_first[(size_t)w], lc = t_end[(size_t)w];
+      // text-token indices to kept-token positions: an uncut end keeps its timestamp tokens
+      auto pos = [&](int t, bool is_end) { return (t == 0 && !is_end) ? 0 : t >= nt[(size_t)w] ? keep : tpos[(size_t)w][(size_t)t]; };
+      const double t_off = win_t_off(w), t_end_w = std::min(t_off + 30.0, rec_end);
+      // the middle of the audio two neighbours share: (start of the right window + end of the left one) / 2
+      TranscribeCall::Cut cut{pos(rc, false), pos(lc, true), 0.f, 0.f};
+      cut.end = std::max(cut.end, cut.first);
+      if (w > 0) cut.t_left = (float)((t_off + std::min(win_t_off(w - 1) + 30.0, rec_end)) / 2.0);
+      if (w + 1 < W) cut.t_right = (float)((win_t_off(w + 1) + t_end_w) / 2.0);
+      tc.emit(r, t_off, t_end_w, e->last, e->prompt, &cut);
+    }
+    held.clear();
   }
   void restore_streams() const {
     for (ohw_state* st : e->states) (void)ohw_state_set_stream(st, nullptr);
@@ -829,13 +902,14 @@ void transcribe_fixed(const TranscribeCall& tc, const float* samples, int64_t n,
   // an engine of a pool that aligns: its share may be one batch while the recording is several, and the alignment's path is
   // sensitive to last bits, so the times must not depend on how the windows were dealt
   // (confidence alike: a score is a function of the last bits of a row)
-  Invariant invariant(e, cuts.n_batches > 1 || ((!e->wt_heads.empty() || e->confidence) && win_step > 1));
+  Invariant invariant(e, cuts.n_batches > 1 || (cuts.stitch && cuts.n_win > 1) || ((!e->wt_heads.empty() || e->confidence) && win_step > 1));
   SharedRecording shared_recording(e, cuts.rec_mel);
   sync_logit_rules(e);
   apply_ctx(e, call_ctx);
   if (schedule == OHW_SCHEDULE_SEQUENTIAL) cuts.sequential();
   else if (schedule == OHW_SCHEDULE_PIPELINE) cuts.pipeline();
   else cuts.lanes();
+  cuts.finish();
 }
 }  // namespace
 

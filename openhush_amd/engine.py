@@ -620,6 +620,8 @@ EXPORTS = [
     "ohw_engine_set_confidence", "ohw_engine_last_token_probs", "ohw_engine_last_word_probs", "ohw_engine_last_segment_info",
     "ohw_engine_batch_confidence", "ohw_pool_set_confidence", "ohw_pool_last_token_probs", "ohw_pool_last_word_probs",
     "ohw_pool_last_segment_info", "ohw_engine_score_batch",
+    "ohw_stitch_plan_host", "ohw_stitch_seams_host", "ohw_stitch_ranges_host", "ohw_stitch_clip_segment_host", "ohw_stitch_seams", "ohw_dbg_stitch",
+    "ohw_engine_set_stitch", "ohw_engine_stitch", "ohw_engine_last_seams", "ohw_engine_last_window_tokens",
 ]
 
 
@@ -877,6 +879,16 @@ def lib():
         L.ohw_engine_set_initial_prompt_tokens.argtypes = [vp, ip, C.c_int]
         L.ohw_pool_set_initial_prompt.argtypes = [vp, C.c_char_p]
         L.ohw_engine_set_carry_context.argtypes = [vp, C.c_int]
+        L.ohw_stitch_plan_host.argtypes = [C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.ohw_stitch_seams_host.argtypes = [ip, C.c_int, ip, C.c_int, ip]
+        L.ohw_stitch_ranges_host.argtypes = [ip, ip, C.c_int, ip, ip]
+        L.ohw_stitch_clip_segment_host.argtypes = [C.POINTER(TokenSpan), C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(TokenSpan)]
+        L.ohw_stitch_seams.argtypes = [C.c_int, ip, C.c_int, ip, C.c_int, ip]
+        L.ohw_dbg_stitch.argtypes = [C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, C.c_int32, ip]
+        L.ohw_engine_set_stitch.argtypes = [vp, C.c_int]
+        L.ohw_engine_stitch.argtypes = [vp]
+        L.ohw_engine_last_seams.argtypes = [vp, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int)]
+        L.ohw_engine_last_window_tokens.argtypes = [vp, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int)]
         L.ohw_state_set_prefill_chunk.argtypes = [vp, C.c_int]
         L.ohw_state_prefill_chunk.argtypes = [vp]
         L.ohw_engine_set_prefill_chunk.argtypes = [vp, C.c_int]
@@ -1090,6 +1102,74 @@ def dtw(m: np.ndarray, device: Optional[int] = None) -> np.ndarray:
     else:
         _check(lib().ohw_dbg_dtw(int(device), _fp(m), n, n_keys, _ip(idx)))
     return idx[:n]
+
+
+SEAM_WORDS = ("left_window", "shift", "matches", "left_cut", "right_cut", "n_left", "n_right", "reserved")
+
+
+def _stitch_table(windows):
+    """token-id lists -> (tokens [W][stride] int32, n_text [W] int32, stride); an int32 array [W][stride] with its counts passes through"""
+    if isinstance(windows, tuple):
+        tok, n_text = windows
+        tok = np.ascontiguousarray(tok, dtype=np.int32)
+        return tok, np.ascontiguousarray(n_text, dtype=np.int32), int(tok.shape[1])
+    stride = max([len(w) for w in windows] + [1])
+    tok = np.zeros((len(windows), stride), dtype=np.int32)
+    for i, w in enumerate(windows):
+        tok[i, :len(w)] = np.asarray(w, dtype=np.int32)
+    return tok, np.asarray([len(w) for w in windows], dtype=np.int32), stride
+
+
+def stitch_plan_host(n_samples: int, overlap_ms: int):
+    """ohw_stitch_plan_host -> (hop in samples, windows); window k covers samples [k * hop, min(n, k * hop + 480000))"""
+    hop, nw = C.c_int64(0), C.c_int64(0)
+    _check(lib().ohw_stitch_plan_host(int(n_samples), int(overlap_ms), C.byref(hop), C.byref(nw)))
+    return int(hop.value), int(nw.value)
+
+
+def stitch_seams_host(windows) -> np.ndarray:
+    """ohw_stitch_seams_host: the seam rule between neighbouring windows' TEXT tokens (lists of ids, or (tokens [W][stride],
+    n_text [W])) -> int32 [W - 1][8], the words of SEAM_WORDS.  No GPU needed"""
+    tok, n_text, stride = _stitch_table(windows)
+    out = np.zeros((max(len(n_text) - 1, 0), 8), dtype=np.int32)
+    _check(lib().ohw_stitch_seams_host(_ip(tok), stride, _ip(n_text), len(n_text), _ip(out)))
+    return out
+
+
+def stitch_seams(windows, device: int = 0) -> np.ndarray:
+    """ohw_stitch_seams: stitch_seams_host's device twin (stitch_kernel, one workgroup per seam) on host arrays"""
+    tok, n_text, stride = _stitch_table(windows)
+    out = np.zeros((max(len(n_text) - 1, 0), 8), dtype=np.int32)
+    _check(lib().ohw_stitch_seams(int(device), _ip(tok), stride, _ip(n_text), len(n_text), _ip(out)))
+    return out
+
+
+def dbg_stitch(windows, n_guard: int = 0, sentinel: int = -1, device: int = 0) -> np.ndarray:
+    """ohw_dbg_stitch: stitch_seams with n_guard sentinel-filled seams behind the output -> int32 [W - 1 + n_guard][8] (rows the
+    call never touched, all of them when W <= 1, hold the sentinel)"""
+    tok, n_text, stride = _stitch_table(windows)
+    out = np.full((max(len(n_text) - 1, 0) + int(n_guard), 8), int(sentinel), dtype=np.int32)
+    _check(lib().ohw_dbg_stitch(int(device), _ip(tok), stride, _ip(n_text), len(n_text), int(n_guard), int(sentinel), _ip(out)))
+    return out
+
+
+def stitch_ranges_host(seams, n_text):
+    """ohw_stitch_ranges_host: the text-token range [first, end) every window keeps -> list of (first, end)"""
+    seams = np.ascontiguousarray(seams, dtype=np.int32).reshape(-1, 8)
+    n_text = np.ascontiguousarray(n_text, dtype=np.int32)
+    first, end = np.zeros(max(len(n_text), 1), dtype=np.int32), np.zeros(max(len(n_text), 1), dtype=np.int32)
+    _check(lib().ohw_stitch_ranges_host(_ip(seams), _ip(n_text), len(n_text), _ip(first), _ip(end)))
+    return [(int(a), int(b)) for a, b in zip(first[:len(n_text)], end[:len(n_text)])]
+
+
+def stitch_clip_segment_host(seg, first: int, end: int, t_seam_left: float, t_seam_right: float):
+    """ohw_stitch_clip_segment_host: seg = (first, end, t0, t1) in a window's kept tokens against the range [first, end) ->
+    the retained (first, end, t0, t1), or None for a segment wholly outside"""
+    a, b = TokenSpan(int(seg[0]), int(seg[1]), float(seg[2]), float(seg[3])), TokenSpan()
+    rc = lib().ohw_stitch_clip_segment_host(C.byref(a), int(first), int(end), float(t_seam_left), float(t_seam_right), C.byref(b))
+    if rc < 0:
+        _check(rc)
+    return (b.first, b.end, b.t0, b.t1) if rc == 1 else None
 
 
 def dbg_align_probs(dtype: int, q_ptr: int, xk_ptr: int, rows: int, n_head: int, t_len: int, n_keys: int, heads: Sequence[int],
@@ -3064,6 +3144,31 @@ class WhisperEngine(_ConfidenceMirror):
         n_text_ctx / 2 - 1 tokens, n > 0 = at most n (--max-context), 0 = off (the default here).  The initial prompt then only seeds
         the history.  No effect on fixed cuts and transcribe_batch, where every cut or recording is a call of its own"""
         _check(lib().ohw_engine_set_carry_context(self.h, int(max_tokens)))
+
+    def set_stitch(self, overlap_s=5.0):
+        """ohw_engine_set_stitch: the fixed cuts of transcribe (OHW_WINDOW_FIXED, OHW_WINDOW_FIXED_RECORDING_MEL; every schedule)
+        overlap by overlap_s seconds (1 .. 15, a multiple of 20 ms) and neighbouring windows are merged where their text tokens
+        agree (stitch_seams); None or 0 switches it off (the default).  No effect on OHW_WINDOW_SEEK, transcribe_batch,
+        transcribe_long_batch, transcribe_speech or the pool"""
+        ms = 0 if not overlap_s else int(round(float(overlap_s) * 1000.0))
+        _check(lib().ohw_engine_set_stitch(self.h, ms))
+
+    def stitch(self) -> float:
+        """ohw_engine_stitch: the overlap in seconds, 0.0 = off"""
+        return lib().ohw_engine_stitch(self.h) / 1000.0
+
+    def last_seams(self) -> List[dict]:
+        """ohw_engine_last_seams: one dict of SEAM_WORDS per seam of the last stitched transcribe (shift = matches = 0: unmatched,
+        both windows kept whole)"""
+        p, n = C.POINTER(C.c_int32)(), C.c_int(0)
+        _check(lib().ohw_engine_last_seams(self.h, C.byref(p), C.byref(n)))
+        return [{k: int(p[8 * i + j]) for j, k in enumerate(SEAM_WORDS) if k != "reserved"} for i in range(n.value)]
+
+    def last_window_tokens(self) -> List[List[int]]:
+        """ohw_engine_last_window_tokens: every window's kept tokens before the cut ([] when the last transcribe was not stitched)"""
+        t, o, n = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_int(0)
+        _check(lib().ohw_engine_last_window_tokens(self.h, C.byref(t), C.byref(o), C.byref(n)))
+        return [[int(t[k]) for k in range(o[w], o[w + 1])] for w in range(n.value)]
 
     def _context(self, call) -> List[int]:
         p, n = C.POINTER(C.c_int32)(), C.c_int(0)
